@@ -19,6 +19,9 @@ the headline region; --preflight-ms 0 switches the pre-flight off.
 At N = 1 the line also carries `dropin`: the same workload as a caller written against cv::detail::RotationWarper /
 cv::detail::Blender gets it - every warp returns its corner to the host (W:160), feed() consumes its inputs (W:305-308) -
 with device mats and with host (cv::Mat-like, PCIe-inclusive) mats; timed after the headline region, never part of `value`.
+
+--dump-outputs DIR: after the timed steps, what the last timed step handed its caller is written as float32 .npy files under DIR (see
+dump_outputs); the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import contextlib
@@ -32,6 +35,40 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_BUDGET = 60 << 20  # --dump-outputs: bytes of .npy payload at most (64 MB in all with the headers)
+DUMP_SEED = 20251015
+
+
+def dump_outputs(path, groups, budget=DUMP_BUDGET):
+    """--dump-outputs: writes every array of `groups` ([(prefix, [(name, tensor or ndarray), ...]), ...]) as float32 (float64 stays float64)
+    <prefix>_<name>.npy under `path`.  The arrays of one group share their first dimension (a mosaic and its mask: rows).  A group that does not
+    fit its even share of `budget` is written as a fixed, seeded sample of those rows - the same rows for every array of the group - and the row
+    numbers go to <prefix>_rows.npy (float64).  Call it after the device work is done.  Returns {"dir", "files", "bytes"}."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    share = budget // max(len(groups), 1)
+    files, nbytes = 0, 0
+    for gi, (prefix, arrays) in enumerate(groups):
+        arrays = [(n, torch.as_tensor(a)) for n, a in arrays]
+        rows = arrays[0][1].shape[0]
+        assert all(a.shape[0] == rows for _, a in arrays), prefix
+        row_bytes = sum(a[:1].numel() * (8 if a.dtype == torch.float64 else 4) for _, a in arrays)
+        pick = None
+        if rows * row_bytes > share:
+            k = max(1, share // (row_bytes + 8))
+            pick = np.sort(np.random.default_rng([DUMP_SEED, gi]).choice(rows, size=k, replace=False))
+            np.save(os.path.join(path, prefix + "_rows.npy"), pick.astype(np.float64))
+            files += 1
+            nbytes += pick.size * 8
+        for name, a in arrays:
+            if pick is not None:
+                a = a[torch.from_numpy(pick).to(a.device)]
+            a = a.to(torch.float64 if a.dtype == torch.float64 else torch.float32).cpu().numpy()
+            np.save(os.path.join(path, "%s_%s.npy" % (prefix, name)), a)
+            files += 1
+            nbytes += a.nbytes
+    return {"dir": os.path.abspath(path), "files": files, "bytes": nbytes}
 
 
 def measured_traffic(kernel, args, live=True):
@@ -356,6 +393,7 @@ def a13_line(args):
         call()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
+    dumped = dump_outputs(args.dump_outputs, [("a13", [("pano", pano), ("seam", seam)])]) if args.dump_outputs else None
     # ... and the same K calls again with every launch bracketed by HIP events (outside the timed region: bracketing serialises the launches)
     lib.isx_profile_enable(1); lib.isx_profile_filter(None); lib.isx_profile_sample(1); lib.isx_profile_reset()
     for _ in range(args.steps):
@@ -377,13 +415,15 @@ def a13_line(args):
                         "avg_launch_ms": round(e["ms"] / e["launches"], 5), "alg_bytes_per_launch": int(e["alg_bytes"] / e["launches"]), "launches": e["launches"]},
            "kernels_ms_one_step": per, "kernel_sum_ms": round(sum(v["ms"] for v in per.values()), 4),
            "seam_walk_ms": round(sum(v["ms"] for k, v in per.items() if k.startswith("lin_seam")), 4)}
+    if dumped:
+        out["dump_outputs"] = dumped
     print(json.dumps(out), flush=True)
 
 
 def self_launch(n):
-    """`python bench.py --gpus N` with no launcher around it: check that the node has N GPUs, then become
+    """`python bench.py --gpus N` with no launcher around it: check that the node has N GPUs, then run
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py <same args>`
-    (one process per GPU over RCCL, the same command the driver issues)."""
+    (one process per GPU over RCCL, the same command the driver issues) as a child process, and exit with its status."""
     import socket
     import torch
     have = torch.cuda.device_count()            # hipGetDeviceCount
@@ -397,7 +437,9 @@ def self_launch(n):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush(); sys.stderr.flush()
-    os.execv(sys.executable, cmd)
+    import subprocess
+    # a child process, not exec: this process has already opened the GPU (hipGetDeviceCount above)
+    sys.exit(subprocess.call(cmd))
 
 
 def main():
@@ -468,6 +510,9 @@ def main():
                          "writes them so; feed() receives what the reference's feed() receives, W:302)")
     ap.add_argument("--roi-cache", action="store_true", help="with --sync-roi: isx_warper_set_roi_cache (the ROI of a fixed rig is computed once)")
     ap.add_argument("--sync-roi", action="store_true", help="return every warp's corner to the host (one stream sync per tile) instead of the planned, device-checked ROI")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (every pair's mosaic and mask; with N > 1 also the "
+                         "gathered block rank 0 received) to DIR/<name>.npy as float32, at most 64 MB (a seeded sample of rows past that)")
     args = ap.parse_args()
     if args.cpu_worker:   # one worker of the cpu_baseline leg: no torch, no GPU
         prec_w = {"i16": 0, "f32": 1, "f16acc32": 2}[args.precision]
@@ -489,7 +534,7 @@ def main():
             raise SystemExit("bench.py needs a GPU (torch.cuda.is_available() is False)")
         return a13_line(args)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-        self_launch(args.gpus)      # does not return: this process becomes torch.distributed.run with --gpus ranks
+        self_launch(args.gpus)      # does not return: torch.distributed.run with --gpus ranks runs as a child, its status is this process's
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.pairs is None:
         args.pairs = 1 if world == 1 else 4
@@ -798,6 +843,13 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     gc.enable()
+    # the outputs of the last timed step, before anything below runs the step again
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        groups = [("pair%d" % i, [("mosaic", p.out), ("mask", p.out_mask)]) for i, p in enumerate(pairs)]
+        if use_dist:
+            groups.append(("gathered", [("block", gather_buf)]))
+        dumped = dump_outputs(args.dump_outputs, groups)
     ent = ent_graph if args.graph else _lib.profile_entries()
     lib.isx_profile_enable(0)
     lib.isx_profile_sample(1)
@@ -1084,6 +1136,8 @@ def main():
             ctypes.CDLL(None).fflush(None)
         except Exception:
             pass
+        if dumped:
+            out["dump_outputs"] = dumped
         print(json.dumps(out), flush=True)
     if use_dist:
         dist.barrier()

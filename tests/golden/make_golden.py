@@ -21,6 +21,7 @@
                      the warp of an all-255 mask; tile 1: reconstructed — its part outside the overlap is untouched in
                      mask_seam[1].bmp, inside the overlap every pixel ended up in one of the two seam masks) and the
                      committed mask_seam[0,1].bmp that came out.
+  ref_dense_maps.npz the reference's own mapForward / mapBackward (oracle/_ref/libref_warp.so) on 5000 + 5000 seeded points.
   oracle_regress.npz seeded inputs -> outputs of oracle/liboracle.so for remap / pyramids /
                      MultiBandBlender / linear blend.  NOT reference-derived (OpenCV 3.4.2 is absent:
                      "parity unpinned"); it freezes the restatement so that drift is caught.
@@ -219,8 +220,26 @@ def oracle_regress():
     print("oracle_regress.npz written")
 
 
+def dense_maps():
+    """ref_dense_maps.npz: the 5000 + 5000 points of test_projector_matches_live_reference_build through oracle/_ref/libref_warp.so."""
+    assert O.ref() is not None, "oracle/_ref/libref_warp.so missing: run oracle/build.sh in the build container"
+    rng = np.random.default_rng(1)
+    K, Rs = synth.camera_pair(1101, 1101, 2707.47, yaw=0.5)
+    k, rinv, rk, kr = O.camera(K, Rs[0])
+    O.ref_set(2707.47, rk, kr)
+    x = rng.integers(0, 1101, 5000).astype(np.float32)
+    y = rng.integers(0, 1101, 5000).astype(np.float32)
+    u, v = O.ref_map_forward_n(x, y)
+    uu = rng.integers(-3000, 3000, 5000).astype(np.float32)
+    vv = rng.integers(-1500, 1500, 5000).astype(np.float32)
+    bx, by = O.ref_map_backward_n(uu, vv)
+    np.savez_compressed(os.path.join(HERE, "ref_dense_maps.npz"), x=x, y=y, u=u, v=v, uu=uu, vv=vv, bx=bx, by=by)
+    print("ref_dense_maps.npz written")
+
+
 if __name__ == "__main__":
     cyl_maps()
+    dense_maps()
     if os.path.isdir(REF):
         ref_inputs()
         ref_warp_artifact()

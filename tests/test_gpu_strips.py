@@ -318,8 +318,8 @@ def test_example_stitch_strips_three_ranks(gpu, tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = str(tmp_path / "pano.bmp")
-    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3", "--master-addr", "127.0.0.1",
-                        "--master-port", str(_free_port()), os.path.join(root, "examples", "stitch_strips.py"), "--backend", "gloo", "--check",
+    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3", "--standalone",
+                        os.path.join(root, "examples", "stitch_strips.py"), "--backend", "gloo", "--check",
                         "--tiles", "6", "--width", "960", "--height", "540", "--focal", "750", "--out", out],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]

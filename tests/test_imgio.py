@@ -58,13 +58,23 @@ def test_bmp_top_down_and_errors(isx, tmp_path):
         isx.imwrite(str(tmp_path / "f.bmp"), np.zeros((4, 4, 3), np.float32))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="the reference tree only exists in the build container")
-def test_reads_the_references_committed_bitmaps(isx):
+def _reference_files(kind, tmp_path):
+    """tests/golden/ref_imgio_files.npz: the reference's committed files of `kind` ("bmp" / "jpg"), cut to a band of rows without
+    re-encoding (tests/golden/make_golden_imgio.py), written out as files."""
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_imgio_files.npz"))
+    files = []
+    for i, k in enumerate(sorted(n for n in z.files if n.startswith(kind + "/"))):
+        f = str(tmp_path / ("%d_%s" % (i, os.path.basename(k))))
+        open(f, "wb").write(z[k].tobytes())
+        files.append(f)
+    return files
+
+
+def test_reads_the_references_committed_bitmaps(isx, tmp_path):
     """The artefacts the reference's imwrite produced (S:1195-1198) decode to what Pillow decodes."""
-    import glob
-    files = sorted(glob.glob("/root/reference/**/*.bmp", recursive=True))
-    assert files
-    for f in files[:6]:
+    files = _reference_files("bmp", tmp_path)
+    assert len(files) == 6
+    for f in files:
         ref = np.asarray(PIL.open(f).convert("RGB"))[:, :, ::-1]
         assert np.array_equal(isx.imread(f), ref), f
 
@@ -292,13 +302,12 @@ def test_jpeg_write_then_read_and_unsupported_files(isx, tmp_path):
         isx.imread(str(tmp_path / "junk.jpg"))
 
 
-def test_jpeg_read_of_the_references_own_panorama(isx):
-    """pano.jpg (S:1282) as the reference committed it, decoded as cv::imread would: equal to libjpeg's decode.  Build container only."""
-    import glob
-    files = sorted(glob.glob("/root/reference/*/*/pano.jpg"))
-    if not files:
-        pytest.skip("reference tree not present")
-    for f in files[:2]:
+def test_jpeg_read_of_the_references_own_panorama(isx, tmp_path):
+    """pano.jpg (S:1282) as the reference committed it (its first 128 rows, the coded blocks untouched), decoded as cv::imread would:
+    equal to libjpeg's decode."""
+    files = _reference_files("jpg", tmp_path)
+    assert len(files) == 2
+    for f in files:
         ref = np.asarray(PIL.open(f).convert("RGB"))[:, :, ::-1]
         assert np.array_equal(isx.imread(f), ref), f
 
