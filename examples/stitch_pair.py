@@ -7,7 +7,8 @@
 Registration (features, matching, bundle adjustment — out of scope of this library) is replaced by a known rig: two cameras
 with focal length F rotated by -/+ yaw about the vertical axis.  Without input files a synthetic pair is generated.
 
-Steps = the reference's main(): warp image + mask (W:223-233), gain apply with given gains (W:241-244), convertTo(CV_32F) +
+Steps = the reference's main(): warp image + mask (W:223-233), gain apply with given gains (W:241-244) - or, with
+--estimate-gains, the GainCompensator's feed on the warped tiles (W:238-240) and its apply (W:241-244) -, convertTo(CV_32F) +
 DP seam finder (W:253-262 / S:87-1093), dilate 20x20 & warped mask (W:286-301), FeatherBlender 0.1 (W:278-313) or the
 multi-band blender (W:271-273), imwrite (W:315)."""
 import argparse
@@ -28,6 +29,9 @@ def main():
     ap.add_argument("--yaw", type=float, default=0.18)
     ap.add_argument("--blend", default="feather", choices=["feather", "multiband"])
     ap.add_argument("--gains", type=float, nargs=2, default=[1.0, 1.0])
+    ap.add_argument("--estimate-gains", action="store_true",
+                    help="estimate the gains from the warped tiles as the reference does (GainCompensator feed, then apply; W:238-244) "
+                         "instead of taking --gains")
     ap.add_argument("--out", default="pano.bmp")
     ap.add_argument("--separate", action="store_true",
                     help="gain apply and mask preparation as passes of their own (isx_gain_apply, isx_mask_dilate_and) instead of folded into the warp's "
@@ -43,13 +47,21 @@ def main():
     warper = isx.CylindricalWarper().create(F)                              # W:217-222
     corners, warped, wmasks = [], [], []
     for i in range(2):
-        if a.separate:
+        if a.estimate_gains:                                                # the gains are not known before the warp: apply comes after feed
+            c, wi, wm = warper.warp_with_mask(imgs[i], K, Rs[i])           # W:229, W:232
+        elif a.separate:
             c, wi, wm = warper.warp_with_mask(imgs[i], K, Rs[i])           # W:229, W:232
             isx.gain_apply(wi, a.gains[i])                                  # W:241-244
         else:                                                               # W:241-244 folded into the warp's store (gains known: a fixed rig)
             warper.set_gain(a.gains[i])
             c, wi, wm = warper.warp_with_mask(imgs[i], K, Rs[i])           # W:229, W:232
         corners.append(tuple(c)); warped.append(wi); wmasks.append(wm)
+    if a.estimate_gains:
+        compensator = isx.GainCompensator()                                 # W:238
+        compensator.feed(corners, warped, wmasks)                           # W:240
+        for i in range(2):
+            compensator.apply(i, corners[i], warped[i], wmasks[i])          # W:241-244
+        print("estimated gains", " ".join("%.9f" % g for g in compensator.gains()))
     seam = [m.copy() for m in wmasks]                                       # W:247-249
     isx.DpSeamFinder().find([w.astype(np.float32) for w in warped], corners, seam)   # W:259-262
     sizes = [(w.shape[1], w.shape[0]) for w in warped]

@@ -84,6 +84,8 @@ _SIGS = {
     "isx_blender_set_sharpness": [C.c_void_p, C.c_float],
     "isx_mask_dilate_and": [_MP, _MP, C.c_int, C.c_int, _MP, C.c_int, C.c_void_p],
     "isx_gain_apply": [_MP, C.c_double, C.c_int, C.c_void_p],
+    "isx_gain_compensator_feed": [C.c_int, C.POINTER(C.c_int), _MP, _MP, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_double),
+                                  C.c_int, C.c_void_p],
     "isx_convert_to": [_MP, _MP, C.c_int, C.c_void_p],
     "isx_seam_estimate": [_MP, _MP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _MP, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int,
                           C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_void_p],

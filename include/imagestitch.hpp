@@ -287,4 +287,31 @@ inline void imwrite(const char* path, const Mat& img, int jpeg_quality = 95) {
 // GainCompensator::apply: multiply(image, gain, image)  (W:241-244)
 inline void gainApply(Mat& image, double gain, int device = 0) { check(isx_gain_apply(image.c(), gain, device, nullptr)); }
 
+// cv::detail::GainCompensator, what ExposureCompensator::createDefault(ExposureCompensator::GAIN) returns (W:238-244):
+// feed(corners, images_warped, masks_warped) estimates one gain per tile on the GPU (isx_gain_compensator_feed), apply(i, ...)
+// multiplies tile i by its gain (isx_gain_apply).  Images CV_8UC3, masks CV_8U of the images' sizes (255 = in), host or device.
+class GainCompensator {
+public:
+    explicit GainCompensator(int device = 0) : device_(device) {}
+    void feed(const std::vector<Point>& corners, const std::vector<Mat>& images, const std::vector<Mat>& masks) {
+        if (images.size() != corners.size() || images.size() != masks.size())
+            throw Exception(ISX_ERR_INVALID, "feed: corners, images and masks differ in length");
+        std::vector<isx_mat> im(images.size()), mk(images.size());
+        std::vector<int> c;
+        for (size_t i = 0; i < images.size(); ++i) { im[i] = *images[i].c(); mk[i] = *masks[i].c(); c.push_back(corners[i].x); c.push_back(corners[i].y); }
+        std::vector<double> g(images.size());
+        check(isx_gain_compensator_feed((int)images.size(), c.data(), im.data(), mk.data(), g.data(), nullptr, nullptr, device_, nullptr));
+        gains_ = g;
+    }
+    // gains(): one per tile fed (GainCompensator::gains)
+    std::vector<double> gains() const { return gains_; }
+    void apply(int index, Point /*corner*/, Mat& image, const Mat& /*mask*/) {
+        if (index < 0 || (size_t)index >= gains_.size()) throw Exception(ISX_ERR_STATE, "apply: no gain for this index (feed first)");
+        check(isx_gain_apply(image.c(), gains_[(size_t)index], device_, nullptr));
+    }
+private:
+    int device_;
+    std::vector<double> gains_;
+};
+
 }  // namespace isx

@@ -343,11 +343,22 @@ int isx_blender_debug_level(isx_blender* b, int level, void* lap, float* weight,
 int isx_mask_dilate_and(const isx_mat* mask, const isx_mat* other, int kw, int kh, isx_mat* out,
                         int device, void* hip_stream);
 
-/* ---- exposure compensation, the per-pixel part (W:241-244) ------------------------------------ */
+/* ---- exposure compensation (W:238-244) ---------------------------------------------------------- */
 /* compensator->apply(i, corners[i], images_warped[i], masks_warped[i]) of the GainCompensator every demo creates
  * (W:238-239): multiply(image, gain, image) in place on a CV_8UC3 (or CV_8UC1) image, gain = gains_(i, 0) as
- * computed by compensator->feed (a small linear solve on the host, not part of this library).              */
+ * computed by compensator->feed (isx_gain_compensator_feed below).                                        */
 int isx_gain_apply(isx_mat* image, double gain, int device, void* hip_stream);
+/* compensator->feed(corners, images_warped, masks_warped) of GainCompensator (W:238-240, S:1165-1167, B:117-119; OpenCV 3.4.2
+ * GainCompensator::feed): the overlap statistics of every pair of tiles in one GPU pass - N(i,j) = max(1, count of pixels where both
+ * masks are 255) where the tiles' rectangles overlap and 0 where they do not, I(i,j) = mean of sqrt(r^2 + g^2 + b^2) of image i over
+ * those pixels (0 without any; exact sums: the mean is math.fsum of the terms / N) - then
+ * OpenCV's linear system (alpha = 0.01, beta = 100) solved on the host by LU with partial pivoting.  corners_xy: n (x, y) pairs;
+ * images: n CV_8UC3 mats; masks: n CV_8U mats of the images' sizes; either host or device.  gains: n doubles.  n_out / i_out (may be
+ * NULL): the n x n matrices N and I, row-major, I's diagonal 0.  Synchronises hip_stream (it returns host values); keeps its work table
+ * (about 120 B per band of rows, on the device and pinned on the host) per calling thread between calls.
+ * ISX_ERR_INVALID for num_images < 1, ISX_ERR_TYPE for other mat types, ISX_ERR_SIZE for a mask that is not its image's size. */
+int isx_gain_compensator_feed(int num_images, const int* corners_xy, const isx_mat* images, const isx_mat* masks,
+                              double* gains, long long* n_out, double* i_out, int device, void* hip_stream);
 
 /* ---- the glue conversions of the reference's main() ---------------------------------- */
 /* src.convertTo(dst, dst.type()) with alpha = 1, beta = 0 between the CV_8U, CV_16S and CV_32F depths, same channel count:
