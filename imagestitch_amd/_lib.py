@@ -64,6 +64,7 @@ _SIGS = {
     "isx_warper_set_deferred_verify": [C.c_void_p, C.c_int],
     "isx_remap": [_MP, _MP, _MP, C.c_int, C.c_int, _MP, C.c_int, C.c_void_p],
     "isx_warper_set_roi_cache": [C.c_void_p, C.c_int],
+    "isx_warper_table_resets": [C.c_void_p, C.POINTER(C.c_longlong)],
     "isx_warper_set_gain": [C.c_void_p, C.c_double],
     "isx_blender_feed_dilated": [C.c_void_p, _MP, _MP, _MP, C.c_int, C.c_int, C.c_int, C.c_int],
     "isx_warper_verify": [C.c_void_p],
@@ -106,6 +107,7 @@ _SIGS = {
     "isx_blender_last_path": [C.c_void_p, _IP, _IP],
     "isx_blender_level1_format": [C.c_void_p, _IP],
     "isx_blender_table_uploads": [C.c_void_p, C.POINTER(C.c_longlong)],
+    "isx_blender_retained_bytes": [C.c_void_p, C.POINTER(C.c_longlong)],
     "isx_blender_feed_path": [C.c_void_p, _IP, _IP],
     "isx_blender_set_narrow_copies": [C.c_void_p, C.c_int],
     "isx_blender_blend": [C.c_void_p, _MP, _MP],

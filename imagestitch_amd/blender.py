@@ -136,6 +136,12 @@ class MultiBandBlender:
         check(self._lib.isx_blender_table_uploads(self._h, C.byref(n)))
         return n.value
 
+    def retained_bytes(self):
+        """isx_blender_retained_bytes: device bytes this blender keeps alive for a captured graph after outgrowing them."""
+        n = C.c_longlong()
+        check(self._lib.isx_blender_retained_bytes(self._h, C.byref(n)))
+        return n.value
+
     def set_narrow_copies(self, on=True):
         """isx_blender_set_narrow_copies: False = private copies of CV_16SC3 tiles stay CV_16SC3 and blend() never waits for the GPU
         (with narrowed copies - the default - it polls one pinned word the first launch of its chain publishes)."""

@@ -1505,11 +1505,15 @@ struct DevTable {
     long long uploads = 0;                  // chunks uploaded so far (introspection: the steady state adds none)
     // room for a whole chain's slots before its first put(): growing in the middle of a chain would work (hipFree waits for the kernels that read
     // the old table) but stall the chain once per growth
+    // Another stream: the mirror vouches for nothing (known), but a chunk a graph writes stays baked - the buffer is the same one, and a replay
+    // still rewrites it (capture A, set_stream, eager B, replay A, eager B: the second B must upload again).  A new buffer: nothing written yet,
+    // no graph writes it (the one it replaces is retained for a captured handle, RetainScope).
     int ensure(hipStream_t s, size_t total) {
-        if (total > buf.cap || s != st) {
-            if (total > buf.cap) ISX_TRY(buf.reserve(std::max(total + total / 2, (size_t)64 * TAB_CH)));
-            mirror.assign(buf.cap, 0); known.assign(buf.cap / TAB_CH + 1, 0u); baked.assign(buf.cap / TAB_CH + 1, 0); st = s;
-        }
+        if (total > buf.cap) {
+            ISX_TRY(buf.reserve(std::max(total + total / 2, (size_t)64 * TAB_CH)));
+            mirror.assign(buf.cap, 0); known.assign(buf.cap / TAB_CH + 1, 0u); baked.assign(buf.cap / TAB_CH + 1, 0);
+        } else if (s != st) std::fill(known.begin(), known.end(), 0u);
+        st = s;
         return ISX_OK;
     }
     // `bytes` (a multiple of 16) at offset `off` (a multiple of TAB_CH); *dev = where they lie
@@ -1986,9 +1990,25 @@ struct isx_blender {
     std::vector<hipStream_t> side;
     std::vector<hipEvent_t> ev_ready, ev_done;
     std::vector<char> chain_on_side;   // per recorded tile: its chain was launched by feed()
+    // a graph was captured from this handle's stream: from then on the device buffers it outgrows are kept until destroy (retain_of)
+    bool captured = false;
+    Retained retained;
 };
 
 namespace {
+
+// Every device buffer of a blender can be read or written by a captured step (the level pyramids, the tile arenas and private copies, the tile
+// table, the feather weights, the narrowed copies' state words): once the handle's stream has been seen capturing, every entry point that may grow
+// them (prepare, feed, blend, blend_batch, debug_level) runs under a RetainScope, and a growth keeps the old allocation (isx_blender_retained_bytes) instead of freeing what a replay still uses.
+Retained* retain_of(isx_blender* b) {
+    if (b == nullptr) return nullptr;
+    if (!b->captured) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(b->stream, &cs) != hipSuccess) (void)hipGetLastError();
+        else b->captured = cs != hipStreamCaptureStatusNone;
+    }
+    return b->captured ? &b->retained : nullptr;
+}
 
 int layout_levels(LevelBuf* lv, int L, int rows, int cols, int prec, bool is_dst, char* base, size_t* total) {
     size_t off = 0;
@@ -3631,6 +3651,7 @@ int isx_blender_num_bands(isx_blender* b, int* num_bands) ISX_ENTRY {
 
 int isx_blender_prepare(isx_blender* b, int n, const int* c, const int* s) ISX_ENTRY {
     clear_error();
+    RetainScope rs(retain_of(b));
     ISX_CHECK_ARG(b != nullptr && c != nullptr && s != nullptr, ISX_ERR_INVALID, "prepare: null argument");
     ISX_CHECK_ARG(n > 0, ISX_ERR_INVALID, "prepare: no tiles");
     // resultRoi(corners, sizes)
@@ -3645,22 +3666,26 @@ int isx_blender_prepare(isx_blender* b, int n, const int* c, const int* s) ISX_E
 
 int isx_blender_prepare_roi(isx_blender* b, int x, int y, int width, int height) ISX_ENTRY {
     clear_error();
+    RetainScope rs(retain_of(b));
     ISX_CHECK_ARG(b != nullptr, ISX_ERR_INVALID, "prepare: null blender");
     return do_prepare(b, x, y, width, height);
 } ISX_EXIT("isx_blender_prepare_roi")
 
 int isx_blender_feed(isx_blender* b, const isx_mat* img, const isx_mat* mask, int tl_x, int tl_y) ISX_ENTRY {
     clear_error();
+    RetainScope rs(retain_of(b));
     return do_feed(b, img, mask, tl_x, tl_y, false);
 } ISX_EXIT("isx_blender_feed")
 
 int isx_blender_feed_u8(isx_blender* b, const isx_mat* img, const isx_mat* mask, int tl_x, int tl_y) ISX_ENTRY {
     clear_error();
+    RetainScope rs(retain_of(b));
     return do_feed(b, img, mask, tl_x, tl_y, true);
 } ISX_EXIT("isx_blender_feed_u8")
 
 int isx_blender_feed_dilated(isx_blender* b, const isx_mat* img, const isx_mat* seam_mask, const isx_mat* warped_mask, int kw, int kh, int tl_x, int tl_y) ISX_ENTRY {
     clear_error();
+    RetainScope rs(retain_of(b));
     ISX_CHECK_ARG(b != nullptr && img != nullptr && seam_mask != nullptr && warped_mask != nullptr, ISX_ERR_INVALID, "feed_dilated: null argument");
     ISX_TRY(check_mat(seam_mask, "feed_dilated: seam mask"));
     ISX_CHECK_ARG(seam_mask->type == ISX_8UC1, ISX_ERR_TYPE, "feed_dilated: seam mask must be CV_8U, got %s", type_name(seam_mask->type));
@@ -3688,6 +3713,12 @@ int isx_blender_table_uploads(isx_blender* b, long long* pieces) ISX_ENTRY {
     return ISX_OK;
 } ISX_EXIT("isx_blender_table_uploads")
 
+int isx_blender_retained_bytes(isx_blender* b, long long* bytes) ISX_ENTRY {
+    ISX_CHECK_ARG(b != nullptr && bytes != nullptr, ISX_ERR_INVALID, "isx_blender_retained_bytes: null argument");
+    *bytes = b->retained.bytes;
+    return ISX_OK;
+} ISX_EXIT("isx_blender_retained_bytes")
+
 int isx_blender_set_narrow_copies(isx_blender* b, int on) ISX_ENTRY {
     ISX_CHECK_ARG(b != nullptr, ISX_ERR_INVALID, "isx_blender_set_narrow_copies: null blender");
     ISX_CHECK_ARG(b->tiles.empty() || b->tiles[0].narrow == 0 || on != 0, ISX_ERR_STATE, "isx_blender_set_narrow_copies: a cycle with narrowed tiles is open (call it before the first feed)");
@@ -3712,6 +3743,7 @@ int isx_blender_result_size(isx_blender* b, int* width, int* height) ISX_ENTRY {
 int isx_blender_debug_level(isx_blender* b, int level, void* lap, float* weight, int* rows, int* cols) ISX_ENTRY {
     clear_error();
     ISX_CHECK_ARG(b != nullptr && rows != nullptr && cols != nullptr, ISX_ERR_INVALID, "debug_level: null argument");
+    RetainScope rs(retain_of(b));        // (it may run the recorded tiles through the eager feed first: flush_deferred)
     ISX_CHECK_ARG(b->prepared, ISX_ERR_STATE, "debug_level: prepare() has not been called");
     ISX_CHECK_ARG(level >= 0 && level <= b->num_bands, ISX_ERR_INVALID, "debug_level: level %d of %d", level, b->num_bands);
     ISX_CHECK_ARG(b->type != ISX_BLEND_NO, ISX_ERR_UNSUPPORTED, "debug_level: Blender::NO keeps no pyramid");
@@ -3818,6 +3850,7 @@ static int blend_end(isx_blender* b, isx_mat* dst_mask) {
 
 int isx_blender_blend(isx_blender* b, isx_mat* dst, isx_mat* dst_mask) ISX_ENTRY {
     clear_error();
+    RetainScope rs(retain_of(b));
     OutMat o;
     ISX_TRY(blend_begin(b, dst, dst_mask, &o));
     const bool windowed = b->win_x1 > b->win_x0;
@@ -3862,6 +3895,11 @@ int isx_blender_blend_batch(isx_blender** bs, int n, isx_mat* dsts, isx_mat* dst
     clear_error();
     ISX_CHECK_ARG(bs != nullptr && dsts != nullptr && n >= 1, ISX_ERR_INVALID, "blend_batch: bad argument");
     for (int i = 0; i < n; ++i) ISX_CHECK_ARG(bs[i] != nullptr, ISX_ERR_INVALID, "blend_batch: null blender %d", i);
+    // one chain grows the buffers of several blenders: what they outgrow is kept by the first captured one (a graph of the batch needs every one
+    // of its blenders alive anyway)
+    Retained* keep = nullptr;
+    for (int i = 0; i < n; ++i) if (Retained* r = retain_of(bs[i])) keep = keep ? keep : r;
+    RetainScope rs(keep);
     // Groups of blenders that can share a chain of launches: the deferred multi-band cycle with every tile still recorded, no window, the
     // same precision / bands / tile type / device / stream, at most BATCH_MAX mosaics and DEF_MAX tiles.  Anything else is blended alone.
     int i = 0;

@@ -48,8 +48,16 @@ const char* type_name(int type) {
     }
 }
 
+static thread_local Retained* t_retain = nullptr;
+RetainScope::RetainScope(Retained* r) : prev(t_retain) { t_retain = r; }
+RetainScope::~RetainScope() { t_retain = prev; }
+Retained::~Retained() {
+    for (void* q : ptrs) (void)hipFree(q);
+}
+
 int DevBuf::reserve(size_t bytes) {
     if (bytes <= cap) return ISX_OK;
+    if (p && t_retain) { t_retain->ptrs.push_back(p); t_retain->bytes += (long long)cap; p = nullptr; cap = 0; }
     if (p) { ISX_HIP(hipFree(p)); p = nullptr; cap = 0; }
     // round up so that small geometry changes do not reallocate
     size_t want = (bytes + (1u << 20) - 1) & ~((size_t)(1u << 20) - 1);

@@ -55,10 +55,23 @@ inline int mat_elem_size(int type) {
 const char* type_name(int type);
 
 // ---- device buffer that only ever grows (no hipMalloc in the steady state) -------------------
+// Allocations a captured hipGraph may still point at.  Once a handle's stream has been captured, every DevBuf::reserve made under its
+// RetainScope hands the allocation it outgrows to the handle's Retained instead of freeing it (a later replay still reads and writes it);
+// they are freed when the handle is destroyed.
+struct Retained {
+    std::vector<void*> ptrs;
+    long long bytes = 0;
+    ~Retained();
+};
+struct RetainScope {                 // for the calling thread, while it lives: DevBuf::reserve retains into `r` (nullptr: frees, as always)
+    explicit RetainScope(Retained* r);
+    ~RetainScope();
+    Retained* prev;
+};
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
-    int reserve(size_t bytes);  // grows if needed (synchronous hipFree/hipMalloc), keeps contents undefined
+    int reserve(size_t bytes);  // grows if needed (synchronous hipFree/hipMalloc, see RetainScope), keeps contents undefined
     void release();
     ~DevBuf() { release(); }
     DevBuf() = default;

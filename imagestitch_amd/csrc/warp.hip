@@ -1258,7 +1258,7 @@ struct isx_warper {
     // (round 5: 1024 entries, each with its own host copy.  With 16 entries and one shared host buffer a panorama of more than 16 tiles through
     // one handle missed on EVERY warp - two stream synchronisations and 7 000 sinf / cosf per call: the 64-tile step was host-bound at 68 us per
     // 27 us warp kernel, 9.8 ms against a kernel sum of 7.3, profiles/round5_many_tiles_trace.txt)
-    struct TabEntry { int kind; float scale; int roi[4]; const float* dev; };
+    struct TabEntry { int kind; float scale; int roi[4]; const float* dev; size_t chunk; };
     std::vector<TabEntry> tab_cache;
     std::unordered_multimap<unsigned long long, size_t> tab_index;   // hash of (kind, scale, roi) -> entry (no linear scan of 1024 entries per warp)
     // the tables live in a few 4 MiB chunks, bump-allocated (a DevBuf per entry was a megabyte per entry - reserve() rounds up - i.e. up to a
@@ -1266,6 +1266,13 @@ struct isx_warper {
     std::vector<std::unique_ptr<DevBuf>> tab_chunks;
     size_t tab_chunk = 0, tab_used = 0;    // the chunk being filled and the bytes used in it
     long long tab_resets = 0;
+    // a chunk that a warp enqueued on a CAPTURING stream read from (per tab_chunks entry): a graph holds raw pointers into it, so it is never
+    // rewritten - the start-over moves it to tab_kept (freed at destroy) and the arena goes on in fresh chunks
+    std::vector<char> tab_pinned;
+    std::vector<std::unique_ptr<DevBuf>> tab_kept;
+    // the streams this handle left (isx_warper_set_stream) since the arena last started over, each with an event recorded at its last position
+    // there: the start-over waits for them too, not only for the current stream
+    std::vector<std::pair<hipStream_t, hipEvent_t>> tab_fences;
     std::vector<float> tab_host;           // staging of the one table being built (its upload is waited for)
     std::vector<int> host_cand;
     std::vector<float> host_scratch;      // the host border scan's stand-ins (roihost.cpp)
@@ -1690,6 +1697,11 @@ int make_tabs(isx_warper* w, const int roi[4], MapTabs* t) {
         const unsigned words[6] = {(unsigned)w->kind, sbits, (unsigned)roi[0], (unsigned)roi[1], (unsigned)roi[2], (unsigned)roi[3]};
         for (unsigned v : words) { key ^= v; key *= 1099511628211ull; }
     }
+    // a captured warp reads its tables when the graph is replayed, at a time this handle does not see: it must find them here now (a miss is
+    // refused before anything is enqueued on the stream), and their chunk is pinned for as long as the handle lives
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(w->stream, &cap) != hipSuccess) { cap = hipStreamCaptureStatusNone; (void)hipGetLastError(); }
+    const bool capturing = cap != hipStreamCaptureStatusNone;
     isx_warper::TabEntry* e = nullptr;
     {
         auto r = w->tab_index.equal_range(key);
@@ -1699,11 +1711,21 @@ int make_tabs(isx_warper* w, const int roi[4], MapTabs* t) {
         }
     }
     if (!e) {
+        ISX_CHECK_ARG(!capturing, ISX_ERR_STATE, "warp: no table for the warped tile [%d,%d]-[%d,%d] while the stream is being captured (warm the table before capture: "
+                      "run the same warp once eagerly)", roi[0], roi[1], roi[2], roi[3]);
         const size_t need = (n * sizeof(float) + 255) & ~(size_t)255;
         ISX_CHECK_ARG(need <= TAB_CHUNK, ISX_ERR_UNSUPPORTED, "warp: a %d x %d warped tile needs %zu bytes of column / row tables (limit %zu)", mw, mh, need, TAB_CHUNK);
         auto start_over = [&]() -> int {      // enqueued kernels (and collected ones: isx_warper_begin_batch) may still read the old tables: drain first
             ISX_TRY(flush_warp_batch(w));
+            for (const auto& f : w->tab_fences) ISX_HIP(hipEventSynchronize(f.second));      // ... also on the streams this handle used before
             ISX_HIP(hipStreamSynchronize(w->stream));
+            for (const auto& f : w->tab_fences) (void)hipEventDestroy(f.second);
+            w->tab_fences.clear();
+            std::vector<std::unique_ptr<DevBuf>> reuse;
+            for (size_t c = 0; c < w->tab_chunks.size(); ++c)
+                (c < w->tab_pinned.size() && w->tab_pinned[c] ? w->tab_kept : reuse).push_back(std::move(w->tab_chunks[c]));
+            w->tab_chunks.swap(reuse);
+            w->tab_pinned.assign(w->tab_chunks.size(), 0);
             w->tab_cache.clear(); w->tab_index.clear(); w->tab_chunk = 0; w->tab_used = 0; ++w->tab_resets;
             return ISX_OK;
         };
@@ -1715,6 +1737,7 @@ int make_tabs(isx_warper* w, const int roi[4], MapTabs* t) {
         if (w->tab_chunk >= w->tab_chunks.size()) {
             w->tab_chunks.emplace_back(new DevBuf());
             ISX_TRY(w->tab_chunks.back()->reserve(TAB_CHUNK));
+            w->tab_pinned.resize(w->tab_chunks.size(), 0);
         }
         float* dev = (float*)((char*)w->tab_chunks[w->tab_chunk]->p + w->tab_used);
         w->tab_host.assign(n, 0.f);
@@ -1742,9 +1765,10 @@ int make_tabs(isx_warper* w, const int roi[4], MapTabs* t) {
         w->tab_used += need;
         w->tab_cache.emplace_back();
         e = &w->tab_cache.back();
-        e->kind = w->kind; e->scale = w->scale; std::copy(roi, roi + 4, e->roi); e->dev = dev;
+        e->kind = w->kind; e->scale = w->scale; std::copy(roi, roi + 4, e->roi); e->dev = dev; e->chunk = w->tab_chunk;
         w->tab_index.emplace(key, w->tab_cache.size() - 1);
     }
+    if (capturing) w->tab_pinned[e->chunk] = 1;
     const float* base = e->dev;
     t->col_s = base; t->col_c = base + mwp; t->row_a = base + 2 * mwp; t->row_b = base + 2 * mwp + mhp;
     return ISX_OK;
@@ -1756,8 +1780,8 @@ int check_roi_sane(const int roi[4]) {
     return ISX_OK;
 }
 
-int warp_common(isx_warper* w, const isx_mat* src, const isx_mat* src_mask, const float K[9], const float R[9], int interp, int border,
-                isx_mat* dst, isx_mat* dst_mask, int corner[2], const int* planned, bool fused, bool verify_plan = true) {
+int warp_one(isx_warper* w, const isx_mat* src, const isx_mat* src_mask, const float K[9], const float R[9], int interp, int border,
+             isx_mat* dst, isx_mat* dst_mask, int corner[2], const int* planned, bool fused, bool verify_plan) {
     ISX_CHECK_ARG(w != nullptr, ISX_ERR_INVALID, "warp: null warper");
     ISX_TRY(check_mat(src, "warp: src"));
     ISX_TRY(check_mat(dst, "warp: dst"));
@@ -1913,6 +1937,19 @@ int warp_common(isx_warper* w, const isx_mat* src, const isx_mat* src_mask, cons
     return ISX_OK;
 }
 
+// A warp that fails inside a batch ends the batch: what was collected before it leaves now (those warps returned ISX_OK, so their outputs are
+// written), and the next begin_batch starts empty.  The failure's own status and message are returned (a failing flush replaces them).
+int warp_common(isx_warper* w, const isx_mat* src, const isx_mat* src_mask, const float K[9], const float R[9], int interp, int border,
+                isx_mat* dst, isx_mat* dst_mask, int corner[2], const int* planned, bool fused, bool verify_plan = true) {
+    const int rc = warp_one(w, src, src_mask, K, R, interp, border, dst, dst_mask, corner, planned, fused, verify_plan);
+    if (rc != ISX_OK && w != nullptr && w->batching) {
+        w->batching = false;
+        ISX_TRY(flush_warp_batch(w));
+        if (!w->defer_verify) ISX_TRY(flush_verify(w));
+    }
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1936,7 +1973,10 @@ int isx_warper_create(int kind, float scale, int device, isx_warper** out) ISX_E
 int isx_warper_destroy(isx_warper* w) ISX_ENTRY {
     if (!w) return ISX_OK;
     (void)hipSetDevice(w->device);
+    w->batching = false;
+    (void)flush_warp_batch(w);          // an open batch: its warps returned ISX_OK, their outputs are written before the handle goes
     (void)hipStreamSynchronize(w->stream);
+    for (const auto& f : w->tab_fences) (void)hipEventDestroy(f.second);
     if (w->side) { (void)hipStreamSynchronize(w->side); (void)hipEventDestroy(w->ev_warp); (void)hipEventDestroy(w->ev_scan); }   // the side stream is shared per device
     if (w->pin) (void)hipHostFree(w->pin);
     if (w->pin2) (void)hipHostFree(w->pin2);
@@ -1966,6 +2006,22 @@ int isx_warper_end_batch(isx_warper* w) ISX_ENTRY {
 int isx_warper_set_stream(isx_warper* w, void* hip_stream) ISX_ENTRY {
     ISX_CHECK_ARG(w != nullptr, ISX_ERR_INVALID, "isx_warper_set_stream: null warper");
     ISX_TRY(flush_warp_batch(w));      // collected warps leave on the stream they were issued for
+    if ((hipStream_t)hip_stream != w->stream && !w->tab_cache.empty()) {
+        // the stream being left may still run warps that read the table arena: a later start-over waits for this point of it (a stream being
+        // captured enqueues nothing that runs now, and the chunks its graph reads are pinned)
+        ISX_HIP(hipSetDevice(w->device));
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(w->stream, &cs) != hipSuccess) { cs = hipStreamCaptureStatusNone; (void)hipGetLastError(); }
+        if (cs == hipStreamCaptureStatusNone) {
+            hipEvent_t ev = nullptr;
+            for (const auto& f : w->tab_fences) if (f.first == w->stream) ev = f.second;
+            if (!ev) {
+                ISX_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+                w->tab_fences.emplace_back(w->stream, ev);
+            }
+            ISX_HIP(hipEventRecord(ev, w->stream));
+        }
+    }
     w->stream = (hipStream_t)hip_stream;
     return ISX_OK;
 } ISX_EXIT("isx_warper_set_stream")
@@ -1986,6 +2042,12 @@ int isx_warper_set_gain(isx_warper* w, double gain) ISX_ENTRY {
     w->gain = gain;
     return ISX_OK;
 } ISX_EXIT("isx_warper_set_gain")
+
+int isx_warper_table_resets(isx_warper* w, long long* resets) ISX_ENTRY {
+    ISX_CHECK_ARG(w != nullptr && resets != nullptr, ISX_ERR_INVALID, "isx_warper_table_resets: null argument");
+    *resets = w->tab_resets;
+    return ISX_OK;
+} ISX_EXIT("isx_warper_table_resets")
 
 int isx_warper_set_roi_cache(isx_warper* w, int on) ISX_ENTRY {
     ISX_CHECK_ARG(w != nullptr, ISX_ERR_INVALID, "isx_warper_set_roi_cache: null warper");

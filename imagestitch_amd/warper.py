@@ -165,6 +165,12 @@ class RotationWarper:
         """Opt-in: remember detectResultRoi per (K, R, scale, source size); repeated calls skip the scan and its host sync."""
         check(self._lib.isx_warper_set_roi_cache(self._h, int(bool(on))))
 
+    def table_resets(self):
+        """isx_warper_table_resets: how many times the mapBackward table arena has started over (1024 entries or 16 MiB)."""
+        n = C.c_longlong()
+        check(self._lib.isx_warper_table_resets(self._h, C.byref(n)))
+        return n.value
+
     def set_gain(self, gain=1.0):
         """GainCompensator::apply (W:241-244) folded into the fused warps that follow (warp_with_mask*, all-255 mask): isx_warper_set_gain."""
         check(self._lib.isx_warper_set_gain(self._h, C.c_double(float(gain))))

@@ -117,6 +117,13 @@ int isx_warper_roi(isx_warper* w, int src_w, int src_h, const float K[9], const 
  * Off by default: only the LAST result is then remembered - the reference asks for the same ROI twice in a row (warp(img, K, R), then
  * warp(mask, K, R), W:229,232) and the second call returns the first one's answer; any other call computes its ROI as the reference does. */
 int isx_warper_set_roi_cache(isx_warper* w, int on);
+/* Introspection of the mapBackward table arena: how many times it has started over.  Tables are cached per (kind, scale, ROI) in 4 MiB
+ * chunks, at most 1024 entries and 16 MiB; when either is full the arena starts over, after waiting for the current stream and for every
+ * stream this handle left (isx_warper_set_stream) since the last start-over.  A chunk that a warp enqueued on a CAPTURING stream read from is
+ * never rewritten: a start-over sets it aside until isx_warper_destroy and continues in fresh chunks - at most the 4 chunks (16 MiB) the
+ * arena held per start-over that follows a capture.  A warp on a capturing stream whose table is not cached fails with ISX_ERR_STATE
+ * before it enqueues anything: run the same warp once eagerly before the capture.                                                   */
+int isx_warper_table_resets(isx_warper* w, long long* resets);
 /* compensator->apply(i, corners[i], images_warped[i], masks_warped[i]) (W:241-244) folded into the fused tile warps that
  * follow (isx_warper_warp_with_mask / _roi / _planned with src_mask == NULL): every byte of the warped IMAGE becomes
  * saturate_cast<uchar>(cvRound((double)byte * gain)) - exactly isx_gain_apply on the warped tile, one pass over it less (the gain acts on
@@ -170,6 +177,9 @@ int isx_warper_warp_with_mask_planned(isx_warper* w, const isx_mat* src_img,
  * Same kernel body, same bits.  The outputs are not written, nor even enqueued, before isx_warper_end_batch returns: use them (feed them)
  * after it.  isx_warper_verify / _join / _plan_status / _set_stream end the collection's pending launches as well; anything that cannot be
  * collected (a caller-supplied source mask, host mats, a gain) is launched at once, behind what was collected so far.                  */
+/* A warp that FAILS while a batch is collecting (a wrong dst size, say) ends the batch: the warps collected before it are launched and the
+ * handle is no longer batching (a following isx_warper_end_batch returns ISX_OK and launches nothing).  isx_warper_destroy launches an open
+ * batch before it waits for the stream: a warp that returned ISX_OK always writes its output.                                          */
 int isx_warper_begin_batch(isx_warper* w);
 int isx_warper_end_batch(isx_warper* w);
 int isx_warper_plan_status(isx_warper* w, int* mismatches /* synchronises the stream */);
@@ -298,6 +308,10 @@ int isx_blender_level1_format(isx_blender* b, int* format);
 /* Introspection of cycle 4: how many 3.5 KB pieces of tile tables this blender has uploaded so far.  They travel in kernel arguments, in
  * stream order, and only where they differ from what the device holds: a fixed rig uploads on its first blend() and never again.      */
 int isx_blender_table_uploads(isx_blender* b, long long* pieces);
+/* Once a step of this blender has been captured into a hipGraph (its stream was seen capturing), a later call that outgrows one of its device
+ * buffers - more tiles, a larger panorama, more bands - keeps the old allocation alive until isx_blender_destroy instead of freeing it, since
+ * a replay of the graph still reads and writes it.  This reports the bytes so kept (0 for a blender that was never captured).          */
+int isx_blender_retained_bytes(isx_blender* b, long long* bytes);
 /* How the tiles of the last isx_blender_blend were FED in mode 2 (isx_blender_set_deferred_level0 = 2, OpenCV's contract W:302-308).
  * fused_tiles: tiles whose feed() was ONE pass over the caller's CV_8UC3 / CV_16SC3 device mats - level 1 of the tile's pyramid and the
  * private copy out of the same read (round 5; 0: host mats, other tile types, ISX_FEED_FUSE=0).  narrowed: 0 = no private copy was

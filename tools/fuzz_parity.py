@@ -726,8 +726,91 @@ def case_round6_calls(rng):
         assert np.array_equal(dm.cpu().numpy(), om)
 
 
+def case_long_lived(rng):
+    """One warper and one blender kept for a random sequence of 5-30 operations, as a video stitcher keeps them (the parity families above
+    create fresh handles per call): warps of new and repeated ROIs, multi-band cycles of 2-19 and 21-30 tiles (both sides of DEF_MAX, i.e.
+    kernel-argument tile sets and the device table), band-count changes, eager / deferred / deferred-copy feeds, CV_8UC3 and CV_16SC3 tiles,
+    and set_stream between torch streams (the new stream ordered behind the old one).  The precision is a property of the handle
+    (isx_blender_create): each case draws one.  The case owns its handles, so its seed replays it.  Every result against the oracle."""
+    import torch
+    prec = int(rng.integers(0, 3))
+    kind = int(rng.integers(0, 2))
+    sw, sh = int(rng.integers(24, 90)), int(rng.integers(8, 40))
+    f = float(rng.uniform(0.6, 2.0) * sw)
+    K = np.array([[f, 0, sw / 2], [0, f, sh / 2], [0, 0, 1]], np.float32)
+    src = rng.integers(0, 256, (sh, sw, 3)).astype(np.uint8)
+    streams = [torch.cuda.current_stream(), torch.cuda.Stream(), torch.cuda.Stream()]
+    cur = streams[0]
+    wp = (G.CylindricalWarper() if kind == 0 else G.SphericalWarper()).create(f)
+    wp.set_roi_cache(bool(rng.integers(0, 2)))
+    mb = G.MultiBandBlender(False, int(rng.integers(1, 6)), prec)
+    cams = []
+    src_dev = torch.from_numpy(src).cuda()
+    for _ in range(int(rng.integers(5, 31))):
+        op = rng.choice(["warp", "warp", "cycle", "cycle", "stream"])
+        if op == "stream":
+            nxt = streams[int(rng.integers(0, 3))]
+            nxt.wait_stream(cur)
+            cur = nxt
+            wp.set_stream(cur)
+            mb.set_stream(cur)
+        elif op == "warp":
+            if cams and rng.integers(0, 3) == 0:
+                R = cams[int(rng.integers(0, len(cams)))]
+            else:
+                R = rot(rng, 0.6)
+                cams.append(R)
+            roi, _ = O.detect_roi(kind, f, K, R, sw, sh)
+            if roi[2] < roi[0] or roi[3] < roi[1] or (roi[2] - roi[0] + 1) * (roi[3] - roi[1] + 1) > 1_000_000:
+                continue
+            with torch.cuda.stream(cur):
+                c, wi, wm = wp.warp_with_mask(src_dev, K, R)
+                wi, wm = wi.cpu().numpy(), wm.cpu().numpy()
+            oc, oi, _ = O.warp_u8(kind, f, K, R, src, 1, 2)
+            _, om, _ = O.warp_u8(kind, f, K, R, np.full((sh, sw), 255, np.uint8), 0, 0)
+            assert tuple(c) == tuple(oc), (c, oc)
+            assert np.array_equal(wi, oi) and np.array_equal(wm, om), ("warp", kind, np.argwhere(wi != oi)[:3])
+        else:
+            n = int(rng.integers(2, 20)) if rng.integers(0, 2) else int(rng.integers(21, 31))
+            bands = int(rng.integers(0, 7))
+            mode = [False, True, "copy"][int(rng.integers(0, 3))]
+            s16 = bool(rng.integers(0, 2))
+            corners, sizes, x = [], [], int(rng.integers(-20, 20))
+            for i in range(n):
+                w, h = int(rng.integers(8, 70)), int(rng.integers(6, 50))
+                corners.append((x, int(rng.integers(-8, 9))))
+                sizes.append((w, h))
+                x += int(w * rng.uniform(0.2, 0.9))
+            mb.setNumBands(bands)
+            mb.set_deferred_level0(mode)
+            ob = O.MultiBand(bands, prec)
+            ob.prepare(corners, sizes)
+            keep = []
+            with torch.cuda.stream(cur):
+                mb.prepare(corners, sizes)
+                for (w, h), c in zip(sizes, corners):
+                    img = rng.integers(0, 256, (h, w, 3)).astype(np.uint8)
+                    mask = ((rng.random((h, w)) > rng.uniform(0, 0.4)) * 255).astype(np.uint8)
+                    ob.feed(img.astype(np.int16), mask, c)
+                    ti = torch.from_numpy(img.astype(np.int16) if s16 else img).cuda()
+                    tm = torch.from_numpy(mask).cuda()
+                    keep.append((ti, tm))
+                    if s16:
+                        mb.feed(ti, tm, c)
+                    else:
+                        mb.feed_u8(ti, tm, c)
+                f32 = prec != 0 and bool(rng.integers(0, 2))
+                d, m = mb.blend(out_f32=f32)
+                d, m = d.cpu().numpy(), m.cpu().numpy()
+            od, om = ob.blend(f32)
+            assert np.array_equal(m, om), ("cycle mask", n, bands, prec, mode, s16)
+            assert np.array_equal(d, od), ("cycle", n, bands, prec, mode, s16, mb.last_path(), np.argwhere(d != od)[:3])
+    torch.cuda.synchronize()
+
+
 CASES = [case_warp, case_blend, case_feather, case_prep, case_seam, case_blend_float_and_many, case_pipeline, case_find, case_warp_fused,
-         case_linear_pair, case_strip, case_strip_feather, case_batch, case_s16_tiles, case_round4_calls, case_many_tiles, case_fused_feed, case_round6_calls]
+         case_linear_pair, case_strip, case_strip_feather, case_batch, case_s16_tiles, case_round4_calls, case_many_tiles, case_fused_feed, case_round6_calls,
+         case_long_lived]
 
 
 def run(budget, seed0, verbose=True, progress_path=None):
