@@ -1,0 +1,571 @@
+// graphcut.hip — GraphCutSeamFinder(COST_COLOR) (OpenCV 3.4.2 stitching/src/seam_finders.cpp) on gfx950:
+//   isx_graphcut_seam_find        seam_finder = new GraphCutSeamFinder(GraphCutSeamFinder::COST_COLOR);  W:257
+//                                 seam_finder->find(images_warped_f, corners, masks_warped)             W:264
+//   isx_graphcut_seam_find_pair   one pair, optionally with a certificate of its maximum flow
+//
+// The specification (DESIGN.md §8 "graph-cut seam finder"; OpenCV parity unpinned): for i < j with a non-empty overlapRoi, a padded grid
+// of (roi.h + 20) x (roi.w + 20) nodes (gap 10; outside a tile: image 0, mask 0); mask1 only -> source 10000, mask2 only -> sink 10000;
+// every right / down edge w = |d(p)|^2 + |d(q)|^2 + 1 (+ 1000 when a mask byte of p or q is 0) both ways; write-back over the roi from
+// the MAXIMAL source side (the nodes that cannot reach the sink in the residual graph of a maximum flow - unique, whatever the schedule).
+// With CV_8UC3 tiles, or CV_32FC3 tiles holding integers in [0, 255], every w is an integer below 2^24: the flow is exact in int32.
+//
+// The max-flow is push-relabel over the 4-connected grid, one node per thread, launch boundaries the only cross-block synchronisation:
+//   k_gc_relabel   an active node (excess > 0, height finite) takes 1 + the lowest height over its residual out-edges (in place: heights
+//                  only rise, so a neighbour read old or new keeps the labelling valid)
+//   k_gc_push      an active node pushes along admissible edges (the sink when its height is 1, a neighbour one lower).  Residuals are
+//                  stored once per undirected edge by its left / upper node (r(v -> v+1) = rR[v], r(v+1 -> v) = 2 capR[v] - rR[v]), so a push
+//                  writes one edge word, and the two ends of an edge cannot push across it in the same launch (their heights would have to
+//                  differ by +1 and -1): no atomics, no lost updates.  A node's excess is not stored: it follows from its terminal and
+//                  edge residuals, and a neighbour's concurrent push into it can only raise what it reads.
+//   global relabel every GC_SWEEPS sweeps: heights = BFS distance to the sink over residual edges (k_gc_bfs_init, then k_gc_bfs_tile:
+//                  64 x 16 node tiles relaxed in LDS for up to GC_BFS_ITERS steps per launch, in place - distances only fall), with the
+//                  active-node count (k_gc_count) read back once per batch of GC_BFS_BATCH launches.
+// It ends when no node with a finite height holds excess: the preflow is then maximal and the nodes of infinite height are exactly those
+// that cannot reach the sink.  Every device loop has a fixed trip count; the host loops are capped (GC_MAX_ROUNDS rounds, GC_MAX_BFS_BATCHES
+// batches per global relabel) and the call fails past them with the pair's masks untouched.
+#include "isx_device.hpp"
+#include "isx_internal.hpp"
+
+#include <algorithm>
+#include <memory>
+
+using namespace isx;
+using namespace isxd;
+
+namespace {
+
+constexpr int GC_GAP = 10;
+constexpr int GC_TERM = 10000;
+constexpr int GC_PENALTY = 1000;
+constexpr int GC_INF = 1 << 30;
+constexpr int GC_SWEEPS = 16;            // push-relabel sweeps between global relabels
+constexpr int GC_MAX_ROUNDS = 4096;      // rounds of (GC_SWEEPS sweeps, global relabel) per pair
+constexpr int GC_BFS_BATCH = 4;          // BFS tile launches per read-back
+constexpr int GC_MAX_BFS_BATCHES = 8192; // read-backs per global relabel
+constexpr int GC_BFS_ITERS = 64;         // relaxation steps in LDS per BFS tile launch
+constexpr int GC_TW = 64, GC_TH = 16;    // BFS tile (256 threads, 4 rows each)
+constexpr int GC_NT = 256;
+
+struct GcGeom {
+    const unsigned char* i1; size_t s1;
+    const unsigned char* i2; size_t s2;
+    unsigned char* m1; size_t sm1;
+    unsigned char* m2; size_t sm2;
+    int r1, c1, r2, c2;                  // tile sizes
+    int oy1, ox1, oy2, ox2;              // tile coordinates of grid node (0, 0)
+    int hp, wp;                          // padded grid
+    int rh, rw;                          // the roi
+};
+
+struct GcArr {
+    int* capR; int* capD; int* term; int* rR; int* rD; int* rT; int* h;
+    int hp, wp;
+};
+
+template <bool U8>
+__device__ __forceinline__ void gc_pixel(const unsigned char* p, size_t step, int y, int x, int& b, int& g, int& r) {
+    if constexpr (U8) {
+        const unsigned char* q = p + (size_t)y * step + (size_t)x * 3;
+        b = q[0]; g = q[1]; r = q[2];
+    } else {
+        const float* q = (const float*)(p + (size_t)y * step) + (size_t)x * 3;
+        b = (int)q[0]; g = (int)q[1]; r = (int)q[2];    // integers in [0, 255]: checked before the first pair
+    }
+}
+
+// |img1 - img2|^2 at grid node (y, x) and whether both masks are set there
+template <bool U8>
+__device__ __forceinline__ int gc_node(const GcGeom& G, int y, int x, bool& m1, bool& m2) {
+    int b1 = 0, g1 = 0, r1 = 0, b2 = 0, g2 = 0, r2 = 0;
+    const int y1 = G.oy1 + y, x1 = G.ox1 + x, y2 = G.oy2 + y, x2 = G.ox2 + x;
+    m1 = m2 = false;
+    if ((unsigned)y1 < (unsigned)G.r1 && (unsigned)x1 < (unsigned)G.c1) {
+        gc_pixel<U8>(G.i1, G.s1, y1, x1, b1, g1, r1);
+        m1 = G.m1[(size_t)y1 * G.sm1 + x1] != 0;
+    }
+    if ((unsigned)y2 < (unsigned)G.r2 && (unsigned)x2 < (unsigned)G.c2) {
+        gc_pixel<U8>(G.i2, G.s2, y2, x2, b2, g2, r2);
+        m2 = G.m2[(size_t)y2 * G.sm2 + x2] != 0;
+    }
+    const int db = b1 - b2, dg = g1 - g2, dr = r1 - r2;
+    return db * db + dg * dg + dr * dr;
+}
+
+// setGraphWeightsColor: terminal and edge capacities, the residuals at zero flow, heights to be set by the first global relabel
+template <bool U8>
+__global__ __launch_bounds__(GC_NT) void k_gc_build(GcGeom G, GcArr a) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= G.wp || y >= G.hp) return;
+    const size_t v = (size_t)y * G.wp + x;
+    bool p1, p2;
+    const int dp = gc_node<U8>(G, y, x, p1, p2);
+    int cr = 0, cd = 0;
+    if (x + 1 < G.wp) {
+        bool q1, q2;
+        const int dq = gc_node<U8>(G, y, x + 1, q1, q2);
+        cr = dp + dq + 1 + ((p1 && p2 && q1 && q2) ? 0 : GC_PENALTY);
+    }
+    if (y + 1 < G.hp) {
+        bool q1, q2;
+        const int dq = gc_node<U8>(G, y + 1, x, q1, q2);
+        cd = dp + dq + 1 + ((p1 && p2 && q1 && q2) ? 0 : GC_PENALTY);
+    }
+    const int t = (p1 && !p2) ? GC_TERM : (p2 && !p1) ? -GC_TERM : 0;
+    a.capR[v] = cr; a.rR[v] = cr;
+    a.capD[v] = cd; a.rD[v] = cd;
+    a.term[v] = t; a.rT[v] = t < 0 ? GC_TERM : 0;
+}
+
+// a CV_32FC3 value that is not an integer in [0, 255] (NaN included) raises the flag
+__global__ __launch_bounds__(GC_NT) void k_gc_check_f32(const unsigned char* p, size_t step, int rows, int cols, int* flag) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= cols || y >= rows) return;
+    const float* q = (const float*)(p + (size_t)y * step) + (size_t)x * 3;
+    bool bad = false;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float f = q[c];
+        bad |= !(f >= 0.f && f <= 255.f && f == floorf(f));
+    }
+    if (bad) *flag = 1;
+}
+
+// excess of node v: source inflow - sink outflow + net inflow over its four edges (all from the residuals)
+__device__ __forceinline__ int gc_excess(const GcArr& a, int y, int x, size_t v) {
+    const int t = a.term[v];
+    int e = (t > 0 ? t : 0) - ((t < 0 ? -t : 0) - a.rT[v]);
+    e -= a.capR[v] - a.rR[v];
+    e -= a.capD[v] - a.rD[v];
+    if (x > 0) e += a.capR[v - 1] - a.rR[v - 1];
+    if (y > 0) e += a.capD[v - a.wp] - a.rD[v - a.wp];
+    return e;
+}
+
+// residuals of v's out-edges: right, left, down, up
+__device__ __forceinline__ void gc_res4(const GcArr& a, int y, int x, size_t v, int r[4]) {
+    r[0] = a.rR[v];
+    r[1] = x > 0 ? 2 * a.capR[v - 1] - a.rR[v - 1] : 0;
+    r[2] = a.rD[v];
+    r[3] = y > 0 ? 2 * a.capD[v - a.wp] - a.rD[v - a.wp] : 0;
+}
+
+__global__ __launch_bounds__(GC_NT) void k_gc_relabel(GcArr a) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= a.wp || y >= a.hp) return;
+    const size_t v = (size_t)y * a.wp + x;
+    const int h = a.h[v];
+    if (h >= GC_INF || gc_excess(a, y, x, v) <= 0) return;
+    int r[4];
+    gc_res4(a, y, x, v, r);
+    int m = a.rT[v] > 0 ? 0 : GC_INF;
+    if (r[0] > 0) m = min(m, a.h[v + 1]);
+    if (r[1] > 0) m = min(m, a.h[v - 1]);
+    if (r[2] > 0) m = min(m, a.h[v + a.wp]);
+    if (r[3] > 0) m = min(m, a.h[v - a.wp]);
+    const int nh = m >= GC_INF - 1 ? GC_INF : m + 1;
+    if (nh > h) a.h[v] = nh;
+}
+
+__global__ __launch_bounds__(GC_NT) void k_gc_push(GcArr a) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= a.wp || y >= a.hp) return;
+    const size_t v = (size_t)y * a.wp + x;
+    const int h = a.h[v];
+    if (h >= GC_INF) return;
+    int e = gc_excess(a, y, x, v);
+    if (e <= 0) return;
+    if (h == 1 && a.rT[v] > 0) {
+        const int d = min(e, a.rT[v]);
+        a.rT[v] -= d; e -= d;
+    }
+    if (e > 0 && x + 1 < a.wp && a.h[v + 1] == h - 1 && a.rR[v] > 0) {
+        const int d = min(e, a.rR[v]);
+        a.rR[v] -= d; e -= d;
+    }
+    if (e > 0 && x > 0 && a.h[v - 1] == h - 1) {
+        const int r = 2 * a.capR[v - 1] - a.rR[v - 1];
+        const int d = min(e, r);
+        if (d > 0) { a.rR[v - 1] += d; e -= d; }
+    }
+    if (e > 0 && y + 1 < a.hp && a.h[v + a.wp] == h - 1 && a.rD[v] > 0) {
+        const int d = min(e, a.rD[v]);
+        a.rD[v] -= d; e -= d;
+    }
+    if (e > 0 && y > 0 && a.h[v - a.wp] == h - 1) {
+        const int r = 2 * a.capD[v - a.wp] - a.rD[v - a.wp];
+        const int d = min(e, r);
+        if (d > 0) a.rD[v - a.wp] += d;
+    }
+}
+
+__global__ __launch_bounds__(GC_NT) void k_gc_bfs_init(GcArr a) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= a.wp || y >= a.hp) return;
+    const size_t v = (size_t)y * a.wp + x;
+    a.h[v] = a.rT[v] > 0 ? 1 : GC_INF;
+}
+
+// one 64 x 16 tile: heights with a one-node halo in LDS, relaxed h(v) = min(h(v), 1 + h(w)) over residual v -> w until nothing changes
+// (at most GC_BFS_ITERS steps); lowered heights are written back and raise *changed
+__global__ __launch_bounds__(GC_NT) void k_gc_bfs_tile(GcArr a, int* changed) {
+    __shared__ int sh[GC_TH + 2][GC_TW + 2];
+    const int x0 = blockIdx.x * GC_TW, y0 = blockIdx.y * GC_TH;
+    for (int k = threadIdx.x; k < (GC_TH + 2) * (GC_TW + 2); k += GC_NT) {
+        const int ly = k / (GC_TW + 2), lx = k - ly * (GC_TW + 2);
+        const int y = y0 + ly - 1, x = x0 + lx - 1;
+        sh[ly][lx] = ((unsigned)y < (unsigned)a.hp && (unsigned)x < (unsigned)a.wp) ? a.h[(size_t)y * a.wp + x] : GC_INF;
+    }
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    unsigned dirs[4];                   // residual out-edges of this thread's four nodes: bit 0 right, 1 left, 2 down, 3 up
+    int h0[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int y = y0 + ty + 4 * k, x = x0 + tx;
+        dirs[k] = 0;
+        h0[k] = GC_INF;
+        if (y < a.hp && x < a.wp) {
+            const size_t v = (size_t)y * a.wp + x;
+            int r[4];
+            gc_res4(a, y, x, v, r);
+            dirs[k] = (r[0] > 0 ? 1u : 0u) | (r[1] > 0 ? 2u : 0u) | (r[2] > 0 ? 4u : 0u) | (r[3] > 0 ? 8u : 0u);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) h0[k] = sh[ty + 4 * k + 1][tx + 1];
+    for (int it = 0; it < GC_BFS_ITERS; ++it) {
+        int ch = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int ly = ty + 4 * k + 1, lx = tx + 1;
+            const int cur = sh[ly][lx];
+            int m = GC_INF;
+            if (dirs[k] & 1u) m = min(m, sh[ly][lx + 1]);
+            if (dirs[k] & 2u) m = min(m, sh[ly][lx - 1]);
+            if (dirs[k] & 4u) m = min(m, sh[ly + 1][lx]);
+            if (dirs[k] & 8u) m = min(m, sh[ly - 1][lx]);
+            if (m < GC_INF && m + 1 < cur) { sh[ly][lx] = m + 1; ch = 1; }
+        }
+        if (!__syncthreads_or(ch)) break;
+    }
+    int any = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int y = y0 + ty + 4 * k, x = x0 + tx;
+        const int hn = sh[ty + 4 * k + 1][tx + 1];
+        if (y < a.hp && x < a.wp && hn < h0[k]) {
+            a.h[(size_t)y * a.wp + x] = hn;
+            any = 1;
+        }
+    }
+    if (__syncthreads_or(any) && threadIdx.x == 0) *changed = 1;
+}
+
+// out[0] += active nodes (excess > 0 and a finite height); with flow != nullptr also *flow += sum of the sink links' flow
+__global__ __launch_bounds__(GC_NT) void k_gc_count(GcArr a, int* out, unsigned long long* flow) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    int act = 0, f = 0;
+    if (x < a.wp && y < a.hp) {
+        const size_t v = (size_t)y * a.wp + x;
+        act = (a.h[v] < GC_INF && gc_excess(a, y, x, v) > 0) ? 1 : 0;
+        if (a.term[v] < 0) f = GC_TERM - a.rT[v];
+    }
+    __shared__ int sa[GC_NT / WAVE];
+    __shared__ unsigned long long sf[GC_NT / WAVE];
+    unsigned long long fl = (unsigned long long)f;
+    for (int o = 32; o > 0; o >>= 1) { act += __shfl_xor(act, o); fl += __shfl_xor(fl, o); }
+    if ((threadIdx.x & (WAVE - 1)) == 0) { sa[threadIdx.x / WAVE] = act; sf[threadIdx.x / WAVE] = fl; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int s = 0;
+        unsigned long long t = 0;
+        for (int w = 0; w < GC_NT / WAVE; ++w) { s += sa[w]; t += sf[w]; }
+        if (s) atomicAdd(out, s);
+        if (flow && t) atomicAdd(flow, t);
+    }
+}
+
+// findInPair's write-back over the roi: source side and mask1 set -> mask2 = 0; sink side and mask2 set -> mask1 = 0
+__global__ __launch_bounds__(GC_NT) void k_gc_write_back(GcGeom G, const int* h) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= G.rw || y >= G.rh) return;
+    const int gy = y + GC_GAP, gx = x + GC_GAP;
+    unsigned char* p1 = G.m1 + (size_t)(G.oy1 + gy) * G.sm1 + (G.ox1 + gx);
+    unsigned char* p2 = G.m2 + (size_t)(G.oy2 + gy) * G.sm2 + (G.ox2 + gx);
+    if (h[(size_t)gy * G.wp + gx] >= GC_INF) {
+        if (*p1) *p2 = 0;
+    } else {
+        if (*p2) *p1 = 0;
+    }
+}
+
+// the certificate: per node (right, left, down, up, source, sink) residuals and the label (1 = source side)
+__global__ __launch_bounds__(GC_NT) void k_gc_cert(GcArr a, int* res, unsigned char* labels) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= a.wp || y >= a.hp) return;
+    const size_t v = (size_t)y * a.wp + x;
+    int r[4];
+    gc_res4(a, y, x, v, r);
+    int* o = res + 6 * v;
+    o[0] = r[0]; o[1] = r[1]; o[2] = r[2]; o[3] = r[3];
+    o[4] = 0;                           // every source link stays saturated (the preflow never returns excess to the source)
+    o[5] = a.rT[v];
+    labels[v] = a.h[v] >= GC_INF ? 1 : 0;
+}
+
+// per calling thread, kept between calls: the graph arrays, the counters (device and pinned), staged host images and masks
+struct GcScratch {
+    DevBuf graph, cert;
+    int device = -1;
+    int* pin = nullptr;
+    std::vector<std::unique_ptr<MatStage>> img, msk;
+};
+GcScratch& gc_scratch() {
+    static thread_local GcScratch* s = new GcScratch();   // never destroyed at thread exit (the HIP runtime may be gone by then)
+    return *s;
+}
+
+enum { GC_C_CHANGED = 0, GC_C_COUNT = GC_BFS_BATCH, GC_C_FLAG, GC_C_FLOW, GC_C_WORDS = GC_C_FLOW + 2 };
+
+struct PairOut {
+    long long flow = 0;
+    int rounds = 0, launches = 0, hp = 0, wp = 0;
+};
+
+inline dim3 gc_grid(int w, int h) { return dim3((unsigned)cdiv(w, 64), (unsigned)cdiv(h, 4)); }
+
+// the max-flow of one pair's graph and its write-back; cert_res / cert_lab (device, may be null) receive the certificate
+int gc_solve_pair(GcScratch& s, const GcGeom& G, bool u8, hipStream_t st, PairOut& out, int* cert_res, unsigned char* cert_lab) {
+    const size_t n = (size_t)G.hp * G.wp;
+    const size_t arr = (n * sizeof(int) + 255) & ~(size_t)255;
+    ISX_TRY(s.graph.reserve(7 * arr + 256));
+    char* base = (char*)s.graph.p;
+    GcArr a{(int*)(base), (int*)(base + arr), (int*)(base + 2 * arr), (int*)(base + 3 * arr), (int*)(base + 4 * arr), (int*)(base + 5 * arr),
+            (int*)(base + 6 * arr), G.hp, G.wp};
+    int* cnt = (int*)(base + 7 * arr);               // GC_C_WORDS ints: changed flags, active count, (unused) flag, flow (8-byte aligned)
+    const dim3 grid = gc_grid(G.wp, G.hp), tiles((unsigned)cdiv(G.wp, GC_TW), (unsigned)cdiv(G.hp, GC_TH));
+    const double nb = (double)n * 4.0;
+    out.hp = G.hp; out.wp = G.wp; out.rounds = 0; out.launches = 0;
+    if (u8) ISX_LAUNCH("graphcut_build", nb * 7, st, (k_gc_build<true>), grid, dim3(GC_NT), 0, G, a);
+    else ISX_LAUNCH("graphcut_build", nb * 7, st, (k_gc_build<false>), grid, dim3(GC_NT), 0, G, a);
+    ++out.launches;
+    // global relabel, then the active count; returns the count in *active
+    auto global_relabel = [&](int* active) -> int {
+        ISX_LAUNCH("graphcut_bfs_init", nb * 2, st, k_gc_bfs_init, grid, dim3(GC_NT), 0, a);
+        ++out.launches;
+        for (int b = 0; b < GC_MAX_BFS_BATCHES; ++b) {
+            ISX_HIP(hipMemsetAsync(cnt, 0, (GC_C_COUNT + 1) * sizeof(int), st));
+            for (int k = 0; k < GC_BFS_BATCH; ++k) {
+                ISX_LAUNCH("graphcut_bfs", nb * 6, st, k_gc_bfs_tile, tiles, dim3(GC_NT), 0, a, cnt + GC_C_CHANGED + k);
+                ++out.launches;
+            }
+            ISX_LAUNCH("graphcut_count", nb * 7, st, k_gc_count, grid, dim3(GC_NT), 0, a, cnt + GC_C_COUNT, (unsigned long long*)nullptr);
+            ++out.launches;
+            ISX_HIP(hipMemcpyAsync(s.pin, cnt, (GC_C_COUNT + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
+            ISX_HIP(hipStreamSynchronize(st));
+            if (s.pin[GC_C_CHANGED + GC_BFS_BATCH - 1] == 0) { *active = s.pin[GC_C_COUNT]; return ISX_OK; }
+        }
+        return fail(ISX_ERR_UNSUPPORTED, "graphcut: the global relabel did not settle within %d launches", GC_MAX_BFS_BATCHES * GC_BFS_BATCH);
+    };
+    int active = 0;
+    ISX_TRY(global_relabel(&active));
+    while (active > 0) {
+        if (out.rounds == GC_MAX_ROUNDS)
+            return fail(ISX_ERR_UNSUPPORTED, "graphcut: the max-flow of a %d x %d grid did not finish within %d rounds (%d nodes still active); "
+                        "the pair's masks are unchanged", G.hp, G.wp, GC_MAX_ROUNDS, active);
+        ++out.rounds;
+        for (int k = 0; k < GC_SWEEPS; ++k) {
+            ISX_LAUNCH("graphcut_relabel", nb * 11, st, k_gc_relabel, grid, dim3(GC_NT), 0, a);
+            ISX_LAUNCH("graphcut_push", nb * 12, st, k_gc_push, grid, dim3(GC_NT), 0, a);
+            out.launches += 2;
+        }
+        ISX_TRY(global_relabel(&active));
+    }
+    unsigned long long* flow = (unsigned long long*)(cnt + GC_C_FLOW);
+    ISX_HIP(hipMemsetAsync(cnt, 0, GC_C_WORDS * sizeof(int), st));
+    ISX_LAUNCH("graphcut_count", nb * 7, st, k_gc_count, grid, dim3(GC_NT), 0, a, cnt + GC_C_COUNT, flow);
+    ++out.launches;
+    if (cert_res) {
+        ISX_LAUNCH("graphcut_cert", nb * 30, st, k_gc_cert, grid, dim3(GC_NT), 0, a, cert_res, cert_lab);
+        ++out.launches;
+    }
+    ISX_LAUNCH("graphcut_write_back", (double)G.rw * G.rh * 8.0, st, k_gc_write_back, gc_grid(G.rw, G.rh), dim3(GC_NT), 0, G, (const int*)a.h);
+    ++out.launches;
+    ISX_HIP(hipMemcpyAsync(s.pin, cnt, GC_C_WORDS * sizeof(int), hipMemcpyDeviceToHost, st));
+    ISX_HIP(hipStreamSynchronize(st));
+    unsigned long long f;
+    memcpy(&f, s.pin + GC_C_FLOW, sizeof(f));
+    out.flow = (long long)f;
+    return ISX_OK;
+}
+
+struct GcCall {
+    std::vector<isx_mat> img, msk;       // device views
+    std::vector<MatStage*> out;          // host masks to copy back
+};
+
+int gc_check_args(int n, const isx_mat* images, const isx_mat* masks, int cost_type, const char* who) {
+    ISX_CHECK_ARG(cost_type == ISX_GC_COST_COLOR || cost_type == ISX_GC_COST_COLOR_GRAD, ISX_ERR_INVALID, "%s: cost_type %d", who, cost_type);
+    ISX_CHECK_ARG(cost_type == ISX_GC_COST_COLOR, ISX_ERR_UNSUPPORTED, "%s: COST_COLOR_GRAD is not implemented (its capacities are not integers)", who);
+    for (int i = 0; i < n; ++i) {
+        ISX_TRY(check_mat(&images[i], who));
+        ISX_TRY(check_mat(&masks[i], who));
+        ISX_CHECK_ARG(images[i].type == images[0].type && (images[i].type == ISX_32FC3 || images[i].type == ISX_8UC3), ISX_ERR_TYPE,
+                      "%s: all images must be CV_32FC3 or all CV_8UC3 (image %d is %s)", who, i, type_name(images[i].type));
+        ISX_CHECK_ARG(masks[i].type == ISX_8UC1, ISX_ERR_TYPE, "%s: mask %d is %s (CV_8U)", who, i, type_name(masks[i].type));
+        ISX_CHECK_ARG(masks[i].rows == images[i].rows && masks[i].cols == images[i].cols, ISX_ERR_SIZE,
+                      "%s: mask %d is %dx%d, its image %dx%d", who, i, masks[i].cols, masks[i].rows, images[i].cols, images[i].rows);
+    }
+    return ISX_OK;
+}
+
+// capture check, device views of every image and mask, and the CV_32FC3 value check - all before the first pair writes
+int gc_prepare(GcScratch& s, int n, const isx_mat* images, isx_mat* masks, int device, hipStream_t st, GcCall& c, const char* who) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    ISX_HIP(hipStreamIsCapturing(st, &cs));
+    ISX_CHECK_ARG(cs == hipStreamCaptureStatusNone, ISX_ERR_STATE, "%s: the stream is capturing (the finder reads counters back to the host)", who);
+    if (s.device != device) { s.graph.release(); s.cert.release(); s.img.clear(); s.msk.clear(); s.device = device; }
+    if ((int)s.img.size() < n) { s.img.resize(n); s.msk.resize(n); }
+    if (!s.pin) {
+        void* p = nullptr;
+        ISX_HIP(hipHostMalloc(&p, 64 * sizeof(int), hipHostMallocDefault));
+        s.pin = (int*)p;
+    }
+    c.img.assign(images, images + n);
+    c.msk.assign(masks, masks + n);
+    for (int i = 0; i < n; ++i) {
+        if (images[i].device < 0) {
+            if (!s.img[i]) s.img[i].reset(new MatStage());
+            ISX_TRY(s.img[i]->use_in(&images[i], st, who));
+            c.img[i] = s.img[i]->d;
+        }
+        if (masks[i].device < 0) {
+            if (!s.msk[i]) s.msk[i].reset(new MatStage());
+            ISX_TRY(s.msk[i]->use_in(&masks[i], st, who));
+            s.msk[i]->host = &masks[i];           // copied back by finish_out
+            c.msk[i] = s.msk[i]->d;
+            c.out.push_back(s.msk[i].get());
+        }
+    }
+    if (images[0].type == ISX_32FC3) {
+        ISX_TRY(s.graph.reserve(256));
+        int* flag = (int*)s.graph.p;
+        ISX_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
+        for (int i = 0; i < n; ++i)
+            ISX_LAUNCH("graphcut_check", (double)c.img[i].rows * c.img[i].cols * 12.0, st, k_gc_check_f32, gc_grid(c.img[i].cols, c.img[i].rows), dim3(GC_NT), 0,
+                       (const unsigned char*)c.img[i].data, c.img[i].step, c.img[i].rows, c.img[i].cols, flag);
+        ISX_HIP(hipMemcpyAsync(s.pin, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+        ISX_HIP(hipStreamSynchronize(st));
+        ISX_CHECK_ARG(s.pin[0] == 0, ISX_ERR_UNSUPPORTED, "%s: a CV_32FC3 value is not an integer in [0, 255] (the capacities would not be exact)", who);
+    }
+    return ISX_OK;
+}
+
+bool gc_geom(const isx_mat& i1, const isx_mat& i2, isx_mat& m1, isx_mat& m2, const int tl1[2], const int tl2[2], GcGeom& G) {
+    const long long x0 = std::max(tl1[0], tl2[0]), y0 = std::max(tl1[1], tl2[1]);
+    const long long x1 = std::min((long long)tl1[0] + i1.cols, (long long)tl2[0] + i2.cols);
+    const long long y1 = std::min((long long)tl1[1] + i1.rows, (long long)tl2[1] + i2.rows);
+    if (!(x0 < x1 && y0 < y1)) return false;
+    G.i1 = (const unsigned char*)i1.data; G.s1 = i1.step;
+    G.i2 = (const unsigned char*)i2.data; G.s2 = i2.step;
+    G.m1 = (unsigned char*)m1.data; G.sm1 = m1.step;
+    G.m2 = (unsigned char*)m2.data; G.sm2 = m2.step;
+    G.r1 = i1.rows; G.c1 = i1.cols; G.r2 = i2.rows; G.c2 = i2.cols;
+    G.rw = (int)(x1 - x0); G.rh = (int)(y1 - y0);
+    G.hp = G.rh + 2 * GC_GAP; G.wp = G.rw + 2 * GC_GAP;
+    G.oy1 = (int)(y0 - tl1[1]) - GC_GAP; G.ox1 = (int)(x0 - tl1[0]) - GC_GAP;
+    G.oy2 = (int)(y0 - tl2[1]) - GC_GAP; G.ox2 = (int)(x0 - tl2[0]) - GC_GAP;
+    return true;
+}
+
+int gc_finish(GcCall& c, hipStream_t st) {
+    for (MatStage* m : c.out) ISX_TRY(m->finish_out(st));
+    return ISX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int isx_graphcut_seam_release(void) ISX_ENTRY {
+    clear_error();
+    GcScratch& s = gc_scratch();
+    s.graph.release();
+    s.cert.release();
+    s.img.clear();
+    s.msk.clear();
+    s.device = -1;
+    if (s.pin) { ISX_HIP(hipHostFree(s.pin)); s.pin = nullptr; }
+    return ISX_OK;
+} ISX_EXIT("isx_graphcut_seam_release")
+
+int isx_graphcut_seam_find(int num_images, const isx_mat* images, const int* corners_xy, isx_mat* masks, int cost_type, int device,
+                           void* hip_stream) ISX_ENTRY {
+    clear_error();
+    ISX_CHECK_ARG(num_images >= 0 && (num_images == 0 || (images && corners_xy && masks)), ISX_ERR_INVALID, "graphcut_seam_find: null argument");
+    ISX_TRY(gc_check_args(num_images, images, masks, cost_type, "graphcut_seam_find"));
+    if (num_images < 2) return ISX_OK;     // PairwiseSeamFinder::run visits no pair
+    ISX_HIP(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    GcScratch& s = gc_scratch();
+    GcCall c;
+    ISX_TRY(gc_prepare(s, num_images, images, masks, device, st, c, "graphcut_seam_find"));
+    const bool u8 = images[0].type == ISX_8UC3;
+    for (int i = 0; i + 1 < num_images; ++i)
+        for (int j = i + 1; j < num_images; ++j) {
+            GcGeom G{};
+            if (!gc_geom(c.img[i], c.img[j], c.msk[i], c.msk[j], corners_xy + 2 * i, corners_xy + 2 * j, G)) continue;
+            PairOut po;
+            const int rc = gc_solve_pair(s, G, u8, st, po, nullptr, nullptr);
+            if (rc != ISX_OK) {
+                (void)gc_finish(c, st);     // the pairs before this one keep their edits, host masks as device ones
+                return rc;
+            }
+        }
+    return gc_finish(c, st);
+} ISX_EXIT("isx_graphcut_seam_find")
+
+int isx_graphcut_seam_find_pair(const isx_mat* image1, const isx_mat* image2, const int* corners_xy, isx_mat* mask1, isx_mat* mask2,
+                                int cost_type, long long* flow, int* residuals, unsigned char* labels, long long cert_nodes, int* info,
+                                int device, void* hip_stream) ISX_ENTRY {
+    clear_error();
+    ISX_CHECK_ARG(image1 && image2 && corners_xy && mask1 && mask2, ISX_ERR_INVALID, "graphcut_seam_find_pair: null argument");
+    ISX_CHECK_ARG((residuals == nullptr) == (labels == nullptr), ISX_ERR_INVALID, "graphcut_seam_find_pair: residuals and labels go together");
+    const isx_mat im[2] = {*image1, *image2};
+    isx_mat mk[2] = {*mask1, *mask2};
+    ISX_TRY(gc_check_args(2, im, mk, cost_type, "graphcut_seam_find_pair"));
+    ISX_HIP(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    GcScratch& s = gc_scratch();
+    GcCall c;
+    ISX_TRY(gc_prepare(s, 2, im, mk, device, st, c, "graphcut_seam_find_pair"));   // host masks: copied back through mk, views of the same data
+    GcGeom G{};
+    PairOut po;
+    if (flow) *flow = 0;
+    if (!gc_geom(c.img[0], c.img[1], c.msk[0], c.msk[1], corners_xy, corners_xy + 2, G)) {
+        if (info) { info[0] = info[1] = info[2] = info[3] = 0; }
+        return ISX_OK;
+    }
+    const long long n = (long long)G.hp * G.wp;
+    ISX_CHECK_ARG(residuals == nullptr || cert_nodes >= n, ISX_ERR_SIZE, "graphcut_seam_find_pair: the certificate needs %lld nodes (%d x %d), %lld given",
+                  n, G.hp, G.wp, cert_nodes);
+    int* dres = nullptr;
+    unsigned char* dlab = nullptr;
+    if (residuals) {
+        const size_t rb = ((size_t)n * 6 * sizeof(int) + 255) & ~(size_t)255;
+        ISX_TRY(s.cert.reserve(rb + (size_t)n));
+        dres = (int*)s.cert.p;
+        dlab = (unsigned char*)s.cert.p + rb;
+    }
+    ISX_TRY(gc_solve_pair(s, G, im[0].type == ISX_8UC3, st, po, dres, dlab));
+    if (residuals) {
+        ISX_HIP(hipMemcpyAsync(residuals, dres, (size_t)n * 6 * sizeof(int), hipMemcpyDeviceToHost, st));
+        ISX_HIP(hipMemcpyAsync(labels, dlab, (size_t)n, hipMemcpyDeviceToHost, st));
+        ISX_HIP(hipStreamSynchronize(st));
+    }
+    if (flow) *flow = po.flow;
+    if (info) { info[0] = po.hp; info[1] = po.wp; info[2] = po.rounds; info[3] = po.launches; }
+    return gc_finish(c, st);
+} ISX_EXIT("isx_graphcut_seam_find_pair")
+
+}  // extern "C"

@@ -262,6 +262,24 @@ private:
     int device_;
 };
 
+// GraphCutSeamFinder(GraphCutSeamFinder::COST_COLOR) (W:257) and its find(images_warped_f, corners, masks_warped) (W:264): every pair's
+// max-flow on the GPU, the maximal minimum cut (isx_graphcut_seam_find).  src: CV_32FC3 tiles holding integers in [0, 255] or CV_8UC3;
+// masks: CV_8U, edited in place; host or device mats.
+class GraphCutSeamFinder {
+public:
+    enum CostType { COST_COLOR = ISX_GC_COST_COLOR, COST_COLOR_GRAD = ISX_GC_COST_COLOR_GRAD };
+    explicit GraphCutSeamFinder(int cost_type = COST_COLOR, int device = 0) : cost_type_(cost_type), device_(device) {}
+    void find(const std::vector<Mat>& src, const std::vector<Point>& corners, std::vector<Mat>& masks) {
+        if (src.size() != corners.size() || src.size() != masks.size()) throw Exception(ISX_ERR_INVALID, "find: src, corners and masks differ in length");
+        std::vector<isx_mat> im(src.size()), mk(src.size());
+        std::vector<int> c;
+        for (size_t i = 0; i < src.size(); ++i) { im[i] = *src[i].c(); mk[i] = *masks[i].c(); c.push_back(corners[i].x); c.push_back(corners[i].y); }
+        check(isx_graphcut_seam_find((int)src.size(), im.data(), c.data(), mk.data(), cost_type_, device_, nullptr));
+    }
+private:
+    int cost_type_, device_;
+};
+
 // cv::imread(path) (W:166): the decoder follows the file's signature, as OpenCV's does - "BM" bitmaps and JFIF / Exif JPEGs;
 // cv::imwrite(path, img) for .bmp and .jpg (W:155-156,315; "pano.jpg" S:1282)
 inline Mat imread(const char* path) {

@@ -1,0 +1,55 @@
+// imagestitch_cv_seam.hpp — the seam-finder half of the OpenCV adapter (include/imagestitch_cv.hpp has the warper and the blenders): a
+// subclass of OpenCV 3.4.2's cv::detail::SeamFinder over the C-ABI library, so that the W demo's
+//     seam_finder = new GraphCutSeamFinder(GraphCutSeamFinder::COST_COLOR);      // W:257
+//     seam_finder->find(images_warped_f, corners, masks_warped);                  // W:264
+// becomes  makePtr<isx_cv::HipGraphCutSeamFinder>()  and find runs every pair's max-flow on the MI355X (isx_graphcut_seam_find).  The cut
+// is the maximal minimum cut: where the minimum cut is not unique, OpenCV's Boykov-Kolmogorov search may return another one of the same cost
+// (DESIGN.md §8).  A header of its own, so that imagestitch_cv.hpp and the stub it is tested against stay as they were.
+//
+// Compiled inside the reference tree, where OpenCV 3.4.2 is installed; in this repository against tests/cpp/opencv_stub
+// (tests/cpp/graphcut_demo.cpp, run by tests/test_gpu_graphcut_seam.py).
+#ifndef IMAGESTITCH_CV_SEAM_HPP
+#define IMAGESTITCH_CV_SEAM_HPP
+
+#ifndef ISX_HAVE_OPENCV
+#define ISX_HAVE_OPENCV
+#endif
+#include <opencv2/core.hpp>
+#include <opencv2/stitching/detail/seam_finders.hpp>
+
+#include <vector>
+
+#include "imagestitch.hpp"
+
+namespace isx_cv {
+
+// cv::detail::GraphCutSeamFinder(cost_type)'s find over isx::GraphCutSeamFinder.  COST_COLOR only: COST_COLOR_GRAD throws
+// isx::Exception(ISX_ERR_UNSUPPORTED) from find, as does a CV_32FC3 value that is not an integer in [0, 255].
+class HipGraphCutSeamFinder : public cv::detail::SeamFinder {
+public:
+    explicit HipGraphCutSeamFinder(int cost_type = cv::detail::GraphCutSeamFinderBase::COST_COLOR, int device = 0) : f_(cost_type, device) {}
+    void find(const std::vector<cv::UMat>& src, const std::vector<cv::Point>& corners, std::vector<cv::UMat>& masks) override {
+        CV_Assert(src.size() == corners.size() && masks.size() == corners.size());
+        // the mapped Mat headers live to the end of this call (the unmap of an OpenCL-backed UMat happens in their destructors)
+        std::vector<cv::Mat> im, mk;
+        std::vector<isx::Mat> ii, mm;
+        std::vector<isx::Point> pts;
+        for (size_t i = 0; i < src.size(); ++i) {
+            im.push_back(src[i].getMat(cv::ACCESS_READ));
+            mk.push_back(masks[i].getMat(cv::ACCESS_RW));
+        }
+        for (size_t i = 0; i < src.size(); ++i) {
+            ii.push_back(isx::Mat(im[i]));
+            mm.push_back(isx::Mat(mk[i]));
+            pts.push_back(isx::Point(corners[i].x, corners[i].y));
+        }
+        f_.find(ii, pts, mm);
+    }
+
+private:
+    isx::GraphCutSeamFinder f_;
+};
+
+}  // namespace isx_cv
+
+#endif

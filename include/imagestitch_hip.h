@@ -408,6 +408,40 @@ int isx_dp_seam_find(int num_images, const isx_mat* images, const int* corners_x
  * leaks one finder (tens of MB at 4K) per thread.                                                                    */
 int isx_dp_seam_release(void);
 
+/* ---- the stock graph-cut seam finder of the W demo (W:257, W:264) ----------------------------------------------------------- */
+/* GraphCutSeamFinder::CostType */
+enum { ISX_GC_COST_COLOR = 0, ISX_GC_COST_COLOR_GRAD = 1 };
+/* seam_finder = new GraphCutSeamFinder(GraphCutSeamFinder::COST_COLOR) (W:257); seam_finder->find(images_warped_f, corners, masks_warped)
+ * (W:264), OpenCV 3.4.2's PairwiseSeamFinder + GraphCutSeamFinder::Impl restated (OpenCV parity unpinned): for every pair
+ * i < j (outer i, inner j) whose overlapRoi is not empty, on the masks as the earlier pairs left them, a max-flow over the padded overlap
+ * ((roi.h + 20) x (roi.w + 20) nodes) on the GPU, and the write-back over the roi.  The cut is the MAXIMAL source side of a maximum flow
+ * (the nodes that cannot reach the sink in its residual graph): unique, so the masks do not depend on the schedule.  Where the minimum cut
+ * is not unique OpenCV's Boykov-Kolmogorov search may choose another cut of the same cost.
+ * images: n mats, all CV_32FC3 (W:261: convertTo of the byte tiles) or all CV_8UC3, host or device; CV_32FC3 values must be integers in
+ * [0, 255] (then every capacity is an exact integer): any other value gives ISX_ERR_UNSUPPORTED before a mask is written.  masks: n CV_8UC1
+ * mats of the images' sizes, host or device, edited in place.  cost_type ISX_GC_COST_COLOR; ISX_GC_COST_COLOR_GRAD gives
+ * ISX_ERR_UNSUPPORTED.  Fewer than 2 images: nothing to do.  Synchronises hip_stream (it reads counters back every round), so a capturing
+ * stream gives ISX_ERR_STATE.  A pair whose max-flow does not finish within 4096 rounds (16 push-relabel sweeps and a global relabel
+ * each) gives ISX_ERR_UNSUPPORTED with that pair's masks untouched; the pairs before it keep their edits.                              */
+int isx_graphcut_seam_find(int num_images, const isx_mat* images, const int* corners_xy, isx_mat* masks, int cost_type, int device,
+                           void* hip_stream);
+/* One pair (images 1 and 2 at corners_xy[0..1] and corners_xy[2..3]) as isx_graphcut_seam_find treats it, optionally returning a
+ * certificate of its maximum flow over the padded grid of rows x cols = info[0] x info[1] nodes (row-major, node (y, x) = grid row y,
+ * column x; grid (10, 10) is the roi's top-left):
+ *   flow       (may be NULL) the maximum flow value (without OpenCV's constant 10000 per node that has both masks)
+ *   residuals  (may be NULL, with labels) cert_nodes >= rows * cols records of 6 int32 per node: the residual capacities of its edges
+ *              to the right, to the left, down, up (0 where the grid ends), of the source's link to it and of its link to the sink;
+ *              every edge of weight w has r(u -> v) + r(v -> u) = 2 w
+ *   labels     rows * cols bytes: 1 = source side (the maximal one), 0 = sink side
+ *   info       (may be NULL) 4 ints: rows, cols, push-relabel rounds, kernel launches; all 0 when the tiles do not overlap
+ * ISX_ERR_SIZE when cert_nodes is too small (nothing written). */
+int isx_graphcut_seam_find_pair(const isx_mat* image1, const isx_mat* image2, const int* corners_xy, isx_mat* mask1, isx_mat* mask2,
+                                int cost_type, long long* flow, int* residuals, unsigned char* labels, long long cert_nodes, int* info,
+                                int device, void* hip_stream);
+/* The graph-cut finder keeps its graph (28 B per padded node on the device), counters and staged host mats per calling thread between
+ * calls; this returns them.  PER THREAD and not freed at thread exit, as for isx_dp_seam_release.                                      */
+int isx_graphcut_seam_release(void);
+
 /* ---- on-disk format either side of the path: .bmp (W:166 imread, W:155-156,315 imwrite) ----------- */
 /* Reading: uncompressed Windows bitmaps only (the reference's inputs and committed artefacts are BMPs).
  * isx_bmp_read = cv::imread(path) with IMREAD_COLOR: `out` is a CV_8UC3 mat (host or device) of the size
