@@ -13,12 +13,19 @@ work is fixed.  Mpix = source-tile pixels processed.  Rank 0 prints one JSON lin
 
 Before the W warm-up steps the same step runs untimed for --preflight-ms (default 60 ms; the count is reported as preflight.steps): after the
 idle seconds of the set-up the GPU's clock takes ~70 steps to settle and a 20-step region would end inside that ramp
-(profiles/round4_clock_ramp.txt).  preflight.after_idle_Mpix_s is the rate of the same W + K steps started on an idle GPU, measured after
-the headline region; --preflight-ms 0 switches the pre-flight off.
+(profiles/round4_clock_ramp.txt).  --preflight-ms 0 switches the pre-flight off.
 
-At N = 1 the line also carries `dropin`: the same workload as a caller written against cv::detail::RotationWarper /
-cv::detail::Blender gets it - every warp returns its corner to the host (W:160), feed() consumes its inputs (W:305-308) -
-with device mats and with host (cv::Mat-like, PCIe-inclusive) mats; timed after the headline region, never part of `value`.
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, --dump-outputs, the line.  The figures it carries beside
+`value` (roofline, step_hbm, kernels_ms_one_step) come from the warm-up's serialised step and the timed region themselves.  --full adds the
+legs that take runs of their own, all timed after the headline region and never part of `value`:
+  - roofline.traffic measured live (two child runs under rocprofv3 --pmc; a plain run reports the committed measurement);
+  - preflight.after_idle_Mpix_s: the same W + K steps started on an idle GPU; config.host_enqueue_ms_per_pair;
+  - N = 1: `two_steps_in_flight`, `dropin` (the same workload as a caller written against cv::detail::RotationWarper / cv::detail::Blender
+    gets it - every warp returns its corner to the host (W:160), feed() consumes its inputs (W:305-308) - with device mats and with host
+    (cv::Mat-like, PCIe-inclusive) mats) and `cpu_baseline` (the C oracle on the host's cores);
+  - N > 1: multi_gpu's legs (the K steps without the gathers, the gathers alone, the gather-to-root leg);
+  - --a13: the per-launch profile of the same calls (kernels_ms_one_step, roofline).
+--no-live-traffic, --no-dropin and --no-cpu-baseline leave single legs out of a --full run.
 
 --dump-outputs DIR: after the timed steps, what the last timed step handed its caller is written as float32 .npy files under DIR (see
 dump_outputs); the inputs are seeded, so two builds run with the same arguments can be compared output for output.
@@ -75,7 +82,7 @@ def measured_traffic(kernel, args, live=True):
     measured_traffic.all_kernels = None
     """HBM (fabric) bytes per launch of `kernel` from rocprofv3's PMC counters, (2 x FETCH_SIZE + WRITE_SIZE) KiB with FETCH and WRITE in
     separate passes (tools/measure_traffic.py; the factor 2 is calibrated for the kernels' access shapes, profiles/round2_fetch_calib.txt).
-    live: collected NOW, by two short child runs of this command under `rocprofv3 --kernel-trace --pmc X` (about 30 s); when rocprofv3 is
+    live (--full): collected NOW, by two short child runs of this command under `rocprofv3 --kernel-trace --pmc X` (about 30 s); when rocprofv3 is
     missing or a pass fails, the committed measurement of the same command (profiles/round6_traffic.json) is returned instead.
     Returns (bytes or None, source)."""
     import shutil
@@ -102,7 +109,7 @@ def measured_traffic(kernel, args, live=True):
         if d.get("bench_args", []) != [] or args.precision != "f32" or args.bands != 5 or args.tiles != 2 or args.width != 3840 or args.kind != "cylindrical" or args.tile_type != "u8":
             return None, "no PMC measurement of this command"
         return d["kernels"][kernel]["traffic_bytes"], ("profiles/round6_traffic.json: the committed PMC measurement of this command (tools/measure_traffic.py; "
-                                                      "rocprofv3 was not usable in this run)")
+                                                      "not collected live in this run: that needs --full and a usable rocprofv3)")
     except Exception:
         return None, "no PMC measurement of this command"
 
@@ -394,27 +401,29 @@ def a13_line(args):
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
     dumped = dump_outputs(args.dump_outputs, [("a13", [("pano", pano), ("seam", seam)])]) if args.dump_outputs else None
-    # ... and the same K calls again with every launch bracketed by HIP events (outside the timed region: bracketing serialises the launches)
-    lib.isx_profile_enable(1); lib.isx_profile_filter(None); lib.isx_profile_sample(1); lib.isx_profile_reset()
-    for _ in range(args.steps):
-        call()
-    gc.enable()
-    ent = _lib.profile_entries()
-    lib.isx_profile_enable(0)
-    per = {k: {"ms": round(v["ms"] / args.steps, 4), "alg_MB": round(v["alg_bytes"] / args.steps / 1e6, 2),
-               **({"frac": round(v["alg_bytes"] / v["ms"] / 1e6 / HBM_PEAK_GBS, 3)} if v["ms"] > 0 and v["alg_bytes"] > 0 else {})} for k, v in ent.items()}
-    dom = max(ent.items(), key=lambda kv: kv[1]["ms"])[0]
-    e = ent[dom]
-    ach = e["alg_bytes"] / e["ms"] / 1e6
     mpix = (t1.shape[0] * t1.shape[1] + t2.shape[0] * t2.shape[1]) / 1e6
     out = {"metric": "Mpix/s linear-ramp pair blend (B:141-717) @4K pair", "value": round(mpix / dt, 1), "unit": "Mpix/s", "n_gpus": 1, "steps": args.steps,
            "warmup": args.warmup, "ms_per_step": round(dt * 1e3, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
            "config": {"workload": "A13: 2 warped %dx%d / %dx%d CV_32FC3 tiles of the config-2 pair (overlap %d columns) -> %dx%d panorama, one call per step, the seam returned to the host"
-                                  % (t1.shape[1], t1.shape[0], t2.shape[1], t2.shape[0], x1 + t1.shape[1] - x2, pc.value, pr.value), "warped_Mpix": round(mpix, 3)},
-           "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None,
-                        "avg_launch_ms": round(e["ms"] / e["launches"], 5), "alg_bytes_per_launch": int(e["alg_bytes"] / e["launches"]), "launches": e["launches"]},
-           "kernels_ms_one_step": per, "kernel_sum_ms": round(sum(v["ms"] for v in per.values()), 4),
-           "seam_walk_ms": round(sum(v["ms"] for k, v in per.items() if k.startswith("lin_seam")), 4)}
+                                  % (t1.shape[1], t1.shape[0], t2.shape[1], t2.shape[0], x1 + t1.shape[1] - x2, pc.value, pr.value), "warped_Mpix": round(mpix, 3)}}
+    if args.full:
+        # ... and the same K calls again with every launch bracketed by HIP events (outside the timed region: bracketing serialises the launches)
+        lib.isx_profile_enable(1); lib.isx_profile_filter(None); lib.isx_profile_sample(1); lib.isx_profile_reset()
+        for _ in range(args.steps):
+            call()
+        ent = _lib.profile_entries()
+        lib.isx_profile_enable(0)
+        per = {k: {"ms": round(v["ms"] / args.steps, 4), "alg_MB": round(v["alg_bytes"] / args.steps / 1e6, 2),
+                   **({"frac": round(v["alg_bytes"] / v["ms"] / 1e6 / HBM_PEAK_GBS, 3)} if v["ms"] > 0 and v["alg_bytes"] > 0 else {})} for k, v in ent.items()}
+        dom = max(ent.items(), key=lambda kv: kv[1]["ms"])[0]
+        e = ent[dom]
+        ach = e["alg_bytes"] / e["ms"] / 1e6
+        out.update({"roofline": {"bound": "hbm", "kernel": dom, "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4),
+                                 "traffic": None, "avg_launch_ms": round(e["ms"] / e["launches"], 5), "alg_bytes_per_launch": int(e["alg_bytes"] / e["launches"]),
+                                 "launches": e["launches"]},
+                    "kernels_ms_one_step": per, "kernel_sum_ms": round(sum(v["ms"] for v in per.values()), 4),
+                    "seam_walk_ms": round(sum(v["ms"] for k, v in per.items() if k.startswith("lin_seam")), 4)})
+    gc.enable()
     if dumped:
         out["dump_outputs"] = dumped
     print(json.dumps(out), flush=True)
@@ -450,7 +459,11 @@ def main():
     ap.add_argument("--pairs", type=int, default=None, help="4K pairs per GPU per step (default: 1 with one GPU = BASELINE config 2, "
                                                            "4 with N > 1 = config 4's 8 tiles per GPU)")
     ap.add_argument("--tiles", type=int, default=2, help="tiles per mosaic (2 = a pair; 8 = BASELINE config 5's row of 8, yaw step 2 * --yaw)")
-    ap.add_argument("--no-dropin", action="store_true", help="skip the drop-in (reference call sequence) legs after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline region, also run the legs that take runs of their own: live PMC traffic, the idle-start rate, the "
+                         "enqueue time, two steps in flight, the drop-in legs, the CPU baseline, the N > 1 legs, the --a13 profile (see the "
+                         "module docstring); off: set-up, warm-up, the timed steps, --dump-outputs and the line only")
+    ap.add_argument("--no-dropin", action="store_true", help="--full: skip the drop-in (reference call sequence) legs after the timed region")
     ap.add_argument("--bands", type=int, default=5)
     ap.add_argument("--precision", default="f32", choices=["i16", "f32", "f16acc32"])
     ap.add_argument("--width", type=int, default=3840)
@@ -459,9 +472,9 @@ def main():
     ap.add_argument("--yaw", type=float, default=0.36, help="the pair's cameras are rotated by -/+ yaw about the vertical axis")
     ap.add_argument("--kind", default="cylindrical", choices=["cylindrical", "spherical"],
                     help="spherical = BASELINE config 5's projector (its ROI: a border scan on the device + pole tests; planned and synchronous forms as for the cylinder)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline leg")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="do not collect roofline.traffic now (two child runs under rocprofv3 --pmc, ~30 s); report the committed measurement")
+                    help="--full: do not collect roofline.traffic now (two child runs under rocprofv3 --pmc, ~30 s); report the committed measurement")
     ap.add_argument("--graph", action="store_true", help="capture each pair's planned step into a hipGraph and replay it (BASELINE config 3)")
     ap.add_argument("--streams", type=int, default=None,
                     help="HIP streams the pairs of a step are spread over (default: 1 for one pair, min(pairs, 4) otherwise): independent pairs on "
@@ -855,18 +868,20 @@ def main():
     lib.isx_profile_sample(1)
     for p in pairs:
         p.check_plan()   # raises if any planned step saw a ROI that differs from the plan
-    # host time to ENQUEUE one step (the queue empty when it starts, nothing waited for): what the launch chain costs the caller's thread
-    enq = []
-    for _ in range(5):
+    # --full: host time to ENQUEUE one step (the queue empty when it starts, nothing waited for): what the launch chain costs the caller's thread
+    host_enqueue_ms = None
+    if args.full:
+        enq = []
+        for _ in range(5):
+            fence()
+            te = time.perf_counter()
+            step()
+            enq.append(time.perf_counter() - te)
         fence()
-        te = time.perf_counter()
-        step()
-        enq.append(time.perf_counter() - te)
-    fence()
-    host_enqueue_ms = sorted(enq)[len(enq) // 2] * 1e3
-    # the same W + K steps started on an idle GPU (what the line would read without the pre-flight): reported beside `value`
+        host_enqueue_ms = sorted(enq)[len(enq) // 2] * 1e3
+    # --full: the same W + K steps started on an idle GPU (what the line would read without the pre-flight): reported beside `value`
     after_idle = None
-    if preflight_steps and not use_dist:
+    if preflight_steps and not use_dist and args.full:
         time.sleep(0.4)
         gc.disable()
         for _ in range(args.warmup):
@@ -879,8 +894,9 @@ def main():
         after_idle = time.perf_counter() - ti
         gc.enable()
     split = None
-    if use_dist:
-        # outside the timed region ("report Mpix/s with and without the gather"): the same K steps
+    dt_c = dt_g = dt_r = 0.0
+    if use_dist and args.full:
+        # --full, outside the timed region ("report Mpix/s with and without the gather"): the same K steps
         # without the all-gather, then K all-gathers alone, so that the scaling file shows which of the two bounds N > 1
         fence()
         t1 = time.perf_counter()
@@ -925,10 +941,13 @@ def main():
                 print("bench.py: the gather-to-root leg did not run: %r" % (e,), file=sys.stderr)
                 dt_r = 0.0
             args.gather = keep
+    if use_dist:
+        # the headline is the slowest rank's time
         t = torch.tensor([dt, dt_c, dt_g, dt_r], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt, dt_c, dt_g, dt_r = (float(v) for v in t.tolist())
-        split = (dt_c, dt_g, int(send[0].numel()), dt_r)
+        if args.full:
+            split = (dt_c, dt_g, int(send[0].numel()), dt_r)
     gather_check = None
     if use_dist and args.check_gather:
         # One more step; then every chunk this rank RECEIVED (world x pairs of them) against the same mosaic stitched here, serially, from the
@@ -994,9 +1013,9 @@ def main():
             avg_ms = e["ms"] / e["launches"]
             bytes_per_launch = e["alg_bytes"] / e["launches"]
             ach = bytes_per_launch / (avg_ms * 1e-3) / 1e9
-            # collected live only in the full default line (what the driver runs), never inside a run that is itself being profiled
+            # collected live only in the --full default line, never inside a run that is itself being profiled
             profiled = any("rocprof" in os.environ.get(v, "") for v in ("LD_PRELOAD", "ROCP_TOOL_LIBRARIES", "ROCPROFILER_REGISTER_FORCE_LOAD"))
-            live_ok = (world == 1 and args.pairs == 1 and not args.graph and not args.no_live_traffic and not args.no_dropin
+            live_ok = (args.full and world == 1 and args.pairs == 1 and not args.graph and not args.no_live_traffic and not args.no_dropin
                        and not args.no_cpu_baseline and not profiled)
             traffic, traffic_source = measured_traffic(dominant, args, live=live_ok)
             roof = {"bound": "hbm", "kernel": dominant, "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -1065,7 +1084,8 @@ def main():
                     "tiles_this_rank": pairs[0].active} if strips else {}),
                 "pairs_per_gpu": args.pairs, "tile_type": args.tile_type,
                 # which side of the fast kernels' limits this run was on (isx_blender_last_path): deferred | eager cycle, the kernel of the last collapse step
-                "path": dict(pairs[0].blender.last_path(), level1=pairs[0].blender.level1_format()), "streams": len(pstreams), "graph_branches": graph_branches, "batched_blend": bool(args.batch), "host_enqueue_ms_per_pair": round(host_enqueue_ms / args.pairs, 4), "bands": args.bands, "precision": args.precision, "hipgraph": bool(args.graph), "cycle": args.cycle,
+                "path": dict(pairs[0].blender.last_path(), level1=pairs[0].blender.level1_format()), "streams": len(pstreams), "graph_branches": graph_branches, "batched_blend": bool(args.batch),
+                **({"host_enqueue_ms_per_pair": round(host_enqueue_ms / args.pairs, 4)} if host_enqueue_ms is not None else {}), "bands": args.bands, "precision": args.precision, "hipgraph": bool(args.graph), "cycle": args.cycle,
                 "tile_base_px": bm["tile_base_px"], "mosaic_px": bm["mosaic_px"], "warped_px": bm["warped_px"]},
             # SURVEY §8(d)'s work model of a pair (every pyramid level materialised once, destination pyramid read-modify-written): a
             # normalisation of the step time, NOT bytes this build moves - the deferred cycle never moves most of them
@@ -1102,7 +1122,10 @@ def main():
                                 **({"gather_check": gather_check} if gather_check is not None else {}),
                                 "note": "value = steps with the gathers overlapped with the blends that follow them; the two legs here are timed after "
                                         "it, each bracketed like the timed region; gather_bus_GBs = bytes every rank receives / gather time"}
-        if world == 1 and args.pairs == 1 and not args.graph and not args.no_dropin:
+        elif use_dist:      # a plain run: what ran and, when asked for, --check-gather's verdict; the legs above need --full
+            out["multi_gpu"] = {"rccl_ranks": dist.get_world_size(), "send_bytes_per_rank": int(send[0].numel()), "gather": args.gather,
+                                "gather_backend": args.gather_backend, **({"gather_check": gather_check} if gather_check is not None else {})}
+        if args.full and world == 1 and args.pairs == 1 and not args.graph and not args.no_dropin:
             # The same workload with TWO steps in flight: a second stitcher (own buffers, own stream) takes every other step, so one
             # step's launch-latency-bound small pyramid levels run under the other's large kernels.  Identical mosaics; the latency of
             # a step is unchanged, the throughput is what a stream of frames sees.  Reported beside `value`, never as `value`: in the
@@ -1123,11 +1146,11 @@ def main():
             same = bool(torch.equal(p2.out, pairs[0].out))
             out["two_steps_in_flight"] = {"ms_per_step": round(dt2 * 1e3, 4), "Mpix_s": round(NT * W * H / 1e6 / dt2, 1), "identical_mosaics": same}
             del p2, both
-        if world == 1 and not args.no_dropin:
+        if args.full and world == 1 and not args.no_dropin:
             for p in pairs:
                 del p
             out["dropin"] = dropin_legs(args, K, Rs, host_imgs0, dev, {"f32": _lib.PREC_F32, "i16": _lib.PREC_I16})
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(W, H, F, args.bands, prec, args.kind, NT, args.yaw)
         # RCCL writes a banner (ROCm version, host, library path) through C stdio, which a pipe would deliver AFTER this line at exit:
         # push it out first, so that the JSON line is the last line of rank 0's output

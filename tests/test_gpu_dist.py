@@ -320,7 +320,7 @@ def test_bench_walks_its_n2_path_on_one_gpu(gpu, tmp_path, backend, gather, shar
     # --standalone: the launcher's store binds a port itself and hands it to the ranks (a port picked here may be taken before it is bound)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--standalone",
            os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--pairs", "2", "--width", "1280", "--height", "720", "--focal", "1000",
-           "--gather-backend", backend, "--gather", gather, "--no-cpu-baseline", "--no-dropin", "--no-live-traffic"]
+           "--gather-backend", backend, "--gather", gather, "--full", "--no-cpu-baseline", "--no-dropin", "--no-live-traffic"]
     if shard == "strips":      # ONE panorama of 6 tiles per step, cut into two column strips (strong scaling)
         cmd += ["--shard", "strips", "--tiles", "6", "--yaw", "0.275"]
     out = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
@@ -355,7 +355,7 @@ def test_bench_walks_its_n8_path_on_one_gpu(gpu, tmp_path, backend, gather, shar
     # --standalone: the launcher's store binds a port itself and hands it to the ranks (a port picked here may be taken before it is bound)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--standalone",
            os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "2", "--preflight-ms", "0",
-           "--gather-backend", backend, "--gather", gather, "--check-gather", "--no-cpu-baseline", "--no-dropin", "--no-live-traffic"]
+           "--gather-backend", backend, "--gather", gather, "--check-gather", "--full", "--no-cpu-baseline", "--no-dropin", "--no-live-traffic"]
     if shard == "strips":      # ONE panorama of 64 tiles (config 4's tile count) per step, cut into `world` column strips (strong scaling)
         cmd += ["--shard", "strips", "--tiles", "64", "--pairs", "1", "--width", "320", "--height", "180", "--focal", "800", "--yaw", "0.045", "--bands", "3"]
     else:                      # config 4's 32 pairs in all

@@ -6,19 +6,19 @@ TAG=${1:-round6}; FUZZ=${2:-600}
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/$TAG; mkdir -p $O
 line() { grep "^{" | tail -1; }
-# 1. HBM traffic per kernel (two PMC passes of their own), then the default line that reads it
+# 1. HBM traffic per kernel (two PMC passes of their own), then the --full default line that reads it
 python tools/measure_traffic.py $O/${TAG}_traffic.json > $O/traffic.log 2>&1
 cp $O/${TAG}_traffic.json profiles/round6_traffic.json 2>/dev/null      # (bench.py's fallback when rocprofv3 is not usable in a run)
-python bench.py --steps 20 --warmup 5 2>/dev/null | line > $O/${TAG}_bench_n1.json
+python bench.py --full --steps 20 --warmup 5 2>/dev/null | line > $O/${TAG}_bench_n1.json
 # 2. the same command under the kernel tracer
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-dropin 2>/dev/null | line > $O/${TAG}_bench_under_rocprof.json
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-dropin 2>/dev/null | line > $O/${TAG}_bench_under_rocprof.json
 cp $(ls $O/trace/*/*kernel_stats.csv | head -1) $O/${TAG}_bench_kernel_stats.csv
 # 3. per-kernel VALU utilisation / occupancy
 bash tools/pmc_kernels.sh 1 $TAG/pmc_f32 > $O/${TAG}_pmc_f32.txt 2>&1
 bash tools/pmc_kernels.sh 0 $TAG/pmc_i16 > $O/${TAG}_pmc_i16.txt 2>&1
 # 4. variants
-b() { name=$1; shift; python bench.py --no-cpu-baseline --no-dropin "$@" 2>/dev/null | line > $O/${TAG}_bench_$name.json; }
+b() { name=$1; shift; python bench.py --full --no-cpu-baseline --no-dropin "$@" 2>/dev/null | line > $O/${TAG}_bench_$name.json; }
 b graph --graph
 b i16 --precision i16
 b f16 --precision f16acc32
@@ -40,15 +40,15 @@ b config4_forcedist_single --force-dist --pairs 4 --gather single
 b config4_forcedist_chunk_isx --force-dist --pairs 4 --gather chunk --gather-backend isx
 b config4_forcedist_chunk_p2p --force-dist --pairs 4 --gather chunk --gather-backend p2p
 b config5_ring8_8k --kind spherical --tiles 8 --width 7680 --height 4320 --focal 6000 --yaw 0.275 --bands 7 --precision f16acc32 --steps 5 --warmup 2
-ISX_ROLL_R23=0 python bench.py --no-cpu-baseline --no-dropin --kind spherical --tiles 8 --width 7680 --height 4320 --focal 6000 --yaw 0.275 --bands 7 --precision f16acc32 --steps 5 --warmup 2 2>/dev/null | line > $O/${TAG}_bench_config5_ring8_8k_ISX_ROLL_R23_0.json
+ISX_ROLL_R23=0 python bench.py --full --no-cpu-baseline --no-dropin --kind spherical --tiles 8 --width 7680 --height 4320 --focal 6000 --yaw 0.275 --bands 7 --precision f16acc32 --steps 5 --warmup 2 2>/dev/null | line > $O/${TAG}_bench_config5_ring8_8k_ISX_ROLL_R23_0.json
 b config5_8k_pair --kind spherical --width 7680 --height 4320 --focal 6000 --yaw 0.275 --bands 7 --precision f16acc32 --steps 10 --warmup 3
 # round 4: CV_16SC3 tiles (what the reference's feed() receives) on the planned step, both arithmetic modes; the probes of the round
 b s16_tiles_f32 --tile-type s16
 b s16_tiles_i16 --tile-type s16 --precision i16
 b steps100 --steps 100
 b no_preflight --preflight-ms 0
-ISX_TOP=0 python bench.py --no-cpu-baseline --no-dropin --steps 100 2>/dev/null | line > $O/${TAG}_bench_steps100_ISX_TOP0.json
-ISX_TOP2=0 python bench.py --no-cpu-baseline --no-dropin --steps 100 2>/dev/null | line > $O/${TAG}_bench_steps100_ISX_TOP2_0.json
+ISX_TOP=0 python bench.py --full --no-cpu-baseline --no-dropin --steps 100 2>/dev/null | line > $O/${TAG}_bench_steps100_ISX_TOP0.json
+ISX_TOP2=0 python bench.py --full --no-cpu-baseline --no-dropin --steps 100 2>/dev/null | line > $O/${TAG}_bench_steps100_ISX_TOP2_0.json
 python tools/probes/ramp_probe.py > $O/${TAG}_clock_ramp.txt 2>&1
 python tools/probes/fusion_probe.py > $O/${TAG}_n3_fusions.txt 2>&1
 python tools/probes/graph_probe.py > $O/${TAG}_graph_vs_eager.txt 2>&1
@@ -58,11 +58,11 @@ python tools/probes/literal_host_probe.py 1 > $O/${TAG}_literal_host_time.txt 2>
 for m in "1 5 literal" "0 5 literal" "1 5 sync"; do echo "== pipeline_probe $m" >> $O/${TAG}_literal_kernels.txt; python tools/pipeline_probe.py $m 2>&1 | tail -14 >> $O/${TAG}_literal_kernels.txt; done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 tools/probes/chain_probe.hip -o /tmp/chain_probe 2>/dev/null && timeout 60 /tmp/chain_probe > $O/${TAG}_chain_by_flags.txt 2>&1
 # round 5: A13 (the in-tree linear-ramp pair blend) on the record; the drop-in legs with the fused feed switched off / without narrowing; many tiles
-python bench.py --a13 --steps 50 2>/dev/null | line > $O/${TAG}_bench_a13.json
+python bench.py --full --a13 --steps 50 2>/dev/null | line > $O/${TAG}_bench_a13.json
 for v in "ISX_FEED_FUSE=0" "ISX_FEED_NARROW=0" "ISX_FEED_STRIP=0" "ISX_FEED_FUSE=1"; do for m in "1 5 literal" "0 5 literal" "1 5 sync"; do echo "== [$v] pipeline_probe $m" >> $O/${TAG}_feed_variants.txt; env $v python tools/pipeline_probe.py $m 2>&1 | tail -14 >> $O/${TAG}_feed_variants.txt; done; done
 bash tools/trace_many_tiles.sh ${TAG}_t64 --tiles 64 --focal 24000 --yaw 0.046 --steps 6 --warmup 2 > $O/${TAG}_many_tiles_trace.txt 2>&1
-ISX_TAB=0 python bench.py --no-cpu-baseline --no-dropin --tiles 64 --focal 24000 --yaw 0.046 --steps 6 --warmup 2 2>/dev/null | line > $O/${TAG}_bench_many_tiles_64_ISX_TAB_0.json
-ISX_TAB=0 python bench.py --no-cpu-baseline --no-dropin --tiles 24 --focal 9000 --yaw 0.12 --steps 6 --warmup 2 2>/dev/null | line > $O/${TAG}_bench_many_tiles_24_ISX_TAB_0.json
+ISX_TAB=0 python bench.py --full --no-cpu-baseline --no-dropin --tiles 64 --focal 24000 --yaw 0.046 --steps 6 --warmup 2 2>/dev/null | line > $O/${TAG}_bench_many_tiles_64_ISX_TAB_0.json
+ISX_TAB=0 python bench.py --full --no-cpu-baseline --no-dropin --tiles 24 --focal 9000 --yaw 0.12 --steps 6 --warmup 2 2>/dev/null | line > $O/${TAG}_bench_many_tiles_24_ISX_TAB_0.json
 b many_tiles_24 --tiles 24 --focal 9000 --yaw 0.12 --steps 6 --warmup 2
 b many_tiles_64 --tiles 64 --focal 24000 --yaw 0.046 --steps 6 --warmup 2
 # 4b. config 5 as ONE panorama in column strips: every rank's share at 2 / 4 / 8 ranks, each alone on this GPU (no gather)
