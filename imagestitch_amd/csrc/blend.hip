@@ -135,13 +135,6 @@ __device__ __forceinline__ Px<M> load_px_rgb(const LevelBuf& L, int x, int y) {
     } else return load_px<M, DST>(L, x, y);
 }
 
-// ISX_NT_G (A/B builds): bit 0 - the tiles' level-1 records (store_rgb12 / store_px_planar), bit 1 - every 16-byte level record (store_px) stored
-// non-temporally (written through as the kernel runs instead of left dirty in L2 for the end-of-kernel write-back)
-#ifndef ISX_NT_G
-#define ISX_NT_G 0
-#endif
-template <class T>
-__device__ __forceinline__ void st_g(T* p, const T& v, bool nt) { if (nt) __builtin_nontemporal_store(v, p); else *p = v; }
 template <int M, bool DST>
 __device__ __forceinline__ void store_px(const LevelBuf& L, int x, int y, const Px<M>& p) {
     const unsigned i = __umul24((unsigned)y, (unsigned)L.cols) + (unsigned)x;
@@ -153,8 +146,7 @@ __device__ __forceinline__ void store_px(const LevelBuf& L, int x, int y, const 
     } else if constexpr (M == M_F16 && !DST) {
         ((ushort4*)L.img)[i] = make_ushort4(f2h_bits(p.c0), f2h_bits(p.c1), f2h_bits(p.c2), f2h_bits(p.w));
     } else {
-        if (ISX_NT_G & 2) { typedef float f4v __attribute__((ext_vector_type(4))); __builtin_nontemporal_store(f4v{p.c0, p.c1, p.c2, p.w}, (f4v*)L.img + i); }
-        else ((float4*)L.img)[i] = make_float4(p.c0, p.c1, p.c2, p.w);
+        ((float4*)L.img)[i] = make_float4(p.c0, p.c1, p.c2, p.w);
     }
 }
 
@@ -209,12 +201,12 @@ __device__ __forceinline__ void store_rgb12(const LevelBuf& L, unsigned i, const
     } else if constexpr (Q8) {      // (exact: see Q8 above)
         const unsigned k0 = (unsigned)(p.c0 * 256.f), k1 = (unsigned)(p.c1 * 256.f), k2 = (unsigned)(p.c2 * 256.f);
         char* q = (char*)L.img + (size_t)i * 6u;
-        st_g((u32_rec2*)q, (u32_rec2)(k0 | (k1 << 16)), (ISX_NT_G & 1) != 0);
-        st_g((unsigned short*)(q + 4), (unsigned short)k2, (ISX_NT_G & 1) != 0);
+        *(u32_rec2*)q = (u32_rec2)(k0 | (k1 << 16));
+        *(unsigned short*)(q + 4) = (unsigned short)k2;
     } else {
         u32x3_rec v;
         v.x = __float_as_uint(p.c0); v.y = __float_as_uint(p.c1); v.z = __float_as_uint(p.c2);
-        st_g((u32x3_rec*)((char*)L.img + (size_t)i * 12u), v, (ISX_NT_G & 1) != 0);
+        *(u32x3_rec*)((char*)L.img + (size_t)i * 12u) = v;
     }
 }
 // A tile level that is planar or not - known only when the kernel runs (L.wgt != nullptr, uniform) - read WITHOUT a branch: the image channels as one
@@ -245,7 +237,7 @@ __device__ __forceinline__ void store_px_planar(const LevelBuf& L, int x, int y,
     static_assert(M == M_F32 || M == M_I16, "planar tile levels: 16-byte register records only");
     const unsigned i = __umul24((unsigned)y, (unsigned)L.cols) + (unsigned)x;
     store_rgb12<M, Q8>(L, i, p);
-    st_g(&L.wgt[i], p.w, (ISX_NT_G & 1) != 0);
+    L.wgt[i] = p.w;
 }
 
 // level-0 pixel of the tile pyramid at padded coordinates (x, y) in [0,width) x [0,height)
@@ -1106,20 +1098,6 @@ __device__ __forceinline__ Px<M> top_px(const TS& ts, int tb, int te, int x, int
 // stored as level k-1 of the collapsed pyramid.
 // TOP: this is the first collapse step (k = L): out_L is not read from memory but gathered while its coarse tile is
 // staged (top_px), so the top level of the collapsed pyramid is never materialised and its launch disappears.
-// Optional instrumentation (-DISX_PHASE_TIMING, tools/phase_probe.sh): s_memtime stamps at the phase boundaries of the last
-// collapse step, summed per wave in registers and flushed with one set of atomics at exit (spread over 1024 slots) - the
-// measurement that showed a wave spending half its life getting its loads issued.  Compiles to nothing otherwise.
-#ifdef ISX_PHASE_TIMING
-__device__ unsigned long long g_phase[1024][12];
-#define PT_DECL unsigned long long ph__[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long tprev__ = __builtin_amdgcn_s_memtime()
-#define PT(k) do { if (FINE0) { const unsigned long long now__ = __builtin_amdgcn_s_memtime(); ph__[k] += now__ - tprev__; tprev__ = now__; } } while (0)
-#define PT_FLUSH do { if (FINE0 && (threadIdx.x & 63) == 0) { const int slot__ = (blockIdx.x * 4 + (threadIdx.x >> 6) + blockIdx.y * 37) & 1023; \
-        for (int k__ = 0; k__ < 11; ++k__) atomicAdd(&g_phase[slot__][k__], ph__[k__]); atomicAdd(&g_phase[slot__][11], 1ull); } } while (0)
-#else
-#define PT_DECL do { } while (0)
-#define PT(k) do { } while (0)
-#define PT_FLUSH do { } while (0)
-#endif
 // The tiles [tb, te) of ts are those of ONE mosaic (all of them in a single blend; one mosaic's share in a batched launch, see
 // BatchOut): the body of a collapse step for the block (blockIdx.x, blockIdx.y) of that mosaic.
 template <int M, int SK, bool FINE0, bool TOP, class TS>
@@ -1148,7 +1126,6 @@ __device__ __forceinline__ void collapse_gather_body(const TS& ts, int tb, int t
     // (a TileTab: the tiles whose columns meet the block's, widened by the one coarse column the staged halo of the first step's gathered top
     // level reaches - top_px looks tiles up on the block's coarse columns cx0 - 1 .. cx0 + WAVE; a TileSet: all tiles, as given)
     tile_range(ts, 2 * cx0 - (TOP ? 2 : 0), 2 * cx0 + 2 * WAVE + (TOP ? 2 : 0), tb, te);
-    PT_DECL;
     // float work types: the accumulators and every stencil operation on (b, g) / (r, -) register pairs (packed fp32, see pyr_up_2x2_pk)
     constexpr bool PK = M != M_I16;
     WT acc[2][2][3];
@@ -1187,7 +1164,6 @@ __device__ __forceinline__ void collapse_gather_body(const TS& ts, int tb, int t
                 mine[s] = touch[s] & ((unsigned)lcx < (unsigned)ccols) & ((unsigned)lcy < (unsigned)crows);
             }
         }
-        PT(t0 == tb ? 0 : 4);    // descriptors
         // A round none of whose tiles reaches this block is skipped altogether (block-uniform: no staging, no barrier) unless it is the
         // one that stages out_k - with two tiles side by side that is the first round of every block right of the overlap.
         {
@@ -1237,7 +1213,6 @@ __device__ __forceinline__ void collapse_gather_body(const TS& ts, int tb, int t
                 }
             }
         }
-        PT(t0 == tb ? 1 : 5);    // coarse tiles issued
         // Wave-level tier (FINE0, CV_8UC3 tiles): when EVERY lane of the wave owns pixels of the tile and both of its rows' windows lie
         // inside the tile's buffer - true for all waves but those on a tile's rim - the wave takes a path without a single per-lane
         // branch: the per-pixel form below spends as many scalar instructions on exec-mask bookkeeping (343 per wave against 547
@@ -1308,9 +1283,7 @@ __device__ __forceinline__ void collapse_gather_body(const TS& ts, int tb, int t
                 }
             }
         }
-        PT(t0 == tb ? 2 : 6);    // fine pixels issued
         __syncthreads();
-        PT(t0 == tb ? 3 : 7);    // memory + barrier wait
 #pragma unroll
         for (int s = 0; s < G; ++s) {
             const int t = t0 + s;
@@ -1365,10 +1338,9 @@ __device__ __forceinline__ void collapse_gather_body(const TS& ts, int tb, int t
                     accw[dy][dx] = accw[dy][dx] + g.w;
                 }
         }
-        PT(t0 == tb ? 8 : 9);    // decode + pyrUp + accumulate
     }
     const int cx = cx0 + lane, cy = cy0 + wv;
-    if (cx >= coarse_out.cols || cy >= coarse_out.rows) { PT_FLUSH; return; }
+    if (cx >= coarse_out.cols || cy >= coarse_out.rows) return;
     // Blends of CV_8UC3 / CV_16SC3 tiles in the last step: every Laplacian is an integer minus a multiple of 2^-30 (a pyrUp of fp32 or
     // fp16 levels of integer images), every weight a multiple of 2^-8 / 255 or zero, so a normalised numerator is zero or far above
     // 2^-103 and far below 2^31: the shared-reciprocal division (isx_device.hpp) and the clamp-first conversions are exact.
@@ -1440,13 +1412,11 @@ __device__ __forceinline__ void collapse_gather_body(const TS& ts, int tb, int t
             } else { store_px<M, OUT_DST>(fine_out, 2 * cx, fy, dd[0]); store_px<M, OUT_DST>(fine_out, 2 * cx + 1, fy, dd[1]); }
     }
     }
-    PT(10);                     // epilogue: normalise, pyrUp of out, convert, stores issued
-    PT_FLUSH;
 }
 
 
 #ifndef ISX_GATHER_LEVEL_WPE
-#define ISX_GATHER_LEVEL_WPE 3      // waves per SIMD the level steps of k_collapse_gather are compiled for (re-measured in round 6: tools/probes/retune_round6.sh)
+#define ISX_GATHER_LEVEL_WPE 3      // waves per SIMD the level steps of k_collapse_gather are compiled for (re-measured in round 6)
 #endif
 // One mosaic per launch: its tiles are all of ts.
 template <int M, int SK, bool FINE0, bool TOP = false>
@@ -2078,15 +2048,11 @@ double covered_px(const isx_blender* b, int x, int y, int w, int h) {
 // k_feed_pd0 / k_feed_strip for (precision, tile type, level-1 layout, copy format)
 template <int M, int SK, int PLD, int CF>
 int launch_feed_pd0_v(const Src0& s0, const LevelBuf& g1, FeedCopy fc, dim3 grid, double bytes, hipStream_t st) {
-    // single-wave strips for the whole level (k_feed_strip) unless the tile is too small for its window scheme; ISX_FEED_STRIP=0: the block kernel
-    // (A/B runs), 4: four output rows per strip instead of two
-    static const int strip_no = [] { const char* e = getenv("ISX_FEED_STRIP"); return e ? atoi(e) : 2; }();
-    if (strip_no && s0.iend != 0u && s0.cols >= 2 && s0.rows >= 2 && s0.width >= 4 && s0.height >= 4) {
-        const int no = strip_no == 4 ? 4 : 2;
-        const unsigned n = (unsigned)cdiv(g1.cols, PD_OW) * (unsigned)cdiv(g1.rows, no);
+    // single-wave strips of two output rows for the whole level (k_feed_strip) unless the tile is too small for its window scheme
+    if (s0.iend != 0u && s0.cols >= 2 && s0.rows >= 2 && s0.width >= 4 && s0.height >= 4) {
+        const unsigned n = (unsigned)cdiv(g1.cols, PD_OW) * (unsigned)cdiv(g1.rows, 2);
         const unsigned nblk = (n + 7u) / 8u * 8u;         // (the XCD dealing walks whole groups of 8)
-        if (no == 4) ISX_LAUNCH("feed_strip", bytes, st, (k_feed_strip<M, SK, PLD, CF, 4>), dim3(nblk), dim3(64), 0, s0, g1, fc);
-        else ISX_LAUNCH("feed_strip", bytes, st, (k_feed_strip<M, SK, PLD, CF, 2>), dim3(nblk), dim3(64), 0, s0, g1, fc);
+        ISX_LAUNCH("feed_strip", bytes, st, (k_feed_strip<M, SK, PLD, CF>), dim3(nblk), dim3(64), 0, s0, g1, fc);
         return ISX_OK;
     }
     ISX_LAUNCH("feed_pd0", bytes, st, (k_feed_pd0<M, SK, PLD, CF>), grid, dim3(512), 0, s0, g1, fc);
@@ -2320,7 +2286,7 @@ int flush_deferred(isx_blender* b) {
 
 // The last collapse step as the rolling kernel (collapse_roll.inc) when its limits hold: coarse columns [cx_lo, cx_hi) of level 1 in
 // strips of RL_CW columns x R rows, one wave each, dealt to the XCDs in groups of two strip rows (xcd_block).  *done = false: the
-// caller launches k_collapse_gather instead.  ISX_ROLL=0 forces that (A/B runs); ISX_ROLL_R picks the strip height.
+// caller launches k_collapse_gather instead.  ISX_ROLL=0 forces that (A/B runs).
 // most tiles that reach any one strip of RL_CW x R coarse pixels: every tile covers a rectangle of strip indices; the deepest overlap of
 // those rectangles is found on the grid of their corners (at most 2 n x 2 n cells)
 inline int roll_max_tiles(const TileSet& ts, const LevelBuf& coarse, int cx_lo, int cx_hi, int R) {
@@ -2382,12 +2348,11 @@ template <int M, int SK, int R, int MAXT>
 int launch_collapse_roll_r(hipStream_t st, const TileViews& v, const LevelBuf& coarse, OutMat o, int cx_lo, int cx_hi, double bytes, bool* done) {
     const int nsx = cdiv(cx_hi - cx_lo, RL_CW), nsy = cdiv(coarse.rows, R), nby = cdiv(nsy, ROLL_WAVES);
     if (nsx <= 0 || nsy <= 0) return ISX_OK;
-    static const int band_mode = [] { const char* e = getenv("ISX_ROLL_BAND"); return e ? atoi(e) : 1; }();
-    static const int grp_sel = [] { const char* e = getenv("ISX_ROLL_GRP"); return e ? atoi(e) : 2; }();
-    const int grp = std::max(grp_sel, nsx == 1 ? 2 : 1);      // (xcd_magic needs grp * nsx >= 2)
+    // groups of two strip rows in the XCD band order (the kernel's band == 0 plain order is not selected any more)
+    const int grp = 2;
     o.bx0 = 0; o.grp = grp; o.gx = nsx; o.gy = nby; o.xmagic = xcd_magic(grp, nsx);
-    o.band = band_mode ? cdiv(nby, 8) : 0;
-    const unsigned nblk = o.band ? xcd_band_blocks(grp, nsx, nby) : xcd_grid_blocks(grp, nsx, nby);
+    o.band = cdiv(nby, 8);
+    const unsigned nblk = xcd_band_blocks(grp, nsx, nby);
     if (v.tab) {      // (the table form is instantiated for two-row strips only)
         if constexpr (R == 2) ISX_LAUNCH("collapse_roll", bytes, st, (k_collapse_roll_tab<M, SK, R, MAXT>), dim3(nblk), dim3(64 * ROLL_WAVES), 0, v.tt, coarse, o, cx_lo);
         else return ISX_OK;
@@ -2399,7 +2364,6 @@ int launch_collapse_roll_r(hipStream_t st, const TileViews& v, const LevelBuf& c
 template <int SK>
 int roll_variant(const std::vector<TileDesc>& td, const LevelBuf& coarse, int cx_lo, int cx_hi) {
     static const int mode = [] { const char* e = getenv("ISX_ROLL"); return e ? atoi(e) : 1; }();
-    static const int rsel = [] { const char* e = getenv("ISX_ROLL_R"); return e ? atoi(e) : 2; }();      // rows per wave (tuning runs only)
     if constexpr (SK == SK_U8 || SK == SK_S16) {
         if (!mode || coarse.cols < 2 || (unsigned long long)coarse.rows * coarse.cols * 16ull >= (1ull << 32)) return 0;
         for (const TileDesc& e : td)
@@ -2410,11 +2374,10 @@ int roll_variant(const std::vector<TileDesc>& td, const LevelBuf& coarse, int cx
         // two rows per wave while at most two tiles reach a strip (a pair, a row of tiles with narrow overlaps); a third slot
         // for panoramas whose tiles overlap their second neighbours (BASELINE config 5); k_collapse_gather beyond that
         // ... and two rows with a third slot (round 4: 4 waves per SIMD instead of 5, still faster than one-row strips - config 5's last step
-        // 0.704 -> 0.654 ms; ISX_ROLL_R23=0: the one-row form, for A/B runs)
-        static const bool r23 = [] { const char* e = getenv("ISX_ROLL_R23"); return !(e && e[0] == '0'); }();
-        const int most2 = (rsel != 1 || big) ? roll_max_tiles(td, coarse, cx_lo, cx_hi, 2, 3) : 99;
+        // 0.704 -> 0.654 ms)
+        const int most2 = roll_max_tiles(td, coarse, cx_lo, cx_hi, 2, 3);
         if (most2 <= 2) return 22;
-        if ((r23 || big) && most2 <= 3) return 23;
+        if (most2 <= 3) return 23;
         if (big) return 0;
         const int most = roll_max_tiles(td, coarse, cx_lo, cx_hi, 1, 3);
         if (most <= 2) return 12;
@@ -2437,11 +2400,6 @@ int launch_collapse_roll(isx_blender* b, hipStream_t st, const TileViews& v, con
     return ISX_OK;
 }
 
-// timing-only ablations of the small-level tail (tools/probes/tail_ablation.sh; wrong pixels): 1 = the pyrDown launches of levels >= 2 as one block
-// per tile, 2 = k_collapse_top as one block, 4 = those launches not issued at all - what any fusion of them could at most give
-#ifndef ISX_TAIL_ABL
-#define ISX_TAIL_ABL 0
-#endif
 // blend() of a fully deferred cycle: Gaussian chains of all tiles, top gather, gathering collapse chain
 template <int M, int SK>
 int run_blend_deferred_t(isx_blender* b, const OutMat& out) {
@@ -2504,14 +2462,13 @@ int run_blend_deferred_t(isx_blender* b, const OutMat& out) {
     int roll_var = 0;
     bool rec12 = false, g1_planar = false;
     if (L >= 2) {
-        static const bool top_on0 = [] { const char* e = getenv("ISX_TOP"); return !(e && e[0] == '0'); }();
         static const bool out12_on = [] { const char* e = getenv("ISX_OUT12"); return !(e && e[0] == '0'); }();
         static const bool g1p_on = [] { const char* e = getenv("ISX_G1P"); return !(e && e[0] == '0'); }();
         base(0);
         for (int t = 0; t < n; ++t) { td[(size_t)t].fine = b->tiles[t].g[0]; td[(size_t)t].coarse = b->tiles[t].g[1]; }
         roll_var = roll_variant<SK>(td, d[1], need_lo[0] / 2, std::min((need_hi[0] + 1) / 2, d[1].cols));
         const int D0 = std::min(TOP_DMAX, L - 1);
-        const bool lvl1_by_gather = !(top_on0 && D0 >= 2) || L - D0 >= 2;
+        const bool lvl1_by_gather = D0 < 2 || L - D0 >= 2;
         rec12 = roll_var != 0 && lvl1_by_gather && out12_on;
         g1_planar = roll_var != 0 && lvl1_by_gather && g1p_on && (M == M_F32 || M == M_I16);
     }
@@ -2531,13 +2488,8 @@ int run_blend_deferred_t(isx_blender* b, const OutMat& out) {
     const double g1_b = g1_q8 ? 10.0 : alg_g(prec), g1_rgb_b = g1_q8 ? 6.0 : alg_g_rgb(prec);      // algorithmic bytes of a level-1 record / its image channels
     auto planar_of = [g1_q8](LevelBuf g) { g.wgt = (float*)((char*)g.img + planar_wgt_offset(M, g.rows, g.cols, g1_q8)); return g; };
     // A pair with three fused top steps: k_collapse_top2 (collapse_top2.inc) rebuilds the tiles' level L itself, out of the one read of level L - 1
-    // it makes anyway - the pyrDown launch that produces level L is not issued.  ISX_TOP2=0: k_collapse_top behind that launch (A/B runs).
-    bool use_top2 = false;
-    {
-        static const bool top_on2 = [] { const char* e = getenv("ISX_TOP"); return !(e && e[0] == '0'); }();
-        static const bool top2_on = [] { const char* e = getenv("ISX_TOP2"); return !(e && e[0] == '0'); }();
-        use_top2 = top_on2 && top2_on && n <= 2 && std::min(TOP_DMAX, L - 1) == 3;
-    }
+    // it makes anyway - the pyrDown launch that produces level L is not issued.
+    const bool use_top2 = n <= 2 && std::min(TOP_DMAX, L - 1) == 3;
     // 1. Gaussian chains: one launch per level for all tiles.  (Per-tile chains on side streams, started
     //    by feed() to overlap with the next tile's VALU-bound warp, were measured: no gain — a kernel that
     //    fills every wave slot leaves nothing for a concurrent one — so the simpler form stays.)
@@ -2584,10 +2536,6 @@ int run_blend_deferred_t(isx_blender* b, const OutMat& out) {
             bytes += share * ((double)r.g[k].rows * r.g[k].cols * (k == 0 ? gin0 : (k == 1 ? g1_b : alg_g(prec))) + (double)r.g[k + 1].rows * r.g[k + 1].cols * (k == 0 ? g1_b : alg_g(prec)));
         }
         dim3 grid(cdiv(maxc, PD_OW), cdiv(maxr, PD_TY), n);
-        if ((ISX_TAIL_ABL & 1) && k >= 2) grid = dim3(1, 1, n);
-        if ((ISX_TAIL_ABL & 4) && k >= 2) continue;
-        if ((ISX_TAIL_ABL & 8) && k == 1) continue;                            // round 6 (tools/probes/level2_ablation.sh): the level 1 -> 2 launch not issued
-        if ((ISX_TAIL_ABL & 16) && k == 0) grid.y = (grid.y * 13 + 9) / 10;    // ... and the level-0 pyrDown doing 1.3 x its work (pyr_down0_body wraps the rows)
         if (use_top2 && k == L - 1) {       // level L is rebuilt inside k_collapse_top2
             if (k == b->mark_level && b->mark_event) ISX_HIP(hipEventRecord(b->mark_event, st));
             continue;
@@ -2637,12 +2585,10 @@ int run_blend_deferred_t(isx_blender* b, const OutMat& out) {
     // reaches no pixel of the window - every input of a pixel of need_{k-1} lies in need_k by construction - so the window's pixels
     // are those of the whole mosaic, bit for bit, and a mosaic can be cut into column strips computed on different GPUs.
     // The steps above the last two or three levels in ONE launch (collapse_top.inc): out_L .. out_{kout + 1} then never touch memory.
-    // ISX_TOP=0: one launch per step (A/B runs).
     int k_first = L;
     {
-        static const bool top_on = [] { const char* e = getenv("ISX_TOP"); return !(e && e[0] == '0'); }();
         const int D = std::min(TOP_DMAX, L - 1), kout = L - D;
-        if (top_on && D >= 2) {
+        if (D >= 2) {
             std::vector<TopDesc>& tp = b->tpd;
             tp.resize((size_t)n);
             double bytes = (double)d[kout].rows * d[kout].cols * alg_d_rgb(prec);
@@ -2660,10 +2606,8 @@ int run_blend_deferred_t(isx_blender* b, const OutMat& out) {
             const int gx_all = cdiv(d[kout].cols, TOP_BW);
             const int bx_lo = need_lo[kout] / TOP_BW, bx_hi = std::min(cdiv(need_hi[kout], TOP_BW), gx_all);
             dim3 grid(bx_hi - bx_lo, cdiv(d[kout].rows, TOP_BH));
-            if (ISX_TAIL_ABL & 2) grid = dim3(1, 1);
             bytes *= (double)(bx_hi - bx_lo) / gx_all;
-            if (ISX_TAIL_ABL & 4) {
-            } else if (n <= DEF_MAX) {
+            if (n <= DEF_MAX) {
                 TopTiles tt;
                 memset(&tt, 0, sizeof(tt));
                 tt.n = n; tt.D = D;
@@ -2882,7 +2826,7 @@ int run_blend(isx_blender* b, const OutMat& out) {
     if (b->level0_pending) {
         if (b->tiles.size() <= (size_t)DEF_MAX) return run_blend_deferred<M>(b, out);
         // More than DEF_MAX tiles (round 5): ONE chain over all of them, their descriptors in a device table (TileTab; cycle 4 in isx_blender_last_path).
-        // ISX_TAB=0: round 4's column strips of at most DEF_MAX tiles (run_blend_deferred_strips), ISX_STRIPS=0 as well: the eager cycle (A/B runs).
+        // ISX_TAB=0: round 4's column strips of at most DEF_MAX tiles (run_blend_deferred_strips; A/B runs).
         // One guard of the int16 arithmetic leans on the tile count: a sum of CV_8UC3 Laplacians (+-255 each) cannot wrap a short while at most 128
         // tiles meet in a pixel - k_collapse_gather's last step does not issue the wrap for them - so a cycle with a deeper stack than that over
         // some 128 columns takes the strips / the eager cycle as before.
@@ -2903,9 +2847,8 @@ int run_blend(isx_blender* b, const OutMat& out) {
             b->path_cycle = 4;
             return ISX_OK;
         }
-        static const bool strips_on = [] { const char* e = getenv("ISX_STRIPS"); return !(e && e[0] == '0'); }();    // ISX_STRIPS=0: the eager cycle, as before round 4 (A/B runs)
         bool done = false;
-        if (strips_on) ISX_TRY(run_blend_deferred_strips<M>(b, out, &done));
+        ISX_TRY(run_blend_deferred_strips<M>(b, out, &done));
         if (done) return ISX_OK;
         ISX_CHECK_ARG(b->win_x1 <= b->win_x0, ISX_ERR_UNSUPPORTED, "blend: more than %d tiles reach a %d-column strip of the window - a column window needs the deferred cycle",
                       DEF_MAX, ISX_WINDOW_GRANULE);
@@ -3484,11 +3427,10 @@ int do_feed(isx_blender* b, const isx_mat* img, const isx_mat* mask, int tl_x, i
         }
         // level 1 PLANAR when the chain will most likely want it so (run_blend_deferred_t: the last step as k_collapse_roll with level 1 produced
         // by k_collapse_gather); blend() produces the level again from the private copy in the rare cycle that wants the other layout
-        static const bool top_on0 = [] { const char* e = getenv("ISX_TOP"); return !(e && e[0] == '0'); }();
         static const bool g1p_on = [] { const char* e = getenv("ISX_G1P"); return !(e && e[0] == '0'); }();
         static const bool roll_on = [] { const char* e = getenv("ISX_ROLL"); return !(e && atoi(e) == 0); }();
         const int D0 = std::min(TOP_DMAX, L - 1);
-        const bool planar = L >= 2 && (!(top_on0 && D0 >= 2) || L - D0 >= 2) && g1p_on && roll_on && (b->prec == M_F32 || b->prec == M_I16);
+        const bool planar = L >= 2 && (D0 < 2 || L - D0 >= 2) && g1p_on && roll_on && (b->prec == M_F32 || b->prec == M_I16);
         // ... in Q8 records (load_px_planar) where the tile is bytes: CV_8UC3, or CV_16SC3 being narrowed (a violated cycle is widened and produces
         // its level 1 again)
         static const bool q8_on = [] { const char* e = getenv("ISX_G1Q8"); return !(e && e[0] == '0'); }();
@@ -3617,17 +3559,6 @@ int isx_blender_set_mark_event(isx_blender* b, void* hip_event, int after_level)
     b->mark_level = after_level;
     return ISX_OK;
 } ISX_EXIT("isx_blender_set_mark_event")
-
-#ifdef ISX_PHASE_TIMING
-// instrumented builds only (not declared in the header): sums of the 11 phases + the wave count; reset != 0 clears them
-int isx_debug_phase(unsigned long long* out12, int reset) ISX_ENTRY {
-    static unsigned long long h[1024][12];
-    ISX_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_phase), sizeof(h)));
-    for (int k = 0; k < 12; ++k) { out12[k] = 0; for (int i = 0; i < 1024; ++i) out12[k] += h[i][k]; }
-    if (reset) { memset(h, 0, sizeof(h)); ISX_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_phase), h, sizeof(h))); }
-    return ISX_OK;
-} ISX_EXIT("isx_debug_phase")
-#endif
 
 int isx_blender_set_sharpness(isx_blender* b, float sharpness) ISX_ENTRY {
     ISX_CHECK_ARG(b != nullptr, ISX_ERR_INVALID, "isx_blender_set_sharpness: null blender");

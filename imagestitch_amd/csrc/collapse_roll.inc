@@ -219,28 +219,11 @@ template <int M> struct RollAcc { f32x2 a[2], c, w; };
 
 template <int V> struct IC { static constexpr int value = V; };
 
-// ablation study of the kernel (tools/ab_bench.sh builds): bit 0 no result stores, bit 1 cache-resident coarse rows, bit 2 cache-resident tile rows
-#ifndef ROLL_ABL
-#define ROLL_ABL 0
-#endif
-
-// optional s_memtime stamps (-DISX_PHASE_TIMING, tools/phase_probe.sh): per-wave phase sums flushed into g_phase (blend.hip)
-#ifdef ISX_PHASE_TIMING
-#define RPT(k) do { const unsigned long long now__ = __builtin_amdgcn_s_memtime(); rph[k] += now__ - rprev; rprev = now__; } while (0)
-#define RPT_WAITALL do { __builtin_amdgcn_s_waitcnt(0); } while (0)
-#define RPT_FLUSH do { if (lane == 1) { const int slot__ = (blockIdx.x * 4 + (threadIdx.x >> 6)) & 1023; \
-        for (int k__ = 0; k__ < 11; ++k__) atomicAdd(&g_phase[slot__][k__], rph[k__]); atomicAdd(&g_phase[slot__][11], 1ull); } } while (0)
-#else
-#define RPT(k) do { } while (0)
-#define RPT_WAITALL do { } while (0)
-#define RPT_FLUSH do { } while (0)
-#endif
-
 // The strip with NS tile slots: R coarse rows starting at cy0, coarse columns scx0 - 1 + lane.  Everything indexed by a slot, a row or
 // a fine row is indexed by a constant: registers.
 template <int M, int SK, int R, int NS, int MAXT, class TS>
 __device__ __forceinline__ void roll_strip(const TS& ts, const LevelBuf& coarse_out, const OutMat& out, const int (&sel)[MAXT],
-                                           int scx0, int cy0, int lane, unsigned long long (&rph)[11], unsigned long long& rprev) {
+                                           int scx0, int cy0, int lane) {
     // IX: OpenCV's int16 arithmetic carried on integer-valued floats (exact, see roll_vrow_ix): the registers and the packed instructions of
     // the float modes, the rounding steps of the integer one
     constexpr bool IX = M == M_I16;
@@ -250,13 +233,13 @@ __device__ __forceinline__ void roll_strip(const TS& ts, const LevelBuf& coarse_
     constexpr int NSA = NS > 0 ? NS : 1;
     const int ocw = coarse_out.cols, och = coarse_out.rows;
     const int cxl = scx0 - 1 + lane;                         // this lane's coarse column
-    const bool prod = (ROLL_ABL & 4096) ? (cxl + 1 < ocw) : ((lane >= 1) & (lane <= RL_CW) & (cxl < ocw));      // (ablation 4096: all 64 lanes store, aligned rows, wrong pixels)
+    const bool prod = (lane >= 1) & (lane <= RL_CW) & (cxl < ocw);
     // every producing lane's 2 x 2 pixels inside the result's columns and the image rows fit the vector stores (4-byte aligned; CV_8UC3 and
     // the mask need no alignment: byte-misaligned stores are legal)
     // (a CV_16SC3 result's 12-byte stores are typed 2-byte aligned: the rows of a dense cv::Mat of odd width - what dst.create() gives the
     // reference's result, W:313 - start on 2-byte boundaries; until round 4 such a result took the per-pixel stores and the step 77 us instead of 58)
     const bool allin_x = (out.img_f32 == 2 || (((size_t)out.img | out.img_step) & (out.img_f32 == 0 ? 1 : 3)) == 0) && __builtin_amdgcn_ballot_w64(prod & !(2 * cxl + 1 < out.cols)) == 0ull;
-    const unsigned l_so = (unsigned)(cxl + ((ROLL_ABL & 4096) ? 1 : 0)) * 12u, l_sm = (unsigned)(cxl + ((ROLL_ABL & 4096) ? 1 : 0)) * 2u;      // byte offsets of the lane's pair in a result row / mask row
+    const unsigned l_so = (unsigned)cxl * 12u, l_sm = (unsigned)cxl * 2u;      // byte offsets of the lane's pair in a result row / mask row
     if constexpr (NS == 0) {
         // no tile reaches the strip: every weight is zero, Blender::blend zeroes the pixels and the mask (W:313)
         if (!prod) return;
@@ -341,20 +324,17 @@ __device__ __forceinline__ void roll_strip(const TS& ts, const LevelBuf& coarse_
             const int lcyc = min(max(lcy, 0), S[s].crows - 1);
 #pragma unroll
             for (int dy = 0; dy < 2; ++dy) {
-                int yr = 2 * lcyc + dy - S[s].top;
-                if (ROLL_ABL & 4) yr = dy;      // ablation: every wave reads the tile's first two rows
+                const int yr = 2 * lcyc + dy - S[s].top;
                 ryv[s][r][dy] = roll_reflect(yr, S[s].rows);                                      // copyMakeBorder(BORDER_REFLECT) of the image rows
             }
         }
-    RPT(1);     // slot descriptors, lane offsets
     // ---- every load of the strip: R + 2 coarse rows per source, the level-0 pixels of the 2 R fine rows per slot ----
     WT cr[NSA + 1][R + 2][3];
 #pragma unroll
     for (int s = 0; s < NS; ++s)
 #pragma unroll
         for (int r = 0; r < R + 2; ++r) {
-            int gy = roll_row_map(cy0 - 1 + r - S[s].tyc, S[s].crows);
-            if (ROLL_ABL & 2) gy = r;       // ablation: every wave reads the same three rows (cache-resident)
+            const int gy = roll_row_map(cy0 - 1 + r - S[s].tyc, S[s].crows);
             if constexpr (IX) {
                 int ci[3];
                 roll_load_rgb<M, true>(roll_sgpr(S[s].cimg + (size_t)((unsigned)gy * S[s].crowb)), l_co[s], ci, S[s].cdense);
@@ -364,7 +344,7 @@ __device__ __forceinline__ void roll_strip(const TS& ts, const LevelBuf& coarse_
 #pragma unroll
     for (int r = 0; r < R + 2; ++r)
     {
-        const gcp orow_c = roll_sgpr((gcp)coarse_out.img + (size_t)((unsigned)((ROLL_ABL & 2) ? r : roll_row_map(cy0 - 1 + r, och)) * ocrowb));
+        const gcp orow_c = roll_sgpr((gcp)coarse_out.img + (size_t)((unsigned)roll_row_map(cy0 - 1 + r, och) * ocrowb));
         if constexpr (IX) {
             int ci[3];
             roll_load_rgb<M, false>(orow_c, l_oo, ci, odense);
@@ -418,18 +398,16 @@ __device__ __forceinline__ void roll_strip(const TS& ts, const LevelBuf& coarse_
         for (int r = 0; r < R; ++r)
 #pragma unroll
             for (int dy = 0; dy < 2; ++dy) {
-                const int yr = (ROLL_ABL & 4) ? dy : 2 * (cy0 + r - S[s].tyc) + dy - S[s].top;
+                const int yr = 2 * (cy0 + r - S[s].tyc) + dy - S[s].top;
                 if (!((unsigned)yr < (unsigned)S[s].rows)) rm[s][r][dy] = 0u;
             }
         // A tile whose every weight in this strip is zero adds (g - pyrUp) * 0 = +-0 to sums that are never -0 and 0 to the weight sums: nothing.
         // With seam masks that is one of the two tiles of almost every strip of the overlap (wave-uniform test, one ballot) - its row
         // filters, column filters, decode and accumulate are skipped.  (Level values are finite: pyramids of 8-bit images.)
-        if (!(ROLL_ABL & 8192)) {
-            unsigned any = 0u;
+        unsigned any = 0u;
 #pragma unroll
-            for (int r = 0; r < R; ++r) any |= rm[s][r][0] | rm[s][r][1];
-            if (__builtin_amdgcn_ballot_w64(any != 0u) == 0ull) continue;
-        }
+        for (int r = 0; r < R; ++r) any |= rm[s][r][0] | rm[s][r][1];
+        if (__builtin_amdgcn_ballot_w64(any != 0u) == 0ull) continue;
         HRow<MW> H[R + 2];        // pyrUp's row filter of the source's coarse rows (a clamped lane outside the level only feeds itself)
 #pragma unroll
         for (int r = 0; r < R + 2; ++r) roll_hpass<MW>(cr[s][r], S[s].hedge, l_co[s], S[s].co_last, H[r]);
@@ -484,19 +462,15 @@ __device__ __forceinline__ void roll_strip(const TS& ts, const LevelBuf& coarse_
         }
     }
 
-    RPT(4);     // tiles: row filters, column filters, decode, accumulate
     // no weight anywhere in the strip (outside every seam mask): Blender::blend zeroes the pixels and the mask (W:313), whatever out_1 holds
-    bool all_zero = false;
-    if (!(ROLL_ABL & 8192)) {
-        bool nz = false;
+    bool nz = false;
 #pragma unroll
-        for (int r = 0; r < R; ++r)
+    for (int r = 0; r < R; ++r)
 #pragma unroll
-            for (int dy = 0; dy < 2; ++dy) {
-                nz = nz | (A[r][dy].w.x > WEIGHT_EPS) | (A[r][dy].w.y > WEIGHT_EPS);
-            }
-        all_zero = __builtin_amdgcn_ballot_w64(nz) == 0ull;
-    }
+        for (int dy = 0; dy < 2; ++dy) {
+            nz = nz | (A[r][dy].w.x > WEIGHT_EPS) | (A[r][dy].w.y > WEIGHT_EPS);
+        }
+    const bool all_zero = __builtin_amdgcn_ballot_w64(nz) == 0ull;
     if (all_zero && allin_x) {
         if (!prod) return;
         for (int fy = 2 * cy0; fy < min(2 * (cy0 + R), out.rows); ++fy) {
@@ -515,7 +489,6 @@ __device__ __forceinline__ void roll_strip(const TS& ts, const LevelBuf& coarse_
             constexpr int dy = decltype(DY)::value;
             const int fy = 2 * (cy0 + r) + dy;
             if (fy >= out.rows) return;         // crop to dst_roi_final_
-            if ((ROLL_ABL & 1) && out.cols > -7) return;      // ablation: no stores (a condition the compiler cannot fold)
             Px<M> d0, d1;
             if constexpr (IX) {
                 const UpRowPk u = roll_vrow_ix<dy>(H[r], H[r + 1], H[r + 2]);
@@ -575,10 +548,7 @@ __device__ __forceinline__ void roll_strip(const TS& ts, const LevelBuf& coarse_
                         for (int k = 0; k < 3; ++k) w3[k] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pk_i16(v[2 * k], v[2 * k + 1]));
                         q = u32x3_a2{w3[0], w3[1], w3[2]};
                     }
-                    if (!(ROLL_ABL & 32)) {
-                        if (ROLL_ABL & 2048) *(ROLL_GW(u32x3_a2))(orow + l_so) = q;
-                        else __builtin_nontemporal_store(q, (ROLL_GW(u32x3_a2))(orow + l_so));
-                    }
+                    __builtin_nontemporal_store(q, (ROLL_GW(u32x3_a2))(orow + l_so));
                 } else if (out.img_f32 == 1) {  // CV_32FC3: 24 bytes
                     const f32x3_a4 q0 = {on0 ? (float)d0.c0 : 0.f, on0 ? (float)d0.c1 : 0.f, on0 ? (float)d0.c2 : 0.f}, q1 = {on1 ? (float)d1.c0 : 0.f, on1 ? (float)d1.c1 : 0.f, on1 ? (float)d1.c2 : 0.f};
                     __builtin_nontemporal_store(q0, (ROLL_GW(f32x3_a4))(orow + 2u * l_so));
@@ -597,10 +567,10 @@ __device__ __forceinline__ void roll_strip(const TS& ts, const LevelBuf& coarse_
                     __builtin_nontemporal_store((u32_a2)((unsigned)v[0] | ((unsigned)v[1] << 8) | ((unsigned)v[2] << 16) | ((unsigned)v[3] << 24)), (ROLL_GW(u32_a2))(orow + (l_so >> 1)));
                     __builtin_nontemporal_store((unsigned short)((unsigned)v[4] | ((unsigned)v[5] << 8)), (ROLL_GW(unsigned short))(orow + (l_so >> 1) + 4u));
                 }
-                if (out.mask && !(ROLL_ABL & 16)) {
+                if (out.mask) {
                     ROLL_GW(unsigned short) mq = (ROLL_GW(unsigned short))(roll_sgpr((gp)out.mask + (size_t)((unsigned)fy * (unsigned)out.mask_step)) + l_sm);
                     const unsigned short mv = (unsigned short)((on0 ? 255u : 0u) | (on1 ? 0xff00u : 0u));
-                    if (ROLL_ABL & (2048 | 65536)) *mq = mv; else __builtin_nontemporal_store(mv, mq);      // (65536: only the mask's stores temporal)
+                    __builtin_nontemporal_store(mv, mq);
                 }
             } else {
                 write_final<M, BOUNDED>(out, 2 * cxl, fy, d0);
@@ -610,7 +580,6 @@ __device__ __forceinline__ void roll_strip(const TS& ts, const LevelBuf& coarse_
         fine(IC<0>{});
         fine(IC<1>{});
     }
-    RPT(5);     // out_1: row filters, column filters, normalise, convert, stores issued
 }
 
 #ifndef ROLL_WAVES_N
@@ -632,17 +601,9 @@ template <int M, int SK, int R, int MAXT, class TS>
 __device__ __forceinline__ void roll_wave(const TS& ts, int tb, int te, const LevelBuf& coarse_out, const OutMat& out, int cx_lo) {
     static_assert(SK == SK_U8 || SK == SK_S16, "CV_8UC3 or CV_16SC3 tiles");
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // (the wave index is uniform; say so)
-#ifdef ROLL_DUMMY_LDS       // occupancy study (tools/ab_libs.sh builds): an LDS allocation that caps the resident single-wave workgroups per CU
-    __shared__ unsigned roll_dummy_lds[ROLL_DUMMY_LDS / 4];
-    if (out.cols == -12345) roll_dummy_lds[threadIdx.x] = 1u, out.mask[0] = (unsigned char)roll_dummy_lds[(threadIdx.x + 1) & 63];
-#endif
-    unsigned long long rph[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, rprev = 0;
-#ifdef ISX_PHASE_TIMING
-    rprev = __builtin_amdgcn_s_memtime();
-#endif
     int sx, sy;
     if (out.band > 0 ? !xcd_band_block(blockIdx.x, out.grp, out.gx, out.gy, out.band, out.xmagic, sx, sy) : !xcd_block(blockIdx.x, out.grp, out.gx, out.gy, out.xmagic, sx, sy)) return;
-    const int scx0 = cx_lo + sx * ((ROLL_ABL & (64 | 4096)) ? 64 : RL_CW), cy0 = (sy * ROLL_WAVES + wv) * R;       // first coarse column / row this wave produces (mosaic coordinates)
+    const int scx0 = cx_lo + sx * RL_CW, cy0 = (sy * ROLL_WAVES + wv) * R;       // first coarse column / row this wave produces (mosaic coordinates)
     if (cy0 >= coarse_out.rows) return;
     tile_range(ts, 2 * scx0, 2 * scx0 + 2 * RL_CW, tb, te);      // (a TileTab: the tiles whose columns meet the strip's; a TileSet: all of them)
     // the tiles that reach this strip, in feed order (uniform; the host launches this kernel only when no strip is reached by more than MAXT)
@@ -658,18 +619,12 @@ __device__ __forceinline__ void roll_wave(const TS& ts, int tb, int te, const Le
             ++ns;
         }
     }
-    RPT(0);     // block order, tile selection
-#ifdef ISX_ROLL_ONLY_NS   // register / code-size study of one variant (tools/kstat.sh with ISX_EXTRA_FLAGS=-DISX_ROLL_ONLY_NS=n)
-    roll_strip<M, SK, R, ISX_ROLL_ONLY_NS, MAXT>(ts, coarse_out, out, sel, scx0, cy0, lane, rph, rprev);
-#else
     if constexpr (MAXT >= 3) {
-        if (ns >= 3) { roll_strip<M, SK, R, 3, MAXT>(ts, coarse_out, out, sel, scx0, cy0, lane, rph, rprev); RPT_FLUSH; return; }
+        if (ns >= 3) { roll_strip<M, SK, R, 3, MAXT>(ts, coarse_out, out, sel, scx0, cy0, lane); return; }
     }
-    if (ns >= 2) roll_strip<M, SK, R, 2, MAXT>(ts, coarse_out, out, sel, scx0, cy0, lane, rph, rprev);
-    else if (ns == 1) roll_strip<M, SK, R, 1, MAXT>(ts, coarse_out, out, sel, scx0, cy0, lane, rph, rprev);
-    else roll_strip<M, SK, R, 0, MAXT>(ts, coarse_out, out, sel, scx0, cy0, lane, rph, rprev);
-#endif
-    RPT_FLUSH;
+    if (ns >= 2) roll_strip<M, SK, R, 2, MAXT>(ts, coarse_out, out, sel, scx0, cy0, lane);
+    else if (ns == 1) roll_strip<M, SK, R, 1, MAXT>(ts, coarse_out, out, sel, scx0, cy0, lane);
+    else roll_strip<M, SK, R, 0, MAXT>(ts, coarse_out, out, sel, scx0, cy0, lane);
 }
 
 template <int M, int SK, int R, int MAXT>

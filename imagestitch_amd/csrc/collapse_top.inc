@@ -286,10 +286,6 @@ __device__ __forceinline__ void collapse_top_body(const TT& tt, const LevelBuf& 
         else top_restage<M, 18, 6>(lvA, x0, y0, oc, ccx[2], ccy[2], lev_w(2), lev_h(2));
         __syncthreads();
     }
-#ifndef TOP_ABL
-#define TOP_ABL 0       // ablation builds: 1 stop after the top level, 2 after the first step, 3 after the second
-#endif
-    if (TOP_ABL == 1) return;
     // ---- the steps, coarsest first: level j - 1 from level j (core regions 10 x 4, 18 x 6, 32 x 8 coarse pixels)
     Px<M> (*cur)[TOP_P] = lvB;       // where a step writes its fine level (the one before is free again after the restage)
     if (D == 3) {
@@ -299,12 +295,10 @@ __device__ __forceinline__ void collapse_top_body(const TT& tt, const LevelBuf& 
         __syncthreads();
         cur = lvA;
     }
-    if (TOP_ABL == 2) return;
     top_step<M, false, 18, 6>(tt, tb, te, 1, oc, ct, cur, 2 * ccx[2], 2 * ccy[2], out_g, ccx[2], ccy[2], lev_w(2), lev_h(2));
     __syncthreads();
     top_restage<M, 32, 8>(cur, 2 * ccx[2], 2 * ccy[2], oc, ccx[1], ccy[1], lev_w(1), lev_h(1));
     __syncthreads();
-    if (TOP_ABL == 3) return;
     top_step<M, true, 32, 8>(tt, tb, te, 0, oc, ct, cur, 0, 0, out_g, ccx[1], ccy[1], lev_w(1), lev_h(1));
 }
 template <int M>

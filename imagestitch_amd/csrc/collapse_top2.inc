@@ -13,10 +13,10 @@
 //   2. gathers the top level and runs the three steps out of LDS: a step's fine pixels and its coarse 3 x 3 neighbourhoods are read where the
 //      loads of phase 0 put them (G_L from phase 1), through the same clamp / row-map rules k_collapse_top's staging applies.
 // Per pixel the operations and their order are k_collapse_top's (top_step's accumulate expressions, top_pyr_up's filters, normalise): the same
-// bits (the whole GPU suite runs through it; ISX_TOP2=0 restores k_collapse_top + the pyrDown launch).
+// bits (the whole GPU suite runs through it).
 // LDS: 38.5 KB per block = four blocks per CU: the 748 blocks of a 4K pair are resident at once.
 // What it buys, measured (profiles/round5_top2_ab.txt): the step of a 4K pair -1.5 ... -3 us - all of it the launch that is gone (4.4 us); the kernel
-// itself takes 17.8 us against k_collapse_top's 16.5 - 17.3.  Phase by phase (tools/probes/top2_ablation.sh, timing-only builds): an empty launch 4.1 us;
+// itself takes 17.8 us against k_collapse_top's 16.5 - 17.3.  Phase by phase (timing-only builds, since removed): an empty launch 4.1 us;
 // with the loads, the pyrDown phase and the gathered top level still 4.2 (they hide inside the launch's own ramp); the first step + 3.6 us (40
 // pixels), the second + 3.7 (108), the last + 6.0 (256 pixels, the stores).  A step costs what it costs whatever was tried on it - packed fp32
 // (3 223 -> 2 633 vector instructions per wave), loads issued in the order of use, three or four blocks per CU, other waves of the block doing the
@@ -233,11 +233,6 @@ __device__ __forceinline__ void top2_restage(Px<M> (*lv)[T2_P], int x0, int y0, 
     }
 }
 
-// timing-only ablation builds (tools/probes/top2_ablation.sh; wrong pixels): return after 1 = the loads and G_{L-1}'s LDS copy, 2 = the pyrDown phase,
-// 3 = the gathered top level, 4 = the first step, 5 = the second step; 8 = an empty kernel
-#ifndef T2_ABL
-#define T2_ABL 0
-#endif
 template <int M>
 #ifndef ISX_TOP2_WPE
 #define ISX_TOP2_WPE 1       // (no occupancy request: 110 registers, four 4-wave blocks per CU by its 38.5 KB of LDS)
@@ -259,7 +254,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ISX_TOP2_WP
     Px<M> (*lv)[T2_P] = reinterpret_cast<Px<M> (*)[T2_P]>(smem + SZ_A + SZ_F + SZ_OC);
     Px<M> (*g3)[T2_TH][T2_TW] = reinterpret_cast<Px<M> (*)[T2_TH][T2_TW]>(smem + SZ_A + SZ_F + SZ_OC + 8u * T2_P * 16u);
     const int tid = threadIdx.x;
-    if (T2_ABL == 8) return;
     const int X0 = (blockIdx.x + bx0) * TOP_BW, Y0 = blockIdx.y * TOP_BH;
     int ccx[D + 1], ccy[D + 1], ccw[D + 1], cch[D + 1];      // core regions of the steps, as in k_collapse_top
     ccx[1] = X0 / 2; ccy[1] = Y0 / 2; ccw[1] = TOP_BW / 2; cch[1] = TOP_BH / 2;
@@ -341,7 +335,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ISX_TOP2_WP
         }
     }
     __syncthreads();
-    if (T2_ABL == 1) { if (A[0][0][0].w == 12345.f) out_g.rows = (int)(gg[0][0][0].c0 + gg[1][1][1].c0 + fv[0][0].c0 + fv[1][1].c0); if (out_g.rows == -7) store_px<M, false>(out_g, 0, 0, A[0][1][1]); return; }
     // ---- 1. G_L = pyrDown(G_{L-1}) on the top region: row filter, column filter (k_pyr_down_multi's functions and index maps) ------------------
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -363,7 +356,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ISX_TOP2_WP
         }
     }
     __syncthreads();
-    if (T2_ABL == 2) { if (g3[0][0][0].w == 12345.f) store_px<M, false>(out_g, 0, 0, g3[1][1][1]); return; }
     // G_L of tile s at tile-local (gx, gy) (inside the tile and - by construction of every reader - inside the top region; the index is clamped
     // for the neighbourhood entries of threads that own no pixel)
     auto top_of = [&](int s, int gx, int gy) -> Px<M> {
@@ -396,7 +388,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ISX_TOP2_WP
         top2_restage<M, 10, 4>(lv, x0, y0, oc, ccx[3], ccy[3], lev_w(3), lev_h(3));
         __syncthreads();
     }
-    if (T2_ABL == 3) { if (oc[0][0].w == 12345.f) store_px<M, false>(out_g, 0, 0, oc[1][1]); return; }
     // ---- 3. the three steps, every operand out of LDS / registers --------------------------------------------------------------------------
     // level L - 1 of tile s at tile-local coordinates: the staged A (no reflection inside the tile)
     auto a_of = [&](int s, int gx, int gy) -> Px<M> {
@@ -420,11 +411,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ISX_TOP2_WP
     __syncthreads();
     top2_restage<M, 18, 6>(lv, 2 * ccx[3], 2 * ccy[3], oc, ccx[2], ccy[2], lev_w(2), lev_h(2));
     __syncthreads();
-    if (T2_ABL == 4) { if (oc[0][0].w == 12345.f) store_px<M, false>(out_g, 0, 0, oc[1][1]); return; }
     top2_step<M, false, 18, 6>(T, 2, [&](int s, int fx, int fy, int, int) { return f_of(s, fx, fy); }, a_of, oc, lv, 2 * ccx[2], 2 * ccy[2], out_g, ccx[2], ccy[2], lev_w(2), lev_h(2));
     __syncthreads();
     top2_restage<M, 32, 8>(lv, 2 * ccx[2], 2 * ccy[2], oc, ccx[1], ccy[1], lev_w(1), lev_h(1));
     __syncthreads();
-    if (T2_ABL == 5) { if (oc[0][0].w == 12345.f) store_px<M, false>(out_g, 0, 0, oc[1][1]); return; }
     top2_step<M, true, 32, 8>(T, 1, [&](int s, int, int, int dx, int dy) { return gg[s][dy][dx]; }, f_of, oc, lv, 0, 0, out_g, ccx[1], ccy[1], lev_w(1), lev_h(1));
 }

@@ -14,9 +14,6 @@
 // pyr_down_block: identical bits.  Blocks on the tile's rim run pyr_down_block itself.
 // CV_16SC3 tiles (what Blender::feed receives in the reference, W:294,302): the same path with the pair's 12 bytes as ONE
 // global_load_dwordx3 at a 2-byte aligned address (collapse_roll.inc: RollWin).
-#ifndef ISX_PD0_ABL
-#define ISX_PD0_ABL 0       // ablation builds (tools/ab_libs.sh): 1 no stores, 2 cached loads, 4 no barrier + column phase, 8 no rim blocks
-#endif
 // o[k] = x[k] + (src[k] of the lane below / above; 0 beyond the wave's ends), four at a time: v_add_*_dpp wave_shr:1 / wave_shl:1 written
 // out.  The compiler folds __builtin_amdgcn_update_dpp into the addition only in some of the unrolled rows (the others become v_mov_dpp +
 // v_add, 24 more instructions per row and enough live registers to spill); the s_nop covers the two wait states a DPP read needs
@@ -91,8 +88,7 @@ __device__ __forceinline__ void pd0_interior_rows(const Src0& s0, int ox, int ro
         const int r = wv + PD_WAVES * i;
         rv[i] = RollWin<SK>{}; rm[i] = 0;
         if (r < NR) {
-            unsigned yr = (unsigned)(yr0 + r);
-            if (ISX_PD0_ABL & 2) yr = (unsigned)r;      // ablation: every block reads the tile's first rows (cache-resident)
+            const unsigned yr = (unsigned)(yr0 + r);
             if constexpr (SK == SK_S16) {
                 const u32x3_a2 t = *(ROLL_G(u32x3_a2))(roll_sgpr(img + (size_t)(yr * istep)) + l_io);
                 rv[i].x = t.x; rv[i].y = t.y; rv[i].z = t.z;
@@ -139,9 +135,6 @@ __device__ __forceinline__ void pd0_columns_ix(Px<M_F32> (*hb)[WAVE], const Leve
     }
 }
 
-#ifndef ISX_PD0_BAND
-#define ISX_PD0_BAND 1
-#endif
 // Waves per SIMD the level-0 pyrDown is compiled for.  6 (rounds 3 - 5: three 8-wave blocks per CU) was set when every block took the LDS path;
 // since the rim runs as single-wave strips and level 1 leaves as shorts, 8 (64 registers, four blocks per CU; the fp32 / fp16 CV_8UC3 forms
 // spill 8 dwords in the rim strips) is 2.2 us faster per launch in five of five same-box alternations (27.9 -> 25.7 us serialised,
@@ -154,7 +147,7 @@ __device__ __forceinline__ void pd0_columns_ix(Px<M_F32> (*hb)[WAVE], const Leve
 // rows - k_feed_strip's rim scheme without its copy: the lane's two taps of a row lie in ONE window of two adjacent tile pixels (possibly swapped or
 // doubled: flags), the rows go through the same two maps as scalars; every row index is computed BEFORE the first load (control flow between loads
 // drains them) and the strip makes one memory round trip, no LDS, no barrier.  The block-wide generic path it replaces (pyr_down_block: per-pixel
-// byte loads wherever a window does not fit) made a tenth of the blocks cost a seventh of the launch (tools/ab_libs.sh with -DISX_PD0_ABL=8).
+// byte loads wherever a window does not fit) made a tenth of the blocks cost a seventh of the launch (a timing-only build that skipped the rim blocks, since removed).
 template <int M, int SK, int PLD>
 __device__ __forceinline__ void pd0_rim_wave(const Src0& s0, const LevelBuf& dst, int bx, int oy0) {
     constexpr int NO = 2, NR = 2 * NO + 3;
@@ -226,22 +219,15 @@ __device__ __forceinline__ void pyr_down0_body(const TS& ts) {
     // Workgroups go to the 8 XCDs round robin in dispatch order (x fastest, then y, then z).  A block's rows are 372 image bytes and 124 mask
     // bytes long - no multiple of a 128-byte line - so horizontal neighbours share their boundary lines, vertical neighbours three rows of
     // halo: XCD k takes the k-th eighth of the blocks in (tile, row, column) order, so that neighbours run on the same XCD one after the other
-    // and find the shared lines in its L2 instead of fetching them again (ISX_PD0_BAND=0: dispatch order, for A/B runs).
-    int t = blockIdx.z, bx = blockIdx.x, by = blockIdx.y;
-    if (ISX_PD0_BAND) {
-        const unsigned gx = gridDim.x, gxy = gx * gridDim.y, L = gxy * gridDim.z;
-        const unsigned lin = blockIdx.z * gxy + blockIdx.y * gx + blockIdx.x;
-        const unsigned k = lin & 7u, chunk = L >> 3, rem = L & 7u;
-        const unsigned j = k * chunk + (k < rem ? k : rem) + (lin >> 3);
-        t = (int)(j / gxy);
-        const unsigned r = j - (unsigned)t * gxy;
-        by = (int)(r / gx);
-        bx = (int)(r - (unsigned)by * gx);
-    }
+    // and find the shared lines in its L2 instead of fetching them again.
+    const unsigned gx = gridDim.x, gxy = gx * gridDim.y, L = gxy * gridDim.z;
+    const unsigned lin = blockIdx.z * gxy + blockIdx.y * gx + blockIdx.x;
+    const unsigned k = lin & 7u, chunk = L >> 3, rem = L & 7u;
+    const unsigned j = k * chunk + (k < rem ? k : rem) + (lin >> 3);
+    const int t = (int)(j / gxy);
+    const unsigned r = j - (unsigned)t * gxy;
+    const int by = (int)(r / gx), bx = (int)(r - (unsigned)by * gx);
     const LevelBuf dst = ts.coarse[t];
-#if defined(ISX_TAIL_ABL) && (ISX_TAIL_ABL & 16)
-    by = by % ((dst.rows + PD_TY - 1) / PD_TY);      // timing-only build (tools/probes/level2_ablation.sh): a grid 1.3 x as tall redoes the first rows - the halo a fused level 2 would recompute
-#endif
     if (bx * PD_OW >= dst.cols || by * PD_TY >= dst.rows || bx < ts.bx_lo[t] || bx >= ts.bx_hi[t]) return;
     __shared__ Px<M> hb[PD_NR][WAVE];
     const Src0& s0 = ts.s0[t];
@@ -251,9 +237,7 @@ __device__ __forceinline__ void pyr_down0_body(const TS& ts) {
     // CV_8UC3: off the tile's last row - a lane's 8-byte window holds 2 bytes of the next pixel (or of the next row); iend != 0: the tile is below 2 GiB
     const bool interior = x_lo >= 0 && x_hi < s0.cols && y_lo >= 0 && y_hi < s0.rows - (SK == SK_S16 ? 0 : 1) && s0.iend != 0u;
     if (!interior) {
-        if (ISX_PD0_ABL & 8) return;
-        // (ISX_PD0_ABL & 16: the block-wide generic path, as before round 5's rim strips - A/B builds)
-        if (!(ISX_PD0_ABL & 16) && s0.iend != 0u && s0.cols >= 2 && s0.rows >= 2 && s0.width >= 4 && s0.height >= 4) {
+        if (s0.iend != 0u && s0.cols >= 2 && s0.rows >= 2 && s0.width >= 4 && s0.height >= 4) {
             static_assert(PD_TY == 2 * PD_WAVES, "eight waves x two output rows = one block");
             pd0_rim_wave<M, SK, PLD>(s0, dst, bx, by * PD_TY + 2 * __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)));
             return;
@@ -266,14 +250,11 @@ __device__ __forceinline__ void pyr_down0_body(const TS& ts) {
         static_assert(sizeof(Px<M_F32>) == sizeof(Px<M_I16>), "one LDS array for both forms");
         Px<M_F32>(*hf)[WAVE] = reinterpret_cast<Px<M_F32>(*)[WAVE]>(hb);
         pd0_interior_rows<M_F32, SK, PD_NR>(s0, bx * PD_OW + lane - 1, 2 * by * PD_TY - 2, hf);
-        if (ISX_PD0_ABL & 4) return;
         __syncthreads();
         pd0_columns_ix<PLD>(hf, dst, bx * PD_OW + lane - 1, by * PD_TY, lane, wv);
     } else {
         pd0_interior_rows<M, SK, PD_NR>(s0, bx * PD_OW + lane - 1, 2 * by * PD_TY - 2, hb);
-        if (ISX_PD0_ABL & 4) return;
         __syncthreads();
-        if ((ISX_PD0_ABL & 1) && hb[2 * wv][lane].w != 12345.f) return;
         pyr_down_columns<M, PLD>(hb, dst, bx * PD_OW + lane - 1, by * PD_TY, lane, wv);
     }
 }
@@ -442,15 +423,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(ISX_PD0_WPE
     static_assert(SK == SK_U8 || SK == SK_S16, "CV_8UC3 or CV_16SC3 tiles");
     static_assert(CF == CF_SAME || SK == SK_S16, "only CV_16SC3 tiles are narrowed");
     // the block order of k_pyr_down0 (every XCD one contiguous share of the blocks in row-major order)
-    int bx = blockIdx.x, by = blockIdx.y;
-    if (ISX_PD0_BAND) {
-        const unsigned gx = gridDim.x, L = gx * gridDim.y;
-        const unsigned lin = blockIdx.y * gx + blockIdx.x;
-        const unsigned k = lin & 7u, chunk = L >> 3, rem = L & 7u;
-        const unsigned j = k * chunk + (k < rem ? k : rem) + (lin >> 3);
-        by = (int)(j / gx);
-        bx = (int)(j - (unsigned)by * gx);
-    }
+    const unsigned gx = gridDim.x, L = gx * gridDim.y;
+    const unsigned lin = blockIdx.y * gx + blockIdx.x;
+    const unsigned k = lin & 7u, chunk = L >> 3, rem = L & 7u;
+    const unsigned j = k * chunk + (k < rem ? k : rem) + (lin >> 3);
+    const int by = (int)(j / gx), bx = (int)(j - (unsigned)by * gx);
     __shared__ Px<M> hb[PD_NR][WAVE];
     const int x_lo = 2 * (bx * PD_OW - 1) - s0.left, x_hi = 2 * (bx * PD_OW + WAVE - 2) + 1 - s0.left;
     const int y_lo = 2 * by * PD_TY - 2 - s0.top, y_hi = y_lo + PD_NR - 1;
@@ -506,9 +483,9 @@ __global__ __launch_bounds__(64) void k_feed_publish(unsigned* state, int n, int
 // rim to the block kernel behind it: 16 us per tile for a tenth of the blocks, whose byte-wise generic path lives as long as a whole interior
 // launch).  grid.x = every strip of level 1, dealt to the XCDs in contiguous ranges of the row-major order (vertical neighbours, which share
 // three input rows, meet in one L2).
-template <int M, int SK, int PLD, int CF, int NO>
+template <int M, int SK, int PLD, int CF>
 __global__ __launch_bounds__(64) void k_feed_strip(Src0 s0, LevelBuf dst, FeedCopy fc) {
-    constexpr int NR = 2 * NO + 3;
+    constexpr int NO = 2, NR = 2 * NO + 3;
     constexpr int MWK = M == M_I16 ? M_F32 : M;
     const int lane = threadIdx.x;
     const unsigned gx = (unsigned)((dst.cols + PD_OW - 1) / PD_OW), gy = (unsigned)((dst.rows + NO - 1) / NO), L = gx * gy;

@@ -1,8 +1,8 @@
 // roihost.cpp — detectResultRoi's border scan (W:64-88 where the extrema provably lie on the border; SphericalWarper's
-// detectResultRoiByBorder) ranked ON THE HOST.  Plain C++ (g++), no HIP: called by warp.hip's border_scan_sync.
+// detectResultRoiByBorder) ranked ON THE HOST.  Plain C++ (g++), no HIP: called by warp.hip's border_scan_host.
 //
 // Round 5's literal drop-in leg spent 155 of its 346 us of caller-thread time in four detectResultRoi round trips: one workgroup ranks the
-// 2 (W + H) border pixels on the GPU (k_roi_border_pin) and the host polls for the answer - 25 us on an idle GPU, 40 - 52 us on a busy one,
+// 2 (W + H) border pixels on the GPU (a kernel since removed) and the host polls for the answer - 25 us on an idle GPU, 40 - 52 us on a busy one,
 // because the launch queues behind whatever the device is doing (profiles/round5_roi_latency.txt).  The ranking needs no transcendental and
 // no image: 12 000 points x (nine multiply-adds, a division, a square root, a division) is microseconds of AVX2 / AVX-512 on the caller's thread, with
 // no launch and nothing to wait for.  Same scheme as the kernel: two strictly monotone stand-ins
@@ -177,7 +177,7 @@ __attribute__((target("avx2"))) int hits_avx2(const float* d, const float* q, in
 
 }  // namespace
 
-// The border pixels of an sw x sh source in the order of k_roi_border_pin's border_point (top, bottom, left, right; corners twice), ranked by
+// The border pixels of an sw x sh source in the order of warp.hip's border_point (top, bottom, left, right; corners twice), ranked by
 // their stand-ins; writes the (x, y) of every pixel within the tolerance of one of the four extrema to cand_xy (at most cap pairs) and returns
 // their number (> cap: the list is incomplete, use another path), 0 when no stand-in is finite.  scratch: 2 * (2 sw + 2 sh) floats.
 // isa: 0 = best available (AVX-512F, else AVX2, else scalar), 1 = scalar code, 2 = AVX2 where the CPU has it (tests compare them).

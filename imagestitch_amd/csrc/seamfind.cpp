@@ -9,7 +9,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <climits>
 #include <cstdio>
 #include <cstdlib>
@@ -249,10 +248,6 @@ struct Finder {
         for (const auto& e : wedges)
             if (e.second > 0) edges.insert(e.first);
     }
-
-    // phase times of resolveConflicts (ISX_SEAMFIND_TIMING)
-    double t_tips = 0, t_est = 0, t_upd = 0, t_rec = 0, t_wb = 0;
-    static double tnow() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
     bool has_only_one_neighbor(int comp) const {   // S:574-582
         auto b = edges.lower_bound({comp, INT_MIN});
@@ -550,17 +545,11 @@ struct Finder {
                 states[c1] = states[c2] == FIRST ? SECOND : FIRST;
             } else {
                 Pt p1, p2;
-                const double ta = tnow();
-                const bool tips = get_seam_tips(c1, c2, p1, p2);
-                t_tips += tnow() - ta;
-                if (tips) {
+                if (get_seam_tips(c1, c2, p1, p2)) {
                     std::vector<Pt> seam;
                     bool horiz = false, found = false;
-                    const double tb = tnow();
                     ISX_TRY(estimate_seam(image1, image2, tl1, tl2, c1, p1, p2, seam, horiz, found));
-                    const double tc = tnow();
                     if (found) update_labels_using_seam(c1, c2, seam, horiz);
-                    t_est += tc - tb; t_upd += tnow() - tc;
                 }
                 states[c1] = states[c2] == FIRST ? (INTERS | SECOND) : (INTERS | FIRST);
             }
@@ -568,10 +557,8 @@ struct Finder {
             // intersection component: only such a component is ever the first of a conflicting edge (its neighbours are FIRST- or SECOND-only
             // components, whose states never change), and tls_ / brs_ / contours_ are read for the first component only - so the scan of a
             // whole tile's rectangle that the second call would be is skipped, with nothing observable changed
-            const double td = tnow();
             recompute_region(c1, l1);
             if (states[c2] & INTERS) recompute_region(c2, l2);
-            t_rec += tnow() - td;
             edges.erase({c1, c2});
             edges.erase({c2, c1});
         }
@@ -583,7 +570,6 @@ struct Finder {
         for (size_t i = 0; i < states.size(); ++i) { is_first[i + 1] = (states[i] & FIRST) ? 1 : 0; is_second[i + 1] = (states[i] & SECOND) ? 1 : 0; }
         const int ux0 = std::max(tl1.x, tl2.x) - utlx, ux1 = std::min(tl1.x + cols1, tl2.x + cols2) - utlx;   // intersection in union coordinates
         const int uy0 = std::max(tl1.y, tl2.y) - utly, uy1 = std::min(tl1.y + rows1, tl2.y + rows2) - utly;
-        const double te = tnow();
         // one pass: at a pixel the second loop of the reference (S:509-523) reads mask2 as its first loop (S:495-507) left it AT THAT PIXEL.
         // Row by row over the runs of equal label (eight labels per step), so that what is done per pixel is a byte select
         for (int uy = uy0; uy < uy1; ++uy) {
@@ -599,7 +585,6 @@ struct Finder {
                 ux = e;
             }
         }
-        t_wb += tnow() - te;
         return ISX_OK;
     }
 
@@ -616,18 +601,9 @@ struct Finder {
         // the label image's window: the intersection rectangle widened by one pixel, clipped to the union
         wx0 = std::max(itlx - utlx - 1, 0); wy0 = std::max(itly - utly - 1, 0);
         ww = std::min(ibrx - utlx + 1, uw) - wx0; wh = std::min(ibry - utly + 1, uh) - wy0;
-        static const bool tm = getenv("ISX_SEAMFIND_TIMING") != nullptr;
-        auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-        t_tips = t_est = t_upd = t_rec = t_wb = 0;
-        double t1 = now();
         find_components();
-        double t2 = now();
         find_edges();
-        double t3 = now();
-        int rc = resolve_conflicts(image1, image2, tl1, tl2, mask1, step1, r1, c1, mask2, step2, r2, c2);
-        if (tm) fprintf(stderr, "seamfind: components %.2f ms, edges %.2f ms, resolve %.2f ms (tips %.2f, estimateSeam %.2f, label update %.2f, region recompute %.2f, mask write-back %.2f)\n",
-                        t2 - t1, t3 - t2, now() - t3, t_tips, t_est, t_upd, t_rec, t_wb);
-        return rc;
+        return resolve_conflicts(image1, image2, tl1, tl2, mask1, step1, r1, c1, mask2, step2, r2, c2);
     }
 };
 

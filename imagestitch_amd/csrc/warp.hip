@@ -14,14 +14,12 @@
 #include "isx_internal.hpp"
 
 #include <algorithm>
-#include <chrono>
 #include <climits>
 #include <cmath>
 #include <cstdlib>
 #include <limits>
 #include <memory>
 #include <mutex>
-#include <thread>
 #include <unordered_map>
 #include <cstring>
 #include <new>
@@ -469,11 +467,7 @@ __device__ __forceinline__ int reflect_once(int p, int n2m1) {
     return min(q, n2m1 - q);
 }
 
-// ablation study of the tile warp (tools/ab_libs.sh builds, profiles/round3_warp_ablation.txt): bit 0 no stores, bit 1 every window from
-// one cache-resident source row, bit 2 no transform (coordinates = a shift), bit 3 non-temporal stores; WARP_WAVES waves per workgroup
-#ifndef WARP_ABL
-#define WARP_ABL 0
-#endif
+// WARP_WAVES waves per workgroup
 #ifndef WARP_WAVES
 #define WARP_WAVES 4
 #endif
@@ -557,10 +551,6 @@ __device__ __forceinline__ void warp_tile_body(const Proj& p, const MapTabs& t, 
         const f32x2 ax = div_by_refined(X[h], Z[h], r1), ay = div_by_refined(Y[h], Z[h], r1);
         tx[2 * h] = ax.x; tx[2 * h + 1] = ax.y; ty[2 * h] = ay.x; ty[2 * h + 1] = ay.y;
     }
-    if (WARP_ABL & 4) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { tx[k] = (float)(32 * (dx0 + k) + 7); ty[k] = (float)(32 * dy + 5); Z[k >> 1] = splat2(1.f); }
-    }
     // z of the four pixels inside the division's guarded range?  (A NaN slips through min / max and is caught below: its quotient
     // is NaN, which no clamp leaves unchanged.)  Otherwise - z <= 0 (W:61) included - the generic code path does the thread's row.
     const float zmin = fminf(fminf(Z[0].x, Z[0].y), fminf(Z[1].x, Z[1].y)), zmax = fmaxf(fmaxf(Z[0].x, Z[0].y), fmaxf(Z[1].x, Z[1].y));
@@ -594,7 +584,6 @@ __device__ __forceinline__ void warp_tile_body(const Proj& p, const MapTabs& t, 
             const unsigned bx = __float_as_uint(cxs[k] + RNE_MAGIC), by = __float_as_uint(cys[k] + RNE_MAGIC);
             fxy[k] = (bx & 31u) | ((by & 31u) << 8);
             o0[k] = mad24(__builtin_amdgcn_ubfe(by, 5, 18), step, mad24(__builtin_amdgcn_ubfe(bx, 5, 18), 3u, addr_c));
-            if (WARP_ABL & 2) o0[k] = mad24(__builtin_amdgcn_ubfe(bx, 5, 18), 3u, mis + 12u) - 0x60000u;      // row 0: cache-resident
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {       // all eight loads in flight together
@@ -666,7 +655,6 @@ __device__ __forceinline__ void warp_tile_body(const Proj& p, const MapTabs& t, 
         for (int k = 0; k < 4; ++k) px[k] = (unsigned)s_lut[px[k] & 255u] | ((unsigned)s_lut[(px[k] >> 8) & 255u] << 8) | ((unsigned)s_lut[(px[k] >> 16) & 255u] << 16);
     }
     // ---- stores ------------------------------------------------------------------------------------------------------------
-    if ((WARP_ABL & 1) && d.w > -3) { if (px[0] + px[1] + px[2] + px[3] + m4 == 0x12345u) d.mask[0] = 1; return; }
     if (whole) {
         // one vector store per run, typed for ANY alignment (WV3 / WV1: aligned(1)): a dense cv::Mat row of 3425 CV_8UC3 pixels starts on
         // an odd byte, unaligned global access is legal on this part and a wave's runs are contiguous either way
@@ -682,12 +670,10 @@ __device__ __forceinline__ void warp_tile_body(const Proj& p, const MapTabs& t, 
             const unsigned q0 = px[0] | (px[1] << 24);                                   // b0 g0 r0 b1
             const unsigned q1 = __builtin_amdgcn_perm(px[2], px[1], 0x05040201u);        // g1 r1 b2 g2
             const unsigned q2 = __builtin_amdgcn_perm(px[3], px[2], 0x06050402u);        // r2 b3 g3 r3
-            if (WARP_ABL & 8) __builtin_nontemporal_store(WV3{q0, q1, q2}, (WV3*)q);
-            else *(WV3*)q = WV3{q0, q1, q2};
+            *(WV3*)q = WV3{q0, q1, q2};
         }
         if constexpr (MASK) {
-            if (WARP_ABL & 8) __builtin_nontemporal_store(m4, (WV1*)(d.mask + (__umul24((unsigned)dy, d.mask_step) + (unsigned)dx0)));
-            else *(WV1*)(d.mask + (__umul24((unsigned)dy, d.mask_step) + (unsigned)dx0)) = m4;
+            *(WV1*)(d.mask + (__umul24((unsigned)dy, d.mask_step) + (unsigned)dx0)) = m4;
         }
     } else {    // the partial group at the right edge, or destination rows that are not dword aligned: per-pixel stores
 #pragma unroll 1
@@ -1031,92 +1017,6 @@ __global__ void k_roi_check_rearm(unsigned* keys, RoiBounds b, int* mismatches) 
     keys[0] = 0xffffffffu; keys[1] = 0xffffffffu; keys[2] = 0u; keys[3] = 0u; keys[4] = 0u;
 }
 
-// The synchronous border scan with its answer delivered straight into pinned host memory: detectResultRoi has to hand the corner to the
-// host (W:160), and the round trip - kernel, copy of {count, candidates}, a kernel that re-arms the device-side keys, a stream
-// synchronisation - cost the caller's thread 45 us per call, four times per pair in the reference's own call sequence (W:229, W:232 each
-// run detectResultRoi).  Here ONE workgroup ranks the 2 (W + H) border pixels (stand-ins kept in registers between the two passes while
-// they fit: 16 per thread), counts the candidates in LDS, writes them and the count into the caller's pinned block and publishes a
-// sequence number with a system-scope release store; the host polls that word (detect_roi) - no copy, no second kernel, no
-// hipStreamSynchronize.  Candidates beyond the pinned block's CAND_FIRST also go to the device buffer (the host fetches them: rare).
-constexpr int PIN_CAND = 1024;      // == CAND_FIRST (checked where that is defined)
-struct RoiPin { int seq, count, pad[14]; int cand[2 * PIN_CAND]; };
-__global__ __launch_bounds__(1024) void k_roi_border_pin(Proj p, int sw, int sh, RoiPin* pin, int seq, int* cand_dev, int cap) {
-    __shared__ float red[4][16];
-    __shared__ int s_count;
-    constexpr int PER = 16;
-    const int n = 2 * sw + 2 * sh;
-    const bool fits = n <= PER * 1024;
-    float dv[PER], qv[PER];
-    float dmin = 3.402823466e+38f, qmin = 3.402823466e+38f, dmax = -3.402823466e+38f, qmax = -3.402823466e+38f;
-    if (threadIdx.x == 0) s_count = 0;
-    auto proxy = [&](int i, float& d, float& q) {
-        int x, y;
-        border_point(i, sw, sh, x, y);
-        if (p.kind == ISX_WARP_SPHERICAL) forward_proxy_sph(p, (float)x, (float)y, d, q); else forward_proxy(p, (float)x, (float)y, d, q);
-    };
-    if (fits) {
-#pragma unroll
-        for (int k = 0; k < PER; ++k) {
-            const int i = threadIdx.x + 1024 * k;
-            float d = 0.f, q = 0.f;
-            if (i < n) {
-                proxy(i, d, q);
-                dmin = (d < dmin) ? d : dmin; qmin = (q < qmin) ? q : qmin; dmax = (dmax < d) ? d : dmax; qmax = (qmax < q) ? q : qmax;
-            }
-            dv[k] = d; qv[k] = q;
-        }
-    } else {
-        for (int i = threadIdx.x; i < n; i += 1024) {
-            float d, q;
-            proxy(i, d, q);
-            dmin = (d < dmin) ? d : dmin; qmin = (q < qmin) ? q : qmin; dmax = (dmax < d) ? d : dmax; qmax = (qmax < q) ? q : qmax;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        dmin = fminf(dmin, __shfl_xor(dmin, o)); qmin = fminf(qmin, __shfl_xor(qmin, o));
-        dmax = fmaxf(dmax, __shfl_xor(dmax, o)); qmax = fmaxf(qmax, __shfl_xor(qmax, o));
-    }
-    const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[0][wv] = dmin; red[1][wv] = qmin; red[2][wv] = dmax; red[3][wv] = qmax; }
-    __syncthreads();
-    dmin = red[0][0]; qmin = red[1][0]; dmax = red[2][0]; qmax = red[3][0];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) { dmin = fminf(dmin, red[0][k]); qmin = fminf(qmin, red[1][k]); dmax = fmaxf(dmax, red[2][k]); qmax = fmaxf(qmax, red[3][k]); }
-    const float tol_d = 7.62939453125e-06f;                                   // as k_roi_candidates
-    const float tol_q = 4e-6f * fmaxf(fabsf(qmin), fabsf(qmax)) + 1e-9f;
-    bool wrote = false;
-    auto take = [&](int i, float d, float q) {
-        if (d <= dmin + tol_d || d >= dmax - tol_d || q <= qmin + tol_q || q >= qmax - tol_q) {
-            int x, y;
-            border_point(i, sw, sh, x, y);
-            const int j = atomicAdd(&s_count, 1);
-            if (j < PIN_CAND) { pin->cand[2 * j] = x; pin->cand[2 * j + 1] = y; wrote = true; }
-            if (j < cap) { cand_dev[2 * j] = x; cand_dev[2 * j + 1] = y; }
-        }
-    };
-    if (fits) {
-#pragma unroll
-        for (int k = 0; k < PER; ++k) {
-            const int i = threadIdx.x + 1024 * k;
-            if (i < n) take(i, dv[k], qv[k]);
-        }
-    } else {
-        for (int i = threadIdx.x; i < n; i += 1024) {
-            float d, q;
-            proxy(i, d, q);
-            take(i, d, q);
-        }
-    }
-    if (wrote) __threadfence_system();          // the candidates are in host memory before the sequence number is
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        pin->count = s_count;
-        __threadfence_system();
-        __hip_atomic_store(&pin->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-}
-
 __global__ void k_roi_rearm(unsigned* keys) {
     keys[0] = 0xffffffffu; keys[1] = 0xffffffffu; keys[2] = 0u; keys[3] = 0u; keys[4] = 0u;
 }
@@ -1244,9 +1144,6 @@ struct isx_warper {
     void* pin = nullptr;     // pinned host landing zone of detectResultRoi's {keys, count, first candidates}
     double gain = 1.0;       // isx_warper_set_gain: folded into the fused tile warp's store (1.0 = off)
     unsigned char gain_lut[256] = {};   // its 256-entry table (handed to the kernel in its arguments)
-    int verify_dropped = 0;  // verifications discarded under ISX_VERIFY_NEVER (isx_warper_plan_status reports them)
-    RoiPin* pin2 = nullptr;  // pinned block the border scan writes its answer into (k_roi_border_pin); pin_seq: the call number it publishes
-    int pin_seq = 0;
     // isx_warper_set_deferred_verify: planned warps queue their verification; isx_warper_verify enqueues the
     // queued scans behind the main stream's position AT THAT CALL (e.g. after the last warp of a step, so
     // that they run under the memory-bound pyramid kernels instead of under the next tile's warp)
@@ -1298,7 +1195,6 @@ namespace {
 
 constexpr int CAND_CAP = 1 << 16;
 constexpr int CAND_FIRST = 1024;   // candidates that travel with the count in the one copy of detectResultRoi
-static_assert(CAND_FIRST == PIN_CAND, "k_roi_border_pin's pinned block holds CAND_FIRST candidates");
 
 int set_camera(isx_warper* w, const float K[9], const float R[9]) {
     ISX_CHECK_ARG(K != nullptr && R != nullptr, ISX_ERR_INVALID, "setCameraParams: K and R must be 3x3 CV_32F (got null)");  // W:94-95
@@ -1318,11 +1214,11 @@ int set_camera(isx_warper* w, const float K[9], const float R[9]) {
 
 // The collected tile warps of a batch (isx_warper_begin_batch): runs of the same kernel variant leave as one launch of up to WARP_BATCH_MAX tiles
 // (blockIdx.z = tile, the grid the largest tile's); a run of one takes the ordinary kernel.
-template <int KD, bool O16, bool V>
+template <int KD, bool O16>
 int launch_warp_batch(hipStream_t st, const isx_warper::BatchItem* it, int n) {
     if (n == 1) {
         WarpTileArgs a{it[0].g.p, it[0].g.t, it[0].g.img, it[0].g.d, {}};
-        ISX_LAUNCH("warp_tile", it[0].bytes, st, (k_warp_tile<KD, O16, V>), dim3(it[0].gx, it[0].gy), dim3(64 * WARP_WAVES), 0, a);
+        ISX_LAUNCH("warp_tile", it[0].bytes, st, (k_warp_tile<KD, O16, true>), dim3(it[0].gx, it[0].gy), dim3(64 * WARP_WAVES), 0, a);
         return ISX_OK;
     }
     WarpTileBatch b;
@@ -1334,7 +1230,7 @@ int launch_warp_batch(hipStream_t st, const isx_warper::BatchItem* it, int n) {
         b.a[i].d.xg = 0;          // (the XCD-run order is a function of the launch's own grid: off in a shared one)
         gx = std::max(gx, it[i].gx); gy = std::max(gy, it[i].gy); bytes += it[i].bytes;
     }
-    ISX_LAUNCH("warp_tile", bytes, st, (k_warp_tile_batch<KD, O16, V>), dim3(gx, gy, (unsigned)n), dim3(64 * WARP_WAVES), 0, b);
+    ISX_LAUNCH("warp_tile", bytes, st, (k_warp_tile_batch<KD, O16, true>), dim3(gx, gy, (unsigned)n), dim3(64 * WARP_WAVES), 0, b);
     return ISX_OK;
 }
 int flush_warp_batch(isx_warper* w) {
@@ -1348,14 +1244,10 @@ int flush_warp_batch(isx_warper* w) {
         const int n = (int)(j - i), v = items[i].variant;
         int rc = ISX_OK;
         switch (v) {
-            case 0: rc = launch_warp_batch<ISX_WARP_CYLINDRICAL, false, false>(w->stream, it, n); break;
-            case 1: rc = launch_warp_batch<ISX_WARP_CYLINDRICAL, false, true>(w->stream, it, n); break;
-            case 2: rc = launch_warp_batch<ISX_WARP_CYLINDRICAL, true, false>(w->stream, it, n); break;
-            case 3: rc = launch_warp_batch<ISX_WARP_CYLINDRICAL, true, true>(w->stream, it, n); break;
-            case 4: rc = launch_warp_batch<ISX_WARP_SPHERICAL, false, false>(w->stream, it, n); break;
-            case 5: rc = launch_warp_batch<ISX_WARP_SPHERICAL, false, true>(w->stream, it, n); break;
-            case 6: rc = launch_warp_batch<ISX_WARP_SPHERICAL, true, false>(w->stream, it, n); break;
-            default: rc = launch_warp_batch<ISX_WARP_SPHERICAL, true, true>(w->stream, it, n); break;
+            case 0: rc = launch_warp_batch<ISX_WARP_CYLINDRICAL, false>(w->stream, it, n); break;
+            case 1: rc = launch_warp_batch<ISX_WARP_CYLINDRICAL, true>(w->stream, it, n); break;
+            case 2: rc = launch_warp_batch<ISX_WARP_SPHERICAL, false>(w->stream, it, n); break;
+            default: rc = launch_warp_batch<ISX_WARP_SPHERICAL, true>(w->stream, it, n); break;
         }
         if (rc != ISX_OK) return rc;
         i = j;
@@ -1368,10 +1260,6 @@ int flush_warp_batch(isx_warper* w) {
 int flush_verify(isx_warper* w, hipEvent_t after = nullptr) {
     ISX_TRY(flush_warp_batch(w));      // (the scans start behind the warps they verify)
     if (w->pending.empty()) return ISX_OK;
-    // ISX_VERIFY_NEVER: a measurement aid (what the verification scans cost a step).  A run under it is not a verified run and cannot pass
-    // for one: isx_warper_plan_status answers ISX_ERR_PLAN once a verification has been dropped here.
-    static const bool never = getenv("ISX_VERIFY_NEVER") != nullptr;
-    if (never) { w->verify_dropped += (int)w->pending.size(); w->pending.clear(); return ISX_OK; }
     hipStream_t st = w->stream;
     if (!w->side) {
         // one verification stream per DEVICE, shared by every warper on it (never destroyed): a batch of pairs would otherwise
@@ -1391,8 +1279,7 @@ int flush_verify(isx_warper* w, hipEvent_t after = nullptr) {
     // PLACES them (full scans are VALU-bound and should start under memory-bound work).  A border scan is one workgroup: it starts right
     // away, with no event on the main stream at all - unless that stream is being captured, where the wait is what forks the side
     // stream into the graph.
-    static const bool ordered_always = getenv("ISX_VERIFY_ORDERED") != nullptr;      // A/B aid: the placed form for every scan
-    bool cheap = !ordered_always;
+    bool cheap = true;
     for (const isx_warper::Pending& pd : w->pending)
         cheap = cheap && (pd.proj.kind == ISX_WARP_SPHERICAL || cyl_extrema_on_border(pd.proj, pd.k, pd.rinv, pd.sw, pd.sh));
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -1475,9 +1362,6 @@ int roi_stream_of(isx_warper* w, hipStream_t* out) {
     return ISX_OK;
 }
 
-// The synchronous border scan (k_roi_border_pin) on the ROI stream, its candidates in w->host_cand when this returns: one launch, then the
-// caller's thread polls the sequence number the kernel publishes in pinned memory (ISX_ROI_POLL=0: the round-3 form - kernel, copy, re-arm
-// kernel, hipStreamSynchronize - for A/B runs).
 // detectResultRoi's answer from the candidates of a scan: mapForward with the host's libm on exactly those (W:72-86; spherical:
 // detectResultRoiByBorder's truncation of the border's extrema, then OpenCV's two pole tests)
 void roi_from_candidates(const Proj& p, const float k[9], const float rinv[9], int sw, int sh, const int* cand, int n, int roi[4], float mm_out[4]) {
@@ -1502,8 +1386,8 @@ void roi_from_candidates(const Proj& p, const float k[9], const float rinv[9], i
     roi[0] = f2i_host(tl_u); roi[1] = f2i_host(tl_v); roi[2] = f2i_host(br_u); roi[3] = f2i_host(br_v);   // W:83-86
 }
 
-// Round 6: the ranking runs on the caller's thread (roihost.cpp: no launch, nothing to queue behind, nothing to wait for - the scan reads the
-// projection and the source size only); ISX_ROI_HOST=0 restores the device forms below for A/B runs and for their tests.
+// The synchronous border scan, its candidates in cand_out when this returns.  Round 6: the ranking runs on the caller's thread (roihost.cpp: no
+// launch, nothing to queue behind, nothing to wait for - the scan reads the projection and the source size only).
 int border_scan_host(const float* r_kinv, bool sph, int sw, int sh, std::vector<int>& cand_out, std::vector<float>& scratch, int isa, int* n_out) {
     scratch.resize((size_t)4 * ((size_t)sw + (size_t)sh));
     if (cand_out.size() < (size_t)2 * CAND_FIRST) cand_out.resize((size_t)2 * CAND_FIRST);
@@ -1515,58 +1399,6 @@ int border_scan_host(const float* r_kinv, bool sph, int sw, int sh, std::vector<
     }
     ISX_CHECK_ARG(n > 0, ISX_ERR_INVALID, "detectResultRoi: mapForward is not finite anywhere on the border of the %d x %d source (bad K / R / scale?)", sw, sh);
     cand_out.resize((size_t)n * 2);
-    *n_out = n;
-    return ISX_OK;
-}
-
-int border_scan_sync(isx_warper* w, int sw, int sh, hipStream_t st, const char* label, int* n_out) {
-    static const bool host_scan = [] { const char* e = getenv("ISX_ROI_HOST"); return !(e && e[0] == '0'); }();
-    if (host_scan) return border_scan_host(w->proj.r_kinv, w->kind == ISX_WARP_SPHERICAL, sw, sh, w->host_cand, w->host_scratch, 0, n_out);
-    static const bool poll = [] { const char* e = getenv("ISX_ROI_POLL"); return !(e && e[0] == '0'); }();
-    unsigned* keys = (unsigned*)w->scan.p;
-    int* count = (int*)(keys + 4);
-    int* cand = (int*)((char*)w->scan.p + 64);
-    int n = 0;
-    const int* first = nullptr;
-    if (poll) {
-        if (!w->pin2) {
-            ISX_HIP(hipHostMalloc((void**)&w->pin2, sizeof(RoiPin), hipHostMallocCoherent | hipHostMallocMapped));
-            memset(w->pin2, 0, sizeof(RoiPin));
-        }
-        const int seq = ++w->pin_seq;
-        ISX_LAUNCH(label, 0.0, st, k_roi_border_pin, dim3(1), dim3(1024), 0, w->proj, sw, sh, w->pin2, seq, cand, CAND_CAP);
-        (void)hipStreamQuery(st);           // the dispatch is on its way before the polling starts
-        const auto t0 = std::chrono::steady_clock::now();
-        bool synced = false;
-        while (__atomic_load_n(&w->pin2->seq, __ATOMIC_ACQUIRE) != seq) {
-#if defined(__x86_64__) || defined(__i386__)
-            __builtin_ia32_pause();
-#else
-            std::this_thread::yield();
-#endif
-            if (!synced && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) {   // a busy GPU: wait the ordinary way (and report its errors)
-                ISX_HIP(hipStreamSynchronize(st));
-                synced = true;
-                ISX_CHECK_ARG(__atomic_load_n(&w->pin2->seq, __ATOMIC_ACQUIRE) == seq, ISX_ERR_HIP, "detectResultRoi: the border scan finished without publishing its result");
-            }
-        }
-        n = w->pin2->count;
-        first = w->pin2->cand;
-    } else {
-        ISX_LAUNCH(label, 0.0, st, k_roi_border_sph, dim3(1), dim3(1024), 0, w->proj, sw, sh, (unsigned*)nullptr, cand, CAND_CAP, count);
-        if (!w->pin) ISX_HIP(hipHostMalloc(&w->pin, 64 + (size_t)CAND_FIRST * 8, hipHostMallocDefault));
-        ISX_HIP(hipMemcpyAsync(w->pin, w->scan.p, 64 + (size_t)CAND_FIRST * 8, hipMemcpyDeviceToHost, st));
-        ISX_LAUNCH("roi_rearm", 0.0, st, k_roi_rearm, dim3(1), dim3(1), 0, keys);
-        ISX_HIP(hipStreamSynchronize(st));
-        n = ((const int*)w->pin)[4];
-        first = (const int*)((const char*)w->pin + 64);
-    }
-    ISX_CHECK_ARG(n <= CAND_CAP, ISX_ERR_UNSUPPORTED, "detectResultRoi: %d extremum candidates exceed the refinement buffer (%d)", n, CAND_CAP);
-    ISX_CHECK_ARG(n > 0, ISX_ERR_INVALID, "detectResultRoi: mapForward is not finite anywhere on the border of the %d x %d source (bad K / R / scale?)", sw, sh);
-    w->host_cand.resize((size_t)n * 2);
-    std::memcpy(w->host_cand.data(), first, (size_t)std::min(n, CAND_FIRST) * 8);
-    if (n > CAND_FIRST)     // rare: more candidates than the pinned block carries
-        ISX_HIP(hipMemcpy(w->host_cand.data() + 2 * (size_t)CAND_FIRST, cand + 2 * (size_t)CAND_FIRST, (size_t)(n - CAND_FIRST) * 8, hipMemcpyDeviceToHost));
     *n_out = n;
     return ISX_OK;
 }
@@ -1590,11 +1422,10 @@ int detect_roi(isx_warper* w, int sw, int sh, int roi[4], float mm[4], bool sync
                 if (mm) std::copy(e.mm, e.mm + 4, mm);
                 return ISX_OK;
             }
-        // detectResultRoiByBorder: the border pixels ranked on the device, the candidates for the four extrema evaluated here with the
+        // detectResultRoiByBorder: the border pixels ranked (border_scan_host), the candidates for the four extrema evaluated with the
         // host's libm (exactly the values the host-only scan of round 2 took its minima / maxima over), then OpenCV's two pole tests
-        ISX_TRY(roi_stream_of(w, &st));
         int n = 0;
-        ISX_TRY(border_scan_sync(w, sw, sh, st, "roi_border_sph", &n));
+        ISX_TRY(border_scan_host(w->proj.r_kinv, w->kind == ISX_WARP_SPHERICAL, sw, sh, w->host_cand, w->host_scratch, 0, &n));
         float emm[4];
         roi_from_candidates(w->proj, w->k, w->rinv, sw, sh, w->host_cand.data(), n, roi, emm);
         if (mm) std::copy(emm, emm + 4, mm);
@@ -1632,14 +1463,13 @@ int detect_roi(isx_warper* w, int sw, int sh, int roi[4], float mm[4], bool sync
     // pole of the cylinder within two pixels of it) the scan is the 2 (W + H) border pixels in one workgroup instead of all W x H: away from
     // the poles neither u nor v has a stationary point, so a pixel one step inside the border differs from the border's extremum by about a
     // whole unit (|grad| ~ scale / focal per pixel), four orders of magnitude above the rounding of mapForward - the extrema over the border
-    // ARE the extrema over the image, and the candidates below are evaluated exactly as before.  (ISX_ROI_FULL_SCAN: the full scan always.)
-    static const bool full_always = getenv("ISX_ROI_FULL_SCAN") != nullptr;
-    const bool border_only = !full_always && cyl_extrema_on_border(w->proj, w->k, w->rinv, sw, sh);
+    // ARE the extrema over the image, and the candidates below are evaluated exactly as before.
+    const bool border_only = cyl_extrema_on_border(w->proj, w->k, w->rinv, sw, sh);
     dim3 grid(cdiv(sw, 256), cdiv(sh, SYNC_ROWS));
     float4* blk = nullptr;
     int n = 0;
     if (border_only) {
-        ISX_TRY(border_scan_sync(w, sw, sh, st, "roi_border", &n));
+        ISX_TRY(border_scan_host(w->proj.r_kinv, w->kind == ISX_WARP_SPHERICAL, sw, sh, w->host_cand, w->host_scratch, 0, &n));
     } else {
     ISX_TRY(w->scan_blk.reserve((size_t)grid.x * grid.y * sizeof(float4)));
     blk = (float4*)w->scan_blk.p;
@@ -1828,10 +1658,8 @@ int warp_one(isx_warper* w, const isx_mat* src, const isx_mat* src_mask, const f
         const isx_mat& dd = w->st_dst.d;
         const isx_mat& dm = w->st_dmask.d;
         // k_warp_tile stores 12-byte runs at any alignment (a dense cv::Mat row need not start on a dword); the caller-mask kernel keeps its
-        // dword stores for aligned rows.  ISX_WARP_VEC=0: per-pixel stores (A/B runs)
-        static const bool vec_any = [] { const char* e = getenv("ISX_WARP_VEC"); return !(e && e[0] == '0'); }();
-        const bool vec_al = ((uintptr_t)dd.data % 4 == 0) && (dd.step % 4 == 0) && ((uintptr_t)dm.data % 4 == 0) && (dm.step % 4 == 0);
-        const bool vec = src_mask ? vec_al : vec_any;
+        // dword stores for aligned rows
+        const bool vec = ((uintptr_t)dd.data % 4 == 0) && (dd.step % 4 == 0) && ((uintptr_t)dm.data % 4 == 0) && (dm.step % 4 == 0);
         ISX_CHECK_ARG(dd.step < (1u << 24) && dm.step < (1u << 24) && (unsigned long long)dd.step * dh < (1ull << 32), ISX_ERR_UNSUPPORTED,
                       "warp_with_mask: destination larger than 4 GiB or 16 MiB per row");
         dim3 grid4(cdiv(dw, 256), cdiv(dh, 4));
@@ -1855,9 +1683,8 @@ int warp_one(isx_warper* w, const isx_mat* src, const isx_mat* src_mask, const f
         const dim3 gridt(cdiv(wcrop, 64) - bx0, cdiv(dh, 4 * WARP_WAVES));
         const bool gained = w->gain != 1.0;
         ISX_CHECK_ARG(!(gained && src_mask), ISX_ERR_UNSUPPORTED, "warp_with_mask: isx_warper_set_gain applies to tiles warped with the all-255 mask (src_mask == NULL)");
-        static const int warp_xg = [] { const char* e = getenv("ISX_WARP_XG"); return e ? atoi(e) : 0; }();
-        const int xg = (warp_xg > 0 && gridt.x >= 2 && (unsigned long long)gridt.x * gridt.y * gridt.x < (1ull << 32)) ? warp_xg : 0;   // (one block column: nothing to pair, and the magic would overflow)
-        WarpTileArgs wta{w->proj, t, sv, TileDst{(unsigned char*)dd.data, (unsigned)dd.step, (unsigned char*)dm.data, (unsigned)dm.step, wcrop, dh, bx0, xg, 0xFFFFFFFFu / gridt.x + 1u}, {}};
+        // (xg = 0: the plain block order; k_warp_tile's XCD-run order was measured and left off)
+        WarpTileArgs wta{w->proj, t, sv, TileDst{(unsigned char*)dd.data, (unsigned)dd.step, (unsigned char*)dm.data, (unsigned)dm.step, wcrop, dh, bx0, 0, 0xFFFFFFFFu / gridt.x + 1u}, {}};
         if (gained) memcpy(wta.lut, w->gain_lut, 256);
 #define ISX_WARP_TILE(KD, O16, V)                                                                                                            \
     do {                                                                                                                                     \
@@ -1870,13 +1697,13 @@ int warp_one(isx_warper* w, const isx_mat* src, const isx_mat* src_mask, const f
         if (collect) {
             // collected: leaves with the other tiles of the batch as one launch (flush_warp_batch)
             isx_warper::BatchItem bi;
-            bi.variant = (w->kind == ISX_WARP_CYLINDRICAL ? 0 : 4) | (dst->type == ISX_16SC3 ? 2 : 0) | (vec ? 1 : 0);
+            bi.variant = (w->kind == ISX_WARP_CYLINDRICAL ? 0 : 2) | (dst->type == ISX_16SC3 ? 1 : 0);
             bi.g = WarpTileGeom{wta.p, wta.t, wta.img, wta.d};
             bi.gx = gridt.x; bi.gy = gridt.y; bi.bytes = bytes;
             w->batch.push_back(bi);
         } else if (!src_mask) {
-            if (dst->type == ISX_16SC3) { if (vec) ISX_WARP_TILE_K(true, true); else ISX_WARP_TILE_K(true, false); }
-            else { if (vec) ISX_WARP_TILE_K(false, true); else ISX_WARP_TILE_K(false, false); }
+            if (dst->type == ISX_16SC3) ISX_WARP_TILE_K(true, true);
+            else ISX_WARP_TILE_K(false, true);
         } else if (dst->type == ISX_16SC3) { if (vec) ISX_WARP_FUSED(true, true); else ISX_WARP_FUSED(true, false); }
         else { if (vec) ISX_WARP_FUSED(false, true); else ISX_WARP_FUSED(false, false); }
 #undef ISX_WARP_TILE_K
@@ -1902,26 +1729,21 @@ int warp_one(isx_warper* w, const isx_mat* src, const isx_mat* src_mask, const f
         size_t ds = w->st_dst.d.step;
         // The two calls the reference makes per tile (W:229 image LINEAR / REFLECT, W:232 mask NEAREST / CONSTANT) take the tile kernels:
         // k_warp_tile without its mask output, k_warp_mask_tile.  Same limits as the fused entry (32-bit offsets from 24-bit multiplies).
-        static const bool tile_path = [] { const char* e = getenv("ISX_WARP_LITERAL_FAST"); return !(e && e[0] == '0'); }();
         const bool small = (unsigned long long)w->st_src.d.step * src->rows < (1ull << 31) && w->st_src.d.step < (1u << 24) && src->cols <= 32767 && src->rows <= 32767 &&
                            ds < (1u << 24) && (unsigned long long)ds * dh < (1ull << 32);
-        if (tile_path && small && src->type == ISX_8UC3 && interp == ISX_INTER_LINEAR && border == ISX_BORDER_REFLECT) {
-            static const bool vec = [] { const char* e = getenv("ISX_WARP_VEC"); return !(e && e[0] == '0'); }();
+        if (small && src->type == ISX_8UC3 && interp == ISX_INTER_LINEAR && border == ISX_BORDER_REFLECT) {
             const dim3 gridt(cdiv(dw, 64), cdiv(dh, 4 * WARP_WAVES));
-            static const int warp_xg = [] { const char* e = getenv("ISX_WARP_XG"); return e ? atoi(e) : 0; }();
-            const int xg = (warp_xg > 0 && gridt.x >= 2 && (unsigned long long)gridt.x * gridt.y * gridt.x < (1ull << 32)) ? warp_xg : 0;
-            const WarpTileArgs wta{w->proj, t, sv, TileDst{dp, (unsigned)ds, nullptr, 0u, dw, dh, 0, xg, 0xFFFFFFFFu / gridt.x + 1u}, {}};
-#define ISX_WARP_IMG(KD, V) ISX_LAUNCH("warp_tile_img", bytes, st, (k_warp_tile<KD, false, V, false>), gridt, dim3(64 * WARP_WAVES), 0, wta)
-            if (w->kind == ISX_WARP_CYLINDRICAL) { if (vec) ISX_WARP_IMG(ISX_WARP_CYLINDRICAL, true); else ISX_WARP_IMG(ISX_WARP_CYLINDRICAL, false); }
-            else { if (vec) ISX_WARP_IMG(ISX_WARP_SPHERICAL, true); else ISX_WARP_IMG(ISX_WARP_SPHERICAL, false); }
+            const WarpTileArgs wta{w->proj, t, sv, TileDst{dp, (unsigned)ds, nullptr, 0u, dw, dh, 0, 0, 0xFFFFFFFFu / gridt.x + 1u}, {}};      // (xg = 0: as above)
+#define ISX_WARP_IMG(KD) ISX_LAUNCH("warp_tile_img", bytes, st, (k_warp_tile<KD, false, true, false>), gridt, dim3(64 * WARP_WAVES), 0, wta)
+            if (w->kind == ISX_WARP_CYLINDRICAL) ISX_WARP_IMG(ISX_WARP_CYLINDRICAL);
+            else ISX_WARP_IMG(ISX_WARP_SPHERICAL);
 #undef ISX_WARP_IMG
-        } else if (tile_path && small && src->type == ISX_8UC1 && interp == ISX_INTER_NEAREST && border == ISX_BORDER_CONSTANT) {
-            static const bool vec = [] { const char* e = getenv("ISX_WARP_VEC"); return !(e && e[0] == '0'); }();
+        } else if (small && src->type == ISX_8UC1 && interp == ISX_INTER_NEAREST && border == ISX_BORDER_CONSTANT) {
             const WarpMaskArgs wma{w->proj, t, sv, dp, (unsigned)ds, dw, dh};
             const dim3 gridm(cdiv(dw, 64), cdiv(dh, 16));
-#define ISX_WARP_MSK(KD, V) ISX_LAUNCH("warp_tile_mask", bytes, st, (k_warp_mask_tile<KD, V>), gridm, dim3(256), 0, wma)
-            if (w->kind == ISX_WARP_CYLINDRICAL) { if (vec) ISX_WARP_MSK(ISX_WARP_CYLINDRICAL, true); else ISX_WARP_MSK(ISX_WARP_CYLINDRICAL, false); }
-            else { if (vec) ISX_WARP_MSK(ISX_WARP_SPHERICAL, true); else ISX_WARP_MSK(ISX_WARP_SPHERICAL, false); }
+#define ISX_WARP_MSK(KD) ISX_LAUNCH("warp_tile_mask", bytes, st, (k_warp_mask_tile<KD, true>), gridm, dim3(256), 0, wma)
+            if (w->kind == ISX_WARP_CYLINDRICAL) ISX_WARP_MSK(ISX_WARP_CYLINDRICAL);
+            else ISX_WARP_MSK(ISX_WARP_SPHERICAL);
 #undef ISX_WARP_MSK
         } else
         switch (src->type) {
@@ -1979,7 +1801,6 @@ int isx_warper_destroy(isx_warper* w) ISX_ENTRY {
     for (const auto& f : w->tab_fences) (void)hipEventDestroy(f.second);
     if (w->side) { (void)hipStreamSynchronize(w->side); (void)hipEventDestroy(w->ev_warp); (void)hipEventDestroy(w->ev_scan); }   // the side stream is shared per device
     if (w->pin) (void)hipHostFree(w->pin);
-    if (w->pin2) (void)hipHostFree(w->pin2);
     delete w;
     return ISX_OK;
 } ISX_EXIT("isx_warper_destroy")
@@ -2307,7 +2128,6 @@ int isx_warper_plan_status(isx_warper* w, int* mismatches) ISX_ENTRY {
     *mismatches = 0;
     ISX_HIP(hipSetDevice(w->device));
     ISX_TRY(flush_verify(w));
-    ISX_CHECK_ARG(w->verify_dropped == 0, ISX_ERR_PLAN, "planned warp: %d verification(s) were dropped under ISX_VERIFY_NEVER - this run's plans are unverified", w->verify_dropped);
     if (!w->scan_side.p) return ISX_OK;
     ISX_HIP(hipStreamSynchronize(w->side));
     ISX_HIP(hipStreamSynchronize(w->stream));

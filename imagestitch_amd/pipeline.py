@@ -165,8 +165,6 @@ class PairStitcher:
         if verify_at is not None and verify_at >= 0 and all(
                 self.warper.verify_is_light((self.imgs[i].shape[1], self.imgs[i].shape[0]), self.K, self.Rs[i]) for i in self.active):
             verify_at = -1
-        if os.environ.get("ISX_VERIFY_AT", "") != "":
-            verify_at = int(os.environ["ISX_VERIFY_AT"])
         self.mark = None
         if deferred and not interleave and verify_at is not None and verify_at >= 0 and self.L >= 1:
             self.mark = torch.cuda.Event()
@@ -208,11 +206,8 @@ class PairStitcher:
         return self.out, self.out_mask
 
     def _warps(self):
-        """The planned warps of every active tile - collected and launched as ONE kernel (isx_warper_begin_batch: blockIdx.z = tile; round 6.
-        ISX_WARP_BATCH=0: one launch per tile, for A/B runs)."""
-        batch = os.environ.get("ISX_WARP_BATCH", "1") != "0"
-        if batch:
-            self.warper.begin_batch()
+        """The planned warps of every active tile - collected and launched as ONE kernel (isx_warper_begin_batch: blockIdx.z = tile; round 6)."""
+        self.warper.begin_batch()
         try:
             for i in self.active:
                 if self.tile_cols is not None:
@@ -221,8 +216,7 @@ class PairStitcher:
         finally:
             if self.tile_cols is not None:
                 self.warper.set_dst_columns(0, 0)
-            if batch:
-                self.warper.end_batch()
+            self.warper.end_batch()
 
     def step_until_blend(self):
         """The planned step up to (not including) blend(): warps, prepare, feeds - for step_batch."""

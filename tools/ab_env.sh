@@ -1,6 +1,6 @@
 #!/usr/bin/env bash
 # Same-box A/B of environment-selected variants of ONE library build (run on the GPU box via gpurun):
-#   VARS="ISX_ROLL=0|ISX_ROLL=1,ISX_ROLL_R=7|ISX_ROLL=1" bash tools/ab_env.sh [bench args]
+#   VARS="ISX_ROLL=0|ISX_ROLL=1,ISX_PD0=0|ISX_ROLL=1" bash tools/ab_env.sh [bench args]
 # three alternations; prints Mpix/s, ms per step and the serialised per-kernel times of one step.
 IFS='|' read -ra VS <<< "${VARS:-ISX_ROLL=0|ISX_ROLL=1}"
 for r in 1 2 3; do

@@ -1,5 +1,5 @@
 """The int16 arithmetic on integer-valued floats (k_collapse_roll, k_pyr_down0 since round 4) against the integer forms it replaced
-(k_collapse_gather as the last step, k_pyr_down_multi at level 0: ISX_ROLL=0, ISX_PD0=0) and the three-launch top (ISX_TOP=0), at sizes the
+(k_collapse_gather as the last step, k_pyr_down_multi at level 0: ISX_ROLL=0, ISX_PD0=0), at sizes the
 oracle does not reach: CV_16SC3 tiles of the WHOLE short range and CV_8UC3 tiles, random masks with holes, 5 and 7 bands.  Every combination runs
 in a child process (the switches are read once); the mosaics' SHA-1 must agree.
     python tools/probes/int16_forms_probe.py [out.json]"""
@@ -44,11 +44,11 @@ if __name__ == "__main__":
     ok = True
     for (kind, w, h, bands) in CASES:
         row = {"tiles": kind, "size": [w, h], "bands": bands, "sha1": {}}
-        for roll, pd0, top in itertools.product("10", "10", "10"):
-            env = dict(os.environ, ISX_ROLL=roll, ISX_PD0=pd0, ISX_TOP=top)
+        for roll, pd0 in itertools.product("10", "10"):
+            env = dict(os.environ, ISX_ROLL=roll, ISX_PD0=pd0)
             o = subprocess.run([sys.executable, __file__, "--child", kind, str(w), str(h), str(bands)], env=env, capture_output=True, text=True)
             line = [l for l in o.stdout.splitlines() if l.startswith("RESULT")]
-            row["sha1"]["ROLL=%s PD0=%s TOP=%s" % (roll, pd0, top)] = line[0].split(None, 1)[1] if line else ("FAILED: " + o.stderr[-300:])
+            row["sha1"]["ROLL=%s PD0=%s" % (roll, pd0)] = line[0].split(None, 1)[1] if line else ("FAILED: " + o.stderr[-300:])
         hs = {v.split()[0] for v in row["sha1"].values()}
         row["identical"] = len(hs) == 1 and not any(v.startswith("FAILED") for v in row["sha1"].values())
         ok = ok and row["identical"]
