@@ -96,3 +96,37 @@ class GraphCutSeamFinder:
     def release():
         """Return the graph and staging buffers the finder keeps per calling thread between calls (isx_graphcut_seam_release)."""
         check(_lib.load().isx_graphcut_seam_release())
+
+
+class VoronoiSeamFinder:
+    """The S demo's seam finder: makePtr<detail::VoronoiSeamFinder>() (S:1180), find at S:1192.  Masks only - two city-block distance
+    transforms and a compare per overlapping pair (isx_voronoi_seam_find).  On device masks nothing is synchronised, so find
+    can be captured into a hipGraph on `stream` once reserve() has sized the scratch."""
+
+    def __init__(self, device=0, stream=None):
+        self.device, self.stream = device, stream
+
+    def find(self, src_or_sizes, corners, masks):
+        """find(src, corners, masks) or find(sizes, corners, masks): the images are never read, only their sizes ((width, height) pairs,
+        or anything with a .shape of rows x cols [x channels]); masks = CV_8U arrays / tensors edited in place."""
+        n = len(src_or_sizes)
+        if len(corners) != n or len(masks) != n:
+            raise _lib.IsxError(1, "find: src, corners and masks differ in length")
+        sizes = [(int(a.shape[1]), int(a.shape[0])) if hasattr(a, "shape") else (int(a[0]), int(a[1])) for a in src_or_sizes]
+        mats_m = (_lib.IsxMat * max(n, 1))(*[as_mat(m) for m in masks])
+        sz = (C.c_int * max(2 * n, 1))(*[v for s in sizes for v in s])
+        c = (C.c_int * max(2 * n, 1))(*[int(v) for p in corners for v in p])
+        ptr = getattr(self.stream, "cuda_stream", self.stream)
+        check(_lib.load().isx_voronoi_seam_find(n, sz, c, mats_m, int(self.device), C.c_void_p(ptr or 0)))
+        return masks
+
+    def reserve(self, max_roi_width, max_roi_height):
+        """Size the calling thread's scratch for overlaps of up to max_roi_width x max_roi_height before a capture
+        (isx_voronoi_seam_reserve); it must then stay as it is while the captured graph exists."""
+        check(_lib.load().isx_voronoi_seam_reserve(int(max_roi_width), int(max_roi_height), int(self.device)))
+        return self
+
+    @staticmethod
+    def release():
+        """Return the scratch the finder keeps per calling thread between find() calls (isx_voronoi_seam_release)."""
+        check(_lib.load().isx_voronoi_seam_release())

@@ -280,6 +280,37 @@ private:
     int cost_type_, device_;
 };
 
+// VoronoiSeamFinder (S:1180) and its find(images_warped_f, corners, masks_seam) (S:1192): masks only - two city-block distance transforms
+// and a compare per overlapping pair on the GPU (isx_voronoi_seam_find).  masks: CV_8U, edited in place; host or device mats.  On device
+// masks nothing is synchronised: with a stream set and reserve() called first, find can be captured into a hipGraph.
+class VoronoiSeamFinder {
+public:
+    explicit VoronoiSeamFinder(int device = 0, void* hip_stream = nullptr) : device_(device), stream_(hip_stream) {}
+    void setStream(void* hip_stream) { stream_ = hip_stream; }
+    void find(const std::vector<Size>& sizes, const std::vector<Point>& corners, std::vector<Mat>& masks) {
+        if (sizes.size() != corners.size() || sizes.size() != masks.size()) throw Exception(ISX_ERR_INVALID, "find: sizes, corners and masks differ in length");
+        std::vector<isx_mat> mk(masks.size());
+        std::vector<int> c, sz;
+        for (size_t i = 0; i < masks.size(); ++i) {
+            mk[i] = *masks[i].c();
+            c.push_back(corners[i].x); c.push_back(corners[i].y);
+            sz.push_back(sizes[i].width); sz.push_back(sizes[i].height);
+        }
+        check(isx_voronoi_seam_find((int)masks.size(), sz.data(), c.data(), mk.data(), device_, stream_));
+    }
+    // the images are never read: only their sizes are used
+    void find(const std::vector<Mat>& src, const std::vector<Point>& corners, std::vector<Mat>& masks) {
+        std::vector<Size> sizes;
+        for (size_t i = 0; i < src.size(); ++i) sizes.push_back(src[i].size());
+        find(sizes, corners, masks);
+    }
+    void reserve(int max_roi_width, int max_roi_height) { check(isx_voronoi_seam_reserve(max_roi_width, max_roi_height, device_)); }
+    static void release() { check(isx_voronoi_seam_release()); }
+private:
+    int device_;
+    void* stream_;
+};
+
 // cv::imread(path) (W:166): the decoder follows the file's signature, as OpenCV's does - "BM" bitmaps and JFIF / Exif JPEGs;
 // cv::imwrite(path, img) for .bmp and .jpg (W:155-156,315; "pano.jpg" S:1282)
 inline Mat imread(const char* path) {

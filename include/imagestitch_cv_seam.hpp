@@ -7,7 +7,7 @@
 // (DESIGN.md §8).  A header of its own, so that imagestitch_cv.hpp and the stub it is tested against stay as they were.
 //
 // Compiled inside the reference tree, where OpenCV 3.4.2 is installed; in this repository against tests/cpp/opencv_stub
-// (tests/cpp/graphcut_demo.cpp, run by tests/test_gpu_graphcut_seam.py).
+// (tests/cpp/graphcut_demo.cpp, run by tests/test_gpu_graphcut_seam.py; tests/cpp/voronoi_demo.cpp, run by tests/test_gpu_voronoi_seam.py).
 #ifndef IMAGESTITCH_CV_SEAM_HPP
 #define IMAGESTITCH_CV_SEAM_HPP
 
@@ -48,6 +48,30 @@ public:
 
 private:
     isx::GraphCutSeamFinder f_;
+};
+
+// cv::detail::VoronoiSeamFinder's find over isx::VoronoiSeamFinder (S:1180, S:1192):  makePtr<isx_cv::HipVoronoiSeamFinder>().  The images are
+// not mapped: only their sizes are used.
+class HipVoronoiSeamFinder : public cv::detail::SeamFinder {
+public:
+    explicit HipVoronoiSeamFinder(int device = 0) : f_(device) {}
+    void find(const std::vector<cv::UMat>& src, const std::vector<cv::Point>& corners, std::vector<cv::UMat>& masks) override {
+        CV_Assert(src.size() == corners.size() && masks.size() == corners.size());
+        std::vector<cv::Mat> mk;                 // mapped to the end of this call, as above
+        std::vector<isx::Mat> mm;
+        std::vector<isx::Size> sizes;
+        std::vector<isx::Point> pts;
+        for (size_t i = 0; i < src.size(); ++i) mk.push_back(masks[i].getMat(cv::ACCESS_RW));
+        for (size_t i = 0; i < src.size(); ++i) {
+            mm.push_back(isx::Mat(mk[i]));
+            sizes.push_back(isx::Size(src[i].cols, src[i].rows));
+            pts.push_back(isx::Point(corners[i].x, corners[i].y));
+        }
+        f_.find(sizes, pts, mm);
+    }
+
+private:
+    isx::VoronoiSeamFinder f_;
 };
 
 }  // namespace isx_cv

@@ -442,6 +442,30 @@ int isx_graphcut_seam_find_pair(const isx_mat* image1, const isx_mat* image2, co
  * calls; this returns them.  PER THREAD and not freed at thread exit, as for isx_dp_seam_release.                                      */
 int isx_graphcut_seam_release(void);
 
+/* ---- the Voronoi seam finder of the S demo (S:1180, S:1192) ------------------------------------------------------------------ */
+/* seam_finder = makePtr<detail::VoronoiSeamFinder>() (S:1180); seam_finder->find(images_warped_f, corners, masks_seam) (S:1192), OpenCV
+ * 3.4.2's PairwiseSeamFinder + VoronoiSeamFinder::findInPair restated (OpenCV parity unpinned): for every pair i < j (outer
+ * i, inner j) whose overlapRoi is not empty, on the masks as the earlier pairs left them: the two masks' windows over the roi and a gap of
+ * 10 cells around it (0 outside a tile), the cells both cover removed from each, distanceTransform(DIST_L1, 3) to what is left of each,
+ * and over the roi mask2 = 0 where dist1 < dist2 (compared as the floats the transform returns), mask1 = 0 elsewhere - ties and "neither
+ * tile has a cell of its own" included.  Pixels are never read: sizes_wh holds (width, height) per image.
+ * masks: n CV_8UC1 mats, host or device, any pointer alignment and step, edited in place.  Checked before the first pair writes: null
+ * pointers or a negative size -> ISX_ERR_INVALID; a mask that is not CV_8UC1 -> ISX_ERR_TYPE; a mask whose rows / cols differ from
+ * sizes_wh -> ISX_ERR_SIZE; an overlap that passes 32768 cells a side with its gap -> ISX_ERR_UNSUPPORTED.  Fewer than 2 images: nothing
+ * to do.
+ * Device masks: three kernels per pair are enqueued on hip_stream, nothing is synchronised or read back, and the call works on a
+ * capturing stream.  Host masks are staged to the device and back, which synchronises: on a capturing stream -> ISX_ERR_STATE with nothing
+ * enqueued.  The scratch (about 8 B per cell of the largest padded overlap) is kept per calling thread and grows only outside a capture:
+ * a captured call that needs more than it holds -> ISX_ERR_STATE with nothing enqueued (isx_voronoi_seam_reserve first).               */
+int isx_voronoi_seam_find(int num_images, const int* sizes_wh, const int* corners_xy, isx_mat* masks, int device, void* hip_stream);
+/* Sizes the calling thread's scratch for overlaps of up to max_roi_width x max_roi_height (the roi, without the gap) ahead of a stream
+ * capture (S:1180: the finder's construction).  A captured graph keeps pointing at this scratch: growing it (a larger reserve or find
+ * outside the capture, another device) or releasing it while such a graph exists is the caller's error.                                */
+int isx_voronoi_seam_reserve(int max_roi_width, int max_roi_height, int device);
+/* Returns the scratch and the staged host masks of the calling thread (the finder going out of scope, S:1192).  PER THREAD and not
+ * freed at thread exit, as for isx_dp_seam_release.                                                                                    */
+int isx_voronoi_seam_release(void);
+
 /* ---- on-disk format either side of the path: .bmp (W:166 imread, W:155-156,315 imwrite) ----------- */
 /* Reading: uncompressed Windows bitmaps only (the reference's inputs and committed artefacts are BMPs).
  * isx_bmp_read = cv::imread(path) with IMREAD_COLOR: `out` is a CV_8UC3 mat (host or device) of the size
