@@ -9,7 +9,7 @@ with focal length F rotated by -/+ yaw about the vertical axis.  Without input f
 
 Steps = the reference's main(): warp image + mask (W:223-233), gain apply with given gains (W:241-244) - or, with
 --estimate-gains, the GainCompensator's feed on the warped tiles (W:238-240) and its apply (W:241-244) -, convertTo(CV_32F) +
-DP seam finder (S:87-1093; --seam graphcut: W's own GraphCutSeamFinder, W:257-264; --seam voronoi: the VoronoiSeamFinder S constructs, S:1180), dilate 20x20 & warped mask (W:286-301), FeatherBlender 0.1 (W:278-313) or the
+DP seam finder (S:87-1093, --seam-cost color_grad: DpSeamFinder::COLOR_GRAD W:255; --seam graphcut: W's own GraphCutSeamFinder, W:257-264; --seam voronoi: the VoronoiSeamFinder S constructs, S:1180), dilate 20x20 & warped mask (W:286-301), FeatherBlender 0.1 (W:278-313) or the
 multi-band blender (W:271-273), imwrite (W:315)."""
 import argparse
 import os
@@ -36,6 +36,8 @@ def main():
                     help="dp: the DP seam finder on a copy of the warped masks (S:1192); graphcut: W's own GraphCutSeamFinder(COST_COLOR), "
                          "which edits the warped masks while masks_seam stays their unedited copy (W:247-264); voronoi: the VoronoiSeamFinder of "
                          "S:1180 on masks_seam (S:1192), masks only")
+    ap.add_argument("--seam-cost", default="color", choices=["color", "color_grad"],
+                    help="--seam dp: the finder's cost function, DpSeamFinder::COLOR (W:253) or DpSeamFinder::COLOR_GRAD (W:255, S:1183)")
     ap.add_argument("--out", default="pano.bmp")
     ap.add_argument("--separate", action="store_true",
                     help="gain apply and mask preparation as passes of their own (isx_gain_apply, isx_mask_dilate_and) instead of folded into the warp's "
@@ -73,7 +75,8 @@ def main():
     elif a.seam == "voronoi":
         isx.VoronoiSeamFinder().find(warped, corners, seam)                 # S:1180, S:1192 as written: find edits masks_seam
     else:
-        isx.DpSeamFinder().find([w.astype(np.float32) for w in warped], corners, seam)   # W:259-262
+        cost = isx.DP_COLOR_GRAD if a.seam_cost == "color_grad" else isx.DP_COLOR
+        isx.DpSeamFinder(cost).find([w.astype(np.float32) for w in warped], corners, seam)   # W:253 / W:255, W:259-262
     sizes = [(w.shape[1], w.shape[0]) for w in warped]
     if a.blend == "feather":
         blender = isx.FeatherBlender(False, 0.1)                            # W:278-280

@@ -9,7 +9,7 @@ from ._lib import (BORDER_CONSTANT, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_R
 from .blender import Blender, FeatherBlender, MultiBandBlender, NoBlender, convert_to, dilate_and, gain_apply  # noqa: F401
 from .exposure import GainCompensator  # noqa: F401
 from .imgio import imread, imwrite  # noqa: F401
-from .seam import DpSeamFinder, GraphCutSeamFinder, VoronoiSeamFinder, seam_estimate  # noqa: F401
+from .seam import DP_COLOR, DP_COLOR_GRAD, DpSeamFinder, GraphCutSeamFinder, VoronoiSeamFinder, seam_estimate, seam_gradients  # noqa: F401
 from .warper import CylindricalWarper, RotationWarper, SphericalWarper, remap  # noqa: F401
 
-__all__ = ["Blender", "MultiBandBlender", "FeatherBlender", "NoBlender", "convert_to", "dilate_and", "gain_apply", "GainCompensator", "imread", "imwrite", "seam_estimate", "DpSeamFinder", "GraphCutSeamFinder", "VoronoiSeamFinder", "remap", "CylindricalWarper", "SphericalWarper", "RotationWarper", "IsxError", "load"]
+__all__ = ["Blender", "MultiBandBlender", "FeatherBlender", "NoBlender", "convert_to", "dilate_and", "gain_apply", "GainCompensator", "imread", "imwrite", "seam_estimate", "seam_gradients", "DP_COLOR", "DP_COLOR_GRAD", "DpSeamFinder", "GraphCutSeamFinder", "VoronoiSeamFinder", "remap", "CylindricalWarper", "SphericalWarper", "RotationWarper", "IsxError", "load"]

@@ -97,7 +97,11 @@ _SIGS = {
     "isx_voronoi_seam_release": [],
     "isx_seam_estimate": [_MP, _MP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _MP, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int,
                           C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_void_p],
+    "isx_seam_estimate_cost": [_MP, _MP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _MP, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int,
+                               C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p],
+    "isx_seam_gradients": [_MP, C.POINTER(C.c_int), _MP, _MP, C.c_int, C.c_void_p],
     "isx_dp_seam_find": [C.c_int, _MP, C.POINTER(C.c_int), _MP, C.c_int, C.c_void_p],
+    "isx_dp_seam_find_cost": [C.c_int, _MP, C.POINTER(C.c_int), _MP, C.c_int, C.c_int, C.c_void_p],
     "isx_dp_seam_release": [],
     "isx_bmp_size": [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "isx_bmp_read": [C.c_char_p, _MP],

@@ -1,6 +1,7 @@
 // seam.hip — SURVEY §8(f) N1, the data-parallel part of the in-tree DP seam finder
 // (S = 动态规划法寻找最佳缝合线/.../动态规划法寻找最佳缝合线.cpp) on gfx950:
-//   k_seam_costs  computeCosts S:733-803 (costFunc_ COLOR): costV / costH of one intersection component
+//   k_seam_grad   computeGradients S:549-572 (costFunc_ COLOR_GRAD only): |Sobel x| and |Sobel y| of BGR2GRAY of one tile over a rectangle
+//   k_seam_costs  computeCosts S:733-803 (costFunc_ COLOR or COLOR_GRAD): costV / costH of one intersection component
 //   k_seam_dp     the dynamic programme of estimateSeam S:858-916: one wavefront step per row (column) of the
 //                 component's ROI, the cells of a step in parallel, previous step's cost / reachability in LDS
 //   host          seam direction + swap S:825-842, backtracking through the control map S:918-953
@@ -51,23 +52,103 @@ __device__ __forceinline__ float seam_diff(const SeamGeom& g, int y1, int x1, in
     }
 }
 
+// computeGradients S:549-572 for one tile, evaluated only where computeCosts reads it.  gray = cvtColor(COLOR_BGR2GRAY) (S:558, S:566), then
+// Sobel(gray, CV_32F, 1, 0) and (0, 1) (S:562-563, S:570-571): 3 x 3, BORDER_REFLECT_101 at the IMAGE's edges, row pass then column pass in
+// the order DESIGN.md §8 fixes.  Only magnitudes are ever read (S:769-770, S:794-795), so |gradx| and |grady| are what is stored.
+// One block = a GRAD_TW x GRAD_TH tile of the rectangle (x0, y0, w, h; image coordinates); gray with a one-pixel halo is staged once in LDS.
+// A staged position is clamped into the image after the reflection, so a rectangle that leaves the image reads defined pixels.
+constexpr int GRAD_TW = 64, GRAD_TH = 16;
+
+__device__ __forceinline__ int seam_reflect101(int p, int n) {
+    p = p < 0 ? -p : p;
+    p = p >= n ? 2 * n - 2 - p : p;
+    return min(max(p, 0), n - 1);   // n == 1 reads index 0
+}
+
 template <bool U8>
-__global__ __launch_bounds__(256) void k_seam_costs(SeamGeom g, float* costV, float* costH) {
+__device__ __forceinline__ float seam_gray(const unsigned char* img, size_t step, int y, int x) {
+    if constexpr (U8) {
+        const unsigned char* p = img + (size_t)y * step + (size_t)x * 3;
+        return (float)(((int)p[0] * 1868 + (int)p[1] * 9617 + (int)p[2] * 4899 + 8192) >> 14);
+    } else {
+        const float* p = (const float*)(img + (size_t)y * step) + (size_t)x * 3;
+        return (p[0] * 0.114f + p[1] * 0.587f) + p[2] * 0.299f;
+    }
+}
+
+template <bool U8>
+__global__ __launch_bounds__(256) void k_seam_grad(const unsigned char* img, size_t step, int rows, int cols, int x0, int y0, int w, int h,
+                                                   float* agx, float* agy, size_t xstep, size_t ystep) {
+    __shared__ float gray[GRAD_TH + 2][GRAD_TW + 2];
+    const int bx = blockIdx.x * GRAD_TW, by = blockIdx.y * GRAD_TH;
+    for (int i = threadIdx.x; i < (GRAD_TH + 2) * (GRAD_TW + 2); i += 256) {
+        const int ly = i / (GRAD_TW + 2), lx = i - ly * (GRAD_TW + 2);
+        // cells of the tile past the rectangle's halo are never used: they re-read the halo's pixel
+        const int iy = seam_reflect101(y0 + min(by + ly, h + 1) - 1, rows), ix = seam_reflect101(x0 + min(bx + lx, w + 1) - 1, cols);
+        gray[ly][lx] = seam_gray<U8>(img, step, iy, ix);
+    }
+    __syncthreads();
+    const int lx = threadIdx.x & 63, ly0 = (threadIdx.x >> 6) * 4;
+    const int cx = bx + lx;
+    // row pass for the six rows the thread's four outputs read: d = Sobel x's difference, s = Sobel y's smoothing
+    float d[6], s[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const float a = gray[ly0 + k][lx], b = gray[ly0 + k][lx + 1], c = gray[ly0 + k][lx + 2];
+        d[k] = c - a;
+        s[k] = (a + c) + (b + b);
+    }
+    if (cx >= w) return;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int cy = by + ly0 + k;
+        if (cy >= h) break;
+        agx[(size_t)cy * xstep + cx] = fabsf((d[k] + d[k + 2]) + (d[k + 1] + d[k + 1]));
+        agy[(size_t)cy * ystep + cx] = fabsf(s[k + 2] - s[k]);
+    }
+}
+
+// |gradx| / |grady| of both tiles over the component's rectangle widened by one pixel on every side (all that S:769-770 and S:794-795 can
+// read, also when the rectangle is not the label's true bounding box): (rh + 2) x (rw + 2) floats each, cell (y, x) at [cy + 1][cx + 1].
+struct SeamGrad { const float *gx1, *gy1, *gx2, *gy2; };
+
+// GRAD = costFunc_ COLOR_GRAD: the cell is costColor / costGrad (S:767-772, S:792-797); the quotient is IEEE's correctly rounded one
+// (hipcc's default for fp32 division, -fhip-fp32-correctly-rounded-divide-sqrt).
+template <bool U8, bool GRAD>
+__global__ __launch_bounds__(256) void k_seam_costs(SeamGeom g, float* costV, float* costH, SeamGrad gr) {
     const int cx = blockIdx.x * 64 + (threadIdx.x & 63), cy = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (cx > g.rw || cy > g.rh) return;
     const int x = g.rx + cx, y = g.ry + cy;
     const float bad = 3.f * 255.f * 255.f;   // normL2(Point3f(255, 255, 255), Point3f(0, 0, 0)), S:754
     const bool here = seam_label(g, y, x) == g.label;
+    const size_t gi = (size_t)(cy + 1) * (g.rw + 2) + (cx + 1);
     if (cy < g.rh) {   // S:757-779
         float c = bad;
-        if (here && x > 0 && seam_label(g, y, x - 1) == g.label)
+        if (here && x > 0 && seam_label(g, y, x - 1) == g.label) {
             c = (seam_diff<U8>(g, y + g.dy1, x + g.dx1 - 1, y + g.dy2, x + g.dx2) + seam_diff<U8>(g, y + g.dy1, x + g.dx1, y + g.dy2, x + g.dx2 - 1)) / 2;
+            if constexpr (GRAD) {
+                float cg = gr.gx1[gi] + gr.gx1[gi - 1];
+                cg = cg + gr.gx2[gi];
+                cg = cg + gr.gx2[gi - 1];
+                cg = cg + 1.f;
+                c = c / cg;
+            }
+        }
         costV[(size_t)cy * (g.rw + 1) + cx] = c;
     }
     if (cx < g.rw) {   // S:784-802
         float c = bad;
-        if (here && y > 0 && seam_label(g, y - 1, x) == g.label)
+        if (here && y > 0 && seam_label(g, y - 1, x) == g.label) {
             c = (seam_diff<U8>(g, y + g.dy1 - 1, x + g.dx1, y + g.dy2, x + g.dx2) + seam_diff<U8>(g, y + g.dy1, x + g.dx1, y + g.dy2 - 1, x + g.dx2)) / 2;
+            if constexpr (GRAD) {
+                const size_t up = gi - (size_t)(g.rw + 2);
+                float cg = gr.gy1[gi] + gr.gy1[up];
+                cg = cg + gr.gy2[gi];
+                cg = cg + gr.gy2[up];
+                cg = cg + 1.f;
+                c = c / cg;
+            }
+        }
         costH[(size_t)cy * g.rw + cx] = c;
     }
 }
@@ -228,7 +309,17 @@ __global__ __launch_bounds__(SEAM_NT) void k_seam_dp_global(const float4* ra, co
     if (threadIdx.x == 0) *found = reach[(size_t)cur * n + (horiz ? dy : dx)] ? 1 : 0;   // S:918
 }
 
-struct SeamScratch { MatStage stages[3]; DevBuf scratch; int device = -1; };
+struct SeamScratch {
+    MatStage stages[3]; DevBuf scratch; DevBuf grad; int device = -1;   // grad: the four gradient maps of a COLOR_GRAD estimate
+    void release() {
+        for (int i = 0; i < 3; ++i) stages[i].buf.release();
+        scratch.release();
+        grad.release();
+    }
+    void use_device(int dev) {   // the buffers live on one device: a call for another one starts afresh
+        if (device != dev) { release(); device = dev; }
+    }
+};
 SeamScratch& seam_scratch() {
     static thread_local SeamScratch* s = new SeamScratch();   // never destroyed at thread exit (the HIP runtime may be gone by then)
     return *s;
@@ -239,18 +330,33 @@ SeamScratch& seam_scratch() {
 namespace isx {
 void seam_scratch_release() {
     SeamScratch& ss = seam_scratch();
-    for (int i = 0; i < 3; ++i) ss.stages[i].buf.release();
-    ss.scratch.release();
+    ss.release();
     ss.device = -1;
 }
 }  // namespace isx
 
+namespace {
+
+// One k_seam_grad launch: |gradx| / |grady| of `img` (a device mat, CV_32FC3 or CV_8UC3) over the w x h rectangle at (x0, y0), xstep / ystep floats per output row.
+int seam_grad_launch(const isx_mat& img, int x0, int y0, int w, int h, float* agx, float* agy, size_t xstep, size_t ystep, hipStream_t st) {
+    const dim3 grid(cdiv(w, GRAD_TW), cdiv(h, GRAD_TH));
+    const double bytes = (double)w * h * ((img.type == ISX_8UC3 ? 3.0 : 12.0) + 8.0);
+    if (img.type == ISX_8UC3)
+        ISX_LAUNCH("seam_grad", bytes, st, (k_seam_grad<true>), grid, dim3(256), 0, (const unsigned char*)img.data, img.step, img.rows, img.cols, x0, y0, w, h, agx, agy, xstep, ystep);
+    else
+        ISX_LAUNCH("seam_grad", bytes, st, (k_seam_grad<false>), grid, dim3(256), 0, (const unsigned char*)img.data, img.step, img.rows, img.cols, x0, y0, w, h, agx, agy, xstep, ystep);
+    return ISX_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
-int isx_seam_estimate(const isx_mat* image1, const isx_mat* image2, int tl1_x, int tl1_y, int tl2_x, int tl2_y, int union_tl_x, int union_tl_y,
-                      const isx_mat* labels, int label, const int roi[4], int p1_x, int p1_y, int p2_x, int p2_y,
-                      int* seam_xy, int cap, int* seam_len, int* is_horizontal, int device, void* hip_stream) ISX_ENTRY {
+int isx_seam_estimate_cost(const isx_mat* image1, const isx_mat* image2, int tl1_x, int tl1_y, int tl2_x, int tl2_y, int union_tl_x, int union_tl_y,
+                           const isx_mat* labels, int label, const int roi[4], int p1_x, int p1_y, int p2_x, int p2_y,
+                           int* seam_xy, int cap, int* seam_len, int* is_horizontal, int cost_func, int device, void* hip_stream) ISX_ENTRY {
     clear_error();
+    ISX_CHECK_ARG(cost_func == ISX_DP_COLOR || cost_func == ISX_DP_COLOR_GRAD, ISX_ERR_INVALID, "seam_estimate: cost_func %d is neither ISX_DP_COLOR nor ISX_DP_COLOR_GRAD (S:71)", cost_func);
     ISX_TRY(check_mat(image1, "seam_estimate: image1"));
     ISX_TRY(check_mat(image2, "seam_estimate: image2"));
     ISX_TRY(check_mat(labels, "seam_estimate: labels"));
@@ -280,11 +386,7 @@ int isx_seam_estimate(const isx_mat* image1, const isx_mat* image2, int tl1_x, i
     hipStream_t st = (hipStream_t)hip_stream;
     // staging and scratch persist per host thread (grow-only; isx_dp_seam_release frees them: a finder calls this once per conflict)
     SeamScratch& ss = seam_scratch();
-    if (ss.device != device) {   // the buffers live on one device: a call for another one starts afresh
-        for (int i = 0; i < 3; ++i) ss.stages[i].buf.release();
-        ss.scratch.release();
-        ss.device = device;
-    }
+    ss.use_device(device);
     MatStage &s1 = ss.stages[0], &s2 = ss.stages[1], &sl = ss.stages[2];
     ISX_TRY(s1.use_in(image1, st, "seam_estimate: image1"));
     ISX_TRY(s2.use_in(image2, st, "seam_estimate: image2"));
@@ -310,8 +412,20 @@ int isx_seam_estimate(const isx_mat* image1, const isx_mat* image2, int tl1_x, i
     float2* rb = (float2*)((char*)ra + ra_b);
     dim3 grid(cdiv(rw + 1, 64), cdiv(rh + 1, 4));
     const double cbytes = (double)rw * rh * ((image1->type == ISX_8UC3 ? 6.0 : 24.0) + 4.0 + 8.0);
-    if (image1->type == ISX_8UC3) ISX_LAUNCH("seam_costs", cbytes, st, (k_seam_costs<true>), grid, dim3(256), 0, g, costV, costH);
-    else ISX_LAUNCH("seam_costs", cbytes, st, (k_seam_costs<false>), grid, dim3(256), 0, g, costV, costH);
+    SeamGrad gr{nullptr, nullptr, nullptr, nullptr};
+    if (cost_func == ISX_DP_COLOR_GRAD) {   // computeGradients S:398-399, S:549-572: here per estimateSeam, over what this component's costs can read
+        const size_t gn = (size_t)(rw + 2) * (rh + 2), gm_b = (gn * 4 + 255) & ~(size_t)255;
+        ISX_TRY(ss.grad.reserve(4 * gm_b));
+        float* gm[4];
+        for (int i = 0; i < 4; ++i) gm[i] = (float*)((char*)ss.grad.p + i * gm_b);
+        ISX_TRY(seam_grad_launch(s1.d, rx + dx1 - 1, ry + dy1 - 1, rw + 2, rh + 2, gm[0], gm[1], (size_t)rw + 2, (size_t)rw + 2, st));
+        ISX_TRY(seam_grad_launch(s2.d, rx + dx2 - 1, ry + dy2 - 1, rw + 2, rh + 2, gm[2], gm[3], (size_t)rw + 2, (size_t)rw + 2, st));
+        gr = SeamGrad{gm[0], gm[1], gm[2], gm[3]};
+        const double gbytes = cbytes + (double)rw * rh * 32.0;
+        if (image1->type == ISX_8UC3) ISX_LAUNCH("seam_costs_grad", gbytes, st, (k_seam_costs<true, true>), grid, dim3(256), 0, g, costV, costH, gr);
+        else ISX_LAUNCH("seam_costs_grad", gbytes, st, (k_seam_costs<false, true>), grid, dim3(256), 0, g, costV, costH, gr);
+    } else if (image1->type == ISX_8UC3) ISX_LAUNCH("seam_costs", cbytes, st, (k_seam_costs<true, false>), grid, dim3(256), 0, g, costV, costH, gr);
+    else ISX_LAUNCH("seam_costs", cbytes, st, (k_seam_costs<false, false>), grid, dim3(256), 0, g, costV, costH, gr);
 #define ISX_SEAM_DP(E)                                                                                                                    \
     do {                                                                                                                                  \
         ISX_HIP(hipFuncSetAttribute((const void*)k_seam_dp<E>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));                  \
@@ -366,6 +480,43 @@ int isx_seam_estimate(const isx_mat* image1, const isx_mat* image2, int tl1_x, i
                   "seam_estimate: the restored seam does not join the tips (CV_Assert, S:953-954)");
     *seam_len = len;
     return ISX_OK;
+} ISX_EXIT("isx_seam_estimate_cost")
+
+int isx_seam_estimate(const isx_mat* image1, const isx_mat* image2, int tl1_x, int tl1_y, int tl2_x, int tl2_y, int union_tl_x, int union_tl_y,
+                      const isx_mat* labels, int label, const int roi[4], int p1_x, int p1_y, int p2_x, int p2_y,
+                      int* seam_xy, int cap, int* seam_len, int* is_horizontal, int device, void* hip_stream) ISX_ENTRY {
+    return isx_seam_estimate_cost(image1, image2, tl1_x, tl1_y, tl2_x, tl2_y, union_tl_x, union_tl_y, labels, label, roi, p1_x, p1_y, p2_x, p2_y,
+                                  seam_xy, cap, seam_len, is_horizontal, ISX_DP_COLOR, device, hip_stream);
 } ISX_EXIT("isx_seam_estimate")
+
+int isx_seam_gradients(const isx_mat* image, const int rect[4], isx_mat* abs_gradx, isx_mat* abs_grady, int device, void* hip_stream) ISX_ENTRY {
+    clear_error();
+    ISX_TRY(check_mat(image, "seam_gradients: image"));
+    ISX_TRY(check_mat(abs_gradx, "seam_gradients: abs_gradx"));
+    ISX_TRY(check_mat(abs_grady, "seam_gradients: abs_grady"));
+    ISX_CHECK_ARG(rect != nullptr, ISX_ERR_INVALID, "seam_gradients: null argument");
+    ISX_CHECK_ARG(image->type == ISX_32FC3 || image->type == ISX_8UC3, ISX_ERR_TYPE, "seam_gradients: the image must have CV_32FC3 or CV_8UC3 type (S:551), got %s",
+                  type_name(image->type));
+    ISX_CHECK_ARG(abs_gradx->type == ISX_32FC1 && abs_grady->type == ISX_32FC1, ISX_ERR_TYPE, "seam_gradients: the outputs must be CV_32FC1 (S:562-563), got %s / %s",
+                  type_name(abs_gradx->type), type_name(abs_grady->type));
+    const int x0 = rect[0], y0 = rect[1], w = rect[2], h = rect[3];
+    ISX_CHECK_ARG(w > 0 && h > 0 && x0 >= 0 && y0 >= 0 && x0 <= image->cols - w && y0 <= image->rows - h, ISX_ERR_INVALID,
+                  "seam_gradients: the rectangle (%d,%d) %dx%d lies outside the %dx%d image", x0, y0, w, h, image->cols, image->rows);
+    ISX_CHECK_ARG(abs_gradx->rows == h && abs_gradx->cols == w && abs_grady->rows == h && abs_grady->cols == w, ISX_ERR_SIZE,
+                  "seam_gradients: the outputs must have the rectangle's size %dx%d", w, h);
+    ISX_CHECK_ARG(abs_gradx->step % 4 == 0 && abs_grady->step % 4 == 0, ISX_ERR_INVALID, "seam_gradients: the outputs' steps must be multiples of 4 bytes");
+    ISX_HIP(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    SeamScratch& ss = seam_scratch();
+    ss.use_device(device);
+    MatStage &si = ss.stages[0], &sx = ss.stages[1], &sy = ss.stages[2];
+    ISX_TRY(si.use_in(image, st, "seam_gradients: image"));
+    ISX_TRY(sx.use_out(abs_gradx, st, "seam_gradients: abs_gradx"));
+    ISX_TRY(sy.use_out(abs_grady, st, "seam_gradients: abs_grady"));
+    ISX_TRY(seam_grad_launch(si.d, x0, y0, w, h, (float*)sx.d.data, (float*)sy.d.data, sx.d.step / 4, sy.d.step / 4, st));
+    ISX_TRY(sx.finish_out(st));
+    ISX_TRY(sy.finish_out(st));
+    return ISX_OK;
+} ISX_EXIT("isx_seam_gradients")
 
 }  // extern "C"

@@ -1,9 +1,10 @@
 // seamfind.cpp — SURVEY §8(f) N1: the reference's in-tree DP seam finder as a whole
-// (S = 动态规划法寻找最佳缝合线/.../动态规划法寻找最佳缝合线.cpp, itself a restatement of cv::detail::DpSeamFinder, costFunc_ COLOR):
+// (S = 动态规划法寻找最佳缝合线/.../动态规划法寻找最佳缝合线.cpp, itself a restatement of cv::detail::DpSeamFinder, costFunc_ COLOR or COLOR_GRAD):
 //   find S:87-124 -> process S:127-193 -> findComponents S:196-308, findEdges S:311-392, resolveConflicts S:395-546
 //   (hasOnlyOneNeighbor S:574-582, getSeamTips S:607-706 with closeToContour S:585-604 and cv::partition,
 //   estimateSeam S:806-957, updateLabelsUsingSeam S:960-1093).
-// The component / contour / graph logic is sequential host code over union-sized label images (a few MB); the cost
+// The component / contour / graph logic is sequential host code over union-sized label images (a few MB); the gradient maps of
+// COLOR_GRAD (computeGradients S:549-572, here per estimateSeam over the component's rectangle instead of S:398-399's whole images), the cost
 // maps and the dynamic programme of every estimateSeam call run on the GPU (isx_seam_estimate, seam.hip) straight from
 // the caller's images — device-resident images are never copied.
 #include <hip/hip_runtime.h>
@@ -63,6 +64,7 @@ inline void clear_where(unsigned char* __restrict dst, const unsigned char* __re
 struct Finder {
     int device = 0;
     hipStream_t stream = nullptr;
+    int cost_func = ISX_DP_COLOR;   // costFunc_ S:72
     int utlx = 0, utly = 0, uw = 0, uh = 0;
     // the two masks of the pair, read in place through the union's coordinates (zero outside a tile's rectangle): no union-sized copies
     struct MaskView {
@@ -331,8 +333,8 @@ struct Finder {
         lab.data = &LW(ry, rx); lab.rows = rh; lab.cols = rw; lab.type = ISX_32SC1; lab.step = (size_t)ww * 4; lab.device = -1;
         std::vector<int> xy((size_t)2 * (rw + rh + 2));
         int len = 0, h = 0;
-        ISX_TRY(isx_seam_estimate(image1, image2, tl1.x, tl1.y, tl2.x, tl2.y, utlx + rx, utly + ry, &lab, comp + 1, roi, p1.x - rx, p1.y - ry, p2.x - rx, p2.y - ry,
-                                  xy.data(), rw + rh + 2, &len, &h, device, stream));
+        ISX_TRY(isx_seam_estimate_cost(image1, image2, tl1.x, tl1.y, tl2.x, tl2.y, utlx + rx, utly + ry, &lab, comp + 1, roi, p1.x - rx, p1.y - ry, p2.x - rx, p2.y - ry,
+                                       xy.data(), rw + rh + 2, &len, &h, cost_func, device, stream));
         seam.resize(len);
         for (int i = 0; i < len; ++i) seam[i] = {xy[2 * i] + rx, xy[2 * i + 1] + ry};
         horiz = h != 0;
@@ -629,12 +631,13 @@ int isx_dp_seam_release(void) ISX_ENTRY {
     f = Finder();                       // labels, union masks, contours, the seam mask: back to empty vectors
     finder_stages().img.clear();        // the staged images
     finder_stages().device = -1;
-    isx::seam_scratch_release();        // cost maps, DP records and the staging of isx_seam_estimate
+    isx::seam_scratch_release();        // gradient and cost maps, DP records and the staging of isx_seam_estimate
     return ISX_OK;
 } ISX_EXIT("isx_dp_seam_release")
 
-int isx_dp_seam_find(int num_images, const isx_mat* images, const int* corners_xy, isx_mat* masks, int device, void* hip_stream) ISX_ENTRY {
+int isx_dp_seam_find_cost(int num_images, const isx_mat* images, const int* corners_xy, isx_mat* masks, int cost_func, int device, void* hip_stream) ISX_ENTRY {
     clear_error();
+    ISX_CHECK_ARG(cost_func == ISX_DP_COLOR || cost_func == ISX_DP_COLOR_GRAD, ISX_ERR_INVALID, "dp_seam_find: cost_func %d is neither ISX_DP_COLOR nor ISX_DP_COLOR_GRAD (S:71)", cost_func);
     ISX_CHECK_ARG(num_images >= 0 && (num_images == 0 || (images && corners_xy && masks)), ISX_ERR_INVALID, "dp_seam_find: null argument");
     if (num_images == 0) return ISX_OK;   // S:95-96
     for (int i = 0; i < num_images; ++i) {
@@ -680,6 +683,7 @@ int isx_dp_seam_find(int num_images, const isx_mat* images, const int* corners_x
     Finder& f = finder();
     f.device = device;
     f.stream = (hipStream_t)hip_stream;
+    f.cost_func = cost_func;
     std::vector<std::pair<int, int>> pairs;   // S:98-113
     for (int i = 0; i + 1 < num_images; ++i)
         for (int j = i + 1; j < num_images; ++j) pairs.push_back({i, j});
@@ -693,6 +697,10 @@ int isx_dp_seam_find(int num_images, const isx_mat* images, const int* corners_x
             ISX_HIP(hipMemcpy2DAsync(masks[i].data, masks[i].step, hostm[i].data(), masks[i].cols, masks[i].cols, masks[i].rows, hipMemcpyHostToDevice, (hipStream_t)hip_stream));
     if (any_dev) ISX_HIP(hipStreamSynchronize((hipStream_t)hip_stream));   // hostm dies with this frame
     return ISX_OK;
+} ISX_EXIT("isx_dp_seam_find_cost")
+
+int isx_dp_seam_find(int num_images, const isx_mat* images, const int* corners_xy, isx_mat* masks, int device, void* hip_stream) ISX_ENTRY {
+    return isx_dp_seam_find_cost(num_images, images, corners_xy, masks, ISX_DP_COLOR, device, hip_stream);
 } ISX_EXIT("isx_dp_seam_find")
 
 }  // extern "C"

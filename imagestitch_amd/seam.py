@@ -1,5 +1,6 @@
 """The data-parallel part of the reference's in-tree DP seam finder: estimateSeam S:806-957 with
-computeCosts S:733-803 — cost maps and dynamic programme on the GPU.  The component analysis around it stays with the caller."""
+computeCosts S:733-803 (both cost functions, S:71; COLOR_GRAD with computeGradients S:549-572) — gradient maps, cost maps and dynamic
+programme on the GPU.  The component analysis around it stays with the caller."""
 import ctypes as C
 
 import numpy as np
@@ -8,9 +9,13 @@ from . import _lib
 from ._lib import as_mat, check
 
 
-def seam_estimate(image1, image2, tl1, tl2, union_tl, labels, label, roi, p1, p2, device=0, stream=None):
+DP_COLOR, DP_COLOR_GRAD = 0, 1           # DpSeamFinder::CostFunction (S:71)
+
+
+def seam_estimate(image1, image2, tl1, tl2, union_tl, labels, label, roi, p1, p2, device=0, stream=None, cost_func=DP_COLOR):
     """estimateSeam(image1, image2, tl1, tl2, comp, p1, p2, seam, isHorizontal).  labels = labels_ (HxW int32, union-sized),
     label = comp + 1, roi = (x, y, width, height) of Rect(tls_[comp], brs_[comp]); points are (x, y) in union coordinates.
+    cost_func = DP_COLOR or DP_COLOR_GRAD (costFunc_, S:765-772 / S:790-797).
     Returns (seam as an (N, 2) int32 array, p1 first — empty when p2 is not reachable —, is_horizontal)."""
     m1, m2, ml = as_mat(image1), as_mat(image2), as_mat(labels)
     cap = int(roi[2]) + int(roi[3]) + 2
@@ -18,17 +23,44 @@ def seam_estimate(image1, image2, tl1, tl2, union_tl, labels, label, roi, p1, p2
     n, horiz = C.c_int(0), C.c_int(0)
     r = (C.c_int * 4)(*[int(v) for v in roi])
     ptr = getattr(stream, "cuda_stream", stream)
-    check(_lib.load().isx_seam_estimate(C.byref(m1), C.byref(m2), int(tl1[0]), int(tl1[1]), int(tl2[0]), int(tl2[1]), int(union_tl[0]), int(union_tl[1]),
-                                        C.byref(ml), int(label), r, int(p1[0]), int(p1[1]), int(p2[0]), int(p2[1]),
-                                        out.ctypes.data_as(C.POINTER(C.c_int)), cap, C.byref(n), C.byref(horiz), int(device), C.c_void_p(ptr or 0)))
+    check(_lib.load().isx_seam_estimate_cost(C.byref(m1), C.byref(m2), int(tl1[0]), int(tl1[1]), int(tl2[0]), int(tl2[1]), int(union_tl[0]), int(union_tl[1]),
+                                             C.byref(ml), int(label), r, int(p1[0]), int(p1[1]), int(p2[0]), int(p2[1]),
+                                             out.ctypes.data_as(C.POINTER(C.c_int)), cap, C.byref(n), C.byref(horiz), int(cost_func), int(device),
+                                             C.c_void_p(ptr or 0)))
     return out[: n.value].copy(), bool(horiz.value)
 
 
-class DpSeamFinder:
-    """The reference's in-tree DP seam finder (S:60-1093, `find` as called at S:1192; costFunc_ COLOR)."""
+def seam_gradients(image, rect=None, device=0, stream=None, out=None):
+    """The gradient maps of computeGradients S:549-572 as magnitudes: (|Sobel(gray, CV_32F, 1, 0)|, |Sobel(gray, CV_32F, 0, 1)|) of
+    gray = cvtColor(image, COLOR_BGR2GRAY) over rect = (x, y, width, height) of the image (default: all of it); the values are those of
+    the whole image's maps.  image: CV_32FC3 or CV_8UC3 array / tensor.  Returns two float32 maps of the rectangle's size: tensors on the
+    image's device for a device image, NumPy arrays otherwise - or the pair given as `out`, filled."""
+    m = as_mat(image)
+    if rect is None:
+        rect = (0, 0, m.cols, m.rows)
+    w, h = int(rect[2]), int(rect[3])
+    if out is None:
+        if m.device >= 0:
+            import torch
+            out = tuple(torch.empty((max(h, 0), max(w, 0)), dtype=torch.float32, device=image.device) for _ in range(2))
+        else:
+            out = tuple(np.empty((max(h, 0), max(w, 0)), np.float32) for _ in range(2))
+    gx, gy = as_mat(out[0]), as_mat(out[1])
+    r = (C.c_int * 4)(*[int(v) for v in rect])
+    ptr = getattr(stream, "cuda_stream", stream)
+    check(_lib.load().isx_seam_gradients(C.byref(m), r, C.byref(gx), C.byref(gy), int(device), C.c_void_p(ptr or 0)))
+    return out[0], out[1]
 
-    def __init__(self, device=0, stream=None):
-        self.device, self.stream = device, stream
+
+class DpSeamFinder:
+    """The reference's in-tree DP seam finder (S:60-1093, `find` as called at S:1192): DpSeamFinder(DP_COLOR), the default (W:253), or
+    DpSeamFinder(DP_COLOR_GRAD), the alternative every demo lists (W:255, S:1183)."""
+
+    def __init__(self, cost_func=DP_COLOR, device=0, stream=None):
+        self.cost_func, self.device, self.stream = int(cost_func), device, stream
+
+    def costFunction(self):
+        return self.cost_func
 
     def find(self, src, corners, masks):
         """find(src, corners, masks): src = CV_32FC3 (or CV_8UC3) images, masks = CV_8U arrays / tensors edited in place."""
@@ -37,7 +69,7 @@ class DpSeamFinder:
         mats_m = (_lib.IsxMat * n)(*[as_mat(m) for m in masks])
         c = (C.c_int * (2 * n))(*[int(v) for p in corners for v in p])
         ptr = getattr(self.stream, "cuda_stream", self.stream)
-        check(_lib.load().isx_dp_seam_find(n, mats_i, c, mats_m, int(self.device), C.c_void_p(ptr or 0)))
+        check(_lib.load().isx_dp_seam_find_cost(n, mats_i, c, mats_m, self.cost_func, int(self.device), C.c_void_p(ptr or 0)))
         return masks
 
     @staticmethod

@@ -248,17 +248,24 @@ inline void dilateAnd(const Mat& mask, int kw, int kh, const Mat* other, Mat& ou
 }
 
 // cv::detail::DpSeamFinder as the reference restates it in-tree (S:60-1093): seam_finder->find(images_warped_f, corners, masks_seam)
+// DpSeamFinder(DpSeamFinder::COLOR_GRAD) is the alternative every demo lists (W:255, S:1183): computeGradients S:549-572 and the COLOR_GRAD
+// branches of computeCosts S:767-772 / S:792-797 on the GPU (isx_dp_seam_find_cost).
 class DpSeamFinder {
 public:
-    explicit DpSeamFinder(int device = 0) : device_(device) {}
+    enum CostFunction { COLOR = ISX_DP_COLOR, COLOR_GRAD = ISX_DP_COLOR_GRAD };   // S:71
+    explicit DpSeamFinder(int device = 0) : cost_func_(COLOR), device_(device) {}
+    explicit DpSeamFinder(CostFunction costFunc, int device = 0) : cost_func_(costFunc), device_(device) {}   // S:72
+    CostFunction costFunction() const { return cost_func_; }
+    void setCostFunction(CostFunction val) { cost_func_ = val; }
     void find(const std::vector<Mat>& src, const std::vector<Point>& corners, std::vector<Mat>& masks) {   // S:87, called at S:1192
         if (src.size() != corners.size() || src.size() != masks.size()) throw Exception(ISX_ERR_INVALID, "find: src, corners and masks differ in length");
         std::vector<isx_mat> im(src.size()), mk(src.size());
         std::vector<int> c;
         for (size_t i = 0; i < src.size(); ++i) { im[i] = *src[i].c(); mk[i] = *masks[i].c(); c.push_back(corners[i].x); c.push_back(corners[i].y); }
-        check(isx_dp_seam_find((int)src.size(), im.data(), c.data(), mk.data(), device_, nullptr));
+        check(isx_dp_seam_find_cost((int)src.size(), im.data(), c.data(), mk.data(), (int)cost_func_, device_, nullptr));
     }
 private:
+    CostFunction cost_func_;
     int device_;
 };
 

@@ -7,7 +7,8 @@
 // (DESIGN.md §8).  A header of its own, so that imagestitch_cv.hpp and the stub it is tested against stay as they were.
 //
 // Compiled inside the reference tree, where OpenCV 3.4.2 is installed; in this repository against tests/cpp/opencv_stub
-// (tests/cpp/graphcut_demo.cpp, run by tests/test_gpu_graphcut_seam.py; tests/cpp/voronoi_demo.cpp, run by tests/test_gpu_voronoi_seam.py).
+// (tests/cpp/graphcut_demo.cpp, run by tests/test_gpu_graphcut_seam.py; tests/cpp/voronoi_demo.cpp, run by tests/test_gpu_voronoi_seam.py;
+// tests/cpp/seam_grad_demo.cpp, run by tests/test_gpu_seam_grad.py).
 #ifndef IMAGESTITCH_CV_SEAM_HPP
 #define IMAGESTITCH_CV_SEAM_HPP
 
@@ -72,6 +73,36 @@ public:
 
 private:
     isx::VoronoiSeamFinder f_;
+};
+
+// cv::detail::DpSeamFinder(costFunc)'s find over isx::DpSeamFinder:  `new DpSeamFinder(DpSeamFinder::COLOR)` (W:253) becomes
+// makePtr<isx_cv::HipDpSeamFinder>(), `new DpSeamFinder(DpSeamFinder::COLOR_GRAD)` (W:255, S:1183) makePtr<isx_cv::HipDpSeamFinder>(
+// isx_cv::HipDpSeamFinder::COLOR_GRAD).  The enum is the adapter's own, with OpenCV's values (COLOR = 0, COLOR_GRAD = 1).
+class HipDpSeamFinder : public cv::detail::SeamFinder {
+public:
+    enum CostFunction { COLOR, COLOR_GRAD };
+    explicit HipDpSeamFinder(CostFunction costFunc = COLOR, int device = 0)
+        : f_(costFunc == COLOR_GRAD ? isx::DpSeamFinder::COLOR_GRAD : isx::DpSeamFinder::COLOR, device) {}
+    CostFunction costFunction() const { return f_.costFunction() == isx::DpSeamFinder::COLOR_GRAD ? COLOR_GRAD : COLOR; }
+    void find(const std::vector<cv::UMat>& src, const std::vector<cv::Point>& corners, std::vector<cv::UMat>& masks) override {
+        CV_Assert(src.size() == corners.size() && masks.size() == corners.size());
+        std::vector<cv::Mat> im, mk;             // mapped to the end of this call, as above
+        std::vector<isx::Mat> ii, mm;
+        std::vector<isx::Point> pts;
+        for (size_t i = 0; i < src.size(); ++i) {
+            im.push_back(src[i].getMat(cv::ACCESS_READ));
+            mk.push_back(masks[i].getMat(cv::ACCESS_RW));
+        }
+        for (size_t i = 0; i < src.size(); ++i) {
+            ii.push_back(isx::Mat(im[i]));
+            mm.push_back(isx::Mat(mk[i]));
+            pts.push_back(isx::Point(corners[i].x, corners[i].y));
+        }
+        f_.find(ii, pts, mm);
+    }
+
+private:
+    isx::DpSeamFinder f_;
 };
 
 }  // namespace isx_cv

@@ -383,8 +383,8 @@ int isx_convert_to(const isx_mat* src, isx_mat* dst, int device, void* hip_strea
 
 /* ---- DP seam finder, its data-parallel part (S = 动态规划法寻找最佳缝合线.cpp) ------------------------- */
 /* estimateSeam(image1, image2, tl1, tl2, comp, p1, p2, seam, isHorizontal) S:806-957 incl. computeCosts S:733-803
- * (costFunc_ COLOR, what `new DpSeamFinder(DpSeamFinder::COLOR)` W:253 / S:71-72 runs): the cost maps and the dynamic
- * programme run on the GPU, direction choice and backtracking on the host.  The component analysis around it
+ * (costFunc_ COLOR, what `new DpSeamFinder(DpSeamFinder::COLOR)` W:253 / S:71-72 runs; isx_seam_estimate_cost below takes
+ * the cost function): the cost maps and the dynamic programme run on the GPU, direction choice and backtracking on the host.  The component analysis around it
  * (findComponents, findEdges, resolveConflicts, getSeamTips, updateLabelsUsingSeam) stays with the caller and supplies
  * `labels` (labels_, CV_32SC1, union-sized), `label` = comp + 1, roi = {x, y, width, height} of Rect(tls_[comp],
  * brs_[comp]) and the tips p1, p2 (union coordinates).  Images: both CV_32FC3 (W:261) or both CV_8UC3.
@@ -393,6 +393,24 @@ int isx_seam_estimate(const isx_mat* image1, const isx_mat* image2, int tl1_x, i
                       int union_tl_x, int union_tl_y, const isx_mat* labels, int label, const int roi[4],
                       int p1_x, int p1_y, int p2_x, int p2_y, int* seam_xy, int cap, int* seam_len,
                       int* is_horizontal, int device, void* hip_stream);
+/* DpSeamFinder::CostFunction (S:71) */
+enum { ISX_DP_COLOR = 0, ISX_DP_COLOR_GRAD = 1 };
+/* isx_seam_estimate with costFunc_ as an argument; isx_seam_estimate is its ISX_DP_COLOR case.  ISX_DP_COLOR_GRAD (what
+ * `new DpSeamFinder(DpSeamFinder::COLOR_GRAD)` W:255 / S:1183 runs): computeGradients S:549-572 (cvtColor(COLOR_BGR2GRAY) + two 3 x 3
+ * Sobels per image, BORDER_REFLECT_101 at the image's own edges) evaluated over the component's rectangle, and both cost loops'
+ * COLOR_GRAD branches S:767-772 / S:792-797: a cell is costColor / costGrad, costGrad = the four |gradients| next to the cell + 1
+ * (evaluation order and OpenCV parity: DESIGN.md §8).  Any other cost_func -> ISX_ERR_INVALID.                          */
+int isx_seam_estimate_cost(const isx_mat* image1, const isx_mat* image2, int tl1_x, int tl1_y, int tl2_x, int tl2_y,
+                           int union_tl_x, int union_tl_y, const isx_mat* labels, int label, const int roi[4],
+                           int p1_x, int p1_y, int p2_x, int p2_y, int* seam_xy, int cap, int* seam_len,
+                           int* is_horizontal, int cost_func, int device, void* hip_stream);
+/* The gradient maps of computeGradients S:549-572 for one image, as magnitudes (all S:769-770 / S:794-795 read): abs_gradx =
+ * |Sobel(gray, CV_32F, 1, 0)| (S:562, S:570), abs_grady = |Sobel(gray, CV_32F, 0, 1)| (S:563, S:571), gray =
+ * cvtColor(image, COLOR_BGR2GRAY) (S:558, S:566), over rect = {x, y, width, height} of the image.  The values are those of
+ * the whole image's maps (borders reflect at the image's edges, not the rectangle's).  image: CV_32FC3 or CV_8UC3; outputs:
+ * caller-allocated CV_32FC1 of the rectangle's size; host or device mats.                                                */
+int isx_seam_gradients(const isx_mat* image, const int rect[4], isx_mat* abs_gradx, isx_mat* abs_grady, int device,
+                       void* hip_stream);
 
 /* seam_finder->find(images_warped_f, corners, masks_seam) of the in-tree DP seam finder as a whole (S:87-124 `find`, as
  * the S demo calls it at S:1192; W:253 is the stock `DpSeamFinder(DpSeamFinder::COLOR)` it restates): every pair of
@@ -401,8 +419,14 @@ int isx_seam_estimate(const isx_mat* image1, const isx_mat* image2, int tl1_x, i
  * of the images' sizes, edited in place.                                                                            */
 int isx_dp_seam_find(int num_images, const isx_mat* images, const int* corners_xy, isx_mat* masks, int device,
                      void* hip_stream);
-/* isx_dp_seam_find / isx_seam_estimate keep their work images (about 6-10 B per union pixel on the host, the staged images,
- * cost maps and DP records on the device) per calling thread between calls; this returns all of it (the analogue of the
+/* isx_dp_seam_find with the finder's cost function (S:71-72; process -> resolveConflicts S:398-399 -> estimateSeam ->
+ * computeCosts S:765-772, S:790-797): ISX_DP_COLOR is isx_dp_seam_find itself, ISX_DP_COLOR_GRAD the `new
+ * DpSeamFinder(DpSeamFinder::COLOR_GRAD)` every demo lists as the alternative (W:255, S:1183).  Any other cost_func ->
+ * ISX_ERR_INVALID, the masks untouched.                                                                              */
+int isx_dp_seam_find_cost(int num_images, const isx_mat* images, const int* corners_xy, isx_mat* masks, int cost_func,
+                          int device, void* hip_stream);
+/* isx_dp_seam_find / isx_seam_estimate (and their _cost forms, isx_seam_gradients) keep their work images (about 6-10 B per union
+ * pixel on the host, the staged images, gradient maps, cost maps and DP records on the device) per calling thread between calls; this returns all of it (the analogue of the
  * DpSeamFinder going out of scope, S:1188-1192).  PER THREAD: the state is thread-local and is NOT freed when a thread ends (the
  * HIP runtime may already be gone then) - a thread-pool caller calls this on every worker thread before that thread exits, or
  * leaks one finder (tens of MB at 4K) per thread.                                                                    */

@@ -1,0 +1,295 @@
+"""DpSeamFinder's COLOR_GRAD cost function on the GPU (S:71, computeGradients S:549-572, computeCosts S:767-772 / S:792-797):
+isx_seam_gradients, isx_seam_estimate_cost and isx_dp_seam_find_cost against the NumPy model tests/helpers/dpseam_grad_np.py - every
+comparison bit for bit -, the unchanged COLOR entry points, one thread alternating the two cost functions, the error paths, and the C++
+mirror and OpenCV adapter."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from helpers import dpseam_grad_np as M  # noqa: E402
+from seam_cases import make_case, make_find_case  # noqa: E402
+from test_dpseam_grad_model import FIND_CASES, REF_NONZERO_COLOR_GRAD  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def photo(rng, h, w, u8):
+    yy, xx = np.mgrid[0:h, 0:w]
+    img = 128 + 70 * np.sin(xx / 6.0)[..., None] * np.cos(yy / 5.0)[..., None] + rng.normal(0, 12, (h, w, 3))
+    return np.clip(np.rint(img), 0, 255).astype(np.uint8) if u8 else (img + rng.uniform(0, 1, (h, w, 3))).astype(np.float32)
+
+
+def model_abs(image, rect=None):
+    gx, gy = M.gradients(image)
+    x, y, w, h = rect if rect is not None else (0, 0, image.shape[1], image.shape[0])
+    return np.abs(gx)[y:y + h, x:x + w], np.abs(gy)[y:y + h, x:x + w]
+
+
+def same_bits(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype == np.float32 and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+def check_gradients(gpu, image, rect=None, given=None):
+    gx, gy = gpu.seam_gradients(given if given is not None else image, rect)
+    if not isinstance(gx, np.ndarray):
+        gx, gy = gx.cpu().numpy(), gy.cpu().numpy()
+    rx, ry = model_abs(image, rect)
+    assert same_bits(gx, rx), (rect, np.argwhere(gx != rx)[:4])
+    assert same_bits(gy, ry), (rect, np.argwhere(gy != ry)[:4])
+
+
+# ---- isx_seam_gradients ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("u8", [False, True])
+def test_gradients_host_and_device_whole_image_and_rectangles(gpu, u8):
+    import torch
+    rng = np.random.default_rng(11 + u8)
+    h, w = 83, 151
+    img = photo(rng, h, w, u8)
+    dev = torch.from_numpy(img).cuda()
+    rects = [None, (0, 0, w, h), (0, 0, 70, 20), (w - 66, 0, 66, 17), (0, h - 18, 65, 18), (w - 3, h - 5, 3, 5), (17, 9, 64, 16), (17, 9, 65, 17),
+             (30, 40, 1, 1), (0, 0, 1, h), (w - 1, 0, 1, h), (0, 0, w, 1), (0, h - 1, w, 1), (5, 6, 129, 33)]
+    for rect in rects:
+        check_gradients(gpu, img, rect)
+        check_gradients(gpu, img, rect, given=dev)
+
+
+@pytest.mark.parametrize("u8", [False, True])
+def test_gradients_unaligned_device_views_and_odd_steps(gpu, u8):
+    import torch
+    rng = np.random.default_rng(21 + u8)
+    h, w = 37, 70
+    img = photo(rng, h, w, u8)
+    big = torch.zeros((h + 3, w + 9, 3), dtype=torch.uint8 if u8 else torch.float32, device="cuda")
+    for ox, oy in ((1, 0), (3, 2), (5, 1)):                  # a byte view starts at any address, its step (w + 9) * 3 is odd
+        view = big[oy:oy + h, ox:ox + w]
+        view.copy_(torch.from_numpy(img))
+        check_gradients(gpu, img, None, given=view)
+        check_gradients(gpu, img, (w - 40, 3, 40, 30), given=view)
+    # outputs: pitched device views and pitched host arrays
+    ox_, oy_ = torch.zeros((h, w + 5), dtype=torch.float32, device="cuda"), torch.zeros((h, w + 3), dtype=torch.float32, device="cuda")
+    gpu.seam_gradients(img, None, out=(ox_[:, 2:2 + w], oy_[:, 3:3 + w]))
+    rx, ry = model_abs(img)
+    assert same_bits(ox_[:, 2:2 + w].cpu().numpy(), rx) and same_bits(oy_[:, 3:3 + w].cpu().numpy(), ry)
+    assert not ox_[:, :2].any() and not ox_[:, 2 + w:].any()
+    hx, hy = np.zeros((h, w + 4), np.float32), np.zeros((h, w + 1), np.float32)
+    gpu.seam_gradients(torch.from_numpy(img).cuda(), None, out=(hx[:, 1:1 + w], hy[:, :w]))
+    assert same_bits(hx[:, 1:1 + w], rx) and same_bits(hy[:, :w], ry) and not hx[:, 0].any() and not hy[:, w].any()
+
+
+def test_gradients_one_pixel_images(gpu):
+    rng = np.random.default_rng(5)
+    for shape in ((1, 1), (1, 2), (2, 1), (1, 77), (77, 1), (2, 2), (3, 130)):
+        for u8 in (False, True):
+            check_gradients(gpu, photo(rng, shape[0], shape[1], u8))
+
+
+@pytest.mark.parametrize("u8", [False, True])
+def test_gradients_full_4k_tile(gpu, u8):
+    import torch
+    rng = np.random.default_rng(31 + u8)
+    h, w = 2160, 3840
+    if u8:
+        img = rng.integers(0, 256, (h, w, 3)).astype(np.uint8)
+    else:
+        img = (rng.random((h, w, 3), dtype=np.float32) * np.float32(255))
+    check_gradients(gpu, img, None, given=torch.from_numpy(img).cuda())
+
+
+def test_gradients_errors(gpu):
+    img = np.zeros((10, 12, 3), np.uint8)
+    for rect in ((0, 0, 13, 10), (-1, 0, 5, 5), (0, 6, 5, 5), (0, 0, 0, 5)):
+        with pytest.raises(gpu.IsxError) as e:
+            gpu.seam_gradients(img, rect, out=(np.zeros((max(rect[3], 1), max(rect[2], 1)), np.float32),) * 2)
+        assert e.value.code == 1
+    with pytest.raises(gpu.IsxError) as e:
+        gpu.seam_gradients(np.zeros((10, 12), np.uint8))
+    assert e.value.code == 2
+    with pytest.raises(gpu.IsxError) as e:
+        gpu.seam_gradients(img, (0, 0, 5, 5), out=(np.zeros((5, 6), np.float32), np.zeros((5, 5), np.float32)))
+    assert e.value.code == 7
+
+
+# ---- isx_seam_estimate_cost ------------------------------------------------------------------------------------------------------------
+def seam_args(c):
+    return (c["img1"], c["img2"], c["tl1"], c["tl2"], c["union_tl"], c["labels"], c["label"], c["roi"], c["p1"], c["p2"])
+
+
+@pytest.mark.parametrize("seed", range(6))
+@pytest.mark.parametrize("u8", [False, True])
+@pytest.mark.parametrize("horizontal", [False, True])
+def test_color_grad_seam_matches_the_model(gpu, seed, u8, horizontal):
+    c = make_case(seed, u8=u8, horizontal=horizontal, swap=bool(seed & 1), holes=seed % 3 != 0)
+    ref, rh = M.seam_estimate(*seam_args(c), M.COLOR_GRAD)
+    got, gh = gpu.seam_estimate(*seam_args(c), cost_func=gpu.DP_COLOR_GRAD)
+    assert gh == rh and got.shape == ref.shape and np.array_equal(got, ref), (got[:5], ref[:5])
+    color, _ = gpu.seam_estimate(*seam_args(c))
+    assert len(ref) > 0 and not np.array_equal(color, ref)            # the cost function does move this seam
+    assert np.array_equal(color, gpu.seam_estimate(*seam_args(c), cost_func=gpu.DP_COLOR)[0])
+
+
+def test_color_grad_seam_unreachable_tip_wide_roi_and_device_views(gpu):
+    import torch
+    c = make_case(5, holes=False)
+    rx, ry, rw, rh = c["roi"]
+    c["labels"][ry + rh // 2, :] = 9                      # a wall: p2 cannot be reached
+    assert len(gpu.seam_estimate(*seam_args(c), cost_func=gpu.DP_COLOR_GRAD)[0]) == 0
+    c = make_case(42, size1=(260, 1700), size2=(250, 1650), tl1=(0, 0), tl2=(90, 6), holes=True)      # 1500 cells per step > 1024 threads
+    ref, _ = M.seam_estimate(*seam_args(c), M.COLOR_GRAD)
+    assert len(ref) > 0 and c["roi"][2] > 1024
+    got, _ = gpu.seam_estimate(*seam_args(c), cost_func=gpu.DP_COLOR_GRAD)
+    assert np.array_equal(got, ref)
+    big1 = torch.zeros((c["img1"].shape[0], c["img1"].shape[1] + 7, 3), dtype=torch.float32, device="cuda")
+    big1[:, 3:-4] = torch.from_numpy(c["img1"]).cuda()
+    got, _ = gpu.seam_estimate(big1[:, 3:-4], torch.from_numpy(c["img2"]).cuda(), c["tl1"], c["tl2"], c["union_tl"], torch.from_numpy(c["labels"]).cuda(),
+                               c["label"], c["roi"], c["p1"], c["p2"], cost_func=gpu.DP_COLOR_GRAD)
+    assert np.array_equal(got, ref)
+
+
+def test_seam_estimate_bad_cost_func(gpu):
+    c = make_case(1)
+    for bad in (2, -1):
+        with pytest.raises(gpu.IsxError) as e:
+            gpu.seam_estimate(*seam_args(c), cost_func=bad)
+        assert e.value.code == 1
+
+
+# ---- isx_dp_seam_find_cost -------------------------------------------------------------------------------------------------------------
+def model_find(cost_func, images, corners, masks):
+    out = [m.copy() for m in masks]
+    M.DpSeamFinder(cost_func).find(images, corners, out)
+    return out
+
+
+def assert_masks(got, ref):
+    for k, (a, b) in enumerate(zip(got, ref)):
+        a = a if isinstance(a, np.ndarray) else a.cpu().numpy()
+        assert np.array_equal(a, b), (k, np.argwhere(a != b)[:4])
+
+
+@pytest.mark.parametrize("key", sorted(FIND_CASES))
+def test_color_grad_find_matches_the_model(gpu, key):
+    """2- and 3-tile cases, u8 and f32, host arrays and device tensors"""
+    import torch
+    n, u8, seed = key
+    images, corners, masks = make_find_case(1000 * n + seed, n, u8, holes=True)
+    ref = model_find(M.COLOR_GRAD, images, corners, masks)
+    assert [int(np.count_nonzero(m)) for m in ref] == FIND_CASES[key][1]
+    got = [m.copy() for m in masks]
+    finder = gpu.DpSeamFinder(cost_func=gpu.DP_COLOR_GRAD)
+    assert finder.costFunction() == gpu.DP_COLOR_GRAD and finder.find(images, corners, got) is got
+    assert_masks(got, ref)
+    dgot = [torch.from_numpy(m.copy()).cuda() for m in masks]
+    gpu.DpSeamFinder(gpu.DP_COLOR_GRAD).find([torch.from_numpy(im).cuda() for im in images], corners, dgot)
+    assert_masks(dgot, ref)
+    color = [m.copy() for m in masks]
+    gpu.DpSeamFinder().find(images, corners, color)
+    assert any((a != b).any() for a, b in zip(color, got))
+
+
+def test_color_grad_find_on_the_references_tiles(gpu):
+    import torch
+    from test_ref_artifact import dpseam_case
+    c = dpseam_case()
+    ref = model_find(M.COLOR_GRAD, c["images"], c["corners"], c["masks_in"])
+    assert [int(np.count_nonzero(m)) for m in ref] == REF_NONZERO_COLOR_GRAD
+    got = [m.copy() for m in c["masks_in"]]
+    gpu.DpSeamFinder(gpu.DP_COLOR_GRAD).find([torch.from_numpy(im).cuda() for im in c["images"]], c["corners"], got)
+    assert_masks(got, ref)
+    got = [m.copy() for m in c["masks_in"]]
+    gpu.DpSeamFinder(gpu.DP_COLOR_GRAD).find(c["images"], c["corners"], got)
+    assert_masks(got, ref)
+
+
+@pytest.mark.parametrize("u8", [False, True])
+def test_color_grad_find_on_the_4k_pair(gpu, u8):
+    """the config-2 4K pair geometry of tools/find_probe.py: tiles of 2169 x 3417, an overlap of a third"""
+    import torch
+    images, corners, masks = make_find_case(3, 2, u8, holes=False, size=(2169, 3417))
+    ref = model_find(M.COLOR_GRAD, images, corners, masks)
+    got = [m.copy() for m in masks]
+    gpu.DpSeamFinder(gpu.DP_COLOR_GRAD).find([torch.from_numpy(im).cuda() for im in images], corners, got)
+    assert_masks(got, ref)
+    color = [m.copy() for m in masks]
+    gpu.DpSeamFinder(gpu.DP_COLOR).find([torch.from_numpy(im).cuda() for im in images], corners, color)
+    assert_masks(color, model_find(M.COLOR, images, corners, masks))
+    assert any((a != b).any() for a, b in zip(color, got))
+
+
+@pytest.mark.parametrize("seed", range(4))
+@pytest.mark.parametrize("n_images,u8", [(2, False), (2, True), (3, False)])
+def test_color_is_the_old_entry_point(gpu, seed, n_images, u8):
+    """DpSeamFinder() = DpSeamFinder(cost_func=DP_COLOR) = isx_dp_seam_find = oracle/dpseam_np.py"""
+    import ctypes as C
+    from imagestitch_amd import _lib
+    from oracle.dpseam_np import DpSeamFinder as OracleFinder
+    images, corners, masks = make_find_case(1000 * n_images + seed, n_images, u8, holes=seed % 2 == 0)
+    ref = [m.copy() for m in masks]
+    OracleFinder().find(images, corners, ref)
+    a, b, c = ([m.copy() for m in masks] for _ in range(3))
+    gpu.DpSeamFinder().find(images, corners, a)
+    gpu.DpSeamFinder(cost_func=gpu.DP_COLOR).find(images, corners, b)
+    n = len(images)
+    check = _lib.check
+    check(_lib.load().isx_dp_seam_find(n, (_lib.IsxMat * n)(*[_lib.as_mat(x) for x in images]), (C.c_int * (2 * n))(*[int(v) for p in corners for v in p]),
+                                       (_lib.IsxMat * n)(*[_lib.as_mat(x) for x in c]), 0, None))
+    assert_masks(a, ref); assert_masks(b, ref); assert_masks(c, ref)
+    assert gpu.DpSeamFinder().costFunction() == gpu.DP_COLOR
+
+
+def test_alternating_cost_functions_release_and_bad_cost_func(gpu):
+    """One thread, COLOR / COLOR_GRAD in turn over tiles of different sizes (the per-thread scratch grows and is reused), release(), again."""
+    cases = []
+    for k, size in enumerate(((60, 90), (150, 210), (110, 140), (40, 300))):
+        images, corners, masks = make_find_case(70 + k, 2 + (k == 1), bool(k & 1), holes=True, size=size)
+        cases.append((images, corners, masks, {cf: model_find(cf, images, corners, masks) for cf in (M.COLOR, M.COLOR_GRAD)}))
+    for rnd in range(2):
+        for k, (images, corners, masks, want) in enumerate(cases):
+            for cf in ((gpu.DP_COLOR, gpu.DP_COLOR_GRAD) if (k + rnd) & 1 else (gpu.DP_COLOR_GRAD, gpu.DP_COLOR)):
+                got = [m.copy() for m in masks]
+                gpu.DpSeamFinder(cf).find(images, corners, got)
+                assert_masks(got, want[cf])
+        gpu.DpSeamFinder.release()
+    images, corners, masks, _ = cases[2]
+    for bad in (2, -1, 7):
+        got = [m.copy() for m in masks]
+        with pytest.raises(gpu.IsxError) as e:
+            gpu.DpSeamFinder(cost_func=bad).find(images, corners, got)
+        assert e.value.code == 1                                          # ISX_ERR_INVALID
+        assert_masks(got, masks)                                          # untouched
+    gpu.DpSeamFinder.release()
+
+
+# ---- C++ ---------------------------------------------------------------------------------------------------------------------------------
+def test_cpp_seam_grad_demo(gpu, tmp_path):
+    """tests/cpp/seam_grad_demo.cpp through isx::DpSeamFinder(COLOR_GRAD) and isx_cv::HipDpSeamFinder (include/imagestitch_cv_seam.hpp, compiled
+    against tests/cpp/opencv_stub with -Werror=suggest-override -Werror=overloaded-virtual): both leave the Python path's masks."""
+    lib_dir = os.path.join(ROOT, "imagestitch_amd", "csrc")
+    exe = str(tmp_path / "seam_grad_demo")
+    subprocess.check_call(["g++", "-O1", "-std=c++14", "-Wall", "-Wextra", "-Wsuggest-override", "-Woverloaded-virtual", "-Werror=suggest-override",
+                           "-Werror=overloaded-virtual", "-I", os.path.join(ROOT, "tests", "cpp", "opencv_stub"), "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "cpp", "seam_grad_demo.cpp"), "-o", exe, "-L", lib_dir, "-limagestitch_hip",
+                           "-Wl,-rpath," + lib_dir])
+    imgs, corners, masks = make_find_case(3001, 3, True, holes=True)
+    want = [m.copy() for m in masks]
+    gpu.DpSeamFinder(gpu.DP_COLOR_GRAD).find([a.astype(np.float32) for a in imgs], corners, want)
+    assert_masks(want, model_find(M.COLOR_GRAD, [a.astype(np.float32) for a in imgs], corners, masks))
+    d = tmp_path / "io"
+    d.mkdir()
+    for k in range(3):
+        imgs[k].tofile(str(d / ("img%d.bin" % k)))
+        masks[k].tofile(str(d / ("mask%d.bin" % k)))
+    args = [exe, str(d)] + ["%d %d %d %d" % (corners[k][0], corners[k][1], imgs[k].shape[1], imgs[k].shape[0]) for k in range(3)]
+    out = subprocess.check_output(" ".join(args).split(), text=True, timeout=300)
+    lines = [ln for ln in out.splitlines() if ln.startswith(("mirror", "adapter"))]
+    assert len(lines) == 6, out
+    for ln in lines:
+        leg, k, s = ln.split()
+        assert int(s) == int(want[int(k)].astype(np.int64).sum()), ln
+        got = np.fromfile(str(d / ("%s%s.bin" % (leg, k))), np.uint8).reshape(want[int(k)].shape)
+        assert np.array_equal(got, want[int(k)]), ln
