@@ -2,7 +2,7 @@
 """The reference demo's post-registration stage on one pair of images, every step on the GPU through imagestitch_amd
 (needs an MI355X):
 
-    python examples/stitch_pair.py [left.bmp right.bmp] [--focal F] [--yaw RAD] [--blend feather|multiband] [--out pano.bmp | pano.jpg]
+    python examples/stitch_pair.py [left.bmp right.bmp] [--focal F] [--yaw RAD] [--warper cylindrical|spherical|plane] [--blend feather|multiband] [--out pano.bmp | pano.jpg]
 
 Registration (features, matching, bundle adjustment — out of scope of this library) is replaced by a known rig: two cameras
 with focal length F rotated by -/+ yaw about the vertical axis.  Without input files a synthetic pair is generated.
@@ -27,6 +27,8 @@ def main():
     ap.add_argument("images", nargs="*")
     ap.add_argument("--focal", type=float, default=None)
     ap.add_argument("--yaw", type=float, default=0.18)
+    ap.add_argument("--warper", default="cylindrical", choices=["cylindrical", "spherical", "plane"],
+                    help="the warper list of the reference's demos (B:91-95): cv::PlaneWarper, cv::CylindricalWarper (the one they run), cv::SphericalWarper")
     ap.add_argument("--blend", default="feather", choices=["feather", "multiband"])
     ap.add_argument("--gains", type=float, nargs=2, default=[1.0, 1.0])
     ap.add_argument("--estimate-gains", action="store_true",
@@ -50,7 +52,8 @@ def main():
     H, W = imgs[0].shape[:2]
     F = a.focal or 1.1 * W
     K, Rs = synth.camera_pair(W, H, F, yaw=a.yaw)
-    warper = isx.CylindricalWarper().create(F)                              # W:217-222
+    creator = {"cylindrical": isx.CylindricalWarper, "spherical": isx.SphericalWarper, "plane": isx.PlaneWarper}[a.warper]   # B:91-95
+    warper = creator().create(F)                                            # W:217-222
     corners, warped, wmasks = [], [], []
     for i in range(2):
         if a.estimate_gains:                                                # the gains are not known before the warp: apply comes after feed

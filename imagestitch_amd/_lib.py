@@ -15,7 +15,7 @@ ISX_32SC1 = 4
 INTER_NEAREST, INTER_LINEAR = 0, 1
 INTER_TIES_EVEN = 0x100   # OR to INTER_LINEAR: OpenCV's OpenCL (UMat) remap rounding, half to even
 BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT_101 = 0, 1, 2, 3, 4
-WARP_CYLINDRICAL, WARP_SPHERICAL = 0, 1
+WARP_CYLINDRICAL, WARP_SPHERICAL, WARP_PLANE = 0, 1, 2
 BLEND_NO, BLEND_FEATHER, BLEND_MULTI_BAND = 0, 1, 2
 PREC_I16, PREC_F32, PREC_F16ACC32 = 0, 1, 2
 WINDOW_GRANULE = 128       # ISX_WINDOW_GRANULE: a column window of blend() starts on a multiple of it
@@ -66,6 +66,8 @@ _SIGS = {
     "isx_warper_set_roi_cache": [C.c_void_p, C.c_int],
     "isx_warper_table_resets": [C.c_void_p, C.POINTER(C.c_longlong)],
     "isx_warper_set_gain": [C.c_void_p, C.c_double],
+    "isx_warper_set_translation": [C.c_void_p, C.POINTER(C.c_float)],
+    "isx_warper_warp_point": [C.c_void_p, _F9, _F9, C.c_float, C.c_float, C.POINTER(C.c_float)],
     "isx_blender_feed_dilated": [C.c_void_p, _MP, _MP, _MP, C.c_int, C.c_int, C.c_int, C.c_int],
     "isx_warper_verify": [C.c_void_p],
     "isx_warper_discard_pending": [C.c_void_p],
@@ -142,6 +144,7 @@ _SIGS = {
     "isx_gather_p2p_synchronize": [C.c_void_p],
     "isx_selftest_division": [C.c_int, C.c_int, C.c_ulonglong, _IP],
     "isx_selftest_roi_host": [C.c_int, C.c_float, _F9, _F9, C.c_int, C.c_int, C.c_int, _IP, _F9],
+    "isx_selftest_warp_point": [C.c_int, C.c_float, _F9, _F9, C.POINTER(C.c_float), C.c_float, C.c_float, C.POINTER(C.c_float)],
     "isx_selftest_exception_barrier": [C.c_int],
     "isx_profile_enable": [C.c_int],
     "isx_profile_reset": [],

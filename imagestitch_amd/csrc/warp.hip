@@ -1,4 +1,4 @@
-// warp.hip — cylindrical / spherical rotation warper for MI355X (gfx950).
+// warp.hip — cylindrical / spherical / plane rotation warper for MI355X (gfx950).
 // Replaces the reference's in-tree warper (W:30-161: mapForward, mapBackward, detectResultRoi,
 // setCameraParams, buildMaps, warp) and the cv::remap call it ends in (W:157; arithmetic spec:
 // SURVEY.md §8(a) A8).  buildMaps + remap are fused: the back-projection is evaluated per
@@ -10,6 +10,8 @@
 // row with the same libm the reference code would call and the kernels read them from two small
 // tables — the per-pixel work is the 3x3 transform, two IEEE divisions and the sampler, all of
 // which the GPU reproduces bit-for-bit (no FMA contraction, correctly rounded div / sqrt).
+// The plane projector (cv::PlaneWarper, B:91) has no transcendental at all: its tables hold u / scale - t[0] per column and
+// v / scale - t[1] per row, and the constant 1 - t[2] of the call fills the second row table.
 #include "isx_device.hpp"
 #include "isx_internal.hpp"
 
@@ -45,7 +47,7 @@ struct MapTabs {            // device tables of the separable part of mapBackwar
     const float* col_c;     // cosf(u / scale)
     const float* row_a;     // cyl: v / scale             sph: sinf(pi - v / scale)
     const float* row_b;     // cyl: unused                sph: cosf(pi - v / scale)
-};
+};                          // plane: col_s = u / scale - t[0], row_a = v / scale - t[1], row_b = 1 - t[2] in every row, col_c unused
 
 // mapBackward (W:46-63) with the transcendental part tabulated
 __device__ __forceinline__ void map_backward(const Proj& p, const MapTabs& t, int dx, int dy, float& x, float& y) {
@@ -62,6 +64,22 @@ __device__ __forceinline__ void map_backward(const Proj& p, const MapTabs& t, in
     z = p.k_rinv[6] * x_ + p.k_rinv[7] * y_ + p.k_rinv[8] * z_;            // W:58
     if (z > 0) { x /= z; y /= z; }                                        // W:60
     else x = y = -1;                                                       // W:61
+}
+
+// PlaneProjector::mapBackward (OpenCV 3.4 warpers_inl.hpp): u / scale - t[0] and v / scale - t[1] come from the tables, z_ = 1 - t[2] is
+// one constant per call.  No z > 0 test and no (-1, -1) sentinel: the division is done for any z, as the stock class does it.
+__device__ __forceinline__ void map_backward_plane(const Proj& p, const MapTabs& t, int dx, int dy, float& x, float& y) {
+    const float u = t.col_s[dx], v = t.row_a[dy], tz = t.row_b[dy];
+    x = p.k_rinv[0] * u + p.k_rinv[1] * v + p.k_rinv[2] * tz;
+    y = p.k_rinv[3] * u + p.k_rinv[4] * v + p.k_rinv[5] * tz;
+    const float z = p.k_rinv[6] * u + p.k_rinv[7] * v + p.k_rinv[8] * tz;
+    x /= z; y /= z;
+}
+// the plane kind is a compile-time branch: the cylindrical / spherical instantiations keep the code they had
+template <bool PLANE>
+__device__ __forceinline__ void map_backward_k(const Proj& p, const MapTabs& t, int dx, int dy, float& x, float& y) {
+    if constexpr (PLANE) map_backward_plane(p, t, dx, dy, x, y);
+    else map_backward(p, t, dx, dy, x, y);
 }
 
 struct SrcView {
@@ -132,13 +150,13 @@ __device__ __forceinline__ void sample_linear(const SrcView& s, float mx, float 
 }
 
 // generic warp: one destination pixel per thread, 64 x 4 pixels per block
-template <class T, int CN>
+template <class T, int CN, bool PLANE = false>
 __global__ __launch_bounds__(256) void k_warp(Proj p, MapTabs t, SrcView src, unsigned char* dst, size_t dstep,
                                               int dw, int dh, int interp, int border) {
     int dx = blockIdx.x * 64 + (threadIdx.x & 63), dy = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (dx >= dw || dy >= dh) return;
     float mx, my;
-    map_backward(p, t, dx, dy, mx, my);
+    map_backward_k<PLANE>(p, t, dx, dy, mx, my);
     T o[CN];
     if (interp == ISX_INTER_NEAREST) sample_nearest<T, CN>(src, mx, my, border, o);
     else sample_linear<T, CN>(src, mx, my, border, o, (interp & ISX_INTER_TIES_EVEN) != 0);
@@ -210,7 +228,7 @@ __device__ __forceinline__ unsigned fix15(unsigned a, unsigned b, unsigned c, un
     return (__umul24(a, w0) + __umul24(b, w1) + __umul24(c, w2) + __umul24(d, w3) + (1u << 14)) >> 15;
 }
 
-template <bool OUT16, bool VEC>
+template <bool OUT16, bool VEC, bool PLANE = false>
 __global__ __launch_bounds__(256) void k_warp_img_mask(Proj p, MapTabs t, SrcView img, SrcView msk, int has_mask,
                                                        unsigned char* dimg, size_t dimg_step, unsigned char* dmask,
                                                        size_t dmask_step, int dw, int dh,
@@ -248,12 +266,14 @@ __global__ __launch_bounds__(256) void k_warp_img_mask(Proj p, MapTabs t, SrcVie
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         float x_, y_, z_;
-        if (p.kind == ISX_WARP_CYLINDRICAL) { x_ = cs[k]; y_ = ra; z_ = cc[k]; }          // W:51-53
+        if constexpr (PLANE) { x_ = cs[k]; y_ = ra; z_ = rb; }                            // u / scale - t[0], v / scale - t[1], 1 - t[2]
+        else if (p.kind == ISX_WARP_CYLINDRICAL) { x_ = cs[k]; y_ = ra; z_ = cc[k]; }     // W:51-53
         else { x_ = ra * cs[k]; y_ = rb; z_ = ra * cc[k]; }
         float x = p.k_rinv[0] * x_ + p.k_rinv[1] * y_ + p.k_rinv[2] * z_;                  // W:56
         float y = p.k_rinv[3] * x_ + p.k_rinv[4] * y_ + p.k_rinv[5] * z_;                  // W:57
         float z = p.k_rinv[6] * x_ + p.k_rinv[7] * y_ + p.k_rinv[8] * z_;                  // W:58
-        if (z > 0) { x /= z; y /= z; } else x = y = -1;                                   // W:60-61
+        if constexpr (PLANE) { x /= z; y /= z; }                                          // the plane projector divides whatever z is
+        else if (z > 0) { x /= z; y /= z; } else x = y = -1;                              // W:60-61
         mx[k] = x; my[k] = y;
         const int isx = cvround_x86(x * 32.f), isy = cvround_x86(y * 32.f);
         wq[k] = (unsigned)(isx & 31) | ((unsigned)(isy & 31) << 8);
@@ -392,7 +412,7 @@ __device__ __forceinline__ int reflect_inline(int p, int n) {
     return p;
 }
 
-template <bool OUT16>
+template <int KIND, bool OUT16>
 __device__ __forceinline__ void warp_tile_fixup(const Proj* p, const MapTabs* t, const SrcView* img, const TileDst* d, int dx0, int row0, unsigned slow, int nrows, const unsigned char* lut = nullptr) {
     const unsigned char* data = img->data;
     const size_t step = img->step;
@@ -402,7 +422,7 @@ __device__ __forceinline__ void warp_tile_fixup(const Proj* p, const MapTabs* t,
         const int i = j >> 2, k = j & 3, dy = row0 + i, dx = dx0 + k;
         if (dy >= d->h || dx >= d->w || !((slow >> i) & 1u)) continue;
         float mx, my;
-        map_backward(*p, *t, dx, dy, mx, my);
+        map_backward_k<KIND == ISX_WARP_PLANE>(*p, *t, dx, dy, mx, my);
         // cv::remap INTER_LINEAR, BORDER_REFLECT on CV_8UC3 (sample_linear's arithmetic)
         const int isx = cvround_x86(mx * 32.f), isy = cvround_x86(my * 32.f);
         const int fx = isx & 31, fy = isy & 31;
@@ -531,7 +551,7 @@ __device__ __forceinline__ void warp_tile_body(const Proj& p, const MapTabs& t, 
             Y[h] = (splat2(ky0) * cs[h] + qy) + splat2(ky2) * cc[h];                             // W:57 (x 32)
             Z[h] = (splat2(p.k_rinv[6]) * cs[h] + qz) + splat2(p.k_rinv[8]) * cc[h];             // W:58
         }
-    } else {
+    } else if constexpr (KIND == ISX_WARP_SPHERICAL) {
         const float ra = t.row_a[dy], rb = t.row_b[dy];                                         // sinf(pi - v), cosf(pi - v)
         const f32x2 qx = splat2(kx1 * rb), qy = splat2(ky1 * rb), qz = splat2(p.k_rinv[7] * rb);
 #pragma unroll
@@ -540,6 +560,18 @@ __device__ __forceinline__ void warp_tile_body(const Proj& p, const MapTabs& t, 
             X[h] = (splat2(kx0) * x_ + qx) + splat2(kx2) * z_;
             Y[h] = (splat2(ky0) * x_ + qy) + splat2(ky2) * z_;
             Z[h] = (splat2(p.k_rinv[6]) * x_ + qz) + splat2(p.k_rinv[8]) * z_;
+        }
+    } else {
+        // plane: x_ = u / scale - t[0] (column), y_ = v / scale - t[1] (row), z_ = 1 - t[2] (the call's constant): the third products
+        // leave the pixel loop as well, and the cosine table is not read at all
+        const float ra = t.row_a[dy], tz = t.row_b[dy];
+        const f32x2 qx = splat2(kx1 * ra), qy = splat2(ky1 * ra), qz = splat2(p.k_rinv[7] * ra);
+        const f32x2 cx = splat2(kx2 * tz), cy = splat2(ky2 * tz), cz = splat2(p.k_rinv[8] * tz);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            X[h] = (splat2(kx0) * cs[h] + qx) + cx;
+            Y[h] = (splat2(ky0) * cs[h] + qy) + cy;
+            Z[h] = (splat2(p.k_rinv[6]) * cs[h] + qz) + cz;
         }
     }
     // 32 x / z, 32 y / z (W:60): cvRound of these is cv::remap's fixed-point coordinate
@@ -691,7 +723,7 @@ __device__ __forceinline__ void warp_tile_body(const Proj& p, const MapTabs& t, 
     }
     // ---- the rare rest (z out of the guarded range incl. the z <= 0 sentinel, more than one reflection, sources too small for a
     // window, the last columns of the buffer's last row): the whole 4-pixel row of the thread again, by the generic code path
-    if (generic) warp_tile_fixup<OUT16>(&ka->p, &ka->t, &ka->img, &ka->d, dx0, dy, 1u, 1, GAIN ? (const unsigned char*)klut : nullptr);
+    if (generic) warp_tile_fixup<KIND, OUT16>(&ka->p, &ka->t, &ka->img, &ka->d, dx0, dy, 1u, 1, GAIN ? (const unsigned char*)klut : nullptr);
 }
 static_assert(offsetof(WarpTileArgs, lut) == sizeof(WarpTileGeom), "WarpTileArgs = WarpTileGeom + the gain table");
 template <int KIND, bool OUT16, bool VEC, bool MASK = true, bool GAIN = false>
@@ -744,7 +776,7 @@ __global__ __launch_bounds__(256) void k_warp_mask_tile(WarpMaskArgs a) {
             Y[h] = (splat2(p.k_rinv[3]) * cs[h] + qy) + splat2(p.k_rinv[5]) * cc[h];             // W:57
             Z[h] = (splat2(p.k_rinv[6]) * cs[h] + qz) + splat2(p.k_rinv[8]) * cc[h];             // W:58
         }
-    } else {
+    } else if constexpr (KIND == ISX_WARP_SPHERICAL) {
         const float ra = t.row_a[dy], rb = t.row_b[dy];
         const f32x2 qx = splat2(p.k_rinv[1] * rb), qy = splat2(p.k_rinv[4] * rb), qz = splat2(p.k_rinv[7] * rb);
 #pragma unroll
@@ -753,6 +785,16 @@ __global__ __launch_bounds__(256) void k_warp_mask_tile(WarpMaskArgs a) {
             X[h] = (splat2(p.k_rinv[0]) * x_ + qx) + splat2(p.k_rinv[2]) * z_;
             Y[h] = (splat2(p.k_rinv[3]) * x_ + qy) + splat2(p.k_rinv[5]) * z_;
             Z[h] = (splat2(p.k_rinv[6]) * x_ + qz) + splat2(p.k_rinv[8]) * z_;
+        }
+    } else {                                                                                     // plane (see warp_tile_body)
+        const float ra = t.row_a[dy], tz = t.row_b[dy];
+        const f32x2 qx = splat2(p.k_rinv[1] * ra), qy = splat2(p.k_rinv[4] * ra), qz = splat2(p.k_rinv[7] * ra);
+        const f32x2 cx = splat2(p.k_rinv[2] * tz), cy = splat2(p.k_rinv[5] * tz), cz = splat2(p.k_rinv[8] * tz);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            X[h] = (splat2(p.k_rinv[0]) * cs[h] + qx) + cx;
+            Y[h] = (splat2(p.k_rinv[3]) * cs[h] + qy) + cy;
+            Z[h] = (splat2(p.k_rinv[6]) * cs[h] + qz) + cz;
         }
     }
     float tx[4], ty[4];
@@ -787,7 +829,7 @@ __global__ __launch_bounds__(256) void k_warp_mask_tile(WarpMaskArgs a) {
 #pragma unroll 1
         for (int k = 0; k < 4 && dx0 + k < a.w; ++k) {
             float mx, my;
-            map_backward(p, t, dx0 + k, dy, mx, my);
+            map_backward_k<KIND == ISX_WARP_PLANE>(p, t, dx0 + k, dy, mx, my);
             unsigned char m;
             sample_nearest<unsigned char, 1>(src, mx, my, ISX_BORDER_CONSTANT, &m);
             m4 |= (unsigned)m << (8 * k);
@@ -821,11 +863,12 @@ __global__ void k_selftest_division(unsigned long long seed, int n, unsigned* mi
 }
 
 // buildMaps (W:133-141), API parity only
+template <bool PLANE = false>
 __global__ __launch_bounds__(256) void k_build_maps(Proj p, MapTabs t, float* xmap, size_t xstep, float* ymap, size_t ystep, int dw, int dh) {
     int dx = blockIdx.x * 64 + (threadIdx.x & 63), dy = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (dx >= dw || dy >= dh) return;
     float mx, my;
-    map_backward(p, t, dx, dy, mx, my);
+    map_backward_k<PLANE>(p, t, dx, dy, mx, my);
     ((float*)((char*)xmap + (size_t)dy * xstep))[dx] = mx;
     ((float*)((char*)ymap + (size_t)dy * ystep))[dx] = my;
 }
@@ -1066,6 +1109,32 @@ void map_forward_host(const Proj& p, float x, float y, float& u, float& v) {
     }
 }
 
+// PlaneProjector::mapForward (OpenCV 3.4 warpers_inl.hpp), every operation a rounded float operation in the order written
+void map_forward_plane_host(const Proj& p, const float t[3], float x, float y, float& u, float& v) {
+    float x_ = p.r_kinv[0] * x + p.r_kinv[1] * y + p.r_kinv[2];
+    float y_ = p.r_kinv[3] * x + p.r_kinv[4] * y + p.r_kinv[5];
+    float z_ = p.r_kinv[6] * x + p.r_kinv[7] * y + p.r_kinv[8];
+    x_ = t[0] + x_ / z_ * (1 - t[2]);
+    y_ = t[1] + y_ / z_ * (1 - t[2]);
+    u = p.scale * x_;
+    v = p.scale * y_;
+}
+
+// PlaneWarper::detectResultRoi: mapForward of the four source corners, min / max, static_cast<int> (W:83-86) - no scan, nothing launched
+void roi_plane_host(const Proj& p, const float t[3], int sw, int sh, int roi[4], float mm[4]) {
+    float tl_u = std::numeric_limits<float>::max(), tl_v = tl_u, br_u = -tl_u, br_v = -tl_u;
+    const float xs[2] = {0.f, (float)(sw - 1)}, ys[2] = {0.f, (float)(sh - 1)};
+    for (float x : xs)
+        for (float y : ys) {
+            float u, v;
+            map_forward_plane_host(p, t, x, y, u, v);
+            tl_u = (std::min)(tl_u, u); tl_v = (std::min)(tl_v, v);
+            br_u = (std::max)(br_u, u); br_v = (std::max)(br_v, v);
+        }
+    if (mm) { mm[0] = tl_u; mm[1] = tl_v; mm[2] = br_u; mm[3] = br_v; }
+    roi[0] = f2i_host(tl_u); roi[1] = f2i_host(tl_v); roi[2] = f2i_host(br_u); roi[3] = f2i_host(br_v);
+}
+
 // the stand-ins of forward_proxy as functions of u and v (monotone increasing), in double
 double proxy_d_of_u(double u, double scale) {
     double th = u / scale;
@@ -1142,6 +1211,8 @@ struct isx_warper {
     DevBuf scan_side;        // {keys[4], count, mismatches} used on the side stream only
     DevBuf scan_blk;         // the synchronous scan's per-block extrema (k_roi_scan -> k_roi_candidates)
     void* pin = nullptr;     // pinned host landing zone of detectResultRoi's {keys, count, first candidates}
+    float t[3] = {0.f, 0.f, 0.f};   // isx_warper_set_translation: PlaneWarper's T (sticky; non-zero on a plane handle only)
+    int plan_mismatches_host = 0;   // planned plane warps: their four-corner ROI is compared on the host when the verification is queued
     double gain = 1.0;       // isx_warper_set_gain: folded into the fused tile warp's store (1.0 = off)
     unsigned char gain_lut[256] = {};   // its 256-entry table (handed to the kernel in its arguments)
     // isx_warper_set_deferred_verify: planned warps queue their verification; isx_warper_verify enqueues the
@@ -1151,13 +1222,13 @@ struct isx_warper {
     std::vector<Pending> pending;
     bool defer_verify = false;
     MatStage st_src, st_mask, st_dst, st_dmask, st_x, st_y;
-    // cache of mapBackward tables, one entry per (kind, scale, roi): a rig's tiles alternate between a few ROIs
+    // cache of mapBackward tables, one entry per (kind, scale, translation, roi): a rig's tiles alternate between a few ROIs
     // (round 5: 1024 entries, each with its own host copy.  With 16 entries and one shared host buffer a panorama of more than 16 tiles through
     // one handle missed on EVERY warp - two stream synchronisations and 7 000 sinf / cosf per call: the 64-tile step was host-bound at 68 us per
     // 27 us warp kernel, 9.8 ms against a kernel sum of 7.3, profiles/round5_many_tiles_trace.txt)
-    struct TabEntry { int kind; float scale; int roi[4]; const float* dev; size_t chunk; };
+    struct TabEntry { int kind; float scale; float t[3]; int roi[4]; const float* dev; size_t chunk; };
     std::vector<TabEntry> tab_cache;
-    std::unordered_multimap<unsigned long long, size_t> tab_index;   // hash of (kind, scale, roi) -> entry (no linear scan of 1024 entries per warp)
+    std::unordered_multimap<unsigned long long, size_t> tab_index;   // hash of (kind, scale, translation, roi) -> entry (no linear scan of 1024 entries per warp)
     // the tables live in a few 4 MiB chunks, bump-allocated (a DevBuf per entry was a megabyte per entry - reserve() rounds up - i.e. up to a
     // gigabyte per warper at the old cap of 1024 entries): at most TAB_BYTES of them; a full arena is drained and started over
     std::vector<std::unique_ptr<DevBuf>> tab_chunks;
@@ -1247,7 +1318,9 @@ int flush_warp_batch(isx_warper* w) {
             case 0: rc = launch_warp_batch<ISX_WARP_CYLINDRICAL, false>(w->stream, it, n); break;
             case 1: rc = launch_warp_batch<ISX_WARP_CYLINDRICAL, true>(w->stream, it, n); break;
             case 2: rc = launch_warp_batch<ISX_WARP_SPHERICAL, false>(w->stream, it, n); break;
-            default: rc = launch_warp_batch<ISX_WARP_SPHERICAL, true>(w->stream, it, n); break;
+            case 3: rc = launch_warp_batch<ISX_WARP_SPHERICAL, true>(w->stream, it, n); break;
+            case 4: rc = launch_warp_batch<ISX_WARP_PLANE, false>(w->stream, it, n); break;
+            default: rc = launch_warp_batch<ISX_WARP_PLANE, true>(w->stream, it, n); break;
         }
         if (rc != ISX_OK) return rc;
         i = j;
@@ -1404,6 +1477,15 @@ int border_scan_host(const float* r_kinv, bool sph, int sw, int sh, std::vector<
 }
 
 int detect_roi(isx_warper* w, int sw, int sh, int roi[4], float mm[4], bool sync_free, const int* planned) {
+    if (w->kind == ISX_WARP_PLANE) {
+        // the four-corner rule on the caller's thread.  The verification of a planned warp is the same rule: it is done here, when it is
+        // queued, and isx_warper_plan_status reports it with the scans' findings
+        int r[4];
+        roi_plane_host(w->proj, w->t, sw, sh, r, sync_free ? nullptr : mm);
+        if (sync_free) { if (!std::equal(r, r + 4, planned)) ++w->plan_mismatches_host; }
+        else std::copy(r, r + 4, roi);
+        return ISX_OK;
+    }
     hipStream_t st = w->stream;
     if (!sync_free) ISX_TRY(roi_stream_of(w, &st));
     size_t need = 64 + (size_t)CAND_CAP * 8;
@@ -1524,7 +1606,8 @@ int make_tabs(isx_warper* w, const int roi[4], MapTabs* t) {
     unsigned long long key = 1469598103934665603ull;
     {
         unsigned sbits; memcpy(&sbits, &w->scale, 4);
-        const unsigned words[6] = {(unsigned)w->kind, sbits, (unsigned)roi[0], (unsigned)roi[1], (unsigned)roi[2], (unsigned)roi[3]};
+        unsigned tbits[3]; memcpy(tbits, w->t, 12);
+        const unsigned words[9] = {(unsigned)w->kind, sbits, (unsigned)roi[0], (unsigned)roi[1], (unsigned)roi[2], (unsigned)roi[3], tbits[0], tbits[1], tbits[2]};
         for (unsigned v : words) { key ^= v; key *= 1099511628211ull; }
     }
     // a captured warp reads its tables when the graph is replayed, at a time this handle does not see: it must find them here now (a miss is
@@ -1537,7 +1620,7 @@ int make_tabs(isx_warper* w, const int roi[4], MapTabs* t) {
         auto r = w->tab_index.equal_range(key);
         for (auto it = r.first; it != r.second; ++it) {
             isx_warper::TabEntry& c = w->tab_cache[it->second];
-            if (c.kind == w->kind && c.scale == w->scale && std::equal(roi, roi + 4, c.roi)) { e = &c; break; }
+            if (c.kind == w->kind && c.scale == w->scale && memcmp(c.t, w->t, sizeof(c.t)) == 0 && std::equal(roi, roi + 4, c.roi)) { e = &c; break; }
         }
     }
     if (!e) {
@@ -1572,15 +1655,18 @@ int make_tabs(isx_warper* w, const int roi[4], MapTabs* t) {
         float* dev = (float*)((char*)w->tab_chunks[w->tab_chunk]->p + w->tab_used);
         w->tab_host.assign(n, 0.f);
         float* cs = w->tab_host.data(); float* cc = cs + mwp; float* ra = cc + mwp; float* rb = ra + mhp;
+        const bool plane = w->kind == ISX_WARP_PLANE;
         for (int i = 0; i < mw; ++i) {
             float u = (float)(roi[0] + i);
             u /= w->scale;                                 // W:48
-            cs[i] = sinf(u); cc[i] = cosf(u);              // W:51,53
+            if (plane) { cs[i] = u - w->t[0]; cc[i] = 0.f; }      // PlaneProjector::mapBackward: u = u / scale - t[0]
+            else { cs[i] = sinf(u); cc[i] = cosf(u); }     // W:51,53
         }
         for (int i = 0; i < mh; ++i) {
             float v = (float)(roi[1] + i);
             v /= w->scale;                                 // W:49
-            if (w->kind == ISX_WARP_CYLINDRICAL) { ra[i] = v; rb[i] = 0.f; }          // W:52
+            if (plane) { ra[i] = v - w->t[1]; rb[i] = 1 - w->t[2]; }                  // v = v / scale - t[1]; z_ = 1 - t[2]
+            else if (w->kind == ISX_WARP_CYLINDRICAL) { ra[i] = v; rb[i] = 0.f; }     // W:52
             else { ra[i] = sinf(PI_F - v); rb[i] = cosf(PI_F - v); }
         }
         // the padding repeats the last column / row: the fused kernel's partial 4-pixel group at the right edge then computes ordinary
@@ -1595,7 +1681,7 @@ int make_tabs(isx_warper* w, const int roi[4], MapTabs* t) {
         w->tab_used += need;
         w->tab_cache.emplace_back();
         e = &w->tab_cache.back();
-        e->kind = w->kind; e->scale = w->scale; std::copy(roi, roi + 4, e->roi); e->dev = dev; e->chunk = w->tab_chunk;
+        e->kind = w->kind; e->scale = w->scale; memcpy(e->t, w->t, sizeof(e->t)); std::copy(roi, roi + 4, e->roi); e->dev = dev; e->chunk = w->tab_chunk;
         w->tab_index.emplace(key, w->tab_cache.size() - 1);
     }
     if (capturing) w->tab_pinned[e->chunk] = 1;
@@ -1668,9 +1754,10 @@ int warp_one(isx_warper* w, const isx_mat* src, const isx_mat* src_mask, const f
         const unsigned* plan_keys = nullptr;
         int* plan_mism = nullptr;
         const int4 plan4 = make_int4(0, 0, 0, 0);
-#define ISX_WARP_FUSED(O16, V)                                                                                                   \
-        ISX_LAUNCH("warp_img_mask", bytes, st, (k_warp_img_mask<O16, V>), grid4, dim3(256), 0, w->proj, t, sv, mv, src_mask ? 1 : 0, \
+#define ISX_WARP_FUSED_P(O16, V, PL)                                                                                             \
+        ISX_LAUNCH("warp_img_mask", bytes, st, (k_warp_img_mask<O16, V, PL>), grid4, dim3(256), 0, w->proj, t, sv, mv, src_mask ? 1 : 0, \
                    (unsigned char*)dd.data, dd.step, (unsigned char*)dm.data, dm.step, dw, dh, plan_keys, plan4, plan_mism)
+#define ISX_WARP_FUSED(O16, V) do { if (w->kind == ISX_WARP_PLANE) ISX_WARP_FUSED_P(O16, V, true); else ISX_WARP_FUSED_P(O16, V, false); } while (0)
         // the hot kernel: a tile whose mask is all 255 (W:213-214).  Launch names are the kernels' names without the k_ (they can be
         // found in a rocprofv3 kernel trace as they are)
         // isx_warper_set_dst_columns: only the 64-column blocks that hold columns [col0, col1) of the warped tile are computed; the
@@ -1691,13 +1778,18 @@ int warp_one(isx_warper* w, const isx_mat* src, const isx_mat* src_mask, const f
         if (gained) ISX_LAUNCH("warp_tile", bytes, st, (k_warp_tile<KD, O16, V, true, true>), gridt, dim3(64 * WARP_WAVES), 0, wta);          \
         else ISX_LAUNCH("warp_tile", bytes, st, (k_warp_tile<KD, O16, V>), gridt, dim3(64 * WARP_WAVES), 0, wta);                              \
     } while (0)
-#define ISX_WARP_TILE_K(O16, V) do { if (w->kind == ISX_WARP_CYLINDRICAL) ISX_WARP_TILE(ISX_WARP_CYLINDRICAL, O16, V); else ISX_WARP_TILE(ISX_WARP_SPHERICAL, O16, V); } while (0)
+#define ISX_WARP_TILE_K(O16, V)                                                                     \
+    do {                                                                                            \
+        if (w->kind == ISX_WARP_CYLINDRICAL) ISX_WARP_TILE(ISX_WARP_CYLINDRICAL, O16, V);           \
+        else if (w->kind == ISX_WARP_SPHERICAL) ISX_WARP_TILE(ISX_WARP_SPHERICAL, O16, V);          \
+        else ISX_WARP_TILE(ISX_WARP_PLANE, O16, V);                                                 \
+    } while (0)
         const bool collect = !src_mask && w->batching && !gained && dst->device >= 0 && dst_mask->device >= 0 && src->device >= 0;
         if (!collect) ISX_TRY(flush_warp_batch(w));      // whatever is launched here goes out BEHIND what was collected so far
         if (collect) {
             // collected: leaves with the other tiles of the batch as one launch (flush_warp_batch)
             isx_warper::BatchItem bi;
-            bi.variant = (w->kind == ISX_WARP_CYLINDRICAL ? 0 : 2) | (dst->type == ISX_16SC3 ? 1 : 0);
+            bi.variant = 2 * w->kind | (dst->type == ISX_16SC3 ? 1 : 0);
             bi.g = WarpTileGeom{wta.p, wta.t, wta.img, wta.d};
             bi.gx = gridt.x; bi.gy = gridt.y; bi.bytes = bytes;
             w->batch.push_back(bi);
@@ -1709,6 +1801,7 @@ int warp_one(isx_warper* w, const isx_mat* src, const isx_mat* src_mask, const f
 #undef ISX_WARP_TILE_K
 #undef ISX_WARP_TILE
 #undef ISX_WARP_FUSED
+#undef ISX_WARP_FUSED_P
         // a column range (isx_warper_set_dst_columns) leaves the other columns of the mats as they are - also of host mats, of which only the
         // computed columns come back from the staging buffers
         ranged = w->col1 > w->col0 && !src_mask;
@@ -1736,22 +1829,31 @@ int warp_one(isx_warper* w, const isx_mat* src, const isx_mat* src_mask, const f
             const WarpTileArgs wta{w->proj, t, sv, TileDst{dp, (unsigned)ds, nullptr, 0u, dw, dh, 0, 0, 0xFFFFFFFFu / gridt.x + 1u}, {}};      // (xg = 0: as above)
 #define ISX_WARP_IMG(KD) ISX_LAUNCH("warp_tile_img", bytes, st, (k_warp_tile<KD, false, true, false>), gridt, dim3(64 * WARP_WAVES), 0, wta)
             if (w->kind == ISX_WARP_CYLINDRICAL) ISX_WARP_IMG(ISX_WARP_CYLINDRICAL);
-            else ISX_WARP_IMG(ISX_WARP_SPHERICAL);
+            else if (w->kind == ISX_WARP_SPHERICAL) ISX_WARP_IMG(ISX_WARP_SPHERICAL);
+            else ISX_WARP_IMG(ISX_WARP_PLANE);
 #undef ISX_WARP_IMG
         } else if (small && src->type == ISX_8UC1 && interp == ISX_INTER_NEAREST && border == ISX_BORDER_CONSTANT) {
             const WarpMaskArgs wma{w->proj, t, sv, dp, (unsigned)ds, dw, dh};
             const dim3 gridm(cdiv(dw, 64), cdiv(dh, 16));
 #define ISX_WARP_MSK(KD) ISX_LAUNCH("warp_tile_mask", bytes, st, (k_warp_mask_tile<KD, true>), gridm, dim3(256), 0, wma)
             if (w->kind == ISX_WARP_CYLINDRICAL) ISX_WARP_MSK(ISX_WARP_CYLINDRICAL);
-            else ISX_WARP_MSK(ISX_WARP_SPHERICAL);
+            else if (w->kind == ISX_WARP_SPHERICAL) ISX_WARP_MSK(ISX_WARP_SPHERICAL);
+            else ISX_WARP_MSK(ISX_WARP_PLANE);
 #undef ISX_WARP_MSK
-        } else
+        } else {
+#define ISX_WARP_ANY(T, CN)                                                                                                                          \
+    do {                                                                                                                                             \
+        if (w->kind == ISX_WARP_PLANE) ISX_LAUNCH("warp", bytes, st, (k_warp<T, CN, true>), grid, dim3(256), 0, w->proj, t, sv, dp, ds, dw, dh, interp, border); \
+        else ISX_LAUNCH("warp", bytes, st, (k_warp<T, CN>), grid, dim3(256), 0, w->proj, t, sv, dp, ds, dw, dh, interp, border);                      \
+    } while (0)
         switch (src->type) {
-            case ISX_8UC3: ISX_LAUNCH("warp", bytes, st, (k_warp<unsigned char, 3>), grid, dim3(256), 0, w->proj, t, sv, dp, ds, dw, dh, interp, border); break;
-            case ISX_8UC1: ISX_LAUNCH("warp", bytes, st, (k_warp<unsigned char, 1>), grid, dim3(256), 0, w->proj, t, sv, dp, ds, dw, dh, interp, border); break;
-            case ISX_32FC3: ISX_LAUNCH("warp", bytes, st, (k_warp<float, 3>), grid, dim3(256), 0, w->proj, t, sv, dp, ds, dw, dh, interp, border); break;
-            case ISX_32FC1: ISX_LAUNCH("warp", bytes, st, (k_warp<float, 1>), grid, dim3(256), 0, w->proj, t, sv, dp, ds, dw, dh, interp, border); break;
+            case ISX_8UC3: ISX_WARP_ANY(unsigned char, 3); break;
+            case ISX_8UC1: ISX_WARP_ANY(unsigned char, 1); break;
+            case ISX_32FC3: ISX_WARP_ANY(float, 3); break;
+            case ISX_32FC1: ISX_WARP_ANY(float, 1); break;
             default: return fail(ISX_ERR_TYPE, "warp: src type %s is not supported (CV_8UC1/3, CV_32FC1/3)", type_name(src->type));
+        }
+#undef ISX_WARP_ANY
         }
     }
     if (ranged) ISX_TRY(w->st_dst.finish_out_cols(st, rc0, rc1)); else ISX_TRY(w->st_dst.finish_out(st));
@@ -1780,7 +1882,7 @@ int isx_warper_create(int kind, float scale, int device, isx_warper** out) ISX_E
     clear_error();
     ISX_CHECK_ARG(out != nullptr, ISX_ERR_INVALID, "isx_warper_create: null out pointer");
     *out = nullptr;
-    ISX_CHECK_ARG(kind == ISX_WARP_CYLINDRICAL || kind == ISX_WARP_SPHERICAL, ISX_ERR_INVALID, "isx_warper_create: unknown warper kind %d", kind);
+    ISX_CHECK_ARG(kind == ISX_WARP_CYLINDRICAL || kind == ISX_WARP_SPHERICAL || kind == ISX_WARP_PLANE, ISX_ERR_INVALID, "isx_warper_create: unknown warper kind %d", kind);
     ISX_CHECK_ARG(std::isfinite(scale) && scale > 0.f, ISX_ERR_INVALID, "isx_warper_create: scale must be positive, got %g", (double)scale);
     int n = 0;
     ISX_HIP(hipGetDeviceCount(&n));
@@ -1864,6 +1966,25 @@ int isx_warper_set_gain(isx_warper* w, double gain) ISX_ENTRY {
     return ISX_OK;
 } ISX_EXIT("isx_warper_set_gain")
 
+int isx_warper_set_translation(isx_warper* w, const float T[3]) ISX_ENTRY {
+    clear_error();
+    ISX_CHECK_ARG(w != nullptr && T != nullptr, ISX_ERR_INVALID, "isx_warper_set_translation: null argument");
+    ISX_CHECK_ARG(std::isfinite(T[0]) && std::isfinite(T[1]) && std::isfinite(T[2]), ISX_ERR_INVALID, "isx_warper_set_translation: T contains non-finite values");
+    ISX_CHECK_ARG(w->kind == ISX_WARP_PLANE || (T[0] == 0.f && T[1] == 0.f && T[2] == 0.f), ISX_ERR_UNSUPPORTED,
+                  "isx_warper_set_translation: only the plane warper takes a translation (cv::detail::PlaneWarper)");
+    for (int i = 0; i < 3; ++i) w->t[i] = T[i];
+    return ISX_OK;
+} ISX_EXIT("isx_warper_set_translation")
+
+int isx_warper_warp_point(isx_warper* w, const float K[9], const float R[9], float x, float y, float out_uv[2]) ISX_ENTRY {
+    clear_error();
+    ISX_CHECK_ARG(w != nullptr && out_uv != nullptr, ISX_ERR_INVALID, "isx_warper_warp_point: null argument");
+    ISX_TRY(set_camera(w, K, R));
+    if (w->kind == ISX_WARP_PLANE) map_forward_plane_host(w->proj, w->t, x, y, out_uv[0], out_uv[1]);
+    else map_forward_host(w->proj, x, y, out_uv[0], out_uv[1]);
+    return ISX_OK;
+} ISX_EXIT("isx_warper_warp_point")
+
 int isx_warper_table_resets(isx_warper* w, long long* resets) ISX_ENTRY {
     ISX_CHECK_ARG(w != nullptr && resets != nullptr, ISX_ERR_INVALID, "isx_warper_table_resets: null argument");
     *resets = w->tab_resets;
@@ -1922,8 +2043,12 @@ int build_maps_common(isx_warper* w, int src_w, int src_h, const float K[9], con
     ISX_TRY(w->st_x.use_out(xmap, st, "buildMaps: xmap"));
     ISX_TRY(w->st_y.use_out(ymap, st, "buildMaps: ymap"));
     dim3 grid(cdiv(dw, 64), cdiv(dh, 4));
-    ISX_LAUNCH("build_maps", (double)dw * dh * 8.0, st, k_build_maps, grid, dim3(256), 0, w->proj, t, (float*)w->st_x.d.data, w->st_x.d.step,
-               (float*)w->st_y.d.data, w->st_y.d.step, dw, dh);
+    if (w->kind == ISX_WARP_PLANE)
+        ISX_LAUNCH("build_maps", (double)dw * dh * 8.0, st, k_build_maps<true>, grid, dim3(256), 0, w->proj, t, (float*)w->st_x.d.data, w->st_x.d.step,
+                   (float*)w->st_y.d.data, w->st_y.d.step, dw, dh);
+    else
+        ISX_LAUNCH("build_maps", (double)dw * dh * 8.0, st, k_build_maps<false>, grid, dim3(256), 0, w->proj, t, (float*)w->st_x.d.data, w->st_x.d.step,
+                   (float*)w->st_y.d.data, w->st_y.d.step, dw, dh);
     ISX_TRY(w->st_x.finish_out(st));
     ISX_TRY(w->st_y.finish_out(st));
     return ISX_OK;
@@ -2021,7 +2146,7 @@ int isx_warper_warp_with_mask_roi(isx_warper* w, const isx_mat* src_img, const i
 int isx_selftest_roi_host(int kind, float scale, const float K[9], const float R[9], int src_w, int src_h, int isa, int roi[4], float minmax[4]) ISX_ENTRY {
     clear_error();
     ISX_CHECK_ARG(K != nullptr && R != nullptr && roi != nullptr, ISX_ERR_INVALID, "selftest_roi_host: null argument");
-    ISX_CHECK_ARG((kind == ISX_WARP_CYLINDRICAL || kind == ISX_WARP_SPHERICAL) && src_w > 0 && src_h > 0, ISX_ERR_INVALID, "selftest_roi_host: bad kind / size");
+    ISX_CHECK_ARG((kind == ISX_WARP_CYLINDRICAL || kind == ISX_WARP_SPHERICAL || kind == ISX_WARP_PLANE) && src_w > 0 && src_h > 0, ISX_ERR_INVALID, "selftest_roi_host: bad kind / size");
     Proj p;
     float k[9], rinv[9], kinv[9];
     for (int i = 0; i < 9; ++i) k[i] = K[i];
@@ -2030,6 +2155,11 @@ int isx_selftest_roi_host(int kind, float scale, const float K[9], const float R
     mat3_mul(R, kinv, p.r_kinv);
     mat3_mul(K, rinv, p.k_rinv);
     p.scale = scale; p.kind = kind;
+    if (kind == ISX_WARP_PLANE) {      // the four-corner rule, T = 0
+        const float t0[3] = {0.f, 0.f, 0.f};
+        roi_plane_host(p, t0, src_w, src_h, roi, minmax);
+        return ISX_OK;
+    }
     ISX_CHECK_ARG(kind == ISX_WARP_SPHERICAL || cyl_extrema_on_border(p, k, rinv, src_w, src_h), ISX_ERR_UNSUPPORTED,
                   "selftest_roi_host: the extrema of this cylindrical camera are not provably on the border");
     std::vector<int> cand;
@@ -2041,6 +2171,26 @@ int isx_selftest_roi_host(int kind, float scale, const float K[9], const float R
     if (minmax) std::copy(mm, mm + 4, minmax);
     return ISX_OK;
 } ISX_EXIT("isx_selftest_roi_host")
+
+// isx_warper_warp_point without a handle (a handle needs a device): mapForward of one point on the host, so that the CPU test-suite can
+// compare it with the models.  T may be null (zeros); a non-zero T is refused for the kinds that take none.
+int isx_selftest_warp_point(int kind, float scale, const float K[9], const float R[9], const float T[3], float x, float y, float out_uv[2]) ISX_ENTRY {
+    clear_error();
+    ISX_CHECK_ARG(K != nullptr && R != nullptr && out_uv != nullptr, ISX_ERR_INVALID, "selftest_warp_point: null argument");
+    ISX_CHECK_ARG(kind == ISX_WARP_CYLINDRICAL || kind == ISX_WARP_SPHERICAL || kind == ISX_WARP_PLANE, ISX_ERR_INVALID, "selftest_warp_point: unknown warper kind %d", kind);
+    const float t[3] = {T ? T[0] : 0.f, T ? T[1] : 0.f, T ? T[2] : 0.f};
+    ISX_CHECK_ARG(kind == ISX_WARP_PLANE || (t[0] == 0.f && t[1] == 0.f && t[2] == 0.f), ISX_ERR_UNSUPPORTED, "selftest_warp_point: only the plane warper takes a translation");
+    Proj p;
+    float rinv[9], kinv[9];
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) rinv[i * 3 + j] = R[j * 3 + i];
+    mat3_inv(K, kinv);
+    mat3_mul(R, kinv, p.r_kinv);
+    mat3_mul(K, rinv, p.k_rinv);
+    p.scale = scale; p.kind = kind;
+    if (kind == ISX_WARP_PLANE) map_forward_plane_host(p, t, x, y, out_uv[0], out_uv[1]);
+    else map_forward_host(p, x, y, out_uv[0], out_uv[1]);
+    return ISX_OK;
+} ISX_EXIT("isx_selftest_warp_point")
 
 int isx_selftest_division(int device, int n, unsigned long long seed, int* mismatches) ISX_ENTRY {
     clear_error();
@@ -2068,7 +2218,7 @@ int isx_warper_verify_is_light(isx_warper* w, int src_cols, int src_rows, const 
     clear_error();
     ISX_CHECK_ARG(w != nullptr && light != nullptr && src_cols > 0 && src_rows > 0, ISX_ERR_INVALID, "isx_warper_verify_is_light: bad argument");
     ISX_TRY(set_camera(w, K, R));
-    *light = (w->kind == ISX_WARP_SPHERICAL || cyl_extrema_on_border(w->proj, w->k, w->rinv, src_cols, src_rows)) ? 1 : 0;
+    *light = (w->kind == ISX_WARP_PLANE || w->kind == ISX_WARP_SPHERICAL || cyl_extrema_on_border(w->proj, w->k, w->rinv, src_cols, src_rows)) ? 1 : 0;
     return ISX_OK;
 } ISX_EXIT("isx_warper_verify_is_light")
 
@@ -2104,6 +2254,10 @@ int isx_warper_queue_verify(isx_warper* w, int src_w, int src_h, const float K[9
     ISX_CHECK_ARG(src_w > 0 && src_h > 0, ISX_ERR_INVALID, "isx_warper_queue_verify: empty source %d x %d", src_w, src_h);
     ISX_HIP(hipSetDevice(w->device));
     ISX_TRY(set_camera(w, K, R));
+    if (w->kind == ISX_WARP_PLANE) {      // four corners, compared here (detect_roi)
+        int scratch[4];
+        return detect_roi(w, src_w, src_h, scratch, nullptr, true, planned_roi);
+    }
     isx_warper::Pending pd;
     pd.proj = w->proj; pd.sw = src_w; pd.sh = src_h;
     std::copy(planned_roi, planned_roi + 4, pd.planned);
@@ -2128,10 +2282,12 @@ int isx_warper_plan_status(isx_warper* w, int* mismatches) ISX_ENTRY {
     *mismatches = 0;
     ISX_HIP(hipSetDevice(w->device));
     ISX_TRY(flush_verify(w));
-    if (!w->scan_side.p) return ISX_OK;
-    ISX_HIP(hipStreamSynchronize(w->side));
-    ISX_HIP(hipStreamSynchronize(w->stream));
-    ISX_HIP(hipMemcpy(mismatches, (int*)w->scan_side.p + 5, sizeof(int), hipMemcpyDeviceToHost));
+    if (w->scan_side.p) {
+        ISX_HIP(hipStreamSynchronize(w->side));
+        ISX_HIP(hipStreamSynchronize(w->stream));
+        ISX_HIP(hipMemcpy(mismatches, (int*)w->scan_side.p + 5, sizeof(int), hipMemcpyDeviceToHost));
+    }
+    *mismatches += w->plan_mismatches_host;      // plane handles: the four-corner rule, compared when the planned warp was issued
     if (*mismatches) return fail(ISX_ERR_PLAN, "planned warp: %d run(s) produced a ROI that differs from the planned one", *mismatches);
     return ISX_OK;
 } ISX_EXIT("isx_warper_plan_status")

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib, synth
 from .blender import MultiBandBlender
-from .warper import CylindricalWarper, SphericalWarper
+from .warper import CREATORS
 
 
 def feed_geometry(roi, num_bands, tl, size):
@@ -84,7 +84,7 @@ class PairStitcher:
         # tile_type "s16": the warped tiles are CV_16SC3 - the warp writes them so (the convertTo(CV_16S) of W:294 folded into its store) and
         # feed() receives what the reference's feed() receives (W:302); "u8": CV_8UC3 tiles through feed_u8 (the conversion fused into feed)
         self.tile_type = tile_type
-        creator = CylindricalWarper if kind == "cylindrical" else SphericalWarper
+        creator = CREATORS[kind]
         self.warper = creator(device, stream).create(scale)
         self.warper.set_deferred_verify(True)   # both ROI scans start after the last warp of a step (see step())
         self.blender = MultiBandBlender(False, num_bands, precision, device, stream)
@@ -428,7 +428,7 @@ class SplitStitcher:
         from . import mosaic
         self.torch = torch
         dev = torch.device("cuda", device)
-        creator = CylindricalWarper if kind == "cylindrical" else SphericalWarper
+        creator = CREATORS[kind]
         wp = creator(device, None).create(scale)
         src_size = (imgs[0].shape[1], imgs[0].shape[0])
         rois = [wp.warpRoi(src_size, K, R) for R in Rs]

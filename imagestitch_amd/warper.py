@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (BORDER_CONSTANT, BORDER_REFLECT, INTER_LINEAR, INTER_NEAREST, WARP_CYLINDRICAL,  # noqa: F401
-                   WARP_SPHERICAL, IsxError, as_mat, check, f9)
+                   WARP_PLANE, WARP_SPHERICAL, IsxError, as_mat, check, f9)
 
 
 def _is_tensor(a):
@@ -175,6 +175,20 @@ class RotationWarper:
         """GainCompensator::apply (W:241-244) folded into the fused warps that follow (warp_with_mask*, all-255 mask): isx_warper_set_gain."""
         check(self._lib.isx_warper_set_gain(self._h, C.c_double(float(gain))))
 
+    def set_translation(self, T=(0.0, 0.0, 0.0)):
+        """cv::detail::PlaneWarper's T (the `T` overloads of warp / buildMaps / warpRoi / warpPoint): isx_warper_set_translation.  Sticky;
+        zero is what the overloads without T pass.  Only a plane warper takes a non-zero one."""
+        t = np.ascontiguousarray(np.asarray(T, dtype=np.float32).reshape(3))
+        check(self._lib.isx_warper_set_translation(self._h, t.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def warpPoint(self, pt, K, R):
+        """RotationWarper::warpPoint(pt, K, R): mapForward of one source point, on the host (isx_warper_warp_point) -> (u, v) float32."""
+        _k, kp = f9(K)
+        _r, rp = f9(R)
+        uv = (C.c_float * 2)()
+        check(self._lib.isx_warper_warp_point(self._h, kp, rp, C.c_float(float(pt[0])), C.c_float(float(pt[1])), uv))
+        return np.float32(uv[0]), np.float32(uv[1])
+
     def set_dst_columns(self, col0=0, col1=0):
         """The fused warps that follow produce only the columns [col0, col1) of the warped tile (isx_warper_set_dst_columns)."""
         check(self._lib.isx_warper_set_dst_columns(self._h, int(col0), int(col1)))
@@ -236,6 +250,14 @@ class CylindricalWarper(_Creator):
 class SphericalWarper(_Creator):
     """cv::SphericalWarper (B:93, commented out in the reference)."""
     kind = WARP_SPHERICAL
+
+
+class PlaneWarper(_Creator):
+    """cv::PlaneWarper (B:91, the first line of the reference's warper list): no transcendental, takes a translation (set_translation)."""
+    kind = WARP_PLANE
+
+
+CREATORS = {"cylindrical": CylindricalWarper, "spherical": SphericalWarper, "plane": PlaneWarper}
 
 
 def remap(src, xmap, ymap, interp_mode=INTER_LINEAR, border_mode=BORDER_REFLECT, device=0, stream=None):

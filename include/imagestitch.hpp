@@ -34,6 +34,7 @@ enum { BORDER_CONSTANT = ISX_BORDER_CONSTANT, BORDER_REPLICATE = ISX_BORDER_REPL
        BORDER_REFLECT_101 = ISX_BORDER_REFLECT_101 };
 
 struct Point { int x = 0, y = 0; Point() = default; Point(int x_, int y_) : x(x_), y(y_) {} };
+struct Point2f { float x = 0.f, y = 0.f; Point2f() = default; Point2f(float x_, float y_) : x(x_), y(y_) {} };
 struct Size { int width = 0, height = 0; Size() = default; Size(int w, int h) : width(w), height(h) {} };
 struct Rect { int x = 0, y = 0, width = 0, height = 0; };
 
@@ -127,6 +128,15 @@ public:
         return Point(roi[0], roi[1]);
     }
     void setGain(double gain) { check(isx_warper_set_gain(h_, gain)); }
+    // cv::detail::PlaneWarper's T (its warp / buildMaps / warpRoi / warpPoint overloads with a translation): sticky, zero by default; only a
+    // warper made by PlaneWarper takes a non-zero one (isx_warper_set_translation)
+    void setTranslation(const float T[3]) { check(isx_warper_set_translation(h_, T)); }
+    // Point2f warpPoint(pt, K, R): mapForward of one source point, on the host (isx_warper_warp_point)
+    Point2f warpPoint(Point2f pt, const float K[9], const float R[9]) {
+        float uv[2];
+        check(isx_warper_warp_point(h_, K, R, pt.x, pt.y, uv));
+        return Point2f(uv[0], uv[1]);
+    }
     // Not in the reference: the fused tile warps issued between the two calls (planned or _roi forms on device mats) leave as ONE launch
     // (isx_warper_begin_batch / isx_warper_end_batch); their outputs exist once endBatch() has returned and its launch has run
     void beginBatch() { check(isx_warper_begin_batch(h_)); }
@@ -142,6 +152,9 @@ struct CylindricalWarper : WarperCreator {   // cv::CylindricalWarper  W:219
 };
 struct SphericalWarper : WarperCreator {     // cv::SphericalWarper  B:93 (commented out in the reference)
     std::shared_ptr<RotationWarper> create(float scale) const override { return std::make_shared<RotationWarper>(ISX_WARP_SPHERICAL, scale); }
+};
+struct PlaneWarper : WarperCreator {         // cv::PlaneWarper  B:91 (commented out in the reference)
+    std::shared_ptr<RotationWarper> create(float scale) const override { return std::make_shared<RotationWarper>(ISX_WARP_PLANE, scale); }
 };
 
 // cv::detail::Blender / MultiBandBlender (W:271-281,302,313)

@@ -64,8 +64,8 @@ enum { ISX_INTER_NEAREST = 0, ISX_INTER_LINEAR = 1,
 enum { ISX_BORDER_CONSTANT = 0, ISX_BORDER_REPLICATE = 1, ISX_BORDER_REFLECT = 2,
        ISX_BORDER_WRAP = 3, ISX_BORDER_REFLECT_101 = 4 };
 
-/* warper kinds: cv::CylindricalWarper (W:219) / cv::SphericalWarper (B:93, commented) */
-enum { ISX_WARP_CYLINDRICAL = 0, ISX_WARP_SPHERICAL = 1 };
+/* warper kinds: cv::CylindricalWarper (W:219) / cv::SphericalWarper (B:93, commented) / cv::PlaneWarper (B:91, commented) */
+enum { ISX_WARP_CYLINDRICAL = 0, ISX_WARP_SPHERICAL = 1, ISX_WARP_PLANE = 2 };
 
 /* cv::detail::Blender::{NO, FEATHER, MULTI_BAND} (W:271,276,278) */
 enum { ISX_BLEND_NO = 0, ISX_BLEND_FEATHER = 1, ISX_BLEND_MULTI_BAND = 2 };
@@ -129,6 +129,18 @@ int isx_warper_table_resets(isx_warper* w, long long* resets);
  * saturate_cast<uchar>(cvRound((double)byte * gain)) - exactly isx_gain_apply on the warped tile, one pass over it less (the gain acts on
  * the remapped byte, not on the source: remap of scaled pixels is a different number).  gain = 1.0 switches it off.                    */
 int isx_warper_set_gain(isx_warper* w, double gain);
+/* cv::detail::PlaneWarper's translation (B:91 `cv::PlaneWarper()`, created at W:217-222): the T of its warp / buildMaps / warpRoi /
+ * warpPoint (src, K, R, T, ...) overloads, a 3x1 CV_32F.  Sticky like the gain: every call that follows on this handle projects with it;
+ * the default is zero, which is what the overloads without T pass.  Finite values only.  ISX_ERR_UNSUPPORTED on a handle that is not a
+ * plane warper, unless T is all zero.  The plane ROI is mapForward of the four source corners (min / max, trunc-toward-zero casts): it is
+ * computed on the caller's thread, with nothing launched and no synchronisation; a planned warp's ROI is verified by the same rule when the
+ * warp is issued, and isx_warper_plan_status reports a mismatch.                                                                          */
+int isx_warper_set_translation(isx_warper* w, const float T[3]);
+/* RotationWarper::warpPoint(pt, K, R) (the creators of B:91-95, W:217-222): mapForward of one source point under (K, R) - and the handle's
+ * translation, for a plane warper - on the host, with the host's libm as the stock classes use it.  out_uv = {u, v}; no device work.
+ * Like every entry that takes (K, R) it is a setCameraParams on the handle: it overwrites the handle's current projection (harmless - each
+ * entry sets the camera it is given - but a change of handle state), so it must not run concurrently with another call on the same handle. */
+int isx_warper_warp_point(isx_warper* w, const float K[9], const float R[9], float x, float y, float out_uv[2]);
 
 /* buildMaps (W:122-144): xmap,ymap are caller-allocated CV_32FC1 of
  * (roi[3]-roi[1]+1) rows x (roi[2]-roi[0]+1) cols (W:128-129).                               */
@@ -182,6 +194,10 @@ int isx_warper_warp_with_mask_planned(isx_warper* w, const isx_mat* src_img,
  * batch before it waits for the stream: a warp that returned ISX_OK always writes its output.                                          */
 int isx_warper_begin_batch(isx_warper* w);
 int isx_warper_end_batch(isx_warper* w);
+/* The count is STICKY for the life of the handle, for every kind: the device-side counter of the cylindrical / spherical scans is never
+ * cleared, and neither is the host-side count of a plane handle's four-corner checks (isx_warper_discard_pending drops verifications that
+ * have not run yet, not findings).  After one stale plan every later isx_warper_plan_status of that handle returns ISX_ERR_PLAN: make a
+ * new plan on a new handle.                                                                                                           */
 int isx_warper_plan_status(isx_warper* w, int* mismatches /* synchronises the stream */);
 /* The verification scans of planned warps run on an internal side stream.  isx_warper_join makes the
  * handle's stream wait for them without blocking the host — required before hipStreamEndCapture when
@@ -584,6 +600,10 @@ int isx_selftest_division(int device, int n, unsigned long long seed, int* misma
  * Needs no device: the CPU test-suite compares it with the oracle's scan of every source pixel.  isa: 0 = the code isx_warper_roi runs
  * (AVX-512F where the CPU has it, else AVX2, else scalar), 1 = its scalar form, 2 = its AVX2 form.  ISX_ERR_UNSUPPORTED for a cylindrical camera outside that proof (isx_warper_roi scans every pixel on the GPU there). */
 int isx_selftest_roi_host(int kind, float scale, const float K[9], const float R[9], int src_w, int src_h, int isa, int roi[4], float minmax[4]);
+/* isx_warper_warp_point (RotationWarper::warpPoint, B:91-95, W:217-222) without a handle, which needs a device: mapForward of (x, y) under
+ * (K, R) and, for ISX_WARP_PLANE, the translation T (NULL = zeros; a non-zero T is ISX_ERR_UNSUPPORTED for the other kinds).  Host code,
+ * the same functions the handle's entry calls: the CPU test-suite compares it with the plane model and the oracle's mapForward.        */
+int isx_selftest_warp_point(int kind, float scale, const float K[9], const float R[9], const float T[3], float x, float y, float out_uv[2]);
 /* Every entry of this header is a function-try-block: a C++ exception raised underneath it (std::bad_alloc of a host container, a
  * std::length_error, anything a future change throws) is stopped there and comes back as a status - ISX_ERR_NOMEM for the two allocation
  * failures, ISX_ERR_INTERNAL otherwise, the text in isx_last_error() - never as an exception in the caller's frames (the
