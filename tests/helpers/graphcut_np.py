@@ -100,9 +100,11 @@ def max_flow(g):
     A = sp.csr_matrix((caps.astype(np.int32), (rows, cols)), shape=(n + 2, n + 2))
     r = maximum_flow(A, S, T, method="dinic")
     F = r.flow.tocsr()
-    fe = np.asarray(F[u, v]).ravel().astype(np.int64)    # net flow u -> v of each grid edge
-    fs = np.asarray(F[np.full(len(si), S), si]).ravel().astype(np.int64)
-    ft = np.asarray(F[ti, np.full(len(ti), T)]).ravel().astype(np.int64)
+    def at(rows, cols):                                  # F[rows, cols] as int64; an empty index pair (no terminal of that kind) gives a matrix, not an array
+        return np.asarray(F[rows, cols]).ravel().astype(np.int64) if len(rows) else np.zeros(0, np.int64)
+    fe = at(u, v)                                        # net flow u -> v of each grid edge
+    fs = at(np.full(len(si), S), si)
+    ft = at(ti, np.full(len(ti), T))
     res = np.zeros((n, 6), np.int64)
     nr = Hp * (Wp - 1)
     ru, rv = c - fe, c + fe                              # residual u -> v and v -> u

@@ -1,6 +1,8 @@
-"""A 20-second, fixed-seed slice of tools/fuzz_parity.py (the randomised HIP-vs-oracle sweep over every entry point: warps, the fused
-tile kernel, the blenders in all precisions and cycles, mask preparation, the seam finder, the linear pair blend, whole pairs through
-PairStitcher) under -m gpu.  The long soaks are kept as JSON summaries under profiles/."""
+"""A 20-second, fixed-seed slice of tools/fuzz_parity.py (the randomised HIP-vs-oracle sweep over every entry point, 24 families: warps, the
+fused tile kernel, the blenders in all precisions and cycles, mask preparation, the seam finder, the linear pair blend, whole pairs through
+PairStitcher, and - against their NumPy models - the plane projector, GainCompensator::feed, the Voronoi and graph-cut seam finders and
+the COLOR_GRAD cost with seam_gradients) under -m gpu, then 8 seconds of the last five families alone, whose shape classes sit on their
+kernels' tiling constants.  The long soaks are kept as JSON summaries under profiles/."""
 import os
 import sys
 
@@ -16,6 +18,19 @@ def test_fuzz_slice_20s(gpu):
     out = fuzz_parity.run(20.0, 20260928, verbose=True)
     assert out["mismatches"] == 0, out["failing_seeds"]
     assert out["cases"] >= 100 and all(v["cases"] > 0 for v in out["per_family"].values()), out["per_family"]
+
+
+def test_fuzz_slice_new_families(gpu):
+    """The five families of the entry points merged after round 6, alone: each gets enough of the 8 seconds to run at least 5 cases."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "tools"))
+    import fuzz_parity
+    out = fuzz_parity.run(8.0, 20261017, verbose=True, only=fuzz_parity.NEW_FAMILIES)
+    print(out["per_family"], "skipped", out["skipped_geometries"])
+    assert out["mismatches"] == 0, out["failing_seeds"]
+    assert sorted(out["per_family"]) == sorted(fuzz_parity.NEW_FAMILIES)
+    assert all(v["cases"] >= 5 for v in out["per_family"].values()), out["per_family"]
+    assert out["skipped_geometries"] * 10 <= out["cases"], (out["skipped_geometries"], out["cases"])
 
 
 # seeds the soaks have tripped over, kept as cases of their own (family, seed):

@@ -114,6 +114,26 @@ def test_penalty_where_a_mask_byte_is_zero():
     assert g["src"][10, 11] == 10000 and g["snk"][10, 11] == 0             # mask 1 only: a source link
 
 
+def test_a_graph_without_source_or_sink_terminals():
+    """One mask empty: the other tile's cells are all of one terminal kind, or - both masks covering the same cells - there is no terminal
+    at all.  The flow is 0, the maximal source side is every node that cannot reach a sink link, and find() writes accordingly."""
+    pytest.importorskip("scipy")
+    img = np.full((12, 14, 3), 50, np.uint8)
+    full, empty = np.full((12, 14), 255, np.uint8), np.zeros((12, 14), np.uint8)
+    roi = G.overlap_roi((0, 0), (0, 0), (14, 12), (14, 12))
+    for m1, m2, src_side in ((full, empty, True), (empty, full, False), (full, full, True), (empty, empty, True)):
+        g = G.pair_graph(img, img, m1, m2, (0, 0), (0, 0), roi)
+        assert bool(g["src"].any()) == bool(m1.any() and not m2.any()) and bool(g["snk"].any()) == bool(m2.any() and not m1.any())
+        flow, cert = G.max_flow(g)
+        assert flow == 0
+        G.check_certificate(g, flow, cert["residuals"], cert["labels"])
+        assert (cert["labels"] == (1 if src_side else 0)).all()              # no sink link anywhere: every node is on the source side
+        a, b = m1.copy(), m2.copy()
+        G.find([img, img], [(0, 0), (0, 0)], [a, b])
+        # source side and mask 1 set -> mask 2 cleared; otherwise mask 2 set -> mask 1 cleared
+        assert np.array_equal(a, m1) and np.array_equal(b, empty if (src_side and m1.any()) else m2)
+
+
 def test_roi_at_a_tile_border():
     """Tiles meeting corner to corner: the gap reaches past both tiles, where nodes read image 0 and mask 0."""
     img1 = np.full((20, 20, 3), 7, np.uint8)

@@ -808,19 +808,469 @@ def case_long_lived(rng):
     torch.cuda.synchronize()
 
 
+# ---- the families of the entry points merged after round 6 -----------------------------------------------------------------------------
+# Each is three functions: gen_X(rng) draws the inputs (a dict; case["cls"] names the shape class), model_X(case) runs the NumPy model -
+# neither needs a GPU, tests/test_fuzz_generators.py runs them alone - and case_X(rng) runs the GPU entry on them and asserts.  The shape
+# classes sit on the kernels' tiling constants, which are read from the kernels' sources: a constant that moves takes its classes along.
+
+def _kernel_consts(name):
+    """The `constexpr int NAME = <integer or earlier name> [* <integer or earlier name>]...;` definitions of imagestitch_amd/csrc/<name>
+    (several in one declaration too); definitions of another form, such as shifts, are left out, and a name in a product that was left out
+    is an error."""
+    import re
+    out = {}
+    with open(os.path.join(ROOT, "imagestitch_amd", "csrc", name)) as f:
+        text = f.read()
+    for decl in re.findall(r"constexpr\s+int\s+([^;{}()]+);", text):
+        for part in decl.split(","):
+            m = re.fullmatch(r"\s*(\w+)\s*=\s*(\w+(?:\s*\*\s*\w+)*)\s*", part)
+            if not m:
+                continue
+            value = 1
+            for tok in re.split(r"\s*\*\s*", m.group(2)):
+                if not tok.isdigit() and tok not in out:
+                    raise ValueError("%s: %s is defined through %s, which is no integer constant read before it" % (name, m.group(1), tok))
+                value *= int(tok) if tok.isdigit() else out[tok]
+            out[m.group(1)] = value
+    return out
+
+
+_VR, _GC, _GF, _SM = (_kernel_consts(n) for n in ("voronoi.hip", "graphcut.hip", "gain.hip", "seam.hip"))
+SEAM_GAP = 10                                                           # the gap of OpenCV's pairwise seam finders: grids are roi + 2 * gap a side
+VR_WIDTHS = [_VR["VR_CHUNK"] - 1, _VR["VR_CHUNK"], _VR["VR_CHUNK"] + 1, 2 * _VR["VR_CHUNK"], 2 * _VR["VR_CHUNK"] + 1]      # of a submask
+VR_HEIGHTS = [_VR["VR_SEG"] - 1, _VR["VR_SEG"], _VR["VR_SEG"] + 1, 2 * _VR["VR_SEG"], 2 * _VR["VR_SEG"] + 1]
+GC_WIDTHS = [_GC["GC_TW"] - 1, _GC["GC_TW"], _GC["GC_TW"] + 1, 2 * _GC["GC_TW"], 2 * _GC["GC_TW"] + 1]                      # of a padded grid
+GC_HEIGHTS = [2 * _GC["GC_TH"] - 1, 2 * _GC["GC_TH"], 2 * _GC["GC_TH"] + 1, 3 * _GC["GC_TH"]]                                # (one tile row is below roi + 20)
+GF_PAIR_SIZES = [_GF["GF_PAIR_PIXELS"] - 1, _GF["GF_PAIR_PIXELS"], _GF["GF_PAIR_PIXELS"] + 1, 2 * _GF["GF_PAIR_PIXELS"], 2 * _GF["GF_PAIR_PIXELS"] + 1]
+GF_DIAG_SIZES = [_GF["GF_DIAG_BYTES"] - 1, _GF["GF_DIAG_BYTES"], _GF["GF_DIAG_BYTES"] + 1]
+GRAD_WIDTHS = [_SM["GRAD_TW"] - 1, _SM["GRAD_TW"], _SM["GRAD_TW"] + 1, 2 * _SM["GRAD_TW"] + 1]
+GRAD_HEIGHTS = [_SM["GRAD_TH"] - 1, _SM["GRAD_TH"], _SM["GRAD_TH"] + 1, 2 * _SM["GRAD_TH"] + 1]
+
+PLANE_ALL_PAIRS_BELOW = 1 << 17                                          # result pixels up to which case_plane_warp runs all eight warp() modes
+PLANE_CLASSES = ["plain", "tiny", "odd_width", "with_T"]
+GAIN_CLASSES = ["plain", "pair_item_edge", "diag_item_edge", "one_pixel_overlap", "disjoint_pair"]
+VORONOI_CLASSES = ["plain", "chunk_edge", "seg_edge", "thin", "no_unique_rows"]
+GRAPHCUT_CLASSES = ["plain", "tile_edge_w", "tile_edge_h", "flat_tie", "holes_heavy"]
+SEAM_GRAD_CLASSES = ["plain", "tile_edge", "one_pixel", "rect_at_border", "find"]          # the first four: seam_gradients; "find": the whole finder
+WHERE = ["host", "device", "host_view", "device_view"]
+
+
+def overlap_roi(tl1, tl2, sz1, sz2):
+    """cv::detail::overlapRoi: (x, y, w, h) or None.  sz = (width, height)."""
+    x_tl, y_tl = max(tl1[0], tl2[0]), max(tl1[1], tl2[1])
+    x_br, y_br = min(tl1[0] + sz1[0], tl2[0] + sz2[0]), min(tl1[1] + sz1[1], tl2[1] + sz2[1])
+    return (x_tl, y_tl, x_br - x_tl, y_br - y_tl) if x_tl < x_br and y_tl < y_br else None
+
+
+def _pick(rng, seq):
+    return seq[int(rng.integers(0, len(seq)))]
+
+
+def _factor_pair(rng, n):
+    """(w, h) with w * h == n, any divisor pair in either order."""
+    w = _pick(rng, [d for d in range(1, n + 1) if n % d == 0])
+    return w, n // w
+
+
+def _pair_with_overlap(rng, ow, oh):
+    """Two tiles whose overlapRoi is exactly ow x oh: (corners, sizes), the tile that starts the overlap first or second."""
+    a, b, c, d = (int(v) for v in rng.integers(0, 16, 4))
+    x0, y0 = int(rng.integers(-40, 40)), int(rng.integers(-30, 30))
+    corners, sizes = [(x0, y0), (x0 + a, y0 + b)], [(ow + a, oh + b), (ow + c, oh + d)]
+    if rng.integers(0, 2):
+        corners.reverse(); sizes.reverse()
+    return corners, sizes
+
+
+def _tile_onto(rng, corners, sizes, wr, hr):
+    """One more tile of wr x hr (ranges) that overlaps one of the tiles placed so far near that tile's corner."""
+    w, h = int(rng.integers(*wr)), int(rng.integers(*hr))
+    k = int(rng.integers(0, len(corners)))
+    corners.append((corners[k][0] + int(rng.integers(-w + 1, min(sizes[k][0], 60))), corners[k][1] + int(rng.integers(-h + 1, min(sizes[k][1], 40)))))
+    sizes.append((w, h))
+
+
+def _dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _host(a):
+    return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+
+
+def _place(arrays, where, seed):
+    """The arrays as the GPU entry gets them: host copies, device tensors, or (the views() of the fixed-seed files) each one inside a larger
+    buffer of 7s at an odd offset with a pitch that is no multiple of 16.  -> [(mat, buffer or None, (oy, ox, h, w))]"""
+    out = []
+    for k, a in enumerate(arrays):
+        h, w = a.shape[:2]
+        if not where.endswith("_view"):
+            out.append((_dev(a) if where == "device" else a.copy(), None, None))
+            continue
+        oy, ox, pad = 1 + k % 3, 1 + (k + seed) % 5, 3 + 2 * k
+        b = np.full((h + oy + 2, w + ox + pad) + a.shape[2:], 7, a.dtype)
+        if where == "device_view":
+            b = _dev(b)
+        v = b[oy:oy + h, ox:ox + w]
+        v[...] = _dev(a) if where == "device_view" else a
+        out.append((v, b, (oy, ox, h, w)))
+    return out
+
+
+def _frame_untouched(placed):
+    for k, (_, b, box) in enumerate(placed):
+        if b is not None:
+            frame = _host(b).copy()
+            frame[box[0]:box[0] + box[2], box[1]:box[1] + box[3]] = 7
+            assert (frame == 7).all(), ("wrote outside view", k)
+
+
+# ---- the plane projector ------------------------------------------------------------------------------------------------------------------
+def gen_plane_warp(rng):
+    """The rig of _rig() in tests/test_gpu_plane_warp.py (angles up to +-0.5 rad, T zero or not) on a 2..400 x 2..300 source of 1 or 3 channels."""
+    from imagestitch_amd import synth
+    cls = _pick(rng, PLANE_CLASSES)
+    w, h = int(rng.integers(2, 401)), int(rng.integers(2, 301))
+    if cls == "tiny":
+        w, h = int(rng.integers(2, 5)), int(rng.integers(2, 5))
+    elif cls == "odd_width" and w % 2 == 0:
+        w = w - 1 if w > 2 else 3
+    with_t = cls == "with_T" or (cls != "plain" and bool(rng.integers(0, 2)))
+    f = float(rng.uniform(0.9, 2.0) * max(w, h))
+    K = np.array([[f, 0, w / 2 + rng.uniform(-3, 3)], [0, f * rng.uniform(0.95, 1.05), h / 2 + rng.uniform(-3, 3)], [0, 0, 1]], np.float32)
+    yaw, pitch, roll = rng.uniform(-0.5, 0.5, 3)
+    R = (synth._rot("y", yaw) @ synth._rot("x", pitch) @ synth._rot("z", roll)).astype(np.float32)
+    T = np.array([rng.uniform(-0.3, 0.3), rng.uniform(-0.3, 0.3), rng.uniform(-0.2, 0.2)], np.float32) if with_t else None
+    cn = int(rng.choice([1, 3]))
+    return dict(cls=cls, w=w, h=h, scale=float(f * rng.uniform(0.7, 1.3)), K=K, R=R, T=T, cn=cn,
+                src=rng.integers(0, 256, (h, w, 3) if cn == 3 else (h, w)).astype(np.uint8),
+                interp=int(rng.integers(0, 2)), border=int(rng.choice([0, 1, 2, 4])), where=_pick(rng, WHERE), view_seed=int(rng.integers(0, 5)),
+                points=[(0.0, 0.0), (float(w - 1), float(h - 1))] + [(float(rng.uniform(0, w)), float(rng.uniform(0, h))) for _ in range(3)])
+
+
+def model_plane_warp(c):
+    from helpers import plane_np
+    m = plane_np.from_rig(O, c["scale"], c["K"], c["R"], c["T"])
+    roi, mm = m.detect_roi(c["w"], c["h"])
+    roi = [int(v) for v in roi]
+    if roi[2] < roi[0] or roi[3] < roi[1] or (roi[2] - roi[0] + 1) * (roi[3] - roi[1] + 1) > 4_000_000:
+        return "skip"
+    xm, ym = m.build_maps(roi)
+    pairs = [(c["interp"], c["border"])]
+    if xm.size <= PLANE_ALL_PAIRS_BELOW:                               # a small result: every interpolation with every border
+        pairs = [(i, b) for i in (0, 1) for b in (0, 1, 2, 4)]
+    want = dict(roi=tuple(roi), mm=mm, xmap=xm, ymap=ym, warp={ib: O.remap(c["src"], xm, ym, *ib) for ib in pairs},
+                points=[m.map_forward(np.float32(x), np.float32(y)) for x, y in c["points"]])
+    if c["cn"] == 3:
+        want["img"] = O.remap(c["src"], xm, ym, 1, 2)
+        want["mask"] = O.remap(np.full((c["h"], c["w"]), 255, np.uint8), xm, ym, 0, 0)
+    return want
+
+
+def case_plane_warp(rng):
+    """ISX_WARP_PLANE with set_translation: warpRoi, buildMaps, warp (all 2 x 4 interpolation / border pairs where the result has at most
+    PLANE_ALL_PAIRS_BELOW pixels, the one pair the case drew above that), the fused warp_with_mask and warpPoint against
+    tests/helpers/plane_np.py."""
+    c = gen_plane_warp(rng)
+    want = model_plane_warp(c)
+    if want == "skip":
+        return "skip"
+    wp = G.PlaneWarper().create(c["scale"])
+    if c["T"] is not None:
+        wp.set_translation(c["T"])
+    size, K, R = (c["w"], c["h"]), c["K"], c["R"]
+    roi, mm = wp.warpRoi(size, K, R, with_minmax=True)
+    assert tuple(roi) == want["roi"] and np.array_equal(mm, want["mm"]), (roi, want["roi"], mm, want["mm"])
+    r2, gx, gy = wp.buildMaps(size, K, R, like=_dev(np.zeros(1, np.float32)) if c["where"].startswith("device") else None)
+    assert tuple(r2) == want["roi"] and np.array_equal(_host(gx), want["xmap"], equal_nan=True) and np.array_equal(_host(gy), want["ymap"], equal_nan=True)
+    src = _place([c["src"]], c["where"], c["view_seed"])[0][0]
+    for (interp, border), w in want["warp"].items():
+        corner, dst = wp.warp(src, K, R, interp, border)
+        d = _host(dst)
+        assert tuple(corner) == want["roi"][:2] and np.array_equal(d, w), (interp, border, np.argwhere(d != w)[:3])
+    if c["cn"] == 3:
+        corner, gi, gm = wp.warp_with_mask(src, K, R)
+        assert tuple(corner) == want["roi"][:2] and np.array_equal(_host(gi), want["img"]) and np.array_equal(_host(gm), want["mask"])
+    for (x, y), (mu, mv) in zip(c["points"], want["points"]):
+        u, v = wp.warpPoint((x, y), K, R)
+        assert np.array_equal(np.array([u, v]), np.array([mu, mv]), equal_nan=True), (x, y, u, mu, v, mv)
+
+
+# ---- GainCompensator::feed ----------------------------------------------------------------------------------------------------------------
+def gen_gain_feed(rng):
+    """2..7 tiles, masks of 0 / 254 / 255.  The first two tiles carry the class: an overlap rectangle or a mask on a work-item boundary of
+    gain.hip (GF_PAIR_PIXELS overlap pixels, GF_DIAG_BYTES mask bytes per item), one shared pixel, or no overlap at all; every further tile
+    overlaps one placed before it."""
+    cls = _pick(rng, GAIN_CLASSES)
+    n = int(rng.integers(3 if cls in ("one_pixel_overlap", "disjoint_pair") else 2, 8))
+    if cls == "pair_item_edge":
+        corners, sizes = _pair_with_overlap(rng, *_factor_pair(rng, _pick(rng, GF_PAIR_SIZES)))
+    elif cls == "diag_item_edge":
+        w, h = _factor_pair(rng, _pick(rng, GF_DIAG_SIZES))
+        corners, sizes = [(int(rng.integers(-40, 40)), int(rng.integers(-30, 30)))], [(w, h)]
+    else:
+        corners, sizes = [(int(rng.integers(-40, 40)), int(rng.integers(-30, 30)))], [(int(rng.integers(8, 160)), int(rng.integers(6, 120)))]
+        if cls != "plain":
+            (x0, y0), (w0, h0) = corners[0], sizes[0]
+            sizes.append((int(rng.integers(8, 160)), int(rng.integers(6, 120))))
+            corners.append((x0 + w0 - 1, y0 + h0 - 1) if cls == "one_pixel_overlap" else (x0 + w0 + int(rng.integers(0, 3)), y0 + int(rng.integers(-5, 6))))
+    while len(sizes) < n:                                                # (large enough that most overlaps take several work items)
+        _tile_onto(rng, corners, sizes, (8, 160), (6, 120))
+    imgs, masks = [], []
+    for w, h in sizes:
+        imgs.append(rng.integers(int(rng.integers(0, 80)), 256, (h, w, 3), dtype=np.uint8))
+        masks.append(rng.choice(np.array([0, 254, 255, 255, 255, 255], np.uint8), size=(h, w)))
+    if cls == "one_pixel_overlap":                                     # the shared pixel counts on both sides
+        masks[0][-1, -1] = masks[1][0, 0] = 255
+    return dict(cls=cls, corners=corners, sizes=sizes, imgs=imgs, masks=masks, where=_pick(rng, WHERE), view_seed=int(rng.integers(0, 5)))
+
+
+def model_gain_feed(c):
+    from test_gain_model import feed_model
+    N, I, _, _, _, g = feed_model(c["corners"], c["imgs"], c["masks"])
+    return dict(N=N, I=I, gains=g)
+
+
+def case_gain_feed(rng):
+    """isx_gain_compensator_feed against feed_model of tests/test_gain_model.py: N exactly, I bit for bit, gains to 1e-12 relative."""
+    c = gen_gain_feed(rng)
+    want = model_gain_feed(c)
+    imgs = [p[0] for p in _place(c["imgs"], c["where"], c["view_seed"])]
+    masks = [p[0] for p in _place(c["masks"], c["where"], c["view_seed"] + 1)]
+    comp = G.GainCompensator().feed(c["corners"], imgs, masks)
+    assert np.array_equal(comp.N, want["N"]), (c["cls"], comp.N, want["N"])
+    assert np.array_equal(comp.I.view(np.uint64), want["I"].view(np.uint64)), (c["cls"], comp.I, want["I"])
+    np.testing.assert_allclose(comp.gains(), want["gains"], rtol=1e-12, atol=0)
+
+
+# ---- VoronoiSeamFinder --------------------------------------------------------------------------------------------------------------------
+def gen_voronoi(rng):
+    """2..4 tiles, per-cell holes of density 0..0.5, now and then an all-zero mask.  The first two tiles carry the class: a submask
+    (roi + 20) as wide as 1 or 2 of voronoi.hip's row-pass chunks +-1, as high as 1 or 2 of its column segments +-1, a roi one cell wide
+    or high, or rows of the overlap where neither tile has a cell of its own."""
+    cls = _pick(rng, VORONOI_CLASSES)
+    n = int(rng.integers(2, 5))
+    g2 = 2 * SEAM_GAP
+    if cls == "chunk_edge":
+        corners, sizes = _pair_with_overlap(rng, _pick(rng, VR_WIDTHS) - g2, int(rng.integers(1, 9)))
+    elif cls == "seg_edge":
+        corners, sizes = _pair_with_overlap(rng, int(rng.integers(10, 80)), _pick(rng, VR_HEIGHTS) - g2)
+    elif cls == "thin":
+        ow, oh = (1, int(rng.integers(1, 60))) if rng.integers(0, 2) else (int(rng.integers(1, 80)), 1)
+        corners, sizes = _pair_with_overlap(rng, ow, oh)
+    elif cls == "no_unique_rows":                                       # one column range, tile 1 lower: the overlap's rows are collisions or nothing
+        w, h, x0, y0 = int(rng.integers(20, 80)), int(rng.integers(12, 50)), int(rng.integers(-40, 40)), int(rng.integers(-30, 30))
+        corners, sizes = [(x0, y0), (x0, y0 + int(rng.integers(1, h - 2)))], [(w, h), (w, h)]
+    else:
+        sizes = [(int(rng.integers(20, 90)), int(rng.integers(15, 70))) for _ in range(2)]
+        corners = [(int(rng.integers(-30, 30)), int(rng.integers(-20, 20))) for _ in range(2)]
+    while len(sizes) < n:
+        _tile_onto(rng, corners, sizes, (20, 90), (15, 70))
+    masks = []
+    for w, h in sizes:
+        m = rng.integers(1, 256, (h, w)).astype(np.uint8)             # any non-zero byte is "set"
+        m[rng.random((h, w)) < rng.uniform(0, 0.5)] = 0
+        masks.append(m)
+    if cls == "no_unique_rows":
+        x, ww = int(rng.integers(0, sizes[0][0] // 2)), int(rng.integers(1, sizes[0][0] // 2))
+        for m in masks[:2]:
+            m[m == 0] = 255
+            m[:, x:x + ww] = 0
+    if rng.integers(0, 8) == 0:
+        k = int(rng.integers(0, n))
+        for m in (masks[:2] if cls == "no_unique_rows" and k < 2 else masks[k:k + 1]):       # (one of that pair empty would leave the other's cells unique)
+            m[...] = 0
+    return dict(cls=cls, corners=corners, sizes=sizes, masks=masks, where=_pick(rng, WHERE), view_seed=int(rng.integers(0, 5)))
+
+
+def model_voronoi(c):
+    from helpers import voronoi_np
+    out = [m.copy() for m in c["masks"]]
+    voronoi_np.find(c["sizes"], c["corners"], out)
+    return out
+
+
+def case_voronoi(rng):
+    """isx_voronoi_seam_find against tests/helpers/voronoi_np.py: masks byte for byte, nothing written around a view."""
+    c = gen_voronoi(rng)
+    want = model_voronoi(c)
+    placed = _place(c["masks"], c["where"], c["view_seed"])
+    G.VoronoiSeamFinder().find(c["sizes"], c["corners"], [p[0] for p in placed])
+    for k, (p, w) in enumerate(zip(placed, want)):
+        got = _host(p[0])
+        assert np.array_equal(got, w), (c["cls"], k, int((got != w).sum()), np.argwhere(got != w)[:3])
+    _frame_untouched(placed)
+
+
+# ---- GraphCutSeamFinder(COST_COLOR) -------------------------------------------------------------------------------------------------------
+def gen_graphcut(rng):
+    """2..3 tiles, CV_8UC3 or CV_32FC3, smooth (the layout() of tests/test_gpu_graphcut_seam.py), noise or constant images - with constant
+    images every edge weighs the same, many cuts tie and only the maximal source side is right.  The first two tiles carry the class: a
+    padded grid (roi + 20) as wide as 1 or 2 of graphcut.hip's BFS tiles +-1 or as high as 2 or 3 of them, constant images, or masks
+    with 30 % of their cells zero.  No roi above about 130 x 100: the model's max-flow stays in milliseconds."""
+    cls = _pick(rng, GRAPHCUT_CLASSES)
+    n = int(rng.integers(2, 4))
+    g2 = 2 * SEAM_GAP
+    if cls == "tile_edge_w":
+        corners, sizes = _pair_with_overlap(rng, _pick(rng, GC_WIDTHS) - g2, int(rng.integers(8, 60)))
+    elif cls == "tile_edge_h":
+        corners, sizes = _pair_with_overlap(rng, int(rng.integers(8, 90)), _pick(rng, GC_HEIGHTS) - g2)
+    else:                                                               # the sizes and corners of the fixed-seed file's layout()
+        sizes = [(int(rng.integers(40, 90)), int(rng.integers(30, 70))) for _ in range(2)]
+        corners = [(int(rng.integers(-30, 30)), int(rng.integers(-20, 20))) for _ in range(2)]
+    while len(sizes) < n:
+        _tile_onto(rng, corners, sizes, (20, 90), (15, 70))
+    kind = "constant" if cls == "flat_tie" else _pick(rng, ["smooth", "noise", "constant"])
+    imgs, masks = [], []
+    for w, h in sizes:
+        if kind == "smooth":
+            base = rng.integers(0, 256, (h // 8 + 2, w // 8 + 2, 3))
+            img = np.kron(base, np.ones((8, 8, 1), np.int64))[:h, :w] + rng.integers(0, 12, (h, w, 3))
+        elif kind == "noise":
+            img = rng.integers(0, 256, (h, w, 3))
+        else:
+            img = np.broadcast_to(rng.integers(0, 256, 3), (h, w, 3))
+        imgs.append(np.clip(img, 0, 255).astype(np.uint8))
+        m = np.full((h, w), 255, np.uint8)
+        if cls == "holes_heavy":
+            m[rng.random((h, w)) < 0.3] = 0
+        else:
+            for _ in range(int(rng.integers(0, 4))):
+                y, x = int(rng.integers(0, h)), int(rng.integers(0, w))
+                m[y:y + int(rng.integers(2, 10)), x:x + int(rng.integers(2, 10))] = 0
+        masks.append(m)
+    if rng.integers(0, 2):
+        imgs = [a.astype(np.float32) for a in imgs]
+    return dict(cls=cls, kind=kind, corners=corners, sizes=sizes, imgs=imgs, masks=masks, where=_pick(rng, WHERE), view_seed=int(rng.integers(0, 5)))
+
+
+def model_graphcut(c):
+    """-> (masks after find(), the first overlapping pair (i, j, its graph on the untouched masks) or None); "skip" without scipy."""
+    try:
+        import scipy.sparse.csgraph  # noqa: F401
+    except ImportError:
+        return "skip"
+    from helpers import graphcut_np
+    out = [m.copy() for m in c["masks"]]
+    graphcut_np.find(c["imgs"], c["corners"], out)
+    n = len(out)
+    for i in range(n - 1):
+        for j in range(i + 1, n):
+            roi = overlap_roi(c["corners"][i], c["corners"][j], c["sizes"][i], c["sizes"][j])
+            if roi is not None:
+                g = graphcut_np.pair_graph(c["imgs"][i], c["imgs"][j], c["masks"][i], c["masks"][j], c["corners"][i], c["corners"][j], roi)
+                return out, (i, j, g)
+    return out, None
+
+
+def case_graphcut(rng):
+    """isx_graphcut_seam_find against tests/helpers/graphcut_np.py, masks byte for byte; isx_graphcut_seam_find_pair's certificate on the
+    first overlapping pair (the masks no earlier pair has touched): a maximum flow and the maximal minimum cut of the model's graph."""
+    from helpers import graphcut_np
+    c = gen_graphcut(rng)
+    want = model_graphcut(c)
+    if want == "skip":
+        return "skip"
+    want, first = want
+    imgs = [p[0] for p in _place(c["imgs"], c["where"], c["view_seed"])]
+    placed = _place(c["masks"], c["where"], c["view_seed"] + 1)
+    G.GraphCutSeamFinder().find(imgs, c["corners"], [p[0] for p in placed])
+    for k, (p, w) in enumerate(zip(placed, want)):
+        got = _host(p[0])
+        assert np.array_equal(got, w), (c["cls"], c["kind"], k, int((got != w).sum()), np.argwhere(got != w)[:3])
+    _frame_untouched(placed)
+    if first is not None:
+        i, j, g = first
+        r = G.GraphCutSeamFinder().find_pair(imgs[i], imgs[j], c["corners"][i], c["corners"][j], c["masks"][i].copy(), c["masks"][j].copy(), certificate=True)
+        assert (r["rows"], r["cols"]) == g["src"].shape, (r["rows"], r["cols"], g["src"].shape)
+        graphcut_np.check_certificate(g, r["flow"], r["residuals"], r["labels"])
+
+
+# ---- DpSeamFinder(COLOR_GRAD) and isx_seam_gradients ----------------------------------------------------------------------------------------
+def gen_seam_grad(rng):
+    """Two halves.  About a third of the cases: seam_gradients on a rectangle of a CV_8UC3 / CV_32FC3 image - any rectangle, one as wide /
+    high as 1 or 2 of seam.hip's gradient tiles +-1, one pixel, or one on the image's border (where the Sobel taps reflect).  The others
+    (cls "find"): DpSeamFinder(COLOR_GRAD).find on the 2..3 tiles of tests/seam_cases.py's make_find_case, as case_find draws them."""
+    half = "find" if rng.random() < 0.65 else "grad"
+    u8 = bool(rng.integers(0, 2))
+    if half == "find":
+        from seam_cases import make_find_case
+        images, corners, masks = make_find_case(int(rng.integers(0, 1 << 30)), int(rng.integers(2, 4)), u8, holes=bool(rng.integers(0, 2)),
+                                                size=(int(rng.integers(20, 110)), int(rng.integers(30, 150))))
+        return dict(cls="find", imgs=images, corners=corners, masks=masks, where=_pick(rng, WHERE), view_seed=int(rng.integers(0, 5)))
+    cls = _pick(rng, SEAM_GRAD_CLASSES[:4])
+    rw, rh = int(rng.integers(1, 140)), int(rng.integers(1, 100))
+    if cls == "tile_edge":
+        if rng.integers(0, 2):
+            rw = _pick(rng, GRAD_WIDTHS)
+        else:
+            rh = _pick(rng, GRAD_HEIGHTS)
+    elif cls == "one_pixel":
+        rw = rh = 1
+    left, right, top, bottom = (int(v) for v in rng.integers(0, 12, 4))
+    if cls == "rect_at_border":
+        side = int(rng.integers(0, 5))                                  # one side, or (4) all four: the whole image
+        left, right, top, bottom = (0 if side in (k, 4) else v for k, v in enumerate((left, right, top, bottom)))
+    w, h = left + rw + right, top + rh + bottom
+    if u8:
+        img = rng.integers(0, 256, (h, w, 3)).astype(np.uint8)
+    else:
+        img = (rng.random((h, w, 3), dtype=np.float32) * np.float32(255))
+    return dict(cls=cls, img=img, rect=(left, top, rw, rh), where=_pick(rng, WHERE), view_seed=int(rng.integers(0, 5)))
+
+
+def model_seam_grad(c):
+    from helpers import dpseam_grad_np as M
+    if c["cls"] == "find":
+        out = [m.copy() for m in c["masks"]]
+        M.DpSeamFinder(M.COLOR_GRAD).find(c["imgs"], c["corners"], out)
+        return out
+    gx, gy = M.gradients(c["img"])
+    x, y, w, h = c["rect"]
+    return np.abs(gx)[y:y + h, x:x + w], np.abs(gy)[y:y + h, x:x + w]
+
+
+def case_seam_grad(rng):
+    """isx_seam_gradients and isx_dp_seam_find_cost(COLOR_GRAD) against tests/helpers/dpseam_grad_np.py, bit for bit."""
+    c = gen_seam_grad(rng)
+    want = model_seam_grad(c)
+    if c["cls"] == "find":
+        imgs = [p[0] for p in _place(c["imgs"], c["where"], c["view_seed"])]
+        placed = _place(c["masks"], c["where"], c["view_seed"] + 1)
+        G.DpSeamFinder(G.DP_COLOR_GRAD).find(imgs, c["corners"], [p[0] for p in placed])
+        for k, (p, b) in enumerate(zip(placed, want)):
+            assert np.array_equal(_host(p[0]), b), (c["where"], k, np.argwhere(_host(p[0]) != b)[:3])
+        _frame_untouched(placed)
+        return None
+    img = _place([c["img"]], c["where"], c["view_seed"])[0][0]
+    gx, gy = G.seam_gradients(img, c["rect"])
+    for name, a, b in (("gradx", _host(gx), want[0]), ("grady", _host(gy), want[1])):
+        assert a.dtype == np.float32 and a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32)), \
+            (name, c["cls"], c["rect"], np.argwhere(a != b)[:3])
+
+
+NEW_FAMILIES = ["case_plane_warp", "case_gain_feed", "case_voronoi", "case_graphcut", "case_seam_grad"]
+
+
 CASES = [case_warp, case_blend, case_feather, case_prep, case_seam, case_blend_float_and_many, case_pipeline, case_find, case_warp_fused,
          case_linear_pair, case_strip, case_strip_feather, case_batch, case_s16_tiles, case_round4_calls, case_many_tiles, case_fused_feed, case_round6_calls,
-         case_long_lived]
+         case_long_lived, case_plane_warp, case_gain_feed, case_voronoi, case_graphcut, case_seam_grad]
 
 
-def run(budget, seed0, verbose=True, progress_path=None):
+def run(budget, seed0, verbose=True, progress_path=None, only=None):
     """Round-robin over the case families for `budget` seconds; case n uses seed seed0 * 1000003 + n.  Returns the summary dict.
+    only: a list of family names to run (a soak or a slice of what a change touched); None takes the comma-separated ISX_FUZZ_ONLY, or all.
     progress_path: the summary so far is written there every two minutes ("partial": true), so that a soak the GPU box's time limit cuts
     short still leaves its count behind (round 6 lost an hour-long one that way)."""
     G.load()
     t0, n, bad, skipped = time.time(), 0, 0, 0
-    only = os.environ.get("ISX_FUZZ_ONLY", "")       # a comma-separated subset of the families (a soak of what a round changed)
-    CASES = [f for f in globals()["CASES"] if not only or f.__name__ in only.split(",")]
+    if only is None:
+        only = [k for k in os.environ.get("ISX_FUZZ_ONLY", "").split(",") if k]
+    unknown = sorted(set(only) - {f.__name__ for f in globals()["CASES"]})
+    if unknown:
+        raise ValueError("no such fuzz family: " + ", ".join(unknown))
+    CASES = [f for f in globals()["CASES"] if not only or f.__name__ in only]
     counts = {f.__name__: 0 for f in CASES}
     fails = {f.__name__: 0 for f in CASES}
     failing_seeds = []
