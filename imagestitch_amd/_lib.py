@@ -241,3 +241,15 @@ def profile_entries():
         check(lib.isx_profile_entry(i, C.byref(name), C.byref(cnt), C.byref(ms), C.byref(by)))
         out[name.value.decode()] = {"launches": cnt.value, "ms": ms.value, "alg_bytes": by.value}
     return out
+
+
+def tile_args(src, corners, masks, stream, who="find", images=True):
+    """(n, images, corners, masks, stream) as the pairwise entries of the library take them: ctypes arrays of at least one element, the
+    images' one None with images=False.  IsxError(1) when the three sequences differ in length, before the library is called."""
+    n = len(src)
+    if len(corners) != n or len(masks) != n:
+        raise IsxError(1, who + ": src, corners and masks differ in length")
+    mats_i = (IsxMat * max(n, 1))(*[as_mat(a) for a in src]) if images else None
+    mats_m = (IsxMat * max(n, 1))(*[as_mat(m) for m in masks])
+    c = (C.c_int * max(2 * n, 1))(*[int(v) for p in corners for v in p])
+    return n, mats_i, c, mats_m, C.c_void_p(getattr(stream, "cuda_stream", stream) or 0)

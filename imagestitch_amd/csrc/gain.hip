@@ -21,9 +21,8 @@
 // for up to 2^31 pixels per item - then by wave, by block, and per item into a partial record; the host adds the records of a pair
 // in unsigned __int128 and rounds once.  Isum is therefore math.fsum of the terms, bit for bit, whatever the block shape or order.
 #include "isx_device.hpp"
-#include "isx_internal.hpp"
+#include "pairwise.hpp"
 
-#include <algorithm>
 #include <cmath>
 
 using namespace isx;
@@ -199,12 +198,6 @@ struct FeedScratch {
     void* pin = nullptr;
     size_t pin_cap = 0;
 };
-FeedScratch& feed_scratch() {
-    static thread_local FeedScratch* s = new FeedScratch();   // never destroyed at thread exit (the HIP runtime may be gone by then)
-    return *s;
-}
-
-struct StagedU8 { MatStage st; const unsigned char* p = nullptr; size_t step = 0; };
 
 // OpenCV's hal::LU (Gaussian elimination, partial pivoting by the largest |pivot|, row swaps carried into b) and its back substitution,
 // in double; A is n x n row-major, b becomes the solution.  false: a pivot below 100 DBL_EPSILON (cv::solve returns false there).
@@ -244,14 +237,7 @@ int isx_gain_compensator_feed(int num_images, const int* corners_xy, const isx_m
     ISX_CHECK_ARG(num_images >= 1, ISX_ERR_INVALID, "gain_feed: num_images = %d (at least one image)", num_images);
     ISX_CHECK_ARG(corners_xy && images && masks && gains, ISX_ERR_INVALID, "gain_feed: null argument");
     const int n = num_images;
-    for (int i = 0; i < n; ++i) {
-        ISX_TRY(check_mat(&images[i], "gain_feed: image"));
-        ISX_TRY(check_mat(&masks[i], "gain_feed: mask"));
-        ISX_CHECK_ARG(images[i].type == ISX_8UC3, ISX_ERR_TYPE, "gain_feed: image %d is %s (CV_8UC3 only)", i, type_name(images[i].type));
-        ISX_CHECK_ARG(masks[i].type == ISX_8UC1, ISX_ERR_TYPE, "gain_feed: mask %d is %s (CV_8U)", i, type_name(masks[i].type));
-        ISX_CHECK_ARG(masks[i].rows == images[i].rows && masks[i].cols == images[i].cols, ISX_ERR_SIZE,
-                      "gain_feed: mask %d is %dx%d, its image %dx%d", i, masks[i].cols, masks[i].rows, images[i].cols, images[i].rows);
-    }
+    ISX_TRY(check_tiles(n, images, masks, false, "gain_feed"));
     ISX_HIP(hipSetDevice(device));
     hipStream_t st = (hipStream_t)hip_stream;
 
@@ -261,27 +247,19 @@ int isx_gain_compensator_feed(int num_images, const int* corners_xy, const isx_m
     std::vector<GainItem> items;
     for (int i = 0; i < n; ++i)
         for (int j = i; j < n; ++j) {
-            const int xi = corners_xy[2 * i], yi = corners_xy[2 * i + 1], xj = corners_xy[2 * j], yj = corners_xy[2 * j + 1];
-            const long long x0 = std::max(xi, xj), y0 = std::max(yi, yj);
-            const long long x1 = std::min((long long)xi + images[i].cols, (long long)xj + images[j].cols);
-            const long long y1 = std::min((long long)yi + images[i].rows, (long long)yj + images[j].rows);
-            if (!(x0 < x1 && y0 < y1)) continue;
-            PairRoi pr{i, j, (int)x0, (int)y0, (int)(x1 - x0), (int)(y1 - y0), 0, 0};
-            pairs.push_back(pr);
+            int r[4];
+            if (!overlap_roi(corners_xy + 2 * i, images[i].cols, images[i].rows, corners_xy + 2 * j, images[j].cols, images[j].rows, r)) continue;
+            pairs.push_back(PairRoi{i, j, r[0], r[1], r[2], r[3], 0, 0});
         }
-    std::vector<StagedU8> simg(n), smsk(n);
-    for (int i = 0; i < n; ++i) {
-        ISX_TRY(smsk[i].st.use_in(&masks[i], st, "gain_feed: mask"));
-        smsk[i].p = (const unsigned char*)smsk[i].st.d.data; smsk[i].step = smsk[i].st.d.step;
-    }
+    MatStages stages;                        // of this call: slot i mask i, slot n + i image i
+    std::vector<isx_mat> simg(n), smsk(n);   // device views
+    for (int i = 0; i < n; ++i) ISX_TRY(stages.stage(i, &masks[i], false, st, "gain_feed", smsk[i]));
     // images are read by off-diagonal pairs only: a tile that overlaps no other is never staged
     std::vector<char> need_img(n, 0);
     for (const PairRoi& pr : pairs) if (pr.i != pr.j) need_img[pr.i] = need_img[pr.j] = 1;
     for (int i = 0; i < n; ++i)
-        if (need_img[i]) {
-            ISX_TRY(simg[i].st.use_in(&images[i], st, "gain_feed: image"));
-            simg[i].p = (const unsigned char*)simg[i].st.d.data; simg[i].step = simg[i].st.d.step;
-        }
+        if (need_img[i]) ISX_TRY(stages.stage(n + i, &images[i], false, st, "gain_feed", simg[i]));
+    const auto px = [](const isx_mat& m) { return (const unsigned char*)m.data; };
     double bytes = 0.0;
     for (PairRoi& pr : pairs) {
         const int i = pr.i, j = pr.j;
@@ -294,11 +272,11 @@ int isx_gain_compensator_feed(int num_images, const int* corners_xy, const isx_m
         for (int y = 0; y < pr.h; y += band) {
             GainItem it{};
             const int ri = oyi + y, rj = oyj + y;
-            it.m0 = smsk[i].p + (size_t)ri * smsk[i].step + oxi; it.sm0 = smsk[i].step;
+            it.m0 = px(smsk[i]) + (size_t)ri * smsk[i].step + oxi; it.sm0 = smsk[i].step;
             if (!diag) {
-                it.m1 = smsk[j].p + (size_t)rj * smsk[j].step + oxj; it.sm1 = smsk[j].step;
-                it.p0 = simg[i].p + (size_t)ri * simg[i].step + 3 * (size_t)oxi; it.sp0 = simg[i].step;
-                it.p1 = simg[j].p + (size_t)rj * simg[j].step + 3 * (size_t)oxj; it.sp1 = simg[j].step;
+                it.m1 = px(smsk[j]) + (size_t)rj * smsk[j].step + oxj; it.sm1 = smsk[j].step;
+                it.p0 = px(simg[i]) + (size_t)ri * simg[i].step + 3 * (size_t)oxi; it.sp0 = simg[i].step;
+                it.p1 = px(simg[j]) + (size_t)rj * simg[j].step + 3 * (size_t)oxj; it.sp1 = simg[j].step;
             }
             it.rows = std::min(band, pr.h - y); it.cols = pr.w; it.diag = diag ? 1 : 0;
             items.push_back(it);
@@ -308,7 +286,7 @@ int isx_gain_compensator_feed(int num_images, const int* corners_xy, const isx_m
     }
     const size_t ni = items.size();          // >= n: every image overlaps itself
     const size_t tab_bytes = (ni * sizeof(GainItem) + 255) & ~(size_t)255, part_bytes = ni * sizeof(GainPartial);
-    FeedScratch& fs = feed_scratch();
+    FeedScratch& fs = per_thread<FeedScratch>();
     if (fs.device != device) { fs.dev.release(); fs.device = device; }
     ISX_TRY(fs.dev.reserve(tab_bytes + part_bytes));
     if (fs.pin_cap < tab_bytes + part_bytes) {

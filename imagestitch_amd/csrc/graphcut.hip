@@ -24,17 +24,14 @@
 // that cannot reach the sink.  Every device loop has a fixed trip count; the host loops are capped (GC_MAX_ROUNDS rounds, GC_MAX_BFS_BATCHES
 // batches per global relabel) and the call fails past them with the pair's masks untouched.
 #include "isx_device.hpp"
-#include "isx_internal.hpp"
-
-#include <algorithm>
-#include <memory>
+#include "pairwise.hpp"
 
 using namespace isx;
 using namespace isxd;
 
 namespace {
 
-constexpr int GC_GAP = 10;
+constexpr int GC_GAP = isx::PAIR_GAP;
 constexpr int GC_TERM = 10000;
 constexpr int GC_PENALTY = 1000;
 constexpr int GC_INF = 1 << 30;
@@ -318,12 +315,8 @@ struct GcScratch {
     DevBuf graph, cert;
     int device = -1;
     int* pin = nullptr;
-    std::vector<std::unique_ptr<MatStage>> img, msk;
+    MatStages stages;                    // slot 2 i: image i, slot 2 i + 1: mask i
 };
-GcScratch& gc_scratch() {
-    static thread_local GcScratch* s = new GcScratch();   // never destroyed at thread exit (the HIP runtime may be gone by then)
-    return *s;
-}
 
 enum { GC_C_CHANGED = 0, GC_C_COUNT = GC_BFS_BATCH, GC_C_FLAG, GC_C_FLOW, GC_C_WORDS = GC_C_FLOW + 2 };
 
@@ -399,24 +392,12 @@ int gc_solve_pair(GcScratch& s, const GcGeom& G, bool u8, hipStream_t st, PairOu
     return ISX_OK;
 }
 
-struct GcCall {
-    std::vector<isx_mat> img, msk;       // device views
-    std::vector<MatStage*> out;          // host masks to copy back
-};
+struct GcCall { std::vector<isx_mat> img, msk; };   // device views
 
 int gc_check_args(int n, const isx_mat* images, const isx_mat* masks, int cost_type, const char* who) {
     ISX_CHECK_ARG(cost_type == ISX_GC_COST_COLOR || cost_type == ISX_GC_COST_COLOR_GRAD, ISX_ERR_INVALID, "%s: cost_type %d", who, cost_type);
     ISX_CHECK_ARG(cost_type == ISX_GC_COST_COLOR, ISX_ERR_UNSUPPORTED, "%s: COST_COLOR_GRAD is not implemented (its capacities are not integers)", who);
-    for (int i = 0; i < n; ++i) {
-        ISX_TRY(check_mat(&images[i], who));
-        ISX_TRY(check_mat(&masks[i], who));
-        ISX_CHECK_ARG(images[i].type == images[0].type && (images[i].type == ISX_32FC3 || images[i].type == ISX_8UC3), ISX_ERR_TYPE,
-                      "%s: all images must be CV_32FC3 or all CV_8UC3 (image %d is %s)", who, i, type_name(images[i].type));
-        ISX_CHECK_ARG(masks[i].type == ISX_8UC1, ISX_ERR_TYPE, "%s: mask %d is %s (CV_8U)", who, i, type_name(masks[i].type));
-        ISX_CHECK_ARG(masks[i].rows == images[i].rows && masks[i].cols == images[i].cols, ISX_ERR_SIZE,
-                      "%s: mask %d is %dx%d, its image %dx%d", who, i, masks[i].cols, masks[i].rows, images[i].cols, images[i].rows);
-    }
-    return ISX_OK;
+    return check_tiles(n, images, masks, true, who);
 }
 
 // capture check, device views of every image and mask, and the CV_32FC3 value check - all before the first pair writes
@@ -424,28 +405,18 @@ int gc_prepare(GcScratch& s, int n, const isx_mat* images, isx_mat* masks, int d
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     ISX_HIP(hipStreamIsCapturing(st, &cs));
     ISX_CHECK_ARG(cs == hipStreamCaptureStatusNone, ISX_ERR_STATE, "%s: the stream is capturing (the finder reads counters back to the host)", who);
-    if (s.device != device) { s.graph.release(); s.cert.release(); s.img.clear(); s.msk.clear(); s.device = device; }
-    if ((int)s.img.size() < n) { s.img.resize(n); s.msk.resize(n); }
+    if (s.device != device) { s.graph.release(); s.cert.release(); s.device = device; }
+    s.stages.use_device(device);
     if (!s.pin) {
         void* p = nullptr;
         ISX_HIP(hipHostMalloc(&p, 64 * sizeof(int), hipHostMallocDefault));
         s.pin = (int*)p;
     }
-    c.img.assign(images, images + n);
-    c.msk.assign(masks, masks + n);
+    c.img.resize(n);
+    c.msk.resize(n);
     for (int i = 0; i < n; ++i) {
-        if (images[i].device < 0) {
-            if (!s.img[i]) s.img[i].reset(new MatStage());
-            ISX_TRY(s.img[i]->use_in(&images[i], st, who));
-            c.img[i] = s.img[i]->d;
-        }
-        if (masks[i].device < 0) {
-            if (!s.msk[i]) s.msk[i].reset(new MatStage());
-            ISX_TRY(s.msk[i]->use_in(&masks[i], st, who));
-            s.msk[i]->host = &masks[i];           // copied back by finish_out
-            c.msk[i] = s.msk[i]->d;
-            c.out.push_back(s.msk[i].get());
-        }
+        ISX_TRY(s.stages.stage(2 * i, &images[i], false, st, who, c.img[i]));
+        ISX_TRY(s.stages.stage(2 * i + 1, &masks[i], true, st, who, c.msk[i]));
     }
     if (images[0].type == ISX_32FC3) {
         ISX_TRY(s.graph.reserve(256));
@@ -462,25 +433,16 @@ int gc_prepare(GcScratch& s, int n, const isx_mat* images, isx_mat* masks, int d
 }
 
 bool gc_geom(const isx_mat& i1, const isx_mat& i2, isx_mat& m1, isx_mat& m2, const int tl1[2], const int tl2[2], GcGeom& G) {
-    const long long x0 = std::max(tl1[0], tl2[0]), y0 = std::max(tl1[1], tl2[1]);
-    const long long x1 = std::min((long long)tl1[0] + i1.cols, (long long)tl2[0] + i2.cols);
-    const long long y1 = std::min((long long)tl1[1] + i1.rows, (long long)tl2[1] + i2.rows);
-    if (!(x0 < x1 && y0 < y1)) return false;
+    PairGrid p;
+    if (!pair_grid(tl1, i1.cols, i1.rows, tl2, i2.cols, i2.rows, p)) return false;
     G.i1 = (const unsigned char*)i1.data; G.s1 = i1.step;
     G.i2 = (const unsigned char*)i2.data; G.s2 = i2.step;
     G.m1 = (unsigned char*)m1.data; G.sm1 = m1.step;
     G.m2 = (unsigned char*)m2.data; G.sm2 = m2.step;
     G.r1 = i1.rows; G.c1 = i1.cols; G.r2 = i2.rows; G.c2 = i2.cols;
-    G.rw = (int)(x1 - x0); G.rh = (int)(y1 - y0);
-    G.hp = G.rh + 2 * GC_GAP; G.wp = G.rw + 2 * GC_GAP;
-    G.oy1 = (int)(y0 - tl1[1]) - GC_GAP; G.ox1 = (int)(x0 - tl1[0]) - GC_GAP;
-    G.oy2 = (int)(y0 - tl2[1]) - GC_GAP; G.ox2 = (int)(x0 - tl2[0]) - GC_GAP;
+    G.rw = p.rw; G.rh = p.rh; G.hp = p.hp; G.wp = p.wp;
+    G.oy1 = p.oy1; G.ox1 = p.ox1; G.oy2 = p.oy2; G.ox2 = p.ox2;
     return true;
-}
-
-int gc_finish(GcCall& c, hipStream_t st) {
-    for (MatStage* m : c.out) ISX_TRY(m->finish_out(st));
-    return ISX_OK;
 }
 
 }  // namespace
@@ -489,11 +451,10 @@ extern "C" {
 
 int isx_graphcut_seam_release(void) ISX_ENTRY {
     clear_error();
-    GcScratch& s = gc_scratch();
+    GcScratch& s = per_thread<GcScratch>();
     s.graph.release();
     s.cert.release();
-    s.img.clear();
-    s.msk.clear();
+    s.stages.clear();
     s.device = -1;
     if (s.pin) { ISX_HIP(hipHostFree(s.pin)); s.pin = nullptr; }
     return ISX_OK;
@@ -507,7 +468,7 @@ int isx_graphcut_seam_find(int num_images, const isx_mat* images, const int* cor
     if (num_images < 2) return ISX_OK;     // PairwiseSeamFinder::run visits no pair
     ISX_HIP(hipSetDevice(device));
     hipStream_t st = (hipStream_t)hip_stream;
-    GcScratch& s = gc_scratch();
+    GcScratch& s = per_thread<GcScratch>();
     GcCall c;
     ISX_TRY(gc_prepare(s, num_images, images, masks, device, st, c, "graphcut_seam_find"));
     const bool u8 = images[0].type == ISX_8UC3;
@@ -518,11 +479,11 @@ int isx_graphcut_seam_find(int num_images, const isx_mat* images, const int* cor
             PairOut po;
             const int rc = gc_solve_pair(s, G, u8, st, po, nullptr, nullptr);
             if (rc != ISX_OK) {
-                (void)gc_finish(c, st);     // the pairs before this one keep their edits, host masks as device ones
+                (void)s.stages.finish(st);     // the pairs before this one keep their edits, host masks as device ones
                 return rc;
             }
         }
-    return gc_finish(c, st);
+    return s.stages.finish(st);
 } ISX_EXIT("isx_graphcut_seam_find")
 
 int isx_graphcut_seam_find_pair(const isx_mat* image1, const isx_mat* image2, const int* corners_xy, isx_mat* mask1, isx_mat* mask2,
@@ -536,7 +497,7 @@ int isx_graphcut_seam_find_pair(const isx_mat* image1, const isx_mat* image2, co
     ISX_TRY(gc_check_args(2, im, mk, cost_type, "graphcut_seam_find_pair"));
     ISX_HIP(hipSetDevice(device));
     hipStream_t st = (hipStream_t)hip_stream;
-    GcScratch& s = gc_scratch();
+    GcScratch& s = per_thread<GcScratch>();
     GcCall c;
     ISX_TRY(gc_prepare(s, 2, im, mk, device, st, c, "graphcut_seam_find_pair"));   // host masks: copied back through mk, views of the same data
     GcGeom G{};
@@ -565,7 +526,7 @@ int isx_graphcut_seam_find_pair(const isx_mat* image1, const isx_mat* image2, co
     }
     if (flow) *flow = po.flow;
     if (info) { info[0] = po.hp; info[1] = po.wp; info[2] = po.rounds; info[3] = po.launches; }
-    return gc_finish(c, st);
+    return s.stages.finish(st);
 } ISX_EXIT("isx_graphcut_seam_find_pair")
 
 }  // extern "C"

@@ -9,7 +9,7 @@
 // height, a seam walking off the cost map) rows are skipped / columns clamped, exactly as the
 // oracle documents; all in-bounds arithmetic is literal (the ramp expressions are double).
 #include "isx_device.hpp"
-#include "isx_internal.hpp"
+#include "pairwise.hpp"
 
 #include <algorithm>
 
@@ -240,17 +240,13 @@ void geom_sizes(int rows1, int cols1, int rows2, int cols2, int tl1x, int tl1y, 
 
 namespace {
 struct LinScratch { DevBuf buf; int device = -1; };
-LinScratch& lin_scratch() {
-    static thread_local LinScratch* s = new LinScratch();   // never destroyed at thread exit (the HIP runtime may be gone by then)
-    return *s;
-}
 }  // namespace
 
 extern "C" {
 
 int isx_blend_pair_linear_release(void) ISX_ENTRY {
     clear_error();
-    LinScratch& ls = lin_scratch();
+    LinScratch& ls = per_thread<LinScratch>();
     ls.buf.release();      // (hipFree needs no current device: the caller's is left as it is)
     ls.device = -1;
     return ISX_OK;
@@ -297,7 +293,7 @@ int isx_blend_pair_linear(const isx_mat* images1, const isx_mat* images2, int tl
     const int cw = g.iBr + 2, mw = g.width + 2;
     // work buffers (cost map, seam, the two weight maps: 38 MB for a 4K pair) persist per host thread and device, grow-only: a
     // hipMalloc / hipFree pair per call cost 0.24 ms of a 0.55 ms call (isx_blend_pair_linear_release returns them)
-    LinScratch& ls = lin_scratch();
+    LinScratch& ls = per_thread<LinScratch>();
     if (ls.device != device) { ls.buf.release(); ls.device = device; }
     DevBuf& scratch = ls.buf;
     const int nchunks = std::max(cdiv(g.iHe - 1, SEAM_ROWS), 1);

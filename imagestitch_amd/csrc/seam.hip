@@ -9,7 +9,7 @@
 // the caller: it produces labels_, the component's bounding rectangle and the seam tips p1, p2 consumed here.
 // A labels_ read outside the union counts as "not this component" (the reference reads past the row, S:763).
 #include "isx_device.hpp"
-#include "isx_internal.hpp"
+#include "pairwise.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -320,16 +320,12 @@ struct SeamScratch {
         if (device != dev) { release(); device = dev; }
     }
 };
-SeamScratch& seam_scratch() {
-    static thread_local SeamScratch* s = new SeamScratch();   // never destroyed at thread exit (the HIP runtime may be gone by then)
-    return *s;
-}
 
 }  // namespace
 
 namespace isx {
 void seam_scratch_release() {
-    SeamScratch& ss = seam_scratch();
+    SeamScratch& ss = per_thread<SeamScratch>();
     ss.release();
     ss.device = -1;
 }
@@ -385,7 +381,7 @@ int isx_seam_estimate_cost(const isx_mat* image1, const isx_mat* image2, int tl1
     ISX_HIP(hipSetDevice(device));
     hipStream_t st = (hipStream_t)hip_stream;
     // staging and scratch persist per host thread (grow-only; isx_dp_seam_release frees them: a finder calls this once per conflict)
-    SeamScratch& ss = seam_scratch();
+    SeamScratch& ss = per_thread<SeamScratch>();
     ss.use_device(device);
     MatStage &s1 = ss.stages[0], &s2 = ss.stages[1], &sl = ss.stages[2];
     ISX_TRY(s1.use_in(image1, st, "seam_estimate: image1"));
@@ -507,7 +503,7 @@ int isx_seam_gradients(const isx_mat* image, const int rect[4], isx_mat* abs_gra
     ISX_CHECK_ARG(abs_gradx->step % 4 == 0 && abs_grady->step % 4 == 0, ISX_ERR_INVALID, "seam_gradients: the outputs' steps must be multiples of 4 bytes");
     ISX_HIP(hipSetDevice(device));
     hipStream_t st = (hipStream_t)hip_stream;
-    SeamScratch& ss = seam_scratch();
+    SeamScratch& ss = per_thread<SeamScratch>();
     ss.use_device(device);
     MatStage &si = ss.stages[0], &sx = ss.stages[1], &sy = ss.stages[2];
     ISX_TRY(si.use_in(image, st, "seam_gradients: image"));

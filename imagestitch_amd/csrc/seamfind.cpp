@@ -21,7 +21,7 @@
 #include <utility>
 #include <vector>
 
-#include "isx_internal.hpp"
+#include "pairwise.hpp"
 
 using namespace isx;
 
@@ -609,16 +609,6 @@ struct Finder {
     }
 };
 
-Finder& finder() {
-    static thread_local Finder* f = new Finder();
-    return *f;
-}
-struct FinderStages { std::vector<std::unique_ptr<MatStage>> img; int device = -1; };
-FinderStages& finder_stages() {
-    static thread_local FinderStages* s = new FinderStages();
-    return *s;
-}
-
 }  // namespace
 
 namespace isx { void seam_scratch_release(); }
@@ -627,10 +617,8 @@ extern "C" {
 
 int isx_dp_seam_release(void) ISX_ENTRY {
     clear_error();
-    Finder& f = finder();
-    f = Finder();                       // labels, union masks, contours, the seam mask: back to empty vectors
-    finder_stages().img.clear();        // the staged images
-    finder_stages().device = -1;
+    per_thread<Finder>() = Finder();              // labels, union masks, contours, the seam mask: back to empty vectors
+    per_thread<MatStages>().clear();              // the staged images
     isx::seam_scratch_release();        // gradient and cost maps, DP records and the staging of isx_seam_estimate
     return ISX_OK;
 } ISX_EXIT("isx_dp_seam_release")
@@ -640,14 +628,7 @@ int isx_dp_seam_find_cost(int num_images, const isx_mat* images, const int* corn
     ISX_CHECK_ARG(cost_func == ISX_DP_COLOR || cost_func == ISX_DP_COLOR_GRAD, ISX_ERR_INVALID, "dp_seam_find: cost_func %d is neither ISX_DP_COLOR nor ISX_DP_COLOR_GRAD (S:71)", cost_func);
     ISX_CHECK_ARG(num_images >= 0 && (num_images == 0 || (images && corners_xy && masks)), ISX_ERR_INVALID, "dp_seam_find: null argument");
     if (num_images == 0) return ISX_OK;   // S:95-96
-    for (int i = 0; i < num_images; ++i) {
-        ISX_TRY(check_mat(&images[i], "dp_seam_find: image"));
-        ISX_TRY(check_mat(&masks[i], "dp_seam_find: mask"));
-        ISX_CHECK_ARG(images[i].type == images[0].type && (images[i].type == ISX_32FC3 || images[i].type == ISX_8UC3), ISX_ERR_TYPE,
-                      "dp_seam_find: all images must have CV_32FC3 or CV_8UC3 type (S:745-746)");
-        ISX_CHECK_ARG(masks[i].type == ISX_8UC1, ISX_ERR_TYPE, "dp_seam_find: masks must be CV_8U");
-        ISX_CHECK_ARG(masks[i].rows == images[i].rows && masks[i].cols == images[i].cols, ISX_ERR_SIZE, "dp_seam_find: image %d and its mask differ in size (S:133-134)", i);
-    }
+    ISX_TRY(check_tiles(num_images, images, masks, true, "dp_seam_find"));   // S:745-746, S:133-134
     ISX_HIP(hipSetDevice(device));
     // the logic below edits the masks on the host: device masks are brought down and written back
     std::vector<std::vector<unsigned char>> hostm(num_images);
@@ -667,20 +648,17 @@ int isx_dp_seam_find_cost(int num_images, const isx_mat* images, const int* corn
     if (any_dev) ISX_HIP(hipStreamSynchronize((hipStream_t)hip_stream));
     // host images are staged in HBM once per call, not once per conflict (estimateSeam runs for every conflicting pair of
     // components and reads both images each time: ~100 MB per CV_32FC3 4K image and upload otherwise)
-    std::vector<isx_mat> dimg(images, images + num_images);
-    FinderStages& fs = finder_stages();
-    if (fs.device != device) { fs.img.clear(); fs.device = device; }
-    if ((int)fs.img.size() < num_images) fs.img.resize(num_images);
-    for (int i = 0; i < num_images; ++i)
-        if (images[i].device < 0) {
-            if (!fs.img[i]) fs.img[i].reset(new MatStage());
-            ISX_TRY(fs.img[i]->use_in(&images[i], (hipStream_t)hip_stream, "dp_seam_find: image"));
-            dimg[i] = fs.img[i]->d; dimg[i].device = device;
-        }
+    std::vector<isx_mat> dimg(num_images);
+    MatStages& stages = per_thread<MatStages>();
+    stages.use_device(device);
+    for (int i = 0; i < num_images; ++i) {
+        ISX_TRY(stages.stage(i, &images[i], false, (hipStream_t)hip_stream, "dp_seam_find", dimg[i]));
+        if (images[i].device < 0) dimg[i].device = device;
+    }
     images = dimg.data();
     // the union-sized work images (labels, the two masks: ~6 B per union pixel) keep their storage between calls of a thread:
     // a fresh 70 MB of vectors per 4K pair spent a third of the call in page faults (isx_dp_seam_release returns it)
-    Finder& f = finder();
+    Finder& f = per_thread<Finder>();
     f.device = device;
     f.stream = (hipStream_t)hip_stream;
     f.cost_func = cost_func;

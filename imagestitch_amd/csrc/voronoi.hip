@@ -20,17 +20,14 @@
 // A pair writes the masks it reads: k_vr_rows is the only kernel that reads them and k_vr_cols the only one that writes them, in that
 // order on one stream.  Every device loop has a trip count fixed by the kernel's arguments.
 #include "isx_device.hpp"
-#include "isx_internal.hpp"
-
-#include <algorithm>
-#include <memory>
+#include "pairwise.hpp"
 
 using namespace isx;
 using namespace isxd;
 
 namespace {
 
-constexpr int VR_GAP = 10;
+constexpr int VR_GAP = isx::PAIR_GAP;
 constexpr int VR_BIG = 1 << 28;          // "no unique cell in this row"
 constexpr int VR_PX = 16;                // cells per thread of the row pass
 constexpr int VR_NT = 256;
@@ -237,12 +234,8 @@ __global__ __launch_bounds__(64) void k_vr_cols(VrGeom G, const int* __restrict_
 struct VrScratch {
     DevBuf work;
     int device = -1;
-    std::vector<std::unique_ptr<MatStage>> msk;
+    MatStages msk;                       // host masks (a device of its own: isx_voronoi_seam_reserve moves `work` alone)
 };
-VrScratch& vr_scratch() {
-    static thread_local VrScratch* s = new VrScratch();   // never destroyed at thread exit (the HIP runtime may be gone by then)
-    return *s;
-}
 
 inline size_t vr_map_bytes(int rw, int rh) {
     const int hp = rh + 2 * VR_GAP, wp = rw + 2 * VR_GAP;
@@ -254,17 +247,13 @@ inline size_t vr_bytes(int rw, int rh) {
 }
 
 bool vr_geom(const isx_mat& m1, const isx_mat& m2, const int tl1[2], const int tl2[2], VrGeom& G) {
-    const long long x0 = std::max(tl1[0], tl2[0]), y0 = std::max(tl1[1], tl2[1]);
-    const long long x1 = std::min((long long)tl1[0] + m1.cols, (long long)tl2[0] + m2.cols);
-    const long long y1 = std::min((long long)tl1[1] + m1.rows, (long long)tl2[1] + m2.rows);
-    if (!(x0 < x1 && y0 < y1)) return false;
+    PairGrid p;
+    if (!pair_grid(tl1, m1.cols, m1.rows, tl2, m2.cols, m2.rows, p)) return false;
     G.m1 = (unsigned char*)m1.data; G.s1 = m1.step;
     G.m2 = (unsigned char*)m2.data; G.s2 = m2.step;
     G.r1 = m1.rows; G.c1 = m1.cols; G.r2 = m2.rows; G.c2 = m2.cols;
-    G.rw = (int)(x1 - x0); G.rh = (int)(y1 - y0);
-    G.hp = G.rh + 2 * VR_GAP; G.wp = G.rw + 2 * VR_GAP;
-    G.oy1 = (int)(y0 - tl1[1]) - VR_GAP; G.ox1 = (int)(x0 - tl1[0]) - VR_GAP;
-    G.oy2 = (int)(y0 - tl2[1]) - VR_GAP; G.ox2 = (int)(x0 - tl2[0]) - VR_GAP;
+    G.rw = p.rw; G.rh = p.rh; G.hp = p.hp; G.wp = p.wp;
+    G.oy1 = p.oy1; G.ox1 = p.ox1; G.oy2 = p.oy2; G.ox2 = p.ox2;
     G.pitch = (G.wp + 3) & ~3;
     G.nseg = cdiv(G.hp, VR_SEG);
     return true;
@@ -288,7 +277,7 @@ extern "C" {
 
 int isx_voronoi_seam_release(void) ISX_ENTRY {
     clear_error();
-    VrScratch& s = vr_scratch();
+    VrScratch& s = per_thread<VrScratch>();
     s.work.release();
     s.msk.clear();
     s.device = -1;
@@ -301,7 +290,7 @@ int isx_voronoi_seam_reserve(int max_roi_width, int max_roi_height, int device) 
     ISX_CHECK_ARG(max_roi_width + 2 * VR_GAP <= VR_MAX_SIDE && max_roi_height + 2 * VR_GAP <= VR_MAX_SIDE, ISX_ERR_UNSUPPORTED,
                   "voronoi_seam_reserve: a roi of %d x %d passes %d cells a side with its gap", max_roi_width, max_roi_height, VR_MAX_SIDE);
     ISX_HIP(hipSetDevice(device));
-    VrScratch& s = vr_scratch();
+    VrScratch& s = per_thread<VrScratch>();
     if (s.device != device) { s.work.release(); s.device = device; }
     return s.work.reserve(vr_bytes(max_roi_width, max_roi_height));
 } ISX_EXIT("isx_voronoi_seam_reserve")
@@ -310,16 +299,8 @@ int isx_voronoi_seam_find(int num_images, const int* sizes_wh, const int* corner
     clear_error();
     const char* who = "voronoi_seam_find";
     ISX_CHECK_ARG(num_images >= 0 && (num_images == 0 || (sizes_wh && corners_xy && masks)), ISX_ERR_INVALID, "%s: null argument", who);
-    bool any_host = false;
-    for (int i = 0; i < num_images; ++i) {
-        ISX_CHECK_ARG(sizes_wh[2 * i] >= 0 && sizes_wh[2 * i + 1] >= 0, ISX_ERR_INVALID, "%s: image %d has size %d x %d", who, i, sizes_wh[2 * i],
-                      sizes_wh[2 * i + 1]);
-        ISX_TRY(check_mat(&masks[i], who));
-        ISX_CHECK_ARG(masks[i].type == ISX_8UC1, ISX_ERR_TYPE, "%s: mask %d is %s (CV_8U)", who, i, type_name(masks[i].type));
-        ISX_CHECK_ARG(masks[i].cols == sizes_wh[2 * i] && masks[i].rows == sizes_wh[2 * i + 1], ISX_ERR_SIZE, "%s: mask %d is %dx%d, its image %dx%d",
-                      who, i, masks[i].cols, masks[i].rows, sizes_wh[2 * i], sizes_wh[2 * i + 1]);
-        any_host = any_host || masks[i].device < 0;
-    }
+    ISX_TRY(check_masks(num_images, sizes_wh, masks, who));
+    const bool any_host = std::any_of(masks, masks + num_images, [](const isx_mat& m) { return m.device < 0; });
     if (num_images < 2) return ISX_OK;     // PairwiseSeamFinder::run visits no pair
     // the scratch the largest pair needs (a pair's roi depends on sizes and corners only, not on what earlier pairs wrote)
     size_t need = 0;
@@ -336,29 +317,21 @@ int isx_voronoi_seam_find(int num_images, const int* sizes_wh, const int* corner
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     ISX_HIP(hipStreamIsCapturing(st, &cs));
     const bool capturing = cs != hipStreamCaptureStatusNone;
-    VrScratch& s = vr_scratch();
+    VrScratch& s = per_thread<VrScratch>();
     if (capturing) {
         ISX_CHECK_ARG(!any_host, ISX_ERR_STATE, "%s: the stream is capturing and a mask is a host mat (staging it synchronises)", who);
         ISX_CHECK_ARG(need == 0 || (s.device == device && s.work.cap >= need), ISX_ERR_STATE,
                       "%s: the stream is capturing and the scratch holds %zu of the %zu bytes this call needs (isx_voronoi_seam_reserve before the capture)",
                       who, s.device == device ? s.work.cap : (size_t)0, need);
     } else {
-        if (s.device != device) { s.work.release(); s.msk.clear(); s.device = device; }
+        if (s.device != device) { s.work.release(); s.device = device; }
         ISX_TRY(s.work.reserve(need));
     }
     if (need == 0) return ISX_OK;          // no two tiles overlap
     std::vector<isx_mat> mk(masks, masks + num_images);       // device views
-    std::vector<MatStage*> out;                                // host masks to copy back
-    if (any_host) {
-        if ((int)s.msk.size() < num_images) s.msk.resize(num_images);
-        for (int i = 0; i < num_images; ++i) {
-            if (masks[i].device >= 0) continue;
-            if (!s.msk[i]) s.msk[i].reset(new MatStage());
-            ISX_TRY(s.msk[i]->use_in(&masks[i], st, who));
-            s.msk[i]->host = &masks[i];                        // copied back by finish_out
-            mk[i] = s.msk[i]->d;
-            out.push_back(s.msk[i].get());
-        }
+    if (any_host) {                                            // (never under capture)
+        s.msk.use_device(device);
+        for (int i = 0; i < num_images; ++i) ISX_TRY(s.msk.stage(i, &masks[i], true, st, who, mk[i]));
     }
     for (int i = 0; i + 1 < num_images; ++i)
         for (int j = i + 1; j < num_images; ++j) {
@@ -366,8 +339,7 @@ int isx_voronoi_seam_find(int num_images, const int* sizes_wh, const int* corner
             if (!vr_geom(mk[i], mk[j], corners_xy + 2 * i, corners_xy + 2 * j, G)) continue;
             ISX_TRY(vr_pair(G, s.work.p, st));
         }
-    for (MatStage* m : out) ISX_TRY(m->finish_out(st));
-    return ISX_OK;
+    return any_host ? s.msk.finish(st) : ISX_OK;
 } ISX_EXIT("isx_voronoi_seam_find")
 
 }  // extern "C"

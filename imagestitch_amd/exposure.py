@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import as_mat, check
+from ._lib import check, tile_args
 from .blender import gain_apply
 
 
@@ -21,19 +21,13 @@ class GainCompensator:
 
     def feed(self, corners, images, masks):
         """corners: n (x, y); images: n CV_8UC3 (HxWx3 uint8) arrays or tensors; masks: n CV_8U masks of the images' sizes (255 = in)."""
-        n = len(images)
-        if len(corners) != n or len(masks) != n:
-            raise _lib.IsxError(1, "feed: corners, images and masks differ in length")
-        mats_i = (_lib.IsxMat * max(n, 1))(*[as_mat(a) for a in images])
-        mats_m = (_lib.IsxMat * max(n, 1))(*[as_mat(m) for m in masks])
-        c = (C.c_int * max(2 * n, 1))(*[int(v) for p in corners for v in p])
+        n, mats_i, c, mats_m, ptr = tile_args(images, corners, masks, self.stream, who="feed")
         gains = np.zeros(max(n, 1), np.float64)
         N = np.zeros((n, n), np.int64)
         I = np.zeros((n, n), np.float64)
-        ptr = getattr(self.stream, "cuda_stream", self.stream)
         check(_lib.load().isx_gain_compensator_feed(n, c, mats_i, mats_m, gains.ctypes.data_as(C.POINTER(C.c_double)),
                                                     N.ctypes.data_as(C.POINTER(C.c_longlong)), I.ctypes.data_as(C.POINTER(C.c_double)),
-                                                    int(self.device), C.c_void_p(ptr or 0)))
+                                                    int(self.device), ptr))
         self._gains, self.N, self.I = gains[:n], N, I
         return self
 

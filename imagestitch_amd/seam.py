@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import as_mat, check
+from ._lib import as_mat, check, tile_args
 
 
 DP_COLOR, DP_COLOR_GRAD = 0, 1           # DpSeamFinder::CostFunction (S:71)
@@ -64,12 +64,8 @@ class DpSeamFinder:
 
     def find(self, src, corners, masks):
         """find(src, corners, masks): src = CV_32FC3 (or CV_8UC3) images, masks = CV_8U arrays / tensors edited in place."""
-        n = len(src)
-        mats_i = (_lib.IsxMat * n)(*[as_mat(a) for a in src])
-        mats_m = (_lib.IsxMat * n)(*[as_mat(m) for m in masks])
-        c = (C.c_int * (2 * n))(*[int(v) for p in corners for v in p])
-        ptr = getattr(self.stream, "cuda_stream", self.stream)
-        check(_lib.load().isx_dp_seam_find_cost(n, mats_i, c, mats_m, self.cost_func, int(self.device), C.c_void_p(ptr or 0)))
+        n, mats_i, c, mats_m, ptr = tile_args(src, corners, masks, self.stream)
+        check(_lib.load().isx_dp_seam_find_cost(n, mats_i, c, mats_m, self.cost_func, int(self.device), ptr))
         return masks
 
     @staticmethod
@@ -91,14 +87,8 @@ class GraphCutSeamFinder:
     def find(self, src, corners, masks):
         """find(src, corners, masks): src = CV_32FC3 tiles holding integers in [0, 255] (W:261) or CV_8UC3 tiles, masks = CV_8U arrays /
         tensors edited in place."""
-        n = len(src)
-        if len(corners) != n or len(masks) != n:
-            raise _lib.IsxError(1, "find: src, corners and masks differ in length")
-        mats_i = (_lib.IsxMat * max(n, 1))(*[as_mat(a) for a in src])
-        mats_m = (_lib.IsxMat * max(n, 1))(*[as_mat(m) for m in masks])
-        c = (C.c_int * max(2 * n, 1))(*[int(v) for p in corners for v in p])
-        ptr = getattr(self.stream, "cuda_stream", self.stream)
-        check(_lib.load().isx_graphcut_seam_find(n, mats_i, c, mats_m, self.cost_type, int(self.device), C.c_void_p(ptr or 0)))
+        n, mats_i, c, mats_m, ptr = tile_args(src, corners, masks, self.stream)
+        check(_lib.load().isx_graphcut_seam_find(n, mats_i, c, mats_m, self.cost_type, int(self.device), ptr))
         return masks
 
     def find_pair(self, image1, image2, tl1, tl2, mask1, mask2, certificate=False):
@@ -141,15 +131,10 @@ class VoronoiSeamFinder:
     def find(self, src_or_sizes, corners, masks):
         """find(src, corners, masks) or find(sizes, corners, masks): the images are never read, only their sizes ((width, height) pairs,
         or anything with a .shape of rows x cols [x channels]); masks = CV_8U arrays / tensors edited in place."""
-        n = len(src_or_sizes)
-        if len(corners) != n or len(masks) != n:
-            raise _lib.IsxError(1, "find: src, corners and masks differ in length")
+        n, _, c, mats_m, ptr = tile_args(src_or_sizes, corners, masks, self.stream, images=False)
         sizes = [(int(a.shape[1]), int(a.shape[0])) if hasattr(a, "shape") else (int(a[0]), int(a[1])) for a in src_or_sizes]
-        mats_m = (_lib.IsxMat * max(n, 1))(*[as_mat(m) for m in masks])
         sz = (C.c_int * max(2 * n, 1))(*[v for s in sizes for v in s])
-        c = (C.c_int * max(2 * n, 1))(*[int(v) for p in corners for v in p])
-        ptr = getattr(self.stream, "cuda_stream", self.stream)
-        check(_lib.load().isx_voronoi_seam_find(n, sz, c, mats_m, int(self.device), C.c_void_p(ptr or 0)))
+        check(_lib.load().isx_voronoi_seam_find(n, sz, c, mats_m, int(self.device), ptr))
         return masks
 
     def reserve(self, max_roi_width, max_roi_height):

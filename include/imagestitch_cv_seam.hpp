@@ -24,27 +24,36 @@
 
 namespace isx_cv {
 
+namespace detail {
+// The arguments of a find as the isx finders take them.  The mapped Mat headers live as long as this object - to the end of the find that
+// builds it (the unmap of an OpenCL-backed UMat happens in their destructors).  Images are mapped only where they are read.
+struct SeamArgs {
+    std::vector<cv::Mat> im, mk;
+    std::vector<isx::Mat> ii, mm;
+    std::vector<isx::Point> pts;
+    SeamArgs(const std::vector<cv::UMat>& src, const std::vector<cv::Point>& corners, std::vector<cv::UMat>& masks, bool map_images = true) {
+        CV_Assert(src.size() == corners.size() && masks.size() == corners.size());
+        for (size_t i = 0; i < src.size(); ++i) {
+            if (map_images) im.push_back(src[i].getMat(cv::ACCESS_READ));
+            mk.push_back(masks[i].getMat(cv::ACCESS_RW));
+        }
+        for (size_t i = 0; i < src.size(); ++i) {
+            if (map_images) ii.push_back(isx::Mat(im[i]));
+            mm.push_back(isx::Mat(mk[i]));
+            pts.push_back(isx::Point(corners[i].x, corners[i].y));
+        }
+    }
+};
+}  // namespace detail
+
 // cv::detail::GraphCutSeamFinder(cost_type)'s find over isx::GraphCutSeamFinder.  COST_COLOR only: COST_COLOR_GRAD throws
 // isx::Exception(ISX_ERR_UNSUPPORTED) from find, as does a CV_32FC3 value that is not an integer in [0, 255].
 class HipGraphCutSeamFinder : public cv::detail::SeamFinder {
 public:
     explicit HipGraphCutSeamFinder(int cost_type = cv::detail::GraphCutSeamFinderBase::COST_COLOR, int device = 0) : f_(cost_type, device) {}
     void find(const std::vector<cv::UMat>& src, const std::vector<cv::Point>& corners, std::vector<cv::UMat>& masks) override {
-        CV_Assert(src.size() == corners.size() && masks.size() == corners.size());
-        // the mapped Mat headers live to the end of this call (the unmap of an OpenCL-backed UMat happens in their destructors)
-        std::vector<cv::Mat> im, mk;
-        std::vector<isx::Mat> ii, mm;
-        std::vector<isx::Point> pts;
-        for (size_t i = 0; i < src.size(); ++i) {
-            im.push_back(src[i].getMat(cv::ACCESS_READ));
-            mk.push_back(masks[i].getMat(cv::ACCESS_RW));
-        }
-        for (size_t i = 0; i < src.size(); ++i) {
-            ii.push_back(isx::Mat(im[i]));
-            mm.push_back(isx::Mat(mk[i]));
-            pts.push_back(isx::Point(corners[i].x, corners[i].y));
-        }
-        f_.find(ii, pts, mm);
+        detail::SeamArgs a(src, corners, masks);
+        f_.find(a.ii, a.pts, a.mm);
     }
 
 private:
@@ -57,18 +66,10 @@ class HipVoronoiSeamFinder : public cv::detail::SeamFinder {
 public:
     explicit HipVoronoiSeamFinder(int device = 0) : f_(device) {}
     void find(const std::vector<cv::UMat>& src, const std::vector<cv::Point>& corners, std::vector<cv::UMat>& masks) override {
-        CV_Assert(src.size() == corners.size() && masks.size() == corners.size());
-        std::vector<cv::Mat> mk;                 // mapped to the end of this call, as above
-        std::vector<isx::Mat> mm;
+        detail::SeamArgs a(src, corners, masks, false);
         std::vector<isx::Size> sizes;
-        std::vector<isx::Point> pts;
-        for (size_t i = 0; i < src.size(); ++i) mk.push_back(masks[i].getMat(cv::ACCESS_RW));
-        for (size_t i = 0; i < src.size(); ++i) {
-            mm.push_back(isx::Mat(mk[i]));
-            sizes.push_back(isx::Size(src[i].cols, src[i].rows));
-            pts.push_back(isx::Point(corners[i].x, corners[i].y));
-        }
-        f_.find(sizes, pts, mm);
+        for (size_t i = 0; i < src.size(); ++i) sizes.push_back(isx::Size(src[i].cols, src[i].rows));
+        f_.find(sizes, a.pts, a.mm);
     }
 
 private:
@@ -85,20 +86,8 @@ public:
         : f_(costFunc == COLOR_GRAD ? isx::DpSeamFinder::COLOR_GRAD : isx::DpSeamFinder::COLOR, device) {}
     CostFunction costFunction() const { return f_.costFunction() == isx::DpSeamFinder::COLOR_GRAD ? COLOR_GRAD : COLOR; }
     void find(const std::vector<cv::UMat>& src, const std::vector<cv::Point>& corners, std::vector<cv::UMat>& masks) override {
-        CV_Assert(src.size() == corners.size() && masks.size() == corners.size());
-        std::vector<cv::Mat> im, mk;             // mapped to the end of this call, as above
-        std::vector<isx::Mat> ii, mm;
-        std::vector<isx::Point> pts;
-        for (size_t i = 0; i < src.size(); ++i) {
-            im.push_back(src[i].getMat(cv::ACCESS_READ));
-            mk.push_back(masks[i].getMat(cv::ACCESS_RW));
-        }
-        for (size_t i = 0; i < src.size(); ++i) {
-            ii.push_back(isx::Mat(im[i]));
-            mm.push_back(isx::Mat(mk[i]));
-            pts.push_back(isx::Point(corners[i].x, corners[i].y));
-        }
-        f_.find(ii, pts, mm);
+        detail::SeamArgs a(src, corners, masks);
+        f_.find(a.ii, a.pts, a.mm);
     }
 
 private:

@@ -212,3 +212,16 @@ def test_cpp_gain_demo(gpu, tmp_path):
         np.testing.assert_allclose(got[leg], g, rtol=1e-12, atol=0)
     assert np.array_equal(got["mirror"], got["adapter"])
     assert "apply OK" in out and "throws 7" in out
+
+
+def test_mixed_residency(gpu):
+    """Tiles 0 and 2 on the host, tile 1 on the device, every pair overlapping (tile 2 meets tile 0 in one pixel, tile 1 tile 0 in one
+    column): N, I and the gains of the model, and feed leaves images and masks as they were."""
+    corners, imgs, masks = _many_tiles(3, 103)
+    model = feed_model(corners, imgs, masks)
+    assert model[0][0, 1] > 1 and model[0][0, 2] == 1
+    src = [_dev(a) if k == 1 else a.copy() for k, a in enumerate(imgs)]
+    mk = [_dev(m) if k == 1 else m.copy() for k, m in enumerate(masks)]
+    _check(gpu, corners, src, mk, model)
+    for k in range(3):
+        assert np.array_equal(_np(src[k]), imgs[k]) and np.array_equal(_np(mk[k]), masks[k]), k

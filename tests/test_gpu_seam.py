@@ -133,3 +133,21 @@ def test_dp_seam_find_trivial_cases_and_errors(gpu):
     with pytest.raises(gpu.IsxError) as e:
         gpu.DpSeamFinder().find(images, corners, [masks[0].copy(), masks[1][:-1].copy()])
     assert e.value.code == 7                                                         # CV_Assert(image.size() == mask.size()), S:133-134
+
+
+def test_dp_seam_find_mixed_residency(gpu):
+    """Tiles 0 and 2 on the host, tile 1 on the device: the host masks are edited where they are, the device mask comes back edited."""
+    import torch
+    from oracle.dpseam_np import DpSeamFinder as OracleFinder
+    from seam_cases import make_find_case
+    images, corners, masks = make_find_case(3000, 3, True, holes=False)
+    ref = [m.copy() for m in masks]
+    OracleFinder().find(images, corners, ref)
+    assert all((a != m).any() for a, m in zip(ref, masks))            # every tile's mask is cut
+    src = [torch.from_numpy(a).cuda() if k == 1 else a.copy() for k, a in enumerate(images)]
+    got = [torch.from_numpy(m.copy()).cuda() if k == 1 else m.copy() for k, m in enumerate(masks)]
+    assert gpu.DpSeamFinder().find(src, corners, got) is got
+    assert isinstance(got[0], np.ndarray) and got[1].is_cuda and isinstance(got[2], np.ndarray)
+    for k, (a, b) in enumerate(zip(got, ref)):
+        a = a.cpu().numpy() if k == 1 else a
+        assert np.array_equal(a, b), (k, np.argwhere(a != b)[:4])

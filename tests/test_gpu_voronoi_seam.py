@@ -519,3 +519,31 @@ def test_end_to_end_feather_against_the_oracle(gpu, oracle):
     odst, omask = ob.blend()
     assert np.array_equal(_np(dmask), omask)
     assert np.array_equal(_np(dst), odst)
+
+
+def test_mixed_residency(gpu):
+    """Masks 0 and 2 on the host, mask 1 on the device: the host masks are copied back, the device mask is edited in place."""
+    corners, masks = layout(3, 2)
+    want = model(corners, masks)
+    assert all((w != m).any() for w, m in zip(want, masks))           # every tile's mask is cut: each copy-back shows
+    mk = [_dev(m) if k == 1 else m.copy() for k, m in enumerate(masks)]
+    assert gpu.VoronoiSeamFinder().find(_sizes(masks), corners, mk) is mk
+    assert isinstance(mk[0], np.ndarray) and mk[1].is_cuda and isinstance(mk[2], np.ndarray)
+    for k in range(3):
+        assert np.array_equal(_np(mk[k]), want[k]), (k, int((_np(mk[k]) != want[k]).sum()))
+
+
+def test_growing_and_shrinking_sets_on_one_thread(gpu):
+    """2, 5, then 2 host masks through one finder on one thread (the staged copies of a tile index change size and count), then release()
+    and one more call: every call equals the model."""
+    f = gpu.VoronoiSeamFinder()
+    for n, seed in [(2, 1), (5, 4), (2, 1), (0, 0), (3, 2)]:
+        if n == 0:
+            f.release()
+            continue
+        corners, masks = layout(n, seed)
+        want = model(corners, masks)
+        got = [m.copy() for m in masks]
+        f.find(_sizes(masks), corners, got)
+        for k in range(n):
+            assert np.array_equal(got[k], want[k]), (n, k, int((got[k] != want[k]).sum()))
