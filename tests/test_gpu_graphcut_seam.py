@@ -12,6 +12,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from helpers import graphcut_np as G  # noqa: E402
+from helpers import guarded  # noqa: E402
 from imagestitch_amd import synth  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -53,19 +54,9 @@ def model(corners, imgs, masks):
 
 
 def views(arrays, where, seed):
-    """Each array copied into a larger buffer at an odd offset (unaligned first byte for U8, a pitch that is no multiple of 16)."""
-    out = []
-    for k, a in enumerate(arrays):
-        a = np.asarray(a)
-        h, w = a.shape[:2]
-        oy, ox, pad = 1 + k % 3, 1 + (k + seed) % 5, 3 + 2 * k
-        b = np.full((h + oy + 2, w + ox + pad) + a.shape[2:], 7, a.dtype)
-        if where == "device":
-            b = _dev(b)
-        v = b[oy:oy + h, ox:ox + w]
-        v[...] = _dev(a) if where == "device" else a
-        out.append(v)
-    return out
+    """Each array inside a guard band of seeded random bytes (tests/helpers/guarded.py, the "odd" layout: an unaligned first byte for U8,
+    a pitch that is no multiple of 16)."""
+    return [guarded.guarded_like(a, where, "odd", 100 * seed + k) for k, a in enumerate(arrays)]
 
 
 @pytest.mark.parametrize("n,seed", [(2, 1), (3, 2), (4, 3)])
@@ -81,10 +72,16 @@ def test_model_parity(gpu, n, seed, depth, where):
         mk_v = [_dev(m) for m in masks] if where == "device" else [m.copy() for m in masks]
     else:
         kind = where.split("_")[0]
-        src_v, mk_v = views(src, kind, seed), views(masks, kind, seed + 1)
+        g_src, g_mk = views(src, kind, seed), views(masks, kind, seed + 1)
+        src_v, mk_v = [g.view for g in g_src], [g.view for g in g_mk]
     gpu.GraphCutSeamFinder().find(src_v, corners, mk_v)
     for k in range(n):
         assert np.array_equal(_np(mk_v[k]), want[k]), (k, int((_np(mk_v[k]) != want[k]).sum()))
+    if where not in ("host", "device"):
+        for g in g_mk:
+            g.check()                                                # nothing around a mask was written
+        for g in g_src:
+            g.check(guarded.NOTHING)                                 # ... and the images are inputs
 
 
 @pytest.mark.parametrize("n,seed", [(2, 1), (3, 2), (4, 3), (2, 9)])

@@ -11,6 +11,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from helpers import dpseam_grad_np as M  # noqa: E402
+from helpers import guarded  # noqa: E402
 from seam_cases import make_case, make_find_case  # noqa: E402
 from test_dpseam_grad_model import FIND_CASES, REF_NONZERO_COLOR_GRAD  # noqa: E402
 
@@ -71,15 +72,15 @@ def test_gradients_unaligned_device_views_and_odd_steps(gpu, u8):
         view.copy_(torch.from_numpy(img))
         check_gradients(gpu, img, None, given=view)
         check_gradients(gpu, img, (w - 40, 3, 40, 30), given=view)
-    # outputs: pitched device views and pitched host arrays
-    ox_, oy_ = torch.zeros((h, w + 5), dtype=torch.float32, device="cuda"), torch.zeros((h, w + 3), dtype=torch.float32, device="cuda")
-    gpu.seam_gradients(img, None, out=(ox_[:, 2:2 + w], oy_[:, 3:3 + w]))
+    # outputs: pitched device views and pitched host arrays inside guard bands of seeded random bytes (a stray store of any value shows)
     rx, ry = model_abs(img)
-    assert same_bits(ox_[:, 2:2 + w].cpu().numpy(), rx) and same_bits(oy_[:, 3:3 + w].cpu().numpy(), ry)
-    assert not ox_[:, :2].any() and not ox_[:, 2 + w:].any()
-    hx, hy = np.zeros((h, w + 4), np.float32), np.zeros((h, w + 1), np.float32)
-    gpu.seam_gradients(torch.from_numpy(img).cuda(), None, out=(hx[:, 1:1 + w], hy[:, :w]))
-    assert same_bits(hx[:, 1:1 + w], rx) and same_bits(hy[:, :w], ry) and not hx[:, 0].any() and not hy[:, w].any()
+    for where, given in (("device", img), ("host", torch.from_numpy(img).cuda())):
+        for layout in guarded.LAYOUTS:
+            ox_, oy_ = guarded.guarded((h, w), np.float32, where, layout, 31), guarded.guarded((h, w), np.float32, where, layout, 32)
+            gpu.seam_gradients(given, None, out=(ox_.view, oy_.view))
+            torch.cuda.synchronize()
+            assert same_bits(ox_.get(), rx) and same_bits(oy_.get(), ry)
+            ox_.check(), oy_.check()
 
 
 def test_gradients_one_pixel_images(gpu):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from helpers import guarded  # noqa: E402
 from helpers import voronoi_np as V  # noqa: E402
 from imagestitch_amd import synth  # noqa: E402
 from test_voronoi_model import REF_NONZERO_AFTER, REF_ROI, REF_SEAM_CELLS  # noqa: E402
@@ -56,18 +57,9 @@ def model(corners, masks):
 
 
 def views(arrays, where, seed):
-    """Each array copied into a larger buffer at an odd offset (unaligned first byte, a pitch that is no multiple of 16)."""
-    out = []
-    for k, a in enumerate(arrays):
-        h, w = a.shape
-        oy, ox, pad = 1 + k % 3, 1 + (k + seed) % 5, 3 + 2 * k
-        b = np.full((h + oy + 2, w + ox + pad), 7, a.dtype)
-        if where == "device":
-            b = _dev(b)
-        v = b[oy:oy + h, ox:ox + w]
-        v[...] = _dev(a) if where == "device" else a
-        out.append((v, b, (oy, ox, h, w)))
-    return out
+    """Each array inside a guard band of seeded random bytes (tests/helpers/guarded.py, the "odd" layout: an unaligned first byte, a
+    pitch that is no multiple of 16)."""
+    return [guarded.guarded_like(a, where, "odd", 100 * seed + k) for k, a in enumerate(arrays)]
 
 
 def check(gpu, corners, masks, where="device"):
@@ -89,12 +81,10 @@ def test_model_parity(gpu, n, seed, where):
         check(gpu, corners, masks, where)
         return
     vs = views(masks, where.split("_")[0], seed)
-    gpu.VoronoiSeamFinder().find(_sizes(masks), corners, [v for v, _, _ in vs])
-    for k, (v, b, (oy, ox, h, w)) in enumerate(vs):
-        assert np.array_equal(_np(v), want[k]), (k, int((_np(v) != want[k]).sum()))
-        frame = _np(b).copy()
-        frame[oy:oy + h, ox:ox + w] = 7
-        assert (frame == 7).all(), k                                  # nothing around the view was written
+    gpu.VoronoiSeamFinder().find(_sizes(masks), corners, [g.view for g in vs])
+    for k, g in enumerate(vs):
+        assert np.array_equal(_np(g.view), want[k]), (k, int((_np(g.view) != want[k]).sum()))
+        g.check()                                                     # nothing around the view was written
 
 
 def test_src_form_takes_sizes_from_the_images(gpu):
