@@ -8,7 +8,8 @@ Registration (features, matching, bundle adjustment — out of scope of this lib
 with focal length F rotated by -/+ yaw about the vertical axis.  Without input files a synthetic pair is generated.
 
 Steps = the reference's main(): warp image + mask (W:223-233), gain apply with given gains (W:241-244) - or, with
---estimate-gains, the GainCompensator's feed on the warped tiles (W:238-240) and its apply (W:241-244) -, convertTo(CV_32F) +
+--estimate-gains, the compensator's feed on the warped tiles (W:238-240) and its apply (W:241-244): --compensator gain is the
+GainCompensator the demos create, gain_blocks the BlocksGainCompensator of createDefault(GAIN_BLOCKS) -, convertTo(CV_32F) +
 DP seam finder (S:87-1093, --seam-cost color_grad: DpSeamFinder::COLOR_GRAD W:255; --seam graphcut: W's own GraphCutSeamFinder, W:257-264; --seam voronoi: the VoronoiSeamFinder S constructs, S:1180), dilate 20x20 & warped mask (W:286-301), FeatherBlender 0.1 (W:278-313) or the
 multi-band blender (W:271-273), imwrite (W:315)."""
 import argparse
@@ -34,6 +35,9 @@ def main():
     ap.add_argument("--estimate-gains", action="store_true",
                     help="estimate the gains from the warped tiles as the reference does (GainCompensator feed, then apply; W:238-244) "
                          "instead of taking --gains")
+    ap.add_argument("--compensator", default="gain", choices=["gain", "gain_blocks"],
+                    help="with --estimate-gains: ExposureCompensator::createDefault(GAIN), one gain per tile, or (GAIN_BLOCKS), one per 32 x 32 "
+                         "block, applied as a smoothed gain map (W:238)")
     ap.add_argument("--seam", default="dp", choices=["dp", "graphcut", "voronoi"],
                     help="dp: the DP seam finder on a copy of the warped masks (S:1192); graphcut: W's own GraphCutSeamFinder(COST_COLOR), "
                          "which edits the warped masks while masks_seam stays their unedited copy (W:247-264); voronoi: the VoronoiSeamFinder of "
@@ -66,11 +70,15 @@ def main():
             c, wi, wm = warper.warp_with_mask(imgs[i], K, Rs[i])           # W:229, W:232
         corners.append(tuple(c)); warped.append(wi); wmasks.append(wm)
     if a.estimate_gains:
-        compensator = isx.GainCompensator()                                 # W:238
+        compensator = isx.BlocksGainCompensator() if a.compensator == "gain_blocks" else isx.GainCompensator()   # W:238
         compensator.feed(corners, warped, wmasks)                           # W:240
         for i in range(2):
             compensator.apply(i, corners[i], warped[i], wmasks[i])          # W:241-244
-        print("estimated gains", " ".join("%.9f" % g for g in compensator.gains()))
+        g = compensator.gains()
+        if a.compensator == "gain_blocks":
+            print("estimated gains of %d blocks: %.9f to %.9f" % (g.size, g.min(), g.max()))
+        else:
+            print("estimated gains", " ".join("%.9f" % v for v in g))
     seam = [m.copy() for m in wmasks]                                       # W:247-249
     if a.seam == "graphcut":                                                # W:257-264 as written: find edits masks_warped, and the
         isx.GraphCutSeamFinder(isx.seam.COST_COLOR).find(                   # blender gets dilate(masks_seam) & masks_warped (W:286-301)

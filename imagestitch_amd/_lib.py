@@ -89,6 +89,16 @@ _SIGS = {
     "isx_gain_apply": [_MP, C.c_double, C.c_int, C.c_void_p],
     "isx_gain_compensator_feed": [C.c_int, C.POINTER(C.c_int), _MP, _MP, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_double),
                                   C.c_int, C.c_void_p],
+    "isx_blocks_gain_create": [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)],
+    "isx_blocks_gain_destroy": [C.c_void_p],
+    "isx_blocks_gain_feed": [C.c_void_p, C.c_int, C.POINTER(C.c_int), _MP, _MP, C.c_void_p],
+    "isx_blocks_gain_apply": [C.c_void_p, C.c_int, _MP, C.c_void_p],
+    "isx_blocks_gain_num_images": [C.c_void_p, _IP, _IP],
+    "isx_blocks_gain_block_counts": [C.c_void_p, _IP],
+    "isx_blocks_gain_gains": [C.c_void_p, C.POINTER(C.c_double)],
+    "isx_blocks_gain_map": [C.c_void_p, C.c_int, _MP, C.c_void_p],
+    "isx_blocks_gain_stats": [C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong)],
+    "isx_blocks_gain_feed_times": [C.c_void_p, C.POINTER(C.c_double)],
     "isx_convert_to": [_MP, _MP, C.c_int, C.c_void_p],
     "isx_graphcut_seam_find": [C.c_int, _MP, C.POINTER(C.c_int), _MP, C.c_int, C.c_int, C.c_void_p],
     "isx_graphcut_seam_find_pair": [_MP, _MP, C.POINTER(C.c_int), _MP, _MP, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_int),
@@ -143,6 +153,7 @@ _SIGS = {
     "isx_gather_p2p_wait": [C.c_void_p, C.c_void_p],
     "isx_gather_p2p_synchronize": [C.c_void_p],
     "isx_selftest_division": [C.c_int, C.c_int, C.c_ulonglong, _IP],
+    "isx_selftest_lu_solve": [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _IP, C.c_int, C.c_int],
     "isx_selftest_roi_host": [C.c_int, C.c_float, _F9, _F9, C.c_int, C.c_int, C.c_int, _IP, _F9],
     "isx_selftest_warp_point": [C.c_int, C.c_float, _F9, _F9, C.POINTER(C.c_float), C.c_float, C.c_float, C.POINTER(C.c_float)],
     "isx_selftest_exception_barrier": [C.c_int],

@@ -22,6 +22,7 @@
 // in unsigned __int128 and rounds once.  Isum is therefore math.fsum of the terms, bit for bit, whatever the block shape or order.
 #include "isx_device.hpp"
 #include "pairwise.hpp"
+#include "gain_stats.hpp"
 
 #include <cmath>
 
@@ -34,21 +35,6 @@ constexpr int GF_NT = 256;                 // threads per block: one block per w
 constexpr int GF_DIAG_BYTES = 16384;       // mask bytes per diagonal item (about 4 chunks of 16 B per lane)
 constexpr int GF_PAIR_PIXELS = 4096;       // overlap pixels per off-diagonal item (4 groups of 4 pixels per lane)
 constexpr unsigned long long GF_LO_MASK = (1ull << 30) - 1ull;
-
-struct GainItem {
-    const unsigned char* m0;   // mask i at the overlap's top-left, this item's first row
-    const unsigned char* m1;   // mask j (off-diagonal only)
-    const unsigned char* p0;   // image i (CV_8UC3)
-    const unsigned char* p1;   // image j
-    unsigned long long sm0, sm1, sp0, sp1;   // row pitches in bytes
-    int rows, cols;            // the band: rows x cols pixels of the overlap
-    int diag;                  // 1: count mask i only
-    int pad_;
-};
-
-// partial record of one item: count, then the two limbs of image i's and of image j's sum
-enum { GP_N, GP_HI0, GP_LO0, GP_HI1, GP_LO1, GP_COUNT };
-struct GainPartial { unsigned long long v[GP_COUNT]; };
 
 // bytes equal to 0xFF in a dword: their high bits (exact, no carry between bytes)
 __device__ __forceinline__ unsigned ff_bytes(unsigned d) {
@@ -199,8 +185,39 @@ struct FeedScratch {
     size_t pin_cap = 0;
 };
 
-// OpenCV's hal::LU (Gaussian elimination, partial pivoting by the largest |pivot|, row swaps carried into b) and its back substitution,
-// in double; A is n x n row-major, b becomes the solution.  false: a pivot below 100 DBL_EPSILON (cv::solve returns false there).
+}  // namespace
+
+namespace isx {
+
+int gain_item_size(bool diag) { return diag ? GF_DIAG_BYTES : GF_PAIR_PIXELS; }
+
+int gain_feed_items(const std::vector<GainItem>& items, double alg_bytes, int device, hipStream_t st, std::vector<GainPartial>& part) {
+    const size_t ni = items.size();
+    const size_t tab_bytes = (ni * sizeof(GainItem) + 255) & ~(size_t)255, part_bytes = ni * sizeof(GainPartial);
+    FeedScratch& fs = per_thread<FeedScratch>();
+    if (fs.device != device) { fs.dev.release(); fs.device = device; }
+    ISX_TRY(fs.dev.reserve(tab_bytes + part_bytes));
+    if (fs.pin_cap < tab_bytes + part_bytes) {
+        if (fs.pin) { ISX_HIP(hipHostFree(fs.pin)); fs.pin = nullptr; fs.pin_cap = 0; }
+        const size_t want = std::max<size_t>(tab_bytes + part_bytes, 1u << 16);
+        ISX_HIP(hipHostMalloc(&fs.pin, want, hipHostMallocDefault));
+        fs.pin_cap = want;
+    }
+    GainItem* htab = (GainItem*)fs.pin;
+    const GainPartial* hpart = (const GainPartial*)((char*)fs.pin + tab_bytes);
+    std::copy(items.begin(), items.end(), htab);
+    GainItem* dtab = (GainItem*)fs.dev.p;
+    GainPartial* dpart = (GainPartial*)((char*)fs.dev.p + tab_bytes);
+    ISX_HIP(hipMemcpyAsync(dtab, htab, ni * sizeof(GainItem), hipMemcpyHostToDevice, st));
+    ISX_LAUNCH("gain_feed", alg_bytes, st, k_gain_feed, dim3((unsigned)ni), dim3(GF_NT), 0, (const GainItem*)dtab, dpart);
+    ISX_HIP(hipMemcpyAsync((void*)hpart, dpart, part_bytes, hipMemcpyDeviceToHost, st));
+    ISX_HIP(hipStreamSynchronize(st));       // host values come back (and the staging buffers of host mats are freed on return)
+    part.assign(hpart, hpart + ni);
+    return ISX_OK;
+}
+
+// OpenCV's hal::LU and its back substitution on the host (gain_stats.hpp states the contract; blocks_gain.hip runs the same operations
+// on the device)
 bool lu_solve(std::vector<double>& A, std::vector<double>& b, int n) {
     const double eps = 2.220446049250313e-16 * 100;
     for (int i = 0; i < n; ++i) {
@@ -227,7 +244,7 @@ bool lu_solve(std::vector<double>& A, std::vector<double>& b, int n) {
     return true;
 }
 
-}  // namespace
+}  // namespace isx
 
 extern "C" {
 
@@ -284,41 +301,17 @@ int isx_gain_compensator_feed(int num_images, const int* corners_xy, const isx_m
         pr.count = (int)items.size() - pr.first;
         bytes += (double)pr.w * pr.h * (diag ? 1.0 : 8.0);
     }
-    const size_t ni = items.size();          // >= n: every image overlaps itself
-    const size_t tab_bytes = (ni * sizeof(GainItem) + 255) & ~(size_t)255, part_bytes = ni * sizeof(GainPartial);
-    FeedScratch& fs = per_thread<FeedScratch>();
-    if (fs.device != device) { fs.dev.release(); fs.device = device; }
-    ISX_TRY(fs.dev.reserve(tab_bytes + part_bytes));
-    if (fs.pin_cap < tab_bytes + part_bytes) {
-        if (fs.pin) { ISX_HIP(hipHostFree(fs.pin)); fs.pin = nullptr; fs.pin_cap = 0; }
-        const size_t want = std::max<size_t>(tab_bytes + part_bytes, 1u << 16);
-        ISX_HIP(hipHostMalloc(&fs.pin, want, hipHostMallocDefault));
-        fs.pin_cap = want;
-    }
-    GainItem* htab = (GainItem*)fs.pin;
-    const GainPartial* hpart = (const GainPartial*)((char*)fs.pin + tab_bytes);
-    std::copy(items.begin(), items.end(), htab);
-    GainItem* dtab = (GainItem*)fs.dev.p;
-    GainPartial* dpart = (GainPartial*)((char*)fs.dev.p + tab_bytes);
-    ISX_HIP(hipMemcpyAsync(dtab, htab, ni * sizeof(GainItem), hipMemcpyHostToDevice, st));
-    ISX_LAUNCH("gain_feed", bytes, st, k_gain_feed, dim3((unsigned)ni), dim3(GF_NT), 0, (const GainItem*)dtab, dpart);
-    ISX_HIP(hipMemcpyAsync((void*)hpart, dpart, part_bytes, hipMemcpyDeviceToHost, st));
-    ISX_HIP(hipStreamSynchronize(st));       // host values come back (and the staging buffers of host mats are freed on return)
-    const std::vector<GainPartial> part(hpart, hpart + ni);
+    std::vector<GainPartial> part;           // items.size() >= n: every image overlaps itself
+    ISX_TRY(gain_feed_items(items, bytes, device, st, part));
 
     // N and I in OpenCV's layout: both start at 0 (Mat_::setTo(0)), so a pair without overlap keeps N = 0, I = 0; a pair with an
     // overlap gets N = max(1, count) - an empty intersect there gives N = 1, I = 0
     std::vector<long long> N((size_t)n * n, 0);
     std::vector<double> I((size_t)n * n, 0.0);
     for (const PairRoi& pr : pairs) {
-        unsigned long long cnt = 0;
-        unsigned __int128 s0 = 0, s1 = 0;
-        for (int k = pr.first; k < pr.first + pr.count; ++k) {
-            const GainPartial& p = part[k];
-            cnt += p.v[GP_N];
-            s0 += ((unsigned __int128)p.v[GP_HI0] << 30) + p.v[GP_LO0];
-            s1 += ((unsigned __int128)p.v[GP_HI1] << 30) + p.v[GP_LO1];
-        }
+        unsigned long long cnt;
+        unsigned __int128 s0, s1;
+        gain_partial_total(part, pr.first, pr.count, cnt, s0, s1);
         const long long nn = std::max<long long>(1, (long long)cnt);
         N[(size_t)pr.i * n + pr.j] = N[(size_t)pr.j * n + pr.i] = nn;
         if (pr.i != pr.j) {

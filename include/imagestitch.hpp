@@ -383,4 +383,46 @@ private:
     std::vector<double> gains_;
 };
 
+// cv::detail::BlocksGainCompensator(bl_width = 32, bl_height = 32), what ExposureCompensator::createDefault(ExposureCompensator::GAIN_BLOCKS)
+// returns (W:238-244): feed estimates one gain per block of every tile - the statistics and the dense LU solve on the GPU
+// (isx_blocks_gain_feed) - and keeps one smoothed gain map per tile on the device; apply(i, ...) multiplies tile i by its map resized to
+// the tile (isx_blocks_gain_apply).  Images CV_8UC3, masks CV_8U of the images' sizes (255 = in), host or device.
+class BlocksGainCompensator {
+public:
+    explicit BlocksGainCompensator(int bl_width = 32, int bl_height = 32, int device = 0) { check(isx_blocks_gain_create(bl_width, bl_height, device, &h_)); }
+    ~BlocksGainCompensator() { isx_blocks_gain_destroy(h_); }
+    BlocksGainCompensator(const BlocksGainCompensator&) = delete;
+    BlocksGainCompensator& operator=(const BlocksGainCompensator&) = delete;
+    void feed(const std::vector<Point>& corners, const std::vector<Mat>& images, const std::vector<Mat>& masks) {
+        if (images.size() != corners.size() || images.size() != masks.size())
+            throw Exception(ISX_ERR_INVALID, "feed: corners, images and masks differ in length");
+        std::vector<isx_mat> im(images.size()), mk(images.size());
+        std::vector<int> c;
+        for (size_t i = 0; i < images.size(); ++i) { im[i] = *images[i].c(); mk[i] = *masks[i].c(); c.push_back(corners[i].x); c.push_back(corners[i].y); }
+        check(isx_blocks_gain_feed(h_, (int)images.size(), c.data(), im.data(), mk.data(), nullptr));
+    }
+    void apply(int index, Point /*corner*/, Mat& image, const Mat& /*mask*/) { check(isx_blocks_gain_apply(h_, index, image.c(), nullptr)); }
+    // the raw gains, one per block (blocks numbered image by image, rows of blocks outer)
+    std::vector<double> gains() const {
+        int n = 0, nb = 0;
+        check(isx_blocks_gain_num_images(h_, &n, &nb));
+        std::vector<double> g((size_t)nb);
+        check(isx_blocks_gain_gains(h_, g.data()));
+        return g;
+    }
+    // the smoothed gain map of tile `index`: ny x nx CV_32FC1 on the host
+    Mat gainMap(int index) const {
+        int n = 0, nb = 0;
+        check(isx_blocks_gain_num_images(h_, &n, &nb));
+        if (index < 0 || index >= n) throw Exception(ISX_ERR_INVALID, "gainMap: no such image");
+        std::vector<int> cnt(2 * (size_t)n);
+        check(isx_blocks_gain_block_counts(h_, cnt.data()));
+        Mat m(cnt[2 * (size_t)index + 1], cnt[2 * (size_t)index], ISX_32FC1);
+        check(isx_blocks_gain_map(h_, index, m.c(), nullptr));
+        return m;
+    }
+private:
+    isx_blocks_gain* h_ = nullptr;
+};
+
 }  // namespace isx

@@ -390,6 +390,49 @@ int isx_gain_apply(isx_mat* image, double gain, int device, void* hip_stream);
 int isx_gain_compensator_feed(int num_images, const int* corners_xy, const isx_mat* images, const isx_mat* masks,
                               double* gains, long long* n_out, double* i_out, int device, void* hip_stream);
 
+/* BlocksGainCompensator(bl_width = 32, bl_height = 32), what ExposureCompensator::createDefault(ExposureCompensator::GAIN_BLOCKS) returns
+ * (W:238-239; OpenCV's own default in cv::Stitcher and stitching_detailed): one gain per block of every image, estimated by
+ * GainCompensator::feed on the blocks as if each were an image, kept as one smoothed CV_32F gain map per image and applied through
+ * cv::resize(map, image.size(), 0, 0, INTER_LINEAR).  A handle: the maps live on the device between feed and apply.  Restated from OpenCV
+ * 3.4.2 (tests/helpers/blocks_gain_np.py is the model); parity with OpenCV itself is unpinned.  `device` is the HIP device;
+ * create touches no device.  One handle serves one thread at a time.                                                              (W:238-244) */
+typedef struct isx_blocks_gain isx_blocks_gain;
+/* one pair of blocks of different images whose rectangles meet (block_i < block_j, blocks numbered image by image, rows of blocks outer):
+ * N = max(1, pixels where both masks are 255), I_ij = mean of sqrt(r^2 + g^2 + b^2) of block_i's image over them, I_ji of block_j's */
+typedef struct isx_block_pair {
+    int block_i, block_j;
+    long long n;
+    double i_ij, i_ji;
+} isx_block_pair;
+int isx_blocks_gain_create(int bl_width, int bl_height, int device, isx_blocks_gain** out);                              /* W:238-239 */
+int isx_blocks_gain_destroy(isx_blocks_gain* h);
+/* compensator->feed(corners, images_warped, masks_warped) (W:238-240): the statistics of every block and of every pair of blocks that meet
+ * in one GPU pass (exact sums, as isx_gain_compensator_feed), OpenCV's system assembled in its loop order, then solved ON THE DEVICE by
+ * hal::LU's arithmetic (dense, partial pivoting, double, no FMA); the matrix - (blocks + 1) x blocks doubles - is freed before the
+ * call returns.  images: n CV_8UC3, masks: n CV_8U of the images' sizes (255 = in), host or device.  Feeding again replaces everything.
+ * ISX_ERR_UNSUPPORTED for more than 16384 blocks in total (a 2 GiB matrix), ISX_ERR_INTERNAL for a singular system, the argument errors of
+ * isx_gain_compensator_feed.  Reads results back: on a capturing stream ISX_ERR_STATE with nothing enqueued.                 (W:238-244) */
+int isx_blocks_gain_feed(isx_blocks_gain* h, int num_images, const int* corners_xy, const isx_mat* images, const isx_mat* masks,
+                         void* hip_stream);
+/* compensator->apply(index, corner, image, mask) (W:241-244; corner and mask are unused there): image(y, x) = saturate_cast<uchar>(cvRound(
+ * (float)byte * g(y, x))) in place, g = map `index` resized to the image's size (INTER_LINEAR on CV_32F; the map itself when it has the
+ * image's size), one launch.  image: CV_8UC3 (ISX_ERR_TYPE otherwise), host or device, any pointer and pitch, of any size - not only the
+ * one fed.  ISX_ERR_STATE before feed, ISX_ERR_INVALID for an index out of range.  On a device mat it synchronises nothing and can be
+ * captured; a size this handle has not seen yet uploads its tables first (on a capturing stream: ISX_ERR_STATE, nothing enqueued).
+ * The tables of every size seen are kept until destroy; a graph captured before a later feed reads that feed's maps.         (W:238-244) */
+int isx_blocks_gain_apply(isx_blocks_gain* h, int index, isx_mat* image, void* hip_stream);
+/* after feed (ISX_ERR_STATE before): the number of images and of blocks; (nx, ny) per image; the raw gains, one double per block;
+ * the smoothed map of one image into a caller's ny x nx CV_32FC1 mat (host: copied at once; device: enqueued on hip_stream); the
+ * statistics as sparse records - the count, then up to `capacity` records (ISX_ERR_SIZE when too few; pairs may be NULL) and the diagonal
+ * N, one per block (may be NULL); the host's wall-clock milliseconds of the last feed's statistics, assembly, LU and back substitution.
+ * Nothing here builds a blocks x blocks array.                                                                               (W:238-244) */
+int isx_blocks_gain_num_images(const isx_blocks_gain* h, int* num_images, int* num_blocks);
+int isx_blocks_gain_block_counts(const isx_blocks_gain* h, int* nx_ny);
+int isx_blocks_gain_gains(const isx_blocks_gain* h, double* gains);
+int isx_blocks_gain_map(const isx_blocks_gain* h, int index, isx_mat* out, void* hip_stream);
+int isx_blocks_gain_stats(const isx_blocks_gain* h, long long* num_pairs, isx_block_pair* pairs, long long capacity, long long* diag_n);
+int isx_blocks_gain_feed_times(const isx_blocks_gain* h, double* ms4);
+
 /* ---- the glue conversions of the reference's main() ---------------------------------- */
 /* src.convertTo(dst, dst.type()) with alpha = 1, beta = 0 between the CV_8U, CV_16S and CV_32F depths, same channel count:
  * images_warped[i].convertTo(images_warped_f[i], CV_32F) (W:261), images_warped_f[k].convertTo(images_warped_s[k], CV_16S) (W:294; CV_8U ->
@@ -593,6 +636,11 @@ int isx_gather_p2p_synchronize(isx_gather* g);
  * written out in packed FMAs (csrc/warp.hip, k_warp_tile).  This compares that recurrence with the compiler's IEEE division
  * on n pseudo-random operand pairs of the range the kernel admits to it; *mismatches must come back 0.              */
 int isx_selftest_division(int device, int n, unsigned long long seed, int* mismatches);
+/* The dense solver of isx_blocks_gain_feed alone: x = solve(A, b, DECOMP_LU) for a caller's n x n row-major A and b in double, by hal::LU's
+ * arithmetic on the device (where = 0; *swaps, may be NULL, gets the number of row exchanges) or by the host's scalar code that
+ * isx_gain_compensator_feed solves with (where = 1; *swaps = -1).  n from 1 to 16384.  ISX_ERR_INTERNAL for a pivot below 100 DBL_EPSILON
+ * (cv::solve returns false there); x is then untouched.  Uses the null stream and synchronises it.                          (W:238-244) */
+int isx_selftest_lu_solve(int n, const double* A, const double* b, double* x, int* swaps, int where, int device);
 /* detectResultRoi (W:64-88; SphericalWarper's border form) computed on the host alone - what isx_warper_roi returns for the cameras whose
  * extrema provably lie on the source's border (every spherical camera; a cylindrical one with the image in front of the camera and no pole
  * of the cylinder near it: every rig of the reference): the 2 (W + H) border pixels ranked on the caller's thread by two monotone stand-ins
