@@ -361,6 +361,9 @@ int isx_blocks_gain_feed(isx_blocks_gain* h, int num_images, const int* corners_
             block_pairs(corners_xy + 2 * i, grids[(size_t)i], corners_xy + 2 * j, grids[(size_t)j], [&](const BlockPair& p) { bp.push_back(p); });
             if (bp.size() != before) need_img[(size_t)i] = need_img[(size_t)j] = 1;
         }
+    // the records go out by block_i, then block_j: the loop above gives that order within a pair of images, not across three images that
+    // all meet (image 0's blocks against image 2's come after all of image 0's against image 1's)
+    std::sort(bp.begin(), bp.end(), [](const BlockPair& a, const BlockPair& c) { return a.bi != c.bi ? a.bi < c.bi : a.bj < c.bj; });
     for (int i = 0; i < n; ++i)
         if (need_img[(size_t)i]) ISX_TRY(h->stages.stage((size_t)(n + i), &images[i], false, st, who, simg[(size_t)i]));
     // the image of a global block number

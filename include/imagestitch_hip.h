@@ -398,7 +398,8 @@ int isx_gain_compensator_feed(int num_images, const int* corners_xy, const isx_m
  * create touches no device.  One handle serves one thread at a time.                                                              (W:238-244) */
 typedef struct isx_blocks_gain isx_blocks_gain;
 /* one pair of blocks of different images whose rectangles meet (block_i < block_j, blocks numbered image by image, rows of blocks outer):
- * N = max(1, pixels where both masks are 255), I_ij = mean of sqrt(r^2 + g^2 + b^2) of block_i's image over them, I_ji of block_j's */
+ * N = max(1, pixels where both masks are 255), I_ij = mean of sqrt(r^2 + g^2 + b^2) of block_i's image over them, I_ji of block_j's.
+ * isx_blocks_gain_stats gives the records by block_i ascending, then block_j */
 typedef struct isx_block_pair {
     int block_i, block_j;
     long long n;
@@ -419,7 +420,8 @@ int isx_blocks_gain_feed(isx_blocks_gain* h, int num_images, const int* corners_
  * image's size), one launch.  image: CV_8UC3 (ISX_ERR_TYPE otherwise), host or device, any pointer and pitch, of any size - not only the
  * one fed.  ISX_ERR_STATE before feed, ISX_ERR_INVALID for an index out of range.  On a device mat it synchronises nothing and can be
  * captured; a size this handle has not seen yet uploads its tables first (on a capturing stream: ISX_ERR_STATE, nothing enqueued).
- * The tables of every size seen are kept until destroy; a graph captured before a later feed reads that feed's maps.         (W:238-244) */
+ * The tables of every size seen are kept until destroy; a graph captured before a later feed of images of the same sizes reads that
+ * feed's maps (after a feed of other sizes the captured launch keeps the old grid's offset and width: capture again).        (W:238-244) */
 int isx_blocks_gain_apply(isx_blocks_gain* h, int index, isx_mat* image, void* hip_stream);
 /* after feed (ISX_ERR_STATE before): the number of images and of blocks; (nx, ny) per image; the raw gains, one double per block;
  * the smoothed map of one image into a caller's ny x nx CV_32FC1 mat (host: copied at once; device: enqueued on hip_stream); the

@@ -72,12 +72,31 @@ def test_masks_with_holes_leave_pairs_without_a_counted_pixel():
 
 
 def test_sparse_system_is_the_dense_one():
-    for name in cases.CASES:
+    for name in list(cases.CASES) + list(cases.MORE):
         _, _, _, model = cases.case(name)
         r, c, v, b = M.sparse_system(model["pairs"], model["diag_n"])
         A = np.zeros_like(model["A"])
         A[r, c] = v
         assert np.array_equal(A, model["A"]) and np.array_equal(b, model["b"]), name
+
+
+@pytest.mark.parametrize("name", sorted(cases.MORE))
+def test_the_further_sets_reach_what_they_are_for(name):
+    """cases.MORE: records of several work items (the second band shorter), a row wider than an item, no pair of blocks at all (every
+    gain exactly 1.0), one-pixel blocks whose system swaps rows - from the geometry and gain.hip's constants; and the rtol of their gains."""
+    cases.premise(name)
+    rtol, measured = cases.gain_rtol(name)
+    _, _, _, model = cases.case(name)
+    print("%s: %d blocks, cond_1 %.3g, NumPy hal::LU against np.linalg.solve %.3g, rtol %.3g" % (name, len(model["b"]), np.linalg.cond(model["A"], 1), measured, rtol))
+    assert 0 < len(model["b"]) * 2.0 ** -52 <= rtol / 4 <= 2.5e-10 and 4 * measured <= rtol
+
+
+def test_bands_by_hand():
+    assert cases.bands(150, 200, 16384) == [109, 91] and cases.bands(4097, 2, 4096) == [1, 1] and cases.bands(64, 64, 4096) == [64]
+    assert cases.bands(113, 190, 4096) == [36] * 5 + [10] and cases.bands(1, 1, 4096) == [1] and cases.bands(4096, 3, 4096) == [1, 1, 1]
+    diag, pairs = cases.record_items([(0, 0), (5, 0)], [(10, 10), (10, 10)], 32, 32, 16384, 4096)
+    assert diag == [(10, 10, [10])] * 2 and pairs == [(5, 10, [10])]
+    assert cases.record_items([(0, 0), (10, 0)], [(10, 10), (10, 10)], 4, 4, 16384, 4096)[1] == []           # they touch and do not meet
 
 
 # ---- smoothing ---------------------------------------------------------------------------------------------------------------------------
@@ -243,9 +262,13 @@ def test_host_arithmetic_under_sanitizers(tmp_path):
     grids = [(100, 80, 32, 32), (90, 70, 32, 32), (20, 9, 32, 32), (7, 5, 1, 1), (1101, 1101, 32, 32), (3840, 2160, 64, 64), (33, 65, 32, 32), (1, 1, 5, 3)]
     pairs = [(0, 0, 100, 80, 37, 5, 90, 70, 32, 32), (0, 0, 100, 80, 99, 79, 90, 70, 32, 32), (0, 0, 100, 80, 100, 0, 90, 70, 32, 32),
              (-30, -20, 55, 41, -12, -33, 47, 36, 8, 5), (2**31 - 60, 2**31 - 50, 50, 40, 2**31 - 40, 2**31 - 70, 30, 60, 7, 7),
-             (-2**31, -2**31, 64, 64, -2**31 + 13, -2**31 + 40, 90, 30, 16, 9), (5, 5, 10, 10, 0, 0, 60, 60, 4, 4), (0, 0, 37, 29, 0, 0, 37, 29, 5, 3)]
+             (-2**31, -2**31, 64, 64, -2**31 + 13, -2**31 + 40, 90, 30, 16, 9), (5, 5, 10, 10, 0, 0, 60, 60, 4, 4), (0, 0, 37, 29, 0, 0, 37, 29, 5, 3),
+             # blocks larger than the images, a block wider than a work item, one-pixel blocks (the sets of cases.MORE)
+             (0, 0, 300, 200, 37, 5, 280, 190, 200, 200), (0, 0, 4100, 3, -3, 1, 4100, 4, 8192, 32), (0, 0, 9, 7, 4, 3, 8, 6, 1, 1),
+             (0, 0, 40, 30, 100, 100, 20, 20, 32, 32)]
     smooths = [rng.random((ny, nx)).astype(F32) + F32(0.5) for ny, nx in ((1, 1), (1, 3), (3, 3), (1, 2), (2, 1), (5, 7), (34, 3))]
-    tables = [(2, 1, 4, 1), (1, 3, 1, 7), (3, 2, 67, 45), (1, 1, 9, 9), (4, 3, 3, 2), (35, 35, 1101, 1101), (7, 5, 8, 6), (60, 34, 3840, 2160)]
+    tables = [(2, 1, 4, 1), (1, 3, 1, 7), (3, 2, 67, 45), (1, 1, 9, 9), (4, 3, 3, 2), (35, 35, 1101, 1101), (7, 5, 8, 6), (60, 34, 3840, 2160),
+              (13, 7, 5, 7), (13, 7, 13, 3), (13, 7, 4, 3), (13, 7, 40, 3), (1, 5, 20, 40), (5, 1, 257, 17)]      # a map larger than the image, one block wide, one block high
     text = "".join("grid %d %d %d %d\n" % g for g in grids) + "".join("pairs " + " ".join(str(v) for v in p) + "\n" for p in pairs)
     text += "".join("smooth %d %d %s\n" % (m.shape[0], m.shape[1], " ".join(_hex(v) for v in m.ravel())) for m in smooths)
     text += "".join("tables %d %d %d %d\n" % t for t in tables)

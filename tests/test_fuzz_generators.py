@@ -1,5 +1,5 @@
-"""The generator and model halves of the five fuzz families tools/fuzz_parity.py has for the entry points merged after round 6 (the plane
-projector, GainCompensator::feed, the Voronoi and graph-cut seam finders, COLOR_GRAD and seam_gradients), without a GPU: every shape
+"""The generator and model halves of the fuzz families tools/fuzz_parity.py has for the entry points merged after round 6 (the plane
+projector, GainCompensator::feed, the Voronoi and graph-cut seam finders, COLOR_GRAD and seam_gradients, BlocksGainCompensator), without a GPU: every shape
 class of a family is drawn, every drawn case has the shape its class names - recomputed from the case itself, against the tiling
 constants read from the kernels' sources -, and the models stay busy on them: few skips, seams that cut, overlaps that count."""
 import os
@@ -14,7 +14,7 @@ import fuzz_parity as F  # noqa: E402
 from helpers import voronoi_np as V  # noqa: E402
 
 FAMILIES = {"plane_warp": F.PLANE_CLASSES, "gain_feed": F.GAIN_CLASSES, "voronoi": F.VORONOI_CLASSES, "graphcut": F.GRAPHCUT_CLASSES,
-            "seam_grad": F.SEAM_GRAD_CLASSES}
+            "seam_grad": F.SEAM_GRAD_CLASSES, "blocks_gain": F.BLOCKS_GAIN_CLASSES}
 GEN_SEEDS, MODEL_SEEDS = range(200), range(5000, 5030)
 
 
@@ -31,7 +31,10 @@ def test_the_constants_are_the_kernels():
     assert F.GF_PAIR_SIZES == [4095, 4096, 4097, 8192, 8193] and F.GF_DIAG_SIZES == [16383, 16384, 16385]
     assert F.GRAD_WIDTHS == [63, 64, 65, 129] and F.GRAD_HEIGHTS == [15, 16, 17, 33]
     assert F.SEAM_GAP == V.GAP == 10
-    assert [f.__name__ for f in F.CASES[-5:]] == F.NEW_FAMILIES and len(F.CASES) == 24
+    assert [f.__name__ for f in F.CASES[-6:-1]] == F.NEW_FAMILIES and len(F.CASES) == 25
+    assert F.CASES[-1].__name__ == "case_blocks_gain"
+    assert F.BG_WIDE_ROWS == [4095, 4096, 4097, 4101] and F.BG_APPLY_WIDTHS == [255, 256, 257, 511, 512, 513] and F.BG_APPLY_HEIGHTS == [15, 16, 17]
+    assert [F._BG[k] for k in ("BA_PX", "BA_ROWS", "LU_NT", "LU_RB", "LU_PNT")] == [4, 4, 256, 8, 1024] and F.BG_MAX_UNKNOWNS == 250
 
 
 def check_plane_warp(c):
@@ -125,6 +128,41 @@ def check_seam_grad(c):
         assert x == 0 or y == 0 or x + w == iw or y + h == ih
 
 
+def check_blocks_gain(c):
+    from helpers import blocks_gain_np as BG
+    _check_tiles(c, 1, 4)
+    assert all(a.dtype == np.uint8 for a in c["imgs"]) and all(np.isin(m, (0, 254, 255)).all() for m in c["masks"])
+    blw, blh = c["blocks"]
+    assert blw >= 1 and blh >= 1
+    B = sum(nx * ny for nx, ny in (BG.block_grid(w, h, blw, blh)[:2] for w, h in c["sizes"]))
+    assert 1 <= B <= F.BG_MAX_UNKNOWNS
+    diag, pairs = F.bg_record_items(c["corners"], c["sizes"], blw, blh, F._GF["GF_DIAG_BYTES"], F._GF["GF_PAIR_PIXELS"])
+    assert len(diag) == B
+    assert 1 <= len(c["apply"]) <= 2
+    for index, img in c["apply"]:
+        assert 0 <= index < len(c["sizes"]) and img.dtype == np.uint8 and img.ndim == 3 and img.shape[2] == 3 and img.size > 0
+    rois = _rois(c)
+    if c["cls"] == "plain":
+        assert len(c["sizes"]) >= 2 and 6 <= blw and 6 <= blh and any(r is not None for r in rois.values())
+    if c["cls"] == "several_items":
+        assert 96 <= blw <= 256 and 96 <= blh <= 256 and any(len(b) >= 2 for _, _, b in diag + pairs)       # items per record, by the band formula
+    if c["cls"] == "wide_row":
+        assert blw >= max(w for w, _ in c["sizes"])
+        assert any(w in F.BG_WIDE_ROWS and 1 <= h <= 4 and set(b) == {1} for w, h, b in pairs)        # a band is one row
+    if c["cls"] == "one_pixel_blocks":
+        assert (blw, blh) == (1, 1) and all(w <= 10 and h <= 8 for w, h in c["sizes"]) and B == sum(w * h for w, h in c["sizes"])
+    if c["cls"] == "no_pairs":
+        assert all(r is None for r in rois.values()) and pairs == []
+    if c["cls"] == "one_pixel_meeting":
+        assert len(pairs) == 1 and pairs[0][:2] == (1, 1)
+        x, y = rois[(0, 1)][:2]
+        assert rois[(0, 1)][2:] == (1, 1) and all(c["masks"][k][y - c["corners"][k][1], x - c["corners"][k][0]] == 255 for k in (0, 1))      # and it counts
+    if c["cls"] == "apply_edges":
+        for index, img in c["apply"]:
+            h, w = img.shape[:2]
+            assert (w in F.BG_APPLY_WIDTHS or h in F.BG_APPLY_HEIGHTS) and (w, h) != c["sizes"][index]
+
+
 @pytest.mark.parametrize("family", sorted(FAMILIES))
 def test_every_class_is_drawn_and_has_its_shape(family):
     gen, check = getattr(F, "gen_" + family), globals()["check_" + family]
@@ -144,7 +182,7 @@ def test_every_class_is_drawn_and_has_its_shape(family):
 def test_the_models_stay_busy(family):
     """30 cases through gen + model: at most 10 % skips; the seam finders' models change a mask in at least half of the cases that have
     masks (all of them, but for seam_grad's gradient half); at least half of the gain cases count an overlap (an off-diagonal N above 1,
-    the value an empty intersection gets)."""
+    the value an empty intersection gets), and at least half of the blocks-gain cases have an off-diagonal record with N above 1."""
     if family == "graphcut":
         pytest.importorskip("scipy")
     gen, model = getattr(F, "gen_" + family), getattr(F, "model_" + family)
@@ -158,6 +196,10 @@ def test_the_models_stay_busy(family):
         elif family == "gain_feed":
             N = want["N"]
             busy += bool((N - np.diag(np.diag(N)) > 1).any())
+        elif family == "blocks_gain":
+            busy += any(p[2] > 1 for p in want["pairs"])
+            if c["cls"] == "no_pairs":                                   # diag and b are the same sums: the quotient is exact
+                assert want["pairs"] == [] and np.all(want["gains"] == 1.0)
         elif "masks" in c:
             with_masks += 1
             masks = want[0] if family == "graphcut" else want
@@ -165,7 +207,7 @@ def test_the_models_stay_busy(family):
     n = len(MODEL_SEEDS)
     print(family, "skips", skips, "busy", busy, "of", with_masks if with_masks else n)
     assert skips * 10 <= n
-    if family == "gain_feed":
+    if family in ("gain_feed", "blocks_gain"):
         assert busy * 2 >= n, (busy, n)
     elif family != "plane_warp":
         assert with_masks >= (n // 3 if family == "seam_grad" else n - skips) and busy * 2 >= with_masks, (busy, with_masks, n)

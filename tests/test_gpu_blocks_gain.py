@@ -8,7 +8,14 @@ otherwise.  rtol of the gains = 4 x the largest relative difference between np.l
 most 1e-9 - computed by the tests, on the CPU.  Measured on the CPU: 1.03e-15 over the four tile sets of tests/blocks_gain_cases.py (21 and
 18 blocks, condition numbers 9 to 37; rtol 4.1e-15), 6 row swaps in "dark_against_bright"; 1.4e-13 over the dense systems of the solver's
 own test (rtol 5.6e-13).  The 2 450-unknown system: scipy.sparse.linalg.spsolve leaves ||A g - b||inf / (||A||inf ||g||inf + ||b||inf) =
-1.5e-16 (computed by the test from the library's statistics, printed with the library's own figure); the bound is 8 x that."""
+1.5e-16 (computed by the test from the library's statistics, printed with the library's own figure); the bound is 8 x that.
+
+The sets of cases.MORE (three tiles that all meet, records of several work items, a row wider than an item, no pair at all, one-pixel
+blocks) have a rtol of their own: on several of them the two CPU solves agree to the last bit, and rtol 0 is no fair demand of a back
+substitution that adds in another order.  Per set rtol = min(1e-9, 4 max(that difference, B 2^-52 cond_1(A))), A the model's dense system
+(cases.forward_error_rtol): the textbook forward-error scale, from the model alone.  Measured on the CPU: differences 0 to 2.2e-16,
+rtol 4.3e-15 ("apart", 3 blocks, cond 1.6) to 4.3e-12 ("one_pixel_blocks", 111 blocks, cond 44, 20 row swaps).  The solver past one stride
+of its pivot search (n = 513, 1025, 1100): the model's differences are 6.8e-15 to 1.7e-12, its swaps 0, 1, 2, 2 and 0."""
 import functools
 import os
 import subprocess
@@ -58,12 +65,14 @@ def _check_stats(comp, model):
 
 
 def _check(gpu, name, images=None, masks=None):
+    """The sets of cases.CASES keep their rtol (_gain_rtol); a set of cases.MORE has its own, cases.gain_rtol."""
     corners, imgs, msks, model = cases.case(name)
-    comp = gpu.BlocksGainCompensator().feed(corners, imgs if images is None else images, msks if masks is None else masks)
+    comp = gpu.BlocksGainCompensator(*cases.blocks(name)).feed(corners, imgs if images is None else images, msks if masks is None else masks)
     _check_stats(comp, model)
     g = comp.gains()
-    print("%s: largest relative difference of the gains to np.linalg.solve %.3g (rtol %.3g)" % (name, np.max(np.abs(g - model["gains"]) / np.abs(model["gains"])), _gain_rtol()))
-    np.testing.assert_allclose(g, model["gains"], rtol=_gain_rtol(), atol=0)
+    rtol = _gain_rtol() if name in cases.CASES else cases.gain_rtol(name)[0]
+    print("%s: largest relative difference of the gains to np.linalg.solve %.3g (rtol %.3g)" % (name, np.max(np.abs(g - model["gains"]) / np.abs(model["gains"])), rtol))
+    np.testing.assert_allclose(g, model["gains"], rtol=rtol, atol=0)
     maps = comp.gain_maps()
     for got, want in zip(maps, M.maps_from_gains(g, model["counts"])):
         assert got.dtype == F32 and np.array_equal(got.view(np.uint32), want.view(np.uint32))
@@ -111,6 +120,75 @@ def test_feeding_twice_gives_the_second_sets_results(gpu):
     _check_stats(comp, model)
     np.testing.assert_allclose(comp.gains(), model["gains"], rtol=_gain_rtol(), atol=0)
     assert len(comp.gain_maps()) == 3
+
+
+# ---- records of several work items, a row wider than an item, no pair at all, one-pixel blocks -------------------------------------------------
+
+@pytest.mark.parametrize("where", ["host", "device", "host_odd", "device_odd"])
+@pytest.mark.parametrize("name", sorted(cases.MORE))
+def test_more_sets(gpu, name, where):
+    """The sets of cases.MORE through _check (block counts, N exactly, I bit for bit, gains, maps bit for bit), then apply on every tile: as
+    host mats, as device mats, and as pitched unaligned views in guard bands with 255 all around the masks - feed writes nothing, apply
+    the image's bytes only.  Without a pair of blocks that meet every gain is exactly 1.0 and apply leaves the image byte for byte."""
+    import torch
+    corners, imgs, masks, model = cases.case(name)
+    cases.premise(name)
+    gi = gm = None
+    if where == "host":
+        mi, mm = [a.copy() for a in imgs], [m.copy() for m in masks]
+    elif where == "device":
+        mi, mm = [_dev(a) for a in imgs], [_dev(m) for m in masks]
+    else:
+        place = where.split("_")[0]
+        gi = [guarded.guarded_like(a, place, "odd", 20 + k) for k, a in enumerate(imgs)]
+        gm = [guarded.guarded_like(m, place, "odd", 30 + k) for k, m in enumerate(masks)]
+        for g, m in zip(gm, masks):
+            g.buf[...] = 255
+            g.set(m)
+        mi, mm = [g.view for g in gi], [g.view for g in gm]
+    comp = _check(gpu, name, mi, mm)
+    if gi:
+        for g in gi + gm:
+            g.check(guarded.NOTHING)
+    g = comp.gains()
+    maps = comp.gain_maps()
+    if name in cases.NO_PAIRS:
+        assert len(comp.block_stats()[0]) == 0
+        assert np.all(g == 1.0) and all(np.all(m == F32(1)) for m in maps)
+    for k, img in enumerate(imgs):
+        want = M.apply_model(img, maps[k])
+        if name in cases.NO_PAIRS:
+            assert np.array_equal(want, img)
+        comp.apply(k, corners[k], mi[k], mm[k])
+        torch.cuda.synchronize()
+        assert np.array_equal(_np(mi[k]), want), k
+        if gi:
+            gi[k].check()
+            gm[k].check(guarded.NOTHING)
+
+
+def test_map_query_into_pitched_mats(gpu):
+    """isx_blocks_gain_map itself, on the handle's stream: into pitched host mats (row by row) and into pitched device mats (one
+    hipMemcpy2DAsync with the caller's pitch), both layouts, inside guard bands: gain_maps() bit for bit and nothing written beside it."""
+    import ctypes as C
+    import torch
+    from imagestitch_amd import _lib
+    corners, imgs, masks, _ = cases.case("three_tiles")
+    s = torch.cuda.Stream()
+    comp = gpu.BlocksGainCompensator(stream=s).feed(corners, imgs, masks)
+    maps = comp.gain_maps()
+    assert [m.shape for m in maps] == [(2, 3), (2, 3), (3, 2)]
+    lib = _lib.load()
+    for where in ("host", "device"):
+        for layout in guarded.LAYOUTS:
+            for i, m in enumerate(maps):
+                g = guarded.guarded_like(np.zeros_like(m), where, layout, 50 + i)
+                mm = _lib.as_mat(g.view)
+                assert mm.step > m.shape[1] * 4
+                _lib.check(lib.isx_blocks_gain_map(comp._h, i, C.byref(mm), comp._stream()))
+                torch.cuda.synchronize()
+                g.check()
+                assert np.array_equal(g.get().view(np.uint32), m.view(np.uint32)), (where, layout, i)
 
 
 # ---- the solver alone ----------------------------------------------------------------------------------------------------------------------
@@ -162,6 +240,90 @@ def test_solver_alone(gpu):
         np.testing.assert_allclose(x, want, rtol=rtol, atol=0, err_msg=k)
         xh, _ = exposure.lu_solve(A, b, where="host")
         np.testing.assert_allclose(xh, want, rtol=rtol, atol=0, err_msg=k)
+
+
+def _lu_constants():
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import fuzz_parity
+    c = fuzz_parity._kernel_consts("blocks_gain.hip")
+    return c["LU_PNT"], c["LU_NT"]
+
+
+def _dominant(n, seed):
+    """A diagonal in [4, 5] over off-diagonal noise of 0.01 x normal: hal::LU swaps no rows until an entry is planted."""
+    rng = np.random.default_rng(seed)
+    A = 0.01 * rng.standard_normal((n, n))
+    A[np.arange(n), np.arange(n)] = rng.uniform(4, 5, n)
+    return A, rng.uniform(1, 2, n)
+
+
+def _planted(n, seed, entries):
+    A, b = _dominant(n, seed)
+    for (r, c), v in entries.items():
+        A[r, c] = v
+    return A, b
+
+
+def _pivot_in_the_second_stride():
+    """n = LU_PNT + 1: row LU_PNT is the only one k_lu_pivot's second stride holds, and column 0's largest |value| sits there."""
+    n = _lu_constants()[0] + 1
+    A, b = _dense(n, 100 + n)
+    A[n - 1, 0] = 2.0 * np.abs(A[:, 0]).max()
+    return A, b
+
+
+# n = 1100 is past LU_PNT = 1024: rows 1024.. are the pivot search's second stride, and k_lu_backsub's dot products take two strides.
+# "tie_diagonal" and "tie_below": column 0 is searched before anything is eliminated, so its tie is exact.  In the first the diagonal is
+# among the tied rows (0, 70 and 1030) and, being the first of them, is the pivot: no swap there.  In the second the diagonal is smaller
+# than the tied rows (70, 200 and 1030): a swap there.  The two tell "the first of the tied rows when that is the diagonal" from any
+# other choice; which of two tied rows BELOW the diagonal is taken shows neither in x nor in the swap count, and nothing here claims it.
+LARGE = {
+    "pivot_in_the_second_stride": _pivot_in_the_second_stride,
+    "pivots_past_one_stride": lambda: _planted(1100, 79, {(1050, 0): 50.0, (1099, 3): -60.0}),
+    "tie_diagonal": lambda: _planted(1100, 80, {(0, 0): 5.0, (70, 0): -5.0, (1030, 0): 5.0}),
+    "tie_below": lambda: _planted(1100, 80, {(0, 0): 1.0, (70, 0): -9.0, (200, 0): 9.0, (1030, 0): 9.0}),
+    "three_column_blocks": lambda: _dense(2 * _lu_constants()[1] + 1, 613),      # k_lu_update: three column blocks, the last one column (b) wide
+}
+
+
+@functools.lru_cache(maxsize=None)
+def _large(name):
+    """(A, b, np.linalg.solve, the model's swaps, the model's relative difference) of a LARGE system: about 2 s of NumPy hal::LU, once."""
+    A, b = LARGE[name]()
+    x, swaps = M.hal_lu_solve(A, b)
+    want = np.linalg.solve(A, b)
+    return A, b, want, swaps, float(np.max(np.abs(x - want) / np.abs(want)))
+
+
+@pytest.mark.parametrize("name", sorted(LARGE))
+def test_solver_alone_past_one_stride(gpu, name):
+    """Systems larger than one stride of the pivot search (LU_PNT rows) and of k_lu_update's column block (LU_NT): the swaps are the model's,
+    x by the rule of _systems() - 4 x the largest relative difference between np.linalg.solve and the NumPy hal::LU over the systems used
+    (those of _systems() and this one), at most 1e-9."""
+    from imagestitch_amd import exposure
+    pnt, nt = _lu_constants()
+    A, b, want, model_swaps, diff = _large(name)
+    n = b.size
+    rtol = min(4 * max(diff, _systems()[2] / 4), 1e-9)
+    if name == "pivot_in_the_second_stride":
+        assert n == pnt + 1 and int(np.argmax(np.abs(A[:, 0]))) == pnt and model_swaps >= 1
+    elif name == "pivots_past_one_stride":
+        assert n > pnt and int(np.argmax(np.abs(A[:, 0]))) == 1050 >= pnt and int(np.argmax(np.abs(A[:, 3]))) == n - 1 and model_swaps >= 2
+    elif name == "tie_diagonal":
+        tied = np.flatnonzero(np.abs(A[:, 0]) == np.abs(A[:, 0]).max())
+        assert list(tied) == [0, 70, 1030] and tied[-1] >= pnt and int(np.argmax(np.abs(A[:, 0]))) == 0        # the model: no swap at column 0
+    elif name == "tie_below":
+        tied = np.flatnonzero(np.abs(A[:, 0]) == np.abs(A[:, 0]).max())
+        assert list(tied) == [70, 200, 1030] and abs(A[0, 0]) < 9.0 and model_swaps >= _large("tie_diagonal")[3] + 1
+    else:
+        assert n == 2 * nt + 1 and -(-n // nt) == 3 and n - 2 * nt == 1                  # step 0 updates columns 1..n: LU_NT, LU_NT and column n alone
+    x, swaps = exposure.lu_solve(A, b)
+    print("%s: n %d, swaps %d (model %d), largest relative difference to np.linalg.solve %.3g (the model's %.3g, rtol %.3g)"
+          % (name, n, swaps, model_swaps, np.max(np.abs(x - want) / np.abs(want)), diff, rtol))
+    assert swaps == model_swaps
+    np.testing.assert_allclose(x, want, rtol=rtol, atol=0)
+    xh, _ = exposure.lu_solve(A, b, where="host")
+    np.testing.assert_allclose(xh, want, rtol=rtol, atol=0)
 
 
 def test_singular_matrix_is_an_error_and_everything_stays_usable(gpu):
@@ -225,7 +387,15 @@ APPLY = {                     # name: (width, height, bl_width, bl_height)
     "map_1x1": (20, 9, 32, 32),
     "map_of_the_images_size": (13, 7, 1, 1),
     "tall_blocks": (40, 70, 8, 64),
+    # a workgroup's footprint is 4 * 64 = 256 columns x 4 * 4 = 16 rows (asserted against BA_PX, BA_ROWS below): one less, exactly, one more
+    "w255_h15": (255, 15, 32, 32), "w256_h16": (256, 16, 32, 32), "w257_h17": (257, 17, 32, 32),
+    "w511_h16": (511, 16, 32, 32), "w512_h17": (512, 17, 32, 32), "w513_h15": (513, 15, 32, 32),
+    # one row of less than, exactly and more than one group of four pixels
+    "w1_h1": (1, 1, 32, 32), "w2_h1": (2, 1, 32, 32), "w3_h1": (3, 1, 32, 32), "w4_h1": (4, 1, 32, 32), "w5_h1": (5, 1, 32, 32),
+    "map_1_wide_5_high": (20, 40, 32, 8),         # no tap to the right of any column: S[sx] alone
+    "map_5_wide_1_high": (40, 20, 8, 32),         # both row indices clamp to row 0
 }
+EDGE_WIDTHS, EDGE_HEIGHTS = [4 * 64 * k + d for k in (1, 2) for d in (-1, 0, 1)], [15, 16, 17]
 
 
 @functools.lru_cache(maxsize=None)
@@ -241,10 +411,34 @@ def _fed(name):
     maps = comp.gain_maps()
     assert maps[0].shape == M.block_grid(w, h, blw, blh)[1::-1] and maps[0].max() > 1.05 and maps[1].min() < 0.95
     img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+    img[0, 0] = (255, 90, 180)                                     # the bright corner: one byte saturates, two do not (an image of one pixel has no other)
     return comp, maps, img
 
 
-@pytest.mark.parametrize("where", ["host", "device", "host_odd", "device_odd", "device_aligned"])
+APPLY_WHERE = ["host", "device", "host_odd", "device_odd", "device_aligned"]
+
+
+def _apply_and_compare(comp, index, img, want, where, seed):
+    """apply(index) on a copy of img as `where` says: exactly `want`; in a guard band, the image's bytes and nothing beside them."""
+    if where == "host":
+        a = img.copy()
+        assert comp.apply(index, (0, 0), a) is a and np.array_equal(a, want)
+    elif where == "device":
+        t = _dev(img)
+        comp.apply(index, (0, 0), t, None)
+        assert np.array_equal(_np(t), want)
+    else:
+        place, layout = where.split("_")
+        g = guarded.guarded_like(img, place, layout, seed)
+        comp.apply(index, (0, 0), g.view)
+        if place == "device":
+            import torch
+            torch.cuda.synchronize()
+        g.check()
+        assert np.array_equal(g.get(), want)
+
+
+@pytest.mark.parametrize("where", APPLY_WHERE)
 @pytest.mark.parametrize("name", sorted(APPLY))
 def test_apply(gpu, name, where):
     """Bit for bit the model's apply on the library's own maps; in a guard band, the image's bytes and nothing beside them."""
@@ -254,22 +448,7 @@ def test_apply(gpu, name, where):
         if index == 0:
             assert np.any((img.astype(F32) * M.gain_image(maps[0], img.shape[1], img.shape[0])[:, :, None]) > 255.5)      # saturates at 255
             assert want.max() == 255 and not np.array_equal(want, img)
-        if where == "host":
-            a = img.copy()
-            assert comp.apply(index, (0, 0), a) is a and np.array_equal(a, want)
-        elif where == "device":
-            t = _dev(img)
-            comp.apply(index, (0, 0), t, None)
-            assert np.array_equal(_np(t), want)
-        else:
-            place, layout = where.split("_")
-            g = guarded.guarded_like(img, place, layout, 3 + index)
-            comp.apply(index, (0, 0), g.view)
-            if place == "device":
-                import torch
-                torch.cuda.synchronize()
-            g.check()
-            assert np.array_equal(g.get(), want)
+        _apply_and_compare(comp, index, img, want, where, 3 + index)
 
 
 def test_apply_on_an_image_of_another_size(gpu):
@@ -282,6 +461,37 @@ def test_apply_on_an_image_of_another_size(gpu):
         comp.apply(1, (0, 0), t)
         assert np.array_equal(_np(t), M.apply_model(img, maps[1])), (w, h)
     assert np.array_equal(M.gain_image(maps[1], 3, 2), maps[1])
+
+
+@pytest.mark.parametrize("where", APPLY_WHERE)
+def test_apply_on_more_sizes(gpu, where):
+    """Images of another size than the one fed, bit for bit the model's apply on the library's own maps.  A map LARGER than the image - in x
+    only, in y only, in both, and larger in y but smaller in x - from one-pixel blocks on a 13 x 7 tile; every width around one and two
+    workgroups' 256 columns with every height around a workgroup's 16 rows, under a 3 x 2 map; maps one block wide and one block high
+    under sizes that cross a workgroup."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import fuzz_parity
+    c = fuzz_parity._kernel_consts("blocks_gain.hip")
+    assert EDGE_WIDTHS == [c["BA_PX"] * 64 * k + d for k in (1, 2) for d in (-1, 0, 1)] and EDGE_HEIGHTS == [4 * c["BA_ROWS"] + d for d in (-1, 0, 1)]
+    rng = np.random.default_rng(10)
+    comp, maps, _ = _fed("map_of_the_images_size")
+    mh, mw = maps[0].shape
+    assert (mw, mh) == (13, 7)
+    sizes = [(5, 7), (13, 3), (4, 3), (40, 3)]
+    assert [(w < mw, h < mh) for w, h in sizes] == [(True, False), (False, True), (True, True), (False, True)] and sizes[3][0] > mw
+    runs = [(comp, maps, 0, sizes)]
+    comp, maps, _ = _fed("map_3x2")
+    runs.append((comp, maps, 1, [(w, h) for w in EDGE_WIDTHS for h in EDGE_HEIGHTS]))
+    for name in ("map_1_wide_5_high", "map_5_wide_1_high"):
+        comp, maps, _ = _fed(name)
+        assert maps[0].shape == ((5, 1) if name == "map_1_wide_5_high" else (1, 5))
+        runs.append((comp, maps, 0, [(257, 17), (3, 50), (50, 3), (1, 1)]))
+    for comp, maps, index, sizes in runs:
+        for k, (w, h) in enumerate(sizes):
+            img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+            want = M.apply_model(img, maps[index])
+            assert w * h < 64 or not np.array_equal(want, img)
+            _apply_and_compare(comp, index, img, want, where, 70 + k)
 
 
 # ---- the call surface ------------------------------------------------------------------------------------------------------------------------
@@ -343,6 +553,48 @@ def test_feed_refuses_a_capturing_stream_and_apply_is_captured_and_replayed(gpu)
         torch.cuda.synchronize()
         want = M.apply_model(want, maps[0])
         assert float(x[0]) == k + 1.0 and np.array_equal(_np(tile), want), k
+
+
+def test_a_captured_apply_replays_under_a_later_feed_of_the_same_sizes(gpu):
+    """The contract of isx_blocks_gain_apply: a graph captured before a later feed of images of the same sizes reads that feed's maps.
+    What the captured launch keeps: the maps' device buffer plus the image's offset in it, the map's width, and the resize tables.  The
+    buffer holds at most BG_MAX_BLOCKS = 16384 floats and DevBuf::reserve rounds every allocation up to 1 MiB, so it is allocated by the
+    first feed and never again; the offset and width are those of the block grids, which equal sizes give again; the tables are kept
+    until destroy.  (After a feed of OTHER sizes the captured offset and width are stale: outside the contract, not replayed here.)
+    Also the copy path (one-pixel blocks, no tables at all)."""
+    import torch
+    for name, other, blocks in (("two_tiles", "dark_against_bright", (32, 32)), ("one_pixel_blocks", None, (1, 1))):
+        corners, imgs, masks, _ = cases.case(name)
+        imgs2 = cases.case(other)[1] if other else [(255 - a // 2).astype(np.uint8) for a in imgs]
+        assert [a.shape for a in imgs2] == [a.shape for a in imgs] and not np.array_equal(imgs2[0], imgs[0])
+        s = torch.cuda.Stream()
+        comp = gpu.BlocksGainCompensator(*blocks, stream=s)
+        with torch.cuda.stream(s):
+            comp.feed(corners, imgs, masks)
+            tile = _dev(imgs[0])
+        torch.cuda.synchronize()
+        maps1 = comp.gain_maps()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=s, capture_error_mode="relaxed"):
+            comp.apply(0, corners[0], tile)
+        torch.cuda.synchronize()
+        assert np.array_equal(_np(tile), imgs[0])                  # captured, not run
+        g.replay()
+        torch.cuda.synchronize()
+        assert np.array_equal(_np(tile), M.apply_model(imgs[0], maps1[0]))
+        with torch.cuda.stream(s):
+            comp.feed(corners, imgs2, masks)                       # the same sizes and corners, other exposures
+        torch.cuda.synchronize()
+        maps2 = comp.gain_maps()
+        assert maps2[0].shape == maps1[0].shape
+        want1, want2 = M.apply_model(imgs[0], maps1[0]), M.apply_model(imgs[0], maps2[0])
+        assert not np.array_equal(want1, want2)                    # the two feeds are told apart by the tile
+        with torch.cuda.stream(s):
+            tile.copy_(torch.from_numpy(imgs[0]))
+        torch.cuda.synchronize()
+        g.replay()
+        torch.cuda.synchronize()
+        assert np.array_equal(_np(tile), want2), name
 
 
 # ---- end to end ------------------------------------------------------------------------------------------------------------------------------

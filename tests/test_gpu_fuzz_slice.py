@@ -1,8 +1,9 @@
-"""A 20-second, fixed-seed slice of tools/fuzz_parity.py (the randomised HIP-vs-oracle sweep over every entry point, 24 families: warps, the
+"""A 20-second, fixed-seed slice of tools/fuzz_parity.py (the randomised HIP-vs-oracle sweep over every entry point, 25 families: warps, the
 fused tile kernel, the blenders in all precisions and cycles, mask preparation, the seam finder, the linear pair blend, whole pairs through
 PairStitcher, and - against their NumPy models - the plane projector, GainCompensator::feed, the Voronoi and graph-cut seam finders and
-the COLOR_GRAD cost with seam_gradients) under -m gpu, then 8 seconds of the last five families alone, whose shape classes sit on their
-kernels' tiling constants.  The long soaks are kept as JSON summaries under profiles/."""
+the COLOR_GRAD cost with seam_gradients, and BlocksGainCompensator) under -m gpu, then 8 seconds of the five families before the last
+alone, whose shape classes sit on their kernels' tiling constants, and 4 seconds of the last, BlocksGainCompensator's.  The long soaks are
+kept as JSON summaries under profiles/."""
 import os
 import sys
 
@@ -33,10 +34,22 @@ def test_fuzz_slice_new_families(gpu):
     assert out["skipped_geometries"] * 10 <= out["cases"], (out["skipped_geometries"], out["cases"])
 
 
+def test_fuzz_slice_blocks_gain(gpu):
+    """BlocksGainCompensator's family alone: feed (statistics, gains, maps) and apply over its seven shape classes."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "tools"))
+    import fuzz_parity
+    out = fuzz_parity.run(4.0, 20261018, verbose=True, only=["case_blocks_gain"])
+    print(out["per_family"], "skipped", out["skipped_geometries"])
+    assert out["mismatches"] == 0, out["failing_seeds"]
+    assert list(out["per_family"]) == ["case_blocks_gain"] and out["cases"] >= 5 and out["skipped_geometries"] == 0, out
+
+
 # seeds the soaks have tripped over, kept as cases of their own (family, seed):
 #   case_many_tiles 20260988784363 - round 5: 35 tiles in mode 2, two bands; one column strip of the cycle took k_collapse_gather (16-byte level-1
 #   records, produced again on its columns), its neighbour read a shared tile's planar level 1 from feed() behind it
-REGRESSIONS = [("case_many_tiles", 20260988784363)]
+#   case_blocks_gain 20261078783058 - three tiles that all meet: isx_blocks_gain_stats gave the records image pair by image pair, not by (block_i, block_j)
+REGRESSIONS = [("case_many_tiles", 20260988784363), ("case_blocks_gain", 20261078783058)]
 
 
 @pytest.mark.parametrize("family,seed", REGRESSIONS)

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from helpers import blocks_gain_np as BG  # noqa: E402
 from helpers import dpseam_grad_np as M  # noqa: E402
 from helpers import graphcut_np as GC  # noqa: E402
 from helpers import guarded as G  # noqa: E402
@@ -743,6 +744,81 @@ def test_gain_compensator_feed_takes_inputs_only(gpu, where, layout):
         assert np.array_equal(comp.N, N) and np.array_equal(comp.I.view(np.uint64), I.view(np.uint64))
         np.testing.assert_allclose(comp.gains(), g, rtol=1e-12, atol=0)
         unchanged(*gi, *gm)
+
+
+# ---- BlocksGainCompensator ---------------------------------------------------------------------------------------------------------------
+_blocks_gain = {}
+
+
+def blocks_gain_case():
+    """The two tiles of the finder rows (67 x 17 and 65 x 21) in blocks of 32 x 8: 3 x 3 blocks each; the model, and a rtol of the gains by the
+    forward-error rule of tests/blocks_gain_cases.py.  Computed once per module."""
+    if "case" not in _blocks_gain:
+        from blocks_gain_cases import forward_error_rtol      # (tools/fuzz_parity.py's bg_forward_error_rtol)
+        corners, imgs, masks = small_layout(2, 1)
+        for m in masks:
+            m[::3, ::5] = 254                                        # not 255: outside the counts
+        model = BG.feed_blocks_model(corners, imgs, masks, 32, 8)
+        assert model["counts"] == [(3, 3), (3, 3)] and len(model["pairs"]) > 4
+        _blocks_gain["case"] = (corners, imgs, masks, model, forward_error_rtol(model["A"], model["b"], model["gains"])[0])
+    return _blocks_gain["case"]
+
+
+def blocks_gain_fed(gpu):
+    """One handle fed with blocks_gain_case(), for the rows that only read it."""
+    if "fed" not in _blocks_gain:
+        corners, imgs, masks, _, _ = blocks_gain_case()
+        comp = gpu.BlocksGainCompensator(32, 8).feed(corners, imgs, masks)
+        _blocks_gain["fed"] = (comp, comp.gain_maps())
+    return _blocks_gain["fed"]
+
+
+@pytest.mark.parametrize("layout", LAYOUTS)
+@pytest.mark.parametrize("where", WHERE + ("mixed",))
+def test_blocks_gain_feed_takes_inputs_only(gpu, where, layout):
+    """isx_blocks_gain_feed: the images and the masks are inputs."""
+    corners, imgs, masks, model, rtol = blocks_gain_case()
+    res = [("device" if k == 1 else "host") if where == "mixed" else where for k in range(2)]
+    gi = [gin(a, r, layout, "image%d" % k) for k, (a, r) in enumerate(zip(imgs, res))]
+    gm = [gin(m, r, layout, "mask%d" % k) for k, (m, r) in enumerate(zip(masks, res))]
+    comp = gpu.BlocksGainCompensator(32, 8).feed(corners, [x.view for x in gi], [x.view for x in gm])
+    sync()
+    pairs, diag = comp.block_stats()
+    assert comp.block_counts() == model["counts"] and np.array_equal(diag, model["diag_n"])
+    assert [(int(p["block_i"]), int(p["block_j"]), int(p["n"])) for p in pairs] == [p[:3] for p in model["pairs"]]
+    assert np.array_equal(pairs["i_ij"].view(np.uint64), np.array([p[3] for p in model["pairs"]]).view(np.uint64))
+    assert np.array_equal(pairs["i_ji"].view(np.uint64), np.array([p[4] for p in model["pairs"]]).view(np.uint64))
+    np.testing.assert_allclose(comp.gains(), model["gains"], rtol=rtol, atol=0)
+    unchanged(*gi, *gm)
+
+
+@pytest.mark.parametrize("layout", LAYOUTS)
+@pytest.mark.parametrize("where", WHERE)
+def test_blocks_gain_apply_in_place(gpu, where, layout):
+    """isx_blocks_gain_apply: the 3 x 3 maps resized to every shape; the image's bytes are the model's and not one byte beside them."""
+    comp, gmaps = blocks_gain_fed(gpu)
+    rng = np.random.default_rng(15)
+    for k, (w, h) in enumerate(SHAPES):
+        img = img_u8(rng, h, w)
+        g = gin(img, where, layout, "image")
+        comp.apply(k % 2, (0, 0), g.view)
+        sync()
+        equal(g, BG.apply_model(img, gmaps[k % 2]), (w, h))
+        g.check()
+
+
+@pytest.mark.parametrize("layout", LAYOUTS)
+@pytest.mark.parametrize("where", WHERE)
+def test_blocks_gain_map(gpu, where, layout):
+    """isx_blocks_gain_map: the smoothed map into the caller's CV_32FC1 mat."""
+    comp, _ = blocks_gain_fed(gpu)
+    counts = comp.block_counts()
+    for i, want in enumerate(BG.maps_from_gains(comp.gains(), counts)):
+        d = gout(want.shape, np.float32, where, layout, "map")
+        _lib.check(_lib.load().isx_blocks_gain_map(comp._h, i, ref(d), None))
+        sync()
+        equal(d, want, i)
+        d.check()
 
 
 # ---- image files ---------------------------------------------------------------------------------------------------------------------

@@ -835,7 +835,7 @@ def _kernel_consts(name):
     return out
 
 
-_VR, _GC, _GF, _SM = (_kernel_consts(n) for n in ("voronoi.hip", "graphcut.hip", "gain.hip", "seam.hip"))
+_VR, _GC, _GF, _SM, _BG = (_kernel_consts(n) for n in ("voronoi.hip", "graphcut.hip", "gain.hip", "seam.hip", "blocks_gain.hip"))
 SEAM_GAP = 10                                                           # the gap of OpenCV's pairwise seam finders: grids are roi + 2 * gap a side
 VR_WIDTHS = [_VR["VR_CHUNK"] - 1, _VR["VR_CHUNK"], _VR["VR_CHUNK"] + 1, 2 * _VR["VR_CHUNK"], 2 * _VR["VR_CHUNK"] + 1]      # of a submask
 VR_HEIGHTS = [_VR["VR_SEG"] - 1, _VR["VR_SEG"], _VR["VR_SEG"] + 1, 2 * _VR["VR_SEG"], 2 * _VR["VR_SEG"] + 1]
@@ -852,6 +852,12 @@ GAIN_CLASSES = ["plain", "pair_item_edge", "diag_item_edge", "one_pixel_overlap"
 VORONOI_CLASSES = ["plain", "chunk_edge", "seg_edge", "thin", "no_unique_rows"]
 GRAPHCUT_CLASSES = ["plain", "tile_edge_w", "tile_edge_h", "flat_tie", "holes_heavy"]
 SEAM_GRAD_CLASSES = ["plain", "tile_edge", "one_pixel", "rect_at_border", "find"]          # the first four: seam_gradients; "find": the whole finder
+BLOCKS_GAIN_CLASSES = ["plain", "several_items", "wide_row", "one_pixel_blocks", "no_pairs", "one_pixel_meeting", "apply_edges"]
+BG_WIDE_ROWS = [_GF["GF_PAIR_PIXELS"] + d for d in (-1, 0, 1, 5)]          # the width of a pair of blocks whose band is one row
+BG_APPLY_WIDTHS = [_BG["BA_PX"] * 64 * k + d for k in (1, 2) for d in (-1, 0, 1)]      # a workgroup of k_blocks_gain_apply: a wave of BA_PX pixels a lane wide,
+BG_APPLY_HEIGHTS = [4 * _BG["BA_ROWS"] + d for d in (-1, 0, 1)]                        # its four waves BA_ROWS rows each high
+BG_MAX_UNKNOWNS = 250                                                     # the dense model is O(B^2) in Python; below LU_NT and LU_PNT: one column block of
+assert BG_MAX_UNKNOWNS < _BG["LU_NT"] <= _BG["LU_PNT"] and _BG["LU_RB"] > 0                # k_lu_update, one stride of k_lu_pivot (larger: the solver's own test)
 WHERE = ["host", "device", "host_view", "device_view"]
 
 
@@ -1250,12 +1256,169 @@ def case_seam_grad(rng):
             (name, c["cls"], c["rect"], np.argwhere(a != b)[:3])
 
 
+# ---- BlocksGainCompensator ------------------------------------------------------------------------------------------------------------------
+def _bg_counts(sizes, blw, blh):
+    return sum(-(-w // blw) * -(-h // blh) for w, h in sizes)
+
+
+def _bg_fit(sizes, blw, blh):
+    """The block size grown (the axis with more blocks first) until the tiles hold at most BG_MAX_UNKNOWNS blocks."""
+    while _bg_counts(sizes, blw, blh) > BG_MAX_UNKNOWNS:
+        if max(-(-w // blw) for w, _ in sizes) >= max(-(-h // blh) for _, h in sizes):
+            blw += 1 + blw // 4
+        else:
+            blh += 1 + blh // 4
+    return blw, blh
+
+
+def bg_bands(width, height, item_size):
+    """The heights of the bands a record of width x height is cut into: max(1, item_size / width) rows each, the last one what is left."""
+    band = max(1, item_size // width)
+    return [min(band, height - y) for y in range(0, height, band)]
+
+
+def bg_record_items(corners, sizes, bl_width, bl_height, diag_bytes, pair_pixels):
+    """(diag, pairs): per block (width, height, band heights), and the same per pair of blocks of different images whose rectangles meet, by
+    block_i, then block_j - all pairs against all, on Python integers."""
+    from helpers import blocks_gain_np
+    rects, owner = [], []
+    for k, ((cx, cy), (w, h)) in enumerate(zip(corners, sizes)):
+        for x, y, bw, bh in blocks_gain_np.block_rects(w, h, bl_width, bl_height):
+            rects.append((cx + x, cy + y, bw, bh)); owner.append(k)
+    diag = [(w, h, bg_bands(w, h, diag_bytes)) for _, _, w, h in rects]
+    pairs = []
+    for i, (xi, yi, wi, hi) in enumerate(rects):
+        for j in range(i + 1, len(rects)):
+            xj, yj, wj, hj = rects[j]
+            w, h = min(xi + wi, xj + wj) - max(xi, xj), min(yi + hi, yj + hj) - max(yi, yj)
+            if owner[i] != owner[j] and w > 0 and h > 0:
+                pairs.append((w, h, bg_bands(w, h, pair_pixels)))
+    return diag, pairs
+
+
+def bg_forward_error_rtol(A, b, gains):
+    """(rtol, measured): rtol = min(1e-9, 4 max(measured, B 2^-52 cond_1(A))) with `measured` the largest relative difference between
+    np.linalg.solve (gains) and the NumPy hal::LU on the B x B system - the textbook forward-error scale of a backward-stable solve, from the
+    model alone.  Where the two CPU solves agree to the last bit (measured = 0) the device, whose back substitution adds in another order, is
+    still owed the rounding of its own operations."""
+    from helpers import blocks_gain_np
+    x, _ = blocks_gain_np.hal_lu_solve(A, b)
+    measured = float(np.max(np.abs(x - gains) / np.abs(gains)))
+    bound = len(b) * 2.0 ** -52 * float(np.linalg.cond(A, 1))
+    return min(1e-9, 4 * max(measured, bound)), measured
+
+
+def gen_blocks_gain(rng):
+    """1..4 tiles under masks of 0 / 254 / 255, a block size, and one or two images to apply the maps to (of a fed size or not).  The class
+    says what the case reaches: records of several work items of gain.hip, a pair of blocks whose band is one row about GF_PAIR_PIXELS
+    wide, one-pixel blocks (the maps have the images' sizes), no pair of blocks that meet, one shared pixel, or an applied image on the
+    edges of k_blocks_gain_apply's workgroup.  At most BG_MAX_UNKNOWNS blocks."""
+    cls = _pick(rng, BLOCKS_GAIN_CLASSES + ["plain", "several_items"])      # (the two that carry the most arithmetic: twice as likely)
+    x0, y0 = int(rng.integers(-40, 40)), int(rng.integers(-30, 30))
+    blw, blh = int(rng.integers(6, 65)), int(rng.integers(6, 65))
+    if cls == "several_items":
+        blw, blh = int(rng.integers(96, 257)), int(rng.integers(96, 257))
+        while True:                                                      # (large tiles that overlap widely: most draws do at once)
+            sizes = [(int(rng.integers(130, 400)), int(rng.integers(130, 300))) for _ in range(int(rng.integers(2, 4)))]
+            corners = [(x0 + int(rng.integers(-30, 60)) * k, y0 + int(rng.integers(-20, 40)) * k) for k in range(len(sizes))]
+            diag, pairs = bg_record_items(corners, sizes, blw, blh, _GF["GF_DIAG_BYTES"], _GF["GF_PAIR_PIXELS"])
+            if any(len(b) >= 2 for _, _, b in diag + pairs):
+                break
+    elif cls == "wide_row":
+        corners, sizes = _pair_with_overlap(rng, _pick(rng, BG_WIDE_ROWS), int(rng.integers(1, 5)))
+        blw, blh = max(w for w, _ in sizes) + int(rng.integers(0, 100)), int(rng.integers(1, 33))
+    elif cls == "one_pixel_blocks":
+        blw = blh = 1
+        corners, sizes = [(x0, y0)], [(int(rng.integers(1, 11)), int(rng.integers(1, 9)))]
+        for _ in range(int(rng.integers(1, 3))):
+            _tile_onto(rng, corners, sizes, (1, 11), (1, 9))
+    elif cls == "no_pairs":
+        corners, sizes = [], []
+        for k in range(int(rng.integers(1, 4))):                         # left to right, a gap of 0 (they touch and do not meet) or more
+            sizes.append((int(rng.integers(8, 160)), int(rng.integers(6, 120))))
+            corners.append((x0, y0 + int(rng.integers(-5, 6))))
+            x0 += sizes[-1][0] + int(rng.integers(0, 3))
+    elif cls == "one_pixel_meeting":
+        sizes = [(int(rng.integers(8, 160)), int(rng.integers(6, 120))) for _ in range(2)]
+        corners = [(x0, y0), (x0 + sizes[0][0] - 1, y0 + sizes[0][1] - 1)]
+    else:
+        corners, sizes = [(x0, y0)], [(int(rng.integers(8, 160)), int(rng.integers(6, 120)))]
+        if cls == "apply_edges":                                         # any block shape: a map of more rows or columns than the applied image too
+            blw, blh = int(rng.integers(1, 65)), int(rng.integers(1, 65))
+            sizes = [(int(rng.integers(8, 80)), int(rng.integers(6, 60)))]
+        for _ in range(int(rng.integers(1, 4))):
+            _tile_onto(rng, corners, sizes, (8, 80) if cls == "apply_edges" else (8, 160), (6, 60) if cls == "apply_edges" else (6, 120))
+    blw, blh = _bg_fit(sizes, blw, blh)
+    imgs, masks = [], []
+    for w, h in sizes:
+        imgs.append(rng.integers(int(rng.integers(0, 80)), int(rng.integers(120, 257)), (h, w, 3), dtype=np.uint8))
+        masks.append(rng.choice(np.array([0, 254, 255, 255, 255, 255], np.uint8), size=(h, w)))
+    if cls == "one_pixel_meeting":                                      # the shared pixel counts on both sides
+        masks[0][-1, -1] = masks[1][0, 0] = 255
+    apply = []
+    for k in range(int(rng.integers(1, 3))):
+        index = int(rng.integers(0, len(sizes)))
+        w, h = sizes[index]
+        if cls == "apply_edges":
+            while (w, h) == sizes[index]:
+                edge = int(rng.integers(0, 3))                           # the width, the height, or both on an edge
+                w = _pick(rng, BG_APPLY_WIDTHS) if edge != 1 else int(rng.integers(1, 600))
+                h = _pick(rng, BG_APPLY_HEIGHTS) if edge != 0 else int(rng.integers(1, 60))
+        elif (k == 1 or rng.integers(0, 2)) and w * h < (1 << 17):
+            w, h = int(rng.integers(1, 300)), int(rng.integers(1, 100))
+        apply.append((index, rng.integers(0, 256, (h, w, 3), dtype=np.uint8)))
+    return dict(cls=cls, corners=corners, sizes=sizes, imgs=imgs, masks=masks, blocks=(blw, blh), apply=apply, where=_pick(rng, WHERE),
+                view_seed=int(rng.integers(0, 5)))
+
+
+def model_blocks_gain(c):
+    from helpers import blocks_gain_np
+    m = blocks_gain_np.feed_blocks_model(c["corners"], c["imgs"], c["masks"], *c["blocks"])
+    rtol, measured = bg_forward_error_rtol(m["A"], m["b"], m["gains"])
+    return dict(counts=m["counts"], diag_n=m["diag_n"], pairs=m["pairs"], gains=m["gains"], rtol=rtol, measured=measured)
+
+
+def case_blocks_gain(rng):
+    """isx_blocks_gain_feed / _map / _apply against tests/helpers/blocks_gain_np.py: the block counts, N exactly, I bit for bit, the gains
+    to bg_forward_error_rtol (from the model alone), the maps bit for bit the model's smoothing of the
+    library's gains, apply bit for bit in place; nothing written around a view, nor into a fed one."""
+    from helpers import blocks_gain_np
+    import torch
+    c = gen_blocks_gain(rng)
+    want = model_blocks_gain(c)
+    fed = _place(c["imgs"], c["where"], c["view_seed"]) + _place(c["masks"], c["where"], c["view_seed"] + 1)
+    n = len(c["imgs"])
+    comp = G.BlocksGainCompensator(*c["blocks"]).feed(c["corners"], [p[0] for p in fed[:n]], [p[0] for p in fed[n:]])
+    assert comp.block_counts() == want["counts"], (c["cls"], comp.block_counts(), want["counts"])
+    pairs, diag = comp.block_stats()
+    assert np.array_equal(diag, want["diag_n"]), (c["cls"], diag, want["diag_n"])
+    assert [(int(p["block_i"]), int(p["block_j"]), int(p["n"])) for p in pairs] == [p[:3] for p in want["pairs"]], c["cls"]
+    for k, field in ((3, "i_ij"), (4, "i_ji")):
+        assert np.array_equal(pairs[field].view(np.uint64), np.array([p[k] for p in want["pairs"]], np.float64).view(np.uint64)), (c["cls"], field)
+    g = comp.gains()
+    np.testing.assert_allclose(g, want["gains"], rtol=want["rtol"], atol=0)
+    maps = comp.gain_maps()
+    for got, m in zip(maps, blocks_gain_np.maps_from_gains(g, want["counts"])):
+        assert got.dtype == np.float32 and got.shape == m.shape and np.array_equal(got.view(np.uint32), m.view(np.uint32)), c["cls"]
+    for p, a in zip(fed, c["imgs"] + c["masks"]):
+        assert np.array_equal(_host(p[0]), a), (c["cls"], "feed wrote a mat")
+    _frame_untouched(fed)
+    for k, (index, img) in enumerate(c["apply"]):
+        placed = _place([img], c["where"], c["view_seed"] + 2 + k)
+        comp.apply(index, c["corners"][index], placed[0][0])
+        torch.cuda.synchronize()
+        w = blocks_gain_np.apply_model(img, maps[index])
+        got = _host(placed[0][0])
+        assert np.array_equal(got, w), (c["cls"], index, img.shape, maps[index].shape, np.argwhere(got != w)[:3])
+        _frame_untouched(placed)
+
+
 NEW_FAMILIES = ["case_plane_warp", "case_gain_feed", "case_voronoi", "case_graphcut", "case_seam_grad"]
 
 
 CASES = [case_warp, case_blend, case_feather, case_prep, case_seam, case_blend_float_and_many, case_pipeline, case_find, case_warp_fused,
          case_linear_pair, case_strip, case_strip_feather, case_batch, case_s16_tiles, case_round4_calls, case_many_tiles, case_fused_feed, case_round6_calls,
-         case_long_lived, case_plane_warp, case_gain_feed, case_voronoi, case_graphcut, case_seam_grad]
+         case_long_lived, case_plane_warp, case_gain_feed, case_voronoi, case_graphcut, case_seam_grad, case_blocks_gain]
 
 
 def run(budget, seed0, verbose=True, progress_path=None, only=None):
