@@ -2,7 +2,7 @@
 """The reference demo's post-registration stage on one pair of images, every step on the GPU through imagestitch_amd
 (needs an MI355X):
 
-    python examples/stitch_pair.py [left.bmp right.bmp] [--focal F] [--yaw RAD] [--warper cylindrical|spherical|plane] [--blend feather|multiband] [--out pano.bmp | pano.jpg]
+    python examples/stitch_pair.py [left.bmp right.bmp] [--focal F] [--yaw RAD] [--warper cylindrical|spherical|plane] [--blend feather|multiband] [--seam-megapix M] [--out pano.bmp | pano.jpg]
 
 Registration (features, matching, bundle adjustment — out of scope of this library) is replaced by a known rig: two cameras
 with focal length F rotated by -/+ yaw about the vertical axis.  Without input files a synthetic pair is generated.
@@ -11,7 +11,8 @@ Steps = the reference's main(): warp image + mask (W:223-233), gain apply with g
 --estimate-gains, the compensator's feed on the warped tiles (W:238-240) and its apply (W:241-244): --compensator gain is the
 GainCompensator the demos create, gain_blocks the BlocksGainCompensator of createDefault(GAIN_BLOCKS) -, convertTo(CV_32F) +
 DP seam finder (S:87-1093, --seam-cost color_grad: DpSeamFinder::COLOR_GRAD W:255; --seam graphcut: W's own GraphCutSeamFinder, W:257-264; --seam voronoi: the VoronoiSeamFinder S constructs, S:1180), dilate 20x20 & warped mask (W:286-301), FeatherBlender 0.1 (W:278-313) or the
-multi-band blender (W:271-273), imwrite (W:315)."""
+multi-band blender (W:271-273), imwrite (W:315).  --seam-megapix M finds the seams at reduced scale the way OpenCV's stitching_detailed
+does: resize, small warp, finder, then dilate 3x3 + resize + AND per tile at compose time (isx.resize, isx.dilate_resize_and)."""
 import argparse
 import os
 import sys
@@ -44,6 +45,11 @@ def main():
                          "S:1180 on masks_seam (S:1192), masks only")
     ap.add_argument("--seam-cost", default="color", choices=["color", "color_grad"],
                     help="--seam dp: the finder's cost function, DpSeamFinder::COLOR (W:253) or DpSeamFinder::COLOR_GRAD (W:255, S:1183)")
+    ap.add_argument("--seam-megapix", type=float, default=0.0,
+                    help="find the seams at reduced scale, as OpenCV's stitching_detailed does (its default: 0.1): the sources are resized by "
+                         "seam_scale = min(1, sqrt(M * 1e6 / (W * H))) (isx.resize), warped with K and the warper's scale times seam_scale, the finder "
+                         "runs on the small tiles, and dilate_resize_and(small seam mask, full warped mask, 3, 3) replaces the 20 x 20 dilate.  "
+                         "0 (the default): off, the seams are found at full size")
     ap.add_argument("--out", default="pano.bmp")
     ap.add_argument("--separate", action="store_true",
                     help="gain apply and mask preparation as passes of their own (isx_gain_apply, isx_mask_dilate_and) instead of folded into the warp's "
@@ -79,15 +85,35 @@ def main():
             print("estimated gains of %d blocks: %.9f to %.9f" % (g.size, g.min(), g.max()))
         else:
             print("estimated gains", " ".join("%.9f" % v for v in g))
-    seam = [m.copy() for m in wmasks]                                       # W:247-249
-    if a.seam == "graphcut":                                                # W:257-264 as written: find edits masks_warped, and the
-        isx.GraphCutSeamFinder(isx.seam.COST_COLOR).find(                   # blender gets dilate(masks_seam) & masks_warped (W:286-301)
-            [w.astype(np.float32) for w in warped], corners, wmasks)
-    elif a.seam == "voronoi":
-        isx.VoronoiSeamFinder().find(warped, corners, seam)                 # S:1180, S:1192 as written: find edits masks_seam
+    def find(tiles, tile_corners, masks):                                  # the chosen finder, masks edited in place
+        if a.seam == "graphcut":
+            isx.GraphCutSeamFinder(isx.seam.COST_COLOR).find([w.astype(np.float32) for w in tiles], tile_corners, masks)   # W:257-264
+        elif a.seam == "voronoi":
+            isx.VoronoiSeamFinder().find(tiles, tile_corners, masks)        # S:1180, S:1192
+        else:
+            cost = isx.DP_COLOR_GRAD if a.seam_cost == "color_grad" else isx.DP_COLOR
+            isx.DpSeamFinder(cost).find([w.astype(np.float32) for w in tiles], tile_corners, masks)   # W:253 / W:255, W:259-262
+
+    if a.seam_megapix > 0:
+        # OpenCV's stitching_detailed / Stitcher::composePanorama: the seams are found on sources resized to seam_megapix and warped with
+        # K and the warper's scale multiplied by the same factor; the small seam masks come back to full size in the compose loop below
+        seam_scale = min(1.0, float(np.sqrt(a.seam_megapix * 1e6 / (W * H))))
+        small = [isx.resize(im, fx=seam_scale, fy=seam_scale) for im in imgs]
+        Ks = K.copy()
+        for r, c in ((0, 0), (0, 2), (1, 1), (1, 2)):
+            Ks[r, c] = np.float32(Ks[r, c] * np.float32(seam_scale))
+        small_warper = creator().create(float(np.float32(F) * np.float32(seam_scale)))
+        small_corners, small_warped, seam = [], [], []
+        for i in range(2):
+            c, wi, wm = small_warper.warp_with_mask(small[i], Ks, Rs[i])
+            small_corners.append(tuple(c)); small_warped.append(wi); seam.append(wm)
+        find(small_warped, small_corners, seam)
+        print("seam scale %.4f: sources %d x %d, warped tiles %s" % (seam_scale, small[0].shape[1], small[0].shape[0], [(w.shape[1], w.shape[0]) for w in small_warped]))
     else:
-        cost = isx.DP_COLOR_GRAD if a.seam_cost == "color_grad" else isx.DP_COLOR
-        isx.DpSeamFinder(cost).find([w.astype(np.float32) for w in warped], corners, seam)   # W:253 / W:255, W:259-262
+        seam = [m.copy() for m in wmasks]                                   # W:247-249
+        # graphcut, W:257-264 as written: find edits masks_warped, and the blender gets dilate(masks_seam) & masks_warped (W:286-301);
+        # the S demo's finders edit masks_seam (S:1192)
+        find(warped, corners, wmasks if a.seam == "graphcut" else seam)
     sizes = [(w.shape[1], w.shape[0]) for w in warped]
     if a.blend == "feather":
         blender = isx.FeatherBlender(False, 0.1)                            # W:278-280
@@ -95,7 +121,10 @@ def main():
         blender = isx.MultiBandBlender(False, 4, isx.PREC_I16)              # W:271-273
     blender.prepare(corners, sizes)                                         # W:281
     for i in range(2):
-        if a.separate:
+        if a.seam_megapix > 0:                                              # dilate(seam, Mat()); resize(.., mask_warped.size()); & mask_warped
+            mk = isx.dilate_resize_and(seam[i], wmasks[i], 3, 3)
+            blender.feed(warped[i].astype(np.int16), mk, corners[i])        # W:294, W:302
+        elif a.separate:
             mk = isx.dilate_and(seam[i], 20, 20, other=wmasks[i])           # W:295-301
             blender.feed(warped[i].astype(np.int16), mk, corners[i])        # W:294, W:302
         else:                                                               # W:294-302 in one call

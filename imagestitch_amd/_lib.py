@@ -100,6 +100,8 @@ _SIGS = {
     "isx_blocks_gain_stats": [C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong)],
     "isx_blocks_gain_feed_times": [C.c_void_p, C.POINTER(C.c_double)],
     "isx_convert_to": [_MP, _MP, C.c_int, C.c_void_p],
+    "isx_resize": [_MP, _MP, C.c_int, C.c_int, C.c_void_p],
+    "isx_mask_dilate_resize_and": [_MP, _MP, C.c_int, C.c_int, _MP, C.c_int, C.c_void_p],
     "isx_graphcut_seam_find": [C.c_int, _MP, C.POINTER(C.c_int), _MP, C.c_int, C.c_int, C.c_void_p],
     "isx_graphcut_seam_find_pair": [_MP, _MP, C.POINTER(C.c_int), _MP, _MP, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_int),
                                     C.POINTER(C.c_ubyte), C.c_longlong, C.POINTER(C.c_int), C.c_int, C.c_void_p],

@@ -1,6 +1,6 @@
 // blocks_gain_host.hpp — the host arithmetic of BlocksGainCompensator (blocks_gain.hip) in plain C++, so that it also builds into a
 // stand-alone program under the host compiler's sanitizers (tests/cpp/blocks_gain_host.cpp): the block grid of an image, the overlapping
-// block pairs of two images by interval intersection, the smoothing of a gain map and the tables of cv::resize(INTER_LINEAR) on CV_32F.
+// block pairs of two images by interval intersection, the smoothing of a gain map and the tables of cv::resize(INTER_LINEAR) on CV_32F (their taps: resize_taps.hpp).
 // Restated from OpenCV 3.4.2 (stitching/src/exposure_compensate.cpp, imgproc/src/resize.cpp; neither is in the reference tree).
 // Compile with -ffp-contract=off: every float expression below is a rounded multiply, then a rounded add.  Internal, not part of the ABI.
 #pragma once
@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "pairwise.hpp"
+#include "resize_taps.hpp"
 
 namespace isx {
 
@@ -85,29 +86,14 @@ inline void smooth_gain_map(std::vector<float>& m, int ny, int nx) {
 }
 
 // ---- cv::resize(map, image.size(), 0, 0, INTER_LINEAR) on CV_32F: the tables -------------------------------------------------------------------
-// Columns: fx = (float)((dx + 0.5) scale - 0.5), sx = floor(fx), fx -= sx; sx < 0 -> sx = 0, fx = 0; sx >= src_w - 1 -> sx = src_w - 1, fx = 0;
-// h = S[sx] (1 - fx) + S[sx + 1] fx where sx + 1 < src_w, else S[sx].  Rows: the same fy, but fy is KEPT and the two row indices sy, sy + 1 are
-// each clamped to [0, src_h - 1]: g = h_sy0 (1 - fy) + h_sy1 fy.
-struct ColTap { int sx; float a1; };
-struct RowTap { int sy0, sy1; float fy; };
+// The taps are resize_taps.hpp's (col_tap, row_tap: what isx_resize computes per pixel): h = S[sx] (1 - fx) + S[sx + 1] fx where sx + 1 < src_w,
+// else S[sx]; g = h_sy0 (1 - fy) + h_sy1 fy.
 inline void resize_tables(int src_w, int src_h, int dst_w, int dst_h, std::vector<ColTap>& cols, std::vector<RowTap>& rows) {
-    const double scale_x = 1.0 / ((double)dst_w / src_w), scale_y = 1.0 / ((double)dst_h / src_h);
+    const double scale_x = resize_scale(src_w, dst_w), scale_y = resize_scale(src_h, dst_h);
     cols.resize((size_t)dst_w);
     rows.resize((size_t)dst_h);
-    for (int dx = 0; dx < dst_w; ++dx) {
-        float fx = (float)((dx + 0.5) * scale_x - 0.5);
-        int sx = (int)std::floor(fx);
-        fx -= (float)sx;
-        if (sx < 0) { sx = 0; fx = 0.f; }
-        if (sx >= src_w - 1) { sx = src_w - 1; fx = 0.f; }
-        cols[(size_t)dx] = ColTap{sx, fx};
-    }
-    for (int dy = 0; dy < dst_h; ++dy) {
-        float fy = (float)((dy + 0.5) * scale_y - 0.5);
-        const int sy = (int)std::floor(fy);
-        fy -= (float)sy;
-        rows[(size_t)dy] = RowTap{std::min(std::max(sy, 0), src_h - 1), std::min(std::max(sy + 1, 0), src_h - 1), fy};
-    }
+    for (int dx = 0; dx < dst_w; ++dx) cols[(size_t)dx] = col_tap(dx, scale_x, src_w);
+    for (int dy = 0; dy < dst_h; ++dy) rows[(size_t)dy] = row_tap(dy, scale_y, src_h);
 }
 
 }  // namespace isx

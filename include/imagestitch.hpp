@@ -15,6 +15,7 @@
 // With OpenCV available, define ISX_HAVE_OPENCV before including: isx::Mat then converts from / to cv::Mat
 // without copying (same data / rows / cols / type() / step).
 #pragma once
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <stdexcept>
@@ -258,6 +259,29 @@ inline void convertTo(const Mat& src, Mat& dst, int type, int device = 0) {
 inline void dilateAnd(const Mat& mask, int kw, int kh, const Mat* other, Mat& out, int device = 0) {
     out.create(mask.rows(), mask.cols(), ISX_8UC1);
     check(isx_mask_dilate_and(mask.c(), other ? other->c() : nullptr, kw, kh, out.c(), device, nullptr));
+}
+
+// cv::resize(src, dst, dsize, fx, fy, interpolation) as OpenCV's stitching_detailed / Stitcher::composePanorama call it to bring the sources
+// to seam_megapix (between W:264 and W:302 in the reference's flow): INTER_NEAREST or INTER_LINEAR on CV_8U / CV_32F, 1 or 3 channels
+// (isx_resize).  An empty dsize takes (cvRound(cols * fx), cvRound(rows * fy)), ties to even.
+inline void resize(const Mat& src, Mat& dst, Size dsize, double fx = 0, double fy = 0, int interpolation = INTER_LINEAR, int device = 0) {
+    if (dsize.width <= 0 || dsize.height <= 0) dsize = Size((int)std::nearbyint(src.cols() * fx), (int)std::nearbyint(src.rows() * fy));
+    if (dsize.width <= 0 || dsize.height <= 0) throw Exception(ISX_ERR_SIZE, "resize: empty dsize");
+    dst.create(dsize.height, dsize.width, src.type());
+    check(isx_resize(src.c(), dst.c(), interpolation, device, nullptr));
+}
+
+// The compose loop's mask of one tile in one launch (isx_mask_dilate_resize_and):
+//     dilate(masks_warped[i], dilated_mask, Mat());  resize(dilated_mask, seam_mask, mask_warped.size());  mask_warped = seam_mask & mask_warped;
+// out = resize(dilate(seam_mask, MORPH_RECT kw x kh), warped_mask.size(), INTER_LINEAR) & warped_mask; out may be warped_mask itself
+inline void dilateResizeAnd(const Mat& seam_mask, const Mat& warped_mask, Mat& out, int kw = 3, int kh = 3, int device = 0) {
+    out.create(warped_mask.rows(), warped_mask.cols(), ISX_8UC1);
+    check(isx_mask_dilate_resize_and(seam_mask.c(), warped_mask.c(), kw, kh, out.c(), device, nullptr));
+}
+// ... without the AND: resize(dilate(seam_mask, kw x kh), size, INTER_LINEAR)
+inline void dilateResizeAnd(const Mat& seam_mask, Size size, Mat& out, int kw = 3, int kh = 3, int device = 0) {
+    out.create(size.height, size.width, ISX_8UC1);
+    check(isx_mask_dilate_resize_and(seam_mask.c(), nullptr, kw, kh, out.c(), device, nullptr));
 }
 
 // cv::detail::DpSeamFinder as the reference restates it in-tree (S:60-1093): seam_finder->find(images_warped_f, corners, masks_seam)

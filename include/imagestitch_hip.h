@@ -442,6 +442,27 @@ int isx_blocks_gain_feed_times(const isx_blocks_gain* h, double* ms4);
  * saturate_cast (float: cvRound = round-half-even, NaN / overflow -> INT_MIN, then the clamp).  dst is caller-allocated.      */
 int isx_convert_to(const isx_mat* src, isx_mat* dst, int device, void* hip_stream);
 
+/* ---- seam finding at reduced scale: what OpenCV's stitching_detailed / Stitcher::composePanorama (3.4.2) put around the seam finder -------- */
+/* cv::resize(src, dst, dst.size(), 0, 0, interpolation): the sources resized to seam_megapix before the small warp and the finder (the
+ * reference's demos find their seams at full size, W:264; a caller with 4K tiles does not).  dst is caller-allocated, its rows / cols are the
+ * dsize.  interpolation: ISX_INTER_NEAREST or ISX_INTER_LINEAR (ISX_ERR_UNSUPPORTED otherwise); CV_8UC1, CV_8UC3, CV_32FC1, CV_32FC3
+ * (ISX_ERR_UNSUPPORTED otherwise), src and dst of one type (ISX_ERR_TYPE); an empty mat is ISX_ERR_SIZE.  Restated from OpenCV 3.4.2
+ * imgproc/src/resize.cpp, plain C++ path (tests/helpers/resize_np.py is the model): NEAREST takes min(floor(d * scale), n - 1);
+ * LINEAR is the 11-bit fixed point on CV_8U and float multiply-then-add on CV_32F, and the 2 x 2 area rule where src is exactly twice dst
+ * in BOTH directions.  Parity with OpenCV itself is unpinned (and IPP builds of OpenCV differ by +-1 on CV_8U linear).  Host or device mats,
+ * any pointer and pitch.  On device mats one launch, the taps computed in the kernel: nothing synchronises or uploads, and the call can be
+ * captured; with a host mat on a capturing stream ISX_ERR_STATE, nothing enqueued.                                    (between W:264 and W:302) */
+int isx_resize(const isx_mat* src, isx_mat* dst, int interpolation, int device, void* hip_stream);
+/* The compose loop's mask, per tile, in one launch:
+ *     dilate(masks_warped[i], dilated_mask, Mat());  resize(dilated_mask, seam_mask, mask_warped.size());  mask_warped = seam_mask & mask_warped;
+ * out = resize(dilate(seam_mask, MORPH_RECT kw x kh), out.size(), INTER_LINEAR) & warped_mask.  seam_mask: CV_8UC1 at seam scale; warped_mask:
+ * CV_8UC1 of out's size (ISX_ERR_SIZE otherwise) or NULL = no AND; out: CV_8UC1, caller-allocated, may be warped_mask itself.  The dilate is
+ * isx_mask_dilate_and's (anchor (kw / 2, kh / 2), outside pixels take no part, 1 <= kw, kh <= 4096 else ISX_ERR_INVALID; 3 x 3 is
+ * dilate(.., Mat())), the resize isx_resize's CV_8U arithmetic, the AND bitwise: the result keeps the grey ramp of the resize, which is what
+ * OpenCV feeds.  Byte for byte isx_mask_dilate_and(seam_mask, NULL) -> isx_resize -> AND; no intermediate mat at either scale.  Capturable
+ * on device mats, as isx_resize.                                                                                   (between W:264 and W:302) */
+int isx_mask_dilate_resize_and(const isx_mat* seam_mask, const isx_mat* warped_mask, int kw, int kh, isx_mat* out, int device, void* hip_stream);
+
 /* ---- DP seam finder, its data-parallel part (S = 动态规划法寻找最佳缝合线.cpp) ------------------------- */
 /* estimateSeam(image1, image2, tl1, tl2, comp, p1, p2, seam, isHorizontal) S:806-957 incl. computeCosts S:733-803
  * (costFunc_ COLOR, what `new DpSeamFinder(DpSeamFinder::COLOR)` W:253 / S:71-72 runs; isx_seam_estimate_cost below takes
