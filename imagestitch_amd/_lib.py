@@ -229,7 +229,9 @@ def as_mat(a):
         if a.dim() == 2 and a.stride(1) != 1:
             raise IsxError(1, "tensor rows must be dense")
         dev = a.device.index if a.is_cuda else -1
-        return IsxMat(a.data_ptr(), a.shape[0], a.shape[1], _NP_TYPES[key], a.stride(0) * es, dev if dev is not None else 0)
+        # (a single row has no pitch: NumPy and torch keep any stride for a dimension of length 1, the library wants at least a row's bytes)
+        step = a.stride(0) * es if a.shape[0] > 1 else max(a.stride(0) * es, a.shape[1] * cn * es)
+        return IsxMat(a.data_ptr(), a.shape[0], a.shape[1], _NP_TYPES[key], step, dev if dev is not None else 0)
     import numpy as np
     a = np.asarray(a)
     cn = 1 if a.ndim == 2 else a.shape[2]
@@ -240,7 +242,8 @@ def as_mat(a):
         raise IsxError(1, "array must be HWC with dense pixels")
     if a.ndim == 2 and a.strides[1] != a.itemsize:
         raise IsxError(1, "array rows must be dense")
-    return IsxMat(a.ctypes.data, a.shape[0], a.shape[1], _NP_TYPES[key], a.strides[0], -1)
+    step = a.strides[0] if a.shape[0] > 1 else max(a.strides[0], a.shape[1] * cn * a.itemsize)
+    return IsxMat(a.ctypes.data, a.shape[0], a.shape[1], _NP_TYPES[key], step, -1)
 
 
 def profile_entries():

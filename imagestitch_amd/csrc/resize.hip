@@ -9,6 +9,7 @@
 #include "resize_taps.hpp"
 
 #include <algorithm>
+#include <cstdint>
 
 using namespace isx;
 using namespace isxd;
@@ -232,6 +233,20 @@ int not_empty(const isx_mat* m, const char* what) {
 // the launch grids count rows in 16 bits, and the byte offsets inside a row are ints
 constexpr int RZ_MAX_ROWS = 4 * 65535, RZ_MAX_COLS = 1 << 26;
 
+// Both kernels read neighbours of the pixel they write, so an output that lies over an input races.  A mat's bytes are taken as the one range
+// [data, data + (rows - 1) step + cols elemSize): two views whose rows interleave inside one buffer (side by side) count as sharing, views one
+// after the other do not.  Mats in different memories (host / device, two devices) share nothing.
+bool share_a_byte(const isx_mat* a, const isx_mat* b) {
+    if ((a->device < 0) != (b->device < 0) || (a->device >= 0 && a->device != b->device)) return false;
+    const uintptr_t a0 = (uintptr_t)a->data, a1 = a0 + (size_t)(a->rows - 1) * a->step + (size_t)a->cols * mat_elem_size(a->type);
+    const uintptr_t b0 = (uintptr_t)b->data, b1 = b0 + (size_t)(b->rows - 1) * b->step + (size_t)b->cols * mat_elem_size(b->type);
+    return a0 < b1 && b0 < a1;
+}
+// one view of one memory: every pixel at the same address (the pitch of a single row addresses nothing)
+bool same_view(const isx_mat* a, const isx_mat* b) {
+    return a->data == b->data && a->device == b->device && a->rows == b->rows && a->cols == b->cols && a->type == b->type && (a->step == b->step || a->rows == 1);
+}
+
 template <class T, int CN>
 int launch_resize(int mode, const isx_mat& s, const isx_mat& d, hipStream_t st) {
     const double bytes = ((double)d.rows * d.cols + (mode == RZ_NEAREST ? (double)d.rows * d.cols : (double)s.rows * s.cols)) * CN * sizeof(T);
@@ -261,6 +276,7 @@ int isx_resize(const isx_mat* src, isx_mat* dst, int interpolation, int device, 
     ISX_CHECK_ARG(dst->type == src->type, ISX_ERR_TYPE, "resize: dst is %s, src is %s", type_name(dst->type), type_name(src->type));
     ISX_CHECK_ARG(std::max(src->rows, dst->rows) <= RZ_MAX_ROWS && std::max(src->cols, dst->cols) <= RZ_MAX_COLS, ISX_ERR_UNSUPPORTED,
                   "resize: %d x %d -> %d x %d passes %d rows or %d columns", src->cols, src->rows, dst->cols, dst->rows, RZ_MAX_ROWS, RZ_MAX_COLS);
+    ISX_CHECK_ARG(!share_a_byte(src, dst), ISX_ERR_INVALID, "resize: dst shares bytes with src (the kernel reads the neighbours of the pixel it writes)");
     ISX_HIP(hipSetDevice(device));
     hipStream_t st = (hipStream_t)hip_stream;
     const bool any_host = src->device < 0 || dst->device < 0;
@@ -293,6 +309,10 @@ int isx_mask_dilate_resize_and(const isx_mat* seam_mask, const isx_mat* warped_m
     }
     ISX_CHECK_ARG(std::max(seam_mask->rows, out->rows) <= RZ_MAX_ROWS && std::max(seam_mask->cols, out->cols) <= RZ_MAX_COLS, ISX_ERR_UNSUPPORTED,
                   "%s: %d x %d -> %d x %d passes %d rows or %d columns", who, seam_mask->cols, seam_mask->rows, out->cols, out->rows, RZ_MAX_ROWS, RZ_MAX_COLS);
+    ISX_CHECK_ARG(!share_a_byte(seam_mask, out), ISX_ERR_INVALID, "%s: out shares bytes with seam_mask (the kernel reads the neighbours of the pixel it writes)", who);
+    // a lane reads the dword of warped_mask that it then writes: the same view is safe, a shifted one is not
+    ISX_CHECK_ARG(!warped_mask || same_view(warped_mask, out) || !share_a_byte(warped_mask, out), ISX_ERR_INVALID,
+                  "%s: out shares bytes with warped_mask and is not the same view of it (same data, step and size)", who);
     ISX_HIP(hipSetDevice(device));
     hipStream_t st = (hipStream_t)hip_stream;
     const bool any_host = seam_mask->device < 0 || out->device < 0 || (warped_mask && warped_mask->device < 0);

@@ -263,7 +263,7 @@ inline void dilateAnd(const Mat& mask, int kw, int kh, const Mat* other, Mat& ou
 
 // cv::resize(src, dst, dsize, fx, fy, interpolation) as OpenCV's stitching_detailed / Stitcher::composePanorama call it to bring the sources
 // to seam_megapix (between W:264 and W:302 in the reference's flow): INTER_NEAREST or INTER_LINEAR on CV_8U / CV_32F, 1 or 3 channels
-// (isx_resize).  An empty dsize takes (cvRound(cols * fx), cvRound(rows * fy)), ties to even.
+// (isx_resize).  An empty dsize takes (cvRound(cols * fx), cvRound(rows * fy)), ties to even.  dst must not share bytes with src (ISX_ERR_INVALID).
 inline void resize(const Mat& src, Mat& dst, Size dsize, double fx = 0, double fy = 0, int interpolation = INTER_LINEAR, int device = 0) {
     if (dsize.width <= 0 || dsize.height <= 0) dsize = Size((int)std::nearbyint(src.cols() * fx), (int)std::nearbyint(src.rows() * fy));
     if (dsize.width <= 0 || dsize.height <= 0) throw Exception(ISX_ERR_SIZE, "resize: empty dsize");
@@ -273,7 +273,8 @@ inline void resize(const Mat& src, Mat& dst, Size dsize, double fx = 0, double f
 
 // The compose loop's mask of one tile in one launch (isx_mask_dilate_resize_and):
 //     dilate(masks_warped[i], dilated_mask, Mat());  resize(dilated_mask, seam_mask, mask_warped.size());  mask_warped = seam_mask & mask_warped;
-// out = resize(dilate(seam_mask, MORPH_RECT kw x kh), warped_mask.size(), INTER_LINEAR) & warped_mask; out may be warped_mask itself
+// out = resize(dilate(seam_mask, MORPH_RECT kw x kh), warped_mask.size(), INTER_LINEAR) & warped_mask; out may be warped_mask itself (the same
+// view), but must not share bytes with seam_mask, nor lie over warped_mask in any other way (ISX_ERR_INVALID)
 inline void dilateResizeAnd(const Mat& seam_mask, const Mat& warped_mask, Mat& out, int kw = 3, int kh = 3, int device = 0) {
     out.create(warped_mask.rows(), warped_mask.cols(), ISX_8UC1);
     check(isx_mask_dilate_resize_and(seam_mask.c(), warped_mask.c(), kw, kh, out.c(), device, nullptr));

@@ -451,7 +451,11 @@ int isx_convert_to(const isx_mat* src, isx_mat* dst, int device, void* hip_strea
  * LINEAR is the 11-bit fixed point on CV_8U and float multiply-then-add on CV_32F, and the 2 x 2 area rule where src is exactly twice dst
  * in BOTH directions.  Parity with OpenCV itself is unpinned (and IPP builds of OpenCV differ by +-1 on CV_8U linear).  Host or device mats,
  * any pointer and pitch.  On device mats one launch, the taps computed in the kernel: nothing synchronises or uploads, and the call can be
- * captured; with a host mat on a capturing stream ISX_ERR_STATE, nothing enqueued.                                    (between W:264 and W:302) */
+ * captured; with a host mat on a capturing stream ISX_ERR_STATE, nothing enqueued.  At most 262140 rows and 2^26 columns a mat
+ * (ISX_ERR_UNSUPPORTED beyond).  dst must not share a byte with src (the kernel reads the neighbours of the pixel it writes): ISX_ERR_INVALID
+ * with nothing staged or enqueued where the ranges [data, data + (rows - 1) * step + cols * elemSize) of the two meet in one memory (both on
+ * the host, or both on one device) - which also turns down two views side by side in one buffer, whose rows interleave; views one after
+ * the other are fine.                                                                                              (between W:264 and W:302) */
 int isx_resize(const isx_mat* src, isx_mat* dst, int interpolation, int device, void* hip_stream);
 /* The compose loop's mask, per tile, in one launch:
  *     dilate(masks_warped[i], dilated_mask, Mat());  resize(dilated_mask, seam_mask, mask_warped.size());  mask_warped = seam_mask & mask_warped;
@@ -460,7 +464,10 @@ int isx_resize(const isx_mat* src, isx_mat* dst, int interpolation, int device, 
  * isx_mask_dilate_and's (anchor (kw / 2, kh / 2), outside pixels take no part, 1 <= kw, kh <= 4096 else ISX_ERR_INVALID; 3 x 3 is
  * dilate(.., Mat())), the resize isx_resize's CV_8U arithmetic, the AND bitwise: the result keeps the grey ramp of the resize, which is what
  * OpenCV feeds.  Byte for byte isx_mask_dilate_and(seam_mask, NULL) -> isx_resize -> AND; no intermediate mat at either scale.  Capturable
- * on device mats, as isx_resize.                                                                                   (between W:264 and W:302) */
+ * on device mats, as isx_resize, and with its limits.  out must not share a byte with seam_mask (isx_resize's rule and range test:
+ * ISX_ERR_INVALID, nothing staged or enqueued).  out may be warped_mask - the same view: same data, step and size, where a lane reads the
+ * dword it then writes - but an out that meets warped_mask's range in any other way (shifted, another pitch, a part of it) is
+ * ISX_ERR_INVALID too: a lane would read bytes that another has written.                                           (between W:264 and W:302) */
 int isx_mask_dilate_resize_and(const isx_mat* seam_mask, const isx_mat* warped_mask, int kw, int kh, isx_mat* out, int device, void* hip_stream);
 
 /* ---- DP seam finder, its data-parallel part (S = 动态规划法寻找最佳缝合线.cpp) ------------------------- */

@@ -107,6 +107,18 @@ def test_as_mat_and_enums():
     assert (m.rows, m.cols, m.type, m.step, m.device) == (5, 7, 16, 21, -1)
     m = _lib.as_mat(np.zeros((4, 6), np.float32)[:, :5])
     assert (m.cols, m.type, m.step) == (5, 5, 24)
+    # one row: NumPy keeps whatever stride the array's history left on a dimension of length 1 (here 3, on a C-contiguous array); the mat's
+    # step is a row's bytes (the fuzz family case_resize met this as "step 3 smaller than a row")
+    one = np.broadcast_to(np.zeros((1, 70, 1), np.int64), (1, 70, 3)).astype(np.uint8)
+    assert one.flags["C_CONTIGUOUS"] and one.strides[0] == 3
+    m = _lib.as_mat(one)
+    assert (m.rows, m.cols, m.step) == (1, 70, 210)
+    assert _lib.as_mat(np.zeros((1, 9), np.float32)).step == 36
+    try:
+        import torch
+        assert _lib.as_mat(torch.from_numpy(one)).step == 210
+    except ImportError:  # pragma: no cover
+        pass
     assert _lib.as_mat(np.zeros((2, 2, 3), np.int16)).type == 19 and _lib.as_mat(np.zeros((2, 2, 3), np.float32)).type == 21
     with pytest.raises(_lib.IsxError):
         _lib.as_mat(np.zeros((4, 6, 3), np.uint8)[:, :, ::-1])

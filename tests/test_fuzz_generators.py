@@ -1,5 +1,6 @@
 """The generator and model halves of the fuzz families tools/fuzz_parity.py has for the entry points merged after round 6 (the plane
-projector, GainCompensator::feed, the Voronoi and graph-cut seam finders, COLOR_GRAD and seam_gradients, BlocksGainCompensator), without a GPU: every shape
+projector, GainCompensator::feed, the Voronoi and graph-cut seam finders, COLOR_GRAD and seam_gradients, BlocksGainCompensator, cv::resize with
+the scaled mask stage), without a GPU: every shape
 class of a family is drawn, every drawn case has the shape its class names - recomputed from the case itself, against the tiling
 constants read from the kernels' sources -, and the models stay busy on them: few skips, seams that cut, overlaps that count."""
 import os
@@ -14,7 +15,7 @@ import fuzz_parity as F  # noqa: E402
 from helpers import voronoi_np as V  # noqa: E402
 
 FAMILIES = {"plane_warp": F.PLANE_CLASSES, "gain_feed": F.GAIN_CLASSES, "voronoi": F.VORONOI_CLASSES, "graphcut": F.GRAPHCUT_CLASSES,
-            "seam_grad": F.SEAM_GRAD_CLASSES, "blocks_gain": F.BLOCKS_GAIN_CLASSES}
+            "seam_grad": F.SEAM_GRAD_CLASSES, "blocks_gain": F.BLOCKS_GAIN_CLASSES, "resize": F.RESIZE_CLASSES}
 GEN_SEEDS, MODEL_SEEDS = range(200), range(5000, 5030)
 
 
@@ -31,10 +32,12 @@ def test_the_constants_are_the_kernels():
     assert F.GF_PAIR_SIZES == [4095, 4096, 4097, 8192, 8193] and F.GF_DIAG_SIZES == [16383, 16384, 16385]
     assert F.GRAD_WIDTHS == [63, 64, 65, 129] and F.GRAD_HEIGHTS == [15, 16, 17, 33]
     assert F.SEAM_GAP == V.GAP == 10
-    assert [f.__name__ for f in F.CASES[-6:-1]] == F.NEW_FAMILIES and len(F.CASES) == 25
-    assert F.CASES[-1].__name__ == "case_blocks_gain"
+    assert [f.__name__ for f in F.CASES[-7:-2]] == F.NEW_FAMILIES and len(F.CASES) == 26
+    assert F.CASES[-2].__name__ == "case_blocks_gain" and F.CASES[-1].__name__ == "case_resize"
     assert F.BG_WIDE_ROWS == [4095, 4096, 4097, 4101] and F.BG_APPLY_WIDTHS == [255, 256, 257, 511, 512, 513] and F.BG_APPLY_HEIGHTS == [15, 16, 17]
     assert [F._BG[k] for k in ("BA_PX", "BA_ROWS", "LU_NT", "LU_RB", "LU_PNT")] == [4, 4, 256, 8, 1024] and F.BG_MAX_UNKNOWNS == 250
+    assert F.RZ_WAVE_WIDTHS == [255, 256, 257, 511, 512, 513] and F.RZ_ROW_HEIGHTS == [3, 4, 5, 7, 8, 9, 15, 16, 17, 31, 32, 33]
+    assert [F._RZ[k] for k in ("RZ_PX", "DR_ROWS", "RZ_MAX_ROWS")] == [4, 4, 262140] and F.RZ_MAX_SHAPE == (300, 1100)
 
 
 def check_plane_warp(c):
@@ -163,6 +166,39 @@ def check_blocks_gain(c):
             assert (w in F.BG_APPLY_WIDTHS or h in F.BG_APPLY_HEIGHTS) and (w, h) != c["sizes"][index]
 
 
+def check_resize(c):
+    src, (dw, dh) = c["src"], c["dsize"]
+    sh, sw = src.shape[:2]
+    assert (str(src.dtype), 1 if src.ndim == 2 else src.shape[2]) in F.RZ_TYPES and src.ndim in (2, 3) and c["interp"] in (0, 1)
+    assert 1 <= sh <= F.RZ_MAX_SHAPE[0] and 1 <= dh <= F.RZ_MAX_SHAPE[0] and 1 <= sw <= F.RZ_MAX_SHAPE[1] and 1 <= dw <= F.RZ_MAX_SHAPE[1]
+    st = c["stage"]
+    assert (st is not None) == (src.dtype == np.uint8 and src.ndim == 2)                 # the mask stage rides on every CV_8UC1 case
+    if st is not None:
+        assert st["element"] in F.RZ_ELEMENTS and st["mode"] in F.RZ_STAGE_MODES
+        assert st["warped"].shape == (dh, dw) and st["warped"].dtype == np.uint8 and np.isin(st["warped"], (0, 0x5a, 255)).all()
+    if c["cls"] == "wave_edge":
+        assert dw in F.RZ_WAVE_WIDTHS
+    if c["cls"] == "rows_edge":
+        assert dh in F.RZ_ROW_HEIGHTS
+    if c["cls"] == "half":
+        assert sw == 2 * dw and sh == 2 * dh
+    if c["cls"] == "half_one_axis":
+        assert (sw == 2 * dw) != (sh == 2 * dh)
+    if c["cls"] == "tiny_src":
+        assert min(sh, sw) <= 3
+    if c["cls"] == "steep":
+        for a, b in ((sh, dh), (sw, dw)):
+            assert 6 * min(a, b) <= max(a, b) <= 12 * min(a, b)
+    if c["cls"] == "specials":
+        if src.dtype == np.uint8:
+            assert np.isin(src, (0, 255)).all()
+        else:
+            bits = src.view(np.uint32)
+            assert np.isfinite(src).all()
+            if src.size >= 10:                                              # every kind: a denormal, a -0.0, FLT_MAX
+                assert (((bits & 0x7f800000) == 0) & ((bits & 0x007fffff) != 0)).any() and (bits == 0x80000000).any() and (src == np.float32(3.4028235e38)).any()
+
+
 @pytest.mark.parametrize("family", sorted(FAMILIES))
 def test_every_class_is_drawn_and_has_its_shape(family):
     gen, check = getattr(F, "gen_" + family), globals()["check_" + family]
@@ -182,11 +218,12 @@ def test_every_class_is_drawn_and_has_its_shape(family):
 def test_the_models_stay_busy(family):
     """30 cases through gen + model: at most 10 % skips; the seam finders' models change a mask in at least half of the cases that have
     masks (all of them, but for seam_grad's gradient half); at least half of the gain cases count an overlap (an off-diagonal N above 1,
-    the value an empty intersection gets), and at least half of the blocks-gain cases have an off-diagonal record with N above 1."""
+    the value an empty intersection gets), and at least half of the blocks-gain cases have an off-diagonal record with N above 1; the resize
+    family never skips, and at least half of its up-scaled byte cases (larger in both directions) come out with more than 2 distinct values."""
     if family == "graphcut":
         pytest.importorskip("scipy")
     gen, model = getattr(F, "gen_" + family), getattr(F, "model_" + family)
-    skips = busy = with_masks = 0
+    skips = busy = with_masks = upscaled = 0
     for seed in MODEL_SEEDS:
         c = gen(np.random.default_rng(seed))
         want = model(c)
@@ -196,6 +233,11 @@ def test_the_models_stay_busy(family):
         elif family == "gain_feed":
             N = want["N"]
             busy += bool((N - np.diag(np.diag(N)) > 1).any())
+        elif family == "resize":
+            assert want["out"].shape[:2] == c["dsize"][::-1] and (want["stage"] is None) == (c["stage"] is None)
+            if c["src"].dtype == np.uint8 and c["dsize"][0] > c["src"].shape[1] and c["dsize"][1] > c["src"].shape[0]:
+                upscaled += 1
+                busy += len(np.unique(want["out"] if want["stage"] is None else want["stage"])) > 2
         elif family == "blocks_gain":
             busy += any(p[2] > 1 for p in want["pairs"])
             if c["cls"] == "no_pairs":                                   # diag and b are the same sums: the quotient is exact
@@ -205,8 +247,11 @@ def test_the_models_stay_busy(family):
             masks = want[0] if family == "graphcut" else want
             busy += any((a != b).any() for a, b in zip(masks, c["masks"]))
     n = len(MODEL_SEEDS)
-    print(family, "skips", skips, "busy", busy, "of", with_masks if with_masks else n)
+    print(family, "skips", skips, "busy", busy, "of", with_masks or upscaled or n)
     assert skips * 10 <= n
+    if family == "resize":
+        assert skips == 0 and upscaled >= 3 and busy * 2 >= upscaled, (skips, busy, upscaled)
+        return
     if family in ("gain_feed", "blocks_gain"):
         assert busy * 2 >= n, (busy, n)
     elif family != "plane_warp":

@@ -3,7 +3,9 @@
     python tools/fuzz_parity.py [seconds] [seed] [summary.json]
 Every failure prints the seed of the case so that it can be replayed; exit code = number of failing cases.  With a third argument the
 summary (cases, seconds, seed, mismatches per family) is also written as JSON - the file kept under profiles/.
-tests/test_gpu_fuzz_slice.py runs run(20 s, fixed seed) under -m gpu."""
+tests/test_gpu_fuzz_slice.py runs run(20 s, fixed seed) under -m gpu.
+26 families (CASES); ISX_FUZZ_ONLY=case_a,case_b runs only those.  The last, case_resize: cv::resize and the scaled mask stage
+(isx_resize, isx_mask_dilate_resize_and) against tests/helpers/resize_np.py over the shape classes RESIZE_CLASSES."""
 import os
 import sys
 import time
@@ -859,6 +861,14 @@ BG_APPLY_HEIGHTS = [4 * _BG["BA_ROWS"] + d for d in (-1, 0, 1)]                 
 BG_MAX_UNKNOWNS = 250                                                     # the dense model is O(B^2) in Python; below LU_NT and LU_PNT: one column block of
 assert BG_MAX_UNKNOWNS < _BG["LU_NT"] <= _BG["LU_PNT"] and _BG["LU_RB"] > 0                # k_lu_update, one stride of k_lu_pivot (larger: the solver's own test)
 WHERE = ["host", "device", "host_view", "device_view"]
+_RZ = _kernel_consts("resize.hip")
+RESIZE_CLASSES = ["plain", "wave_edge", "rows_edge", "half", "half_one_axis", "tiny_src", "steep", "specials"]
+RZ_WAVE_WIDTHS = [_RZ["RZ_PX"] * 64 * k + d for k in (1, 2) for d in (-1, 0, 1)]          # of a destination: a wave of the resize kernels, RZ_PX pixels a lane
+RZ_ROW_HEIGHTS = [4 * k + d for k in (1, 2) for d in (-1, 0, 1)] + [4 * _RZ["DR_ROWS"] * k + d for k in (1, 2) for d in (-1, 0, 1)]      # a workgroup of k_resize (4 rows) and of
+RZ_MAX_SHAPE = (300, 1100)                                                # k_dilate_resize_and (4 waves of DR_ROWS rows); no mat of a case above this (rows, cols)
+RZ_TYPES = [("uint8", 1), ("uint8", 3), ("float32", 1), ("float32", 3)]
+RZ_ELEMENTS = [(3, 3), (1, 1), (2, 5), (20, 20), (4, 4)]
+RZ_STAGE_MODES = ["no_warped", "warped", "in_place"]
 
 
 def overlap_roi(tl1, tl2, sz1, sz2):
@@ -1413,12 +1423,143 @@ def case_blocks_gain(rng):
         _frame_untouched(placed)
 
 
+# ---- cv::resize and the scaled mask stage ---------------------------------------------------------------------------------------------------
+def rz_float_specials(rng, shape):
+    """Finite floats only: noise with patches and single values of +-0.0, +-1e-40, +-1.4e-45, +-FLT_MAX and +-1.0 (denormals in and out,
+    signed zeros, and - under the area rule - sums that overflow)."""
+    kinds = np.array([0.0, -0.0, 1e-40, -1e-40, 1.4e-45, -1.4e-45, 3.4028235e38, -3.4028235e38, 1.0, -1.0], np.float32)
+    a = (rng.standard_normal(shape) * 10.0 ** rng.uniform(-3, 3, shape)).astype(np.float32)
+    for _ in range(shape[0] * shape[1] // 6 + 1):
+        y, x = int(rng.integers(0, shape[0])), int(rng.integers(0, shape[1]))
+        a[y:y + int(rng.integers(1, 4)), x:x + int(rng.integers(1, 5))] = kinds[int(rng.integers(0, len(kinds)))]
+    single = rng.random(shape) < 0.1
+    a[single] = kinds[rng.integers(0, len(kinds), shape)][single]
+    a.flat[:len(kinds)] = kinds[:a.size]                               # (every kind, where the mat has room)
+    return a
+
+
+def rz_byte_pattern(rng, shape):
+    """0 / 255 only: constant, a one-pixel checkerboard, one-pixel stripes either way, or sparse 255s"""
+    y, x = np.indices(shape[:2])
+    kind = int(rng.integers(0, 6))
+    p = [np.zeros(shape[:2], np.int64), np.full(shape[:2], 255), ((x + y) & 1) * 255, (x & 1) * 255, (y & 1) * 255, (rng.random(shape[:2]) < 0.1) * 255][kind]
+    return np.broadcast_to(p.reshape(p.shape + (1,) * (len(shape) - 2)), shape).astype(np.uint8)
+
+
+def gen_resize(rng):
+    """One source of a type of RZ_TYPES and a destination size, both within RZ_MAX_SHAPE; the class names what the pair reaches: a
+    destination as wide as 1 or 2 waves +-1 or as high as 1 or 2 workgroups +-1 of either kernel, the area rule (both ratios exactly 2) or one
+    ratio of 2 alone, a source of 1..3 rows or columns, a ratio of 6..12 in a direction drawn per axis, or special values.  A CV_8UC1 case also
+    carries the mask stage on the same pair of sizes: an element, and a warped mask that is absent, given, or the output itself."""
+    cls = _pick(rng, RESIZE_CLASSES)
+    dtype, cn = _pick(rng, RZ_TYPES)
+    sh, sw = int(rng.integers(1, 121)), int(rng.integers(1, 201))
+    dh, dw = int(rng.integers(1, 151)), int(rng.integers(1, 301))
+    if cls == "wave_edge":
+        dw, dh = _pick(rng, RZ_WAVE_WIDTHS), int(rng.integers(1, 41))
+    elif cls == "rows_edge":
+        dh = _pick(rng, RZ_ROW_HEIGHTS)
+    elif cls == "half":
+        dh, dw = int(rng.integers(1, 81)), int(rng.integers(1, 251))
+        sh, sw = 2 * dh, 2 * dw
+    elif cls == "half_one_axis":
+        if rng.integers(0, 2):
+            sw = 2 * dw
+            sh += sh == 2 * dh
+        else:
+            sh = 2 * dh
+            sw += sw == 2 * dw
+    elif cls == "tiny_src":
+        axis = int(rng.integers(0, 3))                                  # rows, columns or both
+        sh = int(rng.integers(1, 4)) if axis != 1 else sh
+        sw = int(rng.integers(1, 4)) if axis != 0 else sw
+    elif cls == "steep":
+        small = int(rng.integers(1, RZ_MAX_SHAPE[0] // 12 + 1)), int(rng.integers(1, RZ_MAX_SHAPE[1] // 12 + 1))
+        big = tuple(int(rng.integers(6 * n, 12 * n + 1)) for n in small)
+        (sh, dh) = (small[0], big[0]) if rng.integers(0, 2) else (big[0], small[0])
+        (sw, dw) = (small[1], big[1]) if rng.integers(0, 2) else (big[1], small[1])
+    shape = (sh, sw, cn) if cn > 1 else (sh, sw)
+    if dtype == "uint8":
+        sparse = cls != "specials" and cn == 1 and bool(rng.integers(0, 2))             # a seam mask: 0 / 255 blobs with a few other values
+        if cls == "specials":
+            src = rz_byte_pattern(rng, shape)
+        elif sparse:
+            src = np.where(rng.random(shape) < 0.06, 255, 0).astype(np.uint8)
+            few = rng.random(shape) < 0.02
+            src[few] = rng.integers(1, 255, shape, dtype=np.uint8)[few]
+        else:
+            src = rng.integers(0, 256, shape, dtype=np.uint8)
+    elif cls == "specials":
+        src = rz_float_specials(rng, shape)
+    else:                                                                # either sign, magnitudes up to 1e6: a fused multiply-add would round differently
+        src = (rng.standard_normal(shape) * 10.0 ** rng.uniform(0, 6, shape)).astype(np.float32)
+    stage = None
+    if (dtype, cn) == ("uint8", 1):
+        warped = np.where(rng.random((dh, dw)) < 0.7, 255, 0).astype(np.uint8)
+        warped[rng.random((dh, dw)) < 0.1] = 0x5a
+        stage = dict(element=_pick(rng, RZ_ELEMENTS), mode=_pick(rng, RZ_STAGE_MODES), warped=warped)
+    return dict(cls=cls, src=src, dsize=(dw, dh), interp=int(rng.integers(0, 2)), stage=stage, where=_pick(rng, WHERE), view_seed=int(rng.integers(0, 5)))
+
+
+def model_resize(c):
+    from helpers import resize_np
+    want = dict(out=resize_np.resize(c["src"], c["dsize"], c["interp"]), stage=None)
+    if c["stage"] is not None:
+        st = c["stage"]
+        want["stage"] = resize_np.dilate_resize_and(c["src"], None if st["mode"] == "no_warped" else st["warped"], st["element"][0], st["element"][1], c["dsize"])
+    return want
+
+
+def _same_bits(got, want):
+    """bit for bit, but for NaNs: those by position"""
+    if got.dtype != want.dtype or got.shape != want.shape:
+        return False
+    if want.dtype != np.float32:
+        return np.array_equal(got, want)
+    ok = ~np.isnan(want)
+    return np.array_equal(np.isnan(got), ~ok) and np.array_equal(np.ascontiguousarray(got).view(np.uint32)[ok], np.ascontiguousarray(want).view(np.uint32)[ok])
+
+
+def case_resize(rng):
+    """isx_resize and, on CV_8UC1, isx_mask_dilate_resize_and against tests/helpers/resize_np.py, bit for bit; the inputs keep their bytes and
+    nothing is written around a view."""
+    c = gen_resize(rng)
+    want = model_resize(c)
+    src, dsize = c["src"], c["dsize"]
+    dshape = (dsize[1], dsize[0]) + src.shape[2:]
+    ps = _place([src], c["where"], c["view_seed"])
+    pd = _place([np.zeros(dshape, src.dtype)], c["where"], c["view_seed"] + 1)
+    G.resize(ps[0][0], dsize, interpolation=c["interp"], dst=pd[0][0])
+    got = _host(pd[0][0])
+    note = (c["cls"], str(src.dtype), src.shape, dsize, c["interp"], c["where"])
+    assert _same_bits(got, want["out"]), note + (np.argwhere(got != want["out"])[:3],)
+    assert _same_bits(_host(ps[0][0]), src), note + ("resize wrote its source",)
+    _frame_untouched(ps + pd)
+    if c["stage"] is None:
+        return None
+    st = c["stage"]
+    (kw, kh), mode = st["element"], st["mode"]
+    pw = _place([st["warped"]], c["where"], c["view_seed"] + 2)
+    po = pw if mode == "in_place" else _place([np.zeros(dshape, np.uint8)], c["where"], c["view_seed"] + 3)
+    if mode == "no_warped":
+        G.dilate_resize_and(ps[0][0], dsize, kw, kh, out=po[0][0])
+    else:
+        G.dilate_resize_and(ps[0][0], pw[0][0], kw, kh, out=po[0][0])
+    got = _host(po[0][0])
+    note += ((kw, kh), mode)
+    assert np.array_equal(got, want["stage"]), note + (int((got != want["stage"]).sum()), np.argwhere(got != want["stage"])[:3])
+    assert np.array_equal(_host(ps[0][0]), src), note + ("the stage wrote its seam mask",)
+    if mode != "in_place":
+        assert np.array_equal(_host(pw[0][0]), st["warped"]), note + ("the stage wrote its warped mask",)
+    _frame_untouched(ps + pw + (po if po is not pw else []))
+
+
 NEW_FAMILIES = ["case_plane_warp", "case_gain_feed", "case_voronoi", "case_graphcut", "case_seam_grad"]
 
 
 CASES = [case_warp, case_blend, case_feather, case_prep, case_seam, case_blend_float_and_many, case_pipeline, case_find, case_warp_fused,
          case_linear_pair, case_strip, case_strip_feather, case_batch, case_s16_tiles, case_round4_calls, case_many_tiles, case_fused_feed, case_round6_calls,
-         case_long_lived, case_plane_warp, case_gain_feed, case_voronoi, case_graphcut, case_seam_grad, case_blocks_gain]
+         case_long_lived, case_plane_warp, case_gain_feed, case_voronoi, case_graphcut, case_seam_grad, case_blocks_gain, case_resize]
 
 
 def run(budget, seed0, verbose=True, progress_path=None, only=None):
