@@ -3734,11 +3734,16 @@ static int blend_begin(isx_blender* b, isx_mat* dst, isx_mat* dst_mask, OutMat* 
     }
     ISX_HIP(hipSetDevice(b->device));
     ISX_TRY(b->st_out.use_out(dst, b->stream, "blend: dst"));
-    ISX_CHECK_ARG(b->st_out.d.step < (1u << 24) && (unsigned long long)b->st_out.d.step * dst->rows < (1ull << 32), ISX_ERR_UNSUPPORTED,
+    // The last step stores at 32-bit offsets y * step + x * px from the mats' origins, x a column of the mosaic: a window's origin lies
+    // win_x0 pixels to the left of the mat, so its offsets are that much larger.
+    const unsigned long long win_px = windowed ? (unsigned long long)b->win_x0 : 0ull;
+    const unsigned long long dst_px = dst->type == ISX_32FC3 ? 12 : (dst->type == ISX_8UC3 ? 3 : 6);
+    ISX_CHECK_ARG(b->st_out.d.step < (1u << 24) && (unsigned long long)b->st_out.d.step * dst->rows + win_px * dst_px < (1ull << 32), ISX_ERR_UNSUPPORTED,
                   "blend: dst of %zu bytes per row x %d rows exceeds the supported 4 GiB / 16 MiB per row", b->st_out.d.step, dst->rows);
     if (dst_mask) {
         ISX_TRY(b->st_outmask.use_out(dst_mask, b->stream, "blend: dst_mask"));
-        ISX_CHECK_ARG(b->st_outmask.d.step < (1u << 24), ISX_ERR_UNSUPPORTED, "blend: dst_mask row pitch %zu exceeds 16 MiB", b->st_outmask.d.step);
+        ISX_CHECK_ARG(b->st_outmask.d.step < (1u << 24) && (unsigned long long)b->st_outmask.d.step * dst->rows + win_px < (1ull << 32), ISX_ERR_UNSUPPORTED,
+                      "blend: dst_mask of %zu bytes per row x %d rows exceeds the supported 4 GiB / 16 MiB per row", b->st_outmask.d.step, dst->rows);
     }
     OutMat& o = *po;
     o.img = (unsigned char*)b->st_out.d.data; o.img_step = b->st_out.d.step; o.img_f32 = dst->type == ISX_32FC3 ? 1 : (dst->type == ISX_8UC3 ? 2 : 0);

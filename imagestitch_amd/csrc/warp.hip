@@ -1746,8 +1746,10 @@ int warp_one(isx_warper* w, const isx_mat* src, const isx_mat* src_mask, const f
         // k_warp_tile stores 12-byte runs at any alignment (a dense cv::Mat row need not start on a dword); the caller-mask kernel keeps its
         // dword stores for aligned rows
         const bool vec = ((uintptr_t)dd.data % 4 == 0) && (dd.step % 4 == 0) && ((uintptr_t)dm.data % 4 == 0) && (dm.step % 4 == 0);
-        ISX_CHECK_ARG(dd.step < (1u << 24) && dm.step < (1u << 24) && (unsigned long long)dd.step * dh < (1ull << 32), ISX_ERR_UNSUPPORTED,
-                      "warp_with_mask: destination larger than 4 GiB or 16 MiB per row");
+        // both destinations: the kernels store the mask at a 32-bit offset (24-bit multiply) as they do the image
+        ISX_CHECK_ARG(dd.step < (1u << 24) && dm.step < (1u << 24) && (unsigned long long)dd.step * dh < (1ull << 32) &&
+                      (unsigned long long)dm.step * dh < (1ull << 32), ISX_ERR_UNSUPPORTED,
+                      "warp_with_mask: destination image or mask larger than 4 GiB or 16 MiB per row");
         dim3 grid4(cdiv(dw, 256), cdiv(dh, 4));
         // sync path: the scan ran on this stream and the host has consumed its keys; the kernel re-arms them.
         // planned path: scan + check run on the side stream, nothing to do here.

@@ -154,7 +154,10 @@ int isx_warper_build_maps_roi(isx_warper* w, const float K[9], const float R[9],
 /* Point warp(src,K,R,interp,border,dst) (W:145-161; stock call sites B:105,109): buildMaps +
  * cv::remap (W:157) fused into one gather kernel; the maps are never written to HBM.
  * src: CV_8UC3 / CV_8UC1 (fixed-point bilinear) or CV_32FC3 / CV_32FC1 (float bilinear).
- * dst: caller-allocated, same type, (roi.h+1) x (roi.w+1) (W:150).  corner = roi.tl() (W:160). */
+ * dst: caller-allocated, same type, (roi.h+1) x (roi.w+1) (W:150).  corner = roi.tl() (W:160).
+ * Limits: none that refuses a mat.  The two calls the reference makes (CV_8UC3 LINEAR / REFLECT, CV_8UC1 NEAREST / CONSTANT) take the tile
+ * kernels while the source has step < 2^24 bytes, step * rows < 2^31 and at most 32767 pixels a side and the destination step < 2^24
+ * and step * rows < 2^32 (a host mat: its dense staged copy); any other mat takes the generic kernel (64-bit addresses), same bits. */
 int isx_warper_warp(isx_warper* w, const isx_mat* src, const float K[9], const float R[9],
                     int interp, int border, isx_mat* dst, int corner[2]);
 
@@ -170,7 +173,11 @@ int isx_warper_warp_with_mask_roi(isx_warper* w, const isx_mat* src_img, const i
 
 /* The two calls of W:229 + W:232 on one tile fused: image LINEAR/REFLECT and mask
  * NEAREST/CONSTANT in one pass over the destination.  src_mask may be NULL = all 255
- * (W:213-214).  dst_img may be CV_8UC3 or CV_16SC3 (= warp + convertTo(CV_16S), W:294).      */
+ * (W:213-214).  dst_img may be CV_8UC3 or CV_16SC3 (= warp + convertTo(CV_16S), W:294).
+ * Limits (this call, _roi, _planned and the batched form; there is no generic kernel behind them): src_img with step < 2^24 bytes,
+ * step * rows < 2^31 and at most 32767 pixels a side; dst_img AND dst_mask each with step < 2^24 and step * rows < 2^32 (host mats:
+ * their dense staged copies).  Past any of them: ISX_ERR_UNSUPPORTED, nothing is written - inside a batch the tile is not collected
+ * and the batch ends as for any failing warp.  src_mask (its size is src_img's) is read through 64-bit addresses: any pitch.      */
 int isx_warper_warp_with_mask(isx_warper* w, const isx_mat* src_img, const isx_mat* src_mask,
                               const float K[9], const float R[9],
                               isx_mat* dst_img, isx_mat* dst_mask, int corner[2]);
@@ -233,7 +240,8 @@ int isx_warper_verify_after(isx_warper* w, void* hip_event);
 
 /* cv::remap(src, dst, xmap, ymap, interp_mode, border_mode) itself (W:157), for callers that keep the maps of a
  * fixed rig (isx_warper_build_maps once, isx_remap per frame).  CV_32FC1 maps; src / dst CV_8UC1, CV_8UC3, CV_32FC1 or
- * CV_32FC3; OpenCV's CPU arithmetic (coordinates quantised to 1/32 pixel, 15-bit fixed-point weights for 8-bit images). */
+ * CV_32FC3; OpenCV's CPU arithmetic (coordinates quantised to 1/32 pixel, 15-bit fixed-point weights for 8-bit images).
+ * Limits: a source of more than 32767 pixels a side is ISX_ERR_UNSUPPORTED (cv::remap's short coordinates), dst untouched; any pitch. */
 int isx_remap(const isx_mat* src, const isx_mat* xmap, const isx_mat* ymap, int interp_mode, int border_mode,
               isx_mat* dst, int device, void* hip_stream);
 
@@ -251,13 +259,19 @@ int isx_blender_set_sharpness(isx_blender* b, float sharpness); /* fb->setSharpn
 
 /* blender->prepare(corners, sizes) (W:281): corners_xy = {x0,y0,x1,y1,...}, sizes_wh likewise */
 int isx_blender_prepare(isx_blender* b, int n, const int* corners_xy, const int* sizes_wh);
-/* MultiBandBlender::prepare(Rect dst_roi) */
+/* MultiBandBlender::prepare(Rect dst_roi).
+ * Limits (both forms): the ROI padded to a multiple of 2^num_bands must stay below 2^24 pixels a side and 2^31 pixels in all (records are
+ * indexed with 32 bits; Blender::NO and FEATHER: one level); beyond: ISX_ERR_UNSUPPORTED before anything is allocated.              */
 int isx_blender_prepare_roi(isx_blender* b, int x, int y, int width, int height);
 
 /* blender->feed(img [CV_16SC3], mask [CV_8U], tl) (W:302).  img may also be CV_32FC3 in
  * the F32 / F16ACC32 precisions, and CV_8UC3: OpenCV then takes createLaplacePyr's 8-bit branch,
  * whose numbers are those of the CV_16S branch on the converted image (bytes never saturate in
- * pyrDown / pyrUp) - the same path as isx_blender_feed_u8.                                        */
+ * pyrDown / pyrUp) - the same path as isx_blender_feed_u8.
+ * Limits (isx_blender_feed, _feed_u8, _feed_dilated): none that refuses a tile.  A CV_8UC3 / CV_16SC3 tile whose image and mask both have
+ * step < 2^24 bytes and step * rows < 2^31 is read with 32-bit offsets (the fused feed of mode 2, k_collapse_roll as the last step);
+ * any other tile through 64-bit addresses (mode 2: a plain private copy; the last step k_collapse_gather when the caller's mat itself
+ * is read) - same bits, isx_blender_feed_path / isx_blender_last_path say which.                 */
 int isx_blender_feed(isx_blender* b, const isx_mat* img, const isx_mat* mask, int tl_x, int tl_y);
 /* images_warped.convertTo(CV_16S) (W:261,294) fused into feed: img is CV_8UC3 and is widened
  * to int16 on load; results are identical to converting first and calling isx_blender_feed.   */
@@ -351,7 +365,10 @@ int isx_blender_set_narrow_copies(isx_blender* b, int on);
 /* blender->blend(result, result_mask) (W:313).  dst: CV_16SC3 (I16: exact; F32: saturate_cast
  * round-half-even), CV_32FC3 (F32/F16ACC32 only) or CV_8UC3 (= blend to CV_16SC3 followed by
  * result.convertTo(CV_8U), what imwrite (W:315) does to the panorama); dst_mask: CV_8UC1.  Releases the pyramids:
- * prepare must be called again before the next feed (as in OpenCV).                           */
+ * prepare must be called again before the next feed (as in OpenCV).
+ * Limits: dst AND dst_mask each need step < 2^24 bytes and step * rows < 2^32 (with a column window: plus the window's first column in
+ * bytes; host mats: their dense staged copies).  Past them: ISX_ERR_UNSUPPORTED, nothing is written and the blender stays prepared and
+ * fed - blend() into smaller-pitched mats then succeeds.  The same holds per blender in isx_blender_blend_batch.      */
 int isx_blender_blend(isx_blender* b, isx_mat* dst, isx_mat* dst_mask);
 /* blend() of n blenders at once - the per-image loop of the reference's main() (W:223-233, 285-302, 313) run for a BATCH of independent
  * mosaics (BASELINE configs 3 and 4: 16 / 4 pairs per step).  Blenders that are in the deferred cycle (isx_blender_set_deferred_level0)

@@ -136,6 +136,54 @@ def test_written_limits_the_view(dtype, cn, layout):
         g.check((10, w))
 
 
+# (layout, pitch or None = the layout's default, rows, on the fast side?) - every mat tests/test_gpu_addressing_limits.py builds
+WIDE_CASES = [("wide", None, 8, False), ("wide", (1 << 24) + 64, 24, False), ("wide_below", None, 8, True), ("wide_below", None, 24, True),
+              ("tall31", None, 255, True), ("tall31", None, 256, False), ("tall31", None, 257, False),
+              ("tall32", None, 511, True), ("tall32", None, 512, False), ("tall32", (1 << 24) - 64, 256, True), ("tall32", (1 << 24) - 64, 257, False)]
+
+
+@pytest.mark.parametrize("dtype,cn", TYPES)
+@pytest.mark.parametrize("layout,pitch,rows,fast", WIDE_CASES)
+def test_large_pitch_layout_arithmetic(layout, pitch, rows, fast, dtype, cn):
+    """tests/helpers/guarded_wide.py, its arithmetic only (no device): each layout's pitch and row count lie on the stated side of the
+    threshold it is named for, the view lies inside the buffer behind the lead and before the tail that keep a truncated, wrapped or
+    sign-extended offset inside the allocation, and its first byte and pitch are aligned for the element."""
+    from helpers import guarded_wide as W
+    es = np.dtype(dtype).itemsize
+    for w in (24, 40, 70):
+        p = W.plan((rows, w, cn) if cn > 1 else (rows, w), dtype, layout, pitch)
+        assert p.rows == rows and p.row_bytes == w * cn * es
+        if layout == "wide":
+            assert p.pitch >= 1 << 24 and p.pitch in (1 << 24, (1 << 24) + 64) and 8 <= rows <= 24
+        elif layout == "wide_below":
+            assert (1 << 24) - 64 <= p.pitch < 1 << 24 and (p.pitch == (1 << 24) - 4) == (es * cn == 1)
+        if layout.startswith("wide"):
+            assert (p.pitch < 1 << 24) == fast and p.pitch * rows < 1 << 31             # only the pitch is past a limit
+            assert p.nbytes <= 420 << 20                                                  # "about 400 MiB"
+        elif layout == "tall31":
+            assert p.pitch == 1 << 23 and (p.pitch * rows < 1 << 31) == fast
+            assert p.pitch * 255 < 1 << 31 and p.pitch * 256 == 1 << 31
+        else:
+            assert p.pitch < 1 << 24 and (p.pitch * rows < 1 << 32) == fast
+            if fast:
+                assert p.pitch * (rows + 1) >= 1 << 32                                   # the last row count on the fast side
+            assert p.pitch * rows >= 1 << 31                                             # past the sources' limit either way
+        # the view inside the buffer, behind the lead and before the tail
+        lead = (1 << 31) + (64 << 10) if layout.startswith("tall") else 64 << 10
+        assert p.offset >= lead and p.span == (rows - 1) * p.pitch + p.row_bytes
+        assert p.offset + p.span + (64 << 10) <= p.nbytes
+        if layout == "tall32":
+            assert p.nbytes >= p.offset + (1 << 32)
+        # every offset a fast kernel can get wrong stays inside: the step truncated to 24 bits, the sum wrapped at 2^32, the sum signed
+        last = p.span - 1
+        for wrong in ((rows - 1) * (p.pitch & 0xFFFFFF) + p.row_bytes - 1, last % (1 << 32), last % (1 << 32) - (1 << 32) if last % (1 << 32) >= 1 << 31 else 0):
+            assert 0 <= p.offset + wrong < p.nbytes, (layout, rows, wrong)
+        assert p.offset % 256 == 0 and p.offset % es == 0 and p.pitch % es == 0 and p.pitch % 4 == 0
+        assert W.bytes_needed((rows, w), dtype, layout, pitch) >= p.nbytes
+    with pytest.raises(AssertionError):
+        W.plan((8, 24), np.uint8, layout, 12345)                                          # no pitch but the layout's own
+
+
 def test_guarded_like_holds_the_array():
     a = np.random.default_rng(1).integers(0, 255, (3, 5, 3)).astype(np.int16)
     g = G.guarded_like(a, "host", "aligned", 4)
