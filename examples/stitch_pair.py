@@ -10,7 +10,7 @@ with focal length F rotated by -/+ yaw about the vertical axis.  Without input f
 Steps = the reference's main(): warp image + mask (W:223-233), gain apply with given gains (W:241-244) - or, with
 --estimate-gains, the compensator's feed on the warped tiles (W:238-240) and its apply (W:241-244): --compensator gain is the
 GainCompensator the demos create, gain_blocks the BlocksGainCompensator of createDefault(GAIN_BLOCKS) -, convertTo(CV_32F) +
-DP seam finder (S:87-1093, --seam-cost color_grad: DpSeamFinder::COLOR_GRAD W:255; --seam graphcut: W's own GraphCutSeamFinder, W:257-264; --seam voronoi: the VoronoiSeamFinder S constructs, S:1180), dilate 20x20 & warped mask (W:286-301), FeatherBlender 0.1 (W:278-313) or the
+DP seam finder (S:87-1093, --seam-cost color_grad: DpSeamFinder::COLOR_GRAD W:255; --seam graphcut: W's own GraphCutSeamFinder, W:257-264, with --seam-cost color_grad its COST_COLOR_GRAD, W:258; --seam voronoi: the VoronoiSeamFinder S constructs, S:1180), dilate 20x20 & warped mask (W:286-301), FeatherBlender 0.1 (W:278-313) or the
 multi-band blender (W:271-273), imwrite (W:315).  --seam-megapix M finds the seams at reduced scale the way OpenCV's stitching_detailed
 does: resize, small warp, finder, then dilate 3x3 + resize + AND per tile at compose time (isx.resize, isx.dilate_resize_and)."""
 import argparse
@@ -40,11 +40,12 @@ def main():
                     help="with --estimate-gains: ExposureCompensator::createDefault(GAIN), one gain per tile, or (GAIN_BLOCKS), one per 32 x 32 "
                          "block, applied as a smoothed gain map (W:238)")
     ap.add_argument("--seam", default="dp", choices=["dp", "graphcut", "voronoi"],
-                    help="dp: the DP seam finder on a copy of the warped masks (S:1192); graphcut: W's own GraphCutSeamFinder(COST_COLOR), "
+                    help="dp: the DP seam finder on a copy of the warped masks (S:1192); graphcut: W's own GraphCutSeamFinder(COST_COLOR) (or COST_COLOR_GRAD with --seam-cost color_grad), "
                          "which edits the warped masks while masks_seam stays their unedited copy (W:247-264); voronoi: the VoronoiSeamFinder of "
                          "S:1180 on masks_seam (S:1192), masks only")
     ap.add_argument("--seam-cost", default="color", choices=["color", "color_grad"],
-                    help="--seam dp: the finder's cost function, DpSeamFinder::COLOR (W:253) or DpSeamFinder::COLOR_GRAD (W:255, S:1183)")
+                    help="--seam dp: the finder's cost function, DpSeamFinder::COLOR (W:253) or DpSeamFinder::COLOR_GRAD (W:255, S:1183); "
+                         "--seam graphcut: GraphCutSeamFinder::COST_COLOR (W:257) or COST_COLOR_GRAD (W:258)")
     ap.add_argument("--seam-megapix", type=float, default=0.0,
                     help="find the seams at reduced scale, as OpenCV's stitching_detailed does (its default: 0.1): the sources are resized by "
                          "seam_scale = min(1, sqrt(M * 1e6 / (W * H))) (isx.resize), warped with K and the warper's scale times seam_scale, the finder "
@@ -87,7 +88,8 @@ def main():
             print("estimated gains", " ".join("%.9f" % v for v in g))
     def find(tiles, tile_corners, masks):                                  # the chosen finder, masks edited in place
         if a.seam == "graphcut":
-            isx.GraphCutSeamFinder(isx.seam.COST_COLOR).find([w.astype(np.float32) for w in tiles], tile_corners, masks)   # W:257-264
+            cost = isx.seam.COST_COLOR_GRAD if a.seam_cost == "color_grad" else isx.seam.COST_COLOR
+            isx.GraphCutSeamFinder(cost).find([w.astype(np.float32) for w in tiles], tile_corners, masks)   # W:257 / W:258, W:261-264
         elif a.seam == "voronoi":
             isx.VoronoiSeamFinder().find(tiles, tile_corners, masks)        # S:1180, S:1192
         else:

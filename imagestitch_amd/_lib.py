@@ -105,6 +105,8 @@ _SIGS = {
     "isx_graphcut_seam_find": [C.c_int, _MP, C.POINTER(C.c_int), _MP, C.c_int, C.c_int, C.c_void_p],
     "isx_graphcut_seam_find_pair": [_MP, _MP, C.POINTER(C.c_int), _MP, _MP, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_int),
                                     C.POINTER(C.c_ubyte), C.c_longlong, C.POINTER(C.c_int), C.c_int, C.c_void_p],
+    "isx_graphcut_seam_find_pair64": [_MP, _MP, C.POINTER(C.c_int), _MP, _MP, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                      C.POINTER(C.c_ubyte), C.c_longlong, C.POINTER(C.c_int), C.c_int, C.c_void_p],
     "isx_graphcut_seam_release": [],
     "isx_voronoi_seam_find": [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _MP, C.c_int, C.c_void_p],
     "isx_voronoi_seam_reserve": [C.c_int, C.c_int, C.c_int],

@@ -78,37 +78,44 @@ COST_COLOR, COST_COLOR_GRAD = 0, 1       # GraphCutSeamFinder::CostType
 
 
 class GraphCutSeamFinder:
-    """The stock seam finder of the reference's main(): GraphCutSeamFinder(GraphCutSeamFinder::COST_COLOR) (W:257), find at W:264.
+    """The stock seam finder of the reference's main(): GraphCutSeamFinder(GraphCutSeamFinder::COST_COLOR) (W:257), find at W:264, or
+    GraphCutSeamFinder(COST_COLOR_GRAD), the other graph cut every demo lists (W:258; CV_32FC3 tiles only).
     Every pair's max-flow runs on the GPU (isx_graphcut_seam_find); the cut is the maximal minimum cut."""
+
+    FLOW_SHIFT = 23                      # COST_COLOR_GRAD flows and residuals are in units of 2^-23
 
     def __init__(self, cost_type=COST_COLOR, device=0, stream=None):
         self.cost_type, self.device, self.stream = int(cost_type), device, stream
 
     def find(self, src, corners, masks):
-        """find(src, corners, masks): src = CV_32FC3 tiles holding integers in [0, 255] (W:261) or CV_8UC3 tiles, masks = CV_8U arrays /
-        tensors edited in place."""
+        """find(src, corners, masks): src = CV_32FC3 tiles holding integers in [0, 255] (W:261) or, with COST_COLOR only, CV_8UC3 tiles;
+        masks = CV_8U arrays / tensors edited in place."""
         n, mats_i, c, mats_m, ptr = tile_args(src, corners, masks, self.stream)
         check(_lib.load().isx_graphcut_seam_find(n, mats_i, c, mats_m, self.cost_type, int(self.device), ptr))
         return masks
 
-    def find_pair(self, image1, image2, tl1, tl2, mask1, mask2, certificate=False):
-        """One pair as find() treats it (masks edited in place).  Returns a dict: flow, rows, cols, rounds, launches and, with
-        certificate=True, residuals (rows x cols x 6 int32: right, left, down, up, source link, sink link) and labels (rows x cols
-        uint8, 1 = source side) - the layout of isx_graphcut_seam_find_pair."""
+    def find_pair(self, image1, image2, tl1, tl2, mask1, mask2, certificate=False, wide=False):
+        """One pair as find() treats it (masks edited in place).  Returns a dict: flow, flow_scale (1, or 1 << 23 with COST_COLOR_GRAD:
+        flow and residuals are multiples of 1 / flow_scale), rows, cols, rounds, launches and, with certificate=True, residuals (rows x
+        cols x 6: right, left, down, up, source link, sink link; int32 from isx_graphcut_seam_find_pair, int64 from
+        isx_graphcut_seam_find_pair64 with COST_COLOR_GRAD or wide=True) and labels (rows x cols uint8, 1 = source side)."""
+        wide = bool(wide) or self.cost_type == COST_COLOR_GRAD
         m1, m2, k1, k2 = as_mat(image1), as_mat(image2), as_mat(mask1), as_mat(mask2)
         c = (C.c_int * 4)(int(tl1[0]), int(tl1[1]), int(tl2[0]), int(tl2[1]))
         x0, y0 = max(tl1[0], tl2[0]), max(tl1[1], tl2[1])
         x1, y1 = min(tl1[0] + m1.cols, tl2[0] + m2.cols), min(tl1[1] + m1.rows, tl2[1] + m2.rows)
         nodes = max(0, y1 - y0 + 20) * max(0, x1 - x0 + 20) if (x0 < x1 and y0 < y1) else 0
-        res = np.zeros((max(nodes, 1), 6), np.int32) if certificate else None
+        res = np.zeros((max(nodes, 1), 6), np.int64 if wide else np.int32) if certificate else None
         lab = np.zeros(max(nodes, 1), np.uint8) if certificate else None
         flow, info = C.c_longlong(0), (C.c_int * 4)()
         ptr = getattr(self.stream, "cuda_stream", self.stream)
-        check(_lib.load().isx_graphcut_seam_find_pair(
+        entry = _lib.load().isx_graphcut_seam_find_pair64 if wide else _lib.load().isx_graphcut_seam_find_pair
+        check(entry(
             C.byref(m1), C.byref(m2), c, C.byref(k1), C.byref(k2), self.cost_type, C.byref(flow),
-            res.ctypes.data_as(C.POINTER(C.c_int)) if certificate else None, lab.ctypes.data_as(C.POINTER(C.c_ubyte)) if certificate else None,
-            nodes, info, int(self.device), C.c_void_p(ptr or 0)))
-        out = dict(flow=flow.value, rows=info[0], cols=info[1], rounds=info[2], launches=info[3])
+            res.ctypes.data_as(C.POINTER(C.c_longlong if wide else C.c_int)) if certificate else None,
+            lab.ctypes.data_as(C.POINTER(C.c_ubyte)) if certificate else None, nodes, info, int(self.device), C.c_void_p(ptr or 0)))
+        out = dict(flow=flow.value, flow_scale=1 << self.FLOW_SHIFT if self.cost_type == COST_COLOR_GRAD else 1, rows=info[0], cols=info[1],
+                   rounds=info[2], launches=info[3])
         if certificate:
             out["residuals"] = res[: info[0] * info[1]].reshape(info[0], info[1], 6)
             out["labels"] = lab[: info[0] * info[1]].reshape(info[0], info[1])

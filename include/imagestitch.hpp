@@ -309,7 +309,8 @@ private:
 
 // GraphCutSeamFinder(GraphCutSeamFinder::COST_COLOR) (W:257) and its find(images_warped_f, corners, masks_warped) (W:264): every pair's
 // max-flow on the GPU, the maximal minimum cut (isx_graphcut_seam_find).  src: CV_32FC3 tiles holding integers in [0, 255] or CV_8UC3;
-// masks: CV_8U, edited in place; host or device mats.
+// masks: CV_8U, edited in place; host or device mats.  GraphCutSeamFinder(COST_COLOR_GRAD) (W:258) weighs every edge by the tiles' Sobel
+// gradients as well (exact in 64-bit fixed point); it takes CV_32FC3 tiles only, as OpenCV's does.
 class GraphCutSeamFinder {
 public:
     enum CostType { COST_COLOR = ISX_GC_COST_COLOR, COST_COLOR_GRAD = ISX_GC_COST_COLOR_GRAD };

@@ -7,7 +7,8 @@
 // (DESIGN.md §8).  A header of its own, so that imagestitch_cv.hpp and the stub it is tested against stay as they were.
 //
 // Compiled inside the reference tree, where OpenCV 3.4.2 is installed; in this repository against tests/cpp/opencv_stub
-// (tests/cpp/graphcut_demo.cpp, run by tests/test_gpu_graphcut_seam.py; tests/cpp/voronoi_demo.cpp, run by tests/test_gpu_voronoi_seam.py;
+// (tests/cpp/graphcut_demo.cpp, run by tests/test_gpu_graphcut_seam.py; tests/cpp/graphcut_grad_demo.cpp, run by
+// tests/test_gpu_graphcut_grad.py; tests/cpp/voronoi_demo.cpp, run by tests/test_gpu_voronoi_seam.py;
 // tests/cpp/seam_grad_demo.cpp, run by tests/test_gpu_seam_grad.py).
 #ifndef IMAGESTITCH_CV_SEAM_HPP
 #define IMAGESTITCH_CV_SEAM_HPP
@@ -46,8 +47,8 @@ struct SeamArgs {
 };
 }  // namespace detail
 
-// cv::detail::GraphCutSeamFinder(cost_type)'s find over isx::GraphCutSeamFinder.  COST_COLOR only: COST_COLOR_GRAD throws
-// isx::Exception(ISX_ERR_UNSUPPORTED) from find, as does a CV_32FC3 value that is not an integer in [0, 255].
+// cv::detail::GraphCutSeamFinder(cost_type)'s find over isx::GraphCutSeamFinder, COST_COLOR or COST_COLOR_GRAD.  A CV_32FC3 value that is
+// not an integer in [0, 255] throws isx::Exception(ISX_ERR_UNSUPPORTED) from find, as do CV_8UC3 tiles with COST_COLOR_GRAD.
 class HipGraphCutSeamFinder : public cv::detail::SeamFinder {
 public:
     explicit HipGraphCutSeamFinder(int cost_type = cv::detail::GraphCutSeamFinderBase::COST_COLOR, int device = 0) : f_(cost_type, device) {}

@@ -549,8 +549,14 @@ enum { ISX_GC_COST_COLOR = 0, ISX_GC_COST_COLOR_GRAD = 1 };
  * is not unique OpenCV's Boykov-Kolmogorov search may choose another cut of the same cost.
  * images: n mats, all CV_32FC3 (W:261: convertTo of the byte tiles) or all CV_8UC3, host or device; CV_32FC3 values must be integers in
  * [0, 255] (then every capacity is an exact integer): any other value gives ISX_ERR_UNSUPPORTED before a mask is written.  masks: n CV_8UC1
- * mats of the images' sizes, host or device, edited in place.  cost_type ISX_GC_COST_COLOR; ISX_GC_COST_COLOR_GRAD gives
- * ISX_ERR_UNSUPPORTED.  Fewer than 2 images: nothing to do.  Synchronises hip_stream (it reads counters back every round), so a capturing
+ * mats of the images' sizes, host or device, edited in place.
+ * cost_type ISX_GC_COST_COLOR, or ISX_GC_COST_COLOR_GRAD (setGraphWeightsColorGrad; CV_32FC3 tiles only, CV_8UC3 tiles give
+ * ISX_ERR_UNSUPPORTED with the masks untouched): every edge weight becomes (|d(p)|^2 + |d(q)|^2) / grad + 1.f (+ 1000.f), grad = dx1(p) +
+ * dx1(q) + dx2(p) + dx2(q) + 1.f for a right edge and the same of dy for a down edge, dx_ / dy_ the squared norm over the three channels of
+ * the tile's 3 x 3 Sobel derivatives (BORDER_REFLECT_101 at the tile's edges, 0 outside the tile).  On integer tiles that float is a
+ * multiple of 2^-23, so the capacities are exact int64 in units of 2^-23 (Q23; terminals 10000 * 2^23) and the cut is as unique as
+ * COST_COLOR's.  A pair whose padded grid has more than 2^26 nodes gives ISX_ERR_UNSUPPORTED before anything is launched.
+ * Fewer than 2 images: nothing to do.  Synchronises hip_stream (it reads counters back every round), so a capturing
  * stream gives ISX_ERR_STATE.  A pair whose max-flow does not finish within 4096 rounds (16 push-relabel sweeps and a global relabel
  * each) gives ISX_ERR_UNSUPPORTED with that pair's masks untouched; the pairs before it keep their edits.                              */
 int isx_graphcut_seam_find(int num_images, const isx_mat* images, const int* corners_xy, isx_mat* masks, int cost_type, int device,
@@ -558,17 +564,24 @@ int isx_graphcut_seam_find(int num_images, const isx_mat* images, const int* cor
 /* One pair (images 1 and 2 at corners_xy[0..1] and corners_xy[2..3]) as isx_graphcut_seam_find treats it, optionally returning a
  * certificate of its maximum flow over the padded grid of rows x cols = info[0] x info[1] nodes (row-major, node (y, x) = grid row y,
  * column x; grid (10, 10) is the roi's top-left):
- *   flow       (may be NULL) the maximum flow value (without OpenCV's constant 10000 per node that has both masks)
+ *   flow       (may be NULL) the maximum flow value (without OpenCV's constant 10000 per node that has both masks); with
+ *              ISX_GC_COST_COLOR_GRAD in units of 2^-23
  *   residuals  (may be NULL, with labels) cert_nodes >= rows * cols records of 6 int32 per node: the residual capacities of its edges
  *              to the right, to the left, down, up (0 where the grid ends), of the source's link to it and of its link to the sink;
  *              every edge of weight w has r(u -> v) + r(v -> u) = 2 w
  *   labels     rows * cols bytes: 1 = source side (the maximal one), 0 = sink side
  *   info       (may be NULL) 4 ints: rows, cols, push-relabel rounds, kernel launches; all 0 when the tiles do not overlap
- * ISX_ERR_SIZE when cert_nodes is too small (nothing written). */
+ * ISX_ERR_SIZE when cert_nodes is too small (nothing written).  With ISX_GC_COST_COLOR_GRAD the residuals do not fit 32 bits: residuals
+ * must be NULL (ISX_ERR_INVALID otherwise); isx_graphcut_seam_find_pair64 returns them. */
 int isx_graphcut_seam_find_pair(const isx_mat* image1, const isx_mat* image2, const int* corners_xy, isx_mat* mask1, isx_mat* mask2,
                                 int cost_type, long long* flow, int* residuals, unsigned char* labels, long long cert_nodes, int* info,
                                 int device, void* hip_stream);
-/* The graph-cut finder keeps its graph (28 B per padded node on the device), counters and staged host mats per calling thread between
+/* isx_graphcut_seam_find_pair with 6 int64 residuals per node, same order, for either cost type: ISX_GC_COST_COLOR's are the int32 ones
+ * widened, ISX_GC_COST_COLOR_GRAD's are in units of 2^-23 (an edge of weight w has r(u -> v) + r(v -> u) = 2 * w * 2^23). */
+int isx_graphcut_seam_find_pair64(const isx_mat* image1, const isx_mat* image2, const int* corners_xy, isx_mat* mask1, isx_mat* mask2,
+                                  int cost_type, long long* flow, long long* residuals, unsigned char* labels, long long cert_nodes, int* info,
+                                  int device, void* hip_stream);
+/* The graph-cut finder keeps its graph (28 B per padded node on the device, 48 B with ISX_GC_COST_COLOR_GRAD), counters and staged host mats per calling thread between
  * calls; this returns them.  PER THREAD and not freed at thread exit, as for isx_dp_seam_release.                                      */
 int isx_graphcut_seam_release(void);
 
