@@ -35,6 +35,7 @@
 #include <cstdlib>
 #include <memory>
 #include <new>
+#include <type_traits>
 
 using namespace isx;
 using namespace isxd;
@@ -1450,8 +1451,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FINE0 ? (M 
 #include "collapse_top.inc"
 #include "collapse_top2.inc"
 
-template <int M, int SK>
-int launch_pyr_down0(const TileSet& ts, dim3 grid, double bytes, hipStream_t st, int planar = 0);
+// Layout of level 1 of a tile's pyramid in the deferred cycle (the values are isx_blender_level1_format's): 16-byte register records, PLANAR
+// (dense image records + a weight plane, load_px_planar), PLANAR with the image records in Q8.  The kernels' PLD / PLS template arguments.
+enum G1Format { G1_RECORDS = 0, G1_PLANAR = 1, G1_PLANAR_Q8 = 2 };
+
+// The process-wide switches of the blend's host code (A/B runs and the tests' child processes), read once.  Every one is on unless its variable's
+// first character is '0' - ISX_ROLL: unless atoi() of it is 0.  (ISX_TAB is not here: the tests flip it inside one process, run_blend reads it per call.)
+struct BlendSwitches { bool pd0, roll, out12, g1p, g1q8, feed_fuse, feed_narrow; };
+inline const BlendSwitches& switches() {
+    static const BlendSwitches sw = [] {
+        auto on = [](const char* e) { return !(e && e[0] == '0'); };
+        BlendSwitches s;
+        s.pd0 = on(getenv("ISX_PD0"));                  // level 0 -> 1 of the recorded tiles through k_pyr_down0 (off: the general kernel)
+        const char* roll = getenv("ISX_ROLL");          // the last collapse step as k_collapse_roll (off: k_collapse_gather)
+        s.roll = !(roll && atoi(roll) == 0);
+        s.out12 = on(getenv("ISX_OUT12"));              // out_1 in dense image records (OutMat::rec12)
+        s.g1p = on(getenv("ISX_G1P"));                  // level 1 of the tiles PLANAR
+        s.g1q8 = on(getenv("ISX_G1Q8"));                // ... in Q8 records
+        s.feed_fuse = on(getenv("ISX_FEED_FUSE"));      // mode 2: level 1 and the private copies out of one pass (k_feed_pd0)
+        s.feed_narrow = on(getenv("ISX_FEED_NARROW"));  // ... the copy of a CV_16SC3 tile written as CV_8UC3
+        return s;
+    }();
+    return sw;
+}
 
 // ---- host side of the tile tables (TileTab / TopTab) ---------------------------------------------------------------------------------------
 // DevTable: a device buffer that mirrors host-built tables.  Uploads travel in KERNEL ARGUMENTS (k_tab_write: 3.5 KB per launch) - in stream
@@ -1570,40 +1592,77 @@ inline int make_views(DevTable* tab, TabScratch* sc, hipStream_t st, int slot, s
     return ISX_OK;
 }
 
-// level 0 -> 1 of every recorded tile: CV_8UC3 and CV_16SC3 tiles through k_pyr_down0 (ISX_PD0=0: the general kernel, for A/B runs)
-// planar: level 1 is written as 12-byte image records + a weight plane (ts.coarse[t].wgt set by the caller; k_pyr_down0 only)
-template <int M, int SK>
-int launch_pyr_down0(const TileViews& v, dim3 grid, double bytes, hipStream_t st, int planar = 0) {      // planar: 0 records, 1 planar, 2 planar in Q8 records
-    if (!v.tab) return launch_pyr_down0<M, SK>(v.ts, grid, bytes, st, planar);
-    static const bool fast = [] { const char* e = getenv("ISX_PD0"); return !(e && e[0] == '0'); }();
-    if constexpr (SK == SK_U8 || SK == SK_S16) {
-        if constexpr (M == M_F32 && SK == SK_U8) {
-            if (planar == 2) { ISX_LAUNCH("pyr_down0", bytes, st, (k_pyr_down0_tab<M, SK, 2>), grid, dim3(512), 0, v.tt); return ISX_OK; }
-        }
-        ISX_CHECK_ARG(planar != 2, ISX_ERR_INTERNAL, "pyr_down0: Q8 records asked of a kernel that has none");
-        if constexpr (M == M_F32 || M == M_I16) {
-            if (planar) { ISX_LAUNCH("pyr_down0", bytes, st, (k_pyr_down0_tab<M, SK, 1>), grid, dim3(512), 0, v.tt); return ISX_OK; }
-        }
-        if (fast) { ISX_LAUNCH("pyr_down0", bytes, st, (k_pyr_down0_tab<M, SK>), grid, dim3(512), 0, v.tt); return ISX_OK; }
-    }
-    ISX_LAUNCH("pyr_down_l0", bytes, st, (k_pyr_down_multi_tab<M, SK>), grid, dim3(512), 0, v.tt, FeedPub{nullptr, 0, nullptr, 0});
+// A launch's tiles as its kernel takes them: f(TileSet) or f(TileTab)
+template <class F> int with_tiles(const TileViews& v, F f) { return v.tab ? f(v.tt) : f(v.ts); }
+template <class F> int with_tiles(const TileSet& ts, F f) { return f(ts); }
+
+// k_pyr_down_multi over `ts` (TileSet | TileTab): level k -> k + 1 of every tile, the source level read in layout PLS
+template <int M, int SK, int PLS, class Tiles>
+int launch_pyr_down_multi(const Tiles& ts, const FeedPub& fp, dim3 grid, double bytes, hipStream_t st) {
+    const char* name = SK == SK_LEVEL ? "pyr_down" : "pyr_down_l0";
+    if constexpr (std::is_same<Tiles, TileTab>::value) ISX_LAUNCH(name, bytes, st, (k_pyr_down_multi_tab<M, SK, PLS>), grid, dim3(512), 0, ts, fp);
+    else ISX_LAUNCH(name, bytes, st, (k_pyr_down_multi<M, SK, PLS>), grid, dim3(512), 0, ts, fp);
     return ISX_OK;
 }
-template <int M, int SK>
-int launch_pyr_down0(const TileSet& ts, dim3 grid, double bytes, hipStream_t st, int planar) {
-    static const bool fast = [] { const char* e = getenv("ISX_PD0"); return !(e && e[0] == '0'); }();
-    if constexpr (SK == SK_U8 || SK == SK_S16) {
-        if constexpr (M == M_F32 && SK == SK_U8) {
-            if (planar == 2) { ISX_LAUNCH("pyr_down0", bytes, st, (k_pyr_down0<M, SK, 2>), grid, dim3(512), 0, ts); return ISX_OK; }
+// level k -> k + 1 (k >= 1) of every tile of `tiles` (TileViews | TileSet); src: the layout its SOURCE level is read in (level 1: the cycle's, above: records)
+template <int M, class Tiles>
+int launch_pyr_down_level(const Tiles& tiles, G1Format src, const FeedPub& fp, dim3 grid, double bytes, hipStream_t st) {
+    return with_tiles(tiles, [&](const auto& ts) -> int {
+        if constexpr (M == M_F32) {
+            if (src == G1_PLANAR_Q8) return launch_pyr_down_multi<M, SK_LEVEL, 2>(ts, fp, grid, bytes, st);
         }
-        ISX_CHECK_ARG(planar != 2, ISX_ERR_INTERNAL, "pyr_down0: Q8 records asked of a kernel that has none");
         if constexpr (M == M_F32 || M == M_I16) {
-            if (planar) { ISX_LAUNCH("pyr_down0", bytes, st, (k_pyr_down0<M, SK, 1>), grid, dim3(512), 0, ts); return ISX_OK; }
+            if (src == G1_PLANAR) return launch_pyr_down_multi<M, SK_LEVEL, 1>(ts, fp, grid, bytes, st);
         }
-        if (fast) { ISX_LAUNCH("pyr_down0", bytes, st, (k_pyr_down0<M, SK>), grid, dim3(512), 0, ts); return ISX_OK; }
-    }
-    ISX_LAUNCH("pyr_down_l0", bytes, st, (k_pyr_down_multi<M, SK>), grid, dim3(512), 0, ts, FeedPub{nullptr, 0, nullptr, 0});
+        ISX_CHECK_ARG(src == G1_RECORDS, ISX_ERR_INTERNAL, "pyr_down: a planar source level asked of a kernel that has none");
+        return launch_pyr_down_multi<M, SK_LEVEL, 0>(ts, fp, grid, bytes, st);
+    });
+}
+
+// level 0 -> 1 of every recorded tile: CV_8UC3 and CV_16SC3 tiles through k_pyr_down0 (ISX_PD0=0: the general kernel, for A/B runs)
+// fmt: level 1 is written as 16-byte records, or as dense image records + a weight plane (ts.coarse[t].wgt set by the caller; k_pyr_down0 only)
+template <int M, int SK, int PLD, class Tiles>
+int launch_pyr_down0_as(const Tiles& ts, dim3 grid, double bytes, hipStream_t st) {
+    if constexpr (std::is_same<Tiles, TileTab>::value) ISX_LAUNCH("pyr_down0", bytes, st, (k_pyr_down0_tab<M, SK, PLD>), grid, dim3(512), 0, ts);
+    else ISX_LAUNCH("pyr_down0", bytes, st, (k_pyr_down0<M, SK, PLD>), grid, dim3(512), 0, ts);
     return ISX_OK;
+}
+template <int M, int SK, class Tiles>
+int launch_pyr_down0(const Tiles& tiles, G1Format fmt, dim3 grid, double bytes, hipStream_t st) {
+    return with_tiles(tiles, [&](const auto& ts) -> int {
+        if constexpr (SK == SK_U8 || SK == SK_S16) {
+            if constexpr (M == M_F32 && SK == SK_U8) {
+                if (fmt == G1_PLANAR_Q8) return launch_pyr_down0_as<M, SK, 2>(ts, grid, bytes, st);
+            }
+            ISX_CHECK_ARG(fmt != G1_PLANAR_Q8, ISX_ERR_INTERNAL, "pyr_down0: Q8 records asked of a kernel that has none");
+            if constexpr (M == M_F32 || M == M_I16) {
+                if (fmt != G1_RECORDS) return launch_pyr_down0_as<M, SK, 1>(ts, grid, bytes, st);
+            }
+            if (switches().pd0) return launch_pyr_down0_as<M, SK, 0>(ts, grid, bytes, st);
+        }
+        return launch_pyr_down_multi<M, SK, 0>(ts, FeedPub{nullptr, 0, nullptr, 0}, grid, bytes, st);
+    });
+}
+
+// One step of the gathering collapse chain over one mosaic (v: its tiles) or over a batch of mosaics (ts, bo).  fine0: the last step (reads the tiles
+// themselves, of type SK, and writes the caller's mats); the steps above it read pyramid levels only and share one instantiation for every tile
+// type.  top: the first step (gathers the top level too).
+template <int M, int SK, bool FINE0, bool TOP>
+int launch_collapse_gather_as(dim3 grid, double bytes, hipStream_t st, const TileViews& v, const LevelBuf& coarse_out, const LevelBuf& fine_out, const OutMat& o) {
+    const char* name = FINE0 ? "collapse_gather_final" : "collapse_gather";
+    if (v.tab) ISX_LAUNCH(name, bytes, st, (k_collapse_gather_tab<M, SK, FINE0, TOP>), grid, dim3(256), 0, v.tt, coarse_out, fine_out, o);
+    else ISX_LAUNCH(name, bytes, st, (k_collapse_gather<M, SK, FINE0, TOP>), grid, dim3(256), 0, v.ts, coarse_out, fine_out, o);
+    return ISX_OK;
+}
+template <int M, int SK, bool FINE0, bool TOP>
+int launch_collapse_gather_as(dim3 grid, double bytes, hipStream_t st, const TileSet& ts, const BatchOut& bo) {
+    ISX_LAUNCH(FINE0 ? "collapse_gather_final" : "collapse_gather", bytes, st, (k_collapse_gather_batch<M, SK, FINE0, TOP>), grid, dim3(256), 0, ts, bo);
+    return ISX_OK;
+}
+template <int M, int SK, class... Args>
+int launch_collapse_gather(bool fine0, bool top, dim3 grid, double bytes, hipStream_t st, const Args&... args) {
+    if (fine0) return top ? launch_collapse_gather_as<M, SK, true, true>(grid, bytes, st, args...) : launch_collapse_gather_as<M, SK, true, false>(grid, bytes, st, args...);
+    return top ? launch_collapse_gather_as<M, SK_U8, false, true>(grid, bytes, st, args...) : launch_collapse_gather_as<M, SK_U8, false, false>(grid, bytes, st, args...);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1894,6 +1953,7 @@ double alg_g(int prec) { return prec == M_F32 ? 16.0 : (prec == M_I16 ? 10.0 : 8
 double alg_g_rgb(int prec) { return prec == M_F32 ? 12.0 : 6.0; }
 double alg_d(int prec) { return prec == M_I16 ? 10.0 : 16.0; }
 double alg_d_rgb(int prec) { return prec == M_I16 ? 6.0 : 12.0; }
+double out_px_bytes(const OutMat& o) { return o.img_f32 == 1 ? 13.0 : (o.img_f32 == 2 ? 4.0 : 7.0); }      // a pixel of the caller's result + its mask byte
 
 }  // namespace
 
@@ -1922,11 +1982,15 @@ struct isx_blender {
     std::vector<int4> fed;
     bool cleared = false;
     // deferred level 0: tiles recorded by feed(), consumed by blend()
-    // fused feed (k_feed_pd0, deferred mode 2): g1 = 0 level 1 not produced yet, 1 produced by feed() as 16-byte records, 2 produced PLANAR, 4 PLANAR in Q8 records, 3 produced by
-    // feed() but since rewritten on a window's columns in another layout (to be produced again);
+    // fused feed (k_feed_pd0, deferred mode 2): g1_have = what feed() left of level 1 - G1_NONE: not produced (the tile did not come through the fused
+    // feed), G1_WHOLE: produced, whole, in layout g1_fmt, G1_STALE: produced by feed() but since rewritten on a window's columns in another layout, or
+    // read from copies that were not what they seemed (to be produced again; g1_fmt says nothing then);
     // narrow != 0: a CV_16SC3 tile whose private copy was written as CV_8UC3 (sk = SK_U8, fed_sk = SK_S16) with escape segments in `wide`
+    enum G1Have { G1_NONE = 0, G1_WHOLE, G1_STALE };
     struct TileRec { Src0 s0; int sk; LevelBuf g[MAX_LEVELS]; int x_tl, y_tl, width, height;
-                     int fed_sk = 0, g1 = 0, narrow = 0; unsigned char* wide = nullptr; size_t wide_step = 0; unsigned char* chunk = nullptr; int nbx = 0; };
+                     int fed_sk = 0; G1Have g1_have = G1_NONE; G1Format g1_fmt = G1_RECORDS; int narrow = 0;
+                     unsigned char* wide = nullptr; size_t wide_step = 0; unsigned char* chunk = nullptr; int nbx = 0;
+                     bool g1_is(G1Format f) const { return g1_have == G1_WHOLE && g1_fmt == f; } };
     bool deferred = false;          // requested by the caller
     bool deferred_copy = false;     // ... with private copies of the fed device mats (OpenCV's contract kept)
     std::vector<std::unique_ptr<DevBuf>> tile_copy_img, tile_copy_mask;
@@ -1955,7 +2019,8 @@ struct isx_blender {
     // which code path the last blend() took (isx_blender_last_path): the fast kernels have limits, and a caller / a bench line should be
     // able to say which side of them it ran on.  cycle: 0 eager, 1 deferred, 2 deferred as part of a batched chain; last: the kernel of
     // the last collapse step - 0 none (a 0-band blend, Feather, NO), 1 k_collapse, 2 k_collapse_gather, 3 k_collapse_roll
-    int path_cycle = 0, path_last = 0, path_g1 = 0;      // path_g1: layout of the tiles' level 1 in the last blend (isx_blender_level1_format)
+    int path_cycle = 0, path_last = 0;
+    G1Format path_g1 = G1_RECORDS;      // layout of the tiles' level 1 in the last blend (isx_blender_level1_format)
     int path_fused = 0, path_narrow = 0;   // isx_blender_feed_path: tiles of the last blend() that came through k_feed_pd0; 0 none narrowed, 1 narrowed copies confirmed, 2 widened
     std::vector<hipStream_t> side;
     std::vector<hipEvent_t> ev_ready, ev_done;
@@ -1996,6 +2061,22 @@ int layout_levels(LevelBuf* lv, int L, int rows, int cols, int prec, bool is_dst
         rows = (rows + 1) / 2; cols = (cols + 1) / 2;
     }
     *total = off;
+    return ISX_OK;
+}
+// Levels 0 .. L of a pyramid in the tile-level format whose level 0 lives elsewhere (the caller's tile, the caller's mat): levels 1 .. L in `arena`,
+// grown as needed; lv[0] keeps its size and points nowhere.
+int layout_levels_above0(LevelBuf* lv, int L, int rows, int cols, int prec, DevBuf& arena) {
+    size_t total = 0;
+    layout_levels(lv, L, rows, cols, prec, false, nullptr, &total);
+    const size_t skip = ((size_t)rows * cols * g_px_bytes(prec) + 255) & ~(size_t)255;      // level 0 is not allocated
+    ISX_TRY(arena.reserve(total - skip + 256));
+    layout_levels(lv, L, rows, cols, prec, false, (char*)arena.p - skip, &total);
+    lv[0].img = nullptr; lv[0].wgt = nullptr;
+    return ISX_OK;
+}
+// isx_blender_set_mark_event: the event goes behind the Gaussian chain's launch of level k -> k + 1 (or where that launch would have been)
+int record_mark(isx_blender* b, int k, hipStream_t st) {
+    if (k == b->mark_level && b->mark_event) ISX_HIP(hipEventRecord(b->mark_event, st));
     return ISX_OK;
 }
 
@@ -2058,35 +2139,31 @@ int launch_feed_pd0_v(const Src0& s0, const LevelBuf& g1, FeedCopy fc, dim3 grid
     ISX_LAUNCH("feed_pd0", bytes, st, (k_feed_pd0<M, SK, PLD, CF>), grid, dim3(512), 0, s0, g1, fc);
     return ISX_OK;
 }
-template <int M, int SK>
-int launch_feed_pd0_t(int planar, bool narrow, const Src0& s0, const LevelBuf& g1, const FeedCopy& fc, dim3 grid, double bytes, hipStream_t st) {
-    // planar = 2: level 1 in Q8 records (load_px_planar) - fp32 pyramids over CV_8UC3 tiles and over CV_16SC3 tiles that are being narrowed (if those
+template <int M, int SK, int CF>
+int launch_feed_pd0_c(G1Format fmt, const Src0& s0, const LevelBuf& g1, const FeedCopy& fc, dim3 grid, double bytes, hipStream_t st) {
+    // G1_PLANAR_Q8: level 1 in Q8 records (load_px_planar) - fp32 pyramids over CV_8UC3 tiles and over CV_16SC3 tiles that are being narrowed (if those
     // turn out not to be bytes the cycle is widened and its level 1 produced again, run_blend_deferred_t)
-    ISX_CHECK_ARG(planar != 2 || (M == M_F32 && (SK == SK_U8 || narrow)), ISX_ERR_INTERNAL, "feed: Q8 records asked of a kernel that has none");
-    if constexpr (SK == SK_S16) {
-        if (narrow) {
-            if constexpr (M == M_F32) {
-                if (planar == 2) return launch_feed_pd0_v<M, SK, 2, CF_NARROW>(s0, g1, fc, grid, bytes, st);
-            }
-            if constexpr (M == M_F32 || M == M_I16) {
-                if (planar) return launch_feed_pd0_v<M, SK, 1, CF_NARROW>(s0, g1, fc, grid, bytes, st);
-            }
-            return launch_feed_pd0_v<M, SK, 0, CF_NARROW>(s0, g1, fc, grid, bytes, st);
-        }
+    if constexpr (M == M_F32 && (SK == SK_U8 || CF == CF_NARROW)) {
+        if (fmt == G1_PLANAR_Q8) return launch_feed_pd0_v<M, SK, 2, CF>(s0, g1, fc, grid, bytes, st);
     }
-    if constexpr (M == M_F32 && SK == SK_U8) {
-        if (planar == 2) return launch_feed_pd0_v<M, SK, 2, CF_SAME>(s0, g1, fc, grid, bytes, st);
-    }
+    ISX_CHECK_ARG(fmt != G1_PLANAR_Q8, ISX_ERR_INTERNAL, "feed: Q8 records asked of a kernel that has none");
     if constexpr (M == M_F32 || M == M_I16) {
-        if (planar) return launch_feed_pd0_v<M, SK, 1, CF_SAME>(s0, g1, fc, grid, bytes, st);
+        if (fmt != G1_RECORDS) return launch_feed_pd0_v<M, SK, 1, CF>(s0, g1, fc, grid, bytes, st);
     }
-    return launch_feed_pd0_v<M, SK, 0, CF_SAME>(s0, g1, fc, grid, bytes, st);
+    return launch_feed_pd0_v<M, SK, 0, CF>(s0, g1, fc, grid, bytes, st);
 }
-int launch_feed_pd0(int prec, int sk, int planar, bool narrow, const Src0& s0, const LevelBuf& g1, const FeedCopy& fc, dim3 grid, double bytes, hipStream_t st) {
+template <int M, int SK>
+int launch_feed_pd0_t(G1Format fmt, bool narrow, const Src0& s0, const LevelBuf& g1, const FeedCopy& fc, dim3 grid, double bytes, hipStream_t st) {
+    if constexpr (SK == SK_S16) {
+        if (narrow) return launch_feed_pd0_c<M, SK, CF_NARROW>(fmt, s0, g1, fc, grid, bytes, st);
+    }
+    return launch_feed_pd0_c<M, SK, CF_SAME>(fmt, s0, g1, fc, grid, bytes, st);
+}
+int launch_feed_pd0(int prec, int sk, G1Format fmt, bool narrow, const Src0& s0, const LevelBuf& g1, const FeedCopy& fc, dim3 grid, double bytes, hipStream_t st) {
     switch (prec) {
-        case M_I16: return sk == SK_U8 ? launch_feed_pd0_t<M_I16, SK_U8>(planar, narrow, s0, g1, fc, grid, bytes, st) : launch_feed_pd0_t<M_I16, SK_S16>(planar, narrow, s0, g1, fc, grid, bytes, st);
-        case M_F32: return sk == SK_U8 ? launch_feed_pd0_t<M_F32, SK_U8>(planar, narrow, s0, g1, fc, grid, bytes, st) : launch_feed_pd0_t<M_F32, SK_S16>(planar, narrow, s0, g1, fc, grid, bytes, st);
-        default: return sk == SK_U8 ? launch_feed_pd0_t<M_F16, SK_U8>(planar, narrow, s0, g1, fc, grid, bytes, st) : launch_feed_pd0_t<M_F16, SK_S16>(planar, narrow, s0, g1, fc, grid, bytes, st);
+        case M_I16: return sk == SK_U8 ? launch_feed_pd0_t<M_I16, SK_U8>(fmt, narrow, s0, g1, fc, grid, bytes, st) : launch_feed_pd0_t<M_I16, SK_S16>(fmt, narrow, s0, g1, fc, grid, bytes, st);
+        case M_F32: return sk == SK_U8 ? launch_feed_pd0_t<M_F32, SK_U8>(fmt, narrow, s0, g1, fc, grid, bytes, st) : launch_feed_pd0_t<M_F32, SK_S16>(fmt, narrow, s0, g1, fc, grid, bytes, st);
+        default: return sk == SK_U8 ? launch_feed_pd0_t<M_F16, SK_U8>(fmt, narrow, s0, g1, fc, grid, bytes, st) : launch_feed_pd0_t<M_F16, SK_S16>(fmt, narrow, s0, g1, fc, grid, bytes, st);
     }
 }
 
@@ -2146,18 +2223,24 @@ int narrow_resolve(isx_blender* b, bool* widened) {
 int src_kind_of(int type) { return type == ISX_8UC3 ? SK_U8 : (type == ISX_16SC3 ? SK_S16 : SK_F32); }
 double src_px_bytes(int sk) { return sk == SK_U8 ? 3.0 : (sk == SK_S16 ? 6.0 : 12.0); }
 
+// Gaussian chain of one tile (image + weight): G_{k+1} = pyrDown(G_k)
+template <int M, int SK>
+int launch_down_chain_t(const Src0& s0, const LevelBuf* g, int L, hipStream_t st) {
+    const int prec = M;
+    for (int k = 0; k < L; ++k) {
+        dim3 grid(cdiv(g[k + 1].cols, PD_OW), cdiv(g[k + 1].rows, PD_TY));
+        double bytes = (double)g[k].rows * g[k].cols * (k == 0 ? src_px_bytes(SK) + 1.0 : alg_g(prec)) + (double)g[k + 1].rows * g[k + 1].cols * alg_g(prec);
+        if (k == 0) ISX_LAUNCH("pyr_down_l0", bytes, st, (k_pyr_down<M, SK>), grid, dim3(512), 0, s0, g[0], g[1]);
+        else ISX_LAUNCH("pyr_down", bytes, st, (k_pyr_down<M, SK_LEVEL>), grid, dim3(512), 0, s0, g[k], g[k + 1]);
+    }
+    return ISX_OK;
+}
+
 template <int M, int SK>
 int run_feed(isx_blender* b, const Src0& s0, LevelBuf* g, int L, int x_tl, int y_tl, bool skip_level0) {
     hipStream_t st = b->stream;
     const int prec = M;
-    // Gaussian chain (image + weight): G_{k+1} = pyrDown(G_k)
-    for (int k = 0; k < L; ++k) {
-        dim3 grid(cdiv(g[k + 1].cols, PD_OW), cdiv(g[k + 1].rows, PD_TY));
-        double in_px = (double)g[k].rows * g[k].cols, out_px = (double)g[k + 1].rows * g[k + 1].cols;
-        double bytes = in_px * (k == 0 ? src_px_bytes(SK) + 1.0 : alg_g(prec)) + out_px * alg_g(prec);
-        if (k == 0) ISX_LAUNCH("pyr_down_l0", bytes, st, (k_pyr_down<M, SK>), grid, dim3(512), 0, s0, g[0], g[1]);
-        else ISX_LAUNCH("pyr_down", bytes, st, (k_pyr_down<M, SK_LEVEL>), grid, dim3(512), 0, s0, g[k], g[k + 1]);
-    }
+    ISX_TRY((launch_down_chain_t<M, SK>(s0, g, L, st)));
     // Laplacian + weighted accumulate: every level in one launch
     if (L <= ACC_MAXL) {
         AccArgs a;
@@ -2225,23 +2308,12 @@ Cover make_cover_n(const isx_blender* b, int level, int n) {
     return c;
 }
 
-template <int M, int SK>
-int launch_down_chain_t(isx_blender* b, const isx_blender::TileRec& r, hipStream_t st) {
-    const int L = b->num_bands, prec = M;
-    for (int k = 0; k < L; ++k) {
-        dim3 grid(cdiv(r.g[k + 1].cols, PD_OW), cdiv(r.g[k + 1].rows, PD_TY));
-        double bytes = (double)r.g[k].rows * r.g[k].cols * (k == 0 ? src_px_bytes(SK) + 1.0 : alg_g(prec)) + (double)r.g[k + 1].rows * r.g[k + 1].cols * alg_g(prec);
-        if (k == 0) ISX_LAUNCH("pyr_down_l0", bytes, st, (k_pyr_down<M, SK>), grid, dim3(512), 0, r.s0, r.g[0], r.g[1]);
-        else ISX_LAUNCH("pyr_down", bytes, st, (k_pyr_down<M, SK_LEVEL>), grid, dim3(512), 0, r.s0, r.g[k], r.g[k + 1]);
-    }
-    return ISX_OK;
-}
 template <int M>
 int launch_down_chain_k(isx_blender* b, const isx_blender::TileRec& r, hipStream_t st) {
     switch (r.sk) {
-        case SK_U8: return launch_down_chain_t<M, SK_U8>(b, r, st);
-        case SK_S16: return launch_down_chain_t<M, SK_S16>(b, r, st);
-        default: return launch_down_chain_t<M, SK_F32>(b, r, st);
+        case SK_U8: return launch_down_chain_t<M, SK_U8>(r.s0, r.g, b->num_bands, st);
+        case SK_S16: return launch_down_chain_t<M, SK_S16>(r.s0, r.g, b->num_bands, st);
+        default: return launch_down_chain_t<M, SK_F32>(r.s0, r.g, b->num_bands, st);
     }
 }
 int launch_down_chain(isx_blender* b, const isx_blender::TileRec& r, hipStream_t st) {
@@ -2287,39 +2359,18 @@ int flush_deferred(isx_blender* b) {
 // The last collapse step as the rolling kernel (collapse_roll.inc) when its limits hold: coarse columns [cx_lo, cx_hi) of level 1 in
 // strips of RL_CW columns x R rows, one wave each, dealt to the XCDs in groups of two strip rows (xcd_block).  *done = false: the
 // caller launches k_collapse_gather instead.  ISX_ROLL=0 forces that (A/B runs).
-// most tiles that reach any one strip of RL_CW x R coarse pixels: every tile covers a rectangle of strip indices; the deepest overlap of
-// those rectangles is found on the grid of their corners (at most 2 n x 2 n cells)
-inline int roll_max_tiles(const TileSet& ts, const LevelBuf& coarse, int cx_lo, int cx_hi, int R) {
-    const int nsx = cdiv(cx_hi - cx_lo, RL_CW), nsy = cdiv(coarse.rows, R);
-    int x0[DEF_MAX], x1[DEF_MAX], y0[DEF_MAX], y1[DEF_MAX], m = 0;
-    for (int t = 0; t < ts.n; ++t) {
-        // strip sx covers fine columns [2 (cx_lo + sx RL_CW), + 2 RL_CW); it is reached when that interval meets [x_tl, x_tl + w)
-        const int fx0 = ts.x_tl[t] - 2 * cx_lo, fx1 = fx0 + ts.w[t], fy0 = ts.y_tl[t], fy1 = fy0 + ts.h[t];
-        if (fx1 <= 0 || fy1 <= 0) continue;
-        const int a = fx0 > 0 ? fx0 / (2 * RL_CW) : 0, b = std::min(nsx - 1, (fx1 - 1) / (2 * RL_CW));
-        const int c = fy0 > 0 ? fy0 / (2 * R) : 0, d = std::min(nsy - 1, (fy1 - 1) / (2 * R));
-        if (a > b || c > d) continue;
-        x0[m] = a; x1[m] = b; y0[m] = c; y1[m] = d; ++m;
-    }
-    int most = 0;
-    for (int i = 0; i < m; ++i)
-        for (int j = 0; j < m; ++j) {         // deepest point lies at (a left edge, a top edge)
-            const int px = x0[i], py = y0[j];
-            int cnt = 0;
-            for (int t = 0; t < m; ++t) cnt += (x0[t] <= px) & (px <= x1[t]) & (y0[t] <= py) & (py <= y1[t]);
-            most = std::max(most, cnt);
-        }
-    return most;
-}
-// the same for any number of tiles (TileDesc records at the fine level): per left edge of a tile's strip rectangle, the tiles over that strip
-// column, and among them the deepest overlap of their strip-row intervals; stops as soon as more than `cap` tiles meet (the callers ask "at
+// most tiles (TileDesc records at the fine level) that reach any one strip of RL_CW x R coarse pixels: every tile covers a rectangle of strip
+// indices; the deepest overlap of those rectangles lies at (a left edge, a top edge): per left edge of a tile's strip rectangle, the tiles over that
+// strip column, and among them the deepest overlap of their strip-row intervals; stops as soon as more than `cap` tiles meet (the callers ask "at
 // most 2?", "at most 3?")
 inline int roll_max_tiles(const std::vector<TileDesc>& td, const LevelBuf& coarse, int cx_lo, int cx_hi, int R, int cap) {
     const int nsx = cdiv(cx_hi - cx_lo, RL_CW), nsy = cdiv(coarse.rows, R), n = (int)td.size();
-    std::vector<int4> r;
-    r.reserve((size_t)n);
+    static thread_local std::vector<int4> r;        // (scratch kept per thread: nothing is allocated in the steady state)
+    static thread_local std::vector<int2> over;
+    r.clear();
     for (int t = 0; t < n; ++t) {
         const TileDesc& e = td[(size_t)t];
+        // strip sx covers fine columns [2 (cx_lo + sx RL_CW), + 2 RL_CW); it is reached when that interval meets [x_tl, x_tl + w)
         const int fx0 = e.x_tl - 2 * cx_lo, fx1 = fx0 + e.w, fy0 = e.y_tl, fy1 = fy0 + e.h;
         if (fx1 <= 0 || fy1 <= 0) continue;
         const int a = fx0 > 0 ? fx0 / (2 * RL_CW) : 0, b = std::min(nsx - 1, (fx1 - 1) / (2 * RL_CW));
@@ -2329,7 +2380,6 @@ inline int roll_max_tiles(const std::vector<TileDesc>& td, const LevelBuf& coars
     }
     std::sort(r.begin(), r.end(), [](const int4& p, const int4& q) { return p.x < q.x; });
     int most = 0;
-    std::vector<int2> over;
     for (size_t i = 0; i < r.size(); ++i) {
         if (i > 0 && r[i].x == r[i - 1].x) continue;
         const int px = r[i].x;
@@ -2363,9 +2413,8 @@ int launch_collapse_roll_r(hipStream_t st, const TileViews& v, const LevelBuf& c
 // which instantiation runs the last step: 0 = none (k_collapse_gather), else 10 R + MAXT
 template <int SK>
 int roll_variant(const std::vector<TileDesc>& td, const LevelBuf& coarse, int cx_lo, int cx_hi) {
-    static const int mode = [] { const char* e = getenv("ISX_ROLL"); return e ? atoi(e) : 1; }();
     if constexpr (SK == SK_U8 || SK == SK_S16) {
-        if (!mode || coarse.cols < 2 || (unsigned long long)coarse.rows * coarse.cols * 16ull >= (1ull << 32)) return 0;
+        if (!switches().roll || coarse.cols < 2 || (unsigned long long)coarse.rows * coarse.cols * 16ull >= (1ull << 32)) return 0;
         for (const TileDesc& e : td)
             if (e.coarse.cols < 2 || e.s0.cols < 2 || e.s0.rows < 2 || e.s0.iend == 0u ||      // iend != 0: a CV_8UC3 / CV_16SC3 tile below 2 GiB, 32-bit offsets
                 (unsigned long long)e.coarse.rows * e.coarse.cols * 16ull >= (1ull << 32)) return 0;
@@ -2400,6 +2449,42 @@ int launch_collapse_roll(isx_blender* b, hipStream_t st, const TileViews& v, con
     return ISX_OK;
 }
 
+// Level 1 of the collapsed pyramid comes from k_collapse_gather (and not out of the fused top launch, k_collapse_top): L = 2, or L >= 5
+inline bool level1_by_gather(int L) {
+    const int D0 = std::min(TOP_DMAX, L - 1);
+    return D0 < 2 || L - D0 >= 2;
+}
+// Which kernel will run the last step is known before anything is launched, and two formats follow from it (round 4): when it is k_collapse_roll
+// and level 1 of the collapsed pyramid comes from k_collapse_gather, out_1 is written as dense 12-byte image records (OutMat::rec12) and level 1
+// of every tile PLANAR (load_px_planar) - the last step reads the image channels of both and never their fourth dword: 26.9 MB of 265 per 4K
+// pair fetched for nothing with 16-byte records.  ISX_OUT12=0 / ISX_G1P=0: the 16-byte records (A/B runs).
+// Level 1 in Q8 records (load_px_planar): fp32 pyramids over tiles of bytes - the caller's CV_8UC3 tiles, their private copies, narrowed copies of
+// CV_16SC3 tiles (if those turn out not to be bytes the cycle is widened and level 1 produced again).  ISX_G1Q8=0: off.
+// run_blend_deferred_t and run_blend_batch_t decide; do_feed asks with what it knows when a tile is fed.
+struct Level1Plan {
+    int prec = M_F32;
+    bool rec12 = false;                 // out_1 in dense image records
+    G1Format fmt = G1_RECORDS;          // level 1 of the tiles
+    double g1_b = 0.0, g1_rgb_b = 0.0;  // algorithmic bytes of a level-1 record / of its image channels
+    bool planar() const { return fmt != G1_RECORDS; }
+    bool q8() const { return fmt == G1_PLANAR_Q8; }
+    LevelBuf planar_of(LevelBuf g) const { g.wgt = (float*)((char*)g.img + planar_wgt_offset(prec, g.rows, g.cols, q8())); return g; }
+};
+// sk: the tiles' type as the chain reads them; roll_last: the last step is (will most likely be) k_collapse_roll; by_gather: level 1 of the collapsed
+// pyramid comes from k_collapse_gather; side_chains: the tiles' chains were launched by feed() and wrote 16-byte records; q8_veto: what else of
+// the cycle rules Q8 records out (a level 1 that exists in another layout, narrowed copies still to be confirmed)
+inline Level1Plan plan_level1(int prec, int sk, bool roll_last, bool by_gather, bool side_chains, bool q8_veto) {
+    const BlendSwitches& sw = switches();
+    Level1Plan p;
+    p.prec = prec;
+    p.rec12 = roll_last && by_gather && sw.out12;
+    const bool planar = roll_last && by_gather && sw.g1p && (prec == M_F32 || prec == M_I16) && !side_chains;
+    const bool q8 = planar && sw.g1q8 && prec == M_F32 && sk == SK_U8 && !q8_veto;
+    p.fmt = q8 ? G1_PLANAR_Q8 : (planar ? G1_PLANAR : G1_RECORDS);
+    p.g1_b = q8 ? 10.0 : alg_g(prec); p.g1_rgb_b = q8 ? 6.0 : alg_g_rgb(prec);
+    return p;
+}
+
 // blend() of a fully deferred cycle: Gaussian chains of all tiles, top gather, gathering collapse chain
 template <int M, int SK>
 int run_blend_deferred_t(isx_blender* b, const OutMat& out) {
@@ -2412,12 +2497,7 @@ int run_blend_deferred_t(isx_blender* b, const OutMat& out) {
     // format {int b, g, r; float w} instead, so that every precision stages out_k by LDS-DMA (OUT_DST in the kernel).
     LevelBuf od[MAX_LEVELS];
     if (M == M_I16) {
-        size_t total = 0;
-        layout_levels(od, L, d[0].rows, d[0].cols, prec, false, nullptr, &total);
-        const size_t skip = ((size_t)d[0].rows * d[0].cols * g_px_bytes(prec) + 255) & ~(size_t)255;   // level 0 goes to the caller's mat
-        ISX_TRY(b->out_arena.reserve(total - skip + 256));
-        layout_levels(od, L, d[0].rows, d[0].cols, prec, false, (char*)b->out_arena.p - skip, &total);
-        od[0].img = nullptr;
+        ISX_TRY(layout_levels_above0(od, L, d[0].rows, d[0].cols, prec, b->out_arena));   // level 0 goes to the caller's mat
         d = od;
     }
     // One TileDesc per tile and launch (b->td, reused); make_views() hands them to the kernel - in its arguments up to DEF_MAX tiles, as a device
@@ -2454,55 +2534,31 @@ int run_blend_deferred_t(isx_blender* b, const OutMat& out) {
         prod_hi[k] = std::min(std::max(need_hi[k], 2 * (prod_hi[k + 1] - 1) + 3), d[k].cols);
     }
     const double gin0 = src_px_bytes(SK) + 1.0;
-    // 0. Which kernel will run the last step?  Known before anything is launched, because two formats follow from it (round 4): when it is
-    //    k_collapse_roll and level 1 of the collapsed pyramid comes from k_collapse_gather (L = 2, or L >= 5 with k_collapse_top above it),
-    //    out_1 is written as dense 12-byte image records (OutMat::rec12) and level 1 of every tile PLANAR (load_px_planar) - the last step
-    //    reads the image channels of both and never their fourth dword: 26.9 MB of 265 per 4K pair fetched for nothing with 16-byte records.
-    //    ISX_OUT12=0 / ISX_G1P=0: the 16-byte records (A/B runs).
+    // 0. Which kernel will run the last step, and the layouts of level 1 that follow from it (plan_level1)
     int roll_var = 0;
-    bool rec12 = false, g1_planar = false;
     if (L >= 2) {
-        static const bool out12_on = [] { const char* e = getenv("ISX_OUT12"); return !(e && e[0] == '0'); }();
-        static const bool g1p_on = [] { const char* e = getenv("ISX_G1P"); return !(e && e[0] == '0'); }();
         base(0);
         for (int t = 0; t < n; ++t) { td[(size_t)t].fine = b->tiles[t].g[0]; td[(size_t)t].coarse = b->tiles[t].g[1]; }
         roll_var = roll_variant<SK>(td, d[1], need_lo[0] / 2, std::min((need_hi[0] + 1) / 2, d[1].cols));
-        const int D0 = std::min(TOP_DMAX, L - 1);
-        const bool lvl1_by_gather = D0 < 2 || L - D0 >= 2;
-        rec12 = roll_var != 0 && lvl1_by_gather && out12_on;
-        g1_planar = roll_var != 0 && lvl1_by_gather && g1p_on && (M == M_F32 || M == M_I16);
     }
-    // Level 1 in Q8 records (load_px_planar): fp32 pyramids over tiles of bytes - the caller's CV_8UC3 tiles, their private copies, narrowed copies of
-    // CV_16SC3 tiles (if those turn out not to be bytes the cycle is widened: level 1 is produced again, see narrow_resolve's callers below)
-    bool g1_q8 = false;
-    if constexpr (M == M_F32 && SK == SK_U8) {
-        static const bool q8_on = [] { const char* e = getenv("ISX_G1Q8"); return !(e && e[0] == '0'); }();
-        bool side = b->chain_on_side.size() >= (size_t)n;       // (chains launched by feed() wrote 16-byte records: all_on_side below)
-        for (int t = 0; t < n && side; ++t) side = b->chain_on_side[t] != 0;
-        g1_q8 = g1_planar && q8_on && !side;
-        for (int t = 0; t < n && g1_q8; ++t) {      // (SK_U8: the caller's CV_8UC3 tiles, private CV_8UC3 copies, narrowed copies of CV_16SC3 tiles)
-            const int s = b->tiles[t].g1;
-            g1_q8 = s == 0 || s == 3 || s == 4;      // a level 1 that feed() wrote in another layout keeps that layout
-        }
-    }
-    const double g1_b = g1_q8 ? 10.0 : alg_g(prec), g1_rgb_b = g1_q8 ? 6.0 : alg_g_rgb(prec);      // algorithmic bytes of a level-1 record / its image channels
-    auto planar_of = [g1_q8](LevelBuf g) { g.wgt = (float*)((char*)g.img + planar_wgt_offset(M, g.rows, g.cols, g1_q8)); return g; };
+    bool all_on_side = b->chain_on_side.size() >= (size_t)n;       // (chains launched by feed() wrote 16-byte records)
+    for (int t = 0; t < n && all_on_side; ++t) all_on_side = b->chain_on_side[t] != 0;
+    bool q8_veto = false;      // a level 1 that feed() wrote in another layout keeps that layout
+    for (int t = 0; t < n; ++t) q8_veto = q8_veto || (b->tiles[t].g1_have == isx_blender::G1_WHOLE && b->tiles[t].g1_fmt != G1_PLANAR_Q8);
+    const Level1Plan plan = plan_level1(M, SK, roll_var != 0, level1_by_gather(L), all_on_side, q8_veto);
     // A pair with three fused top steps: k_collapse_top2 (collapse_top2.inc) rebuilds the tiles' level L itself, out of the one read of level L - 1
     // it makes anyway - the pyrDown launch that produces level L is not issued.
     const bool use_top2 = n <= 2 && std::min(TOP_DMAX, L - 1) == 3;
     // 1. Gaussian chains: one launch per level for all tiles.  (Per-tile chains on side streams, started
     //    by feed() to overlap with the next tile's VALU-bound warp, were measured: no gain — a kernel that
     //    fills every wave slot leaves nothing for a concurrent one — so the simpler form stays.)
-    bool all_on_side = b->chain_on_side.size() >= (size_t)n;
-    for (int t = 0; t < n && all_on_side; ++t) all_on_side = b->chain_on_side[t] != 0;
-    if (all_on_side) { ISX_TRY(join_side_streams(b)); g1_planar = false; }     // (chains launched by feed() wrote 16-byte records)
-    b->path_g1 = g1_planar ? (g1_q8 ? 2 : 1) : 0;
+    if (all_on_side) ISX_TRY(join_side_streams(b));
+    b->path_g1 = plan.fmt;
     // Level 1 of tiles that came through the fused feed (k_feed_pd0) exists already, in the layout feed() expected this chain to want; when every
     // tile has it, whole and in that layout, the level-0 launch is skipped.  Otherwise level 1 is produced here from the private copies - whose type
     // must be known for that: the narrowed copies are confirmed first (a widened cycle re-enters as a cycle of CV_16SC3 tiles).
     bool g1_done = true;
-    const int g1_state = g1_planar ? (g1_q8 ? 4 : 2) : 1;
-    for (int t = 0; t < n; ++t) g1_done = g1_done && b->tiles[t].g1 == g1_state;
+    for (int t = 0; t < n; ++t) g1_done = g1_done && b->tiles[t].g1_is(plan.fmt);
     if (b->narrow_pending) {
         if (!(g1_done && L >= 2 && !all_on_side)) ISX_TRY(narrow_publish(b));      // (otherwise the level 1 -> 2 pyrDown below carries the words)
         if (!g1_done) {
@@ -2511,11 +2567,7 @@ int run_blend_deferred_t(isx_blender* b, const OutMat& out) {
             if constexpr (SK == SK_U8) { if (widened) return run_blend_deferred_t<M, SK_S16>(b, out); }
         }
     }
-    for (int k = 0; k < L && !all_on_side; ++k) {
-        if (k == 0 && g1_done) {
-            if (k == b->mark_level && b->mark_event) ISX_HIP(hipEventRecord(b->mark_event, st));
-            continue;
-        }
+    auto pyr_down_step = [&](int k) -> int {      // level k -> k + 1 of every tile
         base(k);
         int maxc = 0, maxr = 0;
         double bytes = 0.0;
@@ -2523,8 +2575,8 @@ int run_blend_deferred_t(isx_blender* b, const OutMat& out) {
             const isx_blender::TileRec& r = b->tiles[t];
             TileDesc& e = td[(size_t)t];
             e.fine = r.g[k]; e.coarse = r.g[k + 1];
-            if (g1_planar && k == 0) e.coarse = planar_of(r.g[1]);
-            if (g1_planar && k == 1) e.fine = planar_of(r.g[1]);
+            if (plan.planar() && k == 0) e.coarse = plan.planar_of(r.g[1]);
+            if (plan.planar() && k == 1) e.fine = plan.planar_of(r.g[1]);
             maxc = std::max(maxc, r.g[k + 1].cols); maxr = std::max(maxr, r.g[k + 1].rows);
             double share = 1.0;
             if (windowed) {   // the tile's columns of level k + 1 inside prod_{k+1}, as block columns of its own grid
@@ -2533,45 +2585,38 @@ int run_blend_deferred_t(isx_blender* b, const OutMat& out) {
                 e.bx_lo = c1 > c0 ? c0 / PD_OW : 0; e.bx_hi = c1 > c0 ? cdiv(c1, PD_OW) : 0;
                 share = (double)(e.bx_hi - e.bx_lo) / nbx;
             }
-            bytes += share * ((double)r.g[k].rows * r.g[k].cols * (k == 0 ? gin0 : (k == 1 ? g1_b : alg_g(prec))) + (double)r.g[k + 1].rows * r.g[k + 1].cols * (k == 0 ? g1_b : alg_g(prec)));
+            bytes += share * ((double)r.g[k].rows * r.g[k].cols * (k == 0 ? gin0 : (k == 1 ? plan.g1_b : alg_g(prec))) + (double)r.g[k + 1].rows * r.g[k + 1].cols * (k == 0 ? plan.g1_b : alg_g(prec)));
         }
         dim3 grid(cdiv(maxc, PD_OW), cdiv(maxr, PD_TY), n);
-        if (use_top2 && k == L - 1) {       // level L is rebuilt inside k_collapse_top2
-            if (k == b->mark_level && b->mark_event) ISX_HIP(hipEventRecord(b->mark_event, st));
-            continue;
-        }
         TileViews v;
         ISX_TRY(views(k, 0, 0, &v));
         if (k == 0) {
-            ISX_TRY((launch_pyr_down0<M, SK>(v, grid, bytes, st, g1_planar ? (g1_q8 ? 2 : 1) : 0)));
-            // Level 1 of these tiles now holds what THIS chain wants, on the columns this chain needs.  A tile whose level 1 came from feed() (g1 = 1 / 2)
-            // no longer has it whole in that layout when only a window's columns were rewritten (3 = fused-fed, level 1 to be produced again): a later
+            ISX_TRY((launch_pyr_down0<M, SK>(v, plan.fmt, grid, bytes, st)));
+            // Level 1 of these tiles now holds what THIS chain wants, on the columns this chain needs.  A tile whose level 1 came from feed() (G1_WHOLE)
+            // no longer has it whole in that layout when only a window's columns were rewritten (G1_STALE = fused-fed, level 1 to be produced again): a later
             // column strip of the same cycle that shares the tile (run_blend_deferred_strips) must not take it for done.  (Found by the fuzzer in round 5:
             // 35 tiles, two bands, a strip with more than three tiles over one place took k_collapse_gather and 16-byte records, its neighbour read the
             // shared tile's planar level 1 behind it.)
-            for (int t = 0; t < n; ++t)
-                if (b->tiles[t].g1 != 0) b->tiles[t].g1 = windowed ? 3 : g1_state;
-        } else {
-            FeedPub fp{nullptr, 0, nullptr, 0};
-            if (b->narrow_pending && !b->narrow_published) {      // the violation words ride on this launch (the first of the chain: level 1 came from feed())
-                fp = FeedPub{(unsigned*)b->feed_state.p, n, b->feed_pin, ++b->feed_seq};
-                b->narrow_published = true;
+            for (int t = 0; t < n; ++t) {
+                isx_blender::TileRec& r = b->tiles[t];
+                if (r.g1_have == isx_blender::G1_NONE) continue;
+                r.g1_have = windowed ? isx_blender::G1_STALE : isx_blender::G1_WHOLE;
+                r.g1_fmt = plan.fmt;
             }
-            if (k == 1 && g1_q8) {
-                if constexpr (M == M_F32) {
-                    if (v.tab) ISX_LAUNCH("pyr_down", bytes, st, (k_pyr_down_multi_tab<M, SK_LEVEL, 2>), grid, dim3(512), 0, v.tt, fp);
-                    else ISX_LAUNCH("pyr_down", bytes, st, (k_pyr_down_multi<M, SK_LEVEL, 2>), grid, dim3(512), 0, v.ts, fp);
-                }
-            } else if (k == 1 && g1_planar) {
-                if constexpr (M == M_F32 || M == M_I16) {
-                    if (v.tab) ISX_LAUNCH("pyr_down", bytes, st, (k_pyr_down_multi_tab<M, SK_LEVEL, 1>), grid, dim3(512), 0, v.tt, fp);
-                    else ISX_LAUNCH("pyr_down", bytes, st, (k_pyr_down_multi<M, SK_LEVEL, 1>), grid, dim3(512), 0, v.ts, fp);
-                }
-            } else if (v.tab) ISX_LAUNCH("pyr_down", bytes, st, (k_pyr_down_multi_tab<M, SK_LEVEL>), grid, dim3(512), 0, v.tt, fp);
-            else ISX_LAUNCH("pyr_down", bytes, st, (k_pyr_down_multi<M, SK_LEVEL>), grid, dim3(512), 0, v.ts, fp);
+            return ISX_OK;
         }
+        FeedPub fp{nullptr, 0, nullptr, 0};
+        if (b->narrow_pending && !b->narrow_published) {      // the violation words ride on this launch (the first of the chain: level 1 came from feed())
+            fp = FeedPub{(unsigned*)b->feed_state.p, n, b->feed_pin, ++b->feed_seq};
+            b->narrow_published = true;
+        }
+        return launch_pyr_down_level<M>(v, k == 1 ? plan.fmt : G1_RECORDS, fp, grid, bytes, st);
+    };
+    for (int k = 0; k < L && !all_on_side; ++k) {
+        // not launched: level 0 -> 1 when level 1 came whole from feed(); L - 1 -> L when level L is rebuilt inside k_collapse_top2
+        if (!(k == 0 && g1_done) && !(use_top2 && k == L - 1)) ISX_TRY(pyr_down_step(k));
         // the full-size level-0 kernel is behind us: from here to the last collapse step the launches are small
-        if (k == b->mark_level && b->mark_event) ISX_HIP(hipEventRecord(b->mark_event, st));
+        ISX_TRY(record_mark(b, k, st));
     }
     // 2. the top level out_L = norm(SUM_t cast(G_{L,t} W_{L,t})) is gathered inside the first collapse step (TOP) while it
     //    stages its coarse tile: no launch, no level-L buffer.
@@ -2657,20 +2702,20 @@ int run_blend_deferred_t(isx_blender* b, const OutMat& out) {
             const isx_blender::TileRec& r = b->tiles[t];
             TileDesc& e = td[(size_t)t];
             e.fine = r.g[k - 1]; e.coarse = r.g[k];
-            if (g1_planar && k == 2) e.fine = planar_of(r.g[1]);
-            if (g1_planar && k == 1) e.coarse = planar_of(r.g[1]);
+            if (plan.planar() && k == 2) e.fine = plan.planar_of(r.g[1]);
+            if (plan.planar() && k == 1) e.coarse = plan.planar_of(r.g[1]);
             if (k == L) bytes += (double)r.g[k].rows * r.g[k].cols * 4.0;                        // + the weights of G_L
-            bytes += (double)r.g[k - 1].rows * r.g[k - 1].cols * (k == 1 ? src_px_bytes(SKL) + 1.0 : (k == 2 ? g1_b : alg_g(prec)))   // G_{k-1,t} (level 0: the tile + mask)
-                   + (double)r.g[k].rows * r.g[k].cols * (k == 1 ? g1_rgb_b : alg_g_rgb(prec));         // G_{k,t} as pyrUp source
+            bytes += (double)r.g[k - 1].rows * r.g[k - 1].cols * (k == 1 ? src_px_bytes(SKL) + 1.0 : (k == 2 ? plan.g1_b : alg_g(prec)))   // G_{k-1,t} (level 0: the tile + mask)
+                   + (double)r.g[k].rows * r.g[k].cols * (k == 1 ? plan.g1_rgb_b : alg_g_rgb(prec));         // G_{k,t} as pyrUp source
         }
         dim3 grid(bx_hi - bx_lo, cdiv(d[k].rows, UP_TY));
         // (index ranges per 128 columns of the step's fine level = one block of k_collapse_gather; a strip of k_collapse_roll spans two)
         TileViews v;
         ISX_TRY(views(L + 1 + k, 7, d[k - 1].cols, &v));
-        v.ts.q8 = v.tt.q8 = (g1_q8 && k <= 2) ? 1 : 0;      // k = 2 reads level 1 as its fine level, k = 1 as its pyrUp source
+        v.ts.q8 = v.tt.q8 = (plan.q8() && k <= 2) ? 1 : 0;      // k = 2 reads level 1 as its fine level, k = 1 as its pyrUp source
         OutMat o = out;
         o.bx0 = bx_lo;
-        o.rec12 = (rec12 && k <= 2) ? 1 : 0;      // k = 2 writes out_1, k = 1 reads it
+        o.rec12 = (plan.rec12 && k <= 2) ? 1 : 0;      // k = 2 writes out_1, k = 1 reads it
         // last two steps (levels 0 and 1; the level-1 step runs at the fabric's rate: 48.5 -> 46.2 us for the four upper steps; no gain
         // from level 2 up): XCD-aware block order in groups of 2 block rows (see OutMat).  Measured on the 4K pair (tools/measure_traffic.py,
         // profiles/round2_xcd_order.txt): fabric traffic per launch 383 MB in plain row-major order, 282 MB with groups of 2, 268 with 4,
@@ -2681,30 +2726,18 @@ int run_blend_deferred_t(isx_blender* b, const OutMat& out) {
             grid = dim3(xcd_grid_blocks(XCD_GRP, o.gx, o.gy), 1);
         }
         if (k == 1) {
-            bytes = bytes * frac + (double)out.rows * (need_hi[0] - need_lo[0]) * (out.img_f32 == 1 ? 13.0 : (out.img_f32 == 2 ? 4.0 : 7.0));   // result + mask
+            bytes = bytes * frac + (double)out.rows * (need_hi[0] - need_lo[0]) * out_px_bytes(out);   // result + mask
             if (k != L) {
                 bool done = false;
                 OutMat o1 = out;
-                o1.rec12 = rec12 ? 1 : 0;
+                o1.rec12 = plan.rec12 ? 1 : 0;
                 ISX_TRY((launch_collapse_roll<M, SKL>(b, st, v, d[1], o1, need_lo[0] / 2, std::min((need_hi[0] + 1) / 2, d[1].cols), bytes, roll_var, &done)));
-                ISX_CHECK_ARG(done || !(rec12 || g1_planar), ISX_ERR_STATE, "blend: the last step's kernel was planned as k_collapse_roll and did not run");
+                ISX_CHECK_ARG(done || !(plan.rec12 || plan.planar()), ISX_ERR_STATE, "blend: the last step's kernel was planned as k_collapse_roll and did not run");
                 if (done) { b->path_last = 3; return ISX_OK; }
             }
             b->path_last = 2;
-            if (v.tab) {
-                if (k == L) ISX_LAUNCH("collapse_gather_final", bytes, st, (k_collapse_gather_tab<M, SKL, true, true>), grid, dim3(256), 0, v.tt, d[1], d[0], o);
-                else ISX_LAUNCH("collapse_gather_final", bytes, st, (k_collapse_gather_tab<M, SKL, true, false>), grid, dim3(256), 0, v.tt, d[1], d[0], o);
-            } else if (k == L) ISX_LAUNCH("collapse_gather_final", bytes, st, (k_collapse_gather<M, SKL, true, true>), grid, dim3(256), 0, v.ts, d[1], d[0], o);
-            else ISX_LAUNCH("collapse_gather_final", bytes, st, (k_collapse_gather<M, SKL, true, false>), grid, dim3(256), 0, v.ts, d[1], d[0], o);
-        } else {
-            bytes = (bytes + (double)d[k - 1].rows * d[k - 1].cols * alg_d_rgb(prec)) * frac;  // + out_{k-1}
-            if (v.tab) {
-                if (k == L) ISX_LAUNCH("collapse_gather", bytes, st, (k_collapse_gather_tab<M, SK_U8, false, true>), grid, dim3(256), 0, v.tt, d[k], d[k - 1], o);
-                else ISX_LAUNCH("collapse_gather", bytes, st, (k_collapse_gather_tab<M, SK_U8, false, false>), grid, dim3(256), 0, v.tt, d[k], d[k - 1], o);
-            } else if (k == L) ISX_LAUNCH("collapse_gather", bytes, st, (k_collapse_gather<M, SK_U8, false, true>), grid, dim3(256), 0, v.ts, d[k], d[k - 1], o);
-            else ISX_LAUNCH("collapse_gather", bytes, st, (k_collapse_gather<M, SK_U8, false, false>), grid, dim3(256), 0, v.ts, d[k], d[k - 1], o);
-        }
-        return ISX_OK;
+        } else bytes = (bytes + (double)d[k - 1].rows * d[k - 1].cols * alg_d_rgb(prec)) * frac;  // + out_{k-1}
+        return launch_collapse_gather<M, SKL>(k == 1, k == L, grid, bytes, st, v, d[k], d[k - 1], o);
     };
     for (int k = k_first; k >= 1; --k) {
         if (k == 1 && b->narrow_pending) {
@@ -2714,8 +2747,8 @@ int run_blend_deferred_t(isx_blender* b, const OutMat& out) {
             ISX_TRY(narrow_resolve(b, &widened));
             if constexpr (SK == SK_U8) {
                 if (widened) {      // (the roll variant was chosen on the tiles' geometry, which widening does not change)
-                    if (g1_q8) {        // the chain above read a level 1 in Q8 records that feed() wrote from shorts that were not bytes: all of it again
-                        for (int t = 0; t < n; ++t) if (b->tiles[t].g1 != 0) b->tiles[t].g1 = 3;
+                    if (plan.q8()) {        // the chain above read a level 1 in Q8 records that feed() wrote from shorts that were not bytes: all of it again
+                        for (int t = 0; t < n; ++t) if (b->tiles[t].g1_have != isx_blender::G1_NONE) b->tiles[t].g1_have = isx_blender::G1_STALE;
                         return run_blend_deferred_t<M, SK_S16>(b, out);
                     }
                     if (roll_var != 0) {
@@ -2807,7 +2840,7 @@ int run_blend_deferred_strips(isx_blender* b, const OutMat& out, bool* done) {
         rc = run_blend_deferred<M>(b, o);
         last = std::max(last, b->path_last);
         if (b->tiles.size() == idx.size())      // what the strip's chain did to the state of its tiles' level 1 (see the level-0 launch there)
-            for (size_t i = 0; i < idx.size(); ++i) all[(size_t)idx[i]].g1 = b->tiles[i].g1;
+            for (size_t i = 0; i < idx.size(); ++i) { all[(size_t)idx[i]].g1_have = b->tiles[i].g1_have; all[(size_t)idx[i]].g1_fmt = b->tiles[i].g1_fmt; }
     }
     b->tiles.swap(all);
     b->chain_on_side.swap(on_side);
@@ -2858,7 +2891,7 @@ int run_blend(isx_blender* b, const OutMat& out) {
     if (L == 0) {
         dim3 grid(cdiv(d[0].cols, 64), cdiv(d[0].rows, 4));
         double px = (double)d[0].rows * d[0].cols;
-        ISX_LAUNCH("norm_top_final", px * alg_d(prec) + (double)out.rows * out.cols * (out.img_f32 == 1 ? 13.0 : (out.img_f32 == 2 ? 4.0 : 7.0)), st, (k_norm_top<M, true>), grid, dim3(256), 0, d[0], out, make_cover(b, 0));
+        ISX_LAUNCH("norm_top_final", px * alg_d(prec) + (double)out.rows * out.cols * out_px_bytes(out), st, (k_norm_top<M, true>), grid, dim3(256), 0, d[0], out, make_cover(b, 0));
         return ISX_OK;
     }
     // the top level is normalised while it is staged as the coarse tile of the first collapse step
@@ -2869,7 +2902,7 @@ int run_blend(isx_blender* b, const OutMat& out) {
         Cover cov = make_cover(b, k - 1), ccov = make_cover(b, k);
         const bool normc = k == L;
         if (k == 1) {
-            double bytes = cb + (double)out.rows * out.cols * (alg_d(prec) + (out.img_f32 == 1 ? 13.0 : (out.img_f32 == 2 ? 4.0 : 7.0)));
+            double bytes = cb + (double)out.rows * out.cols * (alg_d(prec) + out_px_bytes(out));
             if (normc) ISX_LAUNCH("collapse_final", bytes, st, (k_collapse<M, true, true>), grid, dim3(256), 0, d[1], d[0], out, cov, ccov);
             else ISX_LAUNCH("collapse_final", bytes, st, (k_collapse<M, true, false>), grid, dim3(256), 0, d[1], d[0], out, cov, ccov);
         } else {
@@ -2896,12 +2929,7 @@ int run_blend_batch_t(isx_blender** bs, int nb, const OutMat* outs) {
         isx_blender* b = bs[m];
         d[m] = b->dst;
         if (M == M_I16) {      // the collapsed levels as 16-byte register records (see run_blend_deferred_t)
-            size_t total = 0;
-            layout_levels(od[m], L, d[m][0].rows, d[m][0].cols, prec, false, nullptr, &total);
-            const size_t skip = ((size_t)d[m][0].rows * d[m][0].cols * g_px_bytes(prec) + 255) & ~(size_t)255;
-            ISX_TRY(b->out_arena.reserve(total - skip + 256));
-            layout_levels(od[m], L, d[m][0].rows, d[m][0].cols, prec, false, (char*)b->out_arena.p - skip, &total);
-            od[m][0].img = nullptr;
+            ISX_TRY(layout_levels_above0(od[m], L, d[m][0].rows, d[m][0].cols, prec, b->out_arena));
             d[m] = od[m];
         }
         first[m] = nt;
@@ -2931,29 +2959,25 @@ int run_blend_batch_t(isx_blender** bs, int nb, const OutMat* outs) {
         return bs[m]->tiles[(size_t)(t - first[m])];
     };
     const double gin0 = src_px_bytes(SK) + 1.0;
-    // 0. the last step as the rolling kernel when every mosaic qualifies (roll_variant's conditions, two tiles per strip at most) - decided
-    //    before anything is launched: level 1 then goes without its dead fourth dword, as in run_blend_deferred_t (rec12, planar G_1)
+    // 0. the last step as the rolling kernel when every mosaic qualifies for its two-row strips with two tile slots (roll_variant) - decided
+    //    before anything is launched: level 1 then goes without its dead fourth dword, as in run_blend_deferred_t (plan_level1)
     bool roll_ok = false;
     unsigned roll_blocks = 0;
     int r_grp[BATCH_MAX], r_gx[BATCH_MAX], r_gy[BATCH_MAX];
     if (L >= 2) {
-        static const int mode = [] { const char* e = getenv("ISX_ROLL"); return e ? atoi(e) : 1; }();
-        const TileSet ts = base(0);
-        bool ok = mode != 0 && (SK == SK_U8 || SK == SK_S16);
+        bool ok = true;
         for (int m = 0; m < nb && ok; ++m) {
             const LevelBuf& c = d[m][1];
-            ok = c.cols >= 2 && (unsigned long long)c.rows * c.cols * 16ull < (1ull << 32);
-            TileSet one;
-            memset(&one, 0, sizeof(one));
-            one.n = first[m + 1] - first[m];
-            for (int t = 0; t < one.n && ok; ++t) {
-                const int g = first[m] + t;
-                const LevelBuf& g1 = tile_rec(g).g[1];
-                one.x_tl[t] = ts.x_tl[g]; one.y_tl[t] = ts.y_tl[g]; one.w[t] = ts.w[g]; one.h[t] = ts.h[g];
-                ok = g1.cols >= 2 && ts.s0[g].cols >= 2 && ts.s0[g].rows >= 2 && ts.s0[g].iend != 0u &&
-                     (unsigned long long)g1.rows * g1.cols * 16ull < (1ull << 32);
+            std::vector<TileDesc>& td = bs[m]->td;      // the mosaic's tiles at level 0 (reused)
+            td.resize(bs[m]->tiles.size());
+            for (size_t t = 0; t < td.size(); ++t) {
+                const isx_blender::TileRec& r = bs[m]->tiles[t];
+                TileDesc& e = td[t];
+                memset(&e, 0, sizeof(e));
+                e.s0 = r.s0; e.coarse = r.g[1];
+                e.x_tl = r.x_tl; e.y_tl = r.y_tl; e.w = r.g[0].cols; e.h = r.g[0].rows;
             }
-            ok = ok && roll_max_tiles(one, c, 0, c.cols, 2) <= 2;
+            ok = roll_variant<SK>(td, c, 0, c.cols) == 22;
             if (ok) {
                 const int nsx = cdiv(c.cols, RL_CW), nby = cdiv(cdiv(c.rows, 2), ROLL_WAVES), grp = std::max(2, nsx == 1 ? 2 : 1);
                 r_grp[m] = grp; r_gx[m] = nsx; r_gy[m] = nby;
@@ -2962,19 +2986,12 @@ int run_blend_batch_t(isx_blender** bs, int nb, const OutMat* outs) {
         }
         roll_ok = ok;
     }
-    static const bool out12_on = [] { const char* e = getenv("ISX_OUT12"); return !(e && e[0] == '0'); }();
-    static const bool g1p_on = [] { const char* e = getenv("ISX_G1P"); return !(e && e[0] == '0'); }();
-    const bool rec12 = roll_ok && out12_on, g1_planar = roll_ok && g1p_on && (M == M_F32 || M == M_I16);
-    bool g1_q8 = false;      // level 1 in Q8 records, as in run_blend_deferred_t
-    if constexpr (M == M_F32 && SK == SK_U8) {
-        static const bool q8_on = [] { const char* e = getenv("ISX_G1Q8"); return !(e && e[0] == '0'); }();
-        g1_q8 = g1_planar && q8_on;
-        for (int m = 0; m < nb && g1_q8; ++m) g1_q8 = !bs[m]->narrow_pending;
-        for (int t = 0; t < nt && g1_q8; ++t) g1_q8 = tile_rec(t).g1 == 0 && tile_rec(t).fed_sk == SK_U8;
-    }
-    for (int m = 0; m < nb; ++m) bs[m]->path_g1 = g1_planar ? (g1_q8 ? 2 : 1) : 0;
-    const double g1_b = g1_q8 ? 10.0 : alg_g(prec), g1_rgb_b = g1_q8 ? 6.0 : alg_g_rgb(prec);
-    auto planar_of = [g1_q8](LevelBuf g) { g.wgt = (float*)((char*)g.img + planar_wgt_offset(M, g.rows, g.cols, g1_q8)); return g; };
+    // (no fused top launch here: level 1 of the collapsed pyramid always comes from k_collapse_gather; the chains are launched below whatever feed() did)
+    bool q8_veto = false;
+    for (int m = 0; m < nb; ++m) q8_veto = q8_veto || bs[m]->narrow_pending != 0;
+    for (int t = 0; t < nt; ++t) q8_veto = q8_veto || tile_rec(t).g1_have != isx_blender::G1_NONE || tile_rec(t).fed_sk != SK_U8;
+    const Level1Plan plan = plan_level1(M, SK, roll_ok, true, false, q8_veto);
+    for (int m = 0; m < nb; ++m) bs[m]->path_g1 = plan.fmt;
     // 1. Gaussian chains: one launch per level for every tile of every mosaic
     for (int k = 0; k < L; ++k) {
         TileSet ts = base(k);
@@ -2983,25 +3000,20 @@ int run_blend_batch_t(isx_blender** bs, int nb, const OutMat* outs) {
         for (int t = 0; t < nt; ++t) {
             const isx_blender::TileRec& r = tile_rec(t);
             ts.fine[t] = r.g[k]; ts.coarse[t] = r.g[k + 1];
-            if (g1_planar && k == 0) ts.coarse[t] = planar_of(r.g[1]);
-            if (g1_planar && k == 1) ts.fine[t] = planar_of(r.g[1]);
+            if (plan.planar() && k == 0) ts.coarse[t] = plan.planar_of(r.g[1]);
+            if (plan.planar() && k == 1) ts.fine[t] = plan.planar_of(r.g[1]);
             maxc = std::max(maxc, r.g[k + 1].cols); maxr = std::max(maxr, r.g[k + 1].rows);
-            bytes += (double)r.g[k].rows * r.g[k].cols * (k == 0 ? gin0 : (k == 1 ? g1_b : alg_g(prec))) + (double)r.g[k + 1].rows * r.g[k + 1].cols * (k == 0 ? g1_b : alg_g(prec));
+            bytes += (double)r.g[k].rows * r.g[k].cols * (k == 0 ? gin0 : (k == 1 ? plan.g1_b : alg_g(prec))) + (double)r.g[k + 1].rows * r.g[k + 1].cols * (k == 0 ? plan.g1_b : alg_g(prec));
         }
         dim3 grid(cdiv(maxc, PD_OW), cdiv(maxr, PD_TY), nt);
-        if (k == 0) ISX_TRY((launch_pyr_down0<M, SK>(ts, grid, bytes, st, g1_planar ? (g1_q8 ? 2 : 1) : 0)));
-        else if (k == 1 && g1_q8) {
-            if constexpr (M == M_F32) ISX_LAUNCH("pyr_down", bytes, st, (k_pyr_down_multi<M, SK_LEVEL, 2>), grid, dim3(512), 0, ts, FeedPub{nullptr, 0, nullptr, 0});
-        } else if (k == 1 && g1_planar) {
-            if constexpr (M == M_F32 || M == M_I16) ISX_LAUNCH("pyr_down", bytes, st, (k_pyr_down_multi<M, SK_LEVEL, 1>), grid, dim3(512), 0, ts, FeedPub{nullptr, 0, nullptr, 0});
-        } else ISX_LAUNCH("pyr_down", bytes, st, (k_pyr_down_multi<M, SK_LEVEL>), grid, dim3(512), 0, ts, FeedPub{nullptr, 0, nullptr, 0});
-        for (int m = 0; m < nb; ++m)
-            if (k == bs[m]->mark_level && bs[m]->mark_event) ISX_HIP(hipEventRecord(bs[m]->mark_event, st));
+        if (k == 0) ISX_TRY((launch_pyr_down0<M, SK>(ts, plan.fmt, grid, bytes, st)));
+        else ISX_TRY(launch_pyr_down_level<M>(ts, k == 1 ? plan.fmt : G1_RECORDS, FeedPub{nullptr, 0, nullptr, 0}, grid, bytes, st));
+        for (int m = 0; m < nb; ++m) ISX_TRY(record_mark(bs[m], k, st));
     }
     // 2. collapse chain, the mosaic as grid.z
     for (int k = L; k >= 1; --k) {
         TileSet ts = base(k - 1);
-        ts.q8 = (g1_q8 && k <= 2) ? 1 : 0;
+        ts.q8 = (plan.q8() && k <= 2) ? 1 : 0;
         BatchOut bo;
         memset(&bo, 0, sizeof(bo));
         std::copy(first, first + nb + 1, bo.first);
@@ -3010,17 +3022,17 @@ int run_blend_batch_t(isx_blender** bs, int nb, const OutMat* outs) {
         for (int t = 0; t < nt; ++t) {
             const isx_blender::TileRec& r = tile_rec(t);
             ts.fine[t] = r.g[k - 1]; ts.coarse[t] = r.g[k];
-            if (g1_planar && k == 2) ts.fine[t] = planar_of(r.g[1]);
-            if (g1_planar && k == 1) ts.coarse[t] = planar_of(r.g[1]);
+            if (plan.planar() && k == 2) ts.fine[t] = plan.planar_of(r.g[1]);
+            if (plan.planar() && k == 1) ts.coarse[t] = plan.planar_of(r.g[1]);
             if (k == L) bytes += (double)r.g[k].rows * r.g[k].cols * 4.0;
-            bytes += (double)r.g[k - 1].rows * r.g[k - 1].cols * (k == 1 ? gin0 : (k == 2 ? g1_b : alg_g(prec))) + (double)r.g[k].rows * r.g[k].cols * (k == 1 ? g1_rgb_b : alg_g_rgb(prec));
+            bytes += (double)r.g[k - 1].rows * r.g[k - 1].cols * (k == 1 ? gin0 : (k == 2 ? plan.g1_b : alg_g(prec))) + (double)r.g[k].rows * r.g[k].cols * (k == 1 ? plan.g1_rgb_b : alg_g_rgb(prec));
         }
         for (int m = 0; m < nb; ++m) {
             bo.coarse_out[m] = d[m][k]; bo.fine_out[m] = d[m][k - 1]; bo.out[m] = outs[m];
             bo.out[m].bx0 = 0; bo.out[m].grp = 0; bo.out[m].band = 0;
-            bo.out[m].rec12 = (rec12 && k <= 2) ? 1 : 0;       // k = 2 writes out_1, k = 1 reads it
+            bo.out[m].rec12 = (plan.rec12 && k <= 2) ? 1 : 0;       // k = 2 writes out_1, k = 1 reads it
             if (k != L) bytes += (double)d[m][k].rows * d[m][k].cols * alg_d_rgb(prec);
-            if (k == 1) bytes += (double)outs[m].rows * outs[m].cols * (outs[m].img_f32 == 1 ? 13.0 : (outs[m].img_f32 == 2 ? 4.0 : 7.0));
+            if (k == 1) bytes += (double)outs[m].rows * outs[m].cols * out_px_bytes(outs[m]);
             else bytes += (double)d[m][k - 1].rows * d[m][k - 1].cols * alg_d_rgb(prec);
             gx = std::max(gx, cdiv(d[m][k].cols, WAVE)); gy = std::max(gy, cdiv(d[m][k].rows, UP_TY));
         }
@@ -3045,13 +3057,7 @@ int run_blend_batch_t(isx_blender** bs, int nb, const OutMat* outs) {
             }
             grid = dim3(nblk, 1, nb);
         }
-        if (k == 1) {
-            if (k == L) ISX_LAUNCH("collapse_gather_final", bytes, st, (k_collapse_gather_batch<M, SK, true, true>), grid, dim3(256), 0, ts, bo);
-            else ISX_LAUNCH("collapse_gather_final", bytes, st, (k_collapse_gather_batch<M, SK, true, false>), grid, dim3(256), 0, ts, bo);
-        } else {
-            if (k == L) ISX_LAUNCH("collapse_gather", bytes, st, (k_collapse_gather_batch<M, SK_U8, false, true>), grid, dim3(256), 0, ts, bo);
-            else ISX_LAUNCH("collapse_gather", bytes, st, (k_collapse_gather_batch<M, SK_U8, false, false>), grid, dim3(256), 0, ts, bo);
-        }
+        ISX_TRY((launch_collapse_gather<M, SK>(k == 1, k == L, grid, bytes, st, ts, bo)));
     }
     return ISX_OK;
 }
@@ -3279,7 +3285,6 @@ int do_feed(isx_blender* b, const isx_mat* img, const isx_mat* mask, int tl_x, i
     ISX_CHECK_ARG(b != nullptr, ISX_ERR_INVALID, "feed: null blender");
     if (b->type == ISX_BLEND_FEATHER) return do_feed_feather(b, img, mask, tl_x, tl_y, u8_entry, dil);
     if (b->type == ISX_BLEND_NO) return do_feed_no(b, img, mask, tl_x, tl_y, u8_entry, dil);
-    ISX_CHECK_ARG(b != nullptr, ISX_ERR_INVALID, "feed: null blender");
     ISX_CHECK_ARG(b->prepared, ISX_ERR_STATE, "feed: prepare() has not been called (or blend() already released the pyramids)");
     ISX_TRY(check_mat(img, "feed: img"));
     ISX_TRY(check_mat(mask, "feed: mask"));
@@ -3304,9 +3309,8 @@ int do_feed(isx_blender* b, const isx_mat* img, const isx_mat* mask, int tl_x, i
     // Fused feed (round 5, k_feed_pd0): in mode 2 a CV_8UC3 / CV_16SC3 device tile is read ONCE - level 1 of its pyramid and the private copy
     // come out of the same pass (ISX_FEED_FUSE=0: private_copy + the level-0 pyrDown inside blend(), as in round 4) - and the copy of a
     // CV_16SC3 tile is written as CV_8UC3 (ISX_FEED_NARROW=0: as CV_16SC3), see pyrdown_l0.inc.  A cycle narrows all of its tiles or none.
-    static const bool fuse_on = [] { const char* e = getenv("ISX_FEED_FUSE"); return !(e && e[0] == '0'); }();
-    static const bool narrow_on = [] { const char* e = getenv("ISX_FEED_NARROW"); return !(e && e[0] == '0'); }();
-    const bool fusable = b->deferred && b->deferred_copy && fuse_on && !dil && !b->overlap && img->device >= 0 && mask->device >= 0 && (sk == SK_U8 || sk == SK_S16) &&
+    const BlendSwitches& sw = switches();
+    const bool fusable = b->deferred && b->deferred_copy && sw.feed_fuse && !dil && !b->overlap && img->device >= 0 && mask->device >= 0 && (sk == SK_U8 || sk == SK_S16) &&
                          (unsigned long long)img->step * img->rows < (1ull << 31) && (unsigned long long)mask->step * img->rows < (1ull << 31) &&
                          img->step < (1u << 24) && mask->step < (1u << 24) && img->cols >= 2 && img->rows >= 2;
     const bool cycle_narrow = !b->tiles.empty() && b->tiles[0].narrow != 0;
@@ -3318,7 +3322,7 @@ int do_feed(isx_blender* b, const isx_mat* img, const isx_mat* mask, int tl_x, i
     bool narrow = false;
     if (fused && sk == SK_S16) {
         if (!b->tiles.empty()) narrow = cycle_narrow;
-        else if (narrow_on && !b->narrow_off) {
+        else if (sw.feed_narrow && !b->narrow_off) {
             hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;      // blend() reads the violation word on the host: not while the stream is being captured
             narrow = hipStreamIsCapturing(b->stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone;
         }
@@ -3383,17 +3387,8 @@ int do_feed(isx_blender* b, const isx_mat* img, const isx_mat* mask, int tl_x, i
     Src0 s0 = src0_of(di.data, di.step, img->type, dm.data, dm.step);
 
     LevelBuf g[MAX_LEVELS];
-    size_t total = 0;
     // tile Gaussian levels 1..L live in the tile arena; level 0 is the caller's tile
-    layout_levels(g, L, height, width, b->prec, false, nullptr, &total);
-    size_t skip = 0;
-    {   // do not allocate level 0
-        size_t n0 = (size_t)height * width;
-        skip = (n0 * g_px_bytes(b->prec) + 255) & ~(size_t)255;
-    }
-    ISX_TRY(arena.reserve(total - skip + 256));
-    layout_levels(g, L, height, width, b->prec, false, (char*)arena.p - skip, &total);
-    g[0].img = nullptr; g[0].wgt = nullptr;
+    ISX_TRY(layout_levels_above0(g, L, height, width, b->prec, arena));
 
     // the fused pass: G_1 and the private copies out of one read of the caller's tile
     isx_blender::TileRec rec;
@@ -3427,19 +3422,13 @@ int do_feed(isx_blender* b, const isx_mat* img, const isx_mat* mask, int tl_x, i
         }
         // level 1 PLANAR when the chain will most likely want it so (run_blend_deferred_t: the last step as k_collapse_roll with level 1 produced
         // by k_collapse_gather); blend() produces the level again from the private copy in the rare cycle that wants the other layout
-        static const bool g1p_on = [] { const char* e = getenv("ISX_G1P"); return !(e && e[0] == '0'); }();
-        static const bool roll_on = [] { const char* e = getenv("ISX_ROLL"); return !(e && atoi(e) == 0); }();
-        const int D0 = std::min(TOP_DMAX, L - 1);
-        const bool planar = L >= 2 && (D0 < 2 || L - D0 >= 2) && g1p_on && roll_on && (b->prec == M_F32 || b->prec == M_I16);
         // ... in Q8 records (load_px_planar) where the tile is bytes: CV_8UC3, or CV_16SC3 being narrowed (a violated cycle is widened and produces
-        // its level 1 again)
-        static const bool q8_on = [] { const char* e = getenv("ISX_G1Q8"); return !(e && e[0] == '0'); }();
-        const bool q8 = planar && q8_on && b->prec == M_F32 && (sk == SK_U8 || narrow);
-        LevelBuf g1 = g[1];
-        if (planar) g1.wgt = (float*)((char*)g1.img + planar_wgt_offset(b->prec, g1.rows, g1.cols, q8));
-        const double bytes = (double)height * width * (src_px_bytes(sk) + 1.0) + (double)g[1].rows * g[1].cols * (q8 ? 10.0 : alg_g(b->prec)) + (double)img->rows * img->cols * ((double)ipx + 1.0);
-        ISX_TRY(launch_feed_pd0(b->prec, sk, planar ? (q8 ? 2 : 1) : 0, narrow, s0, g1, fc, dim3(nbx, cdiv(g[1].rows, PD_TY)), bytes, b->stream));
-        rec.g1 = planar ? (q8 ? 4 : 2) : 1;
+        // its level 1 again).  What is known here: the rolling kernel is on and the bands allow it; the tiles' geometry will decide in blend().
+        const Level1Plan plan = plan_level1(b->prec, narrow ? SK_U8 : sk, L >= 2 && sw.roll, level1_by_gather(L), false, false);
+        const LevelBuf g1 = plan.planar() ? plan.planar_of(g[1]) : g[1];
+        const double bytes = (double)height * width * (src_px_bytes(sk) + 1.0) + (double)g[1].rows * g[1].cols * plan.g1_b + (double)img->rows * img->cols * ((double)ipx + 1.0);
+        ISX_TRY(launch_feed_pd0(b->prec, sk, plan.fmt, narrow, s0, g1, fc, dim3(nbx, cdiv(g[1].rows, PD_TY)), bytes, b->stream));
+        rec.g1_have = isx_blender::G1_WHOLE; rec.g1_fmt = plan.fmt;
         rec.sk = narrow ? SK_U8 : sk;
         s0 = src0_of(fc.cimg, ipitch, narrow ? ISX_8UC3 : img->type, fc.cmask, mpitch);
         if (narrow) { ++b->narrow_pending; b->narrow_published = false; }
@@ -3634,7 +3623,7 @@ int isx_blender_last_path(isx_blender* b, int* cycle, int* last_step) ISX_ENTRY 
 
 int isx_blender_level1_format(isx_blender* b, int* format) ISX_ENTRY {
     ISX_CHECK_ARG(b != nullptr && format != nullptr, ISX_ERR_INVALID, "isx_blender_level1_format: null argument");
-    *format = (b->type == ISX_BLEND_MULTI_BAND && b->path_cycle != 0) ? b->path_g1 : 0;
+    *format = (b->type == ISX_BLEND_MULTI_BAND && b->path_cycle != 0) ? (int)b->path_g1 : 0;
     return ISX_OK;
 } ISX_EXIT("isx_blender_level1_format")
 
@@ -3775,7 +3764,7 @@ static int blend_end(isx_blender* b, isx_mat* dst_mask) {
         if (dst_mask) ISX_TRY(b->st_outmask.finish_out(b->stream));
     }
     b->path_fused = 0;
-    for (const auto& r : b->tiles) b->path_fused += r.g1 != 0;
+    for (const auto& r : b->tiles) b->path_fused += r.g1_have != isx_blender::G1_NONE;
     b->tiles.clear();
     b->ftiles.clear();
     b->level0_pending = false;
