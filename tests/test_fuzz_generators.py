@@ -15,8 +15,10 @@ import fuzz_parity as F  # noqa: E402
 from helpers import voronoi_np as V  # noqa: E402
 
 FAMILIES = {"plane_warp": F.PLANE_CLASSES, "gain_feed": F.GAIN_CLASSES, "voronoi": F.VORONOI_CLASSES, "graphcut": F.GRAPHCUT_CLASSES,
-            "seam_grad": F.SEAM_GRAD_CLASSES, "blocks_gain": F.BLOCKS_GAIN_CLASSES, "resize": F.RESIZE_CLASSES}
+            "seam_grad": F.SEAM_GRAD_CLASSES, "blocks_gain": F.BLOCKS_GAIN_CLASSES, "resize": F.RESIZE_CLASSES,
+            "graphcut_grad": F.GRAPHCUT_GRAD_CLASSES}
 GEN_SEEDS, MODEL_SEEDS = range(200), range(5000, 5030)
+GCG_MODEL_SEEDS = range(5000, 5010)                                     # graphcut_grad's model is a max-flow on Python ints: a third of the seeds
 
 
 def _rois(c):
@@ -32,8 +34,9 @@ def test_the_constants_are_the_kernels():
     assert F.GF_PAIR_SIZES == [4095, 4096, 4097, 8192, 8193] and F.GF_DIAG_SIZES == [16383, 16384, 16385]
     assert F.GRAD_WIDTHS == [63, 64, 65, 129] and F.GRAD_HEIGHTS == [15, 16, 17, 33]
     assert F.SEAM_GAP == V.GAP == 10
-    assert [f.__name__ for f in F.CASES[-7:-2]] == F.NEW_FAMILIES and len(F.CASES) == 26
-    assert F.CASES[-2].__name__ == "case_blocks_gain" and F.CASES[-1].__name__ == "case_resize"
+    assert [f.__name__ for f in F.CASES[-8:-3]] == F.NEW_FAMILIES and len(F.CASES) == 27
+    assert [f.__name__ for f in F.CASES[-3:]] == ["case_blocks_gain", "case_resize", "case_graphcut_grad"]
+    assert F.GCG_MAX_NODES == 4600 and F.GCG_THIRD_TILE == (24, 16)
     assert F.BG_WIDE_ROWS == [4095, 4096, 4097, 4101] and F.BG_APPLY_WIDTHS == [255, 256, 257, 511, 512, 513] and F.BG_APPLY_HEIGHTS == [15, 16, 17]
     assert [F._BG[k] for k in ("BA_PX", "BA_ROWS", "LU_NT", "LU_RB", "LU_PNT")] == [4, 4, 256, 8, 1024] and F.BG_MAX_UNKNOWNS == 250
     assert F.RZ_WAVE_WIDTHS == [255, 256, 257, 511, 512, 513] and F.RZ_ROW_HEIGHTS == [3, 4, 5, 7, 8, 9, 15, 16, 17, 31, 32, 33]
@@ -111,6 +114,33 @@ def check_graphcut(c):
         assert all((a == a[0, 0]).all() for a in c["imgs"])
     if c["cls"] == "holes_heavy":
         assert all(0.2 < float((m == 0).mean()) < 0.4 for m in c["masks"])
+
+
+def check_graphcut_grad(c):
+    import graphcut_cases
+    _check_tiles(c, 2, 3)
+    assert all(a.dtype == np.float32 for a in c["imgs"])                 # COST_COLOR_GRAD reads Point3f only
+    assert all((a >= 0).all() and (a <= 255).all() and (a == np.floor(a)).all() for a in c["imgs"])
+    rois = _rois(c)
+    g2 = 2 * F.SEAM_GAP
+    first = rois[(0, 1)]
+    assert first is not None and (first[2] + g2) * (first[3] + g2) <= F.GCG_MAX_NODES         # the roi cap: the model's max-flow stays below 0.5 s
+    if len(c["sizes"]) == 3:
+        assert c["sizes"][2][0] <= F.GCG_THIRD_TILE[0] and c["sizes"][2][1] <= F.GCG_THIRD_TILE[1]
+    assert sum((r[2] + g2) * (r[3] + g2) for r in rois.values() if r is not None) <= F.GCG_MAX_NODES + 2 * (F.GCG_THIRD_TILE[0] + g2) * (F.GCG_THIRD_TILE[1] + g2)
+    if c["cls"] == "tile_edge_w":
+        assert first[2] + g2 in F.GC_WIDTHS
+    if c["cls"] == "tile_edge_h":
+        assert first[3] + g2 in F.GC_HEIGHTS
+    assert (c["kind"] == "constant") if c["cls"] == "flat_tie" else (c["cls"] not in ("smooth", "noise", "structured") or c["kind"] == c["cls"])
+    if c["kind"] == "constant":
+        assert all((a == a[0, 0]).all() for a in c["imgs"])
+    assert (c["pattern"] in graphcut_cases.PATTERNS) == (c["kind"] == "structured")
+    if c["kind"] == "structured":
+        for k, (a, (w, h)) in enumerate(zip(c["imgs"], c["sizes"])):
+            assert np.array_equal(a, graphcut_cases.pattern_images(c["pattern"], h, w)[k % 2])
+    if c["cls"] == "holes_heavy":
+        assert all(0.15 < float((m == 0).mean()) < 0.45 for m in c["masks"] if m.size >= 200)
 
 
 def check_seam_grad(c):
@@ -224,7 +254,8 @@ def test_the_models_stay_busy(family):
         pytest.importorskip("scipy")
     gen, model = getattr(F, "gen_" + family), getattr(F, "model_" + family)
     skips = busy = with_masks = upscaled = 0
-    for seed in MODEL_SEEDS:
+    seeds = GCG_MODEL_SEEDS if family == "graphcut_grad" else MODEL_SEEDS
+    for seed in seeds:
         c = gen(np.random.default_rng(seed))
         want = model(c)
         if isinstance(want, str):
@@ -244,9 +275,9 @@ def test_the_models_stay_busy(family):
                 assert want["pairs"] == [] and np.all(want["gains"] == 1.0)
         elif "masks" in c:
             with_masks += 1
-            masks = want[0] if family == "graphcut" else want
+            masks = want[0] if family in ("graphcut", "graphcut_grad") else want
             busy += any((a != b).any() for a, b in zip(masks, c["masks"]))
-    n = len(MODEL_SEEDS)
+    n = len(seeds)
     print(family, "skips", skips, "busy", busy, "of", with_masks or upscaled or n)
     assert skips * 10 <= n
     if family == "resize":
@@ -256,3 +287,31 @@ def test_the_models_stay_busy(family):
         assert busy * 2 >= n, (busy, n)
     elif family != "plane_warp":
         assert with_masks >= (n // 3 if family == "seam_grad" else n - skips) and busy * 2 >= with_masks, (busy, with_masks, n)
+
+
+def test_graphcut_grads_structured_class_yields_ties():
+    """The structured and flat_tie classes are there for graphs whose minimum cuts tie: among the first cases of either class, at least
+    half have a first pair whose minimal and maximal source side differ (the model's own max-flow, Python ints)."""
+    from helpers import graphcut_grad_np as GG
+    from helpers import graphcut_np as GN
+    ties = {"structured": 0, "flat_tie": 0}
+    seen = {"structured": 0, "flat_tie": 0}
+    patterns = set()
+    for seed in range(400):
+        rng = np.random.default_rng(seed)
+        c = F.gen_graphcut_grad(rng)
+        if c["cls"] == "structured":
+            patterns.add(c["pattern"])
+        if c["cls"] not in seen or seen[c["cls"]] == 6 or len(c["sizes"]) != 2:
+            continue
+        seen[c["cls"]] += 1
+        roi = F.overlap_roi(c["corners"][0], c["corners"][1], c["sizes"][0], c["sizes"][1])
+        g = GG.pair_graph_grad(c["imgs"][0], c["imgs"][1], c["masks"][0], c["masks"][1], c["corners"][0], c["corners"][1], roi)
+        flow, cert = GG.max_flow(g)
+        low = GN.minimal_source_side(g, cert["residuals"])
+        assert GN.cut_capacity(g, low) == flow
+        ties[c["cls"]] += not np.array_equal(low, cert["labels"])
+    import graphcut_cases
+    print("ties", ties, "of", seen)
+    assert seen == {"structured": 6, "flat_tie": 6} and all(2 * ties[k] >= seen[k] for k in seen), (ties, seen)
+    assert patterns == set(graphcut_cases.PATTERNS)                      # every pattern is drawn

@@ -7,6 +7,7 @@ written and inputs not one byte, and asserts which path ran: the launch names of
 isx_blender_last_path / _feed_path / _level1_format for the blender.  Shapes are the smallest that reach a path: tiles 24-70 pixels
 wide, 8-24 rows on the wide layouts, 255 / 256 / 257 and 511 / 512 rows on the tall ones."""
 import ctypes as C
+import gc
 import os
 import sys
 import zlib
@@ -101,6 +102,7 @@ def refused(call):
     with pytest.raises(_lib.IsxError) as e:
         call()
     assert e.value.code == UNSUPPORTED, e.value
+    del e       # the info holds the traceback, which holds this frame and the caller's: dropped here, they keep no blender alive until a collection
 
 
 # ---- warper --------------------------------------------------------------------------------------------------------------------------
@@ -589,6 +591,7 @@ def test_prepare_refuses_a_roi_past_the_record_index(gpu, kind):
     """isx_blender_prepare_roi: 2^24 pixels a side and 2^31 pixels are ISX_ERR_UNSUPPORTED before anything is allocated."""
     import torch
     b = make_blender(gpu, "r16", kind, 0)
+    gc.collect()                                                     # a blender of an earlier case (1.2 GiB prepared) that only a dead cycle holds goes now, not between the two readings
     sync()
     kept, free = b.retained_bytes(), torch.cuda.mem_get_info()[0]
     rois = [(0, 0, 65536, 32768)] + ([(0, 0, 1 << 24, 1)] if kind not in ("no",) else [])      # (Blender::NO keeps one level: only the pixel count)
@@ -728,6 +731,11 @@ def _graphcut_seam_find(gpu, oracle):
         GB.GC.find(imgs, corners, want)
         assert any((a != b).any() for a, b in zip(want, masks))
         _finder(lambda gi, gm: gpu.GraphCutSeamFinder().find(gi, corners, gm), [a.astype(np.float32) for a in imgs] if f32 else imgs, masks, want)
+    for n in (2, 3):                                                 # COST_COLOR_GRAD: the Sobel's three row pointers per tile, every mat at the wide pitch
+        corners, imgs, masks = layout16(n, n)
+        want = GB.GCG.find(imgs, corners, [m.copy() for m in masks])
+        assert any((a != b).any() for a, b in zip(want, masks))
+        _finder(lambda gi, gm: gpu.GraphCutSeamFinder(cost_type=GB.GCG.COST_COLOR_GRAD).find(gi, corners, gm), [a.astype(np.float32) for a in imgs], masks, want)
 
 
 def _voronoi_seam_find(gpu, oracle):

@@ -17,6 +17,7 @@ substitution that adds in another order.  Per set rtol = min(1e-9, 4 max(that di
 rtol 4.3e-15 ("apart", 3 blocks, cond 1.6) to 4.3e-12 ("one_pixel_blocks", 111 blocks, cond 44, 20 row swaps).  The solver past one stride
 of its pivot search (n = 513, 1025, 1100): the model's differences are 6.8e-15 to 1.7e-12, its swaps 0, 1, 2, 2 and 0."""
 import functools
+import gc
 import os
 import subprocess
 import sys
@@ -535,6 +536,9 @@ def test_feed_refuses_a_capturing_stream_and_apply_is_captured_and_replayed(gpu)
     maps = comp.gain_maps()
     gains = comp.gains()
     g = torch.cuda.CUDAGraph()
+    # a CUDAGraph that a dead reference cycle still holds (a test frame kept by its own pytest.raises info) must not be freed by a collection
+    # that happens to run inside this capture: its destructor synchronises the device, which a capturing stream turns into an abort
+    gc.collect()
     with torch.cuda.graph(g, stream=s, capture_error_mode="relaxed"):
         x.add_(1.0)
         with pytest.raises(gpu.IsxError) as e:
@@ -575,6 +579,7 @@ def test_a_captured_apply_replays_under_a_later_feed_of_the_same_sizes(gpu):
         torch.cuda.synchronize()
         maps1 = comp.gain_maps()
         g = torch.cuda.CUDAGraph()
+        gc.collect()
         with torch.cuda.graph(g, stream=s, capture_error_mode="relaxed"):
             comp.apply(0, corners[0], tile)
         torch.cuda.synchronize()

@@ -1,9 +1,10 @@
-"""A 20-second, fixed-seed slice of tools/fuzz_parity.py (the randomised HIP-vs-oracle sweep over every entry point, 26 families: warps, the
+"""A 20-second, fixed-seed slice of tools/fuzz_parity.py (the randomised HIP-vs-oracle sweep over every entry point, 27 families: warps, the
 fused tile kernel, the blenders in all precisions and cycles, mask preparation, the seam finder, the linear pair blend, whole pairs through
 PairStitcher, and - against their NumPy models - the plane projector, GainCompensator::feed, the Voronoi and graph-cut seam finders and
 the COLOR_GRAD cost with seam_gradients, BlocksGainCompensator, and cv::resize with the scaled mask stage) under -m gpu, then 8 seconds of
-the five families before the last two alone, whose shape classes sit on their kernels' tiling constants, 4 seconds of BlocksGainCompensator's
-and 4 seconds of the last, cv::resize's.  The long soaks are kept as JSON summaries under profiles/."""
+the five families before the last three alone, whose shape classes sit on their kernels' tiling constants, 4 seconds of BlocksGainCompensator's,
+4 seconds of cv::resize's and 4 seconds of the last, GraphCutSeamFinder(COST_COLOR_GRAD)'s.  The long soaks are kept as JSON summaries under
+profiles/."""
 import os
 import sys
 
@@ -56,13 +57,28 @@ def test_fuzz_slice_resize(gpu):
     assert list(out["per_family"]) == ["case_resize"] and out["cases"] >= 5 and out["skipped_geometries"] == 0, out
 
 
+def test_fuzz_slice_graphcut_grad(gpu):
+    """GraphCutSeamFinder(COST_COLOR_GRAD)'s family alone, over its seven classes (the structured patterns among them) and four placements:
+    masks byte for byte and the 64-bit certificate of the first pair.  Its model is a max-flow on Python ints, about 0.1 s a case."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "tools"))
+    import fuzz_parity
+    out = fuzz_parity.run(4.0, 20261106, verbose=True, only=["case_graphcut_grad"])
+    print(out["per_family"], "skipped", out["skipped_geometries"])
+    assert out["mismatches"] == 0, out["failing_seeds"]
+    assert list(out["per_family"]) == ["case_graphcut_grad"] and out["cases"] >= 5 and out["skipped_geometries"] == 0, out
+
+
 # seeds the soaks have tripped over, kept as cases of their own (family, seed):
 #   case_many_tiles 20260988784363 - round 5: 35 tiles in mode 2, two bands; one column strip of the cycle took k_collapse_gather (16-byte level-1
 #   records, produced again on its columns), its neighbour read a shared tile's planar level 1 from feed() behind it
 #   case_blocks_gain 20261078783058 - three tiles that all meet: isx_blocks_gain_stats gave the records image pair by image pair, not by (block_i, block_j)
 #   case_resize 20261164820493 - a 1 x 72 CV_8UC3 source whose NumPy row stride was 3 (a C-contiguous array keeps any stride on a dimension of
 #   length 1): as_mat handed it on as the step and isx_resize refused it ("step 3 smaller than a row"); as_mat now gives one row its bytes
-REGRESSIONS = [("case_many_tiles", 20260988784363), ("case_blocks_gain", 20261078783058), ("case_resize", 20261164820493)]
+#   case_graphcut_grad 20261166783477 - no soak tripped over it: three tiles in device views, the serpentine against itself flipped, whose first
+#   pair (grid 40 x 103) ties - minimal source side 2 166 nodes, maximal 2 563; kept so that a tie under COST_COLOR_GRAD runs with every suite
+REGRESSIONS = [("case_many_tiles", 20260988784363), ("case_blocks_gain", 20261078783058), ("case_resize", 20261164820493),
+               ("case_graphcut_grad", 20261166783477)]
 
 
 @pytest.mark.parametrize("family,seed", REGRESSIONS)

@@ -4,6 +4,7 @@ tests/helpers/graphcut_grad_np.py: masks byte for byte on random 2-, 3- and 4-ti
 bit for bit through r + r' = 2 w), the smallest shapes, the reference's tiles, the error paths, COST_COLOR and COST_COLOR_GRAD alternating
 on one thread and on two, the C++ mirror and OpenCV adapter, and warp -> convertTo -> graph cut -> dilate & AND -> Feather against the
 oracle.  The full 4K pair is not here: tools/time_graphcut_seam.py --cost color_grad runs it."""
+import gc
 import functools
 import os
 import subprocess
@@ -259,6 +260,9 @@ def test_errors_leave_the_masks_untouched(gpu):
     torch.cuda.synchronize()
     s = torch.cuda.Stream()
     g = torch.cuda.CUDAGraph()
+    # a CUDAGraph that a dead reference cycle still holds (a test frame kept by its own pytest.raises info) must not be freed by a collection
+    # that happens to run inside this capture: its destructor synchronises the device, which a capturing stream turns into an abort
+    gc.collect()
     with torch.cuda.graph(g, stream=s, capture_error_mode="relaxed"):
         with pytest.raises(gpu.IsxError) as e:
             gpu.GraphCutSeamFinder(cost_type=GRAD, stream=s).find(di, corners, dm)

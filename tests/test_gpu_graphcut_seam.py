@@ -2,6 +2,7 @@
 for byte on random 2-, 3- and 4-tile layouts (F32 and U8 tiles; host, device, pitched and unaligned mats), a certificate of every pair's
 maximum flow and maximal cut checked in NumPy (the full 4K pair included), the reference's tiles, determinism, the error paths, threads,
 the C++ mirror and OpenCV adapter, and warp -> gain -> graph cut -> dilate & AND -> Feather against the oracle."""
+import gc
 import os
 import subprocess
 import sys
@@ -190,6 +191,9 @@ def test_errors_leave_the_masks_untouched(gpu):
     torch.cuda.synchronize()
     s = torch.cuda.Stream()
     g = torch.cuda.CUDAGraph()
+    # a CUDAGraph that a dead reference cycle still holds (a test frame kept by its own pytest.raises info) must not be freed by a collection
+    # that happens to run inside this capture: its destructor synchronises the device, which a capturing stream turns into an abort
+    gc.collect()
     with torch.cuda.graph(g, stream=s, capture_error_mode="relaxed"):
         with pytest.raises(gpu.IsxError) as e:
             gpu.GraphCutSeamFinder(stream=s).find(di, corners, dm)

@@ -16,6 +16,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from helpers import blocks_gain_np as BG  # noqa: E402
 from helpers import dpseam_grad_np as M  # noqa: E402
+from helpers import graphcut_grad_np as GCG  # noqa: E402
 from helpers import graphcut_np as GC  # noqa: E402
 from helpers import guarded as G  # noqa: E402
 from helpers import plane_np as P  # noqa: E402
@@ -697,6 +698,17 @@ def test_dp_seam_find(gpu, cost, where, layout):
             run_finder(old, images, masks, want, where, layout, where == "mixed")
 
 
+_GRAD_WANT = {}
+
+
+def _grad_want(n, seed_):
+    """The COST_COLOR_GRAD model's masks of small_layout(n, seed_): solved once for all the parametrised cases, never edited."""
+    if (n, seed_) not in _GRAD_WANT:
+        corners, imgs, masks = small_layout(n, seed_)
+        _GRAD_WANT[(n, seed_)] = GCG.find(imgs, corners, [m.copy() for m in masks])
+    return _GRAD_WANT[(n, seed_)]
+
+
 @pytest.mark.parametrize("layout", LAYOUTS)
 @pytest.mark.parametrize("where", WHERE + ("mixed",))
 def test_graphcut_seam_find(gpu, where, layout):
@@ -714,6 +726,24 @@ def test_graphcut_seam_find(gpu, where, layout):
     GC.find(imgs, corners, want)
     run_finder(lambda gi, gm: gpu.GraphCutSeamFinder().find_pair(gi[0], gi[1], corners[0], corners[1], gm[0], gm[1]), imgs, masks, want, where, layout,
                where == "mixed")
+    # COST_COLOR_GRAD (CV_32FC3: three row pointers per tile in the build kernel) through find(), and isx_graphcut_seam_find_pair64 with its
+    # certificate, which is checked against the model's Q23 graph
+    for n, seed_ in ((2, 1), (3, 2)):
+        corners, imgs, masks = small_layout(n, seed_)
+        want = _grad_want(n, seed_)
+        assert any((a != b).any() for a, b in zip(want, masks))
+        run_finder(lambda gi, gm: gpu.GraphCutSeamFinder(cost_type=GCG.COST_COLOR_GRAD).find(gi, corners, gm), [a.astype(np.float32) for a in imgs], masks,
+                   want, where, layout, where == "mixed")
+    corners, imgs, masks = small_layout(2, 1)
+    want = _grad_want(2, 1)
+    sizes = [(a.shape[1], a.shape[0]) for a in imgs]
+    graph = GCG.pair_graph(imgs[0], imgs[1], masks[0], masks[1], corners[0], corners[1], GC.overlap_roi(corners[0], corners[1], sizes[0], sizes[1]))
+
+    def pair64(gi, gm):
+        r = gpu.GraphCutSeamFinder(cost_type=GCG.COST_COLOR_GRAD).find_pair(gi[0], gi[1], corners[0], corners[1], gm[0], gm[1], certificate=True)
+        assert r["residuals"].dtype == np.int64
+        GC.check_certificate(graph, r["flow"], r["residuals"], r["labels"])
+    run_finder(pair64, [a.astype(np.float32) for a in imgs], masks, want, where, layout, where == "mixed")
 
 
 @pytest.mark.parametrize("layout", LAYOUTS)

@@ -11,6 +11,7 @@ never cross.
 
 Every output is compared bit for bit with the oracle; where a replay is compared with the handle's own eager output, that eager output is
 compared with the oracle in the same test."""
+import gc
 import threading
 
 import numpy as np
@@ -181,6 +182,9 @@ def test_table_miss_while_capturing_is_refused(gpu):
         x = torch.zeros(16, device="cuda")
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
+    # a CUDAGraph that a dead reference cycle still holds (a test frame kept by its own pytest.raises info) must not be freed by a collection
+    # that happens to run inside this capture: its destructor synchronises the device, which a capturing stream turns into an abort
+    gc.collect()
     with torch.cuda.graph(g, stream=s, capture_error_mode="relaxed"):
         x.add_(1.0)
         with pytest.raises(gpu.IsxError) as e:

@@ -7,6 +7,7 @@ Sizes are rows x cols.  The area rule of INTER_LINEAR applies where the SOURCE i
 table lists its pairs in the upscaling direction (37 x 53 -> 74 x 106, 37 x 106 -> 74 x 106; the mask stage's 23 x 31 -> 46 x 62), which the
 general path takes, so each is run in both directions here: the downscaling one is what reaches the rule (and the one-direction-only exception)."""
 import ctypes as C
+import gc
 import os
 import sys
 
@@ -243,6 +244,9 @@ def test_captured_resize_then_mask_stage_replays(gpu):
     torch.cuda.synchronize()
     host_img, host_small = np.zeros((H, W, 3), np.uint8), np.full((23, 31, 3), 7, np.uint8)
     g = torch.cuda.CUDAGraph()
+    # a CUDAGraph that a dead reference cycle still holds (a test frame kept by its own pytest.raises info) must not be freed by a collection
+    # that happens to run inside this capture: its destructor synchronises the device, which a capturing stream turns into an abort
+    gc.collect()
     with torch.cuda.graph(g, stream=s, capture_error_mode="relaxed"):
         x.add_(1.0)
         with pytest.raises(gpu.IsxError) as e:

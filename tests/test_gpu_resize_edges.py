@@ -15,6 +15,7 @@ against the NumPy model (tests/helpers/resize_np.py), np.array_equal throughout 
 
 Sizes are rows x cols."""
 import ctypes as C
+import gc
 import os
 import re
 import sys
@@ -458,6 +459,9 @@ def test_overlap_error_leaves_a_capture_usable(gpu):
         x = torch.zeros(16, device="cuda")
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
+    # a CUDAGraph that a dead reference cycle still holds (a test frame kept by its own pytest.raises info) must not be freed by a collection
+    # that happens to run inside this capture: its destructor synchronises the device, which a capturing stream turns into an abort
+    gc.collect()
     with torch.cuda.graph(g, stream=s, capture_error_mode="relaxed"):
         x.add_(1.0)
         with pytest.raises(gpu.IsxError) as e:

@@ -2,6 +2,7 @@
 2-, 3- and 4-tile layouts (host, device, pitched and unaligned mats), the reference's tiles, a full 4K pair, degenerate rois, the float /
 integer trap past 8192 cells, a captured warp -> find -> dilate & AND -> multi-band cycle replayed on rewritten masks, determinism, threads,
 the error paths, the C++ mirror and OpenCV adapter, and warp -> gain -> Voronoi -> dilate & AND -> Feather against the oracle."""
+import gc
 import os
 import subprocess
 import sys
@@ -373,6 +374,9 @@ def test_captured_chain_replays_on_rewritten_masks(gpu, oracle):
     r["warper"].join()
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
+    # a CUDAGraph that a dead reference cycle still holds (a test frame kept by its own pytest.raises info) must not be freed by a collection
+    # that happens to run inside this capture: its destructor synchronises the device, which a capturing stream turns into an abort
+    gc.collect()
     with torch.cuda.graph(g, stream=s, capture_error_mode="relaxed"):
         _chain(gpu, r)
     for k in range(3):
@@ -419,6 +423,7 @@ def test_captured_find_refuses_host_masks_and_missing_scratch(gpu):
         x = torch.zeros(16, device="cuda")
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
+    gc.collect()
     with torch.cuda.graph(g, stream=s, capture_error_mode="relaxed"):
         x.add_(1.0)
         with pytest.raises(gpu.IsxError) as e:                        # nothing reserved at all
@@ -430,6 +435,7 @@ def test_captured_find_refuses_host_masks_and_missing_scratch(gpu):
     f.reserve(roi[2], roi[3])
     host = [m.copy() for m in masks]
     g = torch.cuda.CUDAGraph()
+    gc.collect()
     with torch.cuda.graph(g, stream=s, capture_error_mode="relaxed"):
         x.add_(1.0)
         with pytest.raises(gpu.IsxError) as e:

@@ -4,8 +4,10 @@
 Every failure prints the seed of the case so that it can be replayed; exit code = number of failing cases.  With a third argument the
 summary (cases, seconds, seed, mismatches per family) is also written as JSON - the file kept under profiles/.
 tests/test_gpu_fuzz_slice.py runs run(20 s, fixed seed) under -m gpu.
-26 families (CASES); ISX_FUZZ_ONLY=case_a,case_b runs only those.  The last, case_resize: cv::resize and the scaled mask stage
-(isx_resize, isx_mask_dilate_resize_and) against tests/helpers/resize_np.py over the shape classes RESIZE_CLASSES."""
+27 families (CASES); ISX_FUZZ_ONLY=case_a,case_b runs only those; ISX_FUZZ_STOP_AT_FIRST=1 ends the run at the first failing case.
+The 26th, case_resize: cv::resize and the scaled mask stage (isx_resize, isx_mask_dilate_resize_and) against tests/helpers/resize_np.py
+over the shape classes RESIZE_CLASSES.  The 27th, case_graphcut_grad: GraphCutSeamFinder(COST_COLOR_GRAD) against
+tests/helpers/graphcut_grad_np.py over GRAPHCUT_GRAD_CLASSES, the structured patterns of tools/graphcut_patterns.py among them."""
 import os
 import sys
 import time
@@ -14,6 +16,7 @@ import traceback
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np  # noqa: E402
 
 import imagestitch_amd as G  # noqa: E402
@@ -853,6 +856,9 @@ PLANE_CLASSES = ["plain", "tiny", "odd_width", "with_T"]
 GAIN_CLASSES = ["plain", "pair_item_edge", "diag_item_edge", "one_pixel_overlap", "disjoint_pair"]
 VORONOI_CLASSES = ["plain", "chunk_edge", "seg_edge", "thin", "no_unique_rows"]
 GRAPHCUT_CLASSES = ["plain", "tile_edge_w", "tile_edge_h", "flat_tie", "holes_heavy"]
+GRAPHCUT_GRAD_CLASSES = ["tile_edge_w", "tile_edge_h", "flat_tie", "holes_heavy", "smooth", "noise", "structured"]
+GCG_MAX_NODES = 4600                                                    # padded-grid nodes of a case's first pair (gen_graphcut_grad)
+GCG_THIRD_TILE = (24, 16)                                               # the third tile is at most this wide and high
 SEAM_GRAD_CLASSES = ["plain", "tile_edge", "one_pixel", "rect_at_border", "find"]          # the first four: seam_gradients; "find": the whole finder
 BLOCKS_GAIN_CLASSES = ["plain", "several_items", "wide_row", "one_pixel_blocks", "no_pairs", "one_pixel_meeting", "apply_edges"]
 BG_WIDE_ROWS = [_GF["GF_PAIR_PIXELS"] + d for d in (-1, 0, 1, 5)]          # the width of a pair of blocks whose band is one row
@@ -1200,6 +1206,105 @@ def case_graphcut(rng):
         i, j, g = first
         r = G.GraphCutSeamFinder().find_pair(imgs[i], imgs[j], c["corners"][i], c["corners"][j], c["masks"][i].copy(), c["masks"][j].copy(), certificate=True)
         assert (r["rows"], r["cols"]) == g["src"].shape, (r["rows"], r["cols"], g["src"].shape)
+        graphcut_np.check_certificate(g, r["flow"], r["residuals"], r["labels"])
+
+
+# ---- GraphCutSeamFinder(COST_COLOR_GRAD) --------------------------------------------------------------------------------------------------
+def _gcg_image(rng, kind, pattern, k, w, h):
+    """Tile k of a case: layout()'s blocky texture, noise, a constant, or image k % 2 of a structured pattern at the tile's own size."""
+    if kind == "smooth":
+        base = rng.integers(0, 256, (h // 8 + 2, w // 8 + 2, 3))
+        img = np.kron(base, np.ones((8, 8, 1), np.int64))[:h, :w] + rng.integers(0, 12, (h, w, 3))
+    elif kind == "noise":
+        img = rng.integers(0, 256, (h, w, 3))
+    elif kind == "constant":
+        img = np.broadcast_to(rng.integers(0, 256, 3), (h, w, 3))
+    else:
+        from graphcut_patterns import pattern_images
+        img = pattern_images(pattern, h, w)[k % 2]
+    return np.clip(img, 0, 255).astype(np.float32)
+
+
+def gen_graphcut_grad(rng):
+    """2..3 CV_32FC3 tiles for GraphCutSeamFinder(COST_COLOR_GRAD).  The first two tiles carry the class: a padded grid (roi + 20) as wide as
+    1 or 2 of graphcut.hip's BFS tiles +-1 (tile_edge_w) or as high as 2 or 3 of them (tile_edge_h), constant images (flat_tie: every
+    weight is 1.0f or one value, all cuts through the overlap tie; half of them the same constant twice), masks with 30 % of their cells
+    zero (holes_heavy), layout()'s texture (smooth), noise, or a pattern of tools/graphcut_patterns.py at random sizes and corners
+    (structured: constants, ramps, steps, checkerboards, serpentines - ties and the ends of the Q23 range).
+    The model's max-flow is a Dinic on Python ints: 0.10 to 0.17 s on a padded grid of 57 x 60 = 3 420 nodes.  So the first pair's grid is
+    capped at GCG_MAX_NODES = 4 600 nodes - a roi of at most 48 x 47 when square, 109 x 15 when as wide as two BFS tiles - and a third
+    tile, drawn for a third of the cases, is at most 24 x 16 (two more grids of at most 44 x 36).  Measured on a CPU over the seeds
+    0..209: 0.07 to 0.13 s of model time a case on average by class, 0.47 s at the worst (a tile_edge_w case of three tiles): below 0.5 s."""
+    cls = _pick(rng, GRAPHCUT_GRAD_CLASSES)
+    g2 = 2 * SEAM_GAP
+    if cls == "tile_edge_w":
+        wp = _pick(rng, GC_WIDTHS)
+        ow, oh = wp - g2, int(rng.integers(1, max(2, GCG_MAX_NODES // wp - g2 + 1)))
+    elif cls == "tile_edge_h":
+        hp = _pick(rng, GC_HEIGHTS)
+        ow, oh = int(rng.integers(1, GCG_MAX_NODES // hp - g2 + 1)), hp - g2
+    else:
+        ow = int(rng.integers(1, 90))
+        oh = int(rng.integers(1, min(60, GCG_MAX_NODES // (ow + g2) - g2) + 1))
+    corners, sizes = _pair_with_overlap(rng, ow, oh)
+    if rng.integers(0, 3) == 0:
+        _tile_onto(rng, corners, sizes, (4, GCG_THIRD_TILE[0] + 1), (4, GCG_THIRD_TILE[1] + 1))
+    kind = {"flat_tie": "constant", "smooth": "smooth", "noise": "noise", "structured": "structured"}.get(cls) or _pick(rng, ["smooth", "noise", "constant", "structured"])
+    pattern = None
+    if kind == "structured":
+        from graphcut_patterns import PATTERNS
+        pattern = _pick(rng, list(PATTERNS))
+    imgs, masks = [], []
+    for k, (w, h) in enumerate(sizes):
+        imgs.append(_gcg_image(rng, kind, pattern, k, w, h))
+        m = np.full((h, w), 255, np.uint8)
+        if cls == "holes_heavy":
+            m[rng.random((h, w)) < 0.3] = 0
+        else:
+            for _ in range(int(rng.integers(0, 4))):
+                y, x = int(rng.integers(0, h)), int(rng.integers(0, w))
+                m[y:y + int(rng.integers(2, 10)), x:x + int(rng.integers(2, 10))] = 0
+        masks.append(m)
+    if cls == "flat_tie" and rng.integers(0, 2):
+        imgs[1][...] = imgs[0][0, 0]                                    # the same constant twice: every unpenalised weight is exactly 1.0f
+    return dict(cls=cls, kind=kind, pattern=pattern, corners=corners, sizes=sizes, imgs=imgs, masks=masks, where=_pick(rng, WHERE),
+                view_seed=int(rng.integers(0, 5)))
+
+
+def model_graphcut_grad(c):
+    """-> (masks after find(), the first overlapping pair (i, j, its Q23 graph on the untouched masks) or None); NumPy and Python ints only."""
+    from helpers import graphcut_grad_np
+    out = [m.copy() for m in c["masks"]]
+    graphcut_grad_np.find(c["imgs"], c["corners"], out)
+    n = len(out)
+    for i in range(n - 1):
+        for j in range(i + 1, n):
+            roi = overlap_roi(c["corners"][i], c["corners"][j], c["sizes"][i], c["sizes"][j])
+            if roi is not None:
+                g = graphcut_grad_np.pair_graph_grad(c["imgs"][i], c["imgs"][j], c["masks"][i], c["masks"][j], c["corners"][i], c["corners"][j], roi)
+                return out, (i, j, g)
+    return out, None
+
+
+def case_graphcut_grad(rng):
+    """isx_graphcut_seam_find(COST_COLOR_GRAD) against tests/helpers/graphcut_grad_np.py, masks byte for byte; the 64-bit certificate of
+    isx_graphcut_seam_find_pair64 on the first overlapping pair: a maximum flow and the maximal minimum cut of the model's Q23 graph."""
+    from helpers import graphcut_np
+    c = gen_graphcut_grad(rng)
+    want, first = model_graphcut_grad(c)
+    note = (c["cls"], c["kind"], c["pattern"], c["where"])
+    imgs = [p[0] for p in _place(c["imgs"], c["where"], c["view_seed"])]
+    placed = _place(c["masks"], c["where"], c["view_seed"] + 1)
+    fdr = G.GraphCutSeamFinder(cost_type=G.seam.COST_COLOR_GRAD)
+    fdr.find(imgs, c["corners"], [p[0] for p in placed])
+    for k, (p, w) in enumerate(zip(placed, want)):
+        got = _host(p[0])
+        assert np.array_equal(got, w), note + (k, int((got != w).sum()), np.argwhere(got != w)[:3])
+    _frame_untouched(placed)
+    if first is not None:
+        i, j, g = first
+        r = fdr.find_pair(imgs[i], imgs[j], c["corners"][i], c["corners"][j], c["masks"][i].copy(), c["masks"][j].copy(), certificate=True)
+        assert (r["rows"], r["cols"]) == g["src"].shape and r["residuals"].dtype == np.int64, note + (r["rows"], r["cols"], g["src"].shape)
         graphcut_np.check_certificate(g, r["flow"], r["residuals"], r["labels"])
 
 
@@ -1559,7 +1664,7 @@ NEW_FAMILIES = ["case_plane_warp", "case_gain_feed", "case_voronoi", "case_graph
 
 CASES = [case_warp, case_blend, case_feather, case_prep, case_seam, case_blend_float_and_many, case_pipeline, case_find, case_warp_fused,
          case_linear_pair, case_strip, case_strip_feather, case_batch, case_s16_tiles, case_round4_calls, case_many_tiles, case_fused_feed, case_round6_calls,
-         case_long_lived, case_plane_warp, case_gain_feed, case_voronoi, case_graphcut, case_seam_grad, case_blocks_gain, case_resize]
+         case_long_lived, case_plane_warp, case_gain_feed, case_voronoi, case_graphcut, case_seam_grad, case_blocks_gain, case_resize, case_graphcut_grad]
 
 
 def run(budget, seed0, verbose=True, progress_path=None, only=None):
@@ -1578,6 +1683,7 @@ def run(budget, seed0, verbose=True, progress_path=None, only=None):
     counts = {f.__name__: 0 for f in CASES}
     fails = {f.__name__: 0 for f in CASES}
     failing_seeds = []
+    stop_at_first = os.environ.get("ISX_FUZZ_STOP_AT_FIRST", "") not in ("", "0")
     def summary(partial):
         d = {"cases": n, "seconds": round(time.time() - t0, 1), "seed": seed0, "mismatches": bad, "skipped_geometries": int(skipped),
              "per_family": {k: {"cases": counts[k], "mismatches": fails[k]} for k in counts}, "failing_seeds": failing_seeds[:50]}
@@ -1611,6 +1717,8 @@ def run(budget, seed0, verbose=True, progress_path=None, only=None):
                 print("EXC ", fn.__name__, "seed", seed, type(e).__name__, code, str(e)[:120])
             bad += 1; fails[fn.__name__] += 1; failing_seeds.append([fn.__name__, seed])
         n += 1
+        if bad and stop_at_first:
+            break
     return summary(False)
 
 
