@@ -1409,6 +1409,27 @@ int flush_verify(isx_warper* w, hipEvent_t after = nullptr) {
             const double m = 4e-6 * std::max(1.0, std::max(std::fabs(plo), std::fabs(phi)));
             rb.lo[k] = (float)(plo - m); rb.hi[k] = (float)(phi + m);
         }
+        // Two rules the host knows exactly, with no scan, and which the intervals above cannot express:
+        //  - mapForward's u = scale * atan2f(..) never leaves +-scale * pi_f, so a planned u bound beyond +-(int)(scale * pi_f) is unattainable.
+        //    proxy_d_of_u clamps at +-pi: both ends of such a bound's interval became -+2, and a tile that straddles the back seam passed.
+        //  - a pole inside the image dictates one bound (north: br.v = (int)(float)(pi scale), south: tl.v = 0: roi_from_candidates).  A plan
+        //    with another value there was compared with the BORDER's extremum, which can lie inside the wrong interval.
+        // Such a plan gets an empty interval: the check flags it on the device, once per verification and once per replay of a captured one,
+        // as it does every other stale plan.
+        const int u_lim = f2i_host(pd.proj.scale * PI_F);
+        bool stale = pd.planned[0] > u_lim || pd.planned[0] < -u_lim || pd.planned[2] > u_lim || pd.planned[2] < -u_lim;
+        if (sph && north && pd.planned[3] != f2i_host((float)(3.1415926535897932384626433832795 * pd.proj.scale))) stale = true;
+        if (sph && south && pd.planned[1] != 0) stale = true;
+        //  - a pole inside the image also enters the other bounds (tl = min(tl, pole), br = max(br, pole), the pole at u = 0): a planned tl
+        //    above the pole's value or a planned br below it cannot come out, whatever the border's extremum is (a border that does not wind
+        //    around the pole has its own u extremum on one side of 0, and it lay inside such a bound's interval)
+        if (sph && (north || south)) {
+            const int pvi = f2i_host((float)(3.1415926535897932384626433832795 * pd.proj.scale));
+            if (pd.planned[0] > 0 || pd.planned[2] < 0 || pd.planned[3] < 0) stale = true;
+            if (north && pd.planned[1] > pvi) stale = true;
+        }
+        if (stale)
+            for (int k = 0; k < 4; ++k) { rb.lo[k] = std::numeric_limits<float>::infinity(); rb.hi[k] = -std::numeric_limits<float>::infinity(); }
         ISX_LAUNCH("roi_check", 0.0, w->side, k_roi_check_rearm, dim3(1), dim3(1), 0, sk, rb, (int*)(sk + 5));
     }
     ISX_HIP(hipEventRecord(w->ev_scan, w->side));

@@ -204,7 +204,17 @@ int isx_warper_end_batch(isx_warper* w);
 /* The count is STICKY for the life of the handle, for every kind: the device-side counter of the cylindrical / spherical scans is never
  * cleared, and neither is the host-side count of a plane handle's four-corner checks (isx_warper_discard_pending drops verifications that
  * have not run yet, not findings).  After one stale plan every later isx_warper_plan_status of that handle returns ISX_ERR_PLAN: make a
- * new plan on a new handle.                                                                                                           */
+ * new plan on a new handle.
+ * What the check can miss.  The device compares monotone stand-ins of the scanned extrema (the diamond angle d of u; v / scale for the
+ * cylinder, w = -cos(v / scale) for the sphere) with the stand-ins of the ends of each planned bound's truncation interval, and allows
+ * 4e-6 * max(1, |stand-in of either end|) beyond an end: the blind zone is relative IN STAND-IN SPACE.  In pixels that is 4e-6 to 1.6e-5 *
+ * scale for u, 4e-6 * max(scale, |v|) for the cylinder's v, and for the sphere's v about 4e-6 * scale / sin(v / scale) away from the poles
+ * but sqrt(d * d + 8e-6 * scale * scale) - d at d pixels from a pole: 0.0028 * scale at the pole itself (1.7 px at scale 617).  Three
+ * kinds of stale plan are decided exactly, on the host, when the verification is issued, with no allowance: a u bound beyond
+ * +-(int)(scale * pi_f); with a pole of the sphere inside the image, a value other than the pole's own for the bound it dictates
+ * (br.v = (int)(float)(pi * scale) for the north pole, tl.v = 0 for the south pole); and, for the other bounds beside a pole, a tl above
+ * the pole's value or a br below it (tl.u > 0, br.u < 0).  They are counted on the device like every other stale plan: once per
+ * verification, and once per replay of a captured one.                                                                               */
 int isx_warper_plan_status(isx_warper* w, int* mismatches /* synchronises the stream */);
 /* The verification scans of planned warps run on an internal side stream.  isx_warper_join makes the
  * handle's stream wait for them without blocking the host — required before hipStreamEndCapture when

@@ -34,8 +34,8 @@ def test_the_constants_are_the_kernels():
     assert F.GF_PAIR_SIZES == [4095, 4096, 4097, 8192, 8193] and F.GF_DIAG_SIZES == [16383, 16384, 16385]
     assert F.GRAD_WIDTHS == [63, 64, 65, 129] and F.GRAD_HEIGHTS == [15, 16, 17, 33]
     assert F.SEAM_GAP == V.GAP == 10
-    assert [f.__name__ for f in F.CASES[-8:-3]] == F.NEW_FAMILIES and len(F.CASES) == 27
-    assert [f.__name__ for f in F.CASES[-3:]] == ["case_blocks_gain", "case_resize", "case_graphcut_grad"]
+    assert [f.__name__ for f in F.CASES[-9:-4]] == F.NEW_FAMILIES and len(F.CASES) == 28
+    assert [f.__name__ for f in F.CASES[-4:]] == ["case_blocks_gain", "case_resize", "case_graphcut_grad", "case_plan_verify"]
     assert F.GCG_MAX_NODES == 4600 and F.GCG_THIRD_TILE == (24, 16)
     assert F.BG_WIDE_ROWS == [4095, 4096, 4097, 4101] and F.BG_APPLY_WIDTHS == [255, 256, 257, 511, 512, 513] and F.BG_APPLY_HEIGHTS == [15, 16, 17]
     assert [F._BG[k] for k in ("BA_PX", "BA_ROWS", "LU_NT", "LU_RB", "LU_PNT")] == [4, 4, 256, 8, 1024] and F.BG_MAX_UNKNOWNS == 250
@@ -315,3 +315,41 @@ def test_graphcut_grads_structured_class_yields_ties():
     print("ties", ties, "of", seen)
     assert seen == {"structured": 6, "flat_tie": 6} and all(2 * ties[k] >= seen[k] for k in seen), (ties, seen)
     assert patterns == set(graphcut_cases.PATTERNS)                      # every pattern is drawn
+
+
+def test_plan_verify_generator_and_model():
+    """Family 28 (case_plan_verify): every class is drawn and every drawn camera is of its class, judged again from K, R and the size; true
+    plans and shifted ones are both drawn, every bound in both directions; the model skips at most 10 %, calls no true plan MUST_FLAG and three
+    in four MUST_PASS, no moved plan MUST_PASS and nine in ten MUST_FLAG, and leaves at most 10 % of all plans without a claim."""
+    from helpers import plan_verify_np as PV
+    seen, shifts = set(), set()
+    for seed in GEN_SEEDS:
+        c = F.gen_plan_verify(np.random.default_rng(seed))
+        assert c["cls"] in F.PLAN_VERIFY_CLASSES and F.pv_is_of_class(c), (seed, c["cls"])
+        assert (c["w"], c["h"]) in F.PV_SIZES and c["K"].dtype == np.float32 and c["R"].dtype == np.float32
+        assert 0.49 <= c["scale"] / float(c["K"][0, 0]) <= 2.01
+        assert np.allclose(c["R"] @ c["R"].T, np.eye(3), atol=1e-5)
+        assert c["shift"] is None or (c["shift"][0] in range(4) and 1 <= abs(c["shift"][1]) <= 40)
+        if c["cls"] == "zero_bound":
+            assert min(abs(float(c["K"][0, 2])), abs(float(c["K"][1, 2]))) < 0.61
+        seen.add(c["cls"])
+        shifts.add(None if c["shift"] is None else (c["shift"][0], int(np.sign(c["shift"][1]))))
+    assert seen == set(F.PLAN_VERIFY_CLASSES)
+    assert shifts == {None} | set(PV.SHIFTS)
+    verdicts = {True: [], False: []}
+    skips = 0
+    for seed in range(5000, 5240):
+        c = F.gen_plan_verify(np.random.default_rng(seed))
+        want = F.model_plan_verify(c)
+        if isinstance(want, str):
+            assert want == "skip"
+            skips += 1
+            continue
+        assert [PV.f2i(e) for e in want["extrema"]] == want["roi"]
+        verdicts[c["shift"] is None].append(want["verdict"])
+    true, moved = verdicts[True], verdicts[False]
+    print("skips", skips, "true", {v: true.count(v) for v in set(true)}, "moved", {v: moved.count(v) for v in set(moved)})
+    assert skips * 10 <= 240 and len(true) >= 40 and len(moved) >= 120
+    assert PV.MUST_FLAG not in true and true.count(PV.MUST_PASS) * 4 >= len(true) * 3       # (a tile on the back seam has a border pixel within the allowance of it now and then)
+    assert PV.MUST_PASS not in moved and moved.count(PV.MUST_FLAG) * 10 >= len(moved) * 9
+    assert (true + moved).count(PV.NO_CLAIM) * 10 <= len(true + moved)

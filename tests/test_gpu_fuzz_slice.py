@@ -1,9 +1,9 @@
-"""A 20-second, fixed-seed slice of tools/fuzz_parity.py (the randomised HIP-vs-oracle sweep over every entry point, 27 families: warps, the
+"""A 20-second, fixed-seed slice of tools/fuzz_parity.py (the randomised HIP-vs-oracle sweep over every entry point, 28 families: warps, the
 fused tile kernel, the blenders in all precisions and cycles, mask preparation, the seam finder, the linear pair blend, whole pairs through
 PairStitcher, and - against their NumPy models - the plane projector, GainCompensator::feed, the Voronoi and graph-cut seam finders and
-the COLOR_GRAD cost with seam_gradients, BlocksGainCompensator, and cv::resize with the scaled mask stage) under -m gpu, then 8 seconds of
+the COLOR_GRAD cost with seam_gradients, BlocksGainCompensator, cv::resize with the scaled mask stage, and the planned warp's ROI verification) under -m gpu, then 8 seconds of
 the five families before the last three alone, whose shape classes sit on their kernels' tiling constants, 4 seconds of BlocksGainCompensator's,
-4 seconds of cv::resize's and 4 seconds of the last, GraphCutSeamFinder(COST_COLOR_GRAD)'s.  The long soaks are kept as JSON summaries under
+4 seconds of cv::resize's, 4 seconds of GraphCutSeamFinder(COST_COLOR_GRAD)'s and 4 seconds of the last, the ROI verification's.  The long soaks are kept as JSON summaries under
 profiles/."""
 import os
 import sys
@@ -69,6 +69,18 @@ def test_fuzz_slice_graphcut_grad(gpu):
     assert list(out["per_family"]) == ["case_graphcut_grad"] and out["cases"] >= 5 and out["skipped_geometries"] == 0, out
 
 
+def test_fuzz_slice_plan_verify(gpu):
+    """The planned warp's ROI verification alone: random cameras of its ten classes with the true plan or one bound of it moved, against the
+    three-valued model (0 where it must pass, 1 where it must flag)."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "tools"))
+    import fuzz_parity
+    out = fuzz_parity.run(4.0, 20261107, verbose=True, only=["case_plan_verify"])
+    print(out["per_family"], "skipped", out["skipped_geometries"])
+    assert out["mismatches"] == 0, out["failing_seeds"]
+    assert list(out["per_family"]) == ["case_plan_verify"] and out["cases"] >= 20 and out["skipped_geometries"] * 10 <= out["cases"], out
+
+
 # seeds the soaks have tripped over, kept as cases of their own (family, seed):
 #   case_many_tiles 20260988784363 - round 5: 35 tiles in mode 2, two bands; one column strip of the cycle took k_collapse_gather (16-byte level-1
 #   records, produced again on its columns), its neighbour read a shared tile's planar level 1 from feed() behind it
@@ -77,8 +89,10 @@ def test_fuzz_slice_graphcut_grad(gpu):
 #   length 1): as_mat handed it on as the step and isx_resize refused it ("step 3 smaller than a row"); as_mat now gives one row its bytes
 #   case_graphcut_grad 20261166783477 - no soak tripped over it: three tiles in device views, the serpentine against itself flipped, whose first
 #   pair (grid 40 x 103) ties - minimal source side 2 166 nodes, maximal 2 563; kept so that a tie under COST_COLOR_GRAD runs with every suite
+#   case_plan_verify 20261168960453, 20261169325876 - the south pole inside the image beside its first row and a border that stays on one
+#   side of u = 0: the ROI's br.u (tl.u) is the pole's 0, and a planned -1 (1) was compared with the border's own extremum, which it fits
 REGRESSIONS = [("case_many_tiles", 20260988784363), ("case_blocks_gain", 20261078783058), ("case_resize", 20261164820493),
-               ("case_graphcut_grad", 20261166783477)]
+               ("case_graphcut_grad", 20261166783477), ("case_plan_verify", 20261168960453), ("case_plan_verify", 20261169325876)]
 
 
 @pytest.mark.parametrize("family,seed", REGRESSIONS)

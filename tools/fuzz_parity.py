@@ -4,10 +4,12 @@
 Every failure prints the seed of the case so that it can be replayed; exit code = number of failing cases.  With a third argument the
 summary (cases, seconds, seed, mismatches per family) is also written as JSON - the file kept under profiles/.
 tests/test_gpu_fuzz_slice.py runs run(20 s, fixed seed) under -m gpu.
-27 families (CASES); ISX_FUZZ_ONLY=case_a,case_b runs only those; ISX_FUZZ_STOP_AT_FIRST=1 ends the run at the first failing case.
+28 families (CASES); ISX_FUZZ_ONLY=case_a,case_b runs only those; ISX_FUZZ_STOP_AT_FIRST=1 ends the run at the first failing case.
 The 26th, case_resize: cv::resize and the scaled mask stage (isx_resize, isx_mask_dilate_resize_and) against tests/helpers/resize_np.py
 over the shape classes RESIZE_CLASSES.  The 27th, case_graphcut_grad: GraphCutSeamFinder(COST_COLOR_GRAD) against
-tests/helpers/graphcut_grad_np.py over GRAPHCUT_GRAD_CLASSES, the structured patterns of tools/graphcut_patterns.py among them."""
+tests/helpers/graphcut_grad_np.py over GRAPHCUT_GRAD_CLASSES, the structured patterns of tools/graphcut_patterns.py among them.  The 28th,
+case_plan_verify: the planned warp's ROI verification (isx_warper_queue_verify, isx_warper_verify, isx_warper_plan_status) against the
+three-valued model tests/helpers/plan_verify_np.py over PLAN_VERIFY_CLASSES, with the true plan or one bound of it moved."""
 import os
 import sys
 import time
@@ -1659,12 +1661,142 @@ def case_resize(rng):
     _frame_untouched(ps + pw + (po if po is not pw else []))
 
 
-NEW_FAMILIES = ["case_plane_warp", "case_gain_feed", "case_voronoi", "case_graphcut", "case_seam_grad"]
+# ---- the planned warp's ROI verification against tests/helpers/plan_verify_np.py ----------------------------------------------------------
+PLAN_VERIFY_CLASSES = ["cyl_light", "cyl_corner_behind", "cyl_pole", "cyl_rolled", "sph_plain", "sph_north", "sph_south", "cyl_straddle",
+                       "sph_straddle", "on_seam", "sph_pole_edge", "zero_bound"]
+PV_SIZES = [(256, 128), (257, 129), (33, 33), (129, 46), (179, 150), (64, 48), (100, 75), (48, 64), (320, 200)]
+PV_MAX_EXTREMUM = 1.0e6       # a cylindrical v beyond this (a pixel on the cylinder's axis): skipped
+
+
+def _pv_rotation(yaw, pitch, roll):
+    """Ry(yaw) Rx(pitch) Rz(roll) in float32 (rot() above with the angles given)"""
+    a, b, c = pitch, yaw, roll
+    Rx = np.array([[1, 0, 0], [0, np.cos(a), -np.sin(a)], [0, np.sin(a), np.cos(a)]])
+    Ry = np.array([[np.cos(b), 0, np.sin(b)], [0, 1, 0], [-np.sin(b), 0, np.cos(b)]])
+    Rz = np.array([[np.cos(c), -np.sin(c), 0], [np.sin(c), np.cos(c), 0], [0, 0, 1]])
+    return (Ry @ Rx @ Rz).astype(np.float32)
+
+
+def _pv_draw(rng, cls):
+    w, h = _pick(rng, PV_SIZES)
+    wide = cls in ("cyl_pole", "cyl_corner_behind")
+    f = float(np.round((rng.uniform(0.3, 0.8) if wide else rng.uniform(0.4, 2.0)) * max(w, h), 1))
+    scale = float(np.float32(np.round(f * rng.uniform(0.5, 2.0), 1)))
+    cx, cy = float(np.round(w / 2 + rng.uniform(-3, 3), 1)), float(np.round(h / 2 + rng.uniform(-3, 3), 1))
+    kind = 0 if cls.startswith("cyl") else 1 if cls.startswith("sph") else int(rng.integers(0, 2))
+    yaw, pitch, roll = rng.uniform(-0.6, 0.6), rng.uniform(-0.4, 0.4), rng.uniform(-0.2, 0.2)
+    if cls.endswith("_straddle"):
+        yaw = np.pi + rng.uniform(-0.3, 0.3)
+    elif cls == "sph_north":
+        pitch = -np.pi / 2 + rng.uniform(-0.3, 0.3)
+    elif cls == "sph_south":
+        pitch = np.pi / 2 + rng.uniform(-0.3, 0.3)
+    elif cls == "cyl_pole":
+        # the cylinder's axis projects to (cx, cy - f / tan(pitch)) when yaw = roll = 0; the line z_ = 0 through it is then horizontal and
+        # misses the image: a pole 0.3 to 1.9 px above the first row or below the last one
+        py = -rng.uniform(0.3, 1.9) if rng.random() < 0.5 else h - 1 + rng.uniform(0.3, 1.9)
+        yaw, roll, pitch = 0.0, 0.0, float(np.arctan(-f / (py - cy)))
+    elif cls == "cyl_corner_behind":
+        yaw = _pick(rng, [-1, 1]) * rng.uniform(0.9, 1.5)
+    elif cls == "cyl_rolled":
+        roll = _pick(rng, [-1, 1]) * rng.uniform(1.65, 2.8)
+    elif cls == "on_seam":            # a pixel exactly on the back seam: yaw = pi, no roll, the principal point on a column
+        yaw, roll, cx = float(np.pi), 0.0, float(np.round(cx))
+    elif cls == "sph_pole_edge":      # a pole of the sphere inside the image, within 0.8 px of its first or last row (see cyl_pole)
+        kind, yaw, roll = 1, float(rng.uniform(-3.0, 3.0)), 0.0
+        if rng.random() < 0.5:
+            pitch = float(-np.arctan(f / (h - 1 + rng.uniform(-0.8, 0.8) - cy)))              # north, beside the last row
+        else:
+            pitch = float(np.pi - np.arctan(f / (cy - rng.uniform(0.05, 0.8))))               # south, beside the first row
+    elif cls == "zero_bound":
+        yaw = pitch = roll = 0.0
+        if rng.random() < 0.5:
+            cx = float(np.round(rng.uniform(-0.6, 0.6), 1))
+        else:
+            cy = float(np.round(rng.uniform(-0.6, 0.6), 1))
+    K = np.array([[f, 0, cx], [0, f, cy], [0, 0, 1]], np.float32)
+    return dict(cls=cls, kind=kind, w=w, h=h, scale=scale, K=K, R=_pv_rotation(yaw, pitch, roll), yaw=float(yaw))
+
+
+def pv_is_of_class(c):
+    """Is the drawn camera what its class names?  (what gen_plan_verify redraws on, and what tests/test_fuzz_generators.py checks again)"""
+    from helpers import plan_verify_np as PV
+    cls = c["cls"]
+    scan, why = PV.scan_kind(c["kind"], c["K"], c["R"], O.camera(c["K"], c["R"])[2], c["w"], c["h"])
+    north, south = PV.sph_poles(c["K"], c["R"], c["w"], c["h"])
+    if cls == "cyl_light":
+        return scan == "roi_border"
+    if cls in ("cyl_corner_behind", "cyl_pole", "cyl_rolled"):
+        return (scan, why) == ("roi_scan", {"cyl_corner_behind": "corner_behind", "cyl_pole": "cyl_pole", "cyl_rolled": "rolled"}[cls])
+    if cls == "sph_plain":
+        return not north and not south
+    if cls in ("sph_north", "sph_south"):
+        return (north, south) == (cls == "sph_north", cls == "sph_south")
+    if cls.endswith("_straddle"):
+        return abs(c["yaw"] - np.pi) <= 0.3 and not north and not south
+    if cls == "on_seam":
+        return c["yaw"] == float(np.pi) and float(c["K"][0, 2]).is_integer() and c["R"][1, 0] == 0 and not north and not south
+    if cls == "sph_pole_edge":
+        return c["kind"] == 1 and north != south
+    return np.array_equal(c["R"], np.eye(3, dtype=np.float32))       # zero_bound
+
+
+def gen_plan_verify(rng):
+    """A camera of one of PLAN_VERIFY_CLASSES (redrawn until it is of its class) and a plan: the true one (shift None) or the true one with one
+    bound moved by +-1 (mostly) or by up to +-40."""
+    cls = _pick(rng, PLAN_VERIFY_CLASSES)
+    for _ in range(200):
+        c = _pv_draw(rng, cls)
+        if pv_is_of_class(c):
+            break
+    else:
+        raise AssertionError("no camera of class " + cls)
+    c["shift"] = None
+    if rng.random() < 0.7:
+        c["shift"] = (int(rng.integers(0, 4)), int(_pick(rng, [-1, 1])) * (1 if rng.random() < 0.8 else int(rng.integers(2, 41))))
+    return c
+
+
+def model_plan_verify(c):
+    """-> dict(roi, plan, verdict, per, extrema) or "skip" (an extremum that is not finite or beyond PV_MAX_EXTREMUM)"""
+    from helpers import plan_verify_np as PV
+    t = PV.truth(O, c["kind"], c["scale"], c["K"], c["R"], c["w"], c["h"])
+    if not all(np.isfinite(e) and abs(e) < PV_MAX_EXTREMUM for e in t["extrema"]):
+        return "skip"
+    plan = list(t["roi"]) if c["shift"] is None else PV.shifted(t["roi"], *c["shift"])
+    verdict, per = PV.verdict(c["kind"], c["scale"], plan, t["extrema"], t["north"], t["south"])
+    return dict(roi=t["roi"], plan=plan, verdict=verdict, per=per, extrema=t["extrema"])
+
+
+def case_plan_verify(rng):
+    """isx_warper_queue_verify -> isx_warper_verify -> isx_warper_plan_status on a fresh handle against the three-valued model: the count is
+    0 where the model says MUST_PASS, 1 where it says MUST_FLAG, either where it makes no claim."""
+    import ctypes as C
+    c = gen_plan_verify(rng)
+    want = model_plan_verify(c)
+    if want == "skip":
+        return "skip"
+    w = (G.CylindricalWarper() if c["kind"] == 0 else G.SphericalWarper()).create(c["scale"])
+    w.queue_verify((c["w"], c["h"]), c["K"], c["R"], want["plan"])
+    w.verify()
+    n = C.c_int(-1)
+    rc = w._lib.isx_warper_plan_status(w._h, C.byref(n))
+    note = (c["cls"], c["kind"], (c["w"], c["h"]), c["scale"], c["K"].tolist(), c["R"].tolist(), c["shift"], want)
+    assert rc in (0, 8) and (rc == 8) == (n.value != 0) and n.value in (0, 1), (rc, n.value) + note
+    if want["verdict"] == "must_pass":
+        assert n.value == 0, note
+    if want["verdict"] == "must_flag":
+        assert n.value == 1, note
+    return None
+
+
+NEW_FAMILIES = ["case_plane_warp","case_gain_feed", "case_voronoi", "case_graphcut", "case_seam_grad"]
 
 
 CASES = [case_warp, case_blend, case_feather, case_prep, case_seam, case_blend_float_and_many, case_pipeline, case_find, case_warp_fused,
          case_linear_pair, case_strip, case_strip_feather, case_batch, case_s16_tiles, case_round4_calls, case_many_tiles, case_fused_feed, case_round6_calls,
-         case_long_lived, case_plane_warp, case_gain_feed, case_voronoi, case_graphcut, case_seam_grad, case_blocks_gain, case_resize, case_graphcut_grad]
+         case_long_lived, case_plane_warp, case_gain_feed, case_voronoi, case_graphcut, case_seam_grad, case_blocks_gain, case_resize, case_graphcut_grad,
+         case_plan_verify]
 
 
 def run(budget, seed0, verbose=True, progress_path=None, only=None):
