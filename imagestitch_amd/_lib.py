@@ -111,6 +111,8 @@ _SIGS = {
     "isx_voronoi_seam_find": [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _MP, C.c_int, C.c_void_p],
     "isx_voronoi_seam_reserve": [C.c_int, C.c_int, C.c_int],
     "isx_voronoi_seam_release": [],
+    "isx_match_features": [C.c_int, _MP, _MP, _IP, C.c_int, _IP, C.c_float, _MP, _MP, _MP, _MP, _IP, C.c_int, C.c_void_p],
+    "isx_match_release": [],
     "isx_seam_estimate": [_MP, _MP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _MP, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int,
                           C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_void_p],
     "isx_seam_estimate_cost": [_MP, _MP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _MP, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int,

@@ -1,0 +1,491 @@
+// match.hip — the features matcher of the M demo (the reference's 特征点匹配/特征点匹配/特征点匹配.cpp) on gfx950:
+//   isx_match_features   BestOf2NearestMatcher1 matcher(false, 0.3f, 6, 6); matcher(features, pairwise_matches)      M:307-308
+//                        = near_pairs M:131-135, CpuMatcher1::match M:232-289 per pair, the point gather M:164-179
+//   isx_match_release    returns the per-thread scratch
+//
+// The specification (DESIGN.md §8 "Features matcher"; tests/helpers/match_np.py): exact 2-nearest neighbours by (Hamming distance, row)
+// in both directions, the ratio test (float)d0 < k * (float)d1 with k = 1.f - match_conf, 1->2 matches in query order, then the 2->1
+// matches 1->2 did not accept.  An accepted match has a unique nearest neighbour, so the list is that of any exact brute-force matcher;
+// the FLANN LSH index of M:241-250 is not reproduced.
+//
+// At most three launches per call, however many pairs, no atomics, nothing read back on device mats:
+//   k_mt_pack      the descriptors of every DEVICE mat, byte loads (any pointer and step), into one dense array of 8 dwords per row; host
+//                  mats are packed on the host into the upload that carries the tables.  Every image is packed once, not once per pair.
+//   k_mt_search    one block per work item (pair, direction, query block, train chunk): a thread owns one query row in 8 registers, the
+//                  chunk's train rows pass through an LDS tile that every lane reads at the same address (a broadcast), a candidate costs
+//                  8 xor + 8 accumulating popcounts and the update of the two smallest keys distance << 22 | row; the two keys of the
+//                  chunk go to the partials.  Keys are unique per query, so the later merge is exact whatever the chunking.
+//   k_mt_finalise  one block per pair: merges the partials, writes knn, runs the ratio test and - for 2->1 - the lookup "1->2 accepted
+//                  this row with that neighbour", compacts in order with a ballot prefix scan and writes matches, points and the count.
+#include "isx_device.hpp"
+#include "pairwise.hpp"
+
+using namespace isx;
+using namespace isxd;
+
+namespace {
+
+constexpr int MT_Q = ISX_MATCH_QUERY_BLOCK;      // queries (threads) per search block
+constexpr int MT_T = ISX_MATCH_TRAIN_TILE;       // train rows per LDS tile
+constexpr int MT_CHUNK = ISX_MATCH_TRAIN_CHUNK;  // train rows per work item (times a factor once an image passes MT_CHUNK * MT_MAX_SPLIT rows)
+constexpr int MT_MAX_SPLIT = 32;                 // chunks per (pair, direction) at most: bounds the partials at 256 B per query
+constexpr int MT_KEY_SHIFT = 22;
+constexpr unsigned MT_IDX_MASK = (1u << MT_KEY_SHIFT) - 1u;
+constexpr unsigned MT_NONE = 0xFFFFFFFFu;        // "no neighbour": above every key (a key is at most 256 << 22 | 2^22 - 1)
+constexpr int MT_FIN_NT = 256;
+constexpr int MT_PACK_ROWS = 32;                 // rows per block of k_mt_pack (8 threads a row)
+static_assert(MT_T == MT_Q, "a thread of the search block stages one train row per tile");
+static_assert(MT_CHUNK % MT_T == 0, "a chunk is whole tiles");
+static_assert(ISX_MATCH_MAX_TOTAL_ROWS <= (1 << MT_KEY_SHIFT) && (256u << MT_KEY_SHIFT) < MT_NONE, "the packed key");
+
+struct MtImage {
+    const unsigned char* desc; long long desc_step;   // the caller's device mat (k_mt_pack); unused for a host mat
+    const unsigned char* kp; long long kp_step;       // n x 2 floats: the caller's device mat or the staged copy of a host mat
+    int rows, off;                                    // off: first row in the packed array
+    float half_w, half_h;                             // img_size * 0.5f
+};
+
+struct MtPair {
+    int from, to;                        // images
+    int nchunks[2], chunk_rows[2];       // per direction (0: 1->2, the train set is image `to`)
+    long long part_off[2];               // first uint2 of the direction's partials: [query][chunk]
+    long long acc_off;                   // n_from ints: the row 1->2 accepted for each query, or -1
+    int* matches; long long matches_step;
+    float* points; long long points_step;
+    int* knn[2]; long long knn_step[2];
+    int* count;
+};
+
+template <class T>
+__device__ __forceinline__ T* as_global(T* p) {      // as in blend.hip: a wave-uniform table pointer the compiler may load through global_load
+    const unsigned long long u = (unsigned long long)p;
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
+    return (T*)(__attribute__((address_space(1))) T*)(((unsigned long long)hi << 32) | lo);
+}
+
+// blocks: (image, first row) per block
+__global__ __launch_bounds__(MT_PACK_ROWS * 8) void k_mt_pack(const MtImage* __restrict__ imgs, const int2* __restrict__ blocks, unsigned* __restrict__ packed) {
+    imgs = as_global(imgs); blocks = as_global(blocks); packed = as_global(packed);
+    const int2 b = blocks[blockIdx.x];
+    const MtImage& I = imgs[b.x];
+    const int row = b.y + (int)(threadIdx.x >> 3), w = (int)(threadIdx.x & 7);
+    if (row >= I.rows) return;
+    const unsigned char* p = as_global(I.desc) + (long long)row * I.desc_step + 4 * w;
+    const unsigned v = (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16) | ((unsigned)p[3] << 24);
+    packed[((size_t)I.off + row) * 8 + w] = v;
+}
+
+__device__ __forceinline__ void mt_update(unsigned key, unsigned& k0, unsigned& k1) {
+    k1 = min(k1, max(k0, key));
+    k0 = min(k0, key);
+}
+
+// work: (pair, direction, query block, train chunk) per block
+__global__ __launch_bounds__(MT_Q) void k_mt_search(const MtPair* __restrict__ pairs, const MtImage* __restrict__ imgs, const int4* __restrict__ work,
+                                                    const uint4* __restrict__ packed, uint2* __restrict__ partial) {
+    __shared__ uint4 s_tile[2 * MT_T];
+    pairs = as_global(pairs); imgs = as_global(imgs); work = as_global(work); packed = as_global(packed); partial = as_global(partial);
+    const int4 wi = work[blockIdx.x];
+    const MtPair& P = pairs[wi.x];
+    const int dir = wi.y, t = (int)threadIdx.x;
+    const MtImage& Q = imgs[dir ? P.to : P.from];
+    const MtImage& R = imgs[dir ? P.from : P.to];
+    const int nq = Q.rows, nt = R.rows, nch = P.nchunks[dir], crows = P.chunk_rows[dir];
+    const int q = wi.z * MT_Q + t;
+    uint4 qa = make_uint4(0u, 0u, 0u, 0u), qb = qa;
+    if (q < nq) { qa = packed[2 * ((size_t)Q.off + q)]; qb = packed[2 * ((size_t)Q.off + q) + 1]; }
+    const int t0 = wi.w * crows, t1 = min(nt, t0 + crows);       // t0 < nt: the host makes no empty chunk
+    unsigned k0 = MT_NONE, k1 = MT_NONE;
+    for (int tb = t0; tb < t1; tb += MT_T) {
+        __syncthreads();                                          // the previous tile's readers are done
+        if (tb + t < t1) { s_tile[2 * t] = packed[2 * ((size_t)R.off + tb + t)]; s_tile[2 * t + 1] = packed[2 * ((size_t)R.off + tb + t) + 1]; }
+        __syncthreads();
+        const int n = min(MT_T, t1 - tb);
+#pragma unroll 4
+        for (int j = 0; j < n; ++j) {
+            const uint4 a = s_tile[2 * j], b = s_tile[2 * j + 1];
+            unsigned d = __popc(qa.x ^ a.x);
+            d += __popc(qa.y ^ a.y); d += __popc(qa.z ^ a.z); d += __popc(qa.w ^ a.w);
+            d += __popc(qb.x ^ b.x); d += __popc(qb.y ^ b.y); d += __popc(qb.z ^ b.z); d += __popc(qb.w ^ b.w);
+            mt_update((d << MT_KEY_SHIFT) | (unsigned)(tb + j), k0, k1);
+        }
+    }
+    if (q < nq) partial[P.part_off[dir] + (long long)q * nch + wi.w] = make_uint2(k0, k1);
+}
+
+__global__ __launch_bounds__(MT_FIN_NT) void k_mt_finalise(const MtPair* __restrict__ pairs, const MtImage* __restrict__ imgs, const uint2* __restrict__ partial,
+                                                           int* acc, float k) {
+    __shared__ int s_cnt[MT_FIN_NT / WAVE];
+    pairs = as_global(pairs); imgs = as_global(imgs); partial = as_global(partial); acc = as_global(acc);
+    const MtPair& P = pairs[blockIdx.x];
+    const MtImage& F = imgs[P.from];
+    const MtImage& T = imgs[P.to];
+    const int t = (int)threadIdx.x, lane = t & (WAVE - 1), wv = t / WAVE;
+    if (F.rows == 0 || T.rows == 0) {                            // M:134: not a near pair
+        if (t == 0) *as_global(P.count) = 0;
+        return;
+    }
+    int* accp = acc + P.acc_off;
+    int* const mrows = as_global(P.matches);
+    float* const prows = as_global(P.points);
+    const unsigned char* const kpf = as_global(F.kp);
+    const unsigned char* const kpt = as_global(T.kp);
+    int base = 0;
+    for (int dir = 0; dir < 2; ++dir) {
+        const int nq = dir ? T.rows : F.rows, nt = dir ? F.rows : T.rows, nch = P.nchunks[dir];
+        const uint2* part = partial + P.part_off[dir];
+        int* knn = as_global(P.knn[dir]);
+        for (int q0 = 0; q0 < nq; q0 += MT_FIN_NT) {
+            const int q = q0 + t;
+            bool ok = false;
+            int i0 = -1, d0 = -1;
+            if (q < nq) {
+                unsigned k0 = MT_NONE, k1 = MT_NONE;
+                for (int c = 0; c < nch; ++c) {
+                    const uint2 p = part[(long long)q * nch + c];
+                    mt_update(p.x, k0, k1); mt_update(p.y, k0, k1);
+                }
+                const int i1 = k1 == MT_NONE ? -1 : (int)(k1 & MT_IDX_MASK), d1 = k1 == MT_NONE ? -1 : (int)(k1 >> MT_KEY_SHIFT);
+                i0 = k0 == MT_NONE ? -1 : (int)(k0 & MT_IDX_MASK); d0 = k0 == MT_NONE ? -1 : (int)(k0 >> MT_KEY_SHIFT);
+                if (knn) {
+                    int* o = (int*)((char*)knn + (long long)q * P.knn_step[dir]);
+                    o[0] = i0; o[1] = d0; o[2] = i1; o[3] = d1;
+                }
+                if (nt >= 2) ok = (float)d0 < k * (float)d1;     // M:260, M:267 (-ffp-contract=off: one rounded multiply)
+                if (dir == 0) accp[q] = ok ? i0 : -1;
+                else if (ok) ok = accp[i0] != q;                 // M:285
+            }
+            const unsigned long long bal = __ballot(ok);
+            if (lane == 0) s_cnt[wv] = __popcll(bal);
+            __syncthreads();
+            int pos = base + __popcll(bal & ((1ull << lane) - 1ull)), total = 0;
+#pragma unroll
+            for (int i = 0; i < MT_FIN_NT / WAVE; ++i) { pos += i < wv ? s_cnt[i] : 0; total += s_cnt[i]; }
+            base += total;
+            if (ok) {
+                const int a = dir ? i0 : q, b = dir ? q : i0;    // rows of `from` and of `to`: M:270, M:286
+                int* o = (int*)((char*)mrows + (long long)pos * P.matches_step);
+                o[0] = a; o[1] = b; o[2] = d0;
+                if (prows) {
+                    const float* pa = (const float*)(kpf + (long long)a * F.kp_step);
+                    const float* pb = (const float*)(kpt + (long long)b * T.kp_step);
+                    float* op = (float*)((char*)prows + (long long)pos * P.points_step);
+                    op[0] = pa[0] - F.half_w; op[1] = pa[1] - F.half_h;      // M:170-173
+                    op[2] = pb[0] - T.half_w; op[3] = pb[1] - T.half_h;      // M:175-178
+                }
+            }
+            __syncthreads();                                      // s_cnt is rewritten by the next step; acc is complete before 2->1 reads it
+        }
+    }
+    if (t == 0) *as_global(P.count) = base;
+}
+
+struct MtScratch {
+    DevBuf work;
+    int device = -1;
+    void* pin = nullptr;                 // the upload: tables, staged keypoints and packed descriptors of host mats
+    size_t pin_cap = 0;
+    hipEvent_t uploaded = nullptr;       // recorded after the upload that reads `pin`
+    bool pending = false;
+    hipEvent_t done = nullptr;           // recorded after the last kernel: a call on another stream waits for it before it reuses `work`
+    hipStream_t last = nullptr;
+    bool ran = false;
+};
+
+int mt_wait_upload(MtScratch& s) {
+    if (s.pending) { ISX_HIP(hipEventSynchronize(s.uploaded)); s.pending = false; }
+    return ISX_OK;
+}
+int mt_release(MtScratch& s) {
+    ISX_TRY(mt_wait_upload(s));
+    if (s.uploaded) { ISX_HIP(hipEventDestroy(s.uploaded)); s.uploaded = nullptr; }
+    if (s.done) { ISX_HIP(hipEventDestroy(s.done)); s.done = nullptr; }
+    s.ran = false;
+    if (s.pin) { ISX_HIP(hipHostFree(s.pin)); s.pin = nullptr; s.pin_cap = 0; }
+    s.work.release();
+    s.device = -1;
+    return ISX_OK;
+}
+
+struct Bump {                            // offsets into one buffer, 256-byte aligned
+    size_t at = 0;
+    size_t take(size_t bytes) { const size_t o = at; at += (bytes + 255) & ~(size_t)255; return o; }
+};
+
+// an output mat of at least rows x cols elements of 4 bytes; null data is fine where no row is needed
+int mt_check_out(const isx_mat& m, int type, long long rows, int cols, int device, const char* who, const char* what, int index) {
+    ISX_CHECK_ARG(m.type == type, ISX_ERR_TYPE, "%s: %s %d is %s (%s)", who, what, index, type_name(m.type), type_name(type));
+    ISX_CHECK_ARG(m.rows >= rows && (rows == 0 || m.cols >= cols), ISX_ERR_SIZE, "%s: %s %d is %d x %d, the call needs %lld x %d", who, what, index,
+                  m.rows, m.cols, rows, cols);
+    if (rows == 0) return ISX_OK;
+    ISX_CHECK_ARG(m.data != nullptr, ISX_ERR_INVALID, "%s: %s %d has a null data pointer", who, what, index);
+    ISX_CHECK_ARG(m.step >= (size_t)m.cols * 4 || m.rows == 1, ISX_ERR_INVALID, "%s: %s %d: step %zu smaller than a row", who, what, index, m.step);
+    ISX_CHECK_ARG(((uintptr_t)m.data & 3) == 0 && (m.step & 3) == 0, ISX_ERR_INVALID, "%s: %s %d is not 4-byte aligned in pointer and step", who, what, index);
+    ISX_CHECK_ARG(m.device < 0 || m.device == device, ISX_ERR_INVALID, "%s: %s %d lives on device %d, the call runs on %d", who, what, index, m.device, device);
+    return ISX_OK;
+}
+
+// a host output mat's rows [0, rows) x cols elements, back from its dense staged copy
+int mt_copy_back(const isx_mat& m, const void* staged, int rows, int cols, hipStream_t st) {
+    if (rows <= 0) return ISX_OK;
+    ISX_HIP(hipMemcpy2DAsync(m.data, m.step, staged, (size_t)cols * 4, (size_t)cols * 4, (size_t)rows, hipMemcpyDeviceToHost, st));
+    return ISX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int isx_match_release(void) ISX_ENTRY {
+    clear_error();
+    return mt_release(per_thread<MtScratch>());
+} ISX_EXIT("isx_match_release")
+
+int isx_match_features(int num_images, const isx_mat* descriptors, const isx_mat* keypoints, const int* image_sizes_wh,
+                       int num_pairs, const int* pairs_ij, float match_conf, isx_mat* matches, isx_mat* points, isx_mat* counts,
+                       isx_mat* knn, int* info, int device, void* hip_stream) ISX_ENTRY {
+    clear_error();
+    const char* who = "match_features";
+    // ---- checks: all of them before anything is written or enqueued ----
+    ISX_CHECK_ARG(num_images >= 0 && num_pairs >= 0, ISX_ERR_INVALID, "%s: %d images, %d pairs", who, num_images, num_pairs);
+    ISX_CHECK_ARG(num_images == 0 || descriptors, ISX_ERR_INVALID, "%s: null descriptors", who);
+    ISX_CHECK_ARG(num_pairs == 0 || (pairs_ij && matches && counts), ISX_ERR_INVALID, "%s: null pairs, matches or counts", who);
+    ISX_CHECK_ARG(!keypoints || image_sizes_wh, ISX_ERR_INVALID, "%s: keypoints without image sizes", who);
+    ISX_CHECK_ARG(!points || keypoints, ISX_ERR_INVALID, "%s: points without keypoints", who);
+    ISX_CHECK_ARG(match_conf >= 0.f && match_conf < 1.f, ISX_ERR_INVALID, "%s: match_conf %g is not in [0, 1)", who, (double)match_conf);
+    for (int p = 0; p < num_pairs; ++p) {
+        const int i = pairs_ij[2 * p], j = pairs_ij[2 * p + 1];
+        ISX_CHECK_ARG(i >= 0 && i < j && j < num_images, ISX_ERR_INVALID, "%s: pair %d is (%d, %d) of %d images (from < to)", who, p, i, j, num_images);
+    }
+    long long total_rows = 0;
+    for (int i = 0; i < num_images; ++i) {
+        const isx_mat& m = descriptors[i];
+        ISX_CHECK_ARG(m.type == ISX_8UC1, ISX_ERR_TYPE, "%s: descriptors %d are %s (CV_8UC1)", who, i, type_name(m.type));
+        ISX_CHECK_ARG(m.rows >= 0, ISX_ERR_INVALID, "%s: descriptors %d have %d rows", who, i, m.rows);
+        if (m.rows > 0) {
+            // CV_32F (SURF) descriptors and binary descriptors of another length are not built
+            ISX_CHECK_ARG(m.cols == 32, ISX_ERR_UNSUPPORTED, "%s: descriptors %d have %d columns (32-byte ORB descriptors only)", who, i, m.cols);
+            ISX_CHECK_ARG(m.rows <= ISX_MATCH_MAX_ROWS, ISX_ERR_UNSUPPORTED, "%s: descriptors %d have %d rows (at most %d)", who, i, m.rows, ISX_MATCH_MAX_ROWS);
+            ISX_CHECK_ARG(m.data != nullptr, ISX_ERR_INVALID, "%s: descriptors %d have a null data pointer", who, i);
+            ISX_CHECK_ARG(m.step >= 32 || m.rows == 1, ISX_ERR_INVALID, "%s: descriptors %d: step %zu smaller than a row", who, i, m.step);
+            ISX_CHECK_ARG(m.device < 0 || m.device == device, ISX_ERR_INVALID, "%s: descriptors %d live on device %d, the call runs on %d", who, i, m.device, device);
+        }
+        total_rows += m.rows;
+        if (keypoints) {
+            const isx_mat& kp = keypoints[i];
+            ISX_CHECK_ARG(kp.type == ISX_32FC1, ISX_ERR_TYPE, "%s: keypoints %d are %s (CV_32FC1)", who, i, type_name(kp.type));
+            ISX_CHECK_ARG(kp.rows == m.rows && (m.rows == 0 || kp.cols == 2), ISX_ERR_SIZE, "%s: keypoints %d are %d x %d, the descriptors have %d rows", who, i,
+                          kp.rows, kp.cols, m.rows);
+            if (m.rows > 0) {
+                ISX_CHECK_ARG(kp.data != nullptr && (kp.step >= 8 || kp.rows == 1), ISX_ERR_INVALID, "%s: keypoints %d: null data or a step smaller than a row", who, i);
+                ISX_CHECK_ARG(((uintptr_t)kp.data & 3) == 0 && (kp.step & 3) == 0, ISX_ERR_INVALID, "%s: keypoints %d are not 4-byte aligned in pointer and step", who, i);
+                ISX_CHECK_ARG(kp.device < 0 || kp.device == device, ISX_ERR_INVALID, "%s: keypoints %d live on device %d, the call runs on %d", who, i, kp.device, device);
+            }
+        }
+    }
+    ISX_CHECK_ARG(total_rows <= ISX_MATCH_MAX_TOTAL_ROWS, ISX_ERR_UNSUPPORTED, "%s: %lld descriptor rows in all (at most %d)", who, total_rows, ISX_MATCH_MAX_TOTAL_ROWS);
+    int searched = 0;
+    bool any_host_out = false;
+    if (num_pairs > 0) {
+        ISX_TRY(mt_check_out(*counts, ISX_32SC1, 1, num_pairs, device, who, "counts", 0));
+        any_host_out |= counts->device < 0;
+    }
+    for (int p = 0; p < num_pairs; ++p) {
+        const int nf = descriptors[pairs_ij[2 * p]].rows, nt = descriptors[pairs_ij[2 * p + 1]].rows;
+        const bool run = nf > 0 && nt > 0;
+        const long long rows = run ? (long long)nf + nt : 0;
+        searched += run;
+        ISX_TRY(mt_check_out(matches[p], ISX_32SC1, rows, 3, device, who, "matches", p));
+        any_host_out |= run && matches[p].device < 0;
+        if (points) {
+            ISX_TRY(mt_check_out(points[p], ISX_32FC1, rows, 4, device, who, "points", p));
+            any_host_out |= run && points[p].device < 0;
+        }
+        if (knn)
+            for (int d = 0; d < 2; ++d) {
+                ISX_TRY(mt_check_out(knn[2 * p + d], ISX_32SC1, run ? (d ? nt : nf) : 0, 4, device, who, "knn", 2 * p + d));
+                any_host_out |= run && knn[2 * p + d].device < 0;
+            }
+    }
+    ISX_HIP(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    ISX_HIP(hipStreamIsCapturing(st, &cs));
+    ISX_CHECK_ARG(cs == hipStreamCaptureStatusNone, ISX_ERR_STATE, "%s: the stream is capturing (the call uploads its tables and may stage host mats)", who);
+    if (num_pairs == 0) {
+        if (info) { info[0] = 0; info[1] = 0; }
+        return ISX_OK;
+    }
+
+    // ---- the plan: packed rows (host mats first: they travel in the upload), chunking, work items ----
+    std::vector<MtImage> imgs((size_t)num_images);
+    int host_rows = 0, dev_rows = 0;
+    for (int i = 0; i < num_images; ++i)
+        if (descriptors[i].rows > 0 && descriptors[i].device < 0) { imgs[i].off = host_rows; host_rows += descriptors[i].rows; }
+    std::vector<int2> pack_blocks;
+    for (int i = 0; i < num_images; ++i) {
+        const isx_mat& m = descriptors[i];
+        MtImage& I = imgs[i];
+        I.rows = m.rows; I.desc = nullptr; I.desc_step = 0; I.kp = nullptr; I.kp_step = 0; I.half_w = I.half_h = 0.f;
+        if (m.rows == 0) { I.off = 0; continue; }
+        if (m.device >= 0) {
+            I.off = host_rows + dev_rows; dev_rows += m.rows;
+            I.desc = (const unsigned char*)m.data; I.desc_step = (long long)m.step;
+            for (int r = 0; r < m.rows; r += MT_PACK_ROWS) pack_blocks.push_back(make_int2(i, r));
+        }
+        if (keypoints) { I.half_w = (float)image_sizes_wh[2 * i] * 0.5f; I.half_h = (float)image_sizes_wh[2 * i + 1] * 0.5f; }
+    }
+    std::vector<MtPair> prs((size_t)num_pairs);
+    std::vector<int4> work;
+    long long part_count = 0, acc_count = 0;
+    for (int p = 0; p < num_pairs; ++p) {
+        MtPair& P = prs[p];
+        std::memset(&P, 0, sizeof(P));
+        P.from = pairs_ij[2 * p]; P.to = pairs_ij[2 * p + 1];
+        const int n[2] = {imgs[P.from].rows, imgs[P.to].rows};
+        if (n[0] == 0 || n[1] == 0) continue;
+        P.acc_off = acc_count; acc_count += n[0];
+        for (int d = 0; d < 2; ++d) {
+            const int nq = n[d], nt = n[1 - d];
+            // MT_CHUNK rows a work item until an image passes MT_CHUNK * MT_MAX_SPLIT rows, whole multiples of it from there
+            P.chunk_rows[d] = MT_CHUNK * cdiv(nt, MT_CHUNK * MT_MAX_SPLIT);
+            P.nchunks[d] = cdiv(nt, P.chunk_rows[d]);
+            P.part_off[d] = part_count; part_count += (long long)nq * P.nchunks[d];
+            for (int qb = 0; qb < cdiv(nq, MT_Q); ++qb)
+                for (int c = 0; c < P.nchunks[d]; ++c) work.push_back(make_int4(p, d, qb, c));
+        }
+    }
+    ISX_CHECK_ARG(work.size() <= (size_t)INT_MAX, ISX_ERR_UNSUPPORTED, "%s: %zu work items", who, work.size());
+
+    // ---- one buffer: [upload: tables | staged keypoints of host mats | packed rows of host mats] [packed rows of device mats] [partials] [acc]
+    //      [staged host outputs]
+    Bump lay;
+    const size_t o_imgs = lay.take(imgs.size() * sizeof(MtImage)), o_prs = lay.take(prs.size() * sizeof(MtPair));
+    const size_t o_work = lay.take(work.size() * sizeof(int4)), o_pblk = lay.take(pack_blocks.size() * sizeof(int2));
+    std::vector<size_t> o_kp((size_t)num_images, 0);
+    if (keypoints)
+        for (int i = 0; i < num_images; ++i)
+            if (imgs[i].rows > 0 && keypoints[i].device < 0) o_kp[i] = lay.take((size_t)imgs[i].rows * 8);
+    const size_t o_packed = lay.take(0);
+    const size_t upload_bytes = o_packed + (size_t)host_rows * 32;
+    lay.take((size_t)(host_rows + dev_rows) * 32);
+    const size_t o_part = lay.take((size_t)part_count * sizeof(uint2)), o_acc = lay.take((size_t)acc_count * sizeof(int));
+    const size_t o_counts = counts->device < 0 ? lay.take((size_t)num_pairs * 4) : 0;
+    std::vector<size_t> o_m((size_t)num_pairs, 0), o_p((size_t)num_pairs, 0), o_k((size_t)2 * num_pairs, 0);
+    for (int p = 0; p < num_pairs; ++p) {
+        const int nf = imgs[prs[p].from].rows, nt = imgs[prs[p].to].rows;
+        if (nf == 0 || nt == 0) continue;
+        if (matches[p].device < 0) o_m[p] = lay.take((size_t)(nf + nt) * 12);
+        if (points && points[p].device < 0) o_p[p] = lay.take((size_t)(nf + nt) * 16);
+        if (knn)
+            for (int d = 0; d < 2; ++d)
+                if (knn[2 * p + d].device < 0) o_k[2 * p + d] = lay.take((size_t)(d ? nt : nf) * 16);
+    }
+
+    MtScratch& s = per_thread<MtScratch>();
+    if (s.device != device) { ISX_TRY(mt_release(s)); s.device = device; }
+    ISX_TRY(mt_wait_upload(s));                                   // the previous call's upload has read `pin`
+    ISX_TRY(s.work.reserve(lay.at));
+    if (s.pin_cap < upload_bytes) {
+        if (s.pin) { ISX_HIP(hipHostFree(s.pin)); s.pin = nullptr; s.pin_cap = 0; }
+        const size_t want = std::max<size_t>(upload_bytes + upload_bytes / 2, 1u << 16);
+        ISX_HIP(hipHostMalloc(&s.pin, want, hipHostMallocDefault));
+        s.pin_cap = want;
+    }
+    if (!s.uploaded) ISX_HIP(hipEventCreateWithFlags(&s.uploaded, hipEventDisableTiming));
+    if (!s.done) ISX_HIP(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+    if (s.ran && s.last != st) ISX_HIP(hipStreamWaitEvent(st, s.done, 0));
+    char* const dev = (char*)s.work.p;
+    char* const pin = (char*)s.pin;
+
+    // ---- fill the upload ----
+    for (int i = 0; i < num_images; ++i) {
+        MtImage& I = imgs[i];
+        if (I.rows == 0) continue;
+        const isx_mat& m = descriptors[i];
+        if (m.device < 0)
+            for (int r = 0; r < m.rows; ++r) std::memcpy(pin + o_packed + ((size_t)I.off + r) * 32, (const char*)m.data + (size_t)r * m.step, 32);
+        if (!keypoints) continue;
+        const isx_mat& kp = keypoints[i];
+        if (kp.device < 0) {
+            for (int r = 0; r < kp.rows; ++r) std::memcpy(pin + o_kp[i] + (size_t)r * 8, (const char*)kp.data + (size_t)r * kp.step, 8);
+            I.kp = (const unsigned char*)dev + o_kp[i]; I.kp_step = 8;
+        } else {
+            I.kp = (const unsigned char*)kp.data; I.kp_step = (long long)kp.step;
+        }
+    }
+    for (int p = 0; p < num_pairs; ++p) {
+        MtPair& P = prs[p];
+        P.count = counts->device < 0 ? (int*)(dev + o_counts) + p : (int*)counts->data + p;
+        if (imgs[P.from].rows == 0 || imgs[P.to].rows == 0) continue;
+        P.matches = matches[p].device < 0 ? (int*)(dev + o_m[p]) : (int*)matches[p].data;
+        P.matches_step = matches[p].device < 0 ? 12 : (long long)matches[p].step;
+        if (points) {
+            P.points = points[p].device < 0 ? (float*)(dev + o_p[p]) : (float*)points[p].data;
+            P.points_step = points[p].device < 0 ? 16 : (long long)points[p].step;
+        }
+        if (knn)
+            for (int d = 0; d < 2; ++d) {
+                const isx_mat& km = knn[2 * p + d];
+                P.knn[d] = km.device < 0 ? (int*)(dev + o_k[2 * p + d]) : (int*)km.data;
+                P.knn_step[d] = km.device < 0 ? 16 : (long long)km.step;
+            }
+    }
+    std::memcpy(pin + o_imgs, imgs.data(), imgs.size() * sizeof(MtImage));
+    std::memcpy(pin + o_prs, prs.data(), prs.size() * sizeof(MtPair));
+    std::memcpy(pin + o_work, work.data(), work.size() * sizeof(int4));
+    std::memcpy(pin + o_pblk, pack_blocks.data(), pack_blocks.size() * sizeof(int2));
+    ISX_HIP(hipMemcpyAsync(dev, pin, upload_bytes, hipMemcpyHostToDevice, st));
+    ISX_HIP(hipEventRecord(s.uploaded, st));
+    s.pending = true;
+
+    // ---- at most three launches ----
+    const MtImage* d_imgs = (const MtImage*)(dev + o_imgs);
+    const MtPair* d_prs = (const MtPair*)(dev + o_prs);
+    int launches = 0;
+    if (!pack_blocks.empty()) {
+        ISX_LAUNCH("match_pack", (double)dev_rows * 64.0, st, k_mt_pack, dim3((unsigned)pack_blocks.size()), dim3(MT_PACK_ROWS * 8), 0, d_imgs,
+                   (const int2*)(dev + o_pblk), (unsigned*)(dev + o_packed));
+        ++launches;
+    }
+    if (!work.empty()) {
+        ISX_LAUNCH("match_search", (double)work.size() * (MT_Q + MT_CHUNK) * 32.0, st, k_mt_search, dim3((unsigned)work.size()), dim3(MT_Q), 0, d_prs, d_imgs,
+                   (const int4*)(dev + o_work), (const uint4*)(dev + o_packed), (uint2*)(dev + o_part));
+        ++launches;
+    }
+    const float k = 1.f - match_conf;
+    ISX_LAUNCH("match_finalise", (double)part_count * 8.0, st, k_mt_finalise, dim3((unsigned)num_pairs), dim3(MT_FIN_NT), 0, d_prs, d_imgs,
+               (const uint2*)(dev + o_part), (int*)(dev + o_acc), k);
+    ++launches;
+    ISX_HIP(hipEventRecord(s.done, st));
+    s.last = st; s.ran = true;
+
+    // ---- host outputs: the counts first, then the rows they name ----
+    if (any_host_out) {
+        std::vector<int> cnt_tmp;
+        const int* cnt;
+        if (counts->device < 0) {
+            ISX_HIP(hipMemcpyAsync(counts->data, dev + o_counts, (size_t)num_pairs * 4, hipMemcpyDeviceToHost, st));
+            cnt = (const int*)counts->data;
+        } else {
+            cnt_tmp.resize((size_t)num_pairs);
+            ISX_HIP(hipMemcpyAsync(cnt_tmp.data(), counts->data, (size_t)num_pairs * 4, hipMemcpyDeviceToHost, st));
+            cnt = cnt_tmp.data();
+        }
+        ISX_HIP(hipStreamSynchronize(st));
+        for (int p = 0; p < num_pairs; ++p) {
+            const int nf = imgs[prs[p].from].rows, nt = imgs[prs[p].to].rows;
+            if (nf == 0 || nt == 0) continue;
+            if (matches[p].device < 0) ISX_TRY(mt_copy_back(matches[p], dev + o_m[p], cnt[p], 3, st));
+            if (points && points[p].device < 0) ISX_TRY(mt_copy_back(points[p], dev + o_p[p], cnt[p], 4, st));
+            if (knn)
+                for (int d = 0; d < 2; ++d)
+                    if (knn[2 * p + d].device < 0) ISX_TRY(mt_copy_back(knn[2 * p + d], dev + o_k[2 * p + d], d ? nt : nf, 4, st));
+        }
+        ISX_HIP(hipStreamSynchronize(st));
+    }
+    if (info) { info[0] = searched; info[1] = launches; }
+    return ISX_OK;
+} ISX_EXIT("isx_match_features")
+
+}  // extern "C"

@@ -357,6 +357,86 @@ private:
     void* stream_;
 };
 
+// The features matcher of the M demo (M = the reference's 特征点匹配 demo): BestOf2NearestMatcher1 matcher(false, 0.3f, 6, 6);
+// matcher(features, pairwise_matches) (M:307-308) as far as M:158 and the point gather of M:164-179 (isx_match_features): an exact 2-nearest-
+// neighbour search over 32-byte descriptors on the GPU, the ratio test and the de-duplication of M:232-289.  Homography, inliers and
+// confidence (M:181-229) are not built.
+struct DMatch { int queryIdx = -1, trainIdx = -1; float distance = 0.f; };
+struct ImageFeatures { int img_idx = 0; Size img_size; std::vector<Point2f> keypoints; Mat descriptors; };      // descriptors: n x 32 CV_8UC1
+struct MatchesInfo { int src_img_idx = -1, dst_img_idx = -1; std::vector<DMatch> matches; std::vector<Point2f> src_points, dst_points; };
+
+class FeaturesMatcher {
+public:
+    explicit FeaturesMatcher(float match_conf = 0.3f, int device = 0, void* hip_stream = nullptr) : conf_(match_conf), device_(device), stream_(hip_stream) {}
+    void setStream(void* hip_stream) { stream_ = hip_stream; }
+    // One MatchesInfo per near pair (M:131-135: i < j, both images with features, mask(i, j) where a CV_8U n x n host mask is given), in
+    // that order.  descriptors: host or device mats; keypoints and img_sizes may both be empty (then no points are gathered).
+    std::vector<MatchesInfo> match(const std::vector<Mat>& descriptors, const std::vector<std::vector<Point2f> >& keypoints = std::vector<std::vector<Point2f> >(),
+                                   const std::vector<Size>& img_sizes = std::vector<Size>(), const Mat& mask = Mat()) {
+        const int n = (int)descriptors.size();
+        const bool pts = !keypoints.empty();
+        if (pts && ((int)keypoints.size() != n || (int)img_sizes.size() != n)) throw Exception(ISX_ERR_INVALID, "match: descriptors, keypoints and img_sizes differ in length");
+        if (!mask.empty() && (mask.type() != ISX_8UC1 || mask.rows() != n || mask.cols() != n || mask.c()->device >= 0))
+            throw Exception(ISX_ERR_INVALID, "match: the mask is not a CV_8U host mat of n x n");
+        std::vector<isx_mat> d(n), kp(n);
+        std::vector<int> sizes, pij;
+        for (int i = 0; i < n; ++i) {
+            d[i] = *descriptors[i].c();
+            if (!pts) continue;
+            if ((int)keypoints[i].size() != d[i].rows) throw Exception(ISX_ERR_SIZE, "match: keypoints and descriptor rows differ");
+            kp[i].data = (void*)keypoints[i].data(); kp[i].rows = d[i].rows; kp[i].cols = 2; kp[i].type = ISX_32FC1; kp[i].step = sizeof(Point2f); kp[i].device = -1;
+            sizes.push_back(img_sizes[i].width); sizes.push_back(img_sizes[i].height);
+        }
+        for (int i = 0; i < n - 1; ++i)
+            for (int j = i + 1; j < n; ++j)
+                if (d[i].rows > 0 && d[j].rows > 0 && (mask.empty() || mask.ptr<unsigned char>(i)[j])) { pij.push_back(i); pij.push_back(j); }
+        const int np = (int)pij.size() / 2;
+        std::vector<MatchesInfo> out(np);
+        if (np == 0) return out;
+        std::vector<Mat> m(np), p(np);
+        std::vector<isx_mat> mm(np), pm(np);
+        Mat counts(1, np, ISX_32SC1);
+        for (int k = 0; k < np; ++k) {
+            const int cap = d[pij[2 * k]].rows + d[pij[2 * k + 1]].rows;
+            m[k].create(cap, 3, ISX_32SC1); mm[k] = *m[k].c();
+            if (pts) { p[k].create(cap, 4, ISX_32FC1); pm[k] = *p[k].c(); }
+        }
+        check(isx_match_features(n, d.data(), pts ? kp.data() : nullptr, pts ? sizes.data() : nullptr, np, pij.data(), conf_, mm.data(), pts ? pm.data() : nullptr,
+                                 counts.c(), nullptr, info_, device_, stream_));
+        for (int k = 0; k < np; ++k) {
+            MatchesInfo& mi = out[k];
+            mi.src_img_idx = pij[2 * k]; mi.dst_img_idx = pij[2 * k + 1];
+            const int cnt = counts.ptr<int>(0)[k];
+            for (int r = 0; r < cnt; ++r) {
+                const int* row = m[k].ptr<int>(r);
+                DMatch dm; dm.queryIdx = row[0]; dm.trainIdx = row[1]; dm.distance = (float)row[2];
+                mi.matches.push_back(dm);
+                if (pts) { const float* q = p[k].ptr<float>(r); mi.src_points.push_back(Point2f(q[0], q[1])); mi.dst_points.push_back(Point2f(q[2], q[3])); }
+            }
+        }
+        return out;
+    }
+    // matcher(features, pairwise_matches, mask) (M:123-144): pairwise_matches gets n * n entries, entry i * n + j filled for a near pair
+    void operator()(const std::vector<ImageFeatures>& features, std::vector<MatchesInfo>& pairwise_matches, const Mat& mask = Mat()) {
+        const size_t n = features.size();
+        std::vector<Mat> d;
+        std::vector<std::vector<Point2f> > kp;
+        std::vector<Size> sz;
+        for (size_t i = 0; i < n; ++i) { d.push_back(features[i].descriptors); kp.push_back(features[i].keypoints); sz.push_back(features[i].img_size); }
+        const std::vector<MatchesInfo> near = match(d, kp, sz, mask);
+        pairwise_matches.assign(n * n, MatchesInfo());                                        // M:137
+        for (size_t k = 0; k < near.size(); ++k) pairwise_matches[(size_t)near[k].src_img_idx * n + near[k].dst_img_idx] = near[k];
+    }
+    int pairsSearched() const { return info_[0]; }
+    int launches() const { return info_[1]; }     // kernel launches of the last call: at most three, however many pairs
+    static void release() { check(isx_match_release()); }
+private:
+    float conf_;
+    int device_;
+    void* stream_;
+    int info_[2] = {0, 0};
+};
+
 // cv::imread(path) (W:166): the decoder follows the file's signature, as OpenCV's does - "BM" bitmaps and JFIF / Exif JPEGs;
 // cv::imwrite(path, img) for .bmp and .jpg (W:155-156,315; "pano.jpg" S:1282)
 inline Mat imread(const char* path) {

@@ -619,6 +619,47 @@ int isx_voronoi_seam_reserve(int max_roi_width, int max_roi_height, int device);
  * freed at thread exit, as for isx_dp_seam_release.                                                                                    */
 int isx_voronoi_seam_release(void);
 
+/* ---- the features matcher of the M demo (M = the reference's 特征点匹配/特征点匹配/特征点匹配.cpp) --------------------------------- */
+/* The tiling of the search kernel (match.hip takes them from here; imagestitch_amd/matcher.py repeats them): queries per block, train rows
+ * per LDS tile, train rows per work item, and the row limits - the width of the packed key distance << 22 | row.                          */
+enum { ISX_MATCH_QUERY_BLOCK = 128, ISX_MATCH_TRAIN_TILE = 128, ISX_MATCH_TRAIN_CHUNK = 256,
+       ISX_MATCH_MAX_ROWS = 1 << 20, ISX_MATCH_MAX_TOTAL_ROWS = 1 << 22 };
+/* BestOf2NearestMatcher1 matcher(false, match_conf, ...); matcher(features, pairwise_matches) (M:307-308) up to where M:158 returns, plus
+ * the point gather of M:164-179: for every pair of near_pairs (M:131-135) CpuMatcher1::match (M:232-289) with an EXACT 2-nearest-neighbour
+ * search over 256-bit Hamming distances in place of the FLANN LSH index of M:241-250 (approximate and randomised: not reproduced).
+ *   1->2 (M:256-274): with n_to >= 2, the two nearest rows of image `to` by (distance, row) for every row q of image `from`; accepted when
+ *        (float)d0 < k * (float)d1, k = 1.f - match_conf in float32, one rounded multiply; appended as (q, row0, d0) in order of q.
+ *   2->1 (M:276-287): the same with the roles swapped, with n_from >= 2; appended as (row0, q, d0) in order of q unless 1->2 accepted
+ *        (row0, q).
+ * An accepted match has a unique nearest neighbour (d0 < k d1 <= d1), so the list does not depend on how ties are ordered.  A pair with an
+ * empty image is skipped: its count is 0 and nothing else of it is written (M:134).  homography, inliers and confidence (M:181-229) are
+ * not built.
+ *   descriptors  num_images CV_8UC1 mats of n_i x 32 (ORB; CV_32F / SURF descriptors are not built: cols != 32 -> ISX_ERR_UNSUPPORTED), host or
+ *                device, any pointer alignment and step; rows may be 0 (then data and cols are not looked at).  At most 2^20 rows an
+ *                image and 2^22 in all (ISX_ERR_UNSUPPORTED).
+ *   keypoints    NULL, or num_images CV_32FC1 mats of n_i x 2 (pt.x, pt.y); then image_sizes_wh holds (width, height) per image (img_size).
+ *   pairs_ij     num_pairs (from, to) with from < to.
+ *   matches      per pair a CV_32SC1 mat of at least (n_from + n_to) x 3: queryIdx, trainIdx, distance.  Rows from counts[p] on are not
+ *                written.
+ *   points       NULL, or (with keypoints) per pair a CV_32FC1 mat of at least (n_from + n_to) x 4: row r = src.x, src.y, dst.x, dst.y of
+ *                match r, each pt - size * 0.5f in float32 (M:170-178).
+ *   counts       a CV_32SC1 mat of at least 1 x num_pairs.
+ *   knn          NULL, or 2 * num_pairs CV_32SC1 mats (pair p: 2p is 1->2, 2p + 1 is 2->1) of at least n_query x 4: row0, d0, row1, d1, with -1, -1
+ *                where there is no such neighbour.  Not written for a skipped pair.
+ *   info         NULL, or 2 ints: the pairs searched and the kernel launches of this call (at most three, however many pairs).
+ * Output mats are host or device mats, 4-byte aligned in pointer and step.  Checked before anything is written or enqueued: null pointers,
+ * num_images < 0, a pair with from >= to or out of range, match_conf not in [0, 1) (outside it the list would depend on the order of ties),
+ * keypoints without image_sizes_wh, points without keypoints, a misaligned output -> ISX_ERR_INVALID; descriptors not CV_8UC1, keypoints or
+ * points not CV_32FC1, matches / counts / knn not CV_32SC1 -> ISX_ERR_TYPE; an output with too few rows or cols, keypoints that are not
+ * n_i x 2 -> ISX_ERR_SIZE.  The call uploads its tables (and packs and stages host mats): on a capturing stream -> ISX_ERR_STATE with nothing
+ * enqueued.  With device mats throughout nothing is read back or synchronised: counts stays on the device.  Host mats synchronise.         */
+int isx_match_features(int num_images, const isx_mat* descriptors, const isx_mat* keypoints, const int* image_sizes_wh,
+                       int num_pairs, const int* pairs_ij, float match_conf, isx_mat* matches, isx_mat* points, isx_mat* counts,
+                       isx_mat* knn, int* info, int device, void* hip_stream);
+/* Returns the scratch of the calling thread (the matcher going out of scope).  PER THREAD and not freed at thread exit, as for
+ * isx_voronoi_seam_release.                                                                                                            */
+int isx_match_release(void);
+
 /* ---- on-disk format either side of the path: .bmp (W:166 imread, W:155-156,315 imwrite) ----------- */
 /* Reading: uncompressed Windows bitmaps only (the reference's inputs and committed artefacts are BMPs).
  * isx_bmp_read = cv::imread(path) with IMREAD_COLOR: `out` is a CV_8UC3 mat (host or device) of the size
