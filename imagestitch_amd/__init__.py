@@ -9,10 +9,11 @@ from ._lib import (BORDER_CONSTANT, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_R
 from .blender import Blender, FeatherBlender, MultiBandBlender, NoBlender, convert_to, dilate_and, gain_apply  # noqa: F401
 from .exposure import BlocksGainCompensator, GainCompensator  # noqa: F401
 from .imgio import imread, imwrite  # noqa: F401
-from .matcher import FeaturesMatcher  # noqa: F401
+from .homography import BestOf2NearestMatcher, find_homography  # noqa: F401
+from .matcher import FeaturesMatcher, MatchesInfo  # noqa: F401
 from .resize import dilate_resize_and, resize  # noqa: F401
 from .seam import DP_COLOR, DP_COLOR_GRAD, DpSeamFinder, GraphCutSeamFinder, VoronoiSeamFinder, seam_estimate, seam_gradients  # noqa: F401
 from ._lib import WARP_CYLINDRICAL, WARP_PLANE, WARP_SPHERICAL  # noqa: F401
 from .warper import CylindricalWarper, PlaneWarper, RotationWarper, SphericalWarper, remap  # noqa: F401
 
-__all__ = ["Blender", "MultiBandBlender", "FeatherBlender", "NoBlender", "convert_to", "dilate_and", "gain_apply", "GainCompensator", "BlocksGainCompensator", "imread", "imwrite", "resize", "dilate_resize_and", "INTER_NEAREST", "INTER_LINEAR", "seam_estimate", "seam_gradients", "DP_COLOR", "DP_COLOR_GRAD", "DpSeamFinder", "GraphCutSeamFinder", "VoronoiSeamFinder", "FeaturesMatcher", "remap", "CylindricalWarper", "SphericalWarper", "PlaneWarper", "WARP_CYLINDRICAL", "WARP_SPHERICAL", "WARP_PLANE", "RotationWarper", "IsxError", "load"]
+__all__ = ["Blender", "MultiBandBlender", "FeatherBlender", "NoBlender", "convert_to", "dilate_and", "gain_apply", "GainCompensator", "BlocksGainCompensator", "imread", "imwrite", "resize", "dilate_resize_and", "INTER_NEAREST", "INTER_LINEAR", "seam_estimate", "seam_gradients", "DP_COLOR", "DP_COLOR_GRAD", "DpSeamFinder", "GraphCutSeamFinder", "VoronoiSeamFinder", "FeaturesMatcher", "BestOf2NearestMatcher", "MatchesInfo", "find_homography", "remap", "CylindricalWarper", "SphericalWarper", "PlaneWarper", "WARP_CYLINDRICAL", "WARP_SPHERICAL", "WARP_PLANE", "RotationWarper", "IsxError", "load"]

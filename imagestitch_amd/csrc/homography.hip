@@ -1,0 +1,753 @@
+// homography.hip — the second half of BestOf2NearestMatcher::match on gfx950, after the reference's 计算单应性矩阵 demo (R = its
+// 计算单应性矩阵.cpp, a hand-unrolled OpenCV 3.4.2 findHomography(RANSAC)):
+//   isx_find_homography     R:836-909 for every pair of a matcher call: findHomography2(src, dst, RANSAC, 3, mask, 2000, 0.995) (R:602-693,
+//                           RANSACPointSetRegistrator1::run R:139-233, HomographyEstimatorCallback R:253-402), the degenerate-H test,
+//                           num_inliers and confidence (R:863-878), the second run on the inliers (R:881-909).  The Levenberg-Marquardt
+//                           polish of R:672 is not run.
+//   isx_homography_release  returns the per-thread scratch
+//
+// The specification is tests/helpers/homography_np.py (DESIGN.md §8 "Homography"): float64 in + - * / sqrt only, every sum in the order of
+// its loop, the float32 of computeError as written; cv::eigen (JacobiImpl_), cv::RNG, haveCollinearPoints and cvRound are restated there.
+// `nmodels = cb->runKernel(ms1, ms2, model)`, which R lost between R:196 and R:197, is in place.
+//
+// ONE launch per call, however many pairs: k_hg_pairs, one block of one wave per pair, both passes.  The sample stream of a RANSAC run
+// depends on the points alone (getSubset and checkSubset), never on the scores, so the wave works in chunks of 64 hypotheses:
+//   draw     lane 0 draws the chunk's subsets in order (cv::RNG, the 10000 attempts of getSubset, checkSubset in double);
+//   solve    lane h solves hypothesis h: the normalised 9 x 9 system of runKernel and its Jacobi eigen-solve.  The Jacobi state (A, V, W, the
+//            pivot tables) is indexed by run-time pivots: it lives in LDS as [element][lane] - with 8-byte elements and 64 lanes the bank
+//            depends on the lane alone, so pivots that differ across lanes do not conflict;
+//   scan     the hypotheses in order, exactly as the sequential loop: the 64 lanes score one hypothesis against all points (a ballot
+//            per 64 points), a better count replaces the model and shortens niters (RANSACUpdateNumIters1), the scan stops at niters.
+// The least-squares refit over all inliers gives each of the 45 LtL[j][k] sums (and each of the 4 + 4 mean and scale sums) to a lane of its
+// own that loops over the points in order: the bits of the sequential loop without a reduction tree.
+#include "isx_device.hpp"
+#include "pairwise.hpp"
+
+#include <cfloat>
+
+using namespace isx;
+using namespace isxd;
+
+namespace {
+
+constexpr int HG_CHUNK = ISX_HOMOGRAPHY_CHUNK;   // hypotheses per chunk = lanes of the block
+constexpr int HG_MAX_ATTEMPTS = 10000;           // getSubset(m1, m2, ms1, ms2, rng, 10000), R:189
+constexpr int HG_ST_H = 1, HG_ST_PASS2 = 2, HG_ST_PASS2_FAILED = 4, HG_ST_CLAMPED = 8, HG_ST_DEGENERATE = 16;
+static_assert(HG_CHUNK == WAVE, "one hypothesis per lane of one wave");
+
+// LDS, in bytes from the start of the dynamic segment: [element][lane]
+constexpr int HG_LDS_A = 0;                                  // 81 doubles a lane: the matrix (its upper triangle is what is read)
+constexpr int HG_LDS_V = HG_LDS_A + 81 * WAVE * 8;           // 81 doubles: the eigenvectors, one a row
+constexpr int HG_LDS_W = HG_LDS_V + 81 * WAVE * 8;           // 9 doubles: the eigenvalues
+constexpr int HG_LDS_INDR = HG_LDS_W + 9 * WAVE * 8;         // 9 ints: the column of the largest element right of the diagonal, per row
+constexpr int HG_LDS_INDC = HG_LDS_INDR + 9 * WAVE * 4;      // 9 ints: the row of the largest element above the diagonal, per column
+constexpr int HG_LDS_SUB = HG_LDS_INDC + 9 * WAVE * 4;       // 4 ints: the subset of hypothesis h
+constexpr int HG_LDS_FOUND = HG_LDS_SUB + 4 * WAVE * 4;      // 1 int: getSubset's result for hypothesis h
+constexpr int HG_LDS_ATT = HG_LDS_FOUND + WAVE * 4;          // 1 int: its attempts
+constexpr int HG_LDS_BYTES = HG_LDS_ATT + WAVE * 4;
+
+struct HgPair {
+    const float* points; long long points_step;   // the caller's device mat or the staged copy of a host mat
+    unsigned char* mask; long long mask_step;     // the caller's device mat or its staged copy
+    float* work_a; float* work_b;                 // cap x 4 floats each: the inliers of pass 1 (the input of pass 2), those of pass 2
+    int cap;                                      // min(rows of points, rows of mask)
+    int pad;
+};
+
+struct HgCall {
+    const HgPair* pairs;
+    const int* counts;
+    double* H; long long H_step;
+    int* stats; long long stats_step;
+    double* conf;
+    double thresh, confidence;
+    int max_iters, thresh1, thresh2;
+};
+
+template <class T>
+__device__ __forceinline__ T* as_global(T* p) {      // as in match.hip: a wave-uniform table pointer the compiler may load through global_load
+    const unsigned long long u = (unsigned long long)p;
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
+    return (T*)(__attribute__((address_space(1))) T*)(((unsigned long long)hi << 32) | lo);
+}
+
+struct HgLds {
+    double* A; double* V; double* W; int* indR; int* indC; int* sub; int* found; int* att;
+};
+
+__device__ __forceinline__ const float* hg_row(const float* pts, long long step, int i) { return (const float*)((const char*)pts + (long long)i * step); }
+
+__device__ __forceinline__ double hg_det3(const double* a) {
+    return (a[0] * (a[4] * a[8] - a[7] * a[5]) - a[1] * (a[3] * a[8] - a[6] * a[5])) + a[2] * (a[3] * a[7] - a[6] * a[4]);
+}
+
+// OpenCV's own hypot
+__device__ __forceinline__ double hg_hypot(double a, double b) {
+    a = fabs(a); b = fabs(b);
+    if (a > b) { b /= a; return a * sqrt(1.0 + b * b); }
+    if (b > 0) { a /= b; return b * sqrt(1.0 + a * a); }
+    return 0.0;
+}
+
+// JacobiImpl_ on the lane's column of the LDS state, n = 9; A and W are set.  Leaves W sorted descending with the rows of V.
+__device__ __forceinline__ void hg_jacobi(const HgLds& s, int lane) {
+    constexpr int n = 9;
+#define HA(r, c) s.A[((r) * n + (c)) * WAVE + lane]
+#define HV(r, c) s.V[((r) * n + (c)) * WAVE + lane]
+#define HW(r) s.W[(r) * WAVE + lane]
+#define HR(r) s.indR[(r) * WAVE + lane]
+#define HC(r) s.indC[(r) * WAVE + lane]
+    for (int i = 0; i < n; ++i) {
+        for (int j = 0; j < n; ++j) HV(i, j) = 0.0;
+        HV(i, i) = 1.0;
+    }
+    for (int k = 0; k < n; ++k) {
+        HW(k) = HA(k, k);
+        if (k < n - 1) {
+            int m = k + 1;
+            double mv = fabs(HA(k, m));
+            for (int i = k + 2; i < n; ++i) {
+                const double val = fabs(HA(k, i));
+                if (mv < val) { mv = val; m = i; }
+            }
+            HR(k) = m;
+        }
+        if (k > 0) {
+            int m = 0;
+            double mv = fabs(HA(0, k));
+            for (int i = 1; i < k; ++i) {
+                const double val = fabs(HA(i, k));
+                if (mv < val) { mv = val; m = i; }
+            }
+            HC(k) = m;
+        }
+    }
+    for (int iters = 0; iters < n * n * 30; ++iters) {
+        int k = 0;
+        double mv = fabs(HA(0, HR(0)));
+        for (int i = 1; i < n - 1; ++i) {
+            const double val = fabs(HA(i, HR(i)));
+            if (mv < val) { mv = val; k = i; }
+        }
+        int l = HR(k);
+        for (int i = 1; i < n; ++i) {
+            const double val = fabs(HA(HC(i), i));
+            if (mv < val) { mv = val; k = HC(i); l = i; }
+        }
+        const double p = HA(k, l);
+        if (fabs(p) <= DBL_EPSILON) break;
+        const double y = (HW(l) - HW(k)) * 0.5;
+        double t = fabs(y) + hg_hypot(p, y);
+        double sn = hg_hypot(p, t);
+        const double c = t / sn;
+        sn = p / sn; t = (p / t) * p;
+        if (y < 0) { sn = -sn; t = -t; }
+        HA(k, l) = 0.0;
+        HW(k) -= t;
+        HW(l) += t;
+#define HG_ROT(v0, v1)                              \
+    do {                                            \
+        const double a0 = v0, b0 = v1;              \
+        v0 = a0 * c - b0 * sn;                      \
+        v1 = a0 * sn + b0 * c;                      \
+    } while (0)
+        for (int i = 0; i < k; ++i) HG_ROT(HA(i, k), HA(i, l));
+        for (int i = k + 1; i < l; ++i) HG_ROT(HA(k, i), HA(i, l));
+        for (int i = l + 1; i < n; ++i) HG_ROT(HA(k, i), HA(l, i));
+        for (int i = 0; i < n; ++i) HG_ROT(HV(k, i), HV(l, i));
+#undef HG_ROT
+        for (int j = 0; j < 2; ++j) {
+            const int idx = j == 0 ? k : l;
+            if (idx < n - 1) {
+                int m = idx + 1;
+                double mx = fabs(HA(idx, m));
+                for (int i = idx + 2; i < n; ++i) {
+                    const double val = fabs(HA(idx, i));
+                    if (mx < val) { mx = val; m = i; }
+                }
+                HR(idx) = m;
+            }
+            if (idx > 0) {
+                int m = 0;
+                double mx = fabs(HA(0, idx));
+                for (int i = 1; i < idx; ++i) {
+                    const double val = fabs(HA(i, idx));
+                    if (mx < val) { mx = val; m = i; }
+                }
+                HC(idx) = m;
+            }
+        }
+    }
+    for (int k = 0; k < n - 1; ++k) {
+        int m = k;
+        for (int i = k + 1; i < n; ++i)
+            if (HW(m) < HW(i)) m = i;
+        if (k != m) {
+            const double w = HW(m); HW(m) = HW(k); HW(k) = w;
+            for (int i = 0; i < n; ++i) { const double v = HV(m, i); HV(m, i) = HV(k, i); HV(k, i) = v; }
+        }
+    }
+#undef HA
+#undef HV
+#undef HW
+#undef HR
+#undef HC
+}
+
+// R:369-371 from row 8 of the lane's sorted V: H = (invHnorm * H0 * Hnorm2) / that(2, 2), the sums k = 0, 1, 2 left to right
+__device__ __forceinline__ void hg_denormalise(const HgLds& s, int lane, const double* inv, const double* hn2, double* H) {
+    double h0[9], ht[9], h2[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) h0[i] = s.V[(8 * 9 + i) * WAVE + lane];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) ht[3 * i + j] = (inv[3 * i] * h0[j] + inv[3 * i + 1] * h0[3 + j]) + inv[3 * i + 2] * h0[6 + j];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) h2[3 * i + j] = (ht[3 * i] * hn2[j] + ht[3 * i + 1] * hn2[3 + j]) + ht[3 * i + 2] * hn2[6 + j];
+    const double sc = 1.0 / h2[8];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) H[i] = h2[i] * sc;
+}
+
+// runKernel (R:304-373) of the lane's own four correspondences q[i] = (src.x, src.y, dst.x, dst.y); false = it returned 0
+__device__ bool hg_run_kernel_lane(const HgLds& s, int lane, const float (&q)[4][4], double* H) {
+    constexpr int count = 4;
+    double cmx = 0, cmy = 0, cMx = 0, cMy = 0;
+#pragma unroll
+    for (int i = 0; i < count; ++i) { cmx += q[i][2]; cmy += q[i][3]; cMx += q[i][0]; cMy += q[i][1]; }
+    cmx /= count; cmy /= count; cMx /= count; cMy /= count;
+    double smx = 0, smy = 0, sMx = 0, sMy = 0;
+#pragma unroll
+    for (int i = 0; i < count; ++i) {
+        smx += fabs(q[i][2] - cmx); smy += fabs(q[i][3] - cmy);
+        sMx += fabs(q[i][0] - cMx); sMy += fabs(q[i][1] - cMy);
+    }
+    if (fabs(smx) < DBL_EPSILON || fabs(smy) < DBL_EPSILON || fabs(sMx) < DBL_EPSILON || fabs(sMy) < DBL_EPSILON) return false;
+    smx = count / smx; smy = count / smy; sMx = count / sMx; sMy = count / sMy;
+    const double inv[9] = {1.0 / smx, 0, cmx, 0, 1.0 / smy, cmy, 0, 0, 1};
+    const double hn2[9] = {sMx, 0, -cMx * sMx, 0, sMy, -cMy * sMy, 0, 0, 1};
+    double acc[45];
+#pragma unroll
+    for (int e = 0; e < 45; ++e) acc[e] = 0.0;
+#pragma unroll
+    for (int i = 0; i < count; ++i) {
+        const double x = (q[i][2] - cmx) * smx, y = (q[i][3] - cmy) * smy;
+        const double X = (q[i][0] - cMx) * sMx, Y = (q[i][1] - cMy) * sMy;
+        const double Lx[9] = {X, Y, 1, 0, 0, 0, -x * X, -x * Y, -x};
+        const double Ly[9] = {0, 0, 0, X, Y, 1, -y * X, -y * Y, -y};
+        int e = 0;
+#pragma unroll
+        for (int j = 0; j < 9; ++j)
+#pragma unroll
+            for (int k = j; k < 9; ++k, ++e) acc[e] = acc[e] + (Lx[j] * Lx[k] + Ly[j] * Ly[k]);
+    }
+    {
+        int e = 0;
+#pragma unroll
+        for (int j = 0; j < 9; ++j)
+#pragma unroll
+            for (int k = j; k < 9; ++k, ++e) s.A[(j * 9 + k) * WAVE + lane] = acc[e];
+    }
+    hg_jacobi(s, lane);
+    hg_denormalise(s, lane, inv, hn2, H);
+    return true;
+}
+
+__device__ __forceinline__ double hg_pick(int j, double X, double Y, double x) {      // Lx[j] of R:356
+    return j == 0 ? X : j == 1 ? Y : j == 2 ? 1.0 : j < 6 ? 0.0 : j == 6 ? -x * X : j == 7 ? -x * Y : -x;
+}
+__device__ __forceinline__ double hg_pick_y(int j, double X, double Y, double y) {    // Ly[j] of R:357
+    return j < 3 ? 0.0 : j == 3 ? X : j == 4 ? Y : j == 5 ? 1.0 : j == 6 ? -y * X : j == 7 ? -y * Y : -y;
+}
+
+// runKernel over `count` dense rows by the whole wave: every sum is one lane's, looping over the rows in order.  The result is uniform.
+__device__ bool hg_run_kernel_wave(const HgLds& s, int lane, const float* pts, long long step, int count, double* H) {
+    const int col = (lane & 3) < 2 ? (lane & 3) + 2 : (lane & 3) - 2;      // lanes 0..3: dst.x, dst.y, src.x, src.y (cm.x, cm.y, cM.x, cM.y)
+    double sum = 0.0;
+    for (int i = 0; i < count; ++i) sum += hg_row(pts, step, i)[col];
+    sum /= count;
+    const double cmx = __shfl(sum, 0), cmy = __shfl(sum, 1), cMx = __shfl(sum, 2), cMy = __shfl(sum, 3);
+    double sa = 0.0;
+    for (int i = 0; i < count; ++i) sa += fabs(hg_row(pts, step, i)[col] - sum);
+    double smx = __shfl(sa, 0), smy = __shfl(sa, 1), sMx = __shfl(sa, 2), sMy = __shfl(sa, 3);
+    if (fabs(smx) < DBL_EPSILON || fabs(smy) < DBL_EPSILON || fabs(sMx) < DBL_EPSILON || fabs(sMy) < DBL_EPSILON) return false;
+    smx = count / smx; smy = count / smy; sMx = count / sMx; sMy = count / sMy;
+    const double inv[9] = {1.0 / smx, 0, cmx, 0, 1.0 / smy, cmy, 0, 0, 1};
+    const double hn2[9] = {sMx, 0, -cMx * sMx, 0, sMy, -cMy * sMy, 0, 0, 1};
+    int j = 0, k = lane < 45 ? lane : 0;                  // lane e < 45 owns LtL[j][k], j <= k, in row-major order of the upper triangle
+    while (k >= 9 - j) { k -= 9 - j; ++j; }
+    k += j;
+    double acc = 0.0;
+    for (int i = 0; i < count; ++i) {
+        const float* r = hg_row(pts, step, i);
+        const double x = (r[2] - cmx) * smx, y = (r[3] - cmy) * smy;
+        const double X = (r[0] - cMx) * sMx, Y = (r[1] - cMy) * sMy;
+        acc = acc + (hg_pick(j, X, Y, x) * hg_pick(k, X, Y, x) + hg_pick_y(j, X, Y, y) * hg_pick_y(k, X, Y, y));
+    }
+    __syncthreads();
+    if (lane < 45) s.A[(j * 9 + k) * WAVE + 0] = acc;     // lane 0's column
+    __syncthreads();
+    if (lane == 0) hg_jacobi(s, 0);
+    __syncthreads();
+    hg_denormalise(s, 0, inv, hn2, H);
+    return true;
+}
+
+// RANSACUpdateNumIters1 (R:39-59) with modelPoints = 4
+__device__ int hg_update_iters(double p, double ep, int max_iters) {
+    p = fmax(p, 0.0); p = fmin(p, 1.0);
+    ep = fmax(ep, 0.0); ep = fmin(ep, 1.0);
+    double num = fmax(1.0 - p, DBL_MIN);
+    double denom = 1.0 - pow(1.0 - ep, 4.0);
+    if (denom < DBL_MIN) return 0;
+    num = log(num);
+    denom = log(denom);
+    return denom >= 0 || -num >= max_iters * (-denom) ? max_iters : (int)rint(num / denom);
+}
+
+__device__ __forceinline__ bool hg_collinear(const float (&q)[4][4], int c) {      // haveCollinearPoints(m, 4): the last point only
+    const double xi = q[3][c], yi = q[3][c + 1];
+    for (int j = 0; j < 3; ++j) {
+        const double dx1 = q[j][c] - xi, dy1 = q[j][c + 1] - yi;
+        for (int k = 0; k < j; ++k) {
+            const double dx2 = q[k][c] - xi, dy2 = q[k][c + 1] - yi;
+            if (fabs(dx2 * dy1 - dy2 * dx1) <= FLT_EPSILON * (fabs(dx1) + fabs(dy1) + fabs(dx2) + fabs(dy2))) return true;
+        }
+    }
+    return false;
+}
+
+__device__ bool hg_check_subset(const float (&q)[4][4]) {                         // R:253-288
+    if (hg_collinear(q, 0) || hg_collinear(q, 2)) return false;
+    const int tt[4][3] = {{0, 1, 2}, {1, 2, 3}, {0, 2, 3}, {0, 1, 3}};
+    int negative = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        double a[9], b[9];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            a[3 * r] = q[tt[i][r]][0]; a[3 * r + 1] = q[tt[i][r]][1]; a[3 * r + 2] = 1.0;
+            b[3 * r] = q[tt[i][r]][2]; b[3 * r + 1] = q[tt[i][r]][3]; b[3 * r + 2] = 1.0;
+        }
+        negative += hg_det3(a) * hg_det3(b) < 0;
+    }
+    return negative == 0 || negative == 4;
+}
+
+// computeError and findInliers (R:383-402, R:67-86) for one row, in float32 as written
+__device__ __forceinline__ bool hg_inlier(const float* Hf, const float* r, float t) {
+    const float Mx = r[0], My = r[1];
+    const float ww = 1.f / ((Hf[6] * Mx + Hf[7] * My) + 1.f);
+    const float dx = ((Hf[0] * Mx + Hf[1] * My) + Hf[2]) * ww - r[2];
+    const float dy = ((Hf[3] * Mx + Hf[4] * My) + Hf[5]) * ww - r[3];
+    return dx * dx + dy * dy <= t;
+}
+
+// rng.uniform(0, n) of cv::RNG: state = (uint64)(unsigned)state * 4294883355u + (unsigned)(state >> 32), the low word modulo n
+__device__ __forceinline__ int hg_uniform(unsigned long long& state, int n) {
+    state = (unsigned long long)(unsigned)state * 4294883355ull + (state >> 32);
+    return (int)((unsigned)state % (unsigned)n);
+}
+
+__device__ __forceinline__ void hg_load4(const float* pts, long long step, int i0, int i1, int i2, int i3, float (&q)[4][4]) {
+    const int idx[4] = {i0, i1, i2, i3};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float* r = hg_row(pts, step, idx[i]);
+        q[i][0] = r[0]; q[i][1] = r[1]; q[i][2] = r[2]; q[i][3] = r[3];
+    }
+}
+
+struct HgRun {
+    bool ok;            // findHomography2's result: H is not empty
+    double H[9];
+    int inliers;        // rows compacted into `work`
+    int iters, win, attempts;
+};
+
+// findHomography2 (R:602-693, RANSAC, without R:672) by the whole wave; every field of the result is uniform.  mask (may be null) gets rows
+// [0, n); work gets the inliers in order, 4 floats a row.
+__device__ void hg_find(const HgLds& s, int lane, const float* pts, long long step, int n, unsigned char* mask, long long mask_step, float* work,
+                        const HgCall& c, HgRun& out) {
+    out.ok = false; out.inliers = 0; out.iters = 0; out.win = -1; out.attempts = 0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) out.H[i] = 0.0;
+    const float t = (float)(c.thresh * c.thresh);
+    const bool direct = n == 4;                                       // R:641-645: runKernel over the four rows, the mask all ones
+    if (n > 4) {                                               // R:139-233
+        unsigned long long rng = ~0ull;                               // RNG rng((uint64)-1): lane 0's copy is the generator
+        int niters = max(c.max_iters, 1), max_good = 0, it = 0;
+        bool stop = false;
+        while (!stop && it < niters) {
+            const int cn = min(HG_CHUNK, niters - it);
+            __syncthreads();                                          // the previous chunk's readers of sub / found / att are done
+            s.found[lane] = 0;                                        // hypotheses past a failed getSubset are never drawn
+            s.att[lane] = 0;
+            __syncthreads();
+            if (lane == 0) {
+                bool found = true;
+                for (int h = 0; h < cn && found; ++h) {
+                    int attempts = 0;
+                    int i0 = 0, i1 = 0, i2 = 0, i3 = 0;
+                    found = false;
+                    while (attempts < HG_MAX_ATTEMPTS) {              // R:111-134: a duplicate draws again, a bad subset costs an attempt
+                        i0 = hg_uniform(rng, n);
+                        do i1 = hg_uniform(rng, n); while (i1 == i0);
+                        do i2 = hg_uniform(rng, n); while (i2 == i0 || i2 == i1);
+                        do i3 = hg_uniform(rng, n); while (i3 == i0 || i3 == i1 || i3 == i2);
+                        float q[4][4];
+                        hg_load4(pts, step, i0, i1, i2, i3, q);
+                        ++attempts;
+                        if (hg_check_subset(q)) { found = true; break; }
+                    }
+                    s.sub[0 * WAVE + h] = i0; s.sub[1 * WAVE + h] = i1; s.sub[2 * WAVE + h] = i2; s.sub[3 * WAVE + h] = i3;
+                    s.found[h] = found ? 1 : 0;
+                    s.att[h] = attempts;
+                }
+            }
+            __syncthreads();
+            bool hok = false;
+            double H[9];
+#pragma unroll
+            for (int i = 0; i < 9; ++i) H[i] = 0.0;
+            if (lane < cn && s.found[lane]) {
+                float q[4][4];
+                hg_load4(pts, step, s.sub[0 * WAVE + lane], s.sub[1 * WAVE + lane], s.sub[2 * WAVE + lane], s.sub[3 * WAVE + lane], q);
+                hok = hg_run_kernel_lane(s, lane, q, H);
+            }
+            for (int h = 0; h < cn && it < niters; ++h) {
+                out.attempts += s.att[h];
+                if (!s.found[h]) { stop = true; break; }              // R:190-195: at iteration 0 nothing was found, later the loop ends
+                if (__shfl((int)hok, h)) {
+                    double Hh[9];
+                    float Hf[8];
+#pragma unroll
+                    for (int i = 0; i < 9; ++i) Hh[i] = __shfl(H[i], h);
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) Hf[i] = (float)Hh[i];
+                    int good = 0;
+                    for (int i0 = 0; i0 < n; i0 += WAVE) {
+                        const int i = i0 + lane;
+                        const bool in = i < n && hg_inlier(Hf, hg_row(pts, step, i), t);
+                        good += __popcll(__ballot(in));
+                    }
+                    if (good > max(max_good, 3)) {                    // R:207
+                        max_good = good; out.win = it;
+#pragma unroll
+                        for (int i = 0; i < 9; ++i) out.H[i] = Hh[i];
+                        niters = hg_update_iters(c.confidence, (double)(n - good) / n, niters);
+                    }
+                }
+                ++it;
+            }
+        }
+        out.iters = it;
+        out.ok = max_good > 0;
+    }
+    // the mask of the model found (R:209, R:226), or zeros (R:687), and the inliers in order (R:659-660); n == 4: every row (R:643)
+    float Hf[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) Hf[i] = (float)out.H[i];
+    int m = 0;
+    for (int i0 = 0; i0 < n; i0 += WAVE) {
+        const int i = i0 + lane;
+        bool in = false;
+        if (i < n) in = direct || (out.ok && hg_inlier(Hf, hg_row(pts, step, i), t));
+        const unsigned long long bal = __ballot(in);
+        if (i < n && mask && !direct) mask[(long long)i * mask_step] = in ? 1 : 0;
+        if (in) {
+            const float* r = hg_row(pts, step, i);
+            float* o = work + 4ll * (m + __popcll(bal & ((1ull << lane) - 1ull)));
+            o[0] = r[0]; o[1] = r[1]; o[2] = r[2]; o[3] = r[3];
+        }
+        m += __popcll(bal);
+    }
+    out.inliers = m;
+    __syncthreads();                                                  // the rows of `work` are written before the wave reads them
+    if (direct || (out.ok && m > 0)) {                                // R:657-668: runKernel over all inliers; 0 leaves the RANSAC model
+        double H[9];
+        const bool ok = hg_run_kernel_wave(s, lane, work, 16, m, H);
+        if (ok) {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) out.H[i] = H[i];
+        }
+        if (direct) {
+            out.ok = ok;
+            if (!ok) out.inliers = 0;
+            if (mask && lane < 4) mask[(long long)lane * mask_step] = ok ? 1 : 0;
+        }
+    }
+}
+
+__global__ __launch_bounds__(HG_CHUNK) void k_hg_pairs(HgCall c) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char hg_smem[];
+    HgLds s;
+    s.A = (double*)(hg_smem + HG_LDS_A); s.V = (double*)(hg_smem + HG_LDS_V); s.W = (double*)(hg_smem + HG_LDS_W);
+    s.indR = (int*)(hg_smem + HG_LDS_INDR); s.indC = (int*)(hg_smem + HG_LDS_INDC); s.sub = (int*)(hg_smem + HG_LDS_SUB);
+    s.found = (int*)(hg_smem + HG_LDS_FOUND); s.att = (int*)(hg_smem + HG_LDS_ATT);
+    const int p = (int)blockIdx.x, lane = (int)threadIdx.x;
+    const HgPair& P = as_global(c.pairs)[p];
+    int n = as_global(c.counts)[p];
+    int status = 0;
+    if (n > P.cap) { n = P.cap; status |= HG_ST_CLAMPED; }
+    if (n < 0) n = 0;
+    double Hout[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) Hout[i] = 0.0;
+    int st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double conf = 0.0;
+    if (n >= c.thresh1) {                                             // R:836
+        float* const work_a = as_global(P.work_a);
+        st[3] = st[5] = -1;
+        int num_inliers = 0;
+        for (int pass = 0; pass < 2; ++pass) {
+            HgRun r;
+            if (pass == 0) hg_find(s, lane, as_global(P.points), P.points_step, n, as_global(P.mask), P.mask_step, work_a, c, r);      // R:862
+            else hg_find(s, lane, work_a, 16, num_inliers, nullptr, 0, as_global(P.work_b), c, r);                                    // R:909
+            st[2 + 2 * pass] = r.iters; st[3 + 2 * pass] = r.win; st[6] += r.attempts;
+#pragma unroll
+            for (int i = 0; i < 9; ++i) Hout[i] = r.ok ? r.H[i] : 0.0;
+            if (pass == 1) {
+                status |= HG_ST_PASS2;
+                if (!r.ok) status = (status | HG_ST_PASS2_FAILED) & ~HG_ST_H;
+                break;
+            }
+            if (!r.ok) break;
+            status |= HG_ST_H;
+            if (fabs(hg_det3(r.H)) < DBL_EPSILON) { status |= HG_ST_DEGENERATE; break; }      // R:863
+            num_inliers = r.inliers;                                                          // R:867-870
+            st[1] = num_inliers;
+            conf = num_inliers / (8 + 0.3 * n);                                               // R:874
+            conf = conf > 3. ? 0. : conf;                                                     // R:878
+            if (num_inliers < c.thresh2) break;                                               // R:881
+        }
+    }
+    st[0] = status;
+    if (lane < 9) {
+        double v = Hout[0];
+#pragma unroll
+        for (int i = 1; i < 9; ++i) v = lane == i ? Hout[i] : v;
+        ((double*)((char*)as_global(c.H) + (3ll * p + lane / 3) * c.H_step))[lane % 3] = v;
+    }
+    if (lane < 8) {
+        int v = st[0];
+#pragma unroll
+        for (int i = 1; i < 8; ++i) v = lane == i ? st[i] : v;
+        ((int*)((char*)as_global(c.stats) + (long long)p * c.stats_step))[lane] = v;
+    }
+    if (lane == 0) as_global(c.conf)[p] = conf;
+}
+
+struct HgScratch {
+    DevBuf work;
+    int device = -1;
+    void* pin = nullptr;                 // the upload: the table, host counts and the staged rows of host points mats
+    size_t pin_cap = 0;
+    hipEvent_t uploaded = nullptr;       // recorded after the upload that reads `pin`
+    bool pending = false;
+    hipEvent_t done = nullptr;           // recorded after the kernel: a call on another stream waits for it before it reuses `work`
+    hipStream_t last = nullptr;
+    bool ran = false;
+    bool lds_set = false;
+};
+
+int hg_wait_upload(HgScratch& s) {
+    if (s.pending) { ISX_HIP(hipEventSynchronize(s.uploaded)); s.pending = false; }
+    return ISX_OK;
+}
+int hg_release(HgScratch& s) {
+    ISX_TRY(hg_wait_upload(s));
+    if (s.uploaded) { ISX_HIP(hipEventDestroy(s.uploaded)); s.uploaded = nullptr; }
+    if (s.done) { ISX_HIP(hipEventDestroy(s.done)); s.done = nullptr; }
+    s.ran = false;
+    if (s.pin) { ISX_HIP(hipHostFree(s.pin)); s.pin = nullptr; s.pin_cap = 0; }
+    s.work.release();
+    s.device = -1;
+    return ISX_OK;
+}
+
+struct Bump {                            // offsets into one buffer, 256-byte aligned
+    size_t at = 0;
+    size_t take(size_t bytes) { const size_t o = at; at += (bytes + 255) & ~(size_t)255; return o; }
+};
+
+// a mat of `type` with at least rows x cols elements, aligned to `align` bytes in pointer and step; null data is fine where no row is needed
+int hg_check_mat(const isx_mat& m, int type, long long rows, int cols, int align, int device, const char* who, const char* what, int index) {
+    ISX_CHECK_ARG(m.type == type, ISX_ERR_TYPE, "%s: %s %d is %s (%s)", who, what, index, type_name(m.type), type_name(type));
+    ISX_CHECK_ARG(m.rows >= rows && (m.rows == 0 || rows == 0 || m.cols >= cols), ISX_ERR_SIZE, "%s: %s %d is %d x %d, the call needs %lld x %d", who, what,
+                  index, m.rows, m.cols, rows, cols);
+    if (m.rows == 0) return ISX_OK;
+    ISX_CHECK_ARG(m.cols >= cols, ISX_ERR_SIZE, "%s: %s %d has %d columns, the call needs %d", who, what, index, m.cols, cols);
+    ISX_CHECK_ARG(m.data != nullptr, ISX_ERR_INVALID, "%s: %s %d has a null data pointer", who, what, index);
+    ISX_CHECK_ARG(m.step >= (size_t)m.cols * mat_elem_size(type) || m.rows == 1, ISX_ERR_INVALID, "%s: %s %d: step %zu smaller than a row", who, what, index, m.step);
+    ISX_CHECK_ARG(((uintptr_t)m.data & (uintptr_t)(align - 1)) == 0 && (m.step & (size_t)(align - 1)) == 0, ISX_ERR_INVALID,
+                  "%s: %s %d is not %d-byte aligned in pointer and step", who, what, index, align);
+    ISX_CHECK_ARG(m.device < 0 || m.device == device, ISX_ERR_INVALID, "%s: %s %d lives on device %d, the call runs on %d", who, what, index, m.device, device);
+    return ISX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int isx_homography_release(void) ISX_ENTRY {
+    clear_error();
+    return hg_release(per_thread<HgScratch>());
+} ISX_EXIT("isx_homography_release")
+
+int isx_find_homography(int num_pairs, const isx_mat* points, const isx_mat* counts, double reproj_thresh, int max_iters, double confidence,
+                        int num_matches_thresh1, int num_matches_thresh2, isx_mat* H, isx_mat* inlier_masks, isx_mat* stats, isx_mat* conf,
+                        int* info, int device, void* hip_stream) ISX_ENTRY {
+    clear_error();
+    const char* who = "find_homography";
+    // ---- checks: all of them before anything is written or enqueued ----
+    ISX_CHECK_ARG(num_pairs >= 0, ISX_ERR_INVALID, "%s: %d pairs", who, num_pairs);
+    ISX_CHECK_ARG(num_pairs == 0 || (points && counts && H && inlier_masks && stats && conf), ISX_ERR_INVALID,
+                  "%s: null points, counts, H, inlier_masks, stats or conf", who);
+    ISX_CHECK_ARG(confidence > 0 && confidence < 1, ISX_ERR_INVALID, "%s: confidence %g is not in (0, 1)", who, confidence);        // R:156
+    ISX_CHECK_ARG(max_iters >= 1, ISX_ERR_INVALID, "%s: max_iters %d", who, max_iters);
+    ISX_CHECK_ARG(num_matches_thresh1 >= 0 && num_matches_thresh2 >= 0, ISX_ERR_INVALID, "%s: thresholds %d, %d", who, num_matches_thresh1, num_matches_thresh2);
+    ISX_CHECK_ARG(reproj_thresh == reproj_thresh, ISX_ERR_INVALID, "%s: reproj_thresh is not a number", who);
+    if (reproj_thresh <= 0) reproj_thresh = 3;                                                                                   // R:636
+    bool any_host_out = false, any_host_mask = false;
+    if (num_pairs > 0) {
+        ISX_TRY(hg_check_mat(*counts, ISX_32SC1, 1, num_pairs, 4, device, who, "counts", 0));
+        ISX_TRY(hg_check_mat(*H, ISX_64FC1, 3ll * num_pairs, 3, 8, device, who, "H", 0));
+        ISX_TRY(hg_check_mat(*stats, ISX_32SC1, num_pairs, 8, 4, device, who, "stats", 0));
+        ISX_TRY(hg_check_mat(*conf, ISX_64FC1, 1, num_pairs, 8, device, who, "conf", 0));
+        any_host_out = H->device < 0 || stats->device < 0 || conf->device < 0;
+    }
+    for (int p = 0; p < num_pairs; ++p) {
+        ISX_CHECK_ARG(points[p].rows >= 0 && inlier_masks[p].rows >= 0, ISX_ERR_INVALID, "%s: pair %d: negative rows", who, p);
+        ISX_TRY(hg_check_mat(points[p], ISX_32FC1, 0, 4, 4, device, who, "points", p));
+        ISX_TRY(hg_check_mat(inlier_masks[p], ISX_8UC1, 0, 1, 1, device, who, "inlier_masks", p));
+        any_host_mask |= inlier_masks[p].device < 0 && inlier_masks[p].rows > 0 && points[p].rows > 0;
+    }
+    any_host_out |= any_host_mask;
+    ISX_HIP(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    ISX_HIP(hipStreamIsCapturing(st, &cs));
+    ISX_CHECK_ARG(cs == hipStreamCaptureStatusNone, ISX_ERR_STATE, "%s: the stream is capturing (the call uploads its tables and may stage host mats)", who);
+    if (num_pairs == 0) {
+        if (info) { info[0] = 0; info[1] = 0; }
+        return ISX_OK;
+    }
+
+    // ---- one buffer: [upload: table | host counts | staged rows of host points] [work_a, work_b per pair] [staged host outputs] ----
+    std::vector<HgPair> prs((size_t)num_pairs);
+    std::vector<int> cap((size_t)num_pairs), up_rows((size_t)num_pairs, 0);
+    const int* h_counts = counts->device < 0 ? (const int*)counts->data : nullptr;
+    Bump lay;
+    const size_t o_prs = lay.take(prs.size() * sizeof(HgPair));
+    const size_t o_counts = h_counts ? lay.take((size_t)num_pairs * 4) : 0;
+    std::vector<size_t> o_pts((size_t)num_pairs, 0), o_wa((size_t)num_pairs, 0), o_wb((size_t)num_pairs, 0), o_mask((size_t)num_pairs, 0);
+    for (int p = 0; p < num_pairs; ++p) {
+        cap[p] = std::min(points[p].rows, inlier_masks[p].rows);
+        if (cap[p] > 0 && points[p].device < 0) {
+            // a host mat: the rows a host count names, else every row the kernel may read
+            up_rows[p] = h_counts ? std::min(std::max(h_counts[p], 0), cap[p]) : cap[p];
+            o_pts[p] = lay.take((size_t)up_rows[p] * 16);
+        }
+    }
+    const size_t upload_bytes = lay.at;
+    for (int p = 0; p < num_pairs; ++p) {
+        o_wa[p] = lay.take((size_t)cap[p] * 16);
+        o_wb[p] = lay.take((size_t)cap[p] * 16);
+    }
+    const size_t o_H = H->device < 0 ? lay.take((size_t)num_pairs * 72) : 0;
+    const size_t o_stats = stats->device < 0 ? lay.take((size_t)num_pairs * 32) : 0;
+    const size_t o_conf = conf->device < 0 ? lay.take((size_t)num_pairs * 8) : 0;
+    for (int p = 0; p < num_pairs; ++p)
+        if (cap[p] > 0 && inlier_masks[p].device < 0) o_mask[p] = lay.take((size_t)cap[p]);
+
+    HgScratch& s = per_thread<HgScratch>();
+    if (s.device != device) { ISX_TRY(hg_release(s)); s.device = device; s.lds_set = false; }
+    ISX_TRY(hg_wait_upload(s));                                   // the previous call's upload has read `pin`
+    ISX_TRY(s.work.reserve(lay.at));
+    if (s.pin_cap < upload_bytes) {
+        if (s.pin) { ISX_HIP(hipHostFree(s.pin)); s.pin = nullptr; s.pin_cap = 0; }
+        const size_t want = std::max<size_t>(upload_bytes + upload_bytes / 2, 1u << 16);
+        ISX_HIP(hipHostMalloc(&s.pin, want, hipHostMallocDefault));
+        s.pin_cap = want;
+    }
+    if (!s.uploaded) ISX_HIP(hipEventCreateWithFlags(&s.uploaded, hipEventDisableTiming));
+    if (!s.done) ISX_HIP(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+    if (!s.lds_set) {
+        ISX_HIP(hipFuncSetAttribute((const void*)k_hg_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, HG_LDS_BYTES));
+        s.lds_set = true;
+    }
+    if (s.ran && s.last != st) ISX_HIP(hipStreamWaitEvent(st, s.done, 0));
+    char* const dev = (char*)s.work.p;
+    char* const pin = (char*)s.pin;
+
+    // ---- fill the upload ----
+    for (int p = 0; p < num_pairs; ++p) {
+        HgPair& P = prs[p];
+        std::memset(&P, 0, sizeof(P));
+        P.cap = cap[p];
+        if (cap[p] == 0) continue;
+        const isx_mat& pm = points[p];
+        if (pm.device < 0) {
+            for (int r = 0; r < up_rows[p]; ++r) std::memcpy(pin + o_pts[p] + (size_t)r * 16, (const char*)pm.data + (size_t)r * pm.step, 16);
+            P.points = (const float*)(dev + o_pts[p]); P.points_step = 16;
+            P.cap = up_rows[p];                                   // the staged rows are what the kernel may read
+        } else {
+            P.points = (const float*)pm.data; P.points_step = (long long)pm.step;
+        }
+        const isx_mat& mm = inlier_masks[p];
+        P.mask = mm.device < 0 ? (unsigned char*)(dev + o_mask[p]) : (unsigned char*)mm.data;
+        P.mask_step = mm.device < 0 ? 1 : (long long)mm.step;
+        P.work_a = (float*)(dev + o_wa[p]); P.work_b = (float*)(dev + o_wb[p]);
+    }
+    std::memcpy(pin + o_prs, prs.data(), prs.size() * sizeof(HgPair));
+    if (h_counts) std::memcpy(pin + o_counts, h_counts, (size_t)num_pairs * 4);
+    ISX_HIP(hipMemcpyAsync(dev, pin, upload_bytes, hipMemcpyHostToDevice, st));
+    ISX_HIP(hipEventRecord(s.uploaded, st));
+    s.pending = true;
+
+    // ---- one launch ----
+    HgCall c;
+    c.pairs = (const HgPair*)(dev + o_prs);
+    c.counts = h_counts ? (const int*)(dev + o_counts) : (const int*)counts->data;
+    c.H = H->device < 0 ? (double*)(dev + o_H) : (double*)H->data;
+    c.H_step = H->device < 0 ? 24 : (long long)H->step;
+    c.stats = stats->device < 0 ? (int*)(dev + o_stats) : (int*)stats->data;
+    c.stats_step = stats->device < 0 ? 32 : (long long)stats->step;
+    c.conf = conf->device < 0 ? (double*)(dev + o_conf) : (double*)conf->data;
+    c.thresh = reproj_thresh; c.confidence = confidence;
+    c.max_iters = max_iters; c.thresh1 = num_matches_thresh1; c.thresh2 = num_matches_thresh2;
+    ISX_LAUNCH("homography_pairs", (double)num_pairs * 4096.0, st, k_hg_pairs, dim3((unsigned)num_pairs), dim3(HG_CHUNK), HG_LDS_BYTES, c);
+    ISX_HIP(hipEventRecord(s.done, st));
+    s.last = st; s.ran = true;
+
+    // ---- host outputs ----
+    if (any_host_out) {
+        std::vector<int> cnt_tmp;
+        const int* cnt = h_counts;
+        if (any_host_mask && !h_counts) {
+            cnt_tmp.resize((size_t)num_pairs);
+            ISX_HIP(hipMemcpyAsync(cnt_tmp.data(), counts->data, (size_t)num_pairs * 4, hipMemcpyDeviceToHost, st));
+            ISX_HIP(hipStreamSynchronize(st));
+            cnt = cnt_tmp.data();
+        }
+        if (H->device < 0) ISX_HIP(hipMemcpy2DAsync(H->data, H->step, dev + o_H, 24, 24, (size_t)3 * num_pairs, hipMemcpyDeviceToHost, st));
+        if (stats->device < 0) ISX_HIP(hipMemcpy2DAsync(stats->data, stats->step, dev + o_stats, 32, 32, (size_t)num_pairs, hipMemcpyDeviceToHost, st));
+        if (conf->device < 0) ISX_HIP(hipMemcpyAsync(conf->data, dev + o_conf, (size_t)num_pairs * 8, hipMemcpyDeviceToHost, st));
+        for (int p = 0; p < num_pairs; ++p) {
+            const isx_mat& mm = inlier_masks[p];
+            if (cap[p] == 0 || mm.device >= 0) continue;
+            const int n = std::min(std::max(cnt[p], 0), cap[p]);
+            if (n < num_matches_thresh1 || n == 0) continue;      // R:836: the mask is not written
+            ISX_HIP(hipMemcpy2DAsync(mm.data, mm.step, dev + o_mask[p], 1, 1, (size_t)n, hipMemcpyDeviceToHost, st));
+        }
+        ISX_HIP(hipStreamSynchronize(st));
+    }
+    if (info) { info[0] = num_pairs; info[1] = 1; }
+    return ISX_OK;
+} ISX_EXIT("isx_find_homography")
+
+}  // extern "C"

@@ -44,6 +44,7 @@ const char* type_name(int type) {
         case ISX_32SC1: return "CV_32SC1";
         case ISX_32FC1: return "CV_32FC1";
         case ISX_32FC3: return "CV_32FC3";
+        case ISX_64FC1: return "CV_64FC1";
         default: return "unsupported type";
     }
 }

@@ -56,11 +56,24 @@ def match_features(descriptors, pairs, match_conf, matches, counts, keypoints=No
 class MatchesInfo:
     """detail::MatchesInfo as far as M:158 and M:164-179 fill it: src_img_idx, dst_img_idx, matches as an (m, 3) int32 array of (queryIdx,
     trainIdx, distance), src_points / dst_points as (m, 2) float32 arrays (None without keypoints), knn as the pair (1->2, 2->1) of
-    n_query x 4 arrays (idx0, dist0, idx1, dist1) when asked for."""
+    n_query x 4 arrays (idx0, dist0, idx1, dist1) when asked for.  BestOf2NearestMatcher (homography.py) fills the rest: H (3 x 3 float64,
+    None when empty), inliers_mask (uint8, one per match; empty below num_matches_thresh1), num_inliers and confidence; FeaturesMatcher
+    leaves them at None, None, 0 and 0."""
 
     def __init__(self, src_img_idx, dst_img_idx, matches, src_points=None, dst_points=None, knn=None):
         self.src_img_idx, self.dst_img_idx, self.matches = src_img_idx, dst_img_idx, matches
         self.src_points, self.dst_points, self.knn = src_points, dst_points, knn
+        self.H, self.inliers_mask, self.num_inliers, self.confidence = None, None, 0, 0.0
+
+    def dual(self):
+        """The entry of the pair (to, from), as the reference's matcher derives it from (from, to): swapped image indices and points,
+        matches with queryIdx and trainIdx swapped, H.inv() by np.linalg.inv.  Host arithmetic: the inverse is not bit-pinned."""
+        m = self.matches.cpu().numpy() if _is_device(self.matches) else np.array(self.matches)
+        d = MatchesInfo(self.dst_img_idx, self.src_img_idx, m[:, [1, 0, 2]], self.dst_points, self.src_points,
+                        None if self.knn is None else (self.knn[1], self.knn[0]))
+        d.H = None if self.H is None else np.linalg.inv(self.H)
+        d.inliers_mask, d.num_inliers, d.confidence = self.inliers_mask, self.num_inliers, self.confidence
+        return d
 
 
 class FeaturesMatcher:
@@ -95,7 +108,7 @@ class FeaturesMatcher:
             dev = torch.device("cuda", int(self.device))
 
             def alloc(r, c, dt):
-                return torch.empty((r, c), dtype=torch.float32 if dt == np.float32 else torch.int32, device=dev)
+                return torch.empty((r, c), dtype=getattr(torch, np.dtype(dt).name), device=dev)
         else:
             def alloc(r, c, dt):
                 return np.empty((r, c), dt)
@@ -107,6 +120,7 @@ class FeaturesMatcher:
         ps = [p_all[at[k]:at[k + 1]] for k in range(len(pairs))] if p_all is not None else None
         ks = [alloc(rows[p[d]], 4, np.int32) for p in pairs for d in range(2)] if knn else None
         self.last_info = match_features(descriptors, pairs, self.match_conf, ms, counts, keypoints, img_sizes, ps, ks, self.device, self.stream)
+        post = self._post_match(alloc, cap, ps, counts)
         if on_device:
             import torch
             s = self.stream if hasattr(self.stream, "synchronize") else None
@@ -114,13 +128,21 @@ class FeaturesMatcher:
             cnt = counts.cpu().numpy()[0]
         else:
             cnt = counts[0]
+        fill = post() if post is not None else None
         out = []
         for k, (i, j) in enumerate(pairs):
             c = int(cnt[k])
             pts = ps[k][:c] if ps is not None else None
             out.append(MatchesInfo(i, j, ms[k][:c], None if pts is None else pts[:, 0:2], None if pts is None else pts[:, 2:4],
                                    (ks[2 * k], ks[2 * k + 1]) if knn else None))
+            if fill is not None:
+                fill(out[-1], k, c)
         return out
+
+    def _post_match(self, alloc, cap, points, counts):
+        """What a subclass enqueues behind the matcher on the same mats, before the read-back: None, or a callable that - once the stream
+        has been synchronised - returns fill(info, k, count)."""
+        return None
 
     __call__ = match
 

@@ -360,10 +360,19 @@ private:
 // The features matcher of the M demo (M = the reference's 特征点匹配 demo): BestOf2NearestMatcher1 matcher(false, 0.3f, 6, 6);
 // matcher(features, pairwise_matches) (M:307-308) as far as M:158 and the point gather of M:164-179 (isx_match_features): an exact 2-nearest-
 // neighbour search over 32-byte descriptors on the GPU, the ratio test and the de-duplication of M:232-289.  Homography, inliers and
-// confidence (M:181-229) are not built.
+// confidence (M:181-229) are BestOf2NearestMatcher's, below: FeaturesMatcher leaves H and inliers_mask empty, num_inliers and confidence 0.
 struct DMatch { int queryIdx = -1, trainIdx = -1; float distance = 0.f; };
 struct ImageFeatures { int img_idx = 0; Size img_size; std::vector<Point2f> keypoints; Mat descriptors; };      // descriptors: n x 32 CV_8UC1
-struct MatchesInfo { int src_img_idx = -1, dst_img_idx = -1; std::vector<DMatch> matches; std::vector<Point2f> src_points, dst_points; };
+struct MatchesInfo {
+    int src_img_idx = -1, dst_img_idx = -1;
+    std::vector<DMatch> matches;
+    std::vector<Point2f> src_points, dst_points;
+    std::vector<double> H;                        // empty, or the 3 x 3 homography, row-major (cv::detail::MatchesInfo::H)
+    std::vector<unsigned char> inliers_mask;      // empty, or one byte per match
+    int num_inliers = 0;
+    double confidence = 0;
+    int status = 0;                               // the ISX_HOMOGRAPHY_* bits of the pair
+};
 
 class FeaturesMatcher {
 public:
@@ -403,6 +412,7 @@ public:
         }
         check(isx_match_features(n, d.data(), pts ? kp.data() : nullptr, pts ? sizes.data() : nullptr, np, pij.data(), conf_, mm.data(), pts ? pm.data() : nullptr,
                                  counts.c(), nullptr, info_, device_, stream_));
+        afterMatch(pts ? &pm : nullptr, counts.c(), out);
         for (int k = 0; k < np; ++k) {
             MatchesInfo& mi = out[k];
             mi.src_img_idx = pij[2 * k]; mi.dst_img_idx = pij[2 * k + 1];
@@ -430,11 +440,59 @@ public:
     int pairsSearched() const { return info_[0]; }
     int launches() const { return info_[1]; }     // kernel launches of the last call: at most three, however many pairs
     static void release() { check(isx_match_release()); }
-private:
+    virtual ~FeaturesMatcher() {}
+protected:
+    // what a subclass runs on the matcher's points (NULL without keypoints) and counts mats before the records are filled
+    virtual void afterMatch(std::vector<isx_mat>*, isx_mat*, std::vector<MatchesInfo>&) {}
     float conf_;
     int device_;
     void* stream_;
+private:
     int info_[2] = {0, 0};
+};
+
+// BestOf2NearestMatcher1(try_use_gpu, match_conf, num_matches_thresh1, num_matches_thresh2) (R:781-782 of the 计算单应性矩阵 demo) with the whole of
+// its match(), R:830-911: FeaturesMatcher's matches, then findHomography(RANSAC), the inlier mask, num_inliers, confidence and the second run
+// on the inliers for every pair in one launch (isx_find_homography; without the Levenberg-Marquardt polish of R:672).  Needs keypoints.
+class BestOf2NearestMatcher : public FeaturesMatcher {
+public:
+    explicit BestOf2NearestMatcher(float match_conf = 0.3f, int num_matches_thresh1 = 6, int num_matches_thresh2 = 6, int device = 0, void* hip_stream = nullptr)
+        : FeaturesMatcher(match_conf, device, hip_stream), thresh1_(num_matches_thresh1), thresh2_(num_matches_thresh2) {}
+    void setRansac(double reproj_thresh, int max_iters, double confidence) { reproj_ = reproj_thresh; max_iters_ = max_iters; confidence_ = confidence; }
+    int homographyLaunches() const { return hinfo_[1]; }      // one, however many pairs
+    static void release() { FeaturesMatcher::release(); check(isx_homography_release()); }
+protected:
+    void afterMatch(std::vector<isx_mat>* points, isx_mat* counts, std::vector<MatchesInfo>& out) override {
+        if (!points) throw Exception(ISX_ERR_INVALID, "BestOf2NearestMatcher: the homography needs keypoints and img_sizes");
+        const int np = (int)out.size();
+        std::vector<double> H((size_t)9 * np), conf((size_t)np);
+        std::vector<int> stats((size_t)8 * np);
+        std::vector<std::vector<unsigned char> > masks(np);
+        std::vector<isx_mat> mm(np);
+        for (int k = 0; k < np; ++k) {
+            masks[k].resize((size_t)(*points)[k].rows);
+            mm[k].data = masks[k].data(); mm[k].rows = (*points)[k].rows; mm[k].cols = 1; mm[k].type = ISX_8UC1; mm[k].step = 1; mm[k].device = -1;
+        }
+        isx_mat hm, sm, cm;
+        hm.data = H.data(); hm.rows = 3 * np; hm.cols = 3; hm.type = ISX_64FC1; hm.step = 24; hm.device = -1;
+        sm.data = stats.data(); sm.rows = np; sm.cols = 8; sm.type = ISX_32SC1; sm.step = 32; sm.device = -1;
+        cm.data = conf.data(); cm.rows = 1; cm.cols = np; cm.type = ISX_64FC1; cm.step = sizeof(double) * (size_t)np; cm.device = -1;
+        check(isx_find_homography(np, points->data(), counts, reproj_, max_iters_, confidence_, thresh1_, thresh2_, &hm, mm.data(), &sm, &cm, hinfo_, device_, stream_));
+        for (int k = 0; k < np; ++k) {
+            MatchesInfo& mi = out[k];
+            const int cnt = ((const int*)counts->data)[k];
+            mi.status = stats[(size_t)8 * k];
+            if (mi.status & ISX_HOMOGRAPHY_H) mi.H.assign(H.begin() + 9 * k, H.begin() + 9 * k + 9);
+            if (cnt >= thresh1_) mi.inliers_mask.assign(masks[k].begin(), masks[k].begin() + cnt);      // R:836 returns before the mask exists
+            mi.num_inliers = stats[(size_t)8 * k + 1];
+            mi.confidence = conf[k];
+        }
+    }
+private:
+    int thresh1_, thresh2_;
+    double reproj_ = 3.0, confidence_ = 0.995;
+    int max_iters_ = 2000;
+    int hinfo_[2] = {0, 0};
 };
 
 // cv::imread(path) (W:166): the decoder follows the file's signature, as OpenCV's does - "BM" bitmaps and JFIF / Exif JPEGs;

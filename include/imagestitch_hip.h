@@ -52,7 +52,8 @@ enum {
     ISX_16SC3 = 19, /* CV_16SC3 : Blender::feed input / blend output (W:294,302,313)          */
     ISX_32SC1 = 4,  /* CV_32SC1 : the seam finder's label image labels_ (S:83)                    */
     ISX_32FC1 = 5,  /* CV_32FC1 : xmap / ymap (W:128-129)                                     */
-    ISX_32FC3 = 21  /* CV_32FC3 : float images (W:261; B:143-145)                             */
+    ISX_32FC3 = 21, /* CV_32FC3 : float images (W:261; B:143-145)                             */
+    ISX_64FC1 = 6   /* CV_64FC1 : MatchesInfo::H and confidence (R:862, R:874): isx_find_homography only */
 };
 
 /* cv::InterpolationFlags / cv::BorderTypes values used by W:229,232 */
@@ -633,7 +634,7 @@ enum { ISX_MATCH_QUERY_BLOCK = 128, ISX_MATCH_TRAIN_TILE = 128, ISX_MATCH_TRAIN_
  *        (row0, q).
  * An accepted match has a unique nearest neighbour (d0 < k d1 <= d1), so the list does not depend on how ties are ordered.  A pair with an
  * empty image is skipped: its count is 0 and nothing else of it is written (M:134).  homography, inliers and confidence (M:181-229) are
- * not built.
+ * isx_find_homography's, which reads `points` and `counts` where this call leaves them.
  *   descriptors  num_images CV_8UC1 mats of n_i x 32 (ORB; CV_32F / SURF descriptors are not built: cols != 32 -> ISX_ERR_UNSUPPORTED), host or
  *                device, any pointer alignment and step; rows may be 0 (then data and cols are not looked at).  At most 2^20 rows an
  *                image and 2^22 in all (ISX_ERR_UNSUPPORTED).
@@ -659,6 +660,55 @@ int isx_match_features(int num_images, const isx_mat* descriptors, const isx_mat
 /* Returns the scratch of the calling thread (the matcher going out of scope).  PER THREAD and not freed at thread exit, as for
  * isx_voronoi_seam_release.                                                                                                            */
 int isx_match_release(void);
+
+/* ---- findHomography, inliers and confidence (R = the reference's 计算单应性矩阵/计算单应性矩阵/计算单应性矩阵.cpp) ------------------------- */
+/* Hypotheses per chunk of the RANSAC kernel (homography.hip takes it from here): one per lane of the pair's wave. */
+enum { ISX_HOMOGRAPHY_CHUNK = 64 };
+/* status bits of stats column 0 */
+enum { ISX_HOMOGRAPHY_H = 1,            /* H is not empty                                                                  */
+       ISX_HOMOGRAPHY_PASS2 = 2,        /* the second run on the inliers ran (R:881-909)                                    */
+       ISX_HOMOGRAPHY_PASS2_FAILED = 4, /* ... and failed: H is empty (R:909 assigns its result), bit 0 is clear            */
+       ISX_HOMOGRAPHY_CLAMPED = 8,      /* the count exceeded the rows of its points or mask mat and was clamped to them    */
+       ISX_HOMOGRAPHY_DEGENERATE = 16   /* |det H| < DBL_EPSILON: R:863 returned, H is pass 1's, num_inliers and conf are 0 */ };
+/* The second half of BestOf2NearestMatcher1::match, R:836-909, for every pair of a matcher call, WITHOUT the Levenberg-Marquardt polish of
+ * R:672 (createLMSolver1(...)->run(H8), R:461-591: not built; it changes neither mask, count nor confidence - H here is the least-squares
+ * runKernel over the inliers that LM starts from).  Per pair, with n = counts[p]:
+ *   n < num_matches_thresh1 (R:836)   H, stats and conf are zeros, the mask is not written.
+ *   pass 1 (R:862)                    findHomography2(src, dst, RANSAC, reproj_thresh, mask, max_iters, confidence) (R:602-693): n < 4 fails
+ *                                     (R:159; H empty, the mask zeros, R:687); n == 4 is runKernel itself with the mask all ones (R:641-645);
+ *                                     else RANSACPointSetRegistrator1::run (R:139-233) with RNG rng((uint64)-1), getSubset's 10000 attempts
+ *                                     (R:88-137), checkSubset (R:253-288), runKernel (R:304-373; R itself lost the call between R:196 and
+ *                                     R:197, it is in place here), computeError / findInliers in float32 (R:383-402, R:67-86),
+ *                                     RANSACUpdateNumIters1 (R:39-59), then runKernel over all inliers (R:657-668).
+ *   R:863                             an empty H or |det H| < DBL_EPSILON stops here: num_inliers = 0, conf = 0, the mask stays as written.
+ *   R:866-878                         num_inliers = the mask's sum; conf = num_inliers / (8 + 0.3 n) in double, a value > 3 becomes 0.
+ *   pass 2 (R:881-909)                with num_inliers >= num_matches_thresh2: findHomography2 again over the inliers only (no mask out, a
+ *                                     fresh RNG); H is its result, empty if it fails.
+ * cv::eigen (JacobiImpl_), cv::RNG, haveCollinearPoints and cvRound are in neither tree and are restated (DESIGN.md §8 "Homography",
+ * tests/helpers/homography_np.py - the specification): parity with OpenCV is not pinned.
+ *   points        per pair the matcher's CV_32FC1 mat, rows x >= 4: src.x, src.y, dst.x, dst.y; host or device, 4-byte aligned.
+ *   counts        the matcher's CV_32SC1 mat of at least 1 x num_pairs.  A device mat is read ON THE DEVICE, never read back to size anything:
+ *                 capacities are the mats' rows.  A count above the rows of its points or mask mat is clamped to them (status bit 3), a
+ *                 negative one is 0.
+ *   reproj_thresh <= 0 means 3 (R:636); max_iters >= 1; confidence in (0, 1) (R:156); the thresholds >= 0 (6 and 6 at R:781).
+ *   H             a CV_64FC1 mat of at least 3 num_pairs x 3, pair p in rows 3p .. 3p + 2; an empty H is nine zeros with status bit 0 clear.
+ *   inlier_masks  per pair a CV_8UC1 mat of at least count x 1 (any pointer and step): rows [0, count) get 0 or 1 (R:82), later rows are not
+ *                 written.
+ *   stats         a CV_32SC1 mat of at least num_pairs x 8: status bits, num_inliers, the iterations run and the winning iteration (-1: none)
+ *                 of pass 1, the same of pass 2, getSubset's attempts in total, 0.
+ *   conf          a CV_64FC1 mat of at least 1 x num_pairs.
+ *   info          NULL, or 2 ints: the pairs processed and the kernel launches of this call - ONE, however many pairs.
+ * Output mats are host or device mats, 4-byte aligned in pointer and step, 8-byte for H and conf.  Checked before anything is written or
+ * enqueued: null pointers, num_pairs < 0, the scalar ranges above, a misaligned mat -> ISX_ERR_INVALID; a mat of another type ->
+ * ISX_ERR_TYPE; too few rows or columns -> ISX_ERR_SIZE.  The call uploads its table (and stages host mats): on a capturing stream ->
+ * ISX_ERR_STATE with nothing enqueued.  With device mats throughout nothing is read back or synchronised.  Host mats synchronise.
+ * The bits of H and conf are those of the specification except where pow / log of R:51-56 land within an ulp of a rounding boundary of the
+ * iteration count.                                                                                                       */
+int isx_find_homography(int num_pairs, const isx_mat* points, const isx_mat* counts, double reproj_thresh, int max_iters, double confidence,
+                        int num_matches_thresh1, int num_matches_thresh2, isx_mat* H, isx_mat* inlier_masks, isx_mat* stats, isx_mat* conf,
+                        int* info, int device, void* hip_stream);
+/* Returns the scratch of the calling thread.  PER THREAD and not freed at thread exit, as for isx_match_release.                          */
+int isx_homography_release(void);
 
 /* ---- on-disk format either side of the path: .bmp (W:166 imread, W:155-156,315 imwrite) ----------- */
 /* Reading: uncompressed Windows bitmaps only (the reference's inputs and committed artefacts are BMPs).

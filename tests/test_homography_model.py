@@ -1,0 +1,179 @@
+"""The NumPy specification of isx_find_homography (tests/helpers/homography_np.py) on its own: cv::RNG's first values by hand, the Jacobi
+against np.linalg.eigh and against its own line-by-line form, runKernel on a planted homography, RANSACUpdateNumIters1's table, every early
+out, and that no named or generated case is fragile (margin >= 1e-9: the outcome does not hang on an ulp of pow / log).  CPU only."""
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import homography_cases as cases  # noqa: E402
+from helpers import homography_np as hm  # noqa: E402
+
+NAMED = cases.named()
+
+
+def test_rng_known_answers():
+    """state = (uint64)(uint32)state * 4294883355 + (uint32)(state >> 32), from 2^64 - 1.  By hand: the low word is 2^32 - 1, so
+    state1 = (2^32 - 1) * 4294883355 + (2^32 - 1) = (2^32 - 1) * 4294883356 = 4294883356 * 2^32 - 4294883356
+           = 4294883355 * 2^32 + (2^32 - 4294883356) = 4294883355 * 2^32 + 83940,
+    the first value is 83940; then state2 = 83940 * 4294883355 + 4294883355 = 83941 * 4294883355 = 360516803702055 = 83939 * 2^32 +
+    (360516803702055 - 360515259858944), the second value is that remainder, 1543843111."""
+    r = hm.RNG()
+    assert r.state == 2 ** 64 - 1
+    assert r.next() == 83940 and r.state == 4294883355 * 2 ** 32 + 83940
+    s2 = 83941 * 4294883355
+    assert s2 == 360516803702055 and s2 // 2 ** 32 == 83939
+    assert r.next() == s2 - 83939 * 2 ** 32 == 1543843111
+    s3 = 1543843111 * 4294883355 + 83939
+    assert r.next() == s3 % 2 ** 32 and r.state == s3
+    r = hm.RNG()
+    assert [r.uniform(0, 10), r.uniform(0, 7)] == [83940 % 10, 1543843111 % 7]
+    r = hm.RNG()
+    assert r.uniform(5, 9) == 5 + 83940 % 4
+
+
+def _case_matrices():
+    out = []
+    for name in ("n6_exact", "n65_half_noisy", "n300_half_noisy", "repeated_5x4", "outliers_to_the_end"):
+        pts = NAMED[name][0]
+        ok, LtL, _, _ = hm.build_ltl(pts[None, :, 0:2], pts[None, :, 2:4])
+        assert ok[0]
+        out.append(LtL[0])
+        ok, LtL, _, _ = hm.build_ltl(pts[None, :4, 0:2], pts[None, :4, 2:4])
+        out.append(LtL[0])
+    return np.array(out)
+
+
+def test_jacobi_against_eigh_and_its_two_forms_agree():
+    A = _case_matrices()
+    full = np.triu(A) + np.triu(A, 1).transpose(0, 2, 1)              # completeSymm; the Jacobi reads the upper triangle only
+    W, V, rot = hm.jacobi(A, batched=True)
+    assert (rot > 20).all() and (rot < 9 * 9 * 30).all()
+    for b in range(len(A)):
+        w = np.linalg.eigvalsh(full[b])[::-1]
+        assert np.abs(W[b] - w).max() <= 1e-9 * np.abs(w).max()
+        assert np.linalg.norm((full[b] - W[b, 8] * np.eye(9)) @ V[b, 8]) <= 1e-9 * np.linalg.norm(full[b])
+        assert abs(np.linalg.norm(V[b, 8]) - 1) < 1e-12 and (np.diff(W[b]) <= 0).all()
+        Ws, Vs, rs = hm.jacobi_scalar(A[b])                           # OpenCV's loop line by line: the same bits
+        assert np.array_equal(np.array(Ws), W[b]) and np.array_equal(np.array(Vs), V[b]) and rs == rot[b]
+    W2, V2, _ = hm.jacobi(np.concatenate([A[3:], A[:3]]), batched=True)      # a lane's result does not depend on its neighbours
+    assert np.array_equal(W2, np.concatenate([W[3:], W[:3]])) and np.array_equal(V2, np.concatenate([V[3:], V[:3]]))
+    W3, V3, _ = hm.jacobi(np.diag(np.arange(9.0))[None])              # nothing to rotate: sorted descending, V a permutation
+    assert np.array_equal(W3[0], np.arange(8.0, -1, -1)) and np.array_equal(V3[0], np.eye(9)[::-1])
+
+
+def test_hypot_is_opencvs():
+    assert hm._hypot1(3.0, 4.0) == 4.0 * np.sqrt(1.0 + 0.75 * 0.75) and hm._hypot1(0.0, 0.0) == 0.0 and hm._hypot1(-5.0, 0.0) == 5.0
+    a, b = np.array([3.0, 0.0, -5.0, 1e-300]), np.array([4.0, 0.0, 0.0, 1e-300])
+    assert np.array_equal(hm._hypot(a, b), [hm._hypot1(x, y) for x, y in zip(a, b)])
+
+
+def test_run_kernel_recovers_a_planted_homography():
+    for n in (4, 5, 30, 300):
+        pts = cases.exact(n, n)
+        ok, H = hm.run_kernel(pts[None, :, 0:2], pts[None, :, 2:4])
+        assert ok[0] and H[0, 8] == 1.0
+        assert np.allclose(H[0].reshape(3, 3), cases.H_TRUE, rtol=1e-4, atol=2e-7), (n, H[0].reshape(3, 3) - cases.H_TRUE)
+    ok, _ = hm.run_kernel(cases.all_the_same(4)[None, :, 0:2], cases.all_the_same(4)[None, :, 2:4])
+    assert not ok[0]                                                  # R:339-341
+    both = np.stack([cases.exact(1, 4), cases.all_the_same(4)])
+    ok, H = hm.run_kernel(both[:, :, 0:2], both[:, :, 2:4])          # a batch with a degenerate member
+    assert ok.tolist() == [True, False] and np.array_equal(H[0], hm.run_kernel(both[:1, :, 0:2], both[:1, :, 2:4])[1][0])
+
+
+def test_check_subset_and_collinearity():
+    sq = np.array([[0, 0], [10, 0], [10, 10], [0, 10]], np.float32)
+    assert hm.check_subset(sq, sq + 3) and hm.check_subset(sq, sq[::-1].copy())        # a reflection flips all four signs
+    assert not hm.check_subset(sq, sq[[0, 1, 3, 2]])                                   # a twisted quadrilateral
+    line = np.array([[0, 0], [1, 2], [5, 1], [2, 4]], np.float32)                      # the LAST point is collinear with 0 and 1
+    assert hm.have_collinear_points(line, 4) and not hm.have_collinear_points(line[[3, 1, 0, 2]], 4)      # only the last point is tested
+    assert not hm.check_subset(line, sq) and not hm.check_subset(sq, line)
+    dup = sq.copy()
+    dup[3] = dup[1]
+    assert hm.have_collinear_points(dup, 4)                                            # a repeated point is collinear with anything
+
+
+def test_update_num_iters_table():
+    assert hm.update_num_iters(0.995, 0.0, 4, 2000) == 0                               # ep = 0: denom < DBL_MIN
+    assert hm.update_num_iters(0.995, 1.0, 4, 2000) == 2000                            # denom = log(1) = 0 >= 0
+    assert hm.update_num_iters(0.995, 0.999, 4, 2000) == 2000                          # more than max_iters
+    assert hm.update_num_iters(0.995, 0.5, 4, 2000) == 82 == round(np.log(0.005) / np.log(1 - 0.5 ** 4))
+    assert hm.update_num_iters(0.995, 0.5, 4, 50) == 50
+    assert hm.update_num_iters(2.0, 0.5, 4, 2000) == 2000                              # p clamps to 1: num = log(DBL_MIN), far past max_iters
+    assert hm.update_num_iters(-1.0, 0.5, 4, 2000) == 0                                # p clamps to 0: log(1) / denom = -0 -> 0
+    assert hm.update_num_iters(0.995, -3.0, 4, 2000) == 0                              # ep clamps to 0
+    assert hm._cv_round(2.5) == 2 and hm._cv_round(3.5) == 4 and hm._cv_round(2.4999) == 2
+    m = []
+    hm.update_num_iters(0.995, 0.5, 4, 2000, m)
+    q = np.log(0.005) / np.log(1 - 0.5 ** 4)
+    assert len(m) == 1 and abs(m[0] - abs(q - (np.floor(q) + 0.5)) / q) < 1e-12
+
+
+def test_every_early_out():
+    z8 = [0] * 8
+    r = hm.find_homography_np(cases.exact(5, 5))                      # n < thresh1 (R:836): nothing, the mask not written
+    assert r["mask"] is None and r["stats"].tolist() == z8 and r["conf"] == 0.0 and not r["H"].any()
+    r = hm.find_homography_np(np.zeros((0, 4), np.float32), num_matches_thresh1=0)
+    assert r["mask"].shape == (0,) and r["stats"].tolist() == [0, 0, 0, -1, 0, -1, 0, 0]
+    r = hm.find_homography_np(cases.exact(3, 3), num_matches_thresh1=2)               # n < 4 (R:159): H empty, the mask zeros (R:687)
+    assert r["mask"].tolist() == [0, 0, 0] and r["stats"][0] == 0 and not r["H"].any()
+    r = hm.find_homography_np(cases.exact(4, 4), num_matches_thresh1=4)               # n == 4 (R:641-645): the mask ones; 4 < thresh2
+    assert r["mask"].tolist() == [1] * 4 and r["stats"].tolist() == [hm.ST_H, 4, 0, -1, 0, -1, 0, 0] and r["conf"] == 4 / (8 + 0.3 * 4)
+    assert np.allclose(r["H"], cases.H_TRUE, rtol=1e-3, atol=1e-6)
+    r2 = hm.find_homography_np(cases.exact(4, 4), num_matches_thresh1=4, num_matches_thresh2=4)      # ... and with pass 2: the same H
+    assert r2["stats"][0] == hm.ST_H | hm.ST_PASS2 and np.array_equal(r2["H"], r["H"])
+    r = hm.find_homography_np(cases.all_the_same(4), num_matches_thresh1=4)           # runKernel returns 0
+    assert r["mask"].tolist() == [0] * 4 and r["stats"][0] == 0
+    r = hm.find_homography_np(cases.collinear(40))                    # getSubset fails at iteration 0
+    assert r["stats"].tolist() == [0, 0, 0, -1, 0, -1, 10000, 0] and r["mask"].tolist() == [0] * 40
+    r = hm.find_homography_np(cases.exact(9, 9), count=12, mask_rows=7)               # clamped to the smaller capacity
+    assert r["stats"][0] & hm.ST_CLAMPED and len(r["mask"]) == 7
+    r = hm.find_homography_np(cases.exact(9, 9), count=-2)
+    assert r["stats"].tolist() == z8 and r["mask"] is None
+    big = cases.exact(300, 300)                                       # conf > 3 becomes 0 (R:878): 300 / 98 > 3
+    r = hm.find_homography_np(big)
+    assert r["stats"][1] == 300 and r["conf"] == 0.0 and r["stats"][0] == hm.ST_H | hm.ST_PASS2
+    k = int(hm.find_homography_np(NAMED["n64_half_noisy"][0])["stats"][1])            # thresh2 (R:881)
+    assert hm.find_homography_np(NAMED["n64_half_noisy"][0], num_matches_thresh2=k + 1)["stats"][0] == hm.ST_H
+
+
+def test_the_degenerate_h_test_stops_before_the_count():
+    """R:863: |det H| < DBL_EPSILON - H is kept, the mask stays as written, nothing is counted."""
+    pts, kw = NAMED["degenerate_det"]
+    r = hm.find_homography_np(pts, **kw)
+    assert r["stats"][0] == hm.ST_H | hm.ST_DEGENERATE and r["stats"][1] == 0 and r["conf"] == 0.0 and r["H"].any() and r["mask"].sum() >= 4
+    assert abs(hm.det3(r["H"].reshape(9))) < hm.DBL_EPSILON
+
+
+@pytest.mark.parametrize("name", sorted(NAMED))
+def test_no_named_case_is_fragile(name):
+    pts, kw = NAMED[name]
+    r = hm.find_homography_np(pts, **kw)
+    assert r["margin"] >= 1e-9
+    n = len(pts)
+    if r["mask"] is not None and r["stats"][0] & hm.ST_H and not r["stats"][0] & hm.ST_DEGENERATE:
+        assert r["stats"][1] == r["mask"].sum() and len(r["mask"]) == n
+
+
+def test_the_generators_first_200_cases_are_not_fragile():
+    margins = [hm.find_homography_np(cases.generated(i))["margin"] for i in range(200)]
+    assert min(margins) >= 1e-9, (int(np.argmin(margins)), min(margins))
+    assert min(margins) >= 1e-7                                       # far inside: a fuzz that skips fragile cases skips next to none
+
+
+def test_header_arity_equals_the_ctypes_signature():
+    from imagestitch_amd import _lib
+    text = open(os.path.join(ROOT, "include", "imagestitch_hip.h"), encoding="utf-8").read()
+    for name in ("isx_find_homography", "isx_homography_release"):
+        m = re.search(r"\bint\s+%s\s*\(([^;]*?)\)\s*;" % name, text, re.S)
+        assert m, name
+        args = m.group(1).strip()
+        arity = 0 if args == "void" else len(args.split(","))
+        assert arity == len(_lib._SIGS[name]), (name, arity)
+        assert name in _lib.declared_symbols()
+    assert _lib.ISX_64FC1 == 6 and re.search(r"ISX_64FC1\s*=\s*6\b", text) and _lib._NP_TYPES[("float64", 1)] == 6
+    assert _lib.as_mat(np.zeros((3, 3), np.float64)).type == 6 and _lib.as_mat(np.zeros((3, 3), np.float64)).step == 24
