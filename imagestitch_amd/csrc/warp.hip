@@ -25,6 +25,7 @@
 #include <unordered_map>
 #include <cstring>
 #include <new>
+#include <type_traits>
 
 using namespace isx;
 using namespace isxd;
@@ -1135,10 +1136,15 @@ void roi_plane_host(const Proj& p, const float t[3], int sw, int sh, int roi[4],
     roi[0] = f2i_host(tl_u); roi[1] = f2i_host(tl_v); roi[2] = f2i_host(br_u); roi[3] = f2i_host(br_v);
 }
 
+constexpr double PI_D = 3.14159265358979323846;
+// v of the spherical projection's north pole, pi * scale in double: SphericalWarper::detectResultRoi rounds it to float once ((float)pi_scale(s));
+// mapForward's own limit of u is the float product scale * PI_F, a different value
+inline double pi_scale(float scale) { return PI_D * scale; }
+
 // the stand-ins of forward_proxy as functions of u and v (monotone increasing), in double
 double proxy_d_of_u(double u, double scale) {
     double th = u / scale;
-    const double pi = 3.14159265358979323846;
+    const double pi = PI_D;
     th = std::max(-pi, std::min(pi, th));
     double sx = std::sin(th), cz = std::cos(th);
     double t = std::fabs(sx) / (std::fabs(sx) + std::fabs(cz));
@@ -1148,8 +1154,7 @@ double proxy_d_of_u(double u, double scale) {
 double proxy_q_of_v(double v, double scale) { return v / scale; }
 // spherical: v = scale (pi - acos w)  =>  w = cos(pi - v / scale) = -cos(v / scale), increasing on [0, pi scale]
 double proxy_w_of_v(double v, double scale) {
-    const double pi = 3.14159265358979323846;
-    const double a = std::max(0.0, std::min(pi, v / scale));
+    const double a = std::max(0.0, std::min(PI_D, v / scale));
     return -std::cos(a);
 }
 
@@ -1194,72 +1199,242 @@ void trunc_interval(int bound, double& lo, double& hi) {
     else { lo = -1.0; hi = 1.0; }
 }
 
+bool valid_kind(int kind) { return kind == ISX_WARP_CYLINDRICAL || kind == ISX_WARP_SPHERICAL || kind == ISX_WARP_PLANE; }
+
+// is what is enqueued on the stream captured instead of run?  (a query that fails counts as no; its error is swallowed)
+bool stream_is_capturing(hipStream_t st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { cs = hipStreamCaptureStatusNone; (void)hipGetLastError(); }
+    return cs != hipStreamCaptureStatusNone;
+}
+
+// The two streams every warper of a device shares (never destroyed).  One stream per warper would run a batch of pairs out of hardware
+// queues (16 pairs: 44 instead of 51 Gpix/s).  (A high-priority stream changes nothing: a resident wave is not preempted; measured 40 us
+// per call beside a saturating kernel either way.)
+enum { SHARED_VERIFY = 0, SHARED_ROI = 1 };      // planned warps' verification scans; the synchronous ROI scans
+int shared_stream(int device, int slot, hipStream_t* out) {
+    static std::mutex mu;
+    static hipStream_t shared[2][64] = {};
+    std::lock_guard<std::mutex> lk(mu);
+    const int d = device >= 0 && device < 64 ? device : 0;
+    if (!shared[slot][d]) ISX_HIP(hipStreamCreateWithFlags(&shared[slot][d], hipStreamNonBlocking));
+    *out = shared[slot][d];
+    return ISX_OK;
+}
+
+// {keys[4], count, mismatches, ...} of a scan: allocated and armed once (min keys 0xffffffff, max keys, candidate count and the sticky
+// mismatch counter 0); every consumer re-arms the keys behind itself (k_roi_rearm / k_roi_check_rearm)
+int arm_scan_once(DevBuf& buf, size_t bytes, hipStream_t st) {
+    if (buf.p) return ISX_OK;
+    ISX_TRY(buf.reserve(bytes));
+    ISX_HIP(hipMemsetAsync(buf.p, 0, 64, st));
+    ISX_HIP(hipMemsetAsync(buf.p, 0xff, 2 * sizeof(unsigned), st));
+    return ISX_OK;
+}
+
+// ---- part 1 of a warper's host state: the arena of mapBackward tables ------------------------------------------------------------------
+// One entry per (kind, scale, translation, roi): a rig's tiles alternate between a few ROIs, and a fixed rig (the reference, every BASELINE
+// config) asks for the same few for ever.  Up to TAB_SLOTS entries stay (round 5: with 16 entries and one shared host buffer a panorama of
+// more than 16 tiles through one handle missed on EVERY warp - two stream synchronisations and 7 000 sinf / cosf per call: the 64-tile step
+// was host-bound at 68 us per 27 us warp kernel, profiles/round5_many_tiles_trace.txt), found through a hash, not a scan.  The
+// tables live in a few TAB_CHUNK chunks, bump-allocated (a DevBuf per entry was a megabyte per entry - reserve() rounds up), at most
+// TAB_BYTES of them: a caller whose camera changes with every frame never hits, and for it the arena is bounded by bytes.
+// The invariants, all of them here:
+//  - an entry exists only once its table is on the device (insert uploads and waits before it records);
+//  - a chunk that a warp enqueued on a CAPTURING stream read from is pinned: a graph holds raw pointers into it, so it is never rewritten -
+//    a start-over moves it to `kept` (freed with the arena) and goes on in fresh chunks;
+//  - the streams the handle left since the last start-over are fenced, each by an event recorded at its last position there;
+//  - a start-over reuses memory only after the caller has flushed what it collected (make_tabs), every fence has passed and the current
+//    stream is drained: enqueued kernels may still read the old tables.
+struct TableArena {
+    static constexpr size_t TAB_SLOTS = 1024, TAB_BYTES = (size_t)16 << 20, TAB_CHUNK = (size_t)4 << 20;
+    struct Entry { int kind; float scale; float t[3]; int roi[4]; const float* dev; size_t chunk; };
+    std::vector<Entry> entries;
+    std::unordered_multimap<unsigned long long, size_t> index;      // hash of (kind, scale, translation, roi) -> entry
+    std::vector<std::unique_ptr<DevBuf>> chunks, kept;
+    std::vector<char> pinned;                                       // per chunk
+    size_t chunk = 0, used = 0;                                     // the chunk being filled and the bytes used in it
+    long long resets = 0;
+    std::vector<std::pair<hipStream_t, hipEvent_t>> fences;
+    std::vector<float> staging;                                     // the one table being built (its upload is waited for)
+
+    ~TableArena() { for (const auto& f : fences) (void)hipEventDestroy(f.second); }
+
+    static size_t room_for(size_t floats) { return (floats * sizeof(float) + 255) & ~(size_t)255; }
+    static unsigned long long hash(int kind, float scale, const float t[3], const int roi[4]) {
+        unsigned sbits; memcpy(&sbits, &scale, 4);
+        unsigned tbits[3]; memcpy(tbits, t, 12);
+        const unsigned words[9] = {(unsigned)kind, sbits, (unsigned)roi[0], (unsigned)roi[1], (unsigned)roi[2], (unsigned)roi[3], tbits[0], tbits[1], tbits[2]};
+        unsigned long long key = 1469598103934665603ull;
+        for (unsigned v : words) { key ^= v; key *= 1099511628211ull; }
+        return key;
+    }
+    const Entry* find(int kind, float scale, const float t[3], const int roi[4]) const {
+        const auto r = index.equal_range(hash(kind, scale, t, roi));
+        for (auto it = r.first; it != r.second; ++it) {
+            const Entry& c = entries[it->second];
+            if (c.kind == kind && c.scale == scale && memcmp(c.t, t, sizeof(c.t)) == 0 && std::equal(roi, roi + 4, c.roi)) return &c;
+        }
+        return nullptr;
+    }
+    // no room for one more table of `need` bytes: the entry list or the last chunk TAB_BYTES allows is full
+    bool full(size_t need) const { return entries.size() >= TAB_SLOTS || (!chunks.empty() && used + need > TAB_CHUNK && (chunk + 2) * TAB_CHUNK > TAB_BYTES); }
+    int start_over(hipStream_t current) {
+        for (const auto& f : fences) ISX_HIP(hipEventSynchronize(f.second));
+        ISX_HIP(hipStreamSynchronize(current));
+        for (const auto& f : fences) (void)hipEventDestroy(f.second);
+        fences.clear();
+        std::vector<std::unique_ptr<DevBuf>> reuse;
+        for (size_t c = 0; c < chunks.size(); ++c) (c < pinned.size() && pinned[c] ? kept : reuse).push_back(std::move(chunks[c]));
+        chunks.swap(reuse);
+        pinned.assign(chunks.size(), 0);
+        entries.clear(); index.clear(); chunk = 0; used = 0; ++resets;
+        return ISX_OK;
+    }
+    // the table in `staging` goes up on `st` and becomes an entry (room_for(staging.size()) <= TAB_CHUNK and !full(): the caller's)
+    int insert(int kind, float scale, const float t[3], const int roi[4], hipStream_t st, const Entry** out) {
+        const size_t need = room_for(staging.size());
+        if (!chunks.empty() && used + need > TAB_CHUNK) { ++chunk; used = 0; }
+        if (chunk >= chunks.size()) {
+            chunks.emplace_back(new DevBuf());
+            ISX_TRY(chunks.back()->reserve(TAB_CHUNK));
+            pinned.resize(chunks.size(), 0);
+        }
+        float* dev = (float*)((char*)chunks[chunk]->p + used);
+        ISX_HIP(hipMemcpyAsync(dev, staging.data(), staging.size() * sizeof(float), hipMemcpyHostToDevice, st));
+        // A miss is a planning-time event: the upload is simply waited for (so one staging vector serves).  (Tried without the wait in round 5, every
+        // entry keeping a host copy alive: the world-8 rehearsal of bench.py then delivered a wrong mosaic in 4 runs of 7 - on this runtime an asynchronous copy
+        // from PAGEABLE memory is not something a kernel launched right behind it on the same stream can rely on; 8 of 8 runs pass with the wait.)
+        ISX_HIP(hipStreamSynchronize(st));
+        used += need;
+        entries.emplace_back();
+        Entry& e = entries.back();
+        e.kind = kind; e.scale = scale; memcpy(e.t, t, sizeof(e.t)); std::copy(roi, roi + 4, e.roi); e.dev = dev; e.chunk = chunk;
+        index.emplace(hash(kind, scale, t, roi), entries.size() - 1);
+        *out = &e;
+        return ISX_OK;
+    }
+    // the handle moves off `st`, which may still run warps that read the arena: a later start-over waits for this point of it (a stream
+    // being captured enqueues nothing that runs now, and the chunks its graph reads are pinned)
+    int leave_stream(hipStream_t st) {
+        if (entries.empty() || stream_is_capturing(st)) return ISX_OK;
+        hipEvent_t ev = nullptr;
+        for (const auto& f : fences) if (f.first == st) ev = f.second;
+        if (!ev) {
+            ISX_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+            fences.emplace_back(st, ev);
+        }
+        ISX_HIP(hipEventRecord(ev, st));
+        return ISX_OK;
+    }
+    void pin(size_t c) { pinned[c] = 1; }
+};
+
+// mapBackward's separable, transcendental part (W:48-53): per column sin / cos of u / scale, per row the terms of v / scale; the four
+// segments padded to 16 bytes (the fused kernel loads float4)
+void fill_tables(int kind, float scale, const float t[3], const int roi[4], std::vector<float>& tab) {
+    const int mw = roi[2] - roi[0] + 1, mh = roi[3] - roi[1] + 1;
+    const int mwp = (mw + 3) & ~3, mhp = (mh + 3) & ~3;
+    tab.assign((size_t)2 * mwp + 2 * mhp, 0.f);
+    float* cs = tab.data(); float* cc = cs + mwp; float* ra = cc + mwp; float* rb = ra + mhp;
+    const bool plane = kind == ISX_WARP_PLANE;
+    for (int i = 0; i < mw; ++i) {
+        float u = (float)(roi[0] + i);
+        u /= scale;                                    // W:48
+        if (plane) { cs[i] = u - t[0]; cc[i] = 0.f; }         // PlaneProjector::mapBackward: u = u / scale - t[0]
+        else { cs[i] = sinf(u); cc[i] = cosf(u); }     // W:51,53
+    }
+    for (int i = 0; i < mh; ++i) {
+        float v = (float)(roi[1] + i);
+        v /= scale;                                    // W:49
+        if (plane) { ra[i] = v - t[1]; rb[i] = 1 - t[2]; }                     // v = v / scale - t[1]; z_ = 1 - t[2]
+        else if (kind == ISX_WARP_CYLINDRICAL) { ra[i] = v; rb[i] = 0.f; }     // W:52
+        else { ra[i] = sinf(PI_F - v); rb[i] = cosf(PI_F - v); }
+    }
+    // the padding repeats the last column / row: the fused kernel's partial 4-pixel group at the right edge then computes ordinary
+    // pixels in its unused lanes (zeros would make z = 0 there and send the whole group down the generic path, once per row)
+    for (int i = mw; i < mwp; ++i) { cs[i] = cs[mw - 1]; cc[i] = cc[mw - 1]; }
+    for (int i = mh; i < mhp; ++i) { ra[i] = ra[mh - 1]; rb[i] = rb[mh - 1]; }
+}
+
+// ---- part 2: the synchronous detectResultRoi ---------------------------------------------------------------------------------------------
+// detectResultRoi is a pure function of (projection, source size): remembered results are returned without the scan, oldest forgotten first.
+// The spherical answer also reads K and R^T themselves (the pole tests), so its list compares them too.
+struct RoiMemo {
+    struct Entry { Proj proj; int sw, sh; int roi[4]; float mm[4]; float k[9], rinv[9]; };
+    bool with_camera;
+    std::vector<Entry> list;
+    explicit RoiMemo(bool camera) : with_camera(camera) {}
+    const Entry* find(const Proj& p, const float k[9], const float rinv[9], int sw, int sh) const {
+        for (const Entry& e : list)
+            if (e.sw == sw && e.sh == sh && memcmp(&e.proj, &p, sizeof(Proj)) == 0 &&
+                (!with_camera || (memcmp(e.k, k, sizeof(e.k)) == 0 && memcmp(e.rinv, rinv, sizeof(e.rinv)) == 0))) return &e;
+        return nullptr;
+    }
+    void remember(size_t cap, const Proj& p, const float k[9], const float rinv[9], int sw, int sh, const int roi[4], const float mm[4]) {
+        if (list.size() >= cap) list.erase(list.begin());
+        Entry e;
+        memset(&e, 0, sizeof(e));
+        e.proj = p; e.sw = sw; e.sh = sh;
+        std::copy(k, k + 9, e.k); std::copy(rinv, rinv + 9, e.rinv);
+        std::copy(roi, roi + 4, e.roi); std::copy(mm, mm + 4, e.mm);
+        list.push_back(e);
+    }
+};
+struct SyncRoi {
+    hipStream_t stream = nullptr;      // shared_stream(SHARED_ROI): see roi_stream_of
+    DevBuf scan;                       // {keys[4], count, mismatches, cand...}
+    DevBuf scan_blk;                   // the scan's per-block extrema (k_roi_scan -> k_roi_candidates)
+    void* pin = nullptr;               // pinned host landing zone of {keys, count, first candidates}
+    std::vector<int> host_cand;
+    std::vector<float> host_scratch;   // the host border scan's stand-ins (roihost.cpp)
+    // isx_warper_set_roi_cache: a fixed rig asks for the same few ROIs again and again.  Off, the cylindrical list holds the LAST result
+    // only: the reference asks for the same ROI twice in a row - warp(img, K, R) then warp(mask, K, R), W:229,232.  The spherical ROI is a
+    // scan of the source's border on the HOST (0.3 ms for an 8K tile) with no synchronisation to preserve: always remembered, 64 entries
+    // (1024 only with the fixed-rig hint: a miss scans the list).
+    bool cache_on = false;
+    RoiMemo sph{true}, cyl{false};
+};
+
+// ---- part 3: the verification of planned (sync-free) warps -------------------------------------------------------------------------------
+// A planned warp's ROI scan + device-side check run on a side stream: the scan is VALU-bound (atan2f / sqrt / div per source pixel) and
+// overlaps with the memory-bound kernels of the main stream; nothing on the main stream depends on it (isx_warper_plan_status joins both).
+struct Pending { Proj proj; int sw, sh; int planned[4]; float k[9], rinv[9]; };
+struct PlanVerify {
+    hipStream_t side = nullptr;        // shared_stream(SHARED_VERIFY)
+    hipEvent_t ev_warp = nullptr;      // recorded on the main stream after a planned warp: its scan starts behind it
+    hipEvent_t ev_scan = nullptr;      // recorded on the side stream after the check: isx_warper_join waits on it
+    DevBuf keys;                       // {keys[4], count, mismatches} used on the side stream only
+    std::vector<Pending> pending;
+    // isx_warper_set_deferred_verify: planned warps queue their verification; isx_warper_verify enqueues the queued scans behind the main
+    // stream's position AT THAT CALL (e.g. after the last warp of a step, so that they run under the memory-bound pyramid kernels instead
+    // of under the next tile's warp)
+    bool deferred = false;
+    int host_mismatches = 0;           // plane handles: the four-corner ROI is compared on the host when the verification is queued
+};
+
+// ---- part 4: the tile batch --------------------------------------------------------------------------------------------------------------
+// isx_warper_begin_batch .. isx_warper_end_batch: the fused tile warps in between are collected and leave as ONE launch (k_warp_tile_batch)
+struct BatchItem { int kind; bool out16; WarpTileGeom g; unsigned gx, gy; double bytes; };
+struct TileBatch { bool open = false; std::vector<BatchItem> items; };
+
 }  // namespace
 
 struct isx_warper {
     int kind = 0, device = 0;
     float scale = 1.f;
     hipStream_t stream = nullptr;
-    // device scratch
-    DevBuf tabs, scan;       // tables; {keys[4], count, mismatches, cand...}
-    // planned (sync-free) warps run their ROI scan + device-side check on a side stream: the scan is
-    // VALU-bound (atan2f / sqrt / div per source pixel) and overlaps with the memory-bound kernels of the
-    // main stream; nothing on the main stream depends on it (isx_warper_plan_status joins both).
-    hipStream_t side = nullptr;
-    hipEvent_t ev_warp = nullptr;   // recorded on the main stream after a planned warp: its scan starts behind it
-    hipEvent_t ev_scan = nullptr;   // recorded on the side stream after the check: isx_warper_join waits on it
-    DevBuf scan_side;        // {keys[4], count, mismatches} used on the side stream only
-    DevBuf scan_blk;         // the synchronous scan's per-block extrema (k_roi_scan -> k_roi_candidates)
-    void* pin = nullptr;     // pinned host landing zone of detectResultRoi's {keys, count, first candidates}
-    float t[3] = {0.f, 0.f, 0.f};   // isx_warper_set_translation: PlaneWarper's T (sticky; non-zero on a plane handle only)
-    int plan_mismatches_host = 0;   // planned plane warps: their four-corner ROI is compared on the host when the verification is queued
-    double gain = 1.0;       // isx_warper_set_gain: folded into the fused tile warp's store (1.0 = off)
+    float t[3] = {0.f, 0.f, 0.f};       // isx_warper_set_translation: PlaneWarper's T (sticky; non-zero on a plane handle only)
+    double gain = 1.0;                  // isx_warper_set_gain: folded into the fused tile warp's store (1.0 = off)
     unsigned char gain_lut[256] = {};   // its 256-entry table (handed to the kernel in its arguments)
-    // isx_warper_set_deferred_verify: planned warps queue their verification; isx_warper_verify enqueues the
-    // queued scans behind the main stream's position AT THAT CALL (e.g. after the last warp of a step, so
-    // that they run under the memory-bound pyramid kernels instead of under the next tile's warp)
-    struct Pending { Proj proj; int sw, sh; int planned[4]; float k[9], rinv[9]; };
-    std::vector<Pending> pending;
-    bool defer_verify = false;
-    MatStage st_src, st_mask, st_dst, st_dmask, st_x, st_y;
-    // cache of mapBackward tables, one entry per (kind, scale, translation, roi): a rig's tiles alternate between a few ROIs
-    // (round 5: 1024 entries, each with its own host copy.  With 16 entries and one shared host buffer a panorama of more than 16 tiles through
-    // one handle missed on EVERY warp - two stream synchronisations and 7 000 sinf / cosf per call: the 64-tile step was host-bound at 68 us per
-    // 27 us warp kernel, 9.8 ms against a kernel sum of 7.3, profiles/round5_many_tiles_trace.txt)
-    struct TabEntry { int kind; float scale; float t[3]; int roi[4]; const float* dev; size_t chunk; };
-    std::vector<TabEntry> tab_cache;
-    std::unordered_multimap<unsigned long long, size_t> tab_index;   // hash of (kind, scale, translation, roi) -> entry (no linear scan of 1024 entries per warp)
-    // the tables live in a few 4 MiB chunks, bump-allocated (a DevBuf per entry was a megabyte per entry - reserve() rounds up - i.e. up to a
-    // gigabyte per warper at the old cap of 1024 entries): at most TAB_BYTES of them; a full arena is drained and started over
-    std::vector<std::unique_ptr<DevBuf>> tab_chunks;
-    size_t tab_chunk = 0, tab_used = 0;    // the chunk being filled and the bytes used in it
-    long long tab_resets = 0;
-    // a chunk that a warp enqueued on a CAPTURING stream read from (per tab_chunks entry): a graph holds raw pointers into it, so it is never
-    // rewritten - the start-over moves it to tab_kept (freed at destroy) and the arena goes on in fresh chunks
-    std::vector<char> tab_pinned;
-    std::vector<std::unique_ptr<DevBuf>> tab_kept;
-    // the streams this handle left (isx_warper_set_stream) since the arena last started over, each with an event recorded at its last position
-    // there: the start-over waits for them too, not only for the current stream
-    std::vector<std::pair<hipStream_t, hipEvent_t>> tab_fences;
-    std::vector<float> tab_host;           // staging of the one table being built (its upload is waited for)
-    std::vector<int> host_cand;
-    std::vector<float> host_scratch;      // the host border scan's stand-ins (roihost.cpp)
-    // isx_warper_begin_batch .. isx_warper_end_batch: the fused tile warps in between are collected and leave as ONE launch (k_warp_tile_batch)
-    struct BatchItem { int variant; WarpTileGeom g; unsigned gx, gy; double bytes; };
-    bool batching = false;
-    std::vector<BatchItem> batch;
-    float k[9], rinv[9];
+    int col0 = 0, col1 = 0;             // isx_warper_set_dst_columns: the warped tile's columns the next fused warps produce (0, 0 = all)
+    float k[9], rinv[9];                // the camera of the call being served (set_camera)
     Proj proj;
-    hipStream_t roi_stream = nullptr;  // the synchronous ROI scans' stream (roi_stream_of)
-    int col0 = 0, col1 = 0;            // isx_warper_set_dst_columns: the warped tile's columns the next fused warps produce (0, 0 = all)
-    // isx_warper_set_roi_cache: detectResultRoi is a pure function of (projection, source size); a fixed rig asks for the
-    // same few again and again.  Opt-in: remembered results are returned without the scan and its host round trip.
-    struct RoiEntry { Proj proj; int sw, sh; int roi[4]; float mm[4]; float k[9], rinv[9]; };
-    std::vector<RoiEntry> roi_cache;
-    bool roi_cache_on = false;
-    // The spherical ROI is a scan of the source's border on the HOST (0.3 ms for an 8K tile): a pure function with no device work and
-    // no synchronisation to preserve, so its results are always remembered (per projection and source size, 1024 entries).
-    std::vector<RoiEntry> sph_memo;
+    MatStage st_src, st_mask, st_dst, st_dmask, st_x, st_y;
+    TableArena tables;
+    SyncRoi roi;
+    PlanVerify verify;
+    TileBatch batch;
 };
 
 namespace {
@@ -1267,31 +1442,122 @@ namespace {
 constexpr int CAND_CAP = 1 << 16;
 constexpr int CAND_FIRST = 1024;   // candidates that travel with the count in the one copy of detectResultRoi
 
-int set_camera(isx_warper* w, const float K[9], const float R[9]) {
-    ISX_CHECK_ARG(K != nullptr && R != nullptr, ISX_ERR_INVALID, "setCameraParams: K and R must be 3x3 CV_32F (got null)");  // W:94-95
-    for (int i = 0; i < 9; ++i) {
-        ISX_CHECK_ARG(std::isfinite(K[i]) && std::isfinite(R[i]), ISX_ERR_INVALID, "setCameraParams: K / R contain non-finite values");
-        w->k[i] = K[i];                                                     // W:98-101
-    }
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) w->rinv[i * 3 + j] = R[j * 3 + i];   // W:103
+// setCameraParams: k = K, rinv = R^T, r_kinv = R K^-1, k_rinv = K R^T
+void make_proj(int kind, float scale, const float K[9], const float R[9], Proj* p, float k[9], float rinv[9]) {
+    for (int i = 0; i < 9; ++i) k[i] = K[i];                                                  // W:98-101
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) rinv[i * 3 + j] = R[j * 3 + i];   // W:103
     float kinv[9];
     mat3_inv(K, kinv);
-    mat3_mul(R, kinv, w->proj.r_kinv);                                      // W:108
-    mat3_mul(K, w->rinv, w->proj.k_rinv);                                   // W:113
-    w->proj.scale = w->scale;
-    w->proj.kind = w->kind;
+    mat3_mul(R, kinv, p->r_kinv);                                                             // W:108
+    mat3_mul(K, rinv, p->k_rinv);                                                             // W:113
+    p->scale = scale;
+    p->kind = kind;
+}
+
+int set_camera(isx_warper* w, const float K[9], const float R[9]) {
+    ISX_CHECK_ARG(K != nullptr && R != nullptr, ISX_ERR_INVALID, "setCameraParams: K and R must be 3x3 CV_32F (got null)");  // W:94-95
+    for (int i = 0; i < 9; ++i)
+        ISX_CHECK_ARG(std::isfinite(K[i]) && std::isfinite(R[i]), ISX_ERR_INVALID, "setCameraParams: K / R contain non-finite values");
+    make_proj(w->kind, w->scale, K, R, &w->proj, w->k, w->rinv);
     return ISX_OK;
 }
 
-// The collected tile warps of a batch (isx_warper_begin_batch): runs of the same kernel variant leave as one launch of up to WARP_BATCH_MAX tiles
-// (blockIdx.z = tile, the grid the largest tile's); a run of one takes the ordinary kernel.
-template <int KD, bool O16>
-int launch_warp_batch(hipStream_t st, const isx_warper::BatchItem* it, int n) {
-    if (n == 1) {
-        WarpTileArgs a{it[0].g.p, it[0].g.t, it[0].g.img, it[0].g.d, {}};
-        ISX_LAUNCH("warp_tile", it[0].bytes, st, (k_warp_tile<KD, O16, true>), dim3(it[0].gx, it[0].gy), dim3(64 * WARP_WAVES), 0, a);
-        return ISX_OK;
-    }
+// ---- from a run-time switch to a template argument: f is called with a std::integral_constant -------------------------------------------
+template <class F>
+int with_kind(int kind, F&& f) {
+    if (kind == ISX_WARP_CYLINDRICAL) return f(std::integral_constant<int, ISX_WARP_CYLINDRICAL>{});
+    if (kind == ISX_WARP_SPHERICAL) return f(std::integral_constant<int, ISX_WARP_SPHERICAL>{});
+    return f(std::integral_constant<int, ISX_WARP_PLANE>{});
+}
+template <class F>
+int with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+// one of the four pixel types of warp() and remap() (the caller has checked it): f(a value of the channel type, the channel count)
+template <class F>
+int with_pixel(int type, F&& f) {
+    if (type == ISX_8UC1) return f((unsigned char)0, std::integral_constant<int, 1>{});
+    if (type == ISX_8UC3) return f((unsigned char)0, std::integral_constant<int, 3>{});
+    if (type == ISX_32FC1) return f(0.f, std::integral_constant<int, 1>{});
+    return f(0.f, std::integral_constant<int, 3>{});
+}
+#define ISX_CT(x) decltype(x)::value
+
+// ---- one launcher per kernel family.  Launch names are the kernels' names without the k_ (they can be found in a rocprofv3 kernel trace
+// as they are) ------------------------------------------------------------------------------------------------------------------------------
+// the hot kernel: image and mask of a tile whose source mask is all 255 (W:213-214), with or without the gain's table in its arguments
+int launch_warp_tile(hipStream_t st, int kind, bool out16, bool gained, dim3 grid, double bytes, const WarpTileArgs& a) {
+    return with_kind(kind, [&](auto kd) {
+        return with_bool(out16, [&](auto o16) {
+            if (gained) ISX_LAUNCH("warp_tile", bytes, st, (k_warp_tile<ISX_CT(kd), ISX_CT(o16), true, true, true>), grid, dim3(64 * WARP_WAVES), 0, a);
+            else ISX_LAUNCH("warp_tile", bytes, st, (k_warp_tile<ISX_CT(kd), ISX_CT(o16), true>), grid, dim3(64 * WARP_WAVES), 0, a);
+            return (int)ISX_OK;
+        });
+    });
+}
+// a tile with the caller's source mask.  vec: dword stores, for 4-byte aligned destination rows.  (The kernel's last three arguments, a
+// device-side plan check, are not used by the host: null.)
+int launch_warp_img_mask(hipStream_t st, int kind, bool out16, bool vec, double bytes, const Proj& p, const MapTabs& t, const SrcView& img, const SrcView& msk,
+                         const isx_mat& dd, const isx_mat& dm, int dw, int dh) {
+    const dim3 grid(cdiv(dw, 256), cdiv(dh, 4));
+    return with_bool(out16, [&](auto o16) {
+        return with_bool(vec, [&](auto v) {
+            return with_bool(kind == ISX_WARP_PLANE, [&](auto pl) {
+                ISX_LAUNCH("warp_img_mask", bytes, st, (k_warp_img_mask<ISX_CT(o16), ISX_CT(v), ISX_CT(pl)>), grid, dim3(256), 0, p, t, img, msk, msk.data ? 1 : 0,
+                           (unsigned char*)dd.data, dd.step, (unsigned char*)dm.data, dm.step, dw, dh, (const unsigned*)nullptr, make_int4(0, 0, 0, 0), (int*)nullptr);
+                return (int)ISX_OK;
+            });
+        });
+    });
+}
+// The two calls the reference makes per tile (W:229 image LINEAR / REFLECT, W:232 mask NEAREST / CONSTANT): k_warp_tile without its mask output ...
+int launch_warp_tile_img(hipStream_t st, int kind, dim3 grid, double bytes, const WarpTileArgs& a) {
+    return with_kind(kind, [&](auto kd) {
+        ISX_LAUNCH("warp_tile_img", bytes, st, (k_warp_tile<ISX_CT(kd), false, true, false>), grid, dim3(64 * WARP_WAVES), 0, a);
+        return (int)ISX_OK;
+    });
+}
+// ... and k_warp_mask_tile
+int launch_warp_mask_tile(hipStream_t st, int kind, double bytes, const WarpMaskArgs& a) {
+    const dim3 grid(cdiv(a.w, 64), cdiv(a.h, 16));
+    return with_kind(kind, [&](auto kd) {
+        ISX_LAUNCH("warp_tile_mask", bytes, st, (k_warp_mask_tile<ISX_CT(kd), true>), grid, dim3(256), 0, a);
+        return (int)ISX_OK;
+    });
+}
+// every other combination of type, interpolation and border
+int launch_warp_any(hipStream_t st, int kind, int type, double bytes, const Proj& p, const MapTabs& t, const SrcView& src, unsigned char* dp, size_t ds, int dw, int dh,
+                    int interp, int border) {
+    if (type != ISX_8UC1 && type != ISX_8UC3 && type != ISX_32FC1 && type != ISX_32FC3)
+        return fail(ISX_ERR_TYPE, "warp: src type %s is not supported (CV_8UC1/3, CV_32FC1/3)", type_name(type));
+    const dim3 grid(cdiv(dw, 64), cdiv(dh, 4));
+    return with_pixel(type, [&](auto pixel, auto cn) {
+        return with_bool(kind == ISX_WARP_PLANE, [&](auto pl) {
+            ISX_LAUNCH("warp", bytes, st, (k_warp<decltype(pixel), ISX_CT(cn), ISX_CT(pl)>), grid, dim3(256), 0, p, t, src, dp, ds, dw, dh, interp, border);
+            return (int)ISX_OK;
+        });
+    });
+}
+int launch_build_maps(hipStream_t st, int kind, const Proj& p, const MapTabs& t, const isx_mat& x, const isx_mat& y, int dw, int dh) {
+    const dim3 grid(cdiv(dw, 64), cdiv(dh, 4));
+    return with_bool(kind == ISX_WARP_PLANE, [&](auto pl) {
+        ISX_LAUNCH("build_maps", (double)dw * dh * 8.0, st, k_build_maps<ISX_CT(pl)>, grid, dim3(256), 0, p, t, (float*)x.data, x.step, (float*)y.data, y.step, dw, dh);
+        return (int)ISX_OK;
+    });
+}
+// (the type is one of the four: isx_remap has checked it)
+int launch_remap(hipStream_t st, int type, double bytes, const SrcView& src, const isx_mat& x, const isx_mat& y, const isx_mat& d, int interp, int border) {
+    const int dw = d.cols, dh = d.rows;
+    const dim3 grid(cdiv(dw, 64), cdiv(dh, 4));
+    return with_pixel(type, [&](auto pixel, auto cn) {
+        ISX_LAUNCH("remap", bytes, st, (k_remap<decltype(pixel), ISX_CT(cn)>), grid, dim3(256), 0, src, (const unsigned char*)x.data, x.step, (const unsigned char*)y.data,
+                   y.step, (unsigned char*)d.data, d.step, dw, dh, interp, border);
+        return (int)ISX_OK;
+    });
+}
+
+// The collected tile warps of a batch: runs of one kind and output type leave as one launch of up to WARP_BATCH_MAX tiles (blockIdx.z =
+// tile, the grid the largest tile's); a run of one takes the ordinary kernel.
+int launch_batch_run(hipStream_t st, const BatchItem* it, int n) {
+    if (n == 1) return launch_warp_tile(st, it->kind, it->out16, false, dim3(it->gx, it->gy), it->bytes, WarpTileArgs{it->g.p, it->g.t, it->g.img, it->g.d, {}});
     WarpTileBatch b;
     memset(&b, 0, sizeof(b));
     unsigned gx = 0, gy = 0;
@@ -1301,158 +1567,174 @@ int launch_warp_batch(hipStream_t st, const isx_warper::BatchItem* it, int n) {
         b.a[i].d.xg = 0;          // (the XCD-run order is a function of the launch's own grid: off in a shared one)
         gx = std::max(gx, it[i].gx); gy = std::max(gy, it[i].gy); bytes += it[i].bytes;
     }
-    ISX_LAUNCH("warp_tile", bytes, st, (k_warp_tile_batch<KD, O16, true>), dim3(gx, gy, (unsigned)n), dim3(64 * WARP_WAVES), 0, b);
-    return ISX_OK;
+    return with_kind(it->kind, [&](auto kd) {
+        return with_bool(it->out16, [&](auto o16) {
+            ISX_LAUNCH("warp_tile", bytes, st, (k_warp_tile_batch<ISX_CT(kd), ISX_CT(o16), true>), dim3(gx, gy, (unsigned)n), dim3(64 * WARP_WAVES), 0, b);
+            return (int)ISX_OK;
+        });
+    });
 }
 int flush_warp_batch(isx_warper* w) {
-    if (w->batch.empty()) return ISX_OK;
-    std::vector<isx_warper::BatchItem> items;
-    items.swap(w->batch);
+    if (w->batch.items.empty()) return ISX_OK;
+    std::vector<BatchItem> items;
+    items.swap(w->batch.items);
     for (size_t i = 0; i < items.size();) {
         size_t j = i + 1;
-        while (j < items.size() && j - i < (size_t)WARP_BATCH_MAX && items[j].variant == items[i].variant) ++j;
-        const isx_warper::BatchItem* it = &items[i];
-        const int n = (int)(j - i), v = items[i].variant;
-        int rc = ISX_OK;
-        switch (v) {
-            case 0: rc = launch_warp_batch<ISX_WARP_CYLINDRICAL, false>(w->stream, it, n); break;
-            case 1: rc = launch_warp_batch<ISX_WARP_CYLINDRICAL, true>(w->stream, it, n); break;
-            case 2: rc = launch_warp_batch<ISX_WARP_SPHERICAL, false>(w->stream, it, n); break;
-            case 3: rc = launch_warp_batch<ISX_WARP_SPHERICAL, true>(w->stream, it, n); break;
-            case 4: rc = launch_warp_batch<ISX_WARP_PLANE, false>(w->stream, it, n); break;
-            default: rc = launch_warp_batch<ISX_WARP_PLANE, true>(w->stream, it, n); break;
-        }
-        if (rc != ISX_OK) return rc;
+        while (j < items.size() && j - i < (size_t)WARP_BATCH_MAX && items[j].kind == items[i].kind && items[j].out16 == items[i].out16) ++j;
+        ISX_TRY(launch_batch_run(w->stream, &items[i], (int)(j - i)));
         i = j;
     }
     return ISX_OK;
 }
 
-// Enqueue the queued verification scans of planned warps on the side stream, behind the main stream's
-// current position.  The scan is VALU-bound like the warp kernel: it should run under memory-bound work.
-int flush_verify(isx_warper* w, hipEvent_t after = nullptr) {
-    ISX_TRY(flush_warp_batch(w));      // (the scans start behind the warps they verify)
-    if (w->pending.empty()) return ISX_OK;
-    hipStream_t st = w->stream;
-    if (!w->side) {
-        // one verification stream per DEVICE, shared by every warper on it (never destroyed): a batch of pairs would otherwise
-        // bring one stream per warper and run out of hardware queues (16 pairs: 44 instead of 51 Gpix/s)
-        static std::mutex mu;
-        static hipStream_t shared[64] = {};
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            const int d = w->device >= 0 && w->device < 64 ? w->device : 0;
-            if (!shared[d]) ISX_HIP(hipStreamCreateWithFlags(&shared[d], hipStreamNonBlocking));
-            w->side = shared[d];
-        }
-        ISX_HIP(hipEventCreateWithFlags(&w->ev_warp, hipEventDisableTiming));
-        ISX_HIP(hipEventCreateWithFlags(&w->ev_scan, hipEventDisableTiming));
-    }
-    // The scans read the projection and the source size, never an image: nothing they need comes from the main stream.  The event only
-    // PLACES them (full scans are VALU-bound and should start under memory-bound work).  A border scan is one workgroup: it starts right
-    // away, with no event on the main stream at all - unless that stream is being captured, where the wait is what forks the side
-    // stream into the graph.
-    bool cheap = true;
-    for (const isx_warper::Pending& pd : w->pending)
-        cheap = cheap && (pd.proj.kind == ISX_WARP_SPHERICAL || cyl_extrema_on_border(pd.proj, pd.k, pd.rinv, pd.sw, pd.sh));
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (cheap) ISX_HIP(hipStreamIsCapturing(st, &cs));
-    if (cheap && cs == hipStreamCaptureStatusNone) {
-        // nothing to wait for
-    } else if (after) ISX_HIP(hipStreamWaitEvent(w->side, after, 0));
-    else {
-        ISX_HIP(hipEventRecord(w->ev_warp, st));
-        ISX_HIP(hipStreamWaitEvent(w->side, w->ev_warp, 0));
-    }
-    if (!w->scan_side.p) {
-        ISX_TRY(w->scan_side.reserve(64));
-        ISX_HIP(hipMemsetAsync(w->scan_side.p, 0, 64, w->side));
-        ISX_HIP(hipMemsetAsync(w->scan_side.p, 0xff, 2 * sizeof(unsigned), w->side));
-    }
-    unsigned* sk = (unsigned*)w->scan_side.p;
-    for (const isx_warper::Pending& pd : w->pending) {
-        const bool sph = pd.proj.kind == ISX_WARP_SPHERICAL;
-        bool north = false, south = false;
-        if (sph) {
-            ISX_LAUNCH("roi_border_sph", 0.0, w->side, k_roi_border_sph, dim3(1), dim3(1024), 0, pd.proj, pd.sw, pd.sh, sk, (int*)nullptr, 0, (int*)nullptr);
-            sph_poles(pd.k, pd.rinv, pd.sw, pd.sh, &north, &south);
-        } else if (cyl_extrema_on_border(pd.proj, pd.k, pd.rinv, pd.sw, pd.sh)) {
-            // The verification of a PLANNED cylindrical ROI (a guard against a stale plan; the ROI itself came from the reference's full
-            // scan, W:64-88): with the whole image in front of the camera (z_ > 0 at the four corners, z_ is linear in x, y) u = atan2(x_, z_)
-            // is monotone along every line of the image, and v = y_ / |(x_, z_)| is the tangent of the latitude, which has no local
-            // extremum on a sphere away from its poles - neither of which lies inside the image.  Both extrema are then attained on the
-            // image's border: 2 (W + H) points in one workgroup instead of a 14 us scan of every source pixel beside the blend's kernels.
-            ISX_LAUNCH("roi_border", 0.0, w->side, k_roi_border_sph, dim3(1), dim3(1024), 0, pd.proj, pd.sw, pd.sh, sk, (int*)nullptr, 0, (int*)nullptr);
-        } else {
-            dim3 sgrid(cdiv(pd.sw, 256), cdiv(pd.sh, ROI_ROWS));   // ~8 K waves at 4K: one full-occupancy round
-            ISX_LAUNCH("roi_scan", 0.0, w->side, k_roi_scan, sgrid, dim3(256), 0, pd.proj, pd.sw, pd.sh, sk, ROI_ROWS, (float4*)nullptr);
-        }
-        RoiBounds rb;
-        for (int k = 0; k < 4; ++k) {
-            double lo, hi;
-            trunc_interval(pd.planned[k], lo, hi);
-            const bool is_u = (k == 0 || k == 2);
-            double plo = is_u ? proxy_d_of_u(lo, pd.proj.scale) : (sph ? proxy_w_of_v(lo, pd.proj.scale) : proxy_q_of_v(lo, pd.proj.scale));
-            double phi = is_u ? proxy_d_of_u(hi, pd.proj.scale) : (sph ? proxy_w_of_v(hi, pd.proj.scale) : proxy_q_of_v(hi, pd.proj.scale));
-            if (sph) {
-                // a pole inside the image replaces the border's extremum by its own value (min / max with 0 or pi scale): where the planned
-                // bound IS the pole's, the border's extremum only has to lie on the border's side of it
-                const double pv = 3.14159265358979323846 * pd.proj.scale;
-                const double pole[2][4] = {{0.0, pv, 0.0, pv}, {0.0, 0.0, 0.0, 0.0}};
-                for (int q = 0; q < 2; ++q)
-                    if ((q == 0 ? north : south) && f2i_host((float)pole[q][k]) == pd.planned[k]) {
-                        if (k < 2) phi = is_u ? 2.0 : 1.0; else plo = is_u ? -2.0 : -1.0;
-                    }
-            }
-            // margin: the stand-ins carry a few ulp of error; an extremum this close to an integer boundary is
-            // not flagged (the check is a guard against a stale plan, not a proof)
-            const double m = 4e-6 * std::max(1.0, std::max(std::fabs(plo), std::fabs(phi)));
-            rb.lo[k] = (float)(plo - m); rb.hi[k] = (float)(phi + m);
-        }
-        // Two rules the host knows exactly, with no scan, and which the intervals above cannot express:
-        //  - mapForward's u = scale * atan2f(..) never leaves +-scale * pi_f, so a planned u bound beyond +-(int)(scale * pi_f) is unattainable.
-        //    proxy_d_of_u clamps at +-pi: both ends of such a bound's interval became -+2, and a tile that straddles the back seam passed.
-        //  - a pole inside the image dictates one bound (north: br.v = (int)(float)(pi scale), south: tl.v = 0: roi_from_candidates).  A plan
-        //    with another value there was compared with the BORDER's extremum, which can lie inside the wrong interval.
-        // Such a plan gets an empty interval: the check flags it on the device, once per verification and once per replay of a captured one,
-        // as it does every other stale plan.
-        const int u_lim = f2i_host(pd.proj.scale * PI_F);
-        bool stale = pd.planned[0] > u_lim || pd.planned[0] < -u_lim || pd.planned[2] > u_lim || pd.planned[2] < -u_lim;
-        if (sph && north && pd.planned[3] != f2i_host((float)(3.1415926535897932384626433832795 * pd.proj.scale))) stale = true;
-        if (sph && south && pd.planned[1] != 0) stale = true;
-        //  - a pole inside the image also enters the other bounds (tl = min(tl, pole), br = max(br, pole), the pole at u = 0): a planned tl
-        //    above the pole's value or a planned br below it cannot come out, whatever the border's extremum is (a border that does not wind
-        //    around the pole has its own u extremum on one side of 0, and it lay inside such a bound's interval)
-        if (sph && (north || south)) {
-            const int pvi = f2i_host((float)(3.1415926535897932384626433832795 * pd.proj.scale));
-            if (pd.planned[0] > 0 || pd.planned[2] < 0 || pd.planned[3] < 0) stale = true;
-            if (north && pd.planned[1] > pvi) stale = true;
-        }
-        if (stale)
-            for (int k = 0; k < 4; ++k) { rb.lo[k] = std::numeric_limits<float>::infinity(); rb.hi[k] = -std::numeric_limits<float>::infinity(); }
-        ISX_LAUNCH("roi_check", 0.0, w->side, k_roi_check_rearm, dim3(1), dim3(1), 0, sk, rb, (int*)(sk + 5));
-    }
-    ISX_HIP(hipEventRecord(w->ev_scan, w->side));
-    w->pending.clear();
+// ---- the verification of planned warps (PlanVerify) ---------------------------------------------------------------------------------------
+// is the scan that verifies a planned ROI the one-workgroup border scan?  Spherical: always (detectResultRoiByBorder).  Cylindrical: where
+// both extrema provably lie on the image's border (cyl_extrema_on_border).  A plane handle scans nothing.
+bool verify_is_light(const Proj& p, const float k[9], const float rinv[9], int sw, int sh) {
+    return p.kind != ISX_WARP_CYLINDRICAL || cyl_extrema_on_border(p, k, rinv, sw, sh);
+}
+
+int ensure_verify_stream(isx_warper* w) {
+    PlanVerify& v = w->verify;
+    if (v.side) return ISX_OK;
+    ISX_TRY(shared_stream(w->device, SHARED_VERIFY, &v.side));
+    ISX_HIP(hipEventCreateWithFlags(&v.ev_warp, hipEventDisableTiming));
+    ISX_HIP(hipEventCreateWithFlags(&v.ev_scan, hipEventDisableTiming));
     return ISX_OK;
 }
 
-// detectResultRoi.  Cylindrical: full scan on the GPU (W:72-81) + host refinement of u.
-// Spherical: OpenCV's detectResultRoiByBorder + pole tests — O(W+H) points, evaluated on the host.
-// The stream the synchronous ROI scans run on: one per device, shared by every warper on it (see flush_verify on why not one each).
-// detectResultRoi is a function of the projection and the source SIZE - it reads no image - so it need not queue behind whatever
-// the handle's stream still holds (the previous blend, typically): the host gets its corner after the scan alone, W:160 is kept,
-// and the strict call sequence stops being bound by one full GPU drain per warp.
-int roi_stream_of(isx_warper* w, hipStream_t* out) {
-    if (!w->roi_stream) {
-        static std::mutex mu;
-        static hipStream_t shared[64] = {};
-        std::lock_guard<std::mutex> lk(mu);
-        const int d = w->device >= 0 && w->device < 64 ? w->device : 0;
-        if (!shared[d]) ISX_HIP(hipStreamCreateWithFlags(&shared[d], hipStreamNonBlocking));      // (a high-priority stream changes nothing here: a resident wave is not preempted; measured 40 us per call beside a saturating kernel either way)
-        w->roi_stream = shared[d];
+// The scans read the projection and the source size, never an image: nothing they need comes from the main stream.  An event only PLACES
+// them (full scans are VALU-bound and should start under memory-bound work): `after`, or the main stream's current position.  A border scan
+// is one workgroup: it starts right away, with no event on the main stream at all - unless that stream is being captured, where the wait is
+// what forks the side stream into the graph.
+int place_scans(isx_warper* w, hipEvent_t after) {
+    PlanVerify& v = w->verify;
+    bool cheap = true;
+    for (const Pending& pd : v.pending) cheap = cheap && verify_is_light(pd.proj, pd.k, pd.rinv, pd.sw, pd.sh);
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (cheap) ISX_HIP(hipStreamIsCapturing(w->stream, &cs));
+    if (cheap && cs == hipStreamCaptureStatusNone) return ISX_OK;      // nothing to wait for
+    if (after) {
+        ISX_HIP(hipStreamWaitEvent(v.side, after, 0));
+        return ISX_OK;
     }
-    *out = w->roi_stream;
+    ISX_HIP(hipEventRecord(v.ev_warp, w->stream));
+    ISX_HIP(hipStreamWaitEvent(v.side, v.ev_warp, 0));
+    return ISX_OK;
+}
+
+// the scan of one pending verification: its extrema land in `keys`
+int launch_scan(hipStream_t side, unsigned* keys, const Pending& pd) {
+    // The verification of a PLANNED cylindrical ROI (a guard against a stale plan; the ROI itself came from the reference's full
+    // scan, W:64-88): with the whole image in front of the camera (z_ > 0 at the four corners, z_ is linear in x, y) u = atan2(x_, z_)
+    // is monotone along every line of the image, and v = y_ / |(x_, z_)| is the tangent of the latitude, which has no local
+    // extremum on a sphere away from its poles - neither of which lies inside the image.  Both extrema are then attained on the
+    // image's border, as the spherical warper's are by definition: 2 (W + H) points in one workgroup instead of a 14 us scan of every
+    // source pixel beside the blend's kernels.
+    const bool sph = pd.proj.kind == ISX_WARP_SPHERICAL;
+    if (sph || cyl_extrema_on_border(pd.proj, pd.k, pd.rinv, pd.sw, pd.sh)) {
+        ISX_LAUNCH(sph ? "roi_border_sph" : "roi_border", 0.0, side, k_roi_border_sph, dim3(1), dim3(1024), 0, pd.proj, pd.sw, pd.sh, keys, (int*)nullptr, 0, (int*)nullptr);
+    } else {
+        const dim3 sgrid(cdiv(pd.sw, 256), cdiv(pd.sh, ROI_ROWS));   // ~8 K waves at 4K: one full-occupancy round
+        ISX_LAUNCH("roi_scan", 0.0, side, k_roi_scan, sgrid, dim3(256), 0, pd.proj, pd.sw, pd.sh, keys, ROI_ROWS, (float4*)nullptr);
+    }
+    return ISX_OK;
+}
+
+// The stand-in intervals the scanned extrema of a planned ROI must lie in (k_roi_check_rearm).  north / south: a pole of the sphere inside
+// the image (sph_poles; false for a cylindrical camera).  Pure host arithmetic: tests/helpers/plan_verify_np.py is its model.
+RoiBounds plan_bounds(const Pending& pd, bool north, bool south) {
+    const bool sph = pd.proj.kind == ISX_WARP_SPHERICAL;
+    const float scale = pd.proj.scale;
+    const double pole_v = pi_scale(scale);             // the north pole's v; the south pole's is 0, and both poles' u
+    const int pole_vi = f2i_host((float)pole_v);       // ... as detectResultRoi truncates it
+    RoiBounds rb;
+    for (int k = 0; k < 4; ++k) {
+        double lo, hi;
+        trunc_interval(pd.planned[k], lo, hi);
+        const bool is_u = (k == 0 || k == 2);
+        double plo = is_u ? proxy_d_of_u(lo, scale) : (sph ? proxy_w_of_v(lo, scale) : proxy_q_of_v(lo, scale));
+        double phi = is_u ? proxy_d_of_u(hi, scale) : (sph ? proxy_w_of_v(hi, scale) : proxy_q_of_v(hi, scale));
+        // a pole inside the image replaces the border's extremum by its own value (min / max with 0 or pi scale): where the planned
+        // bound IS the pole's, the border's extremum only has to lie on the border's side of it
+        const double pole[2][4] = {{0.0, pole_v, 0.0, pole_v}, {0.0, 0.0, 0.0, 0.0}};
+        for (int q = 0; q < 2; ++q)
+            if (sph && (q == 0 ? north : south) && f2i_host((float)pole[q][k]) == pd.planned[k]) {
+                if (k < 2) phi = is_u ? 2.0 : 1.0; else plo = is_u ? -2.0 : -1.0;
+            }
+        // margin: the stand-ins carry a few ulp of error; an extremum this close to an integer boundary is
+        // not flagged (the check is a guard against a stale plan, not a proof)
+        const double m = 4e-6 * std::max(1.0, std::max(std::fabs(plo), std::fabs(phi)));
+        rb.lo[k] = (float)(plo - m); rb.hi[k] = (float)(phi + m);
+    }
+    // Rules the host knows exactly, with no scan, and which the intervals above cannot express:
+    //  - mapForward's u = scale * atan2f(..) never leaves +-scale * pi_f, so a planned u bound beyond +-(int)(scale * pi_f) is unattainable.
+    //    proxy_d_of_u clamps at +-pi: both ends of such a bound's interval became -+2, and a tile that straddles the back seam passed.
+    //  - a pole inside the image dictates one bound (north: br.v = (int)(float)(pi scale), south: tl.v = 0: roi_from_candidates).  A plan
+    //    with another value there was compared with the BORDER's extremum, which can lie inside the wrong interval.
+    //  - a pole inside the image also enters the other bounds (tl = min(tl, pole), br = max(br, pole), the pole at u = 0): a planned tl
+    //    above the pole's value or a planned br below it cannot come out, whatever the border's extremum is (a border that does not wind
+    //    around the pole has its own u extremum on one side of 0, and it lay inside such a bound's interval).
+    // Such a plan gets an empty interval: the check flags it on the device, once per verification and once per replay of a captured one,
+    // as it does every other stale plan.
+    const int u_lim = f2i_host(scale * PI_F);
+    bool stale = pd.planned[0] > u_lim || pd.planned[0] < -u_lim || pd.planned[2] > u_lim || pd.planned[2] < -u_lim;
+    if (sph && north && pd.planned[3] != pole_vi) stale = true;
+    if (sph && south && pd.planned[1] != 0) stale = true;
+    if (sph && (north || south)) {
+        if (pd.planned[0] > 0 || pd.planned[2] < 0 || pd.planned[3] < 0) stale = true;
+        if (north && pd.planned[1] > pole_vi) stale = true;
+    }
+    if (stale)
+        for (int k = 0; k < 4; ++k) { rb.lo[k] = std::numeric_limits<float>::infinity(); rb.hi[k] = -std::numeric_limits<float>::infinity(); }
+    return rb;
+}
+
+// Enqueue the queued verification scans of planned warps on the side stream, behind the main stream's current position (or `after`).
+int flush_verify(isx_warper* w, hipEvent_t after = nullptr) {
+    ISX_TRY(flush_warp_batch(w));      // (the scans start behind the warps they verify)
+    PlanVerify& v = w->verify;
+    if (v.pending.empty()) return ISX_OK;
+    ISX_TRY(ensure_verify_stream(w));
+    ISX_TRY(place_scans(w, after));
+    ISX_TRY(arm_scan_once(v.keys, 64, v.side));
+    unsigned* keys = (unsigned*)v.keys.p;
+    for (const Pending& pd : v.pending) {
+        ISX_TRY(launch_scan(v.side, keys, pd));
+        bool north = false, south = false;
+        if (pd.proj.kind == ISX_WARP_SPHERICAL) sph_poles(pd.k, pd.rinv, pd.sw, pd.sh, &north, &south);
+        const RoiBounds rb = plan_bounds(pd, north, south);
+        ISX_LAUNCH("roi_check", 0.0, v.side, k_roi_check_rearm, dim3(1), dim3(1), 0, keys, rb, (int*)(keys + 5));
+    }
+    ISX_HIP(hipEventRecord(v.ev_scan, v.side));
+    v.pending.clear();
+    return ISX_OK;
+}
+
+// Queue the verification of a planned ROI of the handle's current camera.  A plane handle's ROI is the four-corner rule on the caller's
+// thread: it is compared here, and isx_warper_plan_status reports it with the scans' findings.
+int queue_plan_check(isx_warper* w, int sw, int sh, const int planned[4]) {
+    if (w->kind == ISX_WARP_PLANE) {
+        int r[4];
+        roi_plane_host(w->proj, w->t, sw, sh, r, nullptr);
+        if (!std::equal(r, r + 4, planned)) ++w->verify.host_mismatches;
+        return ISX_OK;
+    }
+    Pending pd;
+    pd.proj = w->proj; pd.sw = sw; pd.sh = sh;
+    std::copy(planned, planned + 4, pd.planned);
+    std::copy(w->k, w->k + 9, pd.k); std::copy(w->rinv, w->rinv + 9, pd.rinv);
+    w->verify.pending.push_back(pd);
+    return ISX_OK;
+}
+
+// ---- detectResultRoi (SyncRoi) -------------------------------------------------------------------------------------------------------------
+// The stream the synchronous ROI scans run on.  detectResultRoi is a function of the projection and the source SIZE - it reads no image -
+// so it need not queue behind whatever the handle's stream still holds (the previous blend, typically): the host gets its corner after the
+// scan alone, W:160 is kept, and the strict call sequence stops being bound by one full GPU drain per warp.
+int roi_stream_of(isx_warper* w, hipStream_t* out) {
+    if (!w->roi.stream) ISX_TRY(shared_stream(w->device, SHARED_ROI, &w->roi.stream));
+    *out = w->roi.stream;
     return ISX_OK;
 }
 
@@ -1471,7 +1753,7 @@ void roi_from_candidates(const Proj& p, const float k[9], const float rinv[9], i
         bool north, south;
         sph_poles(k, rinv, sw, sh, &north, &south);
         if (north) {
-            const float pv = (float)(3.1415926535897932384626433832795 * p.scale);
+            const float pv = (float)pi_scale(p.scale);
             tl_u = (std::min)(tl_u, 0.f); tl_v = (std::min)(tl_v, pv); br_u = (std::max)(br_u, 0.f); br_v = (std::max)(br_v, pv);
         }
         if (south) { tl_u = (std::min)(tl_u, 0.f); tl_v = (std::min)(tl_v, 0.f); br_u = (std::max)(br_u, 0.f); br_v = (std::max)(br_v, 0.f); }
@@ -1497,215 +1779,113 @@ int border_scan_host(const float* r_kinv, bool sph, int sw, int sh, std::vector<
     return ISX_OK;
 }
 
-int detect_roi(isx_warper* w, int sw, int sh, int roi[4], float mm[4], bool sync_free, const int* planned) {
-    if (w->kind == ISX_WARP_PLANE) {
-        // the four-corner rule on the caller's thread.  The verification of a planned warp is the same rule: it is done here, when it is
-        // queued, and isx_warper_plan_status reports it with the scans' findings
-        int r[4];
-        roi_plane_host(w->proj, w->t, sw, sh, r, sync_free ? nullptr : mm);
-        if (sync_free) { if (!std::equal(r, r + 4, planned)) ++w->plan_mismatches_host; }
-        else std::copy(r, r + 4, roi);
-        return ISX_OK;
-    }
-    hipStream_t st = w->stream;
-    if (!sync_free) ISX_TRY(roi_stream_of(w, &st));
-    size_t need = 64 + (size_t)CAND_CAP * 8;
-    if (!w->scan.p) {   // keys armed once here; every consumer re-arms them (k_warp_img_mask / k_roi_rearm)
-        ISX_TRY(w->scan.reserve(need));
-        ISX_HIP(hipMemsetAsync(w->scan.p, 0, 64, st));
-        ISX_HIP(hipMemsetAsync(w->scan.p, 0xff, 2 * sizeof(unsigned), st));
-    }
-    unsigned* keys = (unsigned*)w->scan.p;
-    int* count = (int*)(keys + 4);
-    int* cand = (int*)((char*)w->scan.p + 64);
-    if (w->kind == ISX_WARP_SPHERICAL && !sync_free) {
-        for (const auto& e : w->sph_memo)
-            if (e.sw == sw && e.sh == sh && memcmp(&e.proj, &w->proj, sizeof(Proj)) == 0 && memcmp(e.k, w->k, sizeof(e.k)) == 0 && memcmp(e.rinv, w->rinv, sizeof(e.rinv)) == 0) {
-                std::copy(e.roi, e.roi + 4, roi);
-                if (mm) std::copy(e.mm, e.mm + 4, mm);
-                return ISX_OK;
-            }
-        // detectResultRoiByBorder: the border pixels ranked (border_scan_host), the candidates for the four extrema evaluated with the
-        // host's libm (exactly the values the host-only scan of round 2 took its minima / maxima over), then OpenCV's two pole tests
-        int n = 0;
-        ISX_TRY(border_scan_host(w->proj.r_kinv, w->kind == ISX_WARP_SPHERICAL, sw, sh, w->host_cand, w->host_scratch, 0, &n));
-        float emm[4];
-        roi_from_candidates(w->proj, w->k, w->rinv, sw, sh, w->host_cand.data(), n, roi, emm);
-        if (mm) std::copy(emm, emm + 4, mm);
-        const float tl_u = emm[0], tl_v = emm[1], br_u = emm[2], br_v = emm[3];
-        if (w->sph_memo.size() >= (w->roi_cache_on ? (size_t)1024 : (size_t)64)) w->sph_memo.erase(w->sph_memo.begin());   // (1024 only with the fixed-rig hint: a miss scans the list)
-        isx_warper::RoiEntry e;
-        e.proj = w->proj; e.sw = sw; e.sh = sh;
-        std::copy(w->k, w->k + 9, e.k); std::copy(w->rinv, w->rinv + 9, e.rinv);
-        std::copy(roi, roi + 4, e.roi);
-        e.mm[0] = tl_u; e.mm[1] = tl_v; e.mm[2] = br_u; e.mm[3] = br_v;
-        w->sph_memo.push_back(e);
-        return ISX_OK;
-    }
-    // (without isx_warper_set_roi_cache the list holds the LAST result only: the reference asks for the same ROI twice in a row - warp(img, K, R)
-    // then warp(mask, K, R), W:229,232 - and the second answer is the first one's, a pure function of the same arguments)
-    if (!sync_free)
-        for (const auto& e : w->roi_cache)
-            if (e.sw == sw && e.sh == sh && memcmp(&e.proj, &w->proj, sizeof(Proj)) == 0) {
-                std::copy(e.roi, e.roi + 4, roi);
-                if (mm) std::copy(e.mm, e.mm + 4, mm);
-                return ISX_OK;
-            }
-    if (sync_free) {
-        isx_warper::Pending pd;
-        pd.proj = w->proj; pd.sw = sw; pd.sh = sh;
-        std::copy(planned, planned + 4, pd.planned);
-        std::copy(w->k, w->k + 9, pd.k); std::copy(w->rinv, w->rinv + 9, pd.rinv);
-        w->pending.push_back(pd);
-        if (!w->defer_verify && !w->batching) return flush_verify(w);      // (a collecting batch: its verifications start when it ends)
-        return ISX_OK;
-    }
-    // cylindrical: min keys start at 0xffffffff, max keys and the candidate count at 0 (armed by the
-    // previous consumer); the mismatch counter keys[5] is sticky
-    // Round 3: where both extrema of u and v provably lie on the image's border (cyl_extrema_on_border: the image in front of the camera, no
-    // pole of the cylinder within two pixels of it) the scan is the 2 (W + H) border pixels in one workgroup instead of all W x H: away from
-    // the poles neither u nor v has a stationary point, so a pixel one step inside the border differs from the border's extremum by about a
-    // whole unit (|grad| ~ scale / focal per pixel), four orders of magnitude above the rounding of mapForward - the extrema over the border
-    // ARE the extrema over the image, and the candidates below are evaluated exactly as before.
-    const bool border_only = cyl_extrema_on_border(w->proj, w->k, w->rinv, sw, sh);
-    dim3 grid(cdiv(sw, 256), cdiv(sh, SYNC_ROWS));
-    float4* blk = nullptr;
-    int n = 0;
-    if (border_only) {
-        ISX_TRY(border_scan_host(w->proj.r_kinv, w->kind == ISX_WARP_SPHERICAL, sw, sh, w->host_cand, w->host_scratch, 0, &n));
-    } else {
-    ISX_TRY(w->scan_blk.reserve((size_t)grid.x * grid.y * sizeof(float4)));
-    blk = (float4*)w->scan_blk.p;
-    ISX_LAUNCH("roi_scan", 0.0, st, k_roi_scan, grid, dim3(256), 0, w->proj, sw, sh, (unsigned*)nullptr, SYNC_ROWS, blk);
-    // The scan ranked the pixels by the stand-ins (d, q).  Collect every pixel whose stand-in is within
-    // a tolerance of one of the four extrema and evaluate mapForward on exactly those with the host's
-    // libm: the result is what the reference code computes on this host.  Scan, candidate pass, the copy of
-    // {count, first candidates} into pinned memory and the re-arming of the keys are enqueued back to back:
-    // ONE stream synchronisation per detectResultRoi (the corner must reach the host, W:148-150,160).
-    static_assert(SYNC_ROWS % CAND_ROWS == 0, "a candidate block lies inside one scan block");
-    ISX_LAUNCH("roi_candidates", 0.0, st, k_roi_candidates, dim3(grid.x, cdiv(sh, CAND_ROWS)), dim3(256), 0, w->proj, sw, sh, cand, CAND_CAP, count, CAND_ROWS,
-               (const float4*)blk, SYNC_ROWS, (int)grid.y);
-    if (!w->pin) ISX_HIP(hipHostMalloc(&w->pin, 64 + (size_t)CAND_FIRST * 8, hipHostMallocDefault));
-    ISX_HIP(hipMemcpyAsync(w->pin, w->scan.p, 64 + (size_t)CAND_FIRST * 8, hipMemcpyDeviceToHost, st));
-    ISX_LAUNCH("roi_rearm", 0.0, st, k_roi_rearm, dim3(1), dim3(1), 0, keys);
-    ISX_HIP(hipStreamSynchronize(st));
-    n = ((const int*)w->pin)[4];
-    ISX_CHECK_ARG(n <= CAND_CAP, ISX_ERR_UNSUPPORTED, "detectResultRoi: %d extremum candidates exceed the refinement buffer (%d)", n, CAND_CAP);
-    ISX_CHECK_ARG(n > 0, ISX_ERR_INVALID, "detectResultRoi: mapForward is not finite anywhere on the %d x %d source (bad K / R / scale?)", sw, sh);
-    w->host_cand.resize((size_t)n * 2);
-    std::memcpy(w->host_cand.data(), (const char*)w->pin + 64, (size_t)std::min(n, CAND_FIRST) * 8);
-    if (n > CAND_FIRST)   // rare: more candidates than the first copy carried
-        ISX_HIP(hipMemcpy(w->host_cand.data() + 2 * (size_t)CAND_FIRST, cand + 2 * (size_t)CAND_FIRST, (size_t)(n - CAND_FIRST) * 8, hipMemcpyDeviceToHost));
-    }
+// the answer to the caller: roi always, the float extrema where asked for
+void roi_answer(const int from_roi[4], const float from_mm[4], int roi[4], float mm[4]) {
+    std::copy(from_roi, from_roi + 4, roi);
+    if (mm) std::copy(from_mm, from_mm + 4, mm);
+}
+
+// PlaneWarper: the four-corner rule on the caller's thread, nothing launched
+int roi_plane(isx_warper* w, int sw, int sh, int roi[4], float mm[4]) { roi_plane_host(w->proj, w->t, sw, sh, roi, mm); return ISX_OK; }
+
+// SphericalWarper: detectResultRoiByBorder - the border pixels ranked on the host (border_scan_host), the candidates for the four extrema
+// evaluated with the host's libm (exactly the values the host-only scan of round 2 took its minima / maxima over), then OpenCV's two pole
+// tests.  No device work.
+int roi_spherical(isx_warper* w, int sw, int sh, int roi[4], float mm[4]) {
+    SyncRoi& s = w->roi;
+    if (const RoiMemo::Entry* e = s.sph.find(w->proj, w->k, w->rinv, sw, sh)) { roi_answer(e->roi, e->mm, roi, mm); return ISX_OK; }
+    int n = 0, r[4];
     float emm[4];
-    roi_from_candidates(w->proj, w->k, w->rinv, sw, sh, w->host_cand.data(), n, roi, emm);
-    if (mm) std::copy(emm, emm + 4, mm);
-    const float tl_uf = emm[0], tl_vf = emm[1], br_uf = emm[2], br_vf = emm[3];
-    {
-        const size_t cap = w->roi_cache_on ? 1024 : 1;
-        while (w->roi_cache.size() >= cap) w->roi_cache.erase(w->roi_cache.begin());
-        isx_warper::RoiEntry e;
-        memset(&e, 0, sizeof(e));
-        e.proj = w->proj; e.sw = sw; e.sh = sh;
-        std::copy(roi, roi + 4, e.roi);
-        e.mm[0] = tl_uf; e.mm[1] = tl_vf; e.mm[2] = br_uf; e.mm[3] = br_vf;
-        w->roi_cache.push_back(e);
-    }
+    ISX_TRY(border_scan_host(w->proj.r_kinv, true, sw, sh, s.host_cand, s.host_scratch, 0, &n));
+    roi_from_candidates(w->proj, w->k, w->rinv, sw, sh, s.host_cand.data(), n, r, emm);
+    roi_answer(r, emm, roi, mm);
+    s.sph.remember(s.cache_on ? 1024 : 64, w->proj, w->k, w->rinv, sw, sh, r, emm);
     return ISX_OK;
 }
 
-// per-column / per-row tables of mapBackward's transcendental part, cached per (kind, scale, roi)
+// The cylindrical full scan on the device (W:72-81), its extremum candidates in s.host_cand when this returns.  The scan ranks the pixels
+// by the stand-ins (d, q); the candidate pass collects every pixel whose stand-in is within a tolerance of one of the four extrema.  Scan,
+// candidate pass, the copy of {count, first candidates} into pinned memory and the re-arming of the keys are enqueued back to back: ONE
+// stream synchronisation per detectResultRoi (the corner must reach the host, W:148-150,160).
+int scan_cylindrical_on_device(isx_warper* w, int sw, int sh, hipStream_t st, int* n_out) {
+    SyncRoi& s = w->roi;
+    unsigned* keys = (unsigned*)s.scan.p;
+    int* count = (int*)(keys + 4);
+    int* cand = (int*)((char*)s.scan.p + 64);
+    const dim3 grid(cdiv(sw, 256), cdiv(sh, SYNC_ROWS));
+    ISX_TRY(s.scan_blk.reserve((size_t)grid.x * grid.y * sizeof(float4)));
+    float4* blk = (float4*)s.scan_blk.p;
+    ISX_LAUNCH("roi_scan", 0.0, st, k_roi_scan, grid, dim3(256), 0, w->proj, sw, sh, (unsigned*)nullptr, SYNC_ROWS, blk);
+    static_assert(SYNC_ROWS % CAND_ROWS == 0, "a candidate block lies inside one scan block");
+    ISX_LAUNCH("roi_candidates", 0.0, st, k_roi_candidates, dim3(grid.x, cdiv(sh, CAND_ROWS)), dim3(256), 0, w->proj, sw, sh, cand, CAND_CAP, count, CAND_ROWS,
+               (const float4*)blk, SYNC_ROWS, (int)grid.y);
+    if (!s.pin) ISX_HIP(hipHostMalloc(&s.pin, 64 + (size_t)CAND_FIRST * 8, hipHostMallocDefault));
+    ISX_HIP(hipMemcpyAsync(s.pin, s.scan.p, 64 + (size_t)CAND_FIRST * 8, hipMemcpyDeviceToHost, st));
+    ISX_LAUNCH("roi_rearm", 0.0, st, k_roi_rearm, dim3(1), dim3(1), 0, keys);
+    ISX_HIP(hipStreamSynchronize(st));
+    const int n = ((const int*)s.pin)[4];
+    ISX_CHECK_ARG(n <= CAND_CAP, ISX_ERR_UNSUPPORTED, "detectResultRoi: %d extremum candidates exceed the refinement buffer (%d)", n, CAND_CAP);
+    ISX_CHECK_ARG(n > 0, ISX_ERR_INVALID, "detectResultRoi: mapForward is not finite anywhere on the %d x %d source (bad K / R / scale?)", sw, sh);
+    s.host_cand.resize((size_t)n * 2);
+    std::memcpy(s.host_cand.data(), (const char*)s.pin + 64, (size_t)std::min(n, CAND_FIRST) * 8);
+    if (n > CAND_FIRST)   // rare: more candidates than the first copy carried
+        ISX_HIP(hipMemcpy(s.host_cand.data() + 2 * (size_t)CAND_FIRST, cand + 2 * (size_t)CAND_FIRST, (size_t)(n - CAND_FIRST) * 8, hipMemcpyDeviceToHost));
+    *n_out = n;
+    return ISX_OK;
+}
+
+// CylindricalWarper: the candidates of the four extrema, from the border where that is proven enough and from the full scan elsewhere,
+// evaluated with the host's libm: the result is what the reference code computes on this host.
+// Round 3: where both extrema of u and v provably lie on the image's border (cyl_extrema_on_border: the image in front of the camera, no
+// pole of the cylinder within two pixels of it) the scan is the 2 (W + H) border pixels instead of all W x H: away from the poles neither
+// u nor v has a stationary point, so a pixel one step inside the border differs from the border's extremum by about a whole unit
+// (|grad| ~ scale / focal per pixel), four orders of magnitude above the rounding of mapForward - the extrema over the border ARE the
+// extrema over the image.
+int roi_cylindrical(isx_warper* w, int sw, int sh, hipStream_t st, int roi[4], float mm[4]) {
+    SyncRoi& s = w->roi;
+    if (const RoiMemo::Entry* e = s.cyl.find(w->proj, w->k, w->rinv, sw, sh)) { roi_answer(e->roi, e->mm, roi, mm); return ISX_OK; }
+    int n = 0, r[4];
+    float emm[4];
+    if (cyl_extrema_on_border(w->proj, w->k, w->rinv, sw, sh)) ISX_TRY(border_scan_host(w->proj.r_kinv, false, sw, sh, s.host_cand, s.host_scratch, 0, &n));
+    else ISX_TRY(scan_cylindrical_on_device(w, sw, sh, st, &n));
+    roi_from_candidates(w->proj, w->k, w->rinv, sw, sh, s.host_cand.data(), n, r, emm);
+    roi_answer(r, emm, roi, mm);
+    s.cyl.remember(s.cache_on ? 1024 : 1, w->proj, w->k, w->rinv, sw, sh, r, emm);
+    return ISX_OK;
+}
+
+// detectResultRoi of the handle's current camera, synchronously: roi, and the float extrema where mm is not null
+int detect_roi(isx_warper* w, int sw, int sh, int roi[4], float mm[4]) {
+    if (w->kind == ISX_WARP_PLANE) return roi_plane(w, sw, sh, roi, mm);
+    hipStream_t st = nullptr;
+    ISX_TRY(roi_stream_of(w, &st));
+    ISX_TRY(arm_scan_once(w->roi.scan, 64 + (size_t)CAND_CAP * 8, st));
+    return w->kind == ISX_WARP_SPHERICAL ? roi_spherical(w, sw, sh, roi, mm) : roi_cylindrical(w, sw, sh, st, roi, mm);
+}
+
+// ---- the tables of a warped tile (TableArena) ----------------------------------------------------------------------------------------------
 int make_tabs(isx_warper* w, const int roi[4], MapTabs* t) {
-    int mw = roi[2] - roi[0] + 1, mh = roi[3] - roi[1] + 1;
+    const int mw = roi[2] - roi[0] + 1, mh = roi[3] - roi[1] + 1;
     const int mwp = (mw + 3) & ~3, mhp = (mh + 3) & ~3;   // segments padded to 16 bytes: the fused kernel loads float4
-    size_t n = (size_t)2 * mwp + 2 * mhp;
-    // A fixed rig (the reference, every BASELINE config) asks for the same few ROIs for ever: up to 1024 of them stay (a 64-tile panorama
-    // through one handle needs 64; with 16 every planned warp recomputed 7 000 sinf / cosf, DESIGN.md §3 "Round 5").  A caller whose camera
-    // changes with every frame never hits: for it the cache is bounded by BYTES (TAB_BYTES of tables, ~350 ROIs of 4K tiles) and looked up
-    // through a hash, not scanned; when the arena or the entry list is full the stream is drained once and the cache starts over.
-    constexpr size_t TAB_SLOTS = 1024, TAB_BYTES = (size_t)16 << 20, TAB_CHUNK = (size_t)4 << 20;
-    unsigned long long key = 1469598103934665603ull;
-    {
-        unsigned sbits; memcpy(&sbits, &w->scale, 4);
-        unsigned tbits[3]; memcpy(tbits, w->t, 12);
-        const unsigned words[9] = {(unsigned)w->kind, sbits, (unsigned)roi[0], (unsigned)roi[1], (unsigned)roi[2], (unsigned)roi[3], tbits[0], tbits[1], tbits[2]};
-        for (unsigned v : words) { key ^= v; key *= 1099511628211ull; }
-    }
+    TableArena& a = w->tables;
     // a captured warp reads its tables when the graph is replayed, at a time this handle does not see: it must find them here now (a miss is
     // refused before anything is enqueued on the stream), and their chunk is pinned for as long as the handle lives
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(w->stream, &cap) != hipSuccess) { cap = hipStreamCaptureStatusNone; (void)hipGetLastError(); }
-    const bool capturing = cap != hipStreamCaptureStatusNone;
-    isx_warper::TabEntry* e = nullptr;
-    {
-        auto r = w->tab_index.equal_range(key);
-        for (auto it = r.first; it != r.second; ++it) {
-            isx_warper::TabEntry& c = w->tab_cache[it->second];
-            if (c.kind == w->kind && c.scale == w->scale && memcmp(c.t, w->t, sizeof(c.t)) == 0 && std::equal(roi, roi + 4, c.roi)) { e = &c; break; }
-        }
-    }
+    const bool capturing = stream_is_capturing(w->stream);
+    const TableArena::Entry* e = a.find(w->kind, w->scale, w->t, roi);
     if (!e) {
         ISX_CHECK_ARG(!capturing, ISX_ERR_STATE, "warp: no table for the warped tile [%d,%d]-[%d,%d] while the stream is being captured (warm the table before capture: "
                       "run the same warp once eagerly)", roi[0], roi[1], roi[2], roi[3]);
-        const size_t need = (n * sizeof(float) + 255) & ~(size_t)255;
-        ISX_CHECK_ARG(need <= TAB_CHUNK, ISX_ERR_UNSUPPORTED, "warp: a %d x %d warped tile needs %zu bytes of column / row tables (limit %zu)", mw, mh, need, TAB_CHUNK);
-        auto start_over = [&]() -> int {      // enqueued kernels (and collected ones: isx_warper_begin_batch) may still read the old tables: drain first
+        const size_t need = TableArena::room_for((size_t)2 * mwp + 2 * mhp);
+        ISX_CHECK_ARG(need <= TableArena::TAB_CHUNK, ISX_ERR_UNSUPPORTED, "warp: a %d x %d warped tile needs %zu bytes of column / row tables (limit %zu)", mw, mh, need,
+                      (size_t)TableArena::TAB_CHUNK);
+        if (a.full(need)) {      // drained and started over: what was collected (isx_warper_begin_batch) may still read the old tables, so it leaves first
             ISX_TRY(flush_warp_batch(w));
-            for (const auto& f : w->tab_fences) ISX_HIP(hipEventSynchronize(f.second));      // ... also on the streams this handle used before
-            ISX_HIP(hipStreamSynchronize(w->stream));
-            for (const auto& f : w->tab_fences) (void)hipEventDestroy(f.second);
-            w->tab_fences.clear();
-            std::vector<std::unique_ptr<DevBuf>> reuse;
-            for (size_t c = 0; c < w->tab_chunks.size(); ++c)
-                (c < w->tab_pinned.size() && w->tab_pinned[c] ? w->tab_kept : reuse).push_back(std::move(w->tab_chunks[c]));
-            w->tab_chunks.swap(reuse);
-            w->tab_pinned.assign(w->tab_chunks.size(), 0);
-            w->tab_cache.clear(); w->tab_index.clear(); w->tab_chunk = 0; w->tab_used = 0; ++w->tab_resets;
-            return ISX_OK;
-        };
-        if (w->tab_cache.size() >= TAB_SLOTS) ISX_TRY(start_over());
-        if (!w->tab_chunks.empty() && w->tab_used + need > TAB_CHUNK) {
-            if ((w->tab_chunk + 2) * TAB_CHUNK > TAB_BYTES) ISX_TRY(start_over());
-            else { ++w->tab_chunk; w->tab_used = 0; }
+            ISX_TRY(a.start_over(w->stream));
         }
-        if (w->tab_chunk >= w->tab_chunks.size()) {
-            w->tab_chunks.emplace_back(new DevBuf());
-            ISX_TRY(w->tab_chunks.back()->reserve(TAB_CHUNK));
-            w->tab_pinned.resize(w->tab_chunks.size(), 0);
-        }
-        float* dev = (float*)((char*)w->tab_chunks[w->tab_chunk]->p + w->tab_used);
-        w->tab_host.assign(n, 0.f);
-        float* cs = w->tab_host.data(); float* cc = cs + mwp; float* ra = cc + mwp; float* rb = ra + mhp;
-        const bool plane = w->kind == ISX_WARP_PLANE;
-        for (int i = 0; i < mw; ++i) {
-            float u = (float)(roi[0] + i);
-            u /= w->scale;                                 // W:48
-            if (plane) { cs[i] = u - w->t[0]; cc[i] = 0.f; }      // PlaneProjector::mapBackward: u = u / scale - t[0]
-            else { cs[i] = sinf(u); cc[i] = cosf(u); }     // W:51,53
-        }
-        for (int i = 0; i < mh; ++i) {
-            float v = (float)(roi[1] + i);
-            v /= w->scale;                                 // W:49
-            if (plane) { ra[i] = v - w->t[1]; rb[i] = 1 - w->t[2]; }                  // v = v / scale - t[1]; z_ = 1 - t[2]
-            else if (w->kind == ISX_WARP_CYLINDRICAL) { ra[i] = v; rb[i] = 0.f; }     // W:52
-            else { ra[i] = sinf(PI_F - v); rb[i] = cosf(PI_F - v); }
-        }
-        // the padding repeats the last column / row: the fused kernel's partial 4-pixel group at the right edge then computes ordinary
-        // pixels in its unused lanes (zeros would make z = 0 there and send the whole group down the generic path, once per row)
-        for (int i = mw; i < mwp; ++i) { cs[i] = cs[mw - 1]; cc[i] = cc[mw - 1]; }
-        for (int i = mh; i < mhp; ++i) { ra[i] = ra[mh - 1]; rb[i] = rb[mh - 1]; }
-        ISX_HIP(hipMemcpyAsync(dev, w->tab_host.data(), n * sizeof(float), hipMemcpyHostToDevice, w->stream));
-        // A miss is a planning-time event: the upload is simply waited for (so one staging vector serves).  (Tried without the wait in round 5, every
-        // entry keeping a host copy alive: the world-8 rehearsal of bench.py then delivered a wrong mosaic in 4 runs of 7 - on this runtime an asynchronous copy
-        // from PAGEABLE memory is not something a kernel launched right behind it on the same stream can rely on; 8 of 8 runs pass with the wait.)
-        ISX_HIP(hipStreamSynchronize(w->stream));
-        w->tab_used += need;
-        w->tab_cache.emplace_back();
-        e = &w->tab_cache.back();
-        e->kind = w->kind; e->scale = w->scale; memcpy(e->t, w->t, sizeof(e->t)); std::copy(roi, roi + 4, e->roi); e->dev = dev; e->chunk = w->tab_chunk;
-        w->tab_index.emplace(key, w->tab_cache.size() - 1);
+        fill_tables(w->kind, w->scale, w->t, roi, a.staging);
+        ISX_TRY(a.insert(w->kind, w->scale, w->t, roi, w->stream, &e));
     }
-    if (capturing) w->tab_pinned[e->chunk] = 1;
+    if (capturing) a.pin(e->chunk);
     const float* base = e->dev;
     t->col_s = base; t->col_c = base + mwp; t->row_a = base + 2 * mwp; t->row_b = base + 2 * mwp + mhp;
     return ISX_OK;
@@ -1717,182 +1897,145 @@ int check_roi_sane(const int roi[4]) {
     return ISX_OK;
 }
 
-int warp_one(isx_warper* w, const isx_mat* src, const isx_mat* src_mask, const float K[9], const float R[9], int interp, int border,
-             isx_mat* dst, isx_mat* dst_mask, int corner[2], const int* planned, bool fused, bool verify_plan) {
+// ---- warp ---------------------------------------------------------------------------------------------------------------------------------
+// planned: the caller's ROI (null: detectResultRoi here, synchronously); verify_plan: a planned ROI is checked behind the warp
+struct WarpRequest { const int* planned = nullptr; bool verify_plan = true; };
+// what both warp paths start from: the ROI, its tables, the staged source and destination
+struct WarpSetup { int roi[4]; int dw, dh; MapTabs t; SrcView sv; double spx, dpx; };
+
+int warp_setup(isx_warper* w, const isx_mat* src, isx_mat* dst, const float K[9], const float R[9], const WarpRequest& req, WarpSetup* s) {
     ISX_CHECK_ARG(w != nullptr, ISX_ERR_INVALID, "warp: null warper");
     ISX_TRY(check_mat(src, "warp: src"));
     ISX_TRY(check_mat(dst, "warp: dst"));
     ISX_HIP(hipSetDevice(w->device));
     ISX_TRY(set_camera(w, K, R));
-    int roi[4];
-    bool ranged = false;
-    int rc0 = 0, rc1 = 0;
-    if (planned) std::copy(planned, planned + 4, roi);   // the verifying scan is enqueued behind the warp kernel (below)
-    else ISX_TRY(detect_roi(w, src->cols, src->rows, roi, nullptr, false, nullptr));
-    ISX_TRY(check_roi_sane(roi));
-    const int dw = roi[2] - roi[0] + 1, dh = roi[3] - roi[1] + 1;   // dst.create(roi.height + 1, roi.width + 1)  W:150
-    ISX_CHECK_ARG(dst->rows == dh && dst->cols == dw, ISX_ERR_SIZE, "warp: dst is %dx%d, the warped tile is %dx%d (query isx_warper_roi first)",
-                  dst->cols, dst->rows, dw, dh);
-    MapTabs t;
-    ISX_TRY(make_tabs(w, roi, &t));
-    hipStream_t st = w->stream;
-    ISX_TRY(w->st_src.use_in(src, st, "warp: src"));
-    ISX_TRY(w->st_dst.use_out(dst, st, "warp: dst"));
-    SrcView sv{(const unsigned char*)w->st_src.d.data, w->st_src.d.step, src->rows, src->cols};
-    dim3 grid(cdiv(dw, 64), cdiv(dh, 4));
-    double spx = (double)src->rows * src->cols, dpx = (double)dw * dh;
-    if (fused) {
-        ISX_CHECK_ARG(src->type == ISX_8UC3, ISX_ERR_TYPE, "warp_with_mask: src_img must be CV_8UC3, got %s", type_name(src->type));
-        ISX_CHECK_ARG((unsigned long long)w->st_src.d.step * src->rows < (1ull << 31) && w->st_src.d.step < (1u << 24) && src->cols <= 32767 && src->rows <= 32767,
-                      ISX_ERR_UNSUPPORTED, "warp_with_mask: source larger than 2 GiB, 16 MiB per row or 32767 pixels per side");
-        ISX_CHECK_ARG(dst->type == ISX_8UC3 || dst->type == ISX_16SC3, ISX_ERR_TYPE, "warp_with_mask: dst_img must be CV_8UC3 or CV_16SC3, got %s", type_name(dst->type));
-        ISX_TRY(check_mat(dst_mask, "warp_with_mask: dst_mask"));
-        ISX_CHECK_ARG(dst_mask->type == ISX_8UC1, ISX_ERR_TYPE, "warp_with_mask: dst_mask must be CV_8U, got %s", type_name(dst_mask->type));
-        ISX_CHECK_ARG(dst_mask->rows == dh && dst_mask->cols == dw, ISX_ERR_SIZE, "warp_with_mask: dst_mask is %dx%d, the warped tile is %dx%d",
-                      dst_mask->cols, dst_mask->rows, dw, dh);
-        SrcView mv{nullptr, 0, src->rows, src->cols};
-        if (src_mask) {
-            ISX_TRY(check_mat(src_mask, "warp_with_mask: src_mask"));
-            ISX_CHECK_ARG(src_mask->type == ISX_8UC1, ISX_ERR_TYPE, "warp_with_mask: src_mask must be CV_8U, got %s", type_name(src_mask->type));
-            ISX_CHECK_ARG(src_mask->rows == src->rows && src_mask->cols == src->cols, ISX_ERR_SIZE, "warp_with_mask: src_mask size differs from src_img");
-            ISX_TRY(w->st_mask.use_in(src_mask, st, "warp_with_mask: src_mask"));
-            mv.data = (const unsigned char*)w->st_mask.d.data; mv.step = w->st_mask.d.step;
-        }
-        ISX_TRY(w->st_dmask.use_out(dst_mask, st, "warp_with_mask: dst_mask"));
-        double bytes = spx * (src_mask ? 4.0 : 3.0) + dpx * (dst->type == ISX_16SC3 ? 7.0 : 4.0);
-        // dword stores need 4-byte aligned destination rows (pitch-aligned mats; a dense cv::Mat whose
-        // row length is not a multiple of 4 bytes takes the per-pixel store path)
-        const isx_mat& dd = w->st_dst.d;
-        const isx_mat& dm = w->st_dmask.d;
-        // k_warp_tile stores 12-byte runs at any alignment (a dense cv::Mat row need not start on a dword); the caller-mask kernel keeps its
-        // dword stores for aligned rows
-        const bool vec = ((uintptr_t)dd.data % 4 == 0) && (dd.step % 4 == 0) && ((uintptr_t)dm.data % 4 == 0) && (dm.step % 4 == 0);
-        // both destinations: the kernels store the mask at a 32-bit offset (24-bit multiply) as they do the image
-        ISX_CHECK_ARG(dd.step < (1u << 24) && dm.step < (1u << 24) && (unsigned long long)dd.step * dh < (1ull << 32) &&
-                      (unsigned long long)dm.step * dh < (1ull << 32), ISX_ERR_UNSUPPORTED,
-                      "warp_with_mask: destination image or mask larger than 4 GiB or 16 MiB per row");
-        dim3 grid4(cdiv(dw, 256), cdiv(dh, 4));
-        // sync path: the scan ran on this stream and the host has consumed its keys; the kernel re-arms them.
-        // planned path: scan + check run on the side stream, nothing to do here.
-        const unsigned* plan_keys = nullptr;
-        int* plan_mism = nullptr;
-        const int4 plan4 = make_int4(0, 0, 0, 0);
-#define ISX_WARP_FUSED_P(O16, V, PL)                                                                                             \
-        ISX_LAUNCH("warp_img_mask", bytes, st, (k_warp_img_mask<O16, V, PL>), grid4, dim3(256), 0, w->proj, t, sv, mv, src_mask ? 1 : 0, \
-                   (unsigned char*)dd.data, dd.step, (unsigned char*)dm.data, dm.step, dw, dh, plan_keys, plan4, plan_mism)
-#define ISX_WARP_FUSED(O16, V) do { if (w->kind == ISX_WARP_PLANE) ISX_WARP_FUSED_P(O16, V, true); else ISX_WARP_FUSED_P(O16, V, false); } while (0)
-        // the hot kernel: a tile whose mask is all 255 (W:213-214).  Launch names are the kernels' names without the k_ (they can be
-        // found in a rocprofv3 kernel trace as they are)
-        // isx_warper_set_dst_columns: only the 64-column blocks that hold columns [col0, col1) of the warped tile are computed; the
-        // kernel's right crop is the range's end, its left end the block boundary at or below col0
-        int bx0 = 0, wcrop = dw;
-        if (w->col1 > w->col0 && !src_mask) {
-            bx0 = std::min(w->col0, dw - 1) / 64; wcrop = std::min(w->col1, dw);
-            bytes *= (double)(cdiv(wcrop, 64) - bx0) / cdiv(dw, 64);
-        }
-        const dim3 gridt(cdiv(wcrop, 64) - bx0, cdiv(dh, 4 * WARP_WAVES));
-        const bool gained = w->gain != 1.0;
-        ISX_CHECK_ARG(!(gained && src_mask), ISX_ERR_UNSUPPORTED, "warp_with_mask: isx_warper_set_gain applies to tiles warped with the all-255 mask (src_mask == NULL)");
-        // (xg = 0: the plain block order; k_warp_tile's XCD-run order was measured and left off)
-        WarpTileArgs wta{w->proj, t, sv, TileDst{(unsigned char*)dd.data, (unsigned)dd.step, (unsigned char*)dm.data, (unsigned)dm.step, wcrop, dh, bx0, 0, 0xFFFFFFFFu / gridt.x + 1u}, {}};
-        if (gained) memcpy(wta.lut, w->gain_lut, 256);
-#define ISX_WARP_TILE(KD, O16, V)                                                                                                            \
-    do {                                                                                                                                     \
-        if (gained) ISX_LAUNCH("warp_tile", bytes, st, (k_warp_tile<KD, O16, V, true, true>), gridt, dim3(64 * WARP_WAVES), 0, wta);          \
-        else ISX_LAUNCH("warp_tile", bytes, st, (k_warp_tile<KD, O16, V>), gridt, dim3(64 * WARP_WAVES), 0, wta);                              \
-    } while (0)
-#define ISX_WARP_TILE_K(O16, V)                                                                     \
-    do {                                                                                            \
-        if (w->kind == ISX_WARP_CYLINDRICAL) ISX_WARP_TILE(ISX_WARP_CYLINDRICAL, O16, V);           \
-        else if (w->kind == ISX_WARP_SPHERICAL) ISX_WARP_TILE(ISX_WARP_SPHERICAL, O16, V);          \
-        else ISX_WARP_TILE(ISX_WARP_PLANE, O16, V);                                                 \
-    } while (0)
-        const bool collect = !src_mask && w->batching && !gained && dst->device >= 0 && dst_mask->device >= 0 && src->device >= 0;
-        if (!collect) ISX_TRY(flush_warp_batch(w));      // whatever is launched here goes out BEHIND what was collected so far
-        if (collect) {
-            // collected: leaves with the other tiles of the batch as one launch (flush_warp_batch)
-            isx_warper::BatchItem bi;
-            bi.variant = 2 * w->kind | (dst->type == ISX_16SC3 ? 1 : 0);
-            bi.g = WarpTileGeom{wta.p, wta.t, wta.img, wta.d};
-            bi.gx = gridt.x; bi.gy = gridt.y; bi.bytes = bytes;
-            w->batch.push_back(bi);
-        } else if (!src_mask) {
-            if (dst->type == ISX_16SC3) ISX_WARP_TILE_K(true, true);
-            else ISX_WARP_TILE_K(false, true);
-        } else if (dst->type == ISX_16SC3) { if (vec) ISX_WARP_FUSED(true, true); else ISX_WARP_FUSED(true, false); }
-        else { if (vec) ISX_WARP_FUSED(false, true); else ISX_WARP_FUSED(false, false); }
-#undef ISX_WARP_TILE_K
-#undef ISX_WARP_TILE
-#undef ISX_WARP_FUSED
-#undef ISX_WARP_FUSED_P
-        // a column range (isx_warper_set_dst_columns) leaves the other columns of the mats as they are - also of host mats, of which only the
-        // computed columns come back from the staging buffers
-        ranged = w->col1 > w->col0 && !src_mask;
-        rc0 = bx0 * 64; rc1 = wcrop;
-        if (ranged) ISX_TRY(w->st_dmask.finish_out_cols(st, rc0, rc1)); else ISX_TRY(w->st_dmask.finish_out(st));
-        if (planned && verify_plan) {
-            int scratch[4];
-            ISX_TRY(detect_roi(w, src->cols, src->rows, scratch, nullptr, true, planned));
-        }
+    if (req.planned) std::copy(req.planned, req.planned + 4, s->roi);
+    else ISX_TRY(detect_roi(w, src->cols, src->rows, s->roi, nullptr));
+    ISX_TRY(check_roi_sane(s->roi));
+    s->dw = s->roi[2] - s->roi[0] + 1; s->dh = s->roi[3] - s->roi[1] + 1;   // dst.create(roi.height + 1, roi.width + 1)  W:150
+    ISX_CHECK_ARG(dst->rows == s->dh && dst->cols == s->dw, ISX_ERR_SIZE, "warp: dst is %dx%d, the warped tile is %dx%d (query isx_warper_roi first)",
+                  dst->cols, dst->rows, s->dw, s->dh);
+    ISX_TRY(make_tabs(w, s->roi, &s->t));
+    ISX_TRY(w->st_src.use_in(src, w->stream, "warp: src"));
+    ISX_TRY(w->st_dst.use_out(dst, w->stream, "warp: dst"));
+    s->sv = SrcView{(const unsigned char*)w->st_src.d.data, w->st_src.d.step, src->rows, src->cols};
+    s->spx = (double)src->rows * src->cols; s->dpx = (double)s->dw * s->dh;
+    return ISX_OK;
+}
+
+// image + mask of a tile in one pass (W:229 + W:232, + W:294 for a CV_16SC3 tile)
+int warp_fused(isx_warper* w, const isx_mat* src, const isx_mat* src_mask, const float K[9], const float R[9], isx_mat* dst, isx_mat* dst_mask, int corner[2],
+               const WarpRequest& req) {
+    WarpSetup s;
+    ISX_TRY(warp_setup(w, src, dst, K, R, req, &s));
+    const hipStream_t st = w->stream;
+    const int dw = s.dw, dh = s.dh;
+    ISX_CHECK_ARG(src->type == ISX_8UC3, ISX_ERR_TYPE, "warp_with_mask: src_img must be CV_8UC3, got %s", type_name(src->type));
+    ISX_CHECK_ARG((unsigned long long)w->st_src.d.step * src->rows < (1ull << 31) && w->st_src.d.step < (1u << 24) && src->cols <= 32767 && src->rows <= 32767,
+                  ISX_ERR_UNSUPPORTED, "warp_with_mask: source larger than 2 GiB, 16 MiB per row or 32767 pixels per side");
+    ISX_CHECK_ARG(dst->type == ISX_8UC3 || dst->type == ISX_16SC3, ISX_ERR_TYPE, "warp_with_mask: dst_img must be CV_8UC3 or CV_16SC3, got %s", type_name(dst->type));
+    ISX_TRY(check_mat(dst_mask, "warp_with_mask: dst_mask"));
+    ISX_CHECK_ARG(dst_mask->type == ISX_8UC1, ISX_ERR_TYPE, "warp_with_mask: dst_mask must be CV_8U, got %s", type_name(dst_mask->type));
+    ISX_CHECK_ARG(dst_mask->rows == dh && dst_mask->cols == dw, ISX_ERR_SIZE, "warp_with_mask: dst_mask is %dx%d, the warped tile is %dx%d",
+                  dst_mask->cols, dst_mask->rows, dw, dh);
+    SrcView mv{nullptr, 0, src->rows, src->cols};
+    if (src_mask) {
+        ISX_TRY(check_mat(src_mask, "warp_with_mask: src_mask"));
+        ISX_CHECK_ARG(src_mask->type == ISX_8UC1, ISX_ERR_TYPE, "warp_with_mask: src_mask must be CV_8U, got %s", type_name(src_mask->type));
+        ISX_CHECK_ARG(src_mask->rows == src->rows && src_mask->cols == src->cols, ISX_ERR_SIZE, "warp_with_mask: src_mask size differs from src_img");
+        ISX_TRY(w->st_mask.use_in(src_mask, st, "warp_with_mask: src_mask"));
+        mv.data = (const unsigned char*)w->st_mask.d.data; mv.step = w->st_mask.d.step;
+    }
+    ISX_TRY(w->st_dmask.use_out(dst_mask, st, "warp_with_mask: dst_mask"));
+    const bool out16 = dst->type == ISX_16SC3;
+    double bytes = s.spx * (src_mask ? 4.0 : 3.0) + s.dpx * (out16 ? 7.0 : 4.0);
+    const isx_mat& dd = w->st_dst.d;
+    const isx_mat& dm = w->st_dmask.d;
+    // k_warp_tile stores 12-byte runs at any alignment (a dense cv::Mat row need not start on a dword); the caller-mask kernel keeps its
+    // dword stores for 4-byte aligned destination rows (pitch-aligned mats; a dense cv::Mat whose row length is not a multiple of 4 bytes
+    // takes the per-pixel store path)
+    const bool vec = ((uintptr_t)dd.data % 4 == 0) && (dd.step % 4 == 0) && ((uintptr_t)dm.data % 4 == 0) && (dm.step % 4 == 0);
+    // both destinations: the kernels store the mask at a 32-bit offset (24-bit multiply) as they do the image
+    ISX_CHECK_ARG(dd.step < (1u << 24) && dm.step < (1u << 24) && (unsigned long long)dd.step * dh < (1ull << 32) &&
+                  (unsigned long long)dm.step * dh < (1ull << 32), ISX_ERR_UNSUPPORTED,
+                  "warp_with_mask: destination image or mask larger than 4 GiB or 16 MiB per row");
+    // isx_warper_set_dst_columns: only the 64-column blocks that hold columns [col0, col1) of the warped tile are computed; the
+    // kernel's right crop is the range's end, its left end the block boundary at or below col0.  It leaves the other columns of the mats as
+    // they are - also of host mats, of which only the computed columns come back from the staging buffers.
+    const bool ranged = w->col1 > w->col0 && !src_mask;
+    int bx0 = 0, wcrop = dw;
+    if (ranged) {
+        bx0 = std::min(w->col0, dw - 1) / 64; wcrop = std::min(w->col1, dw);
+        bytes *= (double)(cdiv(wcrop, 64) - bx0) / cdiv(dw, 64);
+    }
+    const dim3 gridt(cdiv(wcrop, 64) - bx0, cdiv(dh, 4 * WARP_WAVES));
+    const bool gained = w->gain != 1.0;
+    ISX_CHECK_ARG(!(gained && src_mask), ISX_ERR_UNSUPPORTED, "warp_with_mask: isx_warper_set_gain applies to tiles warped with the all-255 mask (src_mask == NULL)");
+    const bool collect = !src_mask && w->batch.open && !gained && dst->device >= 0 && dst_mask->device >= 0 && src->device >= 0;
+    if (!collect) ISX_TRY(flush_warp_batch(w));      // whatever is launched here goes out BEHIND what was collected so far
+    if (src_mask) {
+        ISX_TRY(launch_warp_img_mask(st, w->kind, out16, vec, bytes, w->proj, s.t, s.sv, mv, dd, dm, dw, dh));
     } else {
-        ISX_TRY(flush_warp_batch(w));      // (a plain warp() inside a batch: behind the collected tile warps)
-        ISX_CHECK_ARG(dst->type == src->type, ISX_ERR_TYPE, "warp: dst type %s differs from src type %s", type_name(dst->type), type_name(src->type));
-        ISX_CHECK_ARG(interp == ISX_INTER_NEAREST || interp == ISX_INTER_LINEAR || interp == (ISX_INTER_LINEAR | ISX_INTER_TIES_EVEN), ISX_ERR_UNSUPPORTED,
-                      "warp: interpolation %d (only NEAREST and LINEAR)", interp);
-        ISX_CHECK_ARG(border >= ISX_BORDER_CONSTANT && border <= ISX_BORDER_REFLECT_101, ISX_ERR_UNSUPPORTED, "warp: border mode %d", border);
-        double bytes = (spx + dpx) * mat_elem_size(src->type);
-        unsigned char* dp = (unsigned char*)w->st_dst.d.data;
-        size_t ds = w->st_dst.d.step;
-        // The two calls the reference makes per tile (W:229 image LINEAR / REFLECT, W:232 mask NEAREST / CONSTANT) take the tile kernels:
-        // k_warp_tile without its mask output, k_warp_mask_tile.  Same limits as the fused entry (32-bit offsets from 24-bit multiplies).
-        const bool small = (unsigned long long)w->st_src.d.step * src->rows < (1ull << 31) && w->st_src.d.step < (1u << 24) && src->cols <= 32767 && src->rows <= 32767 &&
-                           ds < (1u << 24) && (unsigned long long)ds * dh < (1ull << 32);
-        if (small && src->type == ISX_8UC3 && interp == ISX_INTER_LINEAR && border == ISX_BORDER_REFLECT) {
-            const dim3 gridt(cdiv(dw, 64), cdiv(dh, 4 * WARP_WAVES));
-            const WarpTileArgs wta{w->proj, t, sv, TileDst{dp, (unsigned)ds, nullptr, 0u, dw, dh, 0, 0, 0xFFFFFFFFu / gridt.x + 1u}, {}};      // (xg = 0: as above)
-#define ISX_WARP_IMG(KD) ISX_LAUNCH("warp_tile_img", bytes, st, (k_warp_tile<KD, false, true, false>), gridt, dim3(64 * WARP_WAVES), 0, wta)
-            if (w->kind == ISX_WARP_CYLINDRICAL) ISX_WARP_IMG(ISX_WARP_CYLINDRICAL);
-            else if (w->kind == ISX_WARP_SPHERICAL) ISX_WARP_IMG(ISX_WARP_SPHERICAL);
-            else ISX_WARP_IMG(ISX_WARP_PLANE);
-#undef ISX_WARP_IMG
-        } else if (small && src->type == ISX_8UC1 && interp == ISX_INTER_NEAREST && border == ISX_BORDER_CONSTANT) {
-            const WarpMaskArgs wma{w->proj, t, sv, dp, (unsigned)ds, dw, dh};
-            const dim3 gridm(cdiv(dw, 64), cdiv(dh, 16));
-#define ISX_WARP_MSK(KD) ISX_LAUNCH("warp_tile_mask", bytes, st, (k_warp_mask_tile<KD, true>), gridm, dim3(256), 0, wma)
-            if (w->kind == ISX_WARP_CYLINDRICAL) ISX_WARP_MSK(ISX_WARP_CYLINDRICAL);
-            else if (w->kind == ISX_WARP_SPHERICAL) ISX_WARP_MSK(ISX_WARP_SPHERICAL);
-            else ISX_WARP_MSK(ISX_WARP_PLANE);
-#undef ISX_WARP_MSK
-        } else {
-#define ISX_WARP_ANY(T, CN)                                                                                                                          \
-    do {                                                                                                                                             \
-        if (w->kind == ISX_WARP_PLANE) ISX_LAUNCH("warp", bytes, st, (k_warp<T, CN, true>), grid, dim3(256), 0, w->proj, t, sv, dp, ds, dw, dh, interp, border); \
-        else ISX_LAUNCH("warp", bytes, st, (k_warp<T, CN>), grid, dim3(256), 0, w->proj, t, sv, dp, ds, dw, dh, interp, border);                      \
-    } while (0)
-        switch (src->type) {
-            case ISX_8UC3: ISX_WARP_ANY(unsigned char, 3); break;
-            case ISX_8UC1: ISX_WARP_ANY(unsigned char, 1); break;
-            case ISX_32FC3: ISX_WARP_ANY(float, 3); break;
-            case ISX_32FC1: ISX_WARP_ANY(float, 1); break;
-            default: return fail(ISX_ERR_TYPE, "warp: src type %s is not supported (CV_8UC1/3, CV_32FC1/3)", type_name(src->type));
-        }
-#undef ISX_WARP_ANY
+        // (xg = 0: the plain block order; k_warp_tile's XCD-run order was measured and left off)
+        WarpTileArgs wta{w->proj, s.t, s.sv, TileDst{(unsigned char*)dd.data, (unsigned)dd.step, (unsigned char*)dm.data, (unsigned)dm.step, wcrop, dh, bx0, 0, 0xFFFFFFFFu / gridt.x + 1u}, {}};
+        if (gained) memcpy(wta.lut, w->gain_lut, 256);
+        if (collect) w->batch.items.push_back(BatchItem{w->kind, out16, WarpTileGeom{wta.p, wta.t, wta.img, wta.d}, gridt.x, gridt.y, bytes});      // leaves with the batch (flush_warp_batch)
+        else ISX_TRY(launch_warp_tile(st, w->kind, out16, gained, gridt, bytes, wta));
+    }
+    const int rc0 = bx0 * 64, rc1 = wcrop;
+    if (ranged) ISX_TRY(w->st_dmask.finish_out_cols(st, rc0, rc1)); else ISX_TRY(w->st_dmask.finish_out(st));
+    if (req.planned && req.verify_plan) {
+        if (w->kind == ISX_WARP_PLANE) ISX_TRY(queue_plan_check(w, src->cols, src->rows, req.planned));      // compared at once, on the host
+        else {
+            // the verifying scan runs on the side stream, behind this warp (a collecting batch: its verifications start when it ends)
+            ISX_TRY(arm_scan_once(w->roi.scan, 64 + (size_t)CAND_CAP * 8, st));      // (the synchronous scan's keys: armed by whichever path comes first)
+            ISX_TRY(queue_plan_check(w, src->cols, src->rows, req.planned));
+            if (!w->verify.deferred && !w->batch.open) ISX_TRY(flush_verify(w));
         }
     }
     if (ranged) ISX_TRY(w->st_dst.finish_out_cols(st, rc0, rc1)); else ISX_TRY(w->st_dst.finish_out(st));
-    if (corner) { corner[0] = roi[0]; corner[1] = roi[1]; }   // return dst_roi.tl()  W:160
+    if (corner) { corner[0] = s.roi[0]; corner[1] = s.roi[1]; }   // return dst_roi.tl()  W:160
+    return ISX_OK;
+}
+
+// RotationWarper::warp (W:145-161): one mat, any supported type, interpolation and border
+int warp_plain(isx_warper* w, const isx_mat* src, const float K[9], const float R[9], int interp, int border, isx_mat* dst, int corner[2], const WarpRequest& req) {
+    WarpSetup s;
+    ISX_TRY(warp_setup(w, src, dst, K, R, req, &s));
+    const hipStream_t st = w->stream;
+    const int dw = s.dw, dh = s.dh;
+    ISX_TRY(flush_warp_batch(w));      // (a plain warp() inside a batch: behind the collected tile warps)
+    ISX_CHECK_ARG(dst->type == src->type, ISX_ERR_TYPE, "warp: dst type %s differs from src type %s", type_name(dst->type), type_name(src->type));
+    ISX_CHECK_ARG(interp == ISX_INTER_NEAREST || interp == ISX_INTER_LINEAR || interp == (ISX_INTER_LINEAR | ISX_INTER_TIES_EVEN), ISX_ERR_UNSUPPORTED,
+                  "warp: interpolation %d (only NEAREST and LINEAR)", interp);
+    ISX_CHECK_ARG(border >= ISX_BORDER_CONSTANT && border <= ISX_BORDER_REFLECT_101, ISX_ERR_UNSUPPORTED, "warp: border mode %d", border);
+    const double bytes = (s.spx + s.dpx) * mat_elem_size(src->type);
+    unsigned char* dp = (unsigned char*)w->st_dst.d.data;
+    const size_t ds = w->st_dst.d.step;
+    // The two calls the reference makes per tile take the tile kernels, within the limits of the fused entry (32-bit offsets from 24-bit multiplies)
+    const bool small = (unsigned long long)w->st_src.d.step * src->rows < (1ull << 31) && w->st_src.d.step < (1u << 24) && src->cols <= 32767 && src->rows <= 32767 &&
+                       ds < (1u << 24) && (unsigned long long)ds * dh < (1ull << 32);
+    if (small && src->type == ISX_8UC3 && interp == ISX_INTER_LINEAR && border == ISX_BORDER_REFLECT) {
+        const dim3 gridt(cdiv(dw, 64), cdiv(dh, 4 * WARP_WAVES));
+        const WarpTileArgs wta{w->proj, s.t, s.sv, TileDst{dp, (unsigned)ds, nullptr, 0u, dw, dh, 0, 0, 0xFFFFFFFFu / gridt.x + 1u}, {}};      // (xg = 0: as in warp_fused)
+        ISX_TRY(launch_warp_tile_img(st, w->kind, gridt, bytes, wta));
+    } else if (small && src->type == ISX_8UC1 && interp == ISX_INTER_NEAREST && border == ISX_BORDER_CONSTANT) {
+        ISX_TRY(launch_warp_mask_tile(st, w->kind, bytes, WarpMaskArgs{w->proj, s.t, s.sv, dp, (unsigned)ds, dw, dh}));
+    } else {
+        ISX_TRY(launch_warp_any(st, w->kind, src->type, bytes, w->proj, s.t, s.sv, dp, ds, dw, dh, interp, border));
+    }
+    ISX_TRY(w->st_dst.finish_out(st));
+    if (corner) { corner[0] = s.roi[0]; corner[1] = s.roi[1]; }   // return dst_roi.tl()  W:160
     return ISX_OK;
 }
 
 // A warp that fails inside a batch ends the batch: what was collected before it leaves now (those warps returned ISX_OK, so their outputs are
 // written), and the next begin_batch starts empty.  The failure's own status and message are returned (a failing flush replaces them).
-int warp_common(isx_warper* w, const isx_mat* src, const isx_mat* src_mask, const float K[9], const float R[9], int interp, int border,
-                isx_mat* dst, isx_mat* dst_mask, int corner[2], const int* planned, bool fused, bool verify_plan = true) {
-    const int rc = warp_one(w, src, src_mask, K, R, interp, border, dst, dst_mask, corner, planned, fused, verify_plan);
-    if (rc != ISX_OK && w != nullptr && w->batching) {
-        w->batching = false;
+int end_batch_on_failure(isx_warper* w, int rc) {
+    if (rc != ISX_OK && w != nullptr && w->batch.open) {
+        w->batch.open = false;
         ISX_TRY(flush_warp_batch(w));
-        if (!w->defer_verify) ISX_TRY(flush_verify(w));
+        if (!w->verify.deferred) ISX_TRY(flush_verify(w));
     }
     return rc;
 }
@@ -1905,7 +2048,7 @@ int isx_warper_create(int kind, float scale, int device, isx_warper** out) ISX_E
     clear_error();
     ISX_CHECK_ARG(out != nullptr, ISX_ERR_INVALID, "isx_warper_create: null out pointer");
     *out = nullptr;
-    ISX_CHECK_ARG(kind == ISX_WARP_CYLINDRICAL || kind == ISX_WARP_SPHERICAL || kind == ISX_WARP_PLANE, ISX_ERR_INVALID, "isx_warper_create: unknown warper kind %d", kind);
+    ISX_CHECK_ARG(valid_kind(kind), ISX_ERR_INVALID, "isx_warper_create: unknown warper kind %d", kind);
     ISX_CHECK_ARG(std::isfinite(scale) && scale > 0.f, ISX_ERR_INVALID, "isx_warper_create: scale must be positive, got %g", (double)scale);
     int n = 0;
     ISX_HIP(hipGetDeviceCount(&n));
@@ -1920,13 +2063,13 @@ int isx_warper_create(int kind, float scale, int device, isx_warper** out) ISX_E
 int isx_warper_destroy(isx_warper* w) ISX_ENTRY {
     if (!w) return ISX_OK;
     (void)hipSetDevice(w->device);
-    w->batching = false;
+    w->batch.open = false;
     (void)flush_warp_batch(w);          // an open batch: its warps returned ISX_OK, their outputs are written before the handle goes
     (void)hipStreamSynchronize(w->stream);
-    for (const auto& f : w->tab_fences) (void)hipEventDestroy(f.second);
-    if (w->side) { (void)hipStreamSynchronize(w->side); (void)hipEventDestroy(w->ev_warp); (void)hipEventDestroy(w->ev_scan); }   // the side stream is shared per device
-    if (w->pin) (void)hipHostFree(w->pin);
-    delete w;
+    PlanVerify& v = w->verify;
+    if (v.side) { (void)hipStreamSynchronize(v.side); (void)hipEventDestroy(v.ev_warp); (void)hipEventDestroy(v.ev_scan); }   // the side stream is shared per device
+    if (w->roi.pin) (void)hipHostFree(w->roi.pin);
+    delete w;                           // (the arena's fences go with it)
     return ISX_OK;
 } ISX_EXIT("isx_warper_destroy")
 
@@ -1935,7 +2078,7 @@ int isx_warper_begin_batch(isx_warper* w) ISX_ENTRY {
     ISX_CHECK_ARG(w != nullptr, ISX_ERR_INVALID, "isx_warper_begin_batch: null warper");
     ISX_HIP(hipSetDevice(w->device));
     ISX_TRY(flush_warp_batch(w));
-    w->batching = true;
+    w->batch.open = true;
     return ISX_OK;
 } ISX_EXIT("isx_warper_begin_batch")
 
@@ -1943,30 +2086,18 @@ int isx_warper_end_batch(isx_warper* w) ISX_ENTRY {
     clear_error();
     ISX_CHECK_ARG(w != nullptr, ISX_ERR_INVALID, "isx_warper_end_batch: null warper");
     ISX_HIP(hipSetDevice(w->device));
-    w->batching = false;
+    w->batch.open = false;
     ISX_TRY(flush_warp_batch(w));
-    if (!w->defer_verify) return flush_verify(w);        // the planned warps' verification scans, behind the launch they verify
+    if (!w->verify.deferred) return flush_verify(w);        // the planned warps' verification scans, behind the launch they verify
     return ISX_OK;
 } ISX_EXIT("isx_warper_end_batch")
 
 int isx_warper_set_stream(isx_warper* w, void* hip_stream) ISX_ENTRY {
     ISX_CHECK_ARG(w != nullptr, ISX_ERR_INVALID, "isx_warper_set_stream: null warper");
     ISX_TRY(flush_warp_batch(w));      // collected warps leave on the stream they were issued for
-    if ((hipStream_t)hip_stream != w->stream && !w->tab_cache.empty()) {
-        // the stream being left may still run warps that read the table arena: a later start-over waits for this point of it (a stream being
-        // captured enqueues nothing that runs now, and the chunks its graph reads are pinned)
+    if ((hipStream_t)hip_stream != w->stream && !w->tables.entries.empty()) {
         ISX_HIP(hipSetDevice(w->device));
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(w->stream, &cs) != hipSuccess) { cs = hipStreamCaptureStatusNone; (void)hipGetLastError(); }
-        if (cs == hipStreamCaptureStatusNone) {
-            hipEvent_t ev = nullptr;
-            for (const auto& f : w->tab_fences) if (f.first == w->stream) ev = f.second;
-            if (!ev) {
-                ISX_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-                w->tab_fences.emplace_back(w->stream, ev);
-            }
-            ISX_HIP(hipEventRecord(ev, w->stream));
-        }
+        ISX_TRY(w->tables.leave_stream(w->stream));
     }
     w->stream = (hipStream_t)hip_stream;
     return ISX_OK;
@@ -2010,14 +2141,14 @@ int isx_warper_warp_point(isx_warper* w, const float K[9], const float R[9], flo
 
 int isx_warper_table_resets(isx_warper* w, long long* resets) ISX_ENTRY {
     ISX_CHECK_ARG(w != nullptr && resets != nullptr, ISX_ERR_INVALID, "isx_warper_table_resets: null argument");
-    *resets = w->tab_resets;
+    *resets = w->tables.resets;
     return ISX_OK;
 } ISX_EXIT("isx_warper_table_resets")
 
 int isx_warper_set_roi_cache(isx_warper* w, int on) ISX_ENTRY {
     ISX_CHECK_ARG(w != nullptr, ISX_ERR_INVALID, "isx_warper_set_roi_cache: null warper");
-    w->roi_cache_on = on != 0;
-    if (!on) w->roi_cache.clear();      // (the last result is remembered again from the next call on)
+    w->roi.cache_on = on != 0;
+    if (!on) w->roi.cyl.list.clear();      // (the last result is remembered again from the next call on)
     return ISX_OK;
 } ISX_EXIT("isx_warper_set_roi_cache")
 
@@ -2044,7 +2175,7 @@ int isx_warper_roi(isx_warper* w, int src_w, int src_h, const float K[9], const 
     ISX_CHECK_ARG(src_w > 0 && src_h > 0, ISX_ERR_INVALID, "isx_warper_roi: empty source size %d x %d", src_w, src_h);
     ISX_HIP(hipSetDevice(w->device));
     ISX_TRY(set_camera(w, K, R));
-    return detect_roi(w, src_w, src_h, roi, minmax, false, nullptr);
+    return detect_roi(w, src_w, src_h, roi, minmax);
 } ISX_EXIT("isx_warper_roi")
 
 namespace {
@@ -2055,7 +2186,7 @@ int build_maps_common(isx_warper* w, int src_w, int src_h, const float K[9], con
     ISX_CHECK_ARG(xmap->type == ISX_32FC1 && ymap->type == ISX_32FC1, ISX_ERR_TYPE, "buildMaps: maps must be CV_32FC1");
     ISX_HIP(hipSetDevice(w->device));
     ISX_TRY(set_camera(w, K, R));
-    if (!given_roi) ISX_TRY(detect_roi(w, src_w, src_h, roi, nullptr, false, nullptr));
+    if (!given_roi) ISX_TRY(detect_roi(w, src_w, src_h, roi, nullptr));
     ISX_TRY(check_roi_sane(roi));
     const int dw = roi[2] - roi[0] + 1, dh = roi[3] - roi[1] + 1;   // W:128-129
     ISX_CHECK_ARG(xmap->rows == dh && xmap->cols == dw && ymap->rows == dh && ymap->cols == dw, ISX_ERR_SIZE,
@@ -2065,13 +2196,7 @@ int build_maps_common(isx_warper* w, int src_w, int src_h, const float K[9], con
     hipStream_t st = w->stream;
     ISX_TRY(w->st_x.use_out(xmap, st, "buildMaps: xmap"));
     ISX_TRY(w->st_y.use_out(ymap, st, "buildMaps: ymap"));
-    dim3 grid(cdiv(dw, 64), cdiv(dh, 4));
-    if (w->kind == ISX_WARP_PLANE)
-        ISX_LAUNCH("build_maps", (double)dw * dh * 8.0, st, k_build_maps<true>, grid, dim3(256), 0, w->proj, t, (float*)w->st_x.d.data, w->st_x.d.step,
-                   (float*)w->st_y.d.data, w->st_y.d.step, dw, dh);
-    else
-        ISX_LAUNCH("build_maps", (double)dw * dh * 8.0, st, k_build_maps<false>, grid, dim3(256), 0, w->proj, t, (float*)w->st_x.d.data, w->st_x.d.step,
-                   (float*)w->st_y.d.data, w->st_y.d.step, dw, dh);
+    ISX_TRY(launch_build_maps(st, w->kind, w->proj, t, w->st_x.d, w->st_y.d, dw, dh));
     ISX_TRY(w->st_x.finish_out(st));
     ISX_TRY(w->st_y.finish_out(st));
     return ISX_OK;
@@ -2112,20 +2237,9 @@ int isx_remap(const isx_mat* src, const isx_mat* xmap, const isx_mat* ymap, int 
     ISX_TRY(sx.use_in(xmap, st, "remap: xmap"));
     ISX_TRY(sy.use_in(ymap, st, "remap: ymap"));
     ISX_TRY(sd.use_out(dst, st, "remap: dst"));
-    SrcView sv{(const unsigned char*)ss.d.data, ss.d.step, src->rows, src->cols};
-    const int dw = dst->cols, dh = dst->rows;
-    dim3 grid(cdiv(dw, 64), cdiv(dh, 4));
-    const double bytes = (double)dw * dh * (8.0 + 2.0 * mat_elem_size(src->type));
-#define ISX_REMAP(T, CN)                                                                                                                     \
-    ISX_LAUNCH("remap", bytes, st, (k_remap<T, CN>), grid, dim3(256), 0, sv, (const unsigned char*)sx.d.data, sx.d.step, (const unsigned char*)sy.d.data, \
-               sy.d.step, (unsigned char*)sd.d.data, sd.d.step, dw, dh, interp, border)
-    switch (src->type) {
-        case ISX_8UC1: ISX_REMAP(unsigned char, 1); break;
-        case ISX_8UC3: ISX_REMAP(unsigned char, 3); break;
-        case ISX_32FC1: ISX_REMAP(float, 1); break;
-        default: ISX_REMAP(float, 3); break;
-    }
-#undef ISX_REMAP
+    const SrcView sv{(const unsigned char*)ss.d.data, ss.d.step, src->rows, src->cols};
+    const double bytes = (double)dst->cols * dst->rows * (8.0 + 2.0 * mat_elem_size(src->type));
+    ISX_TRY(launch_remap(st, src->type, bytes, sv, sx.d, sy.d, sd.d, interp, border));
     ISX_TRY(sd.finish_out(st));
     if (src->device < 0 || xmap->device < 0 || ymap->device < 0 || dst->device < 0) ISX_HIP(hipStreamSynchronize(st));   // staging buffers are freed on return
     return ISX_OK;
@@ -2133,33 +2247,33 @@ int isx_remap(const isx_mat* src, const isx_mat* xmap, const isx_mat* ymap, int 
 
 int isx_warper_warp(isx_warper* w, const isx_mat* src, const float K[9], const float R[9], int interp, int border, isx_mat* dst, int corner[2]) ISX_ENTRY {
     clear_error();
-    return warp_common(w, src, nullptr, K, R, interp, border, dst, nullptr, corner, nullptr, false);
+    return end_batch_on_failure(w, warp_plain(w, src, K, R, interp, border, dst, corner, WarpRequest{}));
 } ISX_EXIT("isx_warper_warp")
 
 int isx_warper_warp_with_mask(isx_warper* w, const isx_mat* src_img, const isx_mat* src_mask, const float K[9], const float R[9],
                               isx_mat* dst_img, isx_mat* dst_mask, int corner[2]) ISX_ENTRY {
     clear_error();
-    return warp_common(w, src_img, src_mask, K, R, ISX_INTER_LINEAR, ISX_BORDER_REFLECT, dst_img, dst_mask, corner, nullptr, true);
+    return end_batch_on_failure(w, warp_fused(w, src_img, src_mask, K, R, dst_img, dst_mask, corner, WarpRequest{}));
 } ISX_EXIT("isx_warper_warp_with_mask")
 
 int isx_warper_warp_with_mask_planned(isx_warper* w, const isx_mat* src_img, const isx_mat* src_mask, const float K[9], const float R[9],
                                       const int planned_roi[4], isx_mat* dst_img, isx_mat* dst_mask) ISX_ENTRY {
     clear_error();
     ISX_CHECK_ARG(planned_roi != nullptr, ISX_ERR_INVALID, "planned warp: null planned_roi");
-    return warp_common(w, src_img, src_mask, K, R, ISX_INTER_LINEAR, ISX_BORDER_REFLECT, dst_img, dst_mask, nullptr, planned_roi, true);
+    return end_batch_on_failure(w, warp_fused(w, src_img, src_mask, K, R, dst_img, dst_mask, nullptr, WarpRequest{planned_roi, true}));
 } ISX_EXIT("isx_warper_warp_with_mask_planned")
 
 int isx_warper_warp_roi(isx_warper* w, const isx_mat* src, const float K[9], const float R[9], int interp, int border, const int roi[4], isx_mat* dst) ISX_ENTRY {
     clear_error();
     ISX_CHECK_ARG(roi != nullptr, ISX_ERR_INVALID, "warp_roi: null roi");
-    return warp_common(w, src, nullptr, K, R, interp, border, dst, nullptr, nullptr, roi, false, false);
+    return end_batch_on_failure(w, warp_plain(w, src, K, R, interp, border, dst, nullptr, WarpRequest{roi, false}));
 } ISX_EXIT("isx_warper_warp_roi")
 
 int isx_warper_warp_with_mask_roi(isx_warper* w, const isx_mat* src_img, const isx_mat* src_mask, const float K[9], const float R[9],
                                   const int roi[4], isx_mat* dst_img, isx_mat* dst_mask) ISX_ENTRY {
     clear_error();
     ISX_CHECK_ARG(roi != nullptr, ISX_ERR_INVALID, "warp_with_mask_roi: null roi");
-    return warp_common(w, src_img, src_mask, K, R, ISX_INTER_LINEAR, ISX_BORDER_REFLECT, dst_img, dst_mask, nullptr, roi, true, false);
+    return end_batch_on_failure(w, warp_fused(w, src_img, src_mask, K, R, dst_img, dst_mask, nullptr, WarpRequest{roi, false}));
 } ISX_EXIT("isx_warper_warp_with_mask_roi")
 
 // detectResultRoi computed on the host alone, for the cameras whose ROI the synchronous path takes from the border (every spherical camera;
@@ -2169,15 +2283,10 @@ int isx_warper_warp_with_mask_roi(isx_warper* w, const isx_mat* src_img, const i
 int isx_selftest_roi_host(int kind, float scale, const float K[9], const float R[9], int src_w, int src_h, int isa, int roi[4], float minmax[4]) ISX_ENTRY {
     clear_error();
     ISX_CHECK_ARG(K != nullptr && R != nullptr && roi != nullptr, ISX_ERR_INVALID, "selftest_roi_host: null argument");
-    ISX_CHECK_ARG((kind == ISX_WARP_CYLINDRICAL || kind == ISX_WARP_SPHERICAL || kind == ISX_WARP_PLANE) && src_w > 0 && src_h > 0, ISX_ERR_INVALID, "selftest_roi_host: bad kind / size");
+    ISX_CHECK_ARG(valid_kind(kind) && src_w > 0 && src_h > 0, ISX_ERR_INVALID, "selftest_roi_host: bad kind / size");
     Proj p;
-    float k[9], rinv[9], kinv[9];
-    for (int i = 0; i < 9; ++i) k[i] = K[i];
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) rinv[i * 3 + j] = R[j * 3 + i];
-    mat3_inv(K, kinv);
-    mat3_mul(R, kinv, p.r_kinv);
-    mat3_mul(K, rinv, p.k_rinv);
-    p.scale = scale; p.kind = kind;
+    float k[9], rinv[9];
+    make_proj(kind, scale, K, R, &p, k, rinv);
     if (kind == ISX_WARP_PLANE) {      // the four-corner rule, T = 0
         const float t0[3] = {0.f, 0.f, 0.f};
         roi_plane_host(p, t0, src_w, src_h, roi, minmax);
@@ -2200,16 +2309,12 @@ int isx_selftest_roi_host(int kind, float scale, const float K[9], const float R
 int isx_selftest_warp_point(int kind, float scale, const float K[9], const float R[9], const float T[3], float x, float y, float out_uv[2]) ISX_ENTRY {
     clear_error();
     ISX_CHECK_ARG(K != nullptr && R != nullptr && out_uv != nullptr, ISX_ERR_INVALID, "selftest_warp_point: null argument");
-    ISX_CHECK_ARG(kind == ISX_WARP_CYLINDRICAL || kind == ISX_WARP_SPHERICAL || kind == ISX_WARP_PLANE, ISX_ERR_INVALID, "selftest_warp_point: unknown warper kind %d", kind);
+    ISX_CHECK_ARG(valid_kind(kind), ISX_ERR_INVALID, "selftest_warp_point: unknown warper kind %d", kind);
     const float t[3] = {T ? T[0] : 0.f, T ? T[1] : 0.f, T ? T[2] : 0.f};
     ISX_CHECK_ARG(kind == ISX_WARP_PLANE || (t[0] == 0.f && t[1] == 0.f && t[2] == 0.f), ISX_ERR_UNSUPPORTED, "selftest_warp_point: only the plane warper takes a translation");
     Proj p;
-    float rinv[9], kinv[9];
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) rinv[i * 3 + j] = R[j * 3 + i];
-    mat3_inv(K, kinv);
-    mat3_mul(R, kinv, p.r_kinv);
-    mat3_mul(K, rinv, p.k_rinv);
-    p.scale = scale; p.kind = kind;
+    float k[9], rinv[9];
+    make_proj(kind, scale, K, R, &p, k, rinv);
     if (kind == ISX_WARP_PLANE) map_forward_plane_host(p, t, x, y, out_uv[0], out_uv[1]);
     else map_forward_host(p, x, y, out_uv[0], out_uv[1]);
     return ISX_OK;
@@ -2233,7 +2338,7 @@ int isx_selftest_division(int device, int n, unsigned long long seed, int* misma
 
 int isx_warper_set_deferred_verify(isx_warper* w, int on) ISX_ENTRY {
     ISX_CHECK_ARG(w != nullptr, ISX_ERR_INVALID, "isx_warper_set_deferred_verify: null warper");
-    w->defer_verify = on != 0;
+    w->verify.deferred = on != 0;
     return ISX_OK;
 } ISX_EXIT("isx_warper_set_deferred_verify")
 
@@ -2241,7 +2346,7 @@ int isx_warper_verify_is_light(isx_warper* w, int src_cols, int src_rows, const 
     clear_error();
     ISX_CHECK_ARG(w != nullptr && light != nullptr && src_cols > 0 && src_rows > 0, ISX_ERR_INVALID, "isx_warper_verify_is_light: bad argument");
     ISX_TRY(set_camera(w, K, R));
-    *light = (w->kind == ISX_WARP_PLANE || w->kind == ISX_WARP_SPHERICAL || cyl_extrema_on_border(w->proj, w->k, w->rinv, src_cols, src_rows)) ? 1 : 0;
+    *light = verify_is_light(w->proj, w->k, w->rinv, src_cols, src_rows) ? 1 : 0;
     return ISX_OK;
 } ISX_EXIT("isx_warper_verify_is_light")
 
@@ -2267,7 +2372,7 @@ int isx_warper_verify_after(isx_warper* w, void* hip_event) ISX_ENTRY {
 int isx_warper_discard_pending(isx_warper* w) ISX_ENTRY {
     clear_error();
     ISX_CHECK_ARG(w != nullptr, ISX_ERR_INVALID, "isx_warper_discard_pending: null warper");
-    w->pending.clear();
+    w->verify.pending.clear();
     return ISX_OK;
 } ISX_EXIT("isx_warper_discard_pending")
 
@@ -2277,16 +2382,7 @@ int isx_warper_queue_verify(isx_warper* w, int src_w, int src_h, const float K[9
     ISX_CHECK_ARG(src_w > 0 && src_h > 0, ISX_ERR_INVALID, "isx_warper_queue_verify: empty source %d x %d", src_w, src_h);
     ISX_HIP(hipSetDevice(w->device));
     ISX_TRY(set_camera(w, K, R));
-    if (w->kind == ISX_WARP_PLANE) {      // four corners, compared here (detect_roi)
-        int scratch[4];
-        return detect_roi(w, src_w, src_h, scratch, nullptr, true, planned_roi);
-    }
-    isx_warper::Pending pd;
-    pd.proj = w->proj; pd.sw = src_w; pd.sh = src_h;
-    std::copy(planned_roi, planned_roi + 4, pd.planned);
-    std::copy(w->k, w->k + 9, pd.k); std::copy(w->rinv, w->rinv + 9, pd.rinv);
-    w->pending.push_back(pd);
-    return ISX_OK;
+    return queue_plan_check(w, src_w, src_h, planned_roi);
 } ISX_EXIT("isx_warper_queue_verify")
 
 int isx_warper_join(isx_warper* w) ISX_ENTRY {
@@ -2294,8 +2390,8 @@ int isx_warper_join(isx_warper* w) ISX_ENTRY {
     ISX_CHECK_ARG(w != nullptr, ISX_ERR_INVALID, "isx_warper_join: null warper");
     ISX_HIP(hipSetDevice(w->device));
     ISX_TRY(flush_verify(w));
-    if (!w->side) return ISX_OK;
-    ISX_HIP(hipStreamWaitEvent(w->stream, w->ev_scan, 0));
+    if (!w->verify.side) return ISX_OK;
+    ISX_HIP(hipStreamWaitEvent(w->stream, w->verify.ev_scan, 0));
     return ISX_OK;
 } ISX_EXIT("isx_warper_join")
 
@@ -2305,12 +2401,13 @@ int isx_warper_plan_status(isx_warper* w, int* mismatches) ISX_ENTRY {
     *mismatches = 0;
     ISX_HIP(hipSetDevice(w->device));
     ISX_TRY(flush_verify(w));
-    if (w->scan_side.p) {
-        ISX_HIP(hipStreamSynchronize(w->side));
+    PlanVerify& v = w->verify;
+    if (v.keys.p) {
+        ISX_HIP(hipStreamSynchronize(v.side));
         ISX_HIP(hipStreamSynchronize(w->stream));
-        ISX_HIP(hipMemcpy(mismatches, (int*)w->scan_side.p + 5, sizeof(int), hipMemcpyDeviceToHost));
+        ISX_HIP(hipMemcpy(mismatches, (int*)v.keys.p + 5, sizeof(int), hipMemcpyDeviceToHost));
     }
-    *mismatches += w->plan_mismatches_host;      // plane handles: the four-corner rule, compared when the planned warp was issued
+    *mismatches += v.host_mismatches;      // plane handles: the four-corner rule, compared when the planned warp was issued
     if (*mismatches) return fail(ISX_ERR_PLAN, "planned warp: %d run(s) produced a ROI that differs from the planned one", *mismatches);
     return ISX_OK;
 } ISX_EXIT("isx_warper_plan_status")
