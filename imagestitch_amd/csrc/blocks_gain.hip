@@ -28,6 +28,7 @@
 // by byte.
 #include "isx_device.hpp"
 #include "pairwise.hpp"
+#include "scratch.hpp"
 #include "gain_stats.hpp"
 #include "blocks_gain_host.hpp"
 
@@ -135,7 +136,7 @@ struct LuAux {
     LuState* state = nullptr;
     double* x = nullptr;
     int reserve(int n) {
-        const size_t xb = ((size_t)n * sizeof(double) + 255) & ~(size_t)255, pb = ((size_t)n * sizeof(int) + 255) & ~(size_t)255;
+        const size_t xb = round256((size_t)n * sizeof(double)), pb = round256((size_t)n * sizeof(int));
         ISX_TRY(buf.reserve(xb + pb + 256));
         x = (double*)buf.p; perm = (int*)((char*)buf.p + xb); state = (LuState*)((char*)buf.p + xb + pb);
         return ISX_OK;
@@ -275,16 +276,16 @@ namespace {
 int tables_for(isx_blocks_gain* h, int mw, int mh, int w, int hh, hipStream_t st, const ResizeTables** out) {
     for (const auto& t : h->tables)
         if (t->mw == mw && t->mh == mh && t->w == w && t->h == hh) { *out = t.get(); return ISX_OK; }
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    ISX_HIP(hipStreamIsCapturing(st, &cs));
-    ISX_CHECK_ARG(cs == hipStreamCaptureStatusNone, ISX_ERR_STATE,
+    bool capturing = false;
+    ISX_TRY(is_capturing(st, capturing));
+    ISX_CHECK_ARG(!capturing, ISX_ERR_STATE,
                   "blocks_gain_apply: the stream is capturing and the tables of a %d x %d map for a %d x %d image are not built yet (apply once before the capture)", mw, mh, w, hh);
     std::vector<ColTap> c;
     std::vector<RowTap> r;
     resize_tables(mw, mh, w, hh, c, r);
     std::unique_ptr<ResizeTables> t(new ResizeTables());
     t->mw = mw; t->mh = mh; t->w = w; t->h = hh;
-    const size_t cb = (c.size() * sizeof(ColTap) + 255) & ~(size_t)255;
+    const size_t cb = round256(c.size() * sizeof(ColTap));
     ISX_TRY(t->buf.reserve(cb + r.size() * sizeof(RowTap)));
     ISX_HIP(hipMemcpyAsync(t->buf.p, c.data(), c.size() * sizeof(ColTap), hipMemcpyHostToDevice, st));
     ISX_HIP(hipMemcpyAsync((char*)t->buf.p + cb, r.data(), r.size() * sizeof(RowTap), hipMemcpyHostToDevice, st));
@@ -343,9 +344,7 @@ int isx_blocks_gain_feed(isx_blocks_gain* h, int num_images, const int* corners_
     const int B = (int)total;
     ISX_HIP(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    ISX_HIP(hipStreamIsCapturing(st, &cs));
-    ISX_CHECK_ARG(cs == hipStreamCaptureStatusNone, ISX_ERR_STATE, "%s: the stream is capturing (feed reads the statistics and the gains back to the host)", who);
+    ISX_TRY(refuse_capture(st, who, "feed reads the statistics and the gains back to the host"));
     h->fed = false;
     auto t0 = std::chrono::steady_clock::now();
 
@@ -459,7 +458,7 @@ int isx_blocks_gain_feed(isx_blocks_gain* h, int num_images, const int* corners_
     LuAux aux;
     ISX_TRY(mat.reserve((size_t)B * lda * sizeof(double)));
     ISX_TRY(aux.reserve(B));
-    const size_t db = ((size_t)B * sizeof(double) + 255) & ~(size_t)255;
+    const size_t db = round256((size_t)B * sizeof(double));
     ISX_TRY(sys.reserve(2 * db + std::max<size_t>(off.size(), 1) * sizeof(OffDiag)));
     double* d_diag = (double*)sys.p;
     double* d_b = (double*)((char*)sys.p + db);

@@ -22,6 +22,7 @@
 // in unsigned __int128 and rounds once.  Isum is therefore math.fsum of the terms, bit for bit, whatever the block shape or order.
 #include "isx_device.hpp"
 #include "pairwise.hpp"
+#include "scratch.hpp"
 #include "gain_stats.hpp"
 
 #include <cmath>
@@ -181,8 +182,7 @@ __global__ __launch_bounds__(GF_NT) void k_gain_feed(const GainItem* __restrict_
 struct FeedScratch {
     DevBuf dev;
     int device = -1;
-    void* pin = nullptr;
-    size_t pin_cap = 0;
+    PinBuf pin;
 };
 
 }  // namespace
@@ -193,18 +193,13 @@ int gain_item_size(bool diag) { return diag ? GF_DIAG_BYTES : GF_PAIR_PIXELS; }
 
 int gain_feed_items(const std::vector<GainItem>& items, double alg_bytes, int device, hipStream_t st, std::vector<GainPartial>& part) {
     const size_t ni = items.size();
-    const size_t tab_bytes = (ni * sizeof(GainItem) + 255) & ~(size_t)255, part_bytes = ni * sizeof(GainPartial);
+    const size_t tab_bytes = round256(ni * sizeof(GainItem)), part_bytes = ni * sizeof(GainPartial);
     FeedScratch& fs = per_thread<FeedScratch>();
     if (fs.device != device) { fs.dev.release(); fs.device = device; }
     ISX_TRY(fs.dev.reserve(tab_bytes + part_bytes));
-    if (fs.pin_cap < tab_bytes + part_bytes) {
-        if (fs.pin) { ISX_HIP(hipHostFree(fs.pin)); fs.pin = nullptr; fs.pin_cap = 0; }
-        const size_t want = std::max<size_t>(tab_bytes + part_bytes, 1u << 16);
-        ISX_HIP(hipHostMalloc(&fs.pin, want, hipHostMallocDefault));
-        fs.pin_cap = want;
-    }
-    GainItem* htab = (GainItem*)fs.pin;
-    const GainPartial* hpart = (const GainPartial*)((char*)fs.pin + tab_bytes);
+    ISX_TRY(fs.pin.reserve(tab_bytes + part_bytes, std::max<size_t>(tab_bytes + part_bytes, 1u << 16)));      // (the call ends synchronised: nothing reads the old one)
+    GainItem* htab = (GainItem*)fs.pin.p;
+    const GainPartial* hpart = (const GainPartial*)((char*)fs.pin.p + tab_bytes);
     std::copy(items.begin(), items.end(), htab);
     GainItem* dtab = (GainItem*)fs.dev.p;
     GainPartial* dpart = (GainPartial*)((char*)fs.dev.p + tab_bytes);

@@ -36,6 +36,7 @@
 // batches per global relabel) and the call fails past them with the pair's masks untouched.
 #include "isx_device.hpp"
 #include "pairwise.hpp"
+#include "scratch.hpp"
 
 using namespace isx;
 using namespace isxd;
@@ -440,7 +441,7 @@ __global__ __launch_bounds__(GC_NT) void k_gc_cert(GcArr<CapT> a, OutT* res, uns
 struct GcScratch {
     DevBuf graph, cert;
     int device = -1;
-    int* pin = nullptr;
+    PinBuf pin;                          // 64 ints: the counters read back
     MatStages stages;                    // slot 2 i: image i, slot 2 i + 1: mask i
 };
 
@@ -469,12 +470,16 @@ inline int gc_launch_build(const GcGeom& G, const GcArr<long long>& a, GcMode, d
 template <typename CapT, typename OutT>
 int gc_solve_pair(GcScratch& s, const GcGeom& G, GcMode mode, hipStream_t st, PairOut& out, OutT* cert_res, unsigned char* cert_lab) {
     const size_t n = (size_t)G.hp * G.wp;
-    const size_t arr = (n * sizeof(CapT) + 255) & ~(size_t)255, arr_i = (n * sizeof(int) + 255) & ~(size_t)255;
-    ISX_TRY(s.graph.reserve(5 * arr + 2 * arr_i + 256));
+    Bump lay;                            // five arrays of CapT, two of int, the counters
+    size_t o_cap[5];
+    for (size_t& o : o_cap) o = lay.take(n * sizeof(CapT));
+    const size_t o_i0 = lay.take(n * sizeof(int)), o_i1 = lay.take(n * sizeof(int)), o_cnt = lay.take(256);
+    ISX_TRY(s.graph.reserve(lay.at));
     char* base = (char*)s.graph.p;
-    GcArr<CapT> a{(CapT*)(base), (CapT*)(base + arr), (int*)(base + 5 * arr), (CapT*)(base + 2 * arr), (CapT*)(base + 3 * arr), (CapT*)(base + 4 * arr),
-                  (int*)(base + 5 * arr + arr_i), G.hp, G.wp};
-    int* cnt = (int*)(base + 5 * arr + 2 * arr_i);   // GC_C_WORDS ints: changed flags, active count, (unused) flag, flow (8-byte aligned)
+    GcArr<CapT> a{(CapT*)(base + o_cap[0]), (CapT*)(base + o_cap[1]), (int*)(base + o_i0), (CapT*)(base + o_cap[2]), (CapT*)(base + o_cap[3]),
+                  (CapT*)(base + o_cap[4]), (int*)(base + o_i1), G.hp, G.wp};
+    int* cnt = (int*)(base + o_cnt);     // GC_C_WORDS ints: changed flags, active count, (unused) flag, flow (8-byte aligned)
+    int* const pin = (int*)s.pin.p;
     const dim3 grid = gc_grid(G.wp, G.hp), tiles((unsigned)cdiv(G.wp, GC_TW), (unsigned)cdiv(G.hp, GC_TH));
     const double nb = (double)n * sizeof(CapT);
     out.hp = G.hp; out.wp = G.wp; out.rounds = 0; out.launches = 0;
@@ -492,9 +497,9 @@ int gc_solve_pair(GcScratch& s, const GcGeom& G, GcMode mode, hipStream_t st, Pa
             }
             ISX_LAUNCH("graphcut_count", nb * 7, st, k_gc_count<CapT>, grid, dim3(GC_NT), 0, a, cnt + GC_C_COUNT, (unsigned long long*)nullptr);
             ++out.launches;
-            ISX_HIP(hipMemcpyAsync(s.pin, cnt, (GC_C_COUNT + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
+            ISX_HIP(hipMemcpyAsync(pin, cnt, (GC_C_COUNT + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
             ISX_HIP(hipStreamSynchronize(st));
-            if (s.pin[GC_C_CHANGED + GC_BFS_BATCH - 1] == 0) { *active = s.pin[GC_C_COUNT]; return ISX_OK; }
+            if (pin[GC_C_CHANGED + GC_BFS_BATCH - 1] == 0) { *active = pin[GC_C_COUNT]; return ISX_OK; }
         }
         return fail(ISX_ERR_UNSUPPORTED, "graphcut: the global relabel did not settle within %d launches", GC_MAX_BFS_BATCHES * GC_BFS_BATCH);
     };
@@ -522,10 +527,10 @@ int gc_solve_pair(GcScratch& s, const GcGeom& G, GcMode mode, hipStream_t st, Pa
     }
     ISX_LAUNCH("graphcut_write_back", (double)G.rw * G.rh * 8.0, st, k_gc_write_back, gc_grid(G.rw, G.rh), dim3(GC_NT), 0, G, (const int*)a.h);
     ++out.launches;
-    ISX_HIP(hipMemcpyAsync(s.pin, cnt, GC_C_WORDS * sizeof(int), hipMemcpyDeviceToHost, st));
+    ISX_HIP(hipMemcpyAsync(pin, cnt, GC_C_WORDS * sizeof(int), hipMemcpyDeviceToHost, st));
     ISX_HIP(hipStreamSynchronize(st));
     unsigned long long f;
-    memcpy(&f, s.pin + GC_C_FLOW, sizeof(f));
+    memcpy(&f, pin + GC_C_FLOW, sizeof(f));
     out.flow = (long long)f;
     return ISX_OK;
 }
@@ -568,16 +573,10 @@ int gc_check_size(int n, const isx_mat* images, const int* corners_xy, int cost_
 
 // capture check, device views of every image and mask, and the CV_32FC3 value check - all before the first pair writes
 int gc_prepare(GcScratch& s, int n, const isx_mat* images, isx_mat* masks, int device, hipStream_t st, GcCall& c, const char* who) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    ISX_HIP(hipStreamIsCapturing(st, &cs));
-    ISX_CHECK_ARG(cs == hipStreamCaptureStatusNone, ISX_ERR_STATE, "%s: the stream is capturing (the finder reads counters back to the host)", who);
+    ISX_TRY(refuse_capture(st, who, "the finder reads counters back to the host"));
     if (s.device != device) { s.graph.release(); s.cert.release(); s.device = device; }
     s.stages.use_device(device);
-    if (!s.pin) {
-        void* p = nullptr;
-        ISX_HIP(hipHostMalloc(&p, 64 * sizeof(int), hipHostMallocDefault));
-        s.pin = (int*)p;
-    }
+    ISX_TRY(s.pin.reserve(64 * sizeof(int), 64 * sizeof(int)));
     c.img.resize(n);
     c.msk.resize(n);
     for (int i = 0; i < n; ++i) {
@@ -591,9 +590,9 @@ int gc_prepare(GcScratch& s, int n, const isx_mat* images, isx_mat* masks, int d
         for (int i = 0; i < n; ++i)
             ISX_LAUNCH("graphcut_check", (double)c.img[i].rows * c.img[i].cols * 12.0, st, k_gc_check_f32, gc_grid(c.img[i].cols, c.img[i].rows), dim3(GC_NT), 0,
                        (const unsigned char*)c.img[i].data, c.img[i].step, c.img[i].rows, c.img[i].cols, flag);
-        ISX_HIP(hipMemcpyAsync(s.pin, flag, sizeof(int), hipMemcpyDeviceToHost, st));
+        ISX_HIP(hipMemcpyAsync(s.pin.p, flag, sizeof(int), hipMemcpyDeviceToHost, st));
         ISX_HIP(hipStreamSynchronize(st));
-        ISX_CHECK_ARG(s.pin[0] == 0, ISX_ERR_UNSUPPORTED, "%s: a CV_32FC3 value is not an integer in [0, 255] (the capacities would not be exact)", who);
+        ISX_CHECK_ARG(*(const int*)s.pin.p == 0, ISX_ERR_UNSUPPORTED, "%s: a CV_32FC3 value is not an integer in [0, 255] (the capacities would not be exact)", who);
     }
     return ISX_OK;
 }
@@ -642,7 +641,7 @@ int gc_find_pair(const isx_mat* image1, const isx_mat* image2, const int* corner
     OutT* dres = nullptr;
     unsigned char* dlab = nullptr;
     if (residuals) {
-        const size_t rb = ((size_t)n * 6 * sizeof(OutT) + 255) & ~(size_t)255;
+        const size_t rb = round256((size_t)n * 6 * sizeof(OutT));
         ISX_TRY(s.cert.reserve(rb + (size_t)n));
         dres = (OutT*)s.cert.p;
         dlab = (unsigned char*)s.cert.p + rb;
@@ -669,8 +668,7 @@ int isx_graphcut_seam_release(void) ISX_ENTRY {
     s.cert.release();
     s.stages.clear();
     s.device = -1;
-    if (s.pin) { ISX_HIP(hipHostFree(s.pin)); s.pin = nullptr; }
-    return ISX_OK;
+    return s.pin.release();
 } ISX_EXIT("isx_graphcut_seam_release")
 
 int isx_graphcut_seam_find(int num_images, const isx_mat* images, const int* corners_xy, isx_mat* masks, int cost_type, int device,

@@ -22,6 +22,7 @@
 // own that loops over the points in order: the bits of the sequential loop without a reduction tree.
 #include "isx_device.hpp"
 #include "pairwise.hpp"
+#include "scratch.hpp"
 
 #include <cfloat>
 
@@ -541,53 +542,9 @@ __global__ __launch_bounds__(HG_CHUNK) void k_hg_pairs(HgCall c) {
     if (lane == 0) as_global(c.conf)[p] = conf;
 }
 
-struct HgScratch {
-    DevBuf work;
-    int device = -1;
-    void* pin = nullptr;                 // the upload: the table, host counts and the staged rows of host points mats
-    size_t pin_cap = 0;
-    hipEvent_t uploaded = nullptr;       // recorded after the upload that reads `pin`
-    bool pending = false;
-    hipEvent_t done = nullptr;           // recorded after the kernel: a call on another stream waits for it before it reuses `work`
-    hipStream_t last = nullptr;
-    bool ran = false;
-    bool lds_set = false;
+struct HgScratch : UploadScratch {       // pin: the table, host counts and the staged rows of host points mats (scratch.hpp)
+    bool lds_set = false;                // k_hg_pairs may use HG_LDS_BYTES of LDS on `device`
 };
-
-int hg_wait_upload(HgScratch& s) {
-    if (s.pending) { ISX_HIP(hipEventSynchronize(s.uploaded)); s.pending = false; }
-    return ISX_OK;
-}
-int hg_release(HgScratch& s) {
-    ISX_TRY(hg_wait_upload(s));
-    if (s.uploaded) { ISX_HIP(hipEventDestroy(s.uploaded)); s.uploaded = nullptr; }
-    if (s.done) { ISX_HIP(hipEventDestroy(s.done)); s.done = nullptr; }
-    s.ran = false;
-    if (s.pin) { ISX_HIP(hipHostFree(s.pin)); s.pin = nullptr; s.pin_cap = 0; }
-    s.work.release();
-    s.device = -1;
-    return ISX_OK;
-}
-
-struct Bump {                            // offsets into one buffer, 256-byte aligned
-    size_t at = 0;
-    size_t take(size_t bytes) { const size_t o = at; at += (bytes + 255) & ~(size_t)255; return o; }
-};
-
-// a mat of `type` with at least rows x cols elements, aligned to `align` bytes in pointer and step; null data is fine where no row is needed
-int hg_check_mat(const isx_mat& m, int type, long long rows, int cols, int align, int device, const char* who, const char* what, int index) {
-    ISX_CHECK_ARG(m.type == type, ISX_ERR_TYPE, "%s: %s %d is %s (%s)", who, what, index, type_name(m.type), type_name(type));
-    ISX_CHECK_ARG(m.rows >= rows && (m.rows == 0 || rows == 0 || m.cols >= cols), ISX_ERR_SIZE, "%s: %s %d is %d x %d, the call needs %lld x %d", who, what,
-                  index, m.rows, m.cols, rows, cols);
-    if (m.rows == 0) return ISX_OK;
-    ISX_CHECK_ARG(m.cols >= cols, ISX_ERR_SIZE, "%s: %s %d has %d columns, the call needs %d", who, what, index, m.cols, cols);
-    ISX_CHECK_ARG(m.data != nullptr, ISX_ERR_INVALID, "%s: %s %d has a null data pointer", who, what, index);
-    ISX_CHECK_ARG(m.step >= (size_t)m.cols * mat_elem_size(type) || m.rows == 1, ISX_ERR_INVALID, "%s: %s %d: step %zu smaller than a row", who, what, index, m.step);
-    ISX_CHECK_ARG(((uintptr_t)m.data & (uintptr_t)(align - 1)) == 0 && (m.step & (size_t)(align - 1)) == 0, ISX_ERR_INVALID,
-                  "%s: %s %d is not %d-byte aligned in pointer and step", who, what, index, align);
-    ISX_CHECK_ARG(m.device < 0 || m.device == device, ISX_ERR_INVALID, "%s: %s %d lives on device %d, the call runs on %d", who, what, index, m.device, device);
-    return ISX_OK;
-}
 
 }  // namespace
 
@@ -595,7 +552,7 @@ extern "C" {
 
 int isx_homography_release(void) ISX_ENTRY {
     clear_error();
-    return hg_release(per_thread<HgScratch>());
+    return per_thread<HgScratch>().release();
 } ISX_EXIT("isx_homography_release")
 
 int isx_find_homography(int num_pairs, const isx_mat* points, const isx_mat* counts, double reproj_thresh, int max_iters, double confidence,
@@ -614,24 +571,22 @@ int isx_find_homography(int num_pairs, const isx_mat* points, const isx_mat* cou
     if (reproj_thresh <= 0) reproj_thresh = 3;                                                                                   // R:636
     bool any_host_out = false, any_host_mask = false;
     if (num_pairs > 0) {
-        ISX_TRY(hg_check_mat(*counts, ISX_32SC1, 1, num_pairs, 4, device, who, "counts", 0));
-        ISX_TRY(hg_check_mat(*H, ISX_64FC1, 3ll * num_pairs, 3, 8, device, who, "H", 0));
-        ISX_TRY(hg_check_mat(*stats, ISX_32SC1, num_pairs, 8, 4, device, who, "stats", 0));
-        ISX_TRY(hg_check_mat(*conf, ISX_64FC1, 1, num_pairs, 8, device, who, "conf", 0));
+        ISX_TRY(check_mat_holds(*counts, ISX_32SC1, 1, num_pairs, 4, STOP_NO_ROW_PRESENT, device, who, "counts", 0));
+        ISX_TRY(check_mat_holds(*H, ISX_64FC1, 3ll * num_pairs, 3, 8, STOP_NO_ROW_PRESENT, device, who, "H", 0));
+        ISX_TRY(check_mat_holds(*stats, ISX_32SC1, num_pairs, 8, 4, STOP_NO_ROW_PRESENT, device, who, "stats", 0));
+        ISX_TRY(check_mat_holds(*conf, ISX_64FC1, 1, num_pairs, 8, STOP_NO_ROW_PRESENT, device, who, "conf", 0));
         any_host_out = H->device < 0 || stats->device < 0 || conf->device < 0;
     }
     for (int p = 0; p < num_pairs; ++p) {
         ISX_CHECK_ARG(points[p].rows >= 0 && inlier_masks[p].rows >= 0, ISX_ERR_INVALID, "%s: pair %d: negative rows", who, p);
-        ISX_TRY(hg_check_mat(points[p], ISX_32FC1, 0, 4, 4, device, who, "points", p));
-        ISX_TRY(hg_check_mat(inlier_masks[p], ISX_8UC1, 0, 1, 1, device, who, "inlier_masks", p));
+        ISX_TRY(check_mat_holds(points[p], ISX_32FC1, 0, 4, 4, STOP_NO_ROW_PRESENT, device, who, "points", p));
+        ISX_TRY(check_mat_holds(inlier_masks[p], ISX_8UC1, 0, 1, 1, STOP_NO_ROW_PRESENT, device, who, "inlier_masks", p));
         any_host_mask |= inlier_masks[p].device < 0 && inlier_masks[p].rows > 0 && points[p].rows > 0;
     }
     any_host_out |= any_host_mask;
     ISX_HIP(hipSetDevice(device));
     hipStream_t st = (hipStream_t)hip_stream;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    ISX_HIP(hipStreamIsCapturing(st, &cs));
-    ISX_CHECK_ARG(cs == hipStreamCaptureStatusNone, ISX_ERR_STATE, "%s: the stream is capturing (the call uploads its tables and may stage host mats)", who);
+    ISX_TRY(refuse_capture(st, who, "the call uploads its tables and may stage host mats"));
     if (num_pairs == 0) {
         if (info) { info[0] = 0; info[1] = 0; }
         return ISX_OK;
@@ -665,24 +620,13 @@ int isx_find_homography(int num_pairs, const isx_mat* points, const isx_mat* cou
         if (cap[p] > 0 && inlier_masks[p].device < 0) o_mask[p] = lay.take((size_t)cap[p]);
 
     HgScratch& s = per_thread<HgScratch>();
-    if (s.device != device) { ISX_TRY(hg_release(s)); s.device = device; s.lds_set = false; }
-    ISX_TRY(hg_wait_upload(s));                                   // the previous call's upload has read `pin`
-    ISX_TRY(s.work.reserve(lay.at));
-    if (s.pin_cap < upload_bytes) {
-        if (s.pin) { ISX_HIP(hipHostFree(s.pin)); s.pin = nullptr; s.pin_cap = 0; }
-        const size_t want = std::max<size_t>(upload_bytes + upload_bytes / 2, 1u << 16);
-        ISX_HIP(hipHostMalloc(&s.pin, want, hipHostMallocDefault));
-        s.pin_cap = want;
-    }
-    if (!s.uploaded) ISX_HIP(hipEventCreateWithFlags(&s.uploaded, hipEventDisableTiming));
-    if (!s.done) ISX_HIP(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-    if (!s.lds_set) {
+    if (s.device != device || !s.lds_set) {                       // before begin(), so before this stream is made to wait for another
         ISX_HIP(hipFuncSetAttribute((const void*)k_hg_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, HG_LDS_BYTES));
         s.lds_set = true;
     }
-    if (s.ran && s.last != st) ISX_HIP(hipStreamWaitEvent(st, s.done, 0));
+    ISX_TRY(s.begin(device, st, lay.at, upload_bytes));
     char* const dev = (char*)s.work.p;
-    char* const pin = (char*)s.pin;
+    char* const pin = (char*)s.pin.p;
 
     // ---- fill the upload ----
     for (int p = 0; p < num_pairs; ++p) {
@@ -705,9 +649,7 @@ int isx_find_homography(int num_pairs, const isx_mat* points, const isx_mat* cou
     }
     std::memcpy(pin + o_prs, prs.data(), prs.size() * sizeof(HgPair));
     if (h_counts) std::memcpy(pin + o_counts, h_counts, (size_t)num_pairs * 4);
-    ISX_HIP(hipMemcpyAsync(dev, pin, upload_bytes, hipMemcpyHostToDevice, st));
-    ISX_HIP(hipEventRecord(s.uploaded, st));
-    s.pending = true;
+    ISX_TRY(s.upload(st, upload_bytes));
 
     // ---- one launch ----
     HgCall c;
@@ -721,8 +663,7 @@ int isx_find_homography(int num_pairs, const isx_mat* points, const isx_mat* cou
     c.thresh = reproj_thresh; c.confidence = confidence;
     c.max_iters = max_iters; c.thresh1 = num_matches_thresh1; c.thresh2 = num_matches_thresh2;
     ISX_LAUNCH("homography_pairs", (double)num_pairs * 4096.0, st, k_hg_pairs, dim3((unsigned)num_pairs), dim3(HG_CHUNK), HG_LDS_BYTES, c);
-    ISX_HIP(hipEventRecord(s.done, st));
-    s.last = st; s.ran = true;
+    ISX_TRY(s.ran(st));
 
     // ---- host outputs ----
     if (any_host_out) {
@@ -734,15 +675,15 @@ int isx_find_homography(int num_pairs, const isx_mat* points, const isx_mat* cou
             ISX_HIP(hipStreamSynchronize(st));
             cnt = cnt_tmp.data();
         }
-        if (H->device < 0) ISX_HIP(hipMemcpy2DAsync(H->data, H->step, dev + o_H, 24, 24, (size_t)3 * num_pairs, hipMemcpyDeviceToHost, st));
-        if (stats->device < 0) ISX_HIP(hipMemcpy2DAsync(stats->data, stats->step, dev + o_stats, 32, 32, (size_t)num_pairs, hipMemcpyDeviceToHost, st));
+        if (H->device < 0) ISX_TRY(copy_rows_back(*H, dev + o_H, 3ll * num_pairs, 24, st));
+        if (stats->device < 0) ISX_TRY(copy_rows_back(*stats, dev + o_stats, num_pairs, 32, st));
         if (conf->device < 0) ISX_HIP(hipMemcpyAsync(conf->data, dev + o_conf, (size_t)num_pairs * 8, hipMemcpyDeviceToHost, st));
         for (int p = 0; p < num_pairs; ++p) {
             const isx_mat& mm = inlier_masks[p];
             if (cap[p] == 0 || mm.device >= 0) continue;
             const int n = std::min(std::max(cnt[p], 0), cap[p]);
             if (n < num_matches_thresh1 || n == 0) continue;      // R:836: the mask is not written
-            ISX_HIP(hipMemcpy2DAsync(mm.data, mm.step, dev + o_mask[p], 1, 1, (size_t)n, hipMemcpyDeviceToHost, st));
+            ISX_TRY(copy_rows_back(mm, dev + o_mask[p], n, 1, st));
         }
         ISX_HIP(hipStreamSynchronize(st));
     }

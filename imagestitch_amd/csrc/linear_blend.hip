@@ -10,6 +10,7 @@
 // oracle documents; all in-bounds arithmetic is literal (the ramp expressions are double).
 #include "isx_device.hpp"
 #include "pairwise.hpp"
+#include "scratch.hpp"
 
 #include <algorithm>
 
@@ -298,15 +299,20 @@ int isx_blend_pair_linear(const isx_mat* images1, const isx_mat* images2, int tl
     DevBuf& scratch = ls.buf;
     const int nchunks = std::max(cdiv(g.iHe - 1, SEAM_ROWS), 1);
     const int half_ibr = g.iBr / 2;
-    size_t cost_b = ((size_t)g.iHe * cw * 4 + 255) & ~(size_t)255, seam_b = ((size_t)g.iHe * 4 + 255) & ~(size_t)255,
-           m_b = ((size_t)g.height * mw * 4 + 255) & ~(size_t)255, maps_b = (((size_t)nchunks * cw + 255) & ~(size_t)255) + 256, entry_b = ((size_t)nchunks * 4 + 255) & ~(size_t)255;
-    ISX_TRY(scratch.reserve(cost_b + seam_b + 2 * m_b + maps_b + entry_b));
-    float* costV = (float*)scratch.p;
-    int* seam = (int*)((char*)scratch.p + cost_b);
-    float* m1 = (float*)((char*)scratch.p + cost_b + seam_b);
-    float* m2 = (float*)((char*)m1 + m_b);
-    signed char* maps = (signed char*)((char*)m2 + m_b);
-    int* entry = (int*)((char*)maps + maps_b);
+    Bump lay;
+    const size_t o_cost = lay.take((size_t)g.iHe * cw * 4), o_seam = lay.take((size_t)g.iHe * 4);
+    const size_t o_m1 = lay.take((size_t)g.height * mw * 4), o_m2 = lay.take((size_t)g.height * mw * 4);
+    const size_t o_maps = lay.take((size_t)nchunks * cw);
+    lay.take(256);                                                     // the maps keep the 256 bytes they always had past their rounded size
+    const size_t o_entry = lay.take((size_t)nchunks * 4);
+    ISX_TRY(scratch.reserve(lay.at));
+    char* const base = (char*)scratch.p;
+    float* costV = (float*)(base + o_cost);
+    int* seam = (int*)(base + o_seam);
+    float* m1 = (float*)(base + o_m1);
+    float* m2 = (float*)(base + o_m2);
+    signed char* maps = (signed char*)(base + o_maps);
+    int* entry = (int*)(base + o_entry);
     const unsigned char* i1 = (const unsigned char*)s1.d.data;
     const unsigned char* i2 = (const unsigned char*)s2.d.data;
     // algorithmic bytes of the launches (bench.py --a13): every input read once, every output written once

@@ -19,6 +19,7 @@
 //                  this row with that neighbour", compacts in order with a ballot prefix scan and writes matches, points and the count.
 #include "isx_device.hpp"
 #include "pairwise.hpp"
+#include "scratch.hpp"
 
 using namespace isx;
 using namespace isxd;
@@ -180,57 +181,7 @@ __global__ __launch_bounds__(MT_FIN_NT) void k_mt_finalise(const MtPair* __restr
     if (t == 0) *as_global(P.count) = base;
 }
 
-struct MtScratch {
-    DevBuf work;
-    int device = -1;
-    void* pin = nullptr;                 // the upload: tables, staged keypoints and packed descriptors of host mats
-    size_t pin_cap = 0;
-    hipEvent_t uploaded = nullptr;       // recorded after the upload that reads `pin`
-    bool pending = false;
-    hipEvent_t done = nullptr;           // recorded after the last kernel: a call on another stream waits for it before it reuses `work`
-    hipStream_t last = nullptr;
-    bool ran = false;
-};
-
-int mt_wait_upload(MtScratch& s) {
-    if (s.pending) { ISX_HIP(hipEventSynchronize(s.uploaded)); s.pending = false; }
-    return ISX_OK;
-}
-int mt_release(MtScratch& s) {
-    ISX_TRY(mt_wait_upload(s));
-    if (s.uploaded) { ISX_HIP(hipEventDestroy(s.uploaded)); s.uploaded = nullptr; }
-    if (s.done) { ISX_HIP(hipEventDestroy(s.done)); s.done = nullptr; }
-    s.ran = false;
-    if (s.pin) { ISX_HIP(hipHostFree(s.pin)); s.pin = nullptr; s.pin_cap = 0; }
-    s.work.release();
-    s.device = -1;
-    return ISX_OK;
-}
-
-struct Bump {                            // offsets into one buffer, 256-byte aligned
-    size_t at = 0;
-    size_t take(size_t bytes) { const size_t o = at; at += (bytes + 255) & ~(size_t)255; return o; }
-};
-
-// an output mat of at least rows x cols elements of 4 bytes; null data is fine where no row is needed
-int mt_check_out(const isx_mat& m, int type, long long rows, int cols, int device, const char* who, const char* what, int index) {
-    ISX_CHECK_ARG(m.type == type, ISX_ERR_TYPE, "%s: %s %d is %s (%s)", who, what, index, type_name(m.type), type_name(type));
-    ISX_CHECK_ARG(m.rows >= rows && (rows == 0 || m.cols >= cols), ISX_ERR_SIZE, "%s: %s %d is %d x %d, the call needs %lld x %d", who, what, index,
-                  m.rows, m.cols, rows, cols);
-    if (rows == 0) return ISX_OK;
-    ISX_CHECK_ARG(m.data != nullptr, ISX_ERR_INVALID, "%s: %s %d has a null data pointer", who, what, index);
-    ISX_CHECK_ARG(m.step >= (size_t)m.cols * 4 || m.rows == 1, ISX_ERR_INVALID, "%s: %s %d: step %zu smaller than a row", who, what, index, m.step);
-    ISX_CHECK_ARG(((uintptr_t)m.data & 3) == 0 && (m.step & 3) == 0, ISX_ERR_INVALID, "%s: %s %d is not 4-byte aligned in pointer and step", who, what, index);
-    ISX_CHECK_ARG(m.device < 0 || m.device == device, ISX_ERR_INVALID, "%s: %s %d lives on device %d, the call runs on %d", who, what, index, m.device, device);
-    return ISX_OK;
-}
-
-// a host output mat's rows [0, rows) x cols elements, back from its dense staged copy
-int mt_copy_back(const isx_mat& m, const void* staged, int rows, int cols, hipStream_t st) {
-    if (rows <= 0) return ISX_OK;
-    ISX_HIP(hipMemcpy2DAsync(m.data, m.step, staged, (size_t)cols * 4, (size_t)cols * 4, (size_t)rows, hipMemcpyDeviceToHost, st));
-    return ISX_OK;
-}
+struct MtScratch : UploadScratch {};      // pin: the tables, staged keypoints and packed descriptors of host mats (scratch.hpp)
 
 }  // namespace
 
@@ -238,7 +189,7 @@ extern "C" {
 
 int isx_match_release(void) ISX_ENTRY {
     clear_error();
-    return mt_release(per_thread<MtScratch>());
+    return per_thread<MtScratch>().release();
 } ISX_EXIT("isx_match_release")
 
 int isx_match_features(int num_images, const isx_mat* descriptors, const isx_mat* keypoints, const int* image_sizes_wh,
@@ -287,7 +238,7 @@ int isx_match_features(int num_images, const isx_mat* descriptors, const isx_mat
     int searched = 0;
     bool any_host_out = false;
     if (num_pairs > 0) {
-        ISX_TRY(mt_check_out(*counts, ISX_32SC1, 1, num_pairs, device, who, "counts", 0));
+        ISX_TRY(check_mat_holds(*counts, ISX_32SC1, 1, num_pairs, 4, STOP_NO_ROW_WANTED, device, who, "counts", 0));
         any_host_out |= counts->device < 0;
     }
     for (int p = 0; p < num_pairs; ++p) {
@@ -295,23 +246,21 @@ int isx_match_features(int num_images, const isx_mat* descriptors, const isx_mat
         const bool run = nf > 0 && nt > 0;
         const long long rows = run ? (long long)nf + nt : 0;
         searched += run;
-        ISX_TRY(mt_check_out(matches[p], ISX_32SC1, rows, 3, device, who, "matches", p));
+        ISX_TRY(check_mat_holds(matches[p], ISX_32SC1, rows, 3, 4, STOP_NO_ROW_WANTED, device, who, "matches", p));
         any_host_out |= run && matches[p].device < 0;
         if (points) {
-            ISX_TRY(mt_check_out(points[p], ISX_32FC1, rows, 4, device, who, "points", p));
+            ISX_TRY(check_mat_holds(points[p], ISX_32FC1, rows, 4, 4, STOP_NO_ROW_WANTED, device, who, "points", p));
             any_host_out |= run && points[p].device < 0;
         }
         if (knn)
             for (int d = 0; d < 2; ++d) {
-                ISX_TRY(mt_check_out(knn[2 * p + d], ISX_32SC1, run ? (d ? nt : nf) : 0, 4, device, who, "knn", 2 * p + d));
+                ISX_TRY(check_mat_holds(knn[2 * p + d], ISX_32SC1, run ? (d ? nt : nf) : 0, 4, 4, STOP_NO_ROW_WANTED, device, who, "knn", 2 * p + d));
                 any_host_out |= run && knn[2 * p + d].device < 0;
             }
     }
     ISX_HIP(hipSetDevice(device));
     hipStream_t st = (hipStream_t)hip_stream;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    ISX_HIP(hipStreamIsCapturing(st, &cs));
-    ISX_CHECK_ARG(cs == hipStreamCaptureStatusNone, ISX_ERR_STATE, "%s: the stream is capturing (the call uploads its tables and may stage host mats)", who);
+    ISX_TRY(refuse_capture(st, who, "the call uploads its tables and may stage host mats"));
     if (num_pairs == 0) {
         if (info) { info[0] = 0; info[1] = 0; }
         return ISX_OK;
@@ -383,20 +332,9 @@ int isx_match_features(int num_images, const isx_mat* descriptors, const isx_mat
     }
 
     MtScratch& s = per_thread<MtScratch>();
-    if (s.device != device) { ISX_TRY(mt_release(s)); s.device = device; }
-    ISX_TRY(mt_wait_upload(s));                                   // the previous call's upload has read `pin`
-    ISX_TRY(s.work.reserve(lay.at));
-    if (s.pin_cap < upload_bytes) {
-        if (s.pin) { ISX_HIP(hipHostFree(s.pin)); s.pin = nullptr; s.pin_cap = 0; }
-        const size_t want = std::max<size_t>(upload_bytes + upload_bytes / 2, 1u << 16);
-        ISX_HIP(hipHostMalloc(&s.pin, want, hipHostMallocDefault));
-        s.pin_cap = want;
-    }
-    if (!s.uploaded) ISX_HIP(hipEventCreateWithFlags(&s.uploaded, hipEventDisableTiming));
-    if (!s.done) ISX_HIP(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-    if (s.ran && s.last != st) ISX_HIP(hipStreamWaitEvent(st, s.done, 0));
+    ISX_TRY(s.begin(device, st, lay.at, upload_bytes));
     char* const dev = (char*)s.work.p;
-    char* const pin = (char*)s.pin;
+    char* const pin = (char*)s.pin.p;
 
     // ---- fill the upload ----
     for (int i = 0; i < num_images; ++i) {
@@ -435,9 +373,7 @@ int isx_match_features(int num_images, const isx_mat* descriptors, const isx_mat
     std::memcpy(pin + o_prs, prs.data(), prs.size() * sizeof(MtPair));
     std::memcpy(pin + o_work, work.data(), work.size() * sizeof(int4));
     std::memcpy(pin + o_pblk, pack_blocks.data(), pack_blocks.size() * sizeof(int2));
-    ISX_HIP(hipMemcpyAsync(dev, pin, upload_bytes, hipMemcpyHostToDevice, st));
-    ISX_HIP(hipEventRecord(s.uploaded, st));
-    s.pending = true;
+    ISX_TRY(s.upload(st, upload_bytes));
 
     // ---- at most three launches ----
     const MtImage* d_imgs = (const MtImage*)(dev + o_imgs);
@@ -457,8 +393,7 @@ int isx_match_features(int num_images, const isx_mat* descriptors, const isx_mat
     ISX_LAUNCH("match_finalise", (double)part_count * 8.0, st, k_mt_finalise, dim3((unsigned)num_pairs), dim3(MT_FIN_NT), 0, d_prs, d_imgs,
                (const uint2*)(dev + o_part), (int*)(dev + o_acc), k);
     ++launches;
-    ISX_HIP(hipEventRecord(s.done, st));
-    s.last = st; s.ran = true;
+    ISX_TRY(s.ran(st));
 
     // ---- host outputs: the counts first, then the rows they name ----
     if (any_host_out) {
@@ -476,11 +411,11 @@ int isx_match_features(int num_images, const isx_mat* descriptors, const isx_mat
         for (int p = 0; p < num_pairs; ++p) {
             const int nf = imgs[prs[p].from].rows, nt = imgs[prs[p].to].rows;
             if (nf == 0 || nt == 0) continue;
-            if (matches[p].device < 0) ISX_TRY(mt_copy_back(matches[p], dev + o_m[p], cnt[p], 3, st));
-            if (points && points[p].device < 0) ISX_TRY(mt_copy_back(points[p], dev + o_p[p], cnt[p], 4, st));
+            if (matches[p].device < 0) ISX_TRY(copy_rows_back(matches[p], dev + o_m[p], cnt[p], 12, st));
+            if (points && points[p].device < 0) ISX_TRY(copy_rows_back(points[p], dev + o_p[p], cnt[p], 16, st));
             if (knn)
                 for (int d = 0; d < 2; ++d)
-                    if (knn[2 * p + d].device < 0) ISX_TRY(mt_copy_back(knn[2 * p + d], dev + o_k[2 * p + d], d ? nt : nf, 4, st));
+                    if (knn[2 * p + d].device < 0) ISX_TRY(copy_rows_back(knn[2 * p + d], dev + o_k[2 * p + d], d ? nt : nf, 16, st));
         }
         ISX_HIP(hipStreamSynchronize(st));
     }

@@ -6,6 +6,7 @@
 // Both kernels are byte-bound: a lane owns four adjacent output pixels of a row and stores them as whole dwords, no LDS.
 #include "isx_device.hpp"
 #include "isx_internal.hpp"
+#include "scratch.hpp"
 #include "resize_taps.hpp"
 
 #include <algorithm>
@@ -220,9 +221,9 @@ __global__ __launch_bounds__(256) void k_dilate_resize_and(const unsigned char* 
 
 // nothing may synchronise on a capturing stream, and staging a host mat does
 int no_host_mats_while_capturing(hipStream_t st, bool any_host, const char* who) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    ISX_HIP(hipStreamIsCapturing(st, &cs));
-    ISX_CHECK_ARG(cs == hipStreamCaptureStatusNone || !any_host, ISX_ERR_STATE, "%s: the stream is capturing and a mat is a host mat (staging it synchronises)", who);
+    bool capturing = false;
+    ISX_TRY(is_capturing(st, capturing));
+    ISX_CHECK_ARG(!capturing || !any_host, ISX_ERR_STATE, "%s: the stream is capturing and a mat is a host mat (staging it synchronises)", who);
     return ISX_OK;
 }
 int not_empty(const isx_mat* m, const char* what) {

@@ -10,6 +10,7 @@
 // A labels_ read outside the union counts as "not this component" (the reference reads past the row, S:763).
 #include "isx_device.hpp"
 #include "pairwise.hpp"
+#include "scratch.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -394,23 +395,25 @@ int isx_seam_estimate_cost(const isx_mat* image1, const isx_mat* image2, int tl1
     g.uh = labels->rows; g.uw = labels->cols; g.label = label;
     g.rx = rx; g.ry = ry; g.rw = rw; g.rh = rh; g.dx1 = dx1; g.dy1 = dy1; g.dx2 = dx2; g.dy2 = dy2;
     DevBuf& scratch = ss.scratch;
-    const size_t cv_b = ((size_t)rh * (rw + 1) * 4 + 255) & ~(size_t)255, ch_b = ((size_t)(rh + 1) * rw * 4 + 255) & ~(size_t)255,
-                 ct_b = ((size_t)rh * rw + 255) & ~(size_t)255;
     const int first = (horiz ? sx : sy) + 1, nsteps = std::max((horiz ? dx : dy) - first + 1, 0);
-    const size_t ra_b = ((size_t)std::max(nsteps, 1) * n * 16 + 255) & ~(size_t)255, rb_b = ((size_t)std::max(nsteps, 1) * n * 8 + 255) & ~(size_t)255;
-    const size_t gl_b = lds_fits ? 0 : (((size_t)n * 10 + 255) & ~(size_t)255);
-    ISX_TRY(scratch.reserve(cv_b + ch_b + ct_b + 256 + ra_b + rb_b + gl_b));
-    float* costV = (float*)scratch.p;
-    float* costH = (float*)((char*)scratch.p + cv_b);
-    unsigned char* control = (unsigned char*)scratch.p + cv_b + ch_b;
-    int* found = (int*)(control + ct_b);
-    float4* ra = (float4*)((char*)found + 256);
-    float2* rb = (float2*)((char*)ra + ra_b);
+    Bump lay;
+    const size_t o_cv = lay.take((size_t)rh * (rw + 1) * 4), o_ch = lay.take((size_t)(rh + 1) * rw * 4), o_ct = lay.take((size_t)rh * rw);
+    const size_t o_found = lay.take(256);                              // one int
+    const size_t o_ra = lay.take((size_t)std::max(nsteps, 1) * n * 16), o_rb = lay.take((size_t)std::max(nsteps, 1) * n * 8);
+    const size_t o_gl = lds_fits ? 0 : lay.take((size_t)n * 10);       // the global route's state: 8 n bytes of cost, 2 n of reachability
+    ISX_TRY(scratch.reserve(lay.at));
+    char* const base = (char*)scratch.p;
+    float* costV = (float*)(base + o_cv);
+    float* costH = (float*)(base + o_ch);
+    unsigned char* control = (unsigned char*)base + o_ct;
+    int* found = (int*)(base + o_found);
+    float4* ra = (float4*)(base + o_ra);
+    float2* rb = (float2*)(base + o_rb);
     dim3 grid(cdiv(rw + 1, 64), cdiv(rh + 1, 4));
     const double cbytes = (double)rw * rh * ((image1->type == ISX_8UC3 ? 6.0 : 24.0) + 4.0 + 8.0);
     SeamGrad gr{nullptr, nullptr, nullptr, nullptr};
     if (cost_func == ISX_DP_COLOR_GRAD) {   // computeGradients S:398-399, S:549-572: here per estimateSeam, over what this component's costs can read
-        const size_t gn = (size_t)(rw + 2) * (rh + 2), gm_b = (gn * 4 + 255) & ~(size_t)255;
+        const size_t gn = (size_t)(rw + 2) * (rh + 2), gm_b = round256(gn * 4);
         ISX_TRY(ss.grad.reserve(4 * gm_b));
         float* gm[4];
         for (int i = 0; i < 4; ++i) gm[i] = (float*)((char*)ss.grad.p + i * gm_b);
@@ -432,7 +435,7 @@ int isx_seam_estimate_cost(const isx_mat* image1, const isx_mat* image2, int tl1
         ISX_LAUNCH("seam_pack", (double)nsteps * n * 48.0, st, k_seam_pack, dim3(cdiv(n, 256), nsteps), dim3(256), 0, g, (const float*)costV, (const float*)costH,
                    horiz ? 1 : 0, first, nsteps, n, ra, rb);
     if (!lds_fits) {
-        float* gcost = (float*)((char*)rb + rb_b);
+        float* gcost = (float*)(base + o_gl);
         unsigned char* greach = (unsigned char*)gcost + (size_t)8 * n;
         ISX_LAUNCH("seam_dp", (double)nsteps * n * 25.0, st, k_seam_dp_global, dim3(1), dim3(SEAM_NT), 0, (const float4*)ra, (const float2*)rb, rw, n, horiz ? 1 : 0,
                    sx, sy, dx, dy, control, found, gcost, greach);

@@ -21,6 +21,7 @@
 // order on one stream.  Every device loop has a trip count fixed by the kernel's arguments.
 #include "isx_device.hpp"
 #include "pairwise.hpp"
+#include "scratch.hpp"
 
 using namespace isx;
 using namespace isxd;
@@ -239,7 +240,7 @@ struct VrScratch {
 
 inline size_t vr_map_bytes(int rw, int rh) {
     const int hp = rh + 2 * VR_GAP, wp = rw + 2 * VR_GAP;
-    return (((size_t)hp * ((wp + 3) & ~3) * sizeof(int)) + 255) & ~(size_t)255;
+    return round256((size_t)hp * ((wp + 3) & ~3) * sizeof(int));
 }
 inline size_t vr_bytes(int rw, int rh) {
     const int hp = rh + 2 * VR_GAP;
@@ -314,9 +315,8 @@ int isx_voronoi_seam_find(int num_images, const int* sizes_wh, const int* corner
         }
     ISX_HIP(hipSetDevice(device));
     hipStream_t st = (hipStream_t)hip_stream;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    ISX_HIP(hipStreamIsCapturing(st, &cs));
-    const bool capturing = cs != hipStreamCaptureStatusNone;
+    bool capturing = false;
+    ISX_TRY(is_capturing(st, capturing));
     VrScratch& s = per_thread<VrScratch>();
     if (capturing) {
         ISX_CHECK_ARG(!any_host, ISX_ERR_STATE, "%s: the stream is capturing and a mask is a host mat (staging it synchronises)", who);
