@@ -4,9 +4,11 @@
 //                           RANSACPointSetRegistrator1::run R:139-233, HomographyEstimatorCallback R:253-402), the degenerate-H test,
 //                           num_inliers and confidence (R:863-878), the second run on the inliers (R:881-909).  The Levenberg-Marquardt
 //                           polish of R:672 is not run.
+//   isx_find_homography_lm  the same with the polish (createLMSolver1(HomographyRefineCallback(src, dst), 10)->run(H8), R:404-591) over the
+//                           inliers of both passes: the second instantiation of the kernel, opt-in, its OpenCV calls restated (unpinned)
 //   isx_homography_release  returns the per-thread scratch
 //
-// The specification is tests/helpers/homography_np.py (DESIGN.md §8 "Homography"): float64 in + - * / sqrt only, every sum in the order of
+// The specification is tests/helpers/homography_np.py, with tests/helpers/homography_lm_np.py for the polish (DESIGN.md §8 "Homography"): float64 in + - * / sqrt only, every sum in the order of
 // its loop, the float32 of computeError as written; cv::eigen (JacobiImpl_), cv::RNG, haveCollinearPoints and cvRound are restated there.
 // `nmodels = cb->runKernel(ms1, ms2, model)`, which R lost between R:196 and R:197, is in place.
 //
@@ -63,6 +65,7 @@ struct HgCall {
     double* conf;
     double thresh, confidence;
     int max_iters, thresh1, thresh2;
+    int lm_max_iters;                             // k_hg_pairs<true> only: maxIters of the LM solver (10 at R:672)
 };
 
 template <class T>
@@ -90,9 +93,10 @@ __device__ __forceinline__ double hg_hypot(double a, double b) {
     return 0.0;
 }
 
-// JacobiImpl_ on the lane's column of the LDS state, n = 9; A and W are set.  Leaves W sorted descending with the rows of V.
+// JacobiImpl_ on the lane's column of the LDS state, n x n (9 for runKernel, 8 for the LM solve: the elements are [r * n + c][lane]); A is
+// set.  Leaves W sorted descending with the rows of V.
+template <int n>
 __device__ __forceinline__ void hg_jacobi(const HgLds& s, int lane) {
-    constexpr int n = 9;
 #define HA(r, c) s.A[((r) * n + (c)) * WAVE + lane]
 #define HV(r, c) s.V[((r) * n + (c)) * WAVE + lane]
 #define HW(r) s.W[(r) * WAVE + lane]
@@ -252,7 +256,7 @@ __device__ bool hg_run_kernel_lane(const HgLds& s, int lane, const float (&q)[4]
 #pragma unroll
             for (int k = j; k < 9; ++k, ++e) s.A[(j * 9 + k) * WAVE + lane] = acc[e];
     }
-    hg_jacobi(s, lane);
+    hg_jacobi<9>(s, lane);
     hg_denormalise(s, lane, inv, hn2, H);
     return true;
 }
@@ -291,7 +295,7 @@ __device__ bool hg_run_kernel_wave(const HgLds& s, int lane, const float* pts, l
     __syncthreads();
     if (lane < 45) s.A[(j * 9 + k) * WAVE + 0] = acc;     // lane 0's column
     __syncthreads();
-    if (lane == 0) hg_jacobi(s, 0);
+    if (lane == 0) hg_jacobi<9>(s, 0);
     __syncthreads();
     hg_denormalise(s, 0, inv, hn2, H);
     return true;
@@ -367,13 +371,214 @@ struct HgRun {
     double H[9];
     int inliers;        // rows compacted into `work`
     int iters, win, attempts;
+    int lm_ret, lm_nfj; // LM only: run()'s return value and nfJ (R:580, R:491), 0 where it did not run
 };
 
-// findHomography2 (R:602-693, RANSAC, without R:672) by the whole wave; every field of the result is uniform.  mask (may be null) gets rows
-// [0, n); work gets the inliers in order, 4 floats a row.
+// ---- the Levenberg-Marquardt polish of R:672 (HomographyRefineCallback R:404-459, LMSolverImpl1::run R:473-581): k_hg_pairs<true> only ----
+// Its state lives in the Jacobi's LDS, which no hypothesis uses by then: column 0 of A / V / W / indR / indC is the 8 x 8 Jacobi (Ap of the
+// solve, A of the invert), column 1 of A is LM's A (8 x 8, mirrored), column 2 holds v, D, d, x, xd and the invert's maxval.  Nothing past
+// HG_LDS_BYTES is used.
+#define HG_LA(i, j) s.A[((i) * 8 + (j)) * WAVE + 1]
+#define HG_LX(off, i) s.A[((off) + (i)) * WAVE + 2]
+#define HG_JA(i, j) s.A[((i) * 8 + (j)) * WAVE]
+#define HG_JV(i, j) s.V[((i) * 8 + (j)) * WAVE]
+#define HG_JW(i) s.W[(i) * WAVE]
+constexpr int HG_LM_V = 0, HG_LM_D = 8, HG_LM_DD = 16, HG_LM_X = 24, HG_LM_XD = 32, HG_LM_MAXVAL = 40;
+
+__device__ __forceinline__ double hg_lm_jx(int i, double a, double b, double ww, double g6, double g7) {      // Jptr[i] of R:444-446
+    return i == 0 ? a : i == 1 ? b : i == 2 ? ww : i < 6 ? 0.0 : i == 6 ? g6 : g7;
+}
+__device__ __forceinline__ double hg_lm_jy(int i, double a, double b, double ww, double g6, double g7) {      // Jptr[8 + i] of R:447-449
+    return i < 3 ? 0.0 : i == 3 ? a : i == 4 ? b : i == 5 ? ww : i == 6 ? g6 : g7;
+}
+
+// compute (R:432-453) at the parameters HG_LX(xoff, .) over the m rows of `work`.  Every lane walks the rows in order and keeps
+// norm(err, NORM_L2SQR) (groups of four, then one by one) and norm(err, NORM_INF): both are uniform without a broadcast.  With J, lane
+// e < 36 also owns A[i][j] of mulTransposed(J, A, true) (i <= j, the upper triangle in row-major order) and lane 36 + i owns v[i] of
+// gemm(J, r, GEMM_1_T): each is one lane's sum over the rows 2p, 2p + 1 in order, zero products included, from +0.0.
+template <bool J>
+__device__ void hg_lm_eval(const HgLds& s, int lane, const float* work, int m, int xoff, double& S, double& rinf) {
+    double h[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) h[i] = HG_LX(xoff, i);
+    const bool isA = lane < 36, isV = lane >= 36 && lane < 44;
+    int i = 0, j = 0;
+    if (isA) {
+        j = lane;
+        while (j >= 8 - i) { j -= 8 - i; ++i; }
+        j += i;
+    } else if (isV) {
+        i = lane - 36;
+    }
+    double acc = 0.0, sum = 0.0, grp = 0.0, mx = 0.0;
+    for (int p = 0; p < m; ++p) {
+        const float* r = work + 4ll * p;
+        const double Mx = r[0], My = r[1];
+        double ww = (h[6] * Mx + h[7] * My) + 1.;
+        ww = fabs(ww) > DBL_EPSILON ? 1. / ww : 0.;
+        const double xi = ((h[0] * Mx + h[1] * My) + h[2]) * ww;
+        const double yi = ((h[3] * Mx + h[4] * My) + h[5]) * ww;
+        const double ex = xi - r[2], ey = yi - r[3];
+        if (p & 1) {
+            grp = (grp + ex * ex) + ey * ey;
+            sum = sum + grp;
+        } else if (p + 1 < m) {
+            grp = ex * ex + ey * ey;
+        } else {
+            sum = sum + ex * ex;
+            sum = sum + ey * ey;
+        }
+        if (mx < fabs(ex)) mx = fabs(ex);
+        if (mx < fabs(ey)) mx = fabs(ey);
+        if (J) {
+            const double a = Mx * ww, b = My * ww;
+            const double gx6 = (-a) * xi, gx7 = (-b) * xi, gy6 = (-a) * yi, gy7 = (-b) * yi;
+            const double jx = hg_lm_jx(i, a, b, ww, gx6, gx7), jy = hg_lm_jy(i, a, b, ww, gy6, gy7);
+            const double ox = isA ? hg_lm_jx(j, a, b, ww, gx6, gx7) : ex, oy = isA ? hg_lm_jy(j, a, b, ww, gy6, gy7) : ey;
+            acc = acc + jx * ox;
+            acc = acc + jy * oy;
+        }
+    }
+    S = sum; rinf = mx;
+    if (J) {
+        __syncthreads();
+        if (isA) { HG_LA(i, j) = acc; HG_LA(j, i) = acc; }
+        if (isV) HG_LX(HG_LM_V, i) = acc;
+        __syncthreads();
+    }
+}
+
+// lane 0: Jacobi at n = 8 on HG_JA and SVBkSb's threshold (sum of W) * 2 DBL_EPSILON
+__device__ __forceinline__ double hg_lm_eig(const HgLds& s) {
+    hg_jacobi<8>(s, 0);
+    double t = 0.0;
+    for (int e = 0; e < 8; ++e) t = t + HG_JW(e);
+    return t * (2.0 * DBL_EPSILON);
+}
+
+__device__ __forceinline__ double hg_lm_dot8(const double* a, const double* b) {      // a.dot(b): two groups of four
+    double r = 0.0;
+    r = r + (((a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]) + a[3] * b[3]);
+    r = r + (((a[4] * b[4] + a[5] * b[5]) + a[6] * b[6]) + a[7] * b[7]);
+    return r;
+}
+
+// LMSolverImpl1::run (R:476-580) on H[0..8) over the m rows of `work`, by the whole wave: the sums over the rows are hg_lm_eval's, the
+// 8 x 8 eigen-solves run on lane 0, and every lane computes the scalars (S, Sd, R, lambda, nu) from the same LDS values, so the control
+// flow is uniform without a broadcast.
+__device__ void hg_lm(const HgLds& s, int lane, const float* work, int m, double* H, int max_iters, int& ret, int& nfj) {
+    const double Rlo = 0.25, Rhi = 0.75, epsx = FLT_EPSILON, epsf = FLT_EPSILON;
+    __syncthreads();                                                  // the refit's readers of V are done
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) HG_LX(HG_LM_X, i) = H[i];
+    }
+    __syncthreads();
+    double S, rinf;
+    hg_lm_eval<true>(s, lane, work, m, HG_LM_X, S, rinf);
+    int nfJ = 2;
+    if (lane < 8) HG_LX(HG_LM_D, lane) = HG_LA(lane, lane);           // D = A.diag().clone(): taken once
+    __syncthreads();
+    double lambda = 1, lc = 0.75;
+    int iter = 0;
+    for (;;) {
+        if (lane == 0) {                                              // solve(Ap, v, d, DECOMP_EIG), xd = x - d
+            for (int i = 0; i < 8; ++i)
+                for (int j = 0; j < 8; ++j) HG_JA(i, j) = HG_LA(i, j);
+            for (int i = 0; i < 8; ++i) HG_JA(i, i) = HG_JA(i, i) + lambda * HG_LX(HG_LM_D, i);
+            const double t = hg_lm_eig(s);
+            for (int j = 0; j < 8; ++j) HG_LX(HG_LM_DD, j) = 0.0;
+            for (int e = 0; e < 8; ++e) {
+                const double w = HG_JW(e);
+                if (!(fabs(w) > t)) continue;
+                double sv = 0.0;
+                for (int j = 0; j < 8; ++j) sv = sv + HG_JV(e, j) * HG_LX(HG_LM_V, j);
+                sv = sv * (1.0 / w);
+                for (int j = 0; j < 8; ++j) HG_LX(HG_LM_DD, j) = HG_LX(HG_LM_DD, j) + sv * HG_JV(e, j);
+            }
+            for (int j = 0; j < 8; ++j) HG_LX(HG_LM_XD, j) = HG_LX(HG_LM_X, j) - HG_LX(HG_LM_DD, j);
+        }
+        __syncthreads();
+        double Sd, unused;
+        hg_lm_eval<false>(s, lane, work, m, HG_LM_XD, Sd, unused);
+        ++nfJ;
+        double d[8], v[8], td[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { d[i] = HG_LX(HG_LM_DD, i); v[i] = HG_LX(HG_LM_V, i); }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {                                 // gemm(A, d, -1, v, 2, temp_d)
+            double sv = 0.0;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) sv = sv + HG_LA(i, k) * d[k];
+            td[i] = (-sv) + 2.0 * v[i];
+        }
+        const double dS = hg_lm_dot8(d, td);
+        const double R = (S - Sd) / (fabs(dS) > DBL_EPSILON ? dS : 1);
+        if (R > Rhi) {
+            lambda *= 0.5;
+            if (lambda < lc) lambda = 0;
+        } else if (R < Rlo) {
+            const double t = hg_lm_dot8(d, v);
+            double nu = (Sd - S) / (fabs(t) > DBL_EPSILON ? t : 1) + 2;
+            nu = nu < 2. ? 2. : nu;
+            nu = 10. < nu ? 10. : nu;
+            if (lambda == 0) {                                        // invert(A, Ap, DECOMP_EIG): its diagonal alone is read
+                __syncthreads();
+                if (lane == 0) {
+                    for (int i = 0; i < 8; ++i)
+                        for (int j = 0; j < 8; ++j) HG_JA(i, j) = HG_LA(i, j);
+                    const double th = hg_lm_eig(s);
+                    double maxval = DBL_EPSILON;
+                    for (int i = 0; i < 8; ++i) {
+                        double sv = 0.0;
+                        for (int e = 0; e < 8; ++e) {
+                            const double w = HG_JW(e);
+                            if (fabs(w) > th) sv = sv + HG_JV(e, i) * (HG_JV(e, i) * (1.0 / w));
+                        }
+                        if (maxval < fabs(sv)) maxval = fabs(sv);
+                    }
+                    HG_LX(HG_LM_MAXVAL, 0) = maxval;
+                }
+                __syncthreads();
+                lambda = lc = 1. / HG_LX(HG_LM_MAXVAL, 0);
+                nu *= 0.5;
+            }
+            lambda *= nu;
+        }
+        if (Sd < S) {
+            ++nfJ;
+            S = Sd;
+            __syncthreads();
+            if (lane < 8) HG_LX(HG_LM_X, lane) = HG_LX(HG_LM_XD, lane);      // swap(x, xd): xd is written anew before it is read
+            __syncthreads();
+            hg_lm_eval<true>(s, lane, work, m, HG_LM_X, unused, rinf);
+        }
+        ++iter;
+        double dinf = 0.0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            if (dinf < fabs(d[i])) dinf = fabs(d[i]);
+        if (!(iter < max_iters && dinf >= epsx && rinf >= epsf)) break;
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) H[i] = HG_LX(HG_LM_X, i);
+    __syncthreads();                                                  // before the next user of the Jacobi's LDS
+    ret = iter == max_iters ? -iter : iter;
+    nfj = nfJ;
+}
+#undef HG_LA
+#undef HG_LX
+#undef HG_JA
+#undef HG_JV
+#undef HG_JW
+
+// findHomography2 (R:602-693, RANSAC; R:672 with LM only) by the whole wave; every field of the result is uniform.  mask (may be null) gets
+// rows [0, n); work gets the inliers in order, 4 floats a row.
+template <bool LM>
 __device__ void hg_find(const HgLds& s, int lane, const float* pts, long long step, int n, unsigned char* mask, long long mask_step, float* work,
                         const HgCall& c, HgRun& out) {
     out.ok = false; out.inliers = 0; out.iters = 0; out.win = -1; out.attempts = 0;
+    out.lm_ret = 0; out.lm_nfj = 0;
 #pragma unroll
     for (int i = 0; i < 9; ++i) out.H[i] = 0.0;
     const float t = (float)(c.thresh * c.thresh);
@@ -480,10 +685,17 @@ __device__ void hg_find(const HgLds& s, int lane, const float* pts, long long st
             if (!ok) out.inliers = 0;
             if (mask && lane < 4) mask[(long long)lane * mask_step] = ok ? 1 : 0;
         }
+        if constexpr (LM) {                                           // R:669-672: over the inliers, from the refit or the RANSAC model it left
+            if (!direct) hg_lm(s, lane, work, m, out.H, c.lm_max_iters, out.lm_ret, out.lm_nfj);
+        }
     }
 }
 
+// LM = false is isx_find_homography's kernel; LM = true adds the polish and stats columns 8 - 11 (isx_find_homography_lm).  A template, so
+// that the unrefined call carries none of the polish in registers or code.
+template <bool LM>
 __global__ __launch_bounds__(HG_CHUNK) void k_hg_pairs(HgCall c) {
+    constexpr int NST = LM ? 12 : 8;
     extern __shared__ __attribute__((aligned(16))) unsigned char hg_smem[];
     HgLds s;
     s.A = (double*)(hg_smem + HG_LDS_A); s.V = (double*)(hg_smem + HG_LDS_V); s.W = (double*)(hg_smem + HG_LDS_W);
@@ -498,7 +710,7 @@ __global__ __launch_bounds__(HG_CHUNK) void k_hg_pairs(HgCall c) {
     double Hout[9];
 #pragma unroll
     for (int i = 0; i < 9; ++i) Hout[i] = 0.0;
-    int st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int st[NST] = {};
     double conf = 0.0;
     if (n >= c.thresh1) {                                             // R:836
         float* const work_a = as_global(P.work_a);
@@ -506,9 +718,10 @@ __global__ __launch_bounds__(HG_CHUNK) void k_hg_pairs(HgCall c) {
         int num_inliers = 0;
         for (int pass = 0; pass < 2; ++pass) {
             HgRun r;
-            if (pass == 0) hg_find(s, lane, as_global(P.points), P.points_step, n, as_global(P.mask), P.mask_step, work_a, c, r);      // R:862
-            else hg_find(s, lane, work_a, 16, num_inliers, nullptr, 0, as_global(P.work_b), c, r);                                    // R:909
+            if (pass == 0) hg_find<LM>(s, lane, as_global(P.points), P.points_step, n, as_global(P.mask), P.mask_step, work_a, c, r);      // R:862
+            else hg_find<LM>(s, lane, work_a, 16, num_inliers, nullptr, 0, as_global(P.work_b), c, r);                                    // R:909
             st[2 + 2 * pass] = r.iters; st[3 + 2 * pass] = r.win; st[6] += r.attempts;
+            if constexpr (LM) { st[8 + 2 * pass] = r.lm_ret; st[9 + 2 * pass] = r.lm_nfj; }
 #pragma unroll
             for (int i = 0; i < 9; ++i) Hout[i] = r.ok ? r.H[i] : 0.0;
             if (pass == 1) {
@@ -533,33 +746,24 @@ __global__ __launch_bounds__(HG_CHUNK) void k_hg_pairs(HgCall c) {
         for (int i = 1; i < 9; ++i) v = lane == i ? Hout[i] : v;
         ((double*)((char*)as_global(c.H) + (3ll * p + lane / 3) * c.H_step))[lane % 3] = v;
     }
-    if (lane < 8) {
+    if (lane < NST) {
         int v = st[0];
 #pragma unroll
-        for (int i = 1; i < 8; ++i) v = lane == i ? st[i] : v;
+        for (int i = 1; i < NST; ++i) v = lane == i ? st[i] : v;
         ((int*)((char*)as_global(c.stats) + (long long)p * c.stats_step))[lane] = v;
     }
     if (lane == 0) as_global(c.conf)[p] = conf;
 }
 
 struct HgScratch : UploadScratch {       // pin: the table, host counts and the staged rows of host points mats (scratch.hpp)
-    bool lds_set = false;                // k_hg_pairs may use HG_LDS_BYTES of LDS on `device`
+    bool lds_set = false;                // both k_hg_pairs may use HG_LDS_BYTES of LDS on `device`
 };
 
-}  // namespace
-
-extern "C" {
-
-int isx_homography_release(void) ISX_ENTRY {
-    clear_error();
-    return per_thread<HgScratch>().release();
-} ISX_EXIT("isx_homography_release")
-
-int isx_find_homography(int num_pairs, const isx_mat* points, const isx_mat* counts, double reproj_thresh, int max_iters, double confidence,
-                        int num_matches_thresh1, int num_matches_thresh2, isx_mat* H, isx_mat* inlier_masks, isx_mat* stats, isx_mat* conf,
-                        int* info, int device, void* hip_stream) ISX_ENTRY {
-    clear_error();
-    const char* who = "find_homography";
+// The body of both entries.  lm: isx_find_homography_lm - k_hg_pairs<true>, 12 stats columns.
+int hg_call(bool lm, int lm_max_iters, const char* who, int num_pairs, const isx_mat* points, const isx_mat* counts, double reproj_thresh, int max_iters,
+            double confidence, int num_matches_thresh1, int num_matches_thresh2, isx_mat* H, isx_mat* inlier_masks, isx_mat* stats, isx_mat* conf,
+            int* info, int device, void* hip_stream) {
+    const int nst = lm ? 12 : 8;                                  // stats columns
     // ---- checks: all of them before anything is written or enqueued ----
     ISX_CHECK_ARG(num_pairs >= 0, ISX_ERR_INVALID, "%s: %d pairs", who, num_pairs);
     ISX_CHECK_ARG(num_pairs == 0 || (points && counts && H && inlier_masks && stats && conf), ISX_ERR_INVALID,
@@ -568,12 +772,13 @@ int isx_find_homography(int num_pairs, const isx_mat* points, const isx_mat* cou
     ISX_CHECK_ARG(max_iters >= 1, ISX_ERR_INVALID, "%s: max_iters %d", who, max_iters);
     ISX_CHECK_ARG(num_matches_thresh1 >= 0 && num_matches_thresh2 >= 0, ISX_ERR_INVALID, "%s: thresholds %d, %d", who, num_matches_thresh1, num_matches_thresh2);
     ISX_CHECK_ARG(reproj_thresh == reproj_thresh, ISX_ERR_INVALID, "%s: reproj_thresh is not a number", who);
+    ISX_CHECK_ARG(!lm || (lm_max_iters >= 1 && lm_max_iters <= 1000), ISX_ERR_INVALID, "%s: lm_max_iters %d is not in [1, 1000]", who, lm_max_iters);
     if (reproj_thresh <= 0) reproj_thresh = 3;                                                                                   // R:636
     bool any_host_out = false, any_host_mask = false;
     if (num_pairs > 0) {
         ISX_TRY(check_mat_holds(*counts, ISX_32SC1, 1, num_pairs, 4, STOP_NO_ROW_PRESENT, device, who, "counts", 0));
         ISX_TRY(check_mat_holds(*H, ISX_64FC1, 3ll * num_pairs, 3, 8, STOP_NO_ROW_PRESENT, device, who, "H", 0));
-        ISX_TRY(check_mat_holds(*stats, ISX_32SC1, num_pairs, 8, 4, STOP_NO_ROW_PRESENT, device, who, "stats", 0));
+        ISX_TRY(check_mat_holds(*stats, ISX_32SC1, num_pairs, nst, 4, STOP_NO_ROW_PRESENT, device, who, "stats", 0));
         ISX_TRY(check_mat_holds(*conf, ISX_64FC1, 1, num_pairs, 8, STOP_NO_ROW_PRESENT, device, who, "conf", 0));
         any_host_out = H->device < 0 || stats->device < 0 || conf->device < 0;
     }
@@ -614,14 +819,15 @@ int isx_find_homography(int num_pairs, const isx_mat* points, const isx_mat* cou
         o_wb[p] = lay.take((size_t)cap[p] * 16);
     }
     const size_t o_H = H->device < 0 ? lay.take((size_t)num_pairs * 72) : 0;
-    const size_t o_stats = stats->device < 0 ? lay.take((size_t)num_pairs * 32) : 0;
+    const size_t o_stats = stats->device < 0 ? lay.take((size_t)num_pairs * 4 * nst) : 0;
     const size_t o_conf = conf->device < 0 ? lay.take((size_t)num_pairs * 8) : 0;
     for (int p = 0; p < num_pairs; ++p)
         if (cap[p] > 0 && inlier_masks[p].device < 0) o_mask[p] = lay.take((size_t)cap[p]);
 
     HgScratch& s = per_thread<HgScratch>();
     if (s.device != device || !s.lds_set) {                       // before begin(), so before this stream is made to wait for another
-        ISX_HIP(hipFuncSetAttribute((const void*)k_hg_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, HG_LDS_BYTES));
+        ISX_HIP(hipFuncSetAttribute((const void*)k_hg_pairs<false>, hipFuncAttributeMaxDynamicSharedMemorySize, HG_LDS_BYTES));
+        ISX_HIP(hipFuncSetAttribute((const void*)k_hg_pairs<true>, hipFuncAttributeMaxDynamicSharedMemorySize, HG_LDS_BYTES));
         s.lds_set = true;
     }
     ISX_TRY(s.begin(device, st, lay.at, upload_bytes));
@@ -658,11 +864,13 @@ int isx_find_homography(int num_pairs, const isx_mat* points, const isx_mat* cou
     c.H = H->device < 0 ? (double*)(dev + o_H) : (double*)H->data;
     c.H_step = H->device < 0 ? 24 : (long long)H->step;
     c.stats = stats->device < 0 ? (int*)(dev + o_stats) : (int*)stats->data;
-    c.stats_step = stats->device < 0 ? 32 : (long long)stats->step;
+    c.stats_step = stats->device < 0 ? 4 * nst : (long long)stats->step;
     c.conf = conf->device < 0 ? (double*)(dev + o_conf) : (double*)conf->data;
     c.thresh = reproj_thresh; c.confidence = confidence;
     c.max_iters = max_iters; c.thresh1 = num_matches_thresh1; c.thresh2 = num_matches_thresh2;
-    ISX_LAUNCH("homography_pairs", (double)num_pairs * 4096.0, st, k_hg_pairs, dim3((unsigned)num_pairs), dim3(HG_CHUNK), HG_LDS_BYTES, c);
+    c.lm_max_iters = lm_max_iters;
+    if (lm) ISX_LAUNCH("homography_lm_pairs", (double)num_pairs * 4096.0, st, k_hg_pairs<true>, dim3((unsigned)num_pairs), dim3(HG_CHUNK), HG_LDS_BYTES, c);
+    else ISX_LAUNCH("homography_pairs", (double)num_pairs * 4096.0, st, k_hg_pairs<false>, dim3((unsigned)num_pairs), dim3(HG_CHUNK), HG_LDS_BYTES, c);
     ISX_TRY(s.ran(st));
 
     // ---- host outputs ----
@@ -676,7 +884,7 @@ int isx_find_homography(int num_pairs, const isx_mat* points, const isx_mat* cou
             cnt = cnt_tmp.data();
         }
         if (H->device < 0) ISX_TRY(copy_rows_back(*H, dev + o_H, 3ll * num_pairs, 24, st));
-        if (stats->device < 0) ISX_TRY(copy_rows_back(*stats, dev + o_stats, num_pairs, 32, st));
+        if (stats->device < 0) ISX_TRY(copy_rows_back(*stats, dev + o_stats, num_pairs, 4 * nst, st));
         if (conf->device < 0) ISX_HIP(hipMemcpyAsync(conf->data, dev + o_conf, (size_t)num_pairs * 8, hipMemcpyDeviceToHost, st));
         for (int p = 0; p < num_pairs; ++p) {
             const isx_mat& mm = inlier_masks[p];
@@ -689,6 +897,31 @@ int isx_find_homography(int num_pairs, const isx_mat* points, const isx_mat* cou
     }
     if (info) { info[0] = num_pairs; info[1] = 1; }
     return ISX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int isx_homography_release(void) ISX_ENTRY {
+    clear_error();
+    return per_thread<HgScratch>().release();
+} ISX_EXIT("isx_homography_release")
+
+int isx_find_homography(int num_pairs, const isx_mat* points, const isx_mat* counts, double reproj_thresh, int max_iters, double confidence,
+                        int num_matches_thresh1, int num_matches_thresh2, isx_mat* H, isx_mat* inlier_masks, isx_mat* stats, isx_mat* conf,
+                        int* info, int device, void* hip_stream) ISX_ENTRY {
+    clear_error();
+    return hg_call(false, 0, "find_homography", num_pairs, points, counts, reproj_thresh, max_iters, confidence, num_matches_thresh1,
+                   num_matches_thresh2, H, inlier_masks, stats, conf, info, device, hip_stream);
 } ISX_EXIT("isx_find_homography")
+
+int isx_find_homography_lm(int num_pairs, const isx_mat* points, const isx_mat* counts, double reproj_thresh, int max_iters, double confidence,
+                           int num_matches_thresh1, int num_matches_thresh2, int lm_max_iters, isx_mat* H, isx_mat* inlier_masks, isx_mat* stats,
+                           isx_mat* conf, int* info, int device, void* hip_stream) ISX_ENTRY {
+    clear_error();
+    return hg_call(true, lm_max_iters, "find_homography_lm", num_pairs, points, counts, reproj_thresh, max_iters, confidence, num_matches_thresh1,
+                   num_matches_thresh2, H, inlier_masks, stats, conf, info, device, hip_stream);
+} ISX_EXIT("isx_find_homography_lm")
 
 }  // extern "C"

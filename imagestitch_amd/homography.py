@@ -1,7 +1,8 @@
 """The second half of the reference's BestOf2NearestMatcher::match (R = its 计算单应性矩阵 demo, R:836-909): findHomography(RANSAC), the inlier
 mask, num_inliers, confidence and the second run on the inliers, on the GPU (isx_find_homography, DESIGN.md §8 "Homography").  The
-Levenberg-Marquardt polish of R:672 is not run; cv::eigen, cv::RNG, haveCollinearPoints and cvRound are restated, so parity with OpenCV is
-not pinned (tests/helpers/homography_np.py is the specification)."""
+Levenberg-Marquardt polish of R:672 is opt-in (refine=True: isx_find_homography_lm, four more stats columns); cv::eigen, cv::RNG,
+haveCollinearPoints and cvRound - and, for the polish, OpenCV's mulTransposed, gemm, norm, dot, solve and invert - are restated, so parity
+with OpenCV is not pinned (tests/helpers/homography_np.py and homography_lm_np.py are the specification)."""
 import ctypes as C
 
 import numpy as np
@@ -12,13 +13,15 @@ from .matcher import FeaturesMatcher, _is_device, _mats
 
 # stats columns and status bits (ISX_HOMOGRAPHY_* of include/imagestitch_hip.h); hypotheses per chunk of the kernel
 STATUS, NUM_INLIERS, ITERS1, WIN1, ITERS2, WIN2, ATTEMPTS = range(7)
+LM_RET1, LM_NFJ1, LM_RET2, LM_NFJ2 = 8, 9, 10, 11       # refine only: run()'s return value and nfJ of the LM polish, per pass
 ST_H, ST_PASS2, ST_PASS2_FAILED, ST_CLAMPED, ST_DEGENERATE = 1, 2, 4, 8, 16
 CHUNK = 64
 
 
 def find_homography(points, counts, H, inlier_masks, stats, conf, reproj_thresh=3.0, max_iters=2000, confidence=0.995, num_matches_thresh1=6,
-                    num_matches_thresh2=6, device=0, stream=None):
-    """isx_find_homography on caller-allocated outputs.  points: per pair the matcher's float32 mat (rows x >= 4); counts: its int32 mat of
+                    num_matches_thresh2=6, device=0, stream=None, refine=False, lm_max_iters=10):
+    """isx_find_homography - with refine, isx_find_homography_lm: the LM polish of R:672 with lm_max_iters (1 .. 1000) iterations at the
+    most, and stats of at least len(points) x 12 - on caller-allocated outputs.  points: per pair the matcher's float32 mat (rows x >= 4); counts: its int32 mat of
     at least 1 x len(points), read on the device when it lives there; H: float64, at least 3 len(points) x 3; inlier_masks: per pair uint8,
     at least count x 1; stats: int32, at least len(points) x 8; conf: float64, at least 1 x len(points).  NumPy arrays or CUDA tensors.
     Returns (pairs processed, kernel launches)."""
@@ -27,10 +30,13 @@ def find_homography(points, counts, H, inlier_masks, stats, conf, reproj_thresh=
         raise _lib.IsxError(1, "find_homography: points and inlier_masks differ in length")
     info = (C.c_int * 2)()
     ptr = getattr(stream, "cuda_stream", stream)
-    check(_lib.load().isx_find_homography(
-        npairs, _mats(points), C.byref(as_mat(counts)), float(reproj_thresh), int(max_iters), float(confidence), int(num_matches_thresh1),
-        int(num_matches_thresh2), C.byref(as_mat(H)), _mats(inlier_masks), C.byref(as_mat(stats)), C.byref(as_mat(conf)), info, int(device),
-        C.c_void_p(ptr or 0)))
+    head = (npairs, _mats(points), C.byref(as_mat(counts)), float(reproj_thresh), int(max_iters), float(confidence), int(num_matches_thresh1),
+            int(num_matches_thresh2))
+    tail = (C.byref(as_mat(H)), _mats(inlier_masks), C.byref(as_mat(stats)), C.byref(as_mat(conf)), info, int(device), C.c_void_p(ptr or 0))
+    if refine:
+        check(_lib.load().isx_find_homography_lm(*head, int(lm_max_iters), *tail))
+    else:
+        check(_lib.load().isx_find_homography(*head, *tail))
     return info[0], info[1]
 
 
@@ -41,11 +47,13 @@ def release():
 
 class BestOf2NearestMatcher(FeaturesMatcher):
     """BestOf2NearestMatcher1(try_use_gpu, match_conf, num_matches_thresh1, num_matches_thresh2) (R:781-782, R:830-911): FeaturesMatcher's
-    matches, then H (3 x 3 float64, None when empty), inliers_mask, num_inliers and confidence of every pair.  match() needs keypoints."""
+    matches, then H (3 x 3 float64, None when empty), inliers_mask, num_inliers and confidence of every pair.  match() needs keypoints.
+    refine: H is polished by Levenberg-Marquardt as at R:672 (lm_max_iters: 10 there) and MatchesInfo.stats has 12 columns."""
 
     def __init__(self, match_conf=0.3, num_matches_thresh1=6, num_matches_thresh2=6, device=0, stream=None, reproj_thresh=3.0, max_iters=2000,
-                 confidence=0.995):
+                 confidence=0.995, refine=False, lm_max_iters=10):
         super().__init__(match_conf, device, stream)
+        self.refine, self.lm_max_iters = bool(refine), int(lm_max_iters)
         self.num_matches_thresh1, self.num_matches_thresh2 = int(num_matches_thresh1), int(num_matches_thresh2)
         self.reproj_thresh, self.max_iters, self.confidence = float(reproj_thresh), int(max_iters), float(confidence)
         self.last_homography_info = None
@@ -61,12 +69,13 @@ class BestOf2NearestMatcher(FeaturesMatcher):
 
     def _post_match(self, alloc, cap, points, counts):
         n = len(points)
-        H, stats, conf = alloc(3 * n, 3, np.float64), alloc(n, 8, np.int32), alloc(1, n, np.float64)
+        H, stats, conf = alloc(3 * n, 3, np.float64), alloc(n, 12 if self.refine else 8, np.int32), alloc(1, n, np.float64)
         m_all = alloc(max(sum(cap), 1), 1, np.uint8)
         at = np.concatenate([[0], np.cumsum(cap)])
         masks = [m_all[at[k]:at[k + 1]] for k in range(n)]
         self.last_homography_info = find_homography(points, counts, H, masks, stats, conf, self.reproj_thresh, self.max_iters, self.confidence,
-                                                    self.num_matches_thresh1, self.num_matches_thresh2, self.device, self.stream)
+                                                    self.num_matches_thresh1, self.num_matches_thresh2, self.device, self.stream, self.refine,
+                                                    self.lm_max_iters)
 
         def read_back():
             Hh, sh, ch = (a.cpu().numpy() if _is_device(a) else a for a in (H, stats, conf))

@@ -453,12 +453,15 @@ private:
 
 // BestOf2NearestMatcher1(try_use_gpu, match_conf, num_matches_thresh1, num_matches_thresh2) (R:781-782 of the 计算单应性矩阵 demo) with the whole of
 // its match(), R:830-911: FeaturesMatcher's matches, then findHomography(RANSAC), the inlier mask, num_inliers, confidence and the second run
-// on the inliers for every pair in one launch (isx_find_homography; without the Levenberg-Marquardt polish of R:672).  Needs keypoints.
+// on the inliers for every pair in one launch (isx_find_homography).  Needs keypoints.  The Levenberg-Marquardt polish of R:672 is opt-in, setRefine(true):
+// isx_find_homography_lm, its OpenCV calls restated (unpinned); lmStats() then holds run()'s return value and nfJ of both passes per pair.
 class BestOf2NearestMatcher : public FeaturesMatcher {
 public:
     explicit BestOf2NearestMatcher(float match_conf = 0.3f, int num_matches_thresh1 = 6, int num_matches_thresh2 = 6, int device = 0, void* hip_stream = nullptr)
         : FeaturesMatcher(match_conf, device, hip_stream), thresh1_(num_matches_thresh1), thresh2_(num_matches_thresh2) {}
     void setRansac(double reproj_thresh, int max_iters, double confidence) { reproj_ = reproj_thresh; max_iters_ = max_iters; confidence_ = confidence; }
+    void setRefine(bool refine, int lm_max_iters = 10) { refine_ = refine; lm_max_iters_ = lm_max_iters; }      // 10 at R:672; 1 .. 1000
+    const std::vector<int>& lmStats() const { return lm_stats_; }      // after a refined match(): 4 per pair, stats columns 8 - 11; else empty
     int homographyLaunches() const { return hinfo_[1]; }      // one, however many pairs
     static void release() { FeaturesMatcher::release(); check(isx_homography_release()); }
 protected:
@@ -466,7 +469,8 @@ protected:
         if (!points) throw Exception(ISX_ERR_INVALID, "BestOf2NearestMatcher: the homography needs keypoints and img_sizes");
         const int np = (int)out.size();
         std::vector<double> H((size_t)9 * np), conf((size_t)np);
-        std::vector<int> stats((size_t)8 * np);
+        const int ns = refine_ ? 12 : 8;
+        std::vector<int> stats((size_t)ns * np);
         std::vector<std::vector<unsigned char> > masks(np);
         std::vector<isx_mat> mm(np);
         for (int k = 0; k < np; ++k) {
@@ -475,16 +479,22 @@ protected:
         }
         isx_mat hm, sm, cm;
         hm.data = H.data(); hm.rows = 3 * np; hm.cols = 3; hm.type = ISX_64FC1; hm.step = 24; hm.device = -1;
-        sm.data = stats.data(); sm.rows = np; sm.cols = 8; sm.type = ISX_32SC1; sm.step = 32; sm.device = -1;
+        sm.data = stats.data(); sm.rows = np; sm.cols = ns; sm.type = ISX_32SC1; sm.step = 4 * (size_t)ns; sm.device = -1;
         cm.data = conf.data(); cm.rows = 1; cm.cols = np; cm.type = ISX_64FC1; cm.step = sizeof(double) * (size_t)np; cm.device = -1;
-        check(isx_find_homography(np, points->data(), counts, reproj_, max_iters_, confidence_, thresh1_, thresh2_, &hm, mm.data(), &sm, &cm, hinfo_, device_, stream_));
+        if (refine_)
+            check(isx_find_homography_lm(np, points->data(), counts, reproj_, max_iters_, confidence_, thresh1_, thresh2_, lm_max_iters_, &hm, mm.data(), &sm, &cm,
+                                         hinfo_, device_, stream_));
+        else
+            check(isx_find_homography(np, points->data(), counts, reproj_, max_iters_, confidence_, thresh1_, thresh2_, &hm, mm.data(), &sm, &cm, hinfo_, device_, stream_));
+        lm_stats_.clear();
         for (int k = 0; k < np; ++k) {
             MatchesInfo& mi = out[k];
             const int cnt = ((const int*)counts->data)[k];
-            mi.status = stats[(size_t)8 * k];
+            mi.status = stats[(size_t)ns * k];
+            if (refine_) lm_stats_.insert(lm_stats_.end(), stats.begin() + (size_t)ns * k + 8, stats.begin() + (size_t)ns * k + 12);
             if (mi.status & ISX_HOMOGRAPHY_H) mi.H.assign(H.begin() + 9 * k, H.begin() + 9 * k + 9);
             if (cnt >= thresh1_) mi.inliers_mask.assign(masks[k].begin(), masks[k].begin() + cnt);      // R:836 returns before the mask exists
-            mi.num_inliers = stats[(size_t)8 * k + 1];
+            mi.num_inliers = stats[(size_t)ns * k + 1];
             mi.confidence = conf[k];
         }
     }
@@ -493,6 +503,9 @@ private:
     double reproj_ = 3.0, confidence_ = 0.995;
     int max_iters_ = 2000;
     int hinfo_[2] = {0, 0};
+    bool refine_ = false;
+    int lm_max_iters_ = 10;
+    std::vector<int> lm_stats_;
 };
 
 // cv::imread(path) (W:166): the decoder follows the file's signature, as OpenCV's does - "BM" bitmaps and JFIF / Exif JPEGs;

@@ -671,7 +671,7 @@ enum { ISX_HOMOGRAPHY_H = 1,            /* H is not empty                       
        ISX_HOMOGRAPHY_CLAMPED = 8,      /* the count exceeded the rows of its points or mask mat and was clamped to them    */
        ISX_HOMOGRAPHY_DEGENERATE = 16   /* |det H| < DBL_EPSILON: R:863 returned, H is pass 1's, num_inliers and conf are 0 */ };
 /* The second half of BestOf2NearestMatcher1::match, R:836-909, for every pair of a matcher call, WITHOUT the Levenberg-Marquardt polish of
- * R:672 (createLMSolver1(...)->run(H8), R:461-591: not built; it changes neither mask, count nor confidence - H here is the least-squares
+ * R:672 (createLMSolver1(...)->run(H8), R:461-591: opt-in, isx_find_homography_lm below; it changes neither mask, count nor confidence - H here is the least-squares
  * runKernel over the inliers that LM starts from).  Per pair, with n = counts[p]:
  *   n < num_matches_thresh1 (R:836)   H, stats and conf are zeros, the mask is not written.
  *   pass 1 (R:862)                    findHomography2(src, dst, RANSAC, reproj_thresh, mask, max_iters, confidence) (R:602-693): n < 4 fails
@@ -707,6 +707,20 @@ enum { ISX_HOMOGRAPHY_H = 1,            /* H is not empty                       
 int isx_find_homography(int num_pairs, const isx_mat* points, const isx_mat* counts, double reproj_thresh, int max_iters, double confidence,
                         int num_matches_thresh1, int num_matches_thresh2, isx_mat* H, isx_mat* inlier_masks, isx_mat* stats, isx_mat* conf,
                         int* info, int device, void* hip_stream);
+/* isx_find_homography WITH the Levenberg-Marquardt polish of R:672: after the runKernel over the inliers of each pass (R:657-668, n > 4, at
+ * least one inlier; also where that runKernel returned 0 and left the RANSAC model; never for n == 4) createLMSolver1(makePtr<
+ * HomographyRefineCallback>(src, dst), lm_max_iters)->run(H8) (R:404-591) replaces the first eight doubles of H - H[8] keeps runKernel's
+ * bits (R:669) - so H is the reprojection-error minimiser MatchesInfo::H holds in the reference, and the degenerate test of R:863 sees it.
+ * Mask, num_inliers and confidence are isx_find_homography's.  OPT-IN AND UNPINNED: the OpenCV calls inside LMSolverImpl1::run
+ * (mulTransposed, gemm, norm, dot, solve / invert with DECOMP_EIG) are in neither tree and are restated from OpenCV 3.4.2's published source
+ * in tests/helpers/homography_lm_np.py - the specification, to which H agrees bit for bit (DESIGN.md §8 "Homography").
+ * Arguments, checks, capture rule, scratch (isx_homography_release) and the ONE launch are isx_find_homography's, except:
+ *   lm_max_iters  maxIters of the solver, 10 at R:672; in [1, 1000], else ISX_ERR_INVALID.
+ *   stats         at least num_pairs x 12: columns 0 - 7 as above; 8, 9: run()'s return value (the iterations, negated when they reached
+ *                 lm_max_iters, R:577-580) and nfJ of pass 1; 10, 11: those of pass 2; 0 where LM did not run.                            */
+int isx_find_homography_lm(int num_pairs, const isx_mat* points, const isx_mat* counts, double reproj_thresh, int max_iters, double confidence,
+                           int num_matches_thresh1, int num_matches_thresh2, int lm_max_iters, isx_mat* H, isx_mat* inlier_masks, isx_mat* stats,
+                           isx_mat* conf, int* info, int device, void* hip_stream);
 /* Returns the scratch of the calling thread.  PER THREAD and not freed at thread exit, as for isx_match_release.                          */
 int isx_homography_release(void);
 

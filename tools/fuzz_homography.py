@@ -2,6 +2,10 @@
 H and conf through their uint64 views.
 
     python tools/fuzz_homography.py --seconds 600 --seed 20261201 [--out profiles/fuzz_homography_600s.json]
+    python tools/fuzz_homography.py --refine --seconds 600 [--out profiles/fuzz_homography_lm_600s.json]
+
+--refine runs the same cases through isx_find_homography_lm (the Levenberg-Marquardt polish, 12 stats columns) against
+tests/helpers/homography_lm_np.py, with lm_max_iters drawn from 1, 2 and 10 by a generator of its own: case(seed, cls) is the same either way.
 
 case(seed, cls) draws one of CLASSES (no GPU needed):
     tiny          4 .. 12 correspondences, the thresholds either side of the count
@@ -25,6 +29,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np  # noqa: E402
 
 import homography_cases as cases  # noqa: E402
+from helpers import homography_lm_np as lm  # noqa: E402
 from helpers import homography_np as hm  # noqa: E402
 
 CLASSES = ("tiny", "chunk_edges", "count_limits", "noisy", "degenerate", "multi")
@@ -78,13 +83,21 @@ def case(seed, cls):
     return dict(pairs=pairs, kw=kw, device=bool(rng.integers(2)), wide=bool(rng.integers(2)), spare=int(rng.choice([0, 0, 3])))
 
 
-def expected(c):
-    """The model's results, with the capacities of run_case's mats."""
+def lm_iters_of(seed):
+    """--refine: the case's lm_max_iters, from a generator that case() does not share."""
+    return int(np.random.default_rng([int(seed), 0x4C4D]).choice([1, 2, 10]))
+
+
+def expected(c, lm_max_iters=None):
+    """The model's results, with the capacities of run_case's mats; lm_max_iters: those of the model with the polish."""
+    if lm_max_iters is not None:
+        return [lm.find_homography_lm_np(np.r_[p, np.zeros((c["spare"], 4), np.float32)], count=n, lm_max_iters=lm_max_iters, **c["kw"])
+                for p, n in c["pairs"]]
     return [hm.find_homography_np(np.r_[p, np.zeros((c["spare"], 4), np.float32)], count=n, **c["kw"]) for p, n in c["pairs"]]
 
 
-def run_case(c, want):
-    """The library on the case's layout against `want`; returns the list of differences."""
+def run_case(c, want, lm_max_iters=None):
+    """The library on the case's layout against `want`; returns the list of differences.  lm_max_iters: through isx_find_homography_lm."""
     import torch
     from imagestitch_amd import homography as hg
     put = (lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()) if c["device"] else (lambda a: np.array(a))
@@ -98,8 +111,9 @@ def run_case(c, want):
         ps.append(put(full))
         ms.append(put(np.full((len(p) + c["spare"], 3 if c["wide"] else 1), SENT_B, np.uint8)))
     cnt = put(np.array([[n for _, n in c["pairs"]]], np.int32))
-    H, st, cf = put(np.full((3 * k, 3), SENT_F, np.float64)), put(np.full((k, 8), SENT_I, np.int32)), put(np.full((1, k), SENT_F, np.float64))
-    info = hg.find_homography(ps, cnt, H, ms, st, cf, **c["kw"])
+    H, st, cf = put(np.full((3 * k, 3), SENT_F, np.float64)), put(np.full((k, 8 if lm_max_iters is None else 12), SENT_I, np.int32)), put(np.full((1, k), SENT_F, np.float64))
+    refine = {} if lm_max_iters is None else dict(refine=True, lm_max_iters=lm_max_iters)
+    info = hg.find_homography(ps, cnt, H, ms, st, cf, **c["kw"], **refine)
     torch.cuda.synchronize()
     bad = [] if info == (k, 1) else ["info %s" % (info,)]
     Hh, sh, ch = get(H), get(st), get(cf)
@@ -119,7 +133,7 @@ def run_case(c, want):
     return bad
 
 
-def run(seconds, seed, verbose=False, progress_path=None):
+def run(seconds, seed, verbose=False, progress_path=None, refine=False):
     """Draws cases (the classes in turn) for `seconds` and compares the library with the model.  Returns a summary dict."""
     import torch
     import imagestitch_amd
@@ -134,19 +148,20 @@ def run(seconds, seed, verbose=False, progress_path=None):
         cls = CLASSES[n % len(CLASSES)]
         s = int(seed) * 1000003 + n
         c = case(s, cls)
-        want = expected(c)
+        iters = lm_iters_of(s) if refine else None
+        want = expected(c, iters)
         n += 1
         per[cls] += 1
         if min(w["margin"] for w in want) < 1e-9:
             skipped += 1
             continue
-        bad = run_case(c, want)
+        bad = run_case(c, want, iters)
         pairs += len(c["pairs"])
         if bad:
             failing.append(dict(seed=s, cls=cls, differences=bad[:4]))
             if verbose:
                 print("MISMATCH", s, cls, bad[:4], flush=True)
-    return dict(tool="fuzz_homography", seconds=round(time.time() - t0, 1), seed=int(seed), cases=n, pairs=pairs, mismatches=len(failing),
+    return dict(tool="fuzz_homography", refine=bool(refine), seconds=round(time.time() - t0, 1), seed=int(seed), cases=n, pairs=pairs, mismatches=len(failing),
                 skipped_fragile=skipped, too_many_fragile=bool(skipped > 0.01 * n), per_class=per, failing_seeds=failing[:20],
                 device=torch.cuda.get_device_name(0))
 
@@ -157,8 +172,9 @@ def main():
     ap.add_argument("--seed", type=int, default=20261201)
     ap.add_argument("--out", default=None)
     ap.add_argument("--progress", default=None)
+    ap.add_argument("--refine", action="store_true", help="isx_find_homography_lm against the model with the LM polish")
     a = ap.parse_args()
-    out = run(a.seconds, a.seed, verbose=True, progress_path=a.progress)
+    out = run(a.seconds, a.seed, verbose=True, progress_path=a.progress, refine=a.refine)
     print(json.dumps(out), flush=True)
     if a.out:
         with open(a.out, "w") as f:

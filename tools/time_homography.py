@@ -5,7 +5,8 @@ features, apart from bench.py:
 Every image holds --shared keypoints of one scene under a planted homography (descriptors a bit apart) among random rows, so that each pair
 has a few hundred matches with outliers among them.  Two clocks, since neither call synchronises on device mats: the host clock around the
 chained calls + a stream synchronise (median and minimum of --iters after --warmup) and HIP events around --events chained calls enqueued
-back to back; the homography entry alone is timed the same way on the matcher's outputs.  One JSON line per workload."""
+back to back; the homography entry alone is timed the same way on the matcher's outputs.  One JSON line per workload.  --refine times
+isx_find_homography_lm (the Levenberg-Marquardt polish) in the homography entry's place."""
 import argparse
 import json
 import os
@@ -69,6 +70,8 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--events", type=int, default=50)
+    ap.add_argument("--refine", action="store_true")
+    ap.add_argument("--lm-max-iters", type=int, default=10)
     a = ap.parse_args()
     st = torch.cuda.current_stream()
     for name, n in (("pair2k", 2), ("ring8", 8)):
@@ -80,14 +83,14 @@ def main():
         ps = [torch.empty((2 * a.rows, 4), dtype=torch.float32, **dev) for _ in pairs]
         masks = [torch.empty((2 * a.rows, 1), dtype=torch.uint8, **dev) for _ in pairs]
         cnt = torch.empty((1, k), dtype=torch.int32, **dev)
-        H, stats = torch.empty((3 * k, 3), dtype=torch.float64, **dev), torch.empty((k, 8), dtype=torch.int32, **dev)
+        H, stats = torch.empty((3 * k, 3), dtype=torch.float64, **dev), torch.empty((k, 12 if a.refine else 8), dtype=torch.int32, **dev)
         conf = torch.empty((1, k), dtype=torch.float64, **dev)
 
         def match():
             return matcher.match_features(descs, pairs, 0.3, ms, cnt, kps, sizes, ps, stream=st)
 
         def homog():
-            return homography.find_homography(ps, cnt, H, masks, stats, conf, stream=st)
+            return homography.find_homography(ps, cnt, H, masks, stats, conf, stream=st, refine=a.refine, lm_max_iters=a.lm_max_iters)
 
         def both():
             match()
@@ -95,7 +98,8 @@ def main():
         info = both()
         chained, alone, matching = clocks(both, a), clocks(homog, a), clocks(match, a)
         s = stats.cpu().numpy()
-        print(json.dumps(dict(workload=name, images=n, rows=a.rows, pairs=k, launches_homography=info[1],
+        lm_cols = dict(refine=True, lm_max_iters=a.lm_max_iters, lm_iterations=[[int(v) for v in r] for r in s[:4, 8:12]]) if a.refine else {}
+        print(json.dumps(dict(workload=name, **lm_cols, images=n, rows=a.rows, pairs=k, launches_homography=info[1],
                               chained_ms=dict(median=chained[0], min=chained[1], events=chained[2]),
                               homography_ms=dict(median=alone[0], min=alone[1], events=alone[2]),
                               match_ms=dict(median=matching[0], min=matching[1], events=matching[2]),
