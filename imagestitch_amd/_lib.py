@@ -118,6 +118,8 @@ _SIGS = {
     "isx_find_homography_lm": [C.c_int, _MP, _MP, C.c_double, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _MP, _MP, _MP, _MP, _IP, C.c_int,
                                C.c_void_p],
     "isx_homography_release": [],
+    "isx_estimate_cameras": [C.c_int, _IP, C.c_int, _IP, C.c_int, _IP, _MP, _MP, _MP, _MP, _MP, _MP, _MP, _MP, _IP, C.c_int, C.c_void_p],
+    "isx_estimator_release": [],
     "isx_seam_estimate": [_MP, _MP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _MP, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int,
                           C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_void_p],
     "isx_seam_estimate_cost": [_MP, _MP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _MP, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int,

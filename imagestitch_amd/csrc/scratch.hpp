@@ -28,7 +28,7 @@ struct PinBuf {
     int release() { if (p) { ISX_HIP(hipHostFree(p)); p = nullptr; cap = 0; } return ISX_OK; }
 };
 
-// The scratch of a stage that uploads its tables (isx_match_features, isx_find_homography): a device buffer `work` whose head is the upload,
+// The scratch of a stage that uploads its tables (isx_match_features, isx_find_homography, isx_estimate_cameras): a device buffer `work` whose head is the upload,
 // a pinned buffer `pin` that the host fills and one hipMemcpyAsync sends.  A call is begin(), fill pin.p, upload(), its launches, ran(), and
 // never synchronises host and device where every mat is a device mat.  Two rules make that sound, and they live here only:
 //   1. `pin` is not rewritten (or freed) until the upload that read it has completed: upload() records `uploaded`; begin() and release()

@@ -82,6 +82,7 @@ class FeaturesMatcher:
     def __init__(self, match_conf=0.3, device=0, stream=None):
         self.match_conf, self.device, self.stream = float(match_conf), device, stream
         self.last_info = None
+        self.last_outputs = None      # of the last match(): pairs, counts; a subclass adds its mats (cameras.py reads them where they lie)
 
     @staticmethod
     def near_pairs(rows, mask=None):
@@ -99,6 +100,7 @@ class FeaturesMatcher:
         With CUDA descriptors the outputs are computed into CUDA tensors and returned as such."""
         rows = [int(d.shape[0]) for d in descriptors]
         pairs = self.near_pairs(rows, mask)
+        self.last_outputs = {"pairs": pairs}
         if not pairs:
             self.last_info = (0, 0)
             return []
@@ -120,6 +122,7 @@ class FeaturesMatcher:
         ps = [p_all[at[k]:at[k + 1]] for k in range(len(pairs))] if p_all is not None else None
         ks = [alloc(rows[p[d]], 4, np.int32) for p in pairs for d in range(2)] if knn else None
         self.last_info = match_features(descriptors, pairs, self.match_conf, ms, counts, keypoints, img_sizes, ps, ks, self.device, self.stream)
+        self.last_outputs["counts"] = counts
         post = self._post_match(alloc, cap, ps, counts)
         if on_device:
             import torch

@@ -508,6 +508,79 @@ private:
     std::vector<int> lm_stats_;
 };
 
+// HomographyBasedEstimator1 estimator; estimator(features, pairwise_matches, cameras) (C:313-321 of the reference's 恢复相机内参数 demo;
+// isx_estimate_cameras): a focal from the pairwise homographies (C:26-105), the maximum spanning tree over num_inliers (C:145-213) and the
+// rotations along it (C:215-243), one rig - all images of the call - in one launch.  pairwise_matches is the matcher's n * n vector: entry
+// i * n + j with i < j is read (H where status has ISX_HOMOGRAPHY_H, num_inliers), the duals are formed on the GPU.  Mat::inv(), Mat * Mat
+// and Graph::walkBreadthFirst are restated, equal weights sort by i * n + j: unpinned (tests/helpers/estimator_np.py is the specification).
+struct CameraParams {                             // cv::detail::CameraParams
+    double focal = 1, aspect = 1, ppx = 0, ppy = 0;
+    double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    double t[3] = {0, 0, 0};
+    float K32[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};   // K() and R as convertTo(CV_32F) gives them (C:329-334, C:385-386): what RotationWarper takes
+    float R32[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    int parent = -2, depth = -1;                  // the camera's place in the walk from the tree's center: -1 the root, -2 not reached
+    void K(double k[9]) const { k[0] = focal; k[1] = 0; k[2] = ppx; k[3] = 0; k[4] = focal * aspect; k[5] = ppy; k[6] = 0; k[7] = 0; k[8] = 1; }
+};
+
+class HomographyBasedEstimator {
+public:
+    explicit HomographyBasedEstimator(bool is_focals_estimated = false, int device = 0, void* hip_stream = nullptr)
+        : given_(is_focals_estimated), device_(device), stream_(hip_stream) {}
+    void setStream(void* hip_stream) { stream_ = hip_stream; }
+    // With is_focals_estimated, focal, aspect, ppx and ppy of `cameras` come in (C:264-268); R and t are replaced either way.
+    bool operator()(const std::vector<ImageFeatures>& features, const std::vector<MatchesInfo>& pairwise_matches, std::vector<CameraParams>& cameras) {
+        const int n = (int)features.size();
+        if ((int)pairwise_matches.size() != n * n) throw Exception(ISX_ERR_INVALID, "HomographyBasedEstimator: pairwise_matches is not n * n");
+        if (given_ && (int)cameras.size() != n) throw Exception(ISX_ERR_INVALID, "HomographyBasedEstimator: is_focals_estimated needs n cameras");
+        std::vector<int> sizes, pij, stats;
+        std::vector<double> H, fin;
+        for (int i = 0; i < n; ++i) { sizes.push_back(features[i].img_size.width); sizes.push_back(features[i].img_size.height); }
+        for (int i = 0; i < n - 1; ++i)
+            for (int j = i + 1; j < n; ++j) {
+                const MatchesInfo& mi = pairwise_matches[(size_t)i * n + j];
+                if (mi.src_img_idx < 0) continue;
+                const bool has = (mi.status & ISX_HOMOGRAPHY_H) && mi.H.size() == 9;
+                pij.push_back(i); pij.push_back(j);
+                stats.push_back(has ? ISX_HOMOGRAPHY_H : 0); stats.push_back(mi.num_inliers);
+                for (int e = 0; e < 9; ++e) H.push_back(has ? mi.H[e] : 0.0);
+            }
+        const int np = (int)pij.size() / 2;
+        std::vector<double> conf((size_t)(np > 0 ? np : 1), 0.0), cams((size_t)16 * n);
+        std::vector<float> kr((size_t)18 * n);
+        std::vector<int> tree((size_t)2 * n);
+        if (H.empty()) { H.resize(9); stats.resize(2); }
+        if (given_)
+            for (int i = 0; i < n; ++i) { fin.push_back(cameras[i].focal); fin.push_back(cameras[i].aspect); fin.push_back(cameras[i].ppx); fin.push_back(cameras[i].ppy); }
+        isx_mat hm = host(H.data(), 3 * np, 3, ISX_64FC1, 24), sm = host(stats.data(), np, 2, ISX_32SC1, 8), cm = host(conf.data(), 1, np, ISX_64FC1, 8 * (size_t)(np > 0 ? np : 1));
+        isx_mat fm = host(fin.data(), n, 4, ISX_64FC1, 32), om = host(cams.data(), n, 16, ISX_64FC1, 128), km = host(kr.data(), n, 18, ISX_32FC1, 72);
+        isx_mat tm = host(tree.data(), n, 2, ISX_32SC1, 8), rm = host(rig_stats_, 1, 8, ISX_32SC1, 32);
+        check(isx_estimate_cameras(n, sizes.data(), np, pij.data(), 1, nullptr, &hm, &sm, &cm, given_ ? &fm : nullptr, &om, &km, &tm, &rm, info_, device_, stream_));
+        cameras.assign((size_t)n, CameraParams());
+        for (int i = 0; i < n; ++i) {
+            CameraParams& c = cameras[i];
+            const double* s = &cams[(size_t)16 * i];
+            c.focal = s[0]; c.aspect = s[1]; c.ppx = s[2]; c.ppy = s[3];
+            std::memcpy(c.R, s + 4, sizeof(c.R)); std::memcpy(c.t, s + 13, sizeof(c.t));
+            std::memcpy(c.K32, &kr[(size_t)18 * i], sizeof(c.K32)); std::memcpy(c.R32, &kr[(size_t)18 * i + 9], sizeof(c.R32));
+            c.parent = tree[(size_t)2 * i]; c.depth = tree[(size_t)2 * i + 1];
+        }
+        return true;
+    }
+    const int* rigStats() const { return rig_stats_; }      // status bits (ISX_ESTIMATOR_*), candidates, the two centers, tree edges, reached, centers, min-max distance
+    int launches() const { return info_[1]; }               // one
+    static void release() { check(isx_estimator_release()); }
+private:
+    static isx_mat host(void* data, int rows, int cols, int type, size_t step) {
+        isx_mat m; m.data = data; m.rows = rows; m.cols = cols; m.type = type; m.step = step; m.device = -1; return m;
+    }
+    bool given_;
+    int device_;
+    void* stream_;
+    int rig_stats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int info_[2] = {0, 0};
+};
+
 // cv::imread(path) (W:166): the decoder follows the file's signature, as OpenCV's does - "BM" bitmaps and JFIF / Exif JPEGs;
 // cv::imwrite(path, img) for .bmp and .jpg (W:155-156,315; "pano.jpg" S:1282)
 inline Mat imread(const char* path) {

@@ -724,6 +724,64 @@ int isx_find_homography_lm(int num_pairs, const isx_mat* points, const isx_mat* 
 /* Returns the scratch of the calling thread.  PER THREAD and not freed at thread exit, as for isx_match_release.                          */
 int isx_homography_release(void);
 
+/* ---- HomographyBasedEstimator (C = the reference's 恢复相机内参数/恢复相机内参数/恢复相机内参数.cpp) ---------------------------------------- */
+/* Images a rig at the most (estimator.hip takes it from here): one per lane of the wave that runs Kruskal and the leaf walks. */
+enum { ISX_ESTIMATOR_MAX_IMAGES = 64 };
+/* status bits of rig_stats column 0 */
+enum { ISX_ESTIMATOR_MEDIAN = 1,    /* the focal is the median of the candidates (C:84-95), not the fallback of C:97-104            */
+       ISX_ESTIMATOR_ASSERT = 2,    /* the tree has 0 or more than 2 centers, where C:212 asserts: no walk, every R the identity     */
+       ISX_ESTIMATOR_UNREACHED = 4  /* the walk of C:275 did not reach every camera of the rig; those keep the identity              */ };
+/* HomographyBasedEstimator1 estimator(is_focals_estimated); estimator(features, pairwise_matches, cameras) (C:313-321) for every rig - an
+ * independent image set - of a matcher call, on the mats isx_find_homography / isx_find_homography_lm left.  pairwise_matches[i * n + j]
+ * for i < j is pair (i, j)'s H where its status bit ISX_HOMOGRAPHY_H is set, with num_inliers of stats column 1; for i > j it is the dual
+ * the reference's matcher stores, H.inv() with the same num_inliers; every other entry has an empty H.  Per rig of n images:
+ *   C:253-261    focals not given: estimateFocal1 (C:55-105) - focalsFromHomography1 (C:26-54) over every ordered pair with H, the
+ *                candidates sqrt(f0 * f1) where both are ok, their median when there are at least n - 1 (the mean of the middle two times
+ *                0.5 for an even count, C:92), else sum(width + height) / n (C:99-103); cameras = CameraParams() with that focal.
+ *   C:264-268    focals given: focal, aspect, ppx, ppy per image from focals_in; ppx -= 0.5 * width, ppy -= 0.5 * height.
+ *   C:145-213    findMaxSpanningTree: the edges of every ordered pair with H, weight (float)num_inliers, sorted descending (C:169), Kruskal,
+ *                the leafs, a breadth-first distance from every leaf (C:193-199), max_dists, the min-max distance, the centers in index
+ *                order.  C:212 asserts 1 or 2 centers; with another number (a disconnected graph only) status bit ISX_ESTIMATOR_ASSERT is
+ *                set and every R of the rig is the identity - the focals and K are still written.
+ *   C:215-243    CalcRotation over the breadth-first walk from centers[0] (C:275): R_to = R_from * ((K_from.inv() * H.inv()) * K_to), H the
+ *                entry of the ordered pair (from, to) - for from > to the dual, inverted again as the reference does.  Cameras outside the
+ *                root's component keep the identity (ISX_ESTIMATOR_UNREACHED).
+ *   C:278-282    ppx += 0.5 * width, ppy += 0.5 * height.
+ *   C:329-334, C:385-386   K() and R converted to float32 (round to nearest): what isx_warper_* takes.
+ * THE TIE RULE: std::sort leaves the order of edges of equal weight open, and (i, j) and (j, i) always tie.  Here it is fixed: weight
+ * descending, then i * n + j ascending.  The weight is compared as the integer num_inliers, which (float) holds exactly up to 2^24; the
+ * matcher's row limit (ISX_MATCH_MAX_ROWS) keeps it below 2^21.
+ * RESTATED AND UNPINNED: Mat::inv() of a 3 x 3 CV_64F (cofactors times the reciprocal determinant as in OpenCV 3.4.2; nine zeros for a
+ * determinant of exactly 0), Mat * Mat (three-term sums, left to right), CameraParams() (aspect 1, ppx = ppy = 0, R = eye, t = 0),
+ * CameraParams::K() and Graph::walkBreadthFirst (adjacency in insertion order) are in neither tree: tests/helpers/estimator_np.py is the
+ * specification (DESIGN.md §8 "Camera estimator"), to which every output agrees bit for bit.  float64 + - * / sqrt only, no contraction.
+ *   image_sizes_wh  (width, height) per image (features[i].img_size).
+ *   pairs_from_to   num_pairs (from, to), from < to, both of one rig, no pair twice: row p of stats and conf and rows 3p .. 3p + 2 of H.
+ *   rig_first       num_rigs + 1 increasing image offsets from 0 to num_images; NULL = one rig (num_rigs must be 1).  A rig has from 2
+ *                   (C:84 indexes all_focals[-1] with one image) to ISX_ESTIMATOR_MAX_IMAGES images.
+ *   H, stats, conf  isx_find_homography's: CV_64FC1 of at least 3 num_pairs x 3, CV_32SC1 of at least num_pairs x 2, CV_64FC1 of at least
+ *                   1 x num_pairs; a device mat is read ON THE DEVICE.  conf is checked and not read (the estimator weighs by num_inliers).
+ *   focals_in       NULL = estimate the focals; else CV_64FC1 of at least num_images x 4: focal, aspect, ppx, ppy (is_focals_estimated).
+ *   cameras         CV_64FC1, at least num_images x 16: focal, aspect, ppx, ppy, R[9], t[3] (zeros).
+ *   kr32            CV_32FC1, at least num_images x 18: K()[9], then R[9].
+ *   tree            CV_32SC1, at least num_images x 2: the parent in the walk as an index inside the rig (-1 the root, -2 not reached) and
+ *                   the depth (-1 not reached).
+ *   rig_stats       CV_32SC1, at least num_rigs x 8: status bits, focal candidates, the two centers as indices inside the rig (-1 where
+ *                   absent), tree edges, cameras reached, the number of centers, the min-max distance.
+ *   info            NULL, or 2 ints: the rigs processed and the kernel launches of this call - ONE, a workgroup per rig.
+ * Mats are host or device mats, 4-byte aligned in pointer and step, 8-byte for the CV_64FC1 ones.  Checked before anything is written or
+ * enqueued: null pointers, fewer than 2 images in a rig, a pair with from >= to, a repeated pair, a pair across two rigs, an index out of
+ * range, rig_first not increasing, a misaligned mat -> ISX_ERR_INVALID; a mat of another type -> ISX_ERR_TYPE; too few rows or columns ->
+ * ISX_ERR_SIZE; more than ISX_ESTIMATOR_MAX_IMAGES images in a rig -> ISX_ERR_UNSUPPORTED.  The call uploads its table (and stages host
+ * mats): on a capturing stream -> ISX_ERR_STATE with nothing enqueued.  With device mats throughout nothing is read back or synchronised.
+ * Host mats synchronise.  Not built: the bundle adjusters, waveCorrect (commented out at C:355-361), leaveBiggestComponent.             */
+int isx_estimate_cameras(int num_images, const int* image_sizes_wh, int num_pairs, const int* pairs_from_to, int num_rigs, const int* rig_first,
+                         const isx_mat* H, const isx_mat* stats, const isx_mat* conf, const isx_mat* focals_in, isx_mat* cameras, isx_mat* kr32,
+                         isx_mat* tree, isx_mat* rig_stats, int* info, int device, void* hip_stream);
+/* Returns the scratch of the calling thread (its own: isx_homography_release does not free it).  PER THREAD and not freed at thread exit,
+ * as for isx_homography_release.                                                                                                       */
+int isx_estimator_release(void);
+
 /* ---- on-disk format either side of the path: .bmp (W:166 imread, W:155-156,315 imwrite) ----------- */
 /* Reading: uncompressed Windows bitmaps only (the reference's inputs and committed artefacts are BMPs).
  * isx_bmp_read = cv::imread(path) with IMREAD_COLOR: `out` is a CV_8UC3 mat (host or device) of the size
