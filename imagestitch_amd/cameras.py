@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import as_mat, check
-from .matcher import _is_device, _mat
+from .matcher import _allocator, _is_device, _mat, _synchronize
 
 # limits, status bits and rig_stats columns (ISX_ESTIMATOR_* of include/imagestitch_hip.h)
 MAX_IMAGES = 64
@@ -96,24 +96,15 @@ class HomographyBasedEstimator:
                 raise _lib.IsxError(1, "HomographyBasedEstimator: is_focals_estimated needs the cameras")
             fin = np.ascontiguousarray([[c.focal, c.aspect, c.ppx, c.ppy] for c in cameras] if isinstance(cameras[0], CameraParams)
                                        else cameras, np.float64).reshape(n, 4)
-        if _is_device(H):
+        alloc = _allocator(H.device if _is_device(H) else None)
+        if fin is not None and _is_device(H):
             import torch
-            dev = H.device
-
-            def alloc(r, c, dt):
-                return torch.empty((r, c), dtype=getattr(torch, np.dtype(dt).name), device=dev)
-            if fin is not None:
-                fin = torch.from_numpy(fin).to(dev)
-        else:
-            def alloc(r, c, dt):
-                return np.empty((r, c), dt)
+            fin = torch.from_numpy(fin).to(H.device)
         cams, kr, tree, rs = alloc(n, 16, np.float64), alloc(n, 18, np.float32), alloc(n, 2, np.int32), alloc(nrigs, 8, np.int32)
         self.last_info = estimate_cameras(img_sizes, pairs, H, stats, conf, cams, kr, tree, rs, rig_first, fin, self.device, self.stream)
         self.last_outputs = (cams, kr, tree, rs)
         if _is_device(cams):       # the one small read-back, which the warper's host-side ROI needs
-            import torch
-            s = self.stream if hasattr(self.stream, "synchronize") else None
-            s.synchronize() if s is not None else torch.cuda.synchronize(int(self.device))
+            _synchronize(self.stream, self.device)
             cams, kr, tree, rs = (a.cpu().numpy() for a in (cams, kr, tree, rs))
         self.last_rig_stats = rs
         out = CameraList()

@@ -990,20 +990,7 @@ __device__ __forceinline__ T ld_const(const void* p) {
     for (unsigned i = 0; i < sizeof(T) / 4; ++i) o[i] = s[i];
     return v;
 }
-// A pointer that was LOADED (from the table) is a generic pointer to the compiler, and generic pointers make FLAT loads - counted on lgkmcnt as
-// well as vmcnt, so every LDS wait of a kernel drains them too (collapse_roll.inc, gcp / ROLL_G, tells the same story about pointers that went
-// through an asm statement).  Pointers that arrive in the kernel arguments (TileSet) are known to be global.  The table's pointers are said to
-// be global where they are loaded: a round trip through address space 1 that the optimiser cannot fold away (a plain cast pair is folded, and
-// __builtin_assume(!is_shared && !is_private) is not picked up: both measured) - the two halves go through v_readfirstlane, which is free for a
-// value that already sits in scalar registers (a tile index is wave-uniform by construction and its descriptor comes from s_load; where the
-// compiler cannot see that, inside a per-lane branch, it is two instructions) and from whose result the address-space inference types every
-// access behind it (round 6: 10 - 54 flat_load per *_tab kernel before, none after; tools/isa_flat.py, tests/test_isa_flat.py).
-template <class T>
-__device__ __forceinline__ T* as_global(T* p) {
-    const unsigned long long u = (unsigned long long)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-    return (T*)(__attribute__((address_space(1))) T*)(((unsigned long long)hi << 32) | lo);
-}
+// the table's pointers are said to be global where they are loaded: as_global (isx_device.hpp)
 __device__ __forceinline__ void mark_global(int&) {}
 __device__ __forceinline__ void mark_global(Src0& s) { s.img = as_global(s.img); s.mask = as_global(s.mask); s.img_al = as_global(s.img_al); s.mask_al = as_global(s.mask_al); }
 __device__ __forceinline__ void mark_global(LevelBuf& l) { l.img = as_global(l.img); l.wgt = as_global(l.wgt); }

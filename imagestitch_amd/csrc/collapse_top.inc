@@ -25,7 +25,7 @@ struct TopDesc { int x_tl, y_tl, w, h; const void* g[TOP_DMAX + 1]; };
 static_assert(sizeof(TopDesc) % 16 == 0, "TopDesc records are loaded in 16-byte pieces");
 struct TopGRow {
     const char* row;
-    __device__ __forceinline__ const void* operator[](int i) const { return as_global(ld_const<const void*>(row + (size_t)(unsigned)i * sizeof(void*))); }   // a loaded pointer, said to be global (blend.hip: as_global)
+    __device__ __forceinline__ const void* operator[](int i) const { return as_global(ld_const<const void*>(row + (size_t)(unsigned)i * sizeof(void*))); }   // a loaded pointer, said to be global (isx_device.hpp: as_global)
 };
 struct TopGField {
     const char* base;

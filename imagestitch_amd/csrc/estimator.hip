@@ -54,9 +54,6 @@ struct EsCall {
     int* rs; long long rs_step;
 };
 
-template <class T>
-__device__ __forceinline__ T* row_ptr(T* base, long long row, long long step) { return (T*)((char*)base + row * step); }
-
 // Mat::inv() of a 3 x 3 CV_64F: cofactors times the reciprocal determinant, nine zeros for a determinant of exactly 0
 __device__ void es_inv3(const double* m, double* t) {
     const double a = (m[4] * m[8]) - (m[5] * m[7]);
@@ -456,21 +453,20 @@ int es_call(int num_images, const int* image_sizes_wh, int num_pairs, const int*
         const int a = pairs_from_to[2 * p], b = pairs_from_to[2 * p + 1], r = rig_of[a];
         prs[(size_t)rigs[r].pair_first + fill[r]++] = EsPair{a - first[r], b - first[r], p, 0};
     }
-    const bool host_H = H->device < 0 && num_pairs > 0, host_stats = stats->device < 0 && num_pairs > 0;
-    const bool host_fin = focals_in && focals_in->device < 0;
+    StagedMat m_H, m_stats, m_fin, m_cams, m_kr, m_tree, m_rs;
     Bump lay;
     const size_t o_rigs = lay.take(rigs.size() * sizeof(EsRig));
     const size_t o_prs = lay.take(prs.size() * sizeof(EsPair));
     const size_t o_sizes = lay.take((size_t)num_images * 8);
-    const size_t o_H = host_H ? lay.take((size_t)num_pairs * 72) : 0;
-    const size_t o_stats = host_stats ? lay.take((size_t)num_pairs * 8) : 0;
-    const size_t o_fin = host_fin ? lay.take((size_t)num_images * 32) : 0;
+    m_H.plan(lay, *H, 3ll * num_pairs, 24);
+    m_stats.plan(lay, *stats, num_pairs, 8);
+    if (focals_in) m_fin.plan(lay, *focals_in, num_images, 32);
     const size_t upload_bytes = lay.at;
     const size_t o_dual = lay.take((size_t)std::max(num_pairs, 1) * 72);
-    const size_t o_cams = cameras->device < 0 ? lay.take((size_t)num_images * 128) : 0;
-    const size_t o_kr = kr32->device < 0 ? lay.take((size_t)num_images * 72) : 0;
-    const size_t o_tree = tree->device < 0 ? lay.take((size_t)num_images * 8) : 0;
-    const size_t o_rs = rig_stats->device < 0 ? lay.take((size_t)num_rigs * 32) : 0;
+    m_cams.plan(lay, *cameras, num_images, 128);
+    m_kr.plan(lay, *kr32, num_images, 72);
+    m_tree.plan(lay, *tree, num_images, 8);
+    m_rs.plan(lay, *rig_stats, num_rigs, 32);
 
     EsScratch& s = per_thread<EsScratch>();
     ISX_TRY(s.begin(device, st, lay.at, upload_bytes));
@@ -479,35 +475,32 @@ int es_call(int num_images, const int* image_sizes_wh, int num_pairs, const int*
     std::memcpy(pin + o_rigs, rigs.data(), rigs.size() * sizeof(EsRig));
     std::memcpy(pin + o_prs, prs.data(), prs.size() * sizeof(EsPair));
     std::memcpy(pin + o_sizes, image_sizes_wh, (size_t)num_images * 8);
-    if (host_H)
-        for (long long r = 0; r < 3ll * num_pairs; ++r) std::memcpy(pin + o_H + (size_t)r * 24, (const char*)H->data + (size_t)r * H->step, 24);
-    if (host_stats)
-        for (int r = 0; r < num_pairs; ++r) std::memcpy(pin + o_stats + (size_t)r * 8, (const char*)stats->data + (size_t)r * stats->step, 8);
-    if (host_fin)
-        for (int r = 0; r < num_images; ++r) std::memcpy(pin + o_fin + (size_t)r * 32, (const char*)focals_in->data + (size_t)r * focals_in->step, 32);
+    m_H.fill(pin);
+    m_stats.fill(pin);
+    m_fin.fill(pin);
     ISX_TRY(s.upload(st, upload_bytes));
 
     // ---- one launch ----
     EsCall c;
     c.rigs = (const EsRig*)(dev + o_rigs); c.pairs = (const EsPair*)(dev + o_prs); c.sizes = (const int*)(dev + o_sizes);
-    c.H = host_H ? (const double*)(dev + o_H) : (const double*)H->data; c.H_step = host_H ? 24 : (long long)H->step;
-    c.stats = host_stats ? (const int*)(dev + o_stats) : (const int*)stats->data; c.stats_step = host_stats ? 8 : (long long)stats->step;
-    c.fin = !focals_in ? nullptr : host_fin ? (const double*)(dev + o_fin) : (const double*)focals_in->data;
-    c.fin_step = !focals_in ? 0 : host_fin ? 32 : (long long)focals_in->step;
+    m_H.bind(dev, c.H, c.H_step);
+    m_stats.bind(dev, c.stats, c.stats_step);
+    c.fin = nullptr; c.fin_step = 0;
+    if (focals_in) m_fin.bind(dev, c.fin, c.fin_step);
     c.dual = (double*)(dev + o_dual);
-    c.cams = cameras->device < 0 ? (double*)(dev + o_cams) : (double*)cameras->data; c.cams_step = cameras->device < 0 ? 128 : (long long)cameras->step;
-    c.kr = kr32->device < 0 ? (float*)(dev + o_kr) : (float*)kr32->data; c.kr_step = kr32->device < 0 ? 72 : (long long)kr32->step;
-    c.tree = tree->device < 0 ? (int*)(dev + o_tree) : (int*)tree->data; c.tree_step = tree->device < 0 ? 8 : (long long)tree->step;
-    c.rs = rig_stats->device < 0 ? (int*)(dev + o_rs) : (int*)rig_stats->data; c.rs_step = rig_stats->device < 0 ? 32 : (long long)rig_stats->step;
+    m_cams.bind(dev, c.cams, c.cams_step);
+    m_kr.bind(dev, c.kr, c.kr_step);
+    m_tree.bind(dev, c.tree, c.tree_step);
+    m_rs.bind(dev, c.rs, c.rs_step);
     ISX_LAUNCH("estimator_rigs", (double)num_pairs * 88.0 + (double)num_images * 216.0, st, k_es_rigs, dim3((unsigned)num_rigs), dim3(ES_THREADS), 0, c);
     ISX_TRY(s.ran(st));
 
     // ---- host outputs ----
-    if (cameras->device < 0 || kr32->device < 0 || tree->device < 0 || rig_stats->device < 0) {
-        if (cameras->device < 0) ISX_TRY(copy_rows_back(*cameras, dev + o_cams, num_images, 128, st));
-        if (kr32->device < 0) ISX_TRY(copy_rows_back(*kr32, dev + o_kr, num_images, 72, st));
-        if (tree->device < 0) ISX_TRY(copy_rows_back(*tree, dev + o_tree, num_images, 8, st));
-        if (rig_stats->device < 0) ISX_TRY(copy_rows_back(*rig_stats, dev + o_rs, num_rigs, 32, st));
+    if (m_cams.staged || m_kr.staged || m_tree.staged || m_rs.staged) {
+        ISX_TRY(m_cams.back(dev, num_images, st));
+        ISX_TRY(m_kr.back(dev, num_images, st));
+        ISX_TRY(m_tree.back(dev, num_images, st));
+        ISX_TRY(m_rs.back(dev, num_rigs, st));
         ISX_HIP(hipStreamSynchronize(st));
     }
     if (info) { info[0] = num_rigs; info[1] = 1; }

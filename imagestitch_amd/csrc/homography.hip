@@ -68,18 +68,9 @@ struct HgCall {
     int lm_max_iters;                             // k_hg_pairs<true> only: maxIters of the LM solver (10 at R:672)
 };
 
-template <class T>
-__device__ __forceinline__ T* as_global(T* p) {      // as in match.hip: a wave-uniform table pointer the compiler may load through global_load
-    const unsigned long long u = (unsigned long long)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-    return (T*)(__attribute__((address_space(1))) T*)(((unsigned long long)hi << 32) | lo);
-}
-
 struct HgLds {
     double* A; double* V; double* W; int* indR; int* indC; int* sub; int* found; int* att;
 };
-
-__device__ __forceinline__ const float* hg_row(const float* pts, long long step, int i) { return (const float*)((const char*)pts + (long long)i * step); }
 
 __device__ __forceinline__ double hg_det3(const double* a) {
     return (a[0] * (a[4] * a[8] - a[7] * a[5]) - a[1] * (a[3] * a[8] - a[6] * a[5])) + a[2] * (a[3] * a[7] - a[6] * a[4]);
@@ -272,11 +263,11 @@ __device__ __forceinline__ double hg_pick_y(int j, double X, double Y, double y)
 __device__ bool hg_run_kernel_wave(const HgLds& s, int lane, const float* pts, long long step, int count, double* H) {
     const int col = (lane & 3) < 2 ? (lane & 3) + 2 : (lane & 3) - 2;      // lanes 0..3: dst.x, dst.y, src.x, src.y (cm.x, cm.y, cM.x, cM.y)
     double sum = 0.0;
-    for (int i = 0; i < count; ++i) sum += hg_row(pts, step, i)[col];
+    for (int i = 0; i < count; ++i) sum += row_ptr(pts, i, step)[col];
     sum /= count;
     const double cmx = __shfl(sum, 0), cmy = __shfl(sum, 1), cMx = __shfl(sum, 2), cMy = __shfl(sum, 3);
     double sa = 0.0;
-    for (int i = 0; i < count; ++i) sa += fabs(hg_row(pts, step, i)[col] - sum);
+    for (int i = 0; i < count; ++i) sa += fabs(row_ptr(pts, i, step)[col] - sum);
     double smx = __shfl(sa, 0), smy = __shfl(sa, 1), sMx = __shfl(sa, 2), sMy = __shfl(sa, 3);
     if (fabs(smx) < DBL_EPSILON || fabs(smy) < DBL_EPSILON || fabs(sMx) < DBL_EPSILON || fabs(sMy) < DBL_EPSILON) return false;
     smx = count / smx; smy = count / smy; sMx = count / sMx; sMy = count / sMy;
@@ -287,7 +278,7 @@ __device__ bool hg_run_kernel_wave(const HgLds& s, int lane, const float* pts, l
     k += j;
     double acc = 0.0;
     for (int i = 0; i < count; ++i) {
-        const float* r = hg_row(pts, step, i);
+        const float* r = row_ptr(pts, i, step);
         const double x = (r[2] - cmx) * smx, y = (r[3] - cmy) * smy;
         const double X = (r[0] - cMx) * sMx, Y = (r[1] - cMy) * sMy;
         acc = acc + (hg_pick(j, X, Y, x) * hg_pick(k, X, Y, x) + hg_pick_y(j, X, Y, y) * hg_pick_y(k, X, Y, y));
@@ -361,7 +352,7 @@ __device__ __forceinline__ void hg_load4(const float* pts, long long step, int i
     const int idx[4] = {i0, i1, i2, i3};
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const float* r = hg_row(pts, step, idx[i]);
+        const float* r = row_ptr(pts, idx[i], step);
         q[i][0] = r[0]; q[i][1] = r[1]; q[i][2] = r[2]; q[i][3] = r[3];
     }
 }
@@ -637,7 +628,7 @@ __device__ void hg_find(const HgLds& s, int lane, const float* pts, long long st
                     int good = 0;
                     for (int i0 = 0; i0 < n; i0 += WAVE) {
                         const int i = i0 + lane;
-                        const bool in = i < n && hg_inlier(Hf, hg_row(pts, step, i), t);
+                        const bool in = i < n && hg_inlier(Hf, row_ptr(pts, i, step), t);
                         good += __popcll(__ballot(in));
                     }
                     if (good > max(max_good, 3)) {                    // R:207
@@ -661,11 +652,11 @@ __device__ void hg_find(const HgLds& s, int lane, const float* pts, long long st
     for (int i0 = 0; i0 < n; i0 += WAVE) {
         const int i = i0 + lane;
         bool in = false;
-        if (i < n) in = direct || (out.ok && hg_inlier(Hf, hg_row(pts, step, i), t));
+        if (i < n) in = direct || (out.ok && hg_inlier(Hf, row_ptr(pts, i, step), t));
         const unsigned long long bal = __ballot(in);
         if (i < n && mask && !direct) mask[(long long)i * mask_step] = in ? 1 : 0;
         if (in) {
-            const float* r = hg_row(pts, step, i);
+            const float* r = row_ptr(pts, i, step);
             float* o = work + 4ll * (m + __popcll(bal & ((1ull << lane) - 1ull)));
             o[0] = r[0]; o[1] = r[1]; o[2] = r[2]; o[3] = r[3];
         }
@@ -744,13 +735,13 @@ __global__ __launch_bounds__(HG_CHUNK) void k_hg_pairs(HgCall c) {
         double v = Hout[0];
 #pragma unroll
         for (int i = 1; i < 9; ++i) v = lane == i ? Hout[i] : v;
-        ((double*)((char*)as_global(c.H) + (3ll * p + lane / 3) * c.H_step))[lane % 3] = v;
+        row_ptr(as_global(c.H), 3ll * p + lane / 3, c.H_step)[lane % 3] = v;
     }
     if (lane < NST) {
         int v = st[0];
 #pragma unroll
         for (int i = 1; i < NST; ++i) v = lane == i ? st[i] : v;
-        ((int*)((char*)as_global(c.stats) + (long long)p * c.stats_step))[lane] = v;
+        row_ptr(as_global(c.stats), p, c.stats_step)[lane] = v;
     }
     if (lane == 0) as_global(c.conf)[p] = conf;
 }
@@ -774,21 +765,17 @@ int hg_call(bool lm, int lm_max_iters, const char* who, int num_pairs, const isx
     ISX_CHECK_ARG(reproj_thresh == reproj_thresh, ISX_ERR_INVALID, "%s: reproj_thresh is not a number", who);
     ISX_CHECK_ARG(!lm || (lm_max_iters >= 1 && lm_max_iters <= 1000), ISX_ERR_INVALID, "%s: lm_max_iters %d is not in [1, 1000]", who, lm_max_iters);
     if (reproj_thresh <= 0) reproj_thresh = 3;                                                                                   // R:636
-    bool any_host_out = false, any_host_mask = false;
     if (num_pairs > 0) {
         ISX_TRY(check_mat_holds(*counts, ISX_32SC1, 1, num_pairs, 4, STOP_NO_ROW_PRESENT, device, who, "counts", 0));
         ISX_TRY(check_mat_holds(*H, ISX_64FC1, 3ll * num_pairs, 3, 8, STOP_NO_ROW_PRESENT, device, who, "H", 0));
         ISX_TRY(check_mat_holds(*stats, ISX_32SC1, num_pairs, nst, 4, STOP_NO_ROW_PRESENT, device, who, "stats", 0));
         ISX_TRY(check_mat_holds(*conf, ISX_64FC1, 1, num_pairs, 8, STOP_NO_ROW_PRESENT, device, who, "conf", 0));
-        any_host_out = H->device < 0 || stats->device < 0 || conf->device < 0;
     }
     for (int p = 0; p < num_pairs; ++p) {
         ISX_CHECK_ARG(points[p].rows >= 0 && inlier_masks[p].rows >= 0, ISX_ERR_INVALID, "%s: pair %d: negative rows", who, p);
         ISX_TRY(check_mat_holds(points[p], ISX_32FC1, 0, 4, 4, STOP_NO_ROW_PRESENT, device, who, "points", p));
         ISX_TRY(check_mat_holds(inlier_masks[p], ISX_8UC1, 0, 1, 1, STOP_NO_ROW_PRESENT, device, who, "inlier_masks", p));
-        any_host_mask |= inlier_masks[p].device < 0 && inlier_masks[p].rows > 0 && points[p].rows > 0;
     }
-    any_host_out |= any_host_mask;
     ISX_HIP(hipSetDevice(device));
     hipStream_t st = (hipStream_t)hip_stream;
     ISX_TRY(refuse_capture(st, who, "the call uploads its tables and may stage host mats"));
@@ -801,28 +788,31 @@ int hg_call(bool lm, int lm_max_iters, const char* who, int num_pairs, const isx
     std::vector<HgPair> prs((size_t)num_pairs);
     std::vector<int> cap((size_t)num_pairs), up_rows((size_t)num_pairs, 0);
     const int* h_counts = counts->device < 0 ? (const int*)counts->data : nullptr;
+    StagedMat m_counts, m_H, m_stats, m_conf;
+    std::vector<StagedMat> m_pts((size_t)num_pairs), m_mask((size_t)num_pairs);
     Bump lay;
     const size_t o_prs = lay.take(prs.size() * sizeof(HgPair));
-    const size_t o_counts = h_counts ? lay.take((size_t)num_pairs * 4) : 0;
-    std::vector<size_t> o_pts((size_t)num_pairs, 0), o_wa((size_t)num_pairs, 0), o_wb((size_t)num_pairs, 0), o_mask((size_t)num_pairs, 0);
+    m_counts.plan(lay, *counts, 1, (size_t)num_pairs * 4);
+    std::vector<size_t> o_wa((size_t)num_pairs, 0), o_wb((size_t)num_pairs, 0);
     for (int p = 0; p < num_pairs; ++p) {
         cap[p] = std::min(points[p].rows, inlier_masks[p].rows);
-        if (cap[p] > 0 && points[p].device < 0) {
-            // a host mat: the rows a host count names, else every row the kernel may read
-            up_rows[p] = h_counts ? std::min(std::max(h_counts[p], 0), cap[p]) : cap[p];
-            o_pts[p] = lay.take((size_t)up_rows[p] * 16);
-        }
+        // the rows the kernel may read; of a host mat, those a host count names
+        up_rows[p] = points[p].device < 0 && h_counts ? std::min(std::max(h_counts[p], 0), cap[p]) : cap[p];
+        m_pts[p].plan(lay, points[p], up_rows[p], 16);
     }
     const size_t upload_bytes = lay.at;
     for (int p = 0; p < num_pairs; ++p) {
         o_wa[p] = lay.take((size_t)cap[p] * 16);
         o_wb[p] = lay.take((size_t)cap[p] * 16);
     }
-    const size_t o_H = H->device < 0 ? lay.take((size_t)num_pairs * 72) : 0;
-    const size_t o_stats = stats->device < 0 ? lay.take((size_t)num_pairs * 4 * nst) : 0;
-    const size_t o_conf = conf->device < 0 ? lay.take((size_t)num_pairs * 8) : 0;
-    for (int p = 0; p < num_pairs; ++p)
-        if (cap[p] > 0 && inlier_masks[p].device < 0) o_mask[p] = lay.take((size_t)cap[p]);
+    m_H.plan(lay, *H, 3ll * num_pairs, 24);
+    m_stats.plan(lay, *stats, num_pairs, (size_t)4 * nst);
+    m_conf.plan(lay, *conf, 1, (size_t)num_pairs * 8);
+    bool any_host_mask = false;
+    for (int p = 0; p < num_pairs; ++p) {
+        m_mask[p].plan(lay, inlier_masks[p], cap[p], 1);
+        any_host_mask |= m_mask[p].staged;
+    }
 
     HgScratch& s = per_thread<HgScratch>();
     if (s.device != device || !s.lds_set) {                       // before begin(), so before this stream is made to wait for another
@@ -838,34 +828,24 @@ int hg_call(bool lm, int lm_max_iters, const char* who, int num_pairs, const isx
     for (int p = 0; p < num_pairs; ++p) {
         HgPair& P = prs[p];
         std::memset(&P, 0, sizeof(P));
-        P.cap = cap[p];
+        P.cap = up_rows[p];                                       // of a staged mat, the staged rows are what the kernel may read
         if (cap[p] == 0) continue;
-        const isx_mat& pm = points[p];
-        if (pm.device < 0) {
-            for (int r = 0; r < up_rows[p]; ++r) std::memcpy(pin + o_pts[p] + (size_t)r * 16, (const char*)pm.data + (size_t)r * pm.step, 16);
-            P.points = (const float*)(dev + o_pts[p]); P.points_step = 16;
-            P.cap = up_rows[p];                                   // the staged rows are what the kernel may read
-        } else {
-            P.points = (const float*)pm.data; P.points_step = (long long)pm.step;
-        }
-        const isx_mat& mm = inlier_masks[p];
-        P.mask = mm.device < 0 ? (unsigned char*)(dev + o_mask[p]) : (unsigned char*)mm.data;
-        P.mask_step = mm.device < 0 ? 1 : (long long)mm.step;
+        m_pts[p].fill(pin);
+        m_pts[p].bind(dev, P.points, P.points_step);
+        m_mask[p].bind(dev, P.mask, P.mask_step);
         P.work_a = (float*)(dev + o_wa[p]); P.work_b = (float*)(dev + o_wb[p]);
     }
     std::memcpy(pin + o_prs, prs.data(), prs.size() * sizeof(HgPair));
-    if (h_counts) std::memcpy(pin + o_counts, h_counts, (size_t)num_pairs * 4);
+    m_counts.fill(pin);
     ISX_TRY(s.upload(st, upload_bytes));
 
     // ---- one launch ----
     HgCall c;
     c.pairs = (const HgPair*)(dev + o_prs);
-    c.counts = h_counts ? (const int*)(dev + o_counts) : (const int*)counts->data;
-    c.H = H->device < 0 ? (double*)(dev + o_H) : (double*)H->data;
-    c.H_step = H->device < 0 ? 24 : (long long)H->step;
-    c.stats = stats->device < 0 ? (int*)(dev + o_stats) : (int*)stats->data;
-    c.stats_step = stats->device < 0 ? 4 * nst : (long long)stats->step;
-    c.conf = conf->device < 0 ? (double*)(dev + o_conf) : (double*)conf->data;
+    m_counts.bind(dev, c.counts);
+    m_H.bind(dev, c.H, c.H_step);
+    m_stats.bind(dev, c.stats, c.stats_step);
+    m_conf.bind(dev, c.conf);
     c.thresh = reproj_thresh; c.confidence = confidence;
     c.max_iters = max_iters; c.thresh1 = num_matches_thresh1; c.thresh2 = num_matches_thresh2;
     c.lm_max_iters = lm_max_iters;
@@ -874,24 +854,22 @@ int hg_call(bool lm, int lm_max_iters, const char* who, int num_pairs, const isx
     ISX_TRY(s.ran(st));
 
     // ---- host outputs ----
-    if (any_host_out) {
+    if (m_H.staged || m_stats.staged || m_conf.staged || any_host_mask) {
         std::vector<int> cnt_tmp;
         const int* cnt = h_counts;
         if (any_host_mask && !h_counts) {
             cnt_tmp.resize((size_t)num_pairs);
-            ISX_HIP(hipMemcpyAsync(cnt_tmp.data(), counts->data, (size_t)num_pairs * 4, hipMemcpyDeviceToHost, st));
-            ISX_HIP(hipStreamSynchronize(st));
+            ISX_TRY(counts_to_host(cnt_tmp.data(), (const int*)counts->data, num_pairs, st));
             cnt = cnt_tmp.data();
         }
-        if (H->device < 0) ISX_TRY(copy_rows_back(*H, dev + o_H, 3ll * num_pairs, 24, st));
-        if (stats->device < 0) ISX_TRY(copy_rows_back(*stats, dev + o_stats, num_pairs, 4 * nst, st));
-        if (conf->device < 0) ISX_HIP(hipMemcpyAsync(conf->data, dev + o_conf, (size_t)num_pairs * 8, hipMemcpyDeviceToHost, st));
+        ISX_TRY(m_H.back(dev, 3ll * num_pairs, st));
+        ISX_TRY(m_stats.back(dev, num_pairs, st));
+        ISX_TRY(m_conf.back(dev, 1, st));
         for (int p = 0; p < num_pairs; ++p) {
-            const isx_mat& mm = inlier_masks[p];
-            if (cap[p] == 0 || mm.device >= 0) continue;
+            if (!m_mask[p].staged) continue;
             const int n = std::min(std::max(cnt[p], 0), cap[p]);
             if (n < num_matches_thresh1 || n == 0) continue;      // R:836: the mask is not written
-            ISX_TRY(copy_rows_back(mm, dev + o_mask[p], n, 1, st));
+            ISX_TRY(m_mask[p].back(dev, n, st));
         }
         ISX_HIP(hipStreamSynchronize(st));
     }

@@ -118,6 +118,25 @@ __device__ __forceinline__ f32x2 div_by_refined(f32x2 a, f32x2 z, f32x2 r1) {
     return pk_fma(e, r1, q);
 }
 
+// A pointer that was LOADED (from the table) is a generic pointer to the compiler, and generic pointers make FLAT loads - counted on lgkmcnt as
+// well as vmcnt, so every LDS wait of a kernel drains them too (collapse_roll.inc, gcp / ROLL_G, tells the same story about pointers that went
+// through an asm statement).  Pointers that arrive in the kernel arguments (TileSet) are known to be global.  The table's pointers are said to
+// be global where they are loaded: a round trip through address space 1 that the optimiser cannot fold away (a plain cast pair is folded, and
+// __builtin_assume(!is_shared && !is_private) is not picked up: both measured) - the two halves go through v_readfirstlane, which is free for a
+// value that already sits in scalar registers (a tile index is wave-uniform by construction and its descriptor comes from s_load; where the
+// compiler cannot see that, inside a per-lane branch, it is two instructions) and from whose result the address-space inference types every
+// access behind it (round 6: 10 - 54 flat_load per *_tab kernel before, none after; tools/isa_flat.py, tests/test_isa_flat.py).
+// The blend's tile tables, and the wave-uniform table pointers of the matcher and the homography.
+template <class T>
+__device__ __forceinline__ T* as_global(T* p) {
+    const unsigned long long u = (unsigned long long)p;
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
+    return (T*)(__attribute__((address_space(1))) T*)(((unsigned long long)hi << 32) | lo);
+}
+// row `row` of a mat whose rows lie `step` bytes apart
+template <class T>
+__device__ __forceinline__ T* row_ptr(T* base, long long row, long long step) { return (T*)((char*)base + row * step); }
+
 // f16 storage (RNE both ways; conversions are exact widening on load)
 __device__ __forceinline__ unsigned short f2h_bits(float v) { return __half_as_ushort(__float2half_rn(v)); }
 __device__ __forceinline__ float h2f_bits(unsigned short b) { return __half2float(__ushort_as_half(b)); }

@@ -57,13 +57,6 @@ struct MtPair {
     int* count;
 };
 
-template <class T>
-__device__ __forceinline__ T* as_global(T* p) {      // as in blend.hip: a wave-uniform table pointer the compiler may load through global_load
-    const unsigned long long u = (unsigned long long)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-    return (T*)(__attribute__((address_space(1))) T*)(((unsigned long long)hi << 32) | lo);
-}
-
 // blocks: (image, first row) per block
 __global__ __launch_bounds__(MT_PACK_ROWS * 8) void k_mt_pack(const MtImage* __restrict__ imgs, const int2* __restrict__ blocks, unsigned* __restrict__ packed) {
     imgs = as_global(imgs); blocks = as_global(blocks); packed = as_global(packed);
@@ -236,27 +229,17 @@ int isx_match_features(int num_images, const isx_mat* descriptors, const isx_mat
     }
     ISX_CHECK_ARG(total_rows <= ISX_MATCH_MAX_TOTAL_ROWS, ISX_ERR_UNSUPPORTED, "%s: %lld descriptor rows in all (at most %d)", who, total_rows, ISX_MATCH_MAX_TOTAL_ROWS);
     int searched = 0;
-    bool any_host_out = false;
-    if (num_pairs > 0) {
-        ISX_TRY(check_mat_holds(*counts, ISX_32SC1, 1, num_pairs, 4, STOP_NO_ROW_WANTED, device, who, "counts", 0));
-        any_host_out |= counts->device < 0;
-    }
+    if (num_pairs > 0) ISX_TRY(check_mat_holds(*counts, ISX_32SC1, 1, num_pairs, 4, STOP_NO_ROW_WANTED, device, who, "counts", 0));
     for (int p = 0; p < num_pairs; ++p) {
         const int nf = descriptors[pairs_ij[2 * p]].rows, nt = descriptors[pairs_ij[2 * p + 1]].rows;
         const bool run = nf > 0 && nt > 0;
         const long long rows = run ? (long long)nf + nt : 0;
         searched += run;
         ISX_TRY(check_mat_holds(matches[p], ISX_32SC1, rows, 3, 4, STOP_NO_ROW_WANTED, device, who, "matches", p));
-        any_host_out |= run && matches[p].device < 0;
-        if (points) {
-            ISX_TRY(check_mat_holds(points[p], ISX_32FC1, rows, 4, 4, STOP_NO_ROW_WANTED, device, who, "points", p));
-            any_host_out |= run && points[p].device < 0;
-        }
+        if (points) ISX_TRY(check_mat_holds(points[p], ISX_32FC1, rows, 4, 4, STOP_NO_ROW_WANTED, device, who, "points", p));
         if (knn)
-            for (int d = 0; d < 2; ++d) {
+            for (int d = 0; d < 2; ++d)
                 ISX_TRY(check_mat_holds(knn[2 * p + d], ISX_32SC1, run ? (d ? nt : nf) : 0, 4, 4, STOP_NO_ROW_WANTED, device, who, "knn", 2 * p + d));
-                any_host_out |= run && knn[2 * p + d].device < 0;
-            }
     }
     ISX_HIP(hipSetDevice(device));
     hipStream_t st = (hipStream_t)hip_stream;
@@ -311,24 +294,25 @@ int isx_match_features(int num_images, const isx_mat* descriptors, const isx_mat
     Bump lay;
     const size_t o_imgs = lay.take(imgs.size() * sizeof(MtImage)), o_prs = lay.take(prs.size() * sizeof(MtPair));
     const size_t o_work = lay.take(work.size() * sizeof(int4)), o_pblk = lay.take(pack_blocks.size() * sizeof(int2));
-    std::vector<size_t> o_kp((size_t)num_images, 0);
+    std::vector<StagedMat> m_kp((size_t)num_images);
     if (keypoints)
-        for (int i = 0; i < num_images; ++i)
-            if (imgs[i].rows > 0 && keypoints[i].device < 0) o_kp[i] = lay.take((size_t)imgs[i].rows * 8);
+        for (int i = 0; i < num_images; ++i) m_kp[i].plan(lay, keypoints[i], imgs[i].rows, 8);
     const size_t o_packed = lay.take(0);
     const size_t upload_bytes = o_packed + (size_t)host_rows * 32;
     lay.take((size_t)(host_rows + dev_rows) * 32);
     const size_t o_part = lay.take((size_t)part_count * sizeof(uint2)), o_acc = lay.take((size_t)acc_count * sizeof(int));
-    const size_t o_counts = counts->device < 0 ? lay.take((size_t)num_pairs * 4) : 0;
-    std::vector<size_t> o_m((size_t)num_pairs, 0), o_p((size_t)num_pairs, 0), o_k((size_t)2 * num_pairs, 0);
+    StagedMat m_counts;
+    m_counts.plan(lay, *counts, 1, (size_t)num_pairs * 4);
+    std::vector<StagedMat> m_m((size_t)num_pairs), m_p((size_t)num_pairs), m_k((size_t)2 * num_pairs);
+    bool any_host_out = m_counts.staged;
     for (int p = 0; p < num_pairs; ++p) {
         const int nf = imgs[prs[p].from].rows, nt = imgs[prs[p].to].rows;
         if (nf == 0 || nt == 0) continue;
-        if (matches[p].device < 0) o_m[p] = lay.take((size_t)(nf + nt) * 12);
-        if (points && points[p].device < 0) o_p[p] = lay.take((size_t)(nf + nt) * 16);
+        m_m[p].plan(lay, matches[p], nf + nt, 12);
+        if (points) m_p[p].plan(lay, points[p], nf + nt, 16);
         if (knn)
-            for (int d = 0; d < 2; ++d)
-                if (knn[2 * p + d].device < 0) o_k[2 * p + d] = lay.take((size_t)(d ? nt : nf) * 16);
+            for (int d = 0; d < 2; ++d) m_k[2 * p + d].plan(lay, knn[2 * p + d], d ? nt : nf, 16);
+        any_host_out |= m_m[p].staged || m_p[p].staged || m_k[2 * p].staged || m_k[2 * p + 1].staged;
     }
 
     MtScratch& s = per_thread<MtScratch>();
@@ -344,30 +328,19 @@ int isx_match_features(int num_images, const isx_mat* descriptors, const isx_mat
         if (m.device < 0)
             for (int r = 0; r < m.rows; ++r) std::memcpy(pin + o_packed + ((size_t)I.off + r) * 32, (const char*)m.data + (size_t)r * m.step, 32);
         if (!keypoints) continue;
-        const isx_mat& kp = keypoints[i];
-        if (kp.device < 0) {
-            for (int r = 0; r < kp.rows; ++r) std::memcpy(pin + o_kp[i] + (size_t)r * 8, (const char*)kp.data + (size_t)r * kp.step, 8);
-            I.kp = (const unsigned char*)dev + o_kp[i]; I.kp_step = 8;
-        } else {
-            I.kp = (const unsigned char*)kp.data; I.kp_step = (long long)kp.step;
-        }
+        m_kp[i].fill(pin);
+        m_kp[i].bind(dev, I.kp, I.kp_step);
     }
+    int* d_counts;
+    m_counts.bind(dev, d_counts);
     for (int p = 0; p < num_pairs; ++p) {
         MtPair& P = prs[p];
-        P.count = counts->device < 0 ? (int*)(dev + o_counts) + p : (int*)counts->data + p;
+        P.count = d_counts + p;
         if (imgs[P.from].rows == 0 || imgs[P.to].rows == 0) continue;
-        P.matches = matches[p].device < 0 ? (int*)(dev + o_m[p]) : (int*)matches[p].data;
-        P.matches_step = matches[p].device < 0 ? 12 : (long long)matches[p].step;
-        if (points) {
-            P.points = points[p].device < 0 ? (float*)(dev + o_p[p]) : (float*)points[p].data;
-            P.points_step = points[p].device < 0 ? 16 : (long long)points[p].step;
-        }
+        m_m[p].bind(dev, P.matches, P.matches_step);
+        if (points) m_p[p].bind(dev, P.points, P.points_step);
         if (knn)
-            for (int d = 0; d < 2; ++d) {
-                const isx_mat& km = knn[2 * p + d];
-                P.knn[d] = km.device < 0 ? (int*)(dev + o_k[2 * p + d]) : (int*)km.data;
-                P.knn_step[d] = km.device < 0 ? 16 : (long long)km.step;
-            }
+            for (int d = 0; d < 2; ++d) m_k[2 * p + d].bind(dev, P.knn[d], P.knn_step[d]);
     }
     std::memcpy(pin + o_imgs, imgs.data(), imgs.size() * sizeof(MtImage));
     std::memcpy(pin + o_prs, prs.data(), prs.size() * sizeof(MtPair));
@@ -397,25 +370,13 @@ int isx_match_features(int num_images, const isx_mat* descriptors, const isx_mat
 
     // ---- host outputs: the counts first, then the rows they name ----
     if (any_host_out) {
-        std::vector<int> cnt_tmp;
-        const int* cnt;
-        if (counts->device < 0) {
-            ISX_HIP(hipMemcpyAsync(counts->data, dev + o_counts, (size_t)num_pairs * 4, hipMemcpyDeviceToHost, st));
-            cnt = (const int*)counts->data;
-        } else {
-            cnt_tmp.resize((size_t)num_pairs);
-            ISX_HIP(hipMemcpyAsync(cnt_tmp.data(), counts->data, (size_t)num_pairs * 4, hipMemcpyDeviceToHost, st));
-            cnt = cnt_tmp.data();
-        }
-        ISX_HIP(hipStreamSynchronize(st));
+        std::vector<int> cnt_tmp(m_counts.staged ? 0 : (size_t)num_pairs);      // a host counts mat takes them itself
+        int* const cnt = m_counts.staged ? (int*)counts->data : cnt_tmp.data();
+        ISX_TRY(counts_to_host(cnt, d_counts, num_pairs, st));
         for (int p = 0; p < num_pairs; ++p) {
-            const int nf = imgs[prs[p].from].rows, nt = imgs[prs[p].to].rows;
-            if (nf == 0 || nt == 0) continue;
-            if (matches[p].device < 0) ISX_TRY(copy_rows_back(matches[p], dev + o_m[p], cnt[p], 12, st));
-            if (points && points[p].device < 0) ISX_TRY(copy_rows_back(points[p], dev + o_p[p], cnt[p], 16, st));
-            if (knn)
-                for (int d = 0; d < 2; ++d)
-                    if (knn[2 * p + d].device < 0) ISX_TRY(copy_rows_back(knn[2 * p + d], dev + o_k[2 * p + d], d ? nt : nf, 16, st));
+            ISX_TRY(m_m[p].back(dev, cnt[p], st));
+            ISX_TRY(m_p[p].back(dev, cnt[p], st));
+            for (int d = 0; d < 2; ++d) ISX_TRY(m_k[2 * p + d].back(dev, m_k[2 * p + d].rows, st));
         }
         ISX_HIP(hipStreamSynchronize(st));
     }

@@ -1,8 +1,10 @@
 // scratch.hpp — what the per-thread stages share of their host plumbing (DESIGN.md §8 "The stages' per-thread scratch"): the 256-byte
 // carving of a device buffer, the grow-only pinned buffer, the scratch of a stage that uploads its tables (with its two ordering rules), the
-// capture check, a caller's mat against what a call needs, staged rows back to a host mat.  Internal; per_thread<T>() stays in pairwise.hpp.
+// capture check, a caller's mat against what a call needs, staged rows back to a host mat, device counts to the host, and StagedMat: a
+// caller's host-or-device mat as a call's kernels see it.  Internal; per_thread<T>() stays in pairwise.hpp.
 #pragma once
 #include <algorithm>
+#include <cstring>
 
 #include "isx_internal.hpp"
 
@@ -111,11 +113,47 @@ inline int check_mat_holds(const isx_mat& m, int type, long long rows, int cols,
     return ISX_OK;
 }
 
-// rows [0, rows) of a host mat, row_bytes each, back from their dense staged copy on the device
+// rows [0, rows) of a host mat, row_bytes each, back from their dense staged copy on the device (one row: whatever its step says)
 inline int copy_rows_back(const isx_mat& m, const void* staged, long long rows, size_t row_bytes, hipStream_t st) {
     if (rows <= 0) return ISX_OK;
-    ISX_HIP(hipMemcpy2DAsync(m.data, m.step, staged, row_bytes, row_bytes, (size_t)rows, hipMemcpyDeviceToHost, st));
+    if (rows == 1) ISX_HIP(hipMemcpyAsync(m.data, staged, row_bytes, hipMemcpyDeviceToHost, st));
+    else ISX_HIP(hipMemcpy2DAsync(m.data, m.step, staged, row_bytes, row_bytes, (size_t)rows, hipMemcpyDeviceToHost, st));
     return ISX_OK;
 }
+
+// n counts (ints) of a device array on the host, complete on return: a stage reads them before it copies home the rows they name
+inline int counts_to_host(int* host, const int* device_counts, int n, hipStream_t st) {
+    ISX_HIP(hipMemcpyAsync(host, device_counts, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    ISX_HIP(hipStreamSynchronize(st));
+    return ISX_OK;
+}
+
+// A caller's mat as one call's kernels see it.  A device mat is the mat itself.  A host mat is `staged`: a dense copy of its first `rows`
+// rows, `row_bytes` each, inside the stage's `work` - an input in the upload (filled in `pin`), an output behind it (copied home after the
+// launches).  plan() is the one place that says the row width: the space taken, the step the kernels are told and the bytes copied home all
+// come from it.  An input is planned before upload_bytes is read off the Bump, an output after.  A mat of no rows is never staged, and
+// nothing reads or writes it.  A 1 x n mat may be planned as one row of n elements.
+struct StagedMat {
+    const isx_mat* mat = nullptr;
+    size_t row_bytes = 0, off = 0;       // off: of the staged copy in `work`, and in `pin`
+    long long rows = 0;
+    bool staged = false;
+    void plan(Bump& lay, const isx_mat& m, long long rows_, size_t row_bytes_) {
+        mat = &m; rows = rows_; row_bytes = row_bytes_;
+        staged = m.device < 0 && rows > 0;
+        if (staged) off = lay.take((size_t)rows * row_bytes);
+    }
+    template <class T>
+    void bind(char* dev, T*& ptr) const { ptr = (T*)(staged ? dev + off : (char*)mat->data); }
+    template <class T>
+    void bind(char* dev, T*& ptr, long long& step) const { bind(dev, ptr); step = staged ? (long long)row_bytes : (long long)mat->step; }
+    void fill(char* pin) const {         // an input's rows into the upload
+        if (!staged) return;
+        for (long long r = 0; r < rows; ++r) std::memcpy(pin + off + (size_t)r * row_bytes, (const char*)mat->data + (size_t)r * mat->step, row_bytes);
+    }
+    int back(const char* dev, long long n, hipStream_t st) const {      // an output's rows [0, n) home
+        return staged ? copy_rows_back(*mat, dev + off, n, row_bytes, st) : ISX_OK;
+    }
+};
 
 }  // namespace isx

@@ -18,6 +18,23 @@ def _is_device(a):
     return hasattr(a, "is_cuda") and bool(a.is_cuda)
 
 
+def _allocator(dev):
+    """alloc(rows, cols, dtype): an uninitialised CUDA tensor on the torch device `dev`, or a NumPy array where dev is None"""
+    if dev is None:
+        return lambda r, c, dt: np.empty((r, c), dt)
+    import torch
+    return lambda r, c, dt: torch.empty((r, c), dtype=getattr(torch, np.dtype(dt).name), device=dev)
+
+
+def _synchronize(stream, device):
+    """Wait for the stream, or for the whole device where the stream is None or a raw handle."""
+    if hasattr(stream, "synchronize"):
+        stream.synchronize()
+    else:
+        import torch
+        torch.cuda.synchronize(int(device))
+
+
 def _mat(a):
     """as_mat, and a mat without rows for an array / tensor of shape (0, cols): its strides are whatever its history left, its data is never read."""
     if a.shape[0] == 0:
@@ -105,15 +122,7 @@ class FeaturesMatcher:
             self.last_info = (0, 0)
             return []
         on_device = any(_is_device(d) for d in descriptors)
-        if on_device:
-            import torch
-            dev = torch.device("cuda", int(self.device))
-
-            def alloc(r, c, dt):
-                return torch.empty((r, c), dtype=getattr(torch, np.dtype(dt).name), device=dev)
-        else:
-            def alloc(r, c, dt):
-                return np.empty((r, c), dt)
+        alloc = _allocator("cuda:%d" % int(self.device) if on_device else None)
         cap = [rows[i] + rows[j] for i, j in pairs]
         m_all, counts = alloc(sum(cap), 3, np.int32), alloc(1, len(pairs), np.int32)
         p_all = alloc(sum(cap), 4, np.float32) if keypoints is not None else None
@@ -125,9 +134,7 @@ class FeaturesMatcher:
         self.last_outputs["counts"] = counts
         post = self._post_match(alloc, cap, ps, counts)
         if on_device:
-            import torch
-            s = self.stream if hasattr(self.stream, "synchronize") else None
-            s.synchronize() if s is not None else torch.cuda.synchronize(int(self.device))
+            _synchronize(self.stream, self.device)
             cnt = counts.cpu().numpy()[0]
         else:
             cnt = counts[0]

@@ -1,10 +1,12 @@
 """The host plumbing of the per-thread stages (imagestitch_amd/csrc/scratch.hpp and the stages that use it), pinned in three parts.
 
-1. Decisions against a recorded fixture (tests/golden/stage_scratch.json, recorded from the commit before scratch.hpp existed).  For a fixed
-   set of calls of isx_match_features, isx_find_homography, the graph-cut and Voronoi seam finders, the gain feed, isx_seam_estimate_cost,
-   isx_blend_pair_linear and the first BlocksGainCompensator apply, the fixture holds per step the launches per launch name, their summed
-   algorithmic bytes (isx_profile_*) and the `info` outputs.  Launches must match exactly, bytes to a relative 1e-9 (see
-   tests/test_gpu_warp_plan.py).  Every output is also compared with the model or oracle its own suite uses.  The graph cut's sweeps
+1. Decisions against a recorded fixture (tests/golden/stage_scratch.json, recorded from the commit before scratch.hpp existed; the
+   estimator's entries - estimator-dev, -host, -mixed and -errors - from the commit before StagedMat existed, the last one that spelt every
+   staged mat out by hand).  For a fixed set of calls of isx_match_features, isx_find_homography, isx_estimate_cameras (the host / device
+   cases of its own suite and three rigs in one call; every mat on the device, on the host, and alternating), the graph-cut and Voronoi
+   seam finders, the gain feed, isx_seam_estimate_cost, isx_blend_pair_linear and the first BlocksGainCompensator apply, the fixture holds
+   per step the launches per launch name, their summed algorithmic bytes (isx_profile_*) and the `info` outputs.  Launches must match
+   exactly, bytes to a relative 1e-9 (see tests/test_gpu_warp_plan.py).  Every output is also compared with the model or oracle its own suite uses.  The graph cut's sweeps
    (SWEEPS below) are the exception: how many rounds push-relabel needs depends on the order in which the nodes of one launch see each
    other's pushes - two calls leave different residuals (tests/test_gpu_graphcut_grad.py) - so the host decides their number from
    counters it reads back, not from its arguments.  They are recorded with a count of -1 and the bytes of one launch, as is any other
@@ -15,14 +17,17 @@
 
 2. The cross-stream fence and the pinned upload buffer in use: two different problems at once on two streams with no host synchronisation
    in between, a call with device mats followed at once by one with host mats (which refills the pinned buffer the first call's upload
-   reads), and big / small / release() sequences - for the matcher, the homography and the matcher-then-homography chain.  These pin
-   RESULTS only: a missing fence or a pinned buffer rewritten too early is a race, and a race need not fail on any given run.
+   reads), and big / small / release() sequences - for the matcher, the homography, the matcher-then-homography chain and the estimator.
+   These pin RESULTS only: a missing fence or a pinned buffer rewritten too early is a race, and a race need not fail on any given run.
 
-3. The full message of every refused call that test_errors_leave_the_outputs_untouched of the two suites lists, against the fixture.
+3. The full message of every refused call that test_errors_leave_the_outputs_untouched of the matcher's and the homography's suites
+   lists, and of every one that _refusals() of tests/test_gpu_estimator_guard.py lists plus its capturing stream, against the fixture.
 
     python tests/test_gpu_stage_scratch.py --record      # rewrites the fixture from the library as built (on a GPU)
 """
 import ctypes as C
+import functools
+import gc
 import json
 import os
 import sys
@@ -34,10 +39,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for _p in (ROOT, os.path.dirname(os.path.abspath(__file__)), os.path.join(ROOT, "tools")):      # (run as a script too: --record)
     if _p not in sys.path:
         sys.path.insert(0, _p)
+import estimator_cases as EC  # noqa: E402
 import homography_cases as HC  # noqa: E402
 import match_cases as MC  # noqa: E402
 from helpers import blocks_gain_np as BGM  # noqa: E402
 from helpers import dpseam_grad_np as DPG  # noqa: E402
+from helpers import estimator_np as EM  # noqa: E402
 from helpers import graphcut_grad_np as GG  # noqa: E402
 from helpers import graphcut_np as G  # noqa: E402
 from helpers import homography_np as HM  # noqa: E402
@@ -52,6 +59,7 @@ GOLDEN = os.path.join(ROOT, "tests", "golden", "stage_scratch.json")
 S_I, S_F, S_B = -7777, -7777.25, 0xA5      # what the outputs hold before a call
 SWEEPS = ("graphcut_bfs", "graphcut_bfs_init", "graphcut_count", "graphcut_push", "graphcut_relabel")
 NAMED = HC.named()
+ENAMED = EC.named()
 
 
 def _dev(a):
@@ -196,6 +204,61 @@ def _homography(gpu, oracle):
         _sync()
         rec.note("info", list(b["info"]))
         hg_check(b, wants, name)
+    return rec.done()
+
+
+# ---- the estimator -------------------------------------------------------------------------------------------------------------------------
+ES_SETS = ["complete_9", "focals_given", "two_components_5_3"]      # the cases of the stage's host / device / strided test; focals_given stages focals_in
+ES_RIGS = ["demo_2_images_1_pair", "complete_5", "complete_9"]      # three rigs in one call
+
+
+@functools.lru_cache(maxsize=None)
+def es_problem(name):
+    """(case, model) of a named case of tests/estimator_cases.py, or of ES_RIGS joined ("three-rigs")"""
+    c = EC.join([ENAMED[k] for k in ES_RIGS]) if name == "three-rigs" else ENAMED[name]
+    return c, EM.estimate(c["sizes"], c["pairs"], c["H"], c["stats"], c["rig_first"], c["focals_in"])
+
+
+def es_prepare(prob, where):
+    c = prob[0]
+    put = _placer(where)
+    n, npairs = len(c["sizes"]), len(c["pairs"])
+    nrigs = 1 if c["rig_first"] is None else len(c["rig_first"]) - 1
+    b = dict(case=c)
+    b["H"], b["st"] = put(np.asarray(c["H"], np.float64).reshape(3 * npairs, 3), 0), put(c["stats"], 1)
+    b["cf"] = put(np.zeros((1, npairs)), 2)
+    b["fin"] = None if c["focals_in"] is None else put(c["focals_in"], 3)
+    b["outs"] = [put(np.full((n, 16), S_F, np.float64), 4), put(np.full((n, 18), S_F, np.float32), 5), put(np.full((n, 2), S_I, np.int32), 6),
+                 put(np.full((nrigs, 8), S_I, np.int32), 7)]
+    return b
+
+
+def es_run(b, stream=None):
+    from imagestitch_amd import cameras as cam
+    c = b["case"]
+    b["info"] = cam.estimate_cameras(c["sizes"], c["pairs"], b["H"], b["st"], b["cf"], *b["outs"], rig_first=c["rig_first"], focals_in=b["fin"], stream=stream)
+    return b
+
+
+def es_call(prob, where):
+    b = es_prepare(prob, where)
+    _sync()
+    return es_run(b)
+
+
+def es_check(b, prob, what):
+    from test_gpu_estimator import check
+    check(tuple(_np(a) for a in b["outs"]), prob[1], what)
+
+
+def _estimator(gpu, oracle, where):
+    rec = _Rec()
+    for name in ES_SETS + ["three-rigs"]:
+        prob = es_problem(name)
+        b = rec.step(name, lambda: es_call(prob, where))
+        _sync()
+        rec.note("info", list(b["info"]))
+        es_check(b, prob, (where, name))
     return rec.done()
 
 
@@ -419,10 +482,41 @@ def _homography_errors(gpu, oracle):
     return rec.done()
 
 
+def _estimator_errors(gpu, oracle):
+    """the refused calls that _refusals() of tests/test_gpu_estimator_guard.py lists, in its order, and the capture refusal of that suite"""
+    import torch
+    import test_gpu_estimator_guard as EG
+    from helpers.guarded import guarded
+    rec = _Rec()
+    c = EG._case()
+    ins, outs = EG._mats(c, "device", "aligned", 20)
+    big = dict(cameras=guarded((67, 16), np.float64, "device", "aligned", 31), kr32=guarded((67, 18), np.float32, "device", "aligned", 32),
+               tree=guarded((67, 2), np.int32, "device", "aligned", 33), rig_stats=guarded((2, 8), np.int32, "device", "aligned", 34))
+    for name, code, over in EG._refusals(c):
+        # "65 images": outputs large enough, so that the rig's size alone is what is refused
+        _refused(rec, gpu, name, lambda: EG._call(c, ins, big if "65 images" in name else outs, **over))
+        assert rec.notes["errors"][-1][1] == code, rec.notes["errors"][-1]
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        x = torch.zeros(4, device="cuda")
+    _sync()
+    g = torch.cuda.CUDAGraph()
+    gc.collect()
+    with torch.cuda.graph(g, stream=s, capture_error_mode="relaxed"):
+        x.add_(1.0)
+        _refused(rec, gpu, "a capturing stream", lambda: EG._call(c, ins, outs, stream=s))
+    assert rec.notes["errors"][-1][1] == EG.ERR_STATE
+    EG._untouched(ins, outs)
+    EG._untouched({}, big)
+    return rec.done()
+
+
 CASES = {"match-dev": lambda g, o: _match(g, o, "dev"), "match-host": lambda g, o: _match(g, o, "host"), "match-mixed": lambda g, o: _match(g, o, "mixed"),
          "homography": _homography, "graphcut": _graphcut, "voronoi": _voronoi, "gain-feed": _gain_feed, "seam-estimate": _seam_estimate,
          "blend-pair-linear": _blend_pair_linear, "blocks-gain-apply": _blocks_gain_apply, "match-errors": _match_errors,
-         "homography-errors": _homography_errors}
+         "homography-errors": _homography_errors, "estimator-dev": lambda g, o: _estimator(g, o, "dev"),
+         "estimator-host": lambda g, o: _estimator(g, o, "host"), "estimator-mixed": lambda g, o: _estimator(g, o, "mixed"),
+         "estimator-errors": _estimator_errors}
 
 
 @pytest.fixture(scope="module")
@@ -499,16 +593,20 @@ def _stage(name):
                 lambda b, p, what: mt_check(b, p[3], what))
     if name == "homography":
         return _hg_two(), lambda p, where: hg_prepare(p[0], where, where, where, where), hg_run, lambda b, p, what: hg_check(b, p[1], what)
+    if name == "estimator":      # 17 images and 136 pairs, then 5 and 10
+        return [es_problem("complete_17"), es_problem("complete_5")], es_prepare, es_run, es_check
     return _chain_two(), _chain_prepare, lambda bs, s: (mt_run(bs[0], s), hg_run(bs[1], s)), _chain_check
 
 
 def _release(gpu):
+    from imagestitch_amd import cameras as cam
     from imagestitch_amd import homography as hg
     gpu.FeaturesMatcher.release()
     hg.release()
+    cam.release()
 
 
-STAGES = ["match", "homography", "chain"]
+STAGES = ["match", "homography", "chain", "estimator"]
 
 
 @pytest.mark.parametrize("stage", STAGES)

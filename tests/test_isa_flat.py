@@ -3,7 +3,7 @@
 A FLAT load is what the compiler emits for a pointer whose address space it cannot prove - here: pointers LOADED from the device-resident tile
 table (TileTab, more than 20 tiles in one mosaic) instead of arriving in the kernel arguments.  It is counted on lgkmcnt as well as vmcnt, so every
 LDS wait drains the global loads too (csrc/collapse_roll.inc tells the story for pointers that went through an asm statement).  Round 5's *_tab
-kernels issued 10 - 54 of them each; `as_global` (csrc/blend.hip) types the table's pointers where they are loaded.  This test disassembles the
+kernels issued 10 - 54 of them each; `as_global` (csrc/isx_device.hpp) types the table's pointers where they are loaded.  This test disassembles the
 code object inside the BUILT objects (imagestitch_amd/csrc/build/*.o - what libimagestitch_hip.so was linked from; ~3 s per object, no GPU)."""
 import os
 import subprocess
