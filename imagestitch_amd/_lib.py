@@ -120,6 +120,9 @@ _SIGS = {
     "isx_homography_release": [],
     "isx_estimate_cameras": [C.c_int, _IP, C.c_int, _IP, C.c_int, _IP, _MP, _MP, _MP, _MP, _MP, _MP, _MP, _MP, _IP, C.c_int, C.c_void_p],
     "isx_estimator_release": [],
+    "isx_bundle_adjust_ray": [C.c_int, _IP, _MP, C.c_int, _IP, _MP, _MP, _MP, _MP, _MP, C.c_int, _IP, _MP, _MP, C.c_double, C.c_int, C.c_double, _MP, _MP,
+                              _MP, _MP, _IP, C.c_int, C.c_void_p],
+    "isx_bundle_release": [],
     "isx_seam_estimate": [_MP, _MP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _MP, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int,
                           C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_void_p],
     "isx_seam_estimate_cost": [_MP, _MP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _MP, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int,
@@ -170,6 +173,7 @@ _SIGS = {
     "isx_selftest_roi_host": [C.c_int, C.c_float, _F9, _F9, C.c_int, C.c_int, C.c_int, _IP, _F9],
     "isx_selftest_warp_point": [C.c_int, C.c_float, _F9, _F9, C.POINTER(C.c_float), C.c_float, C.c_float, C.POINTER(C.c_float)],
     "isx_selftest_exception_barrier": [C.c_int],
+    "isx_selftest_bundle_math": [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)],
     "isx_profile_enable": [C.c_int],
     "isx_profile_reset": [],
     "isx_profile_filter": [C.c_char_p],

@@ -18,6 +18,7 @@
 //   5  the leaf walks, a lane per leaf (queue and distances in LDS), max_dists by LDS atomics, the centers;
 //   6  the walk from the root by one lane (parent, depth), every edge's rotation by a thread of its own, then R level by level.
 #include "isx_device.hpp"
+#include "mat3.hpp"
 #include "pairwise.hpp"
 #include "scratch.hpp"
 
@@ -53,30 +54,6 @@ struct EsCall {
     int* tree; long long tree_step;
     int* rs; long long rs_step;
 };
-
-// Mat::inv() of a 3 x 3 CV_64F: cofactors times the reciprocal determinant, nine zeros for a determinant of exactly 0
-__device__ void es_inv3(const double* m, double* t) {
-    const double a = (m[4] * m[8]) - (m[5] * m[7]);
-    const double b = (m[3] * m[8]) - (m[5] * m[6]);
-    const double c = (m[3] * m[7]) - (m[4] * m[6]);
-    double d = ((m[0] * a) - (m[1] * b)) + (m[2] * c);
-    if (!(d != 0.0)) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) t[i] = 0.0;
-        return;
-    }
-    d = 1.0 / d;
-    t[0] = ((m[4] * m[8]) - (m[5] * m[7])) * d; t[1] = ((m[2] * m[7]) - (m[1] * m[8])) * d; t[2] = ((m[1] * m[5]) - (m[2] * m[4])) * d;
-    t[3] = ((m[5] * m[6]) - (m[3] * m[8])) * d; t[4] = ((m[0] * m[8]) - (m[2] * m[6])) * d; t[5] = ((m[2] * m[3]) - (m[0] * m[5])) * d;
-    t[6] = ((m[3] * m[7]) - (m[4] * m[6])) * d; t[7] = ((m[1] * m[6]) - (m[0] * m[7])) * d; t[8] = ((m[0] * m[4]) - (m[1] * m[3])) * d;
-}
-
-__device__ void es_mul3(const double* a, const double* b, double* o) {
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) o[3 * r + c] = ((a[3 * r] * b[c]) + (a[3 * r + 1] * b[3 + c])) + (a[3 * r + 2] * b[6 + c]);
-}
 
 // C:35-43 and C:45-53 share their tail
 __device__ bool es_pick(double d1, double d2, double v1, double v2, double& f) {

@@ -76,7 +76,7 @@ class BestOf2NearestMatcher(FeaturesMatcher):
         self.last_homography_info = find_homography(points, counts, H, masks, stats, conf, self.reproj_thresh, self.max_iters, self.confidence,
                                                     self.num_matches_thresh1, self.num_matches_thresh2, self.device, self.stream, self.refine,
                                                     self.lm_max_iters)
-        self.last_outputs.update(H=H, stats=stats, conf=conf)      # where the next stage reads them (cameras.py)
+        self.last_outputs.update(H=H, stats=stats, conf=conf, masks=masks)      # where the next stages read them (cameras.py, adjuster.py)
 
         def read_back():
             Hh, sh, ch = (a.cpu().numpy() if _is_device(a) else a for a in (H, stats, conf))

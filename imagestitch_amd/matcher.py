@@ -131,7 +131,7 @@ class FeaturesMatcher:
         ps = [p_all[at[k]:at[k + 1]] for k in range(len(pairs))] if p_all is not None else None
         ks = [alloc(rows[p[d]], 4, np.int32) for p in pairs for d in range(2)] if knn else None
         self.last_info = match_features(descriptors, pairs, self.match_conf, ms, counts, keypoints, img_sizes, ps, ks, self.device, self.stream)
-        self.last_outputs["counts"] = counts
+        self.last_outputs.update(counts=counts, matches=ms, keypoints=keypoints)      # where the later stages read them (adjuster.py)
         post = self._post_match(alloc, cap, ps, counts)
         if on_device:
             _synchronize(self.stream, self.device)

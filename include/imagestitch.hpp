@@ -581,6 +581,88 @@ private:
     int info_[2] = {0, 0};
 };
 
+// adjuster = new detail::BundleAdjusterRay(); adjuster->setConfThresh(1); (*adjuster)(features, pairwise_matches, cameras) (W:189-194 of the
+// reference's cylindrical-projection demo; isx_bundle_adjust_ray): focal and rotation of every camera refined over the inlier matches of
+// every pair with confidence > conf_thresh, one rig - all images of the call - in one launch.  pairwise_matches is the matcher's n * n vector
+// (entry i * n + j with i < j is read: matches, inliers_mask, confidence), features carry the keypoints, cameras are the estimator's.  The
+// center is the estimator's span_tree_centers[0]: hand its rigStats() to setEstimatorStats() before the call - findMaxSpanningTree is not
+// built a second time.  OpenCV's BundleAdjusterBase::estimate, CvLevMarq and cvRodrigues2 are restated; the solve is a Cholesky
+// factorisation with SVBkSb's truncation rule, sin / cos / acos are restated, summation orders are fixed: unpinned
+// (tests/helpers/bundle_np.py is the specification).  Returns false where estimate() would (a NaN parameter) and where the rig passes
+// through (no edge, the estimator's assert): cameras are then unchanged but for K32 / R32.
+class BundleAdjusterRay {
+public:
+    explicit BundleAdjusterRay(int device = 0, void* hip_stream = nullptr) : device_(device), stream_(hip_stream) {}
+    void setStream(void* hip_stream) { stream_ = hip_stream; }
+    void setConfThresh(double conf_thresh) { conf_thresh_ = conf_thresh; }
+    void setTermCriteria(int max_iter, double eps) { max_iter_ = max_iter; eps_ = eps; }      // TermCriteria(EPS + COUNT, 1000, DBL_EPSILON)
+    void setEstimatorStats(const int rig_stats[8]) { std::memcpy(est_, rig_stats, sizeof(est_)); }
+    bool operator()(const std::vector<ImageFeatures>& features, const std::vector<MatchesInfo>& pairwise_matches, std::vector<CameraParams>& cameras) {
+        static_assert(sizeof(DMatch) == 12 && sizeof(Point2f) == 8, "DMatch is a row of queryIdx, trainIdx, distance; Point2f a row of x, y");
+        const int n = (int)features.size();
+        if ((int)pairwise_matches.size() != n * n) throw Exception(ISX_ERR_INVALID, "BundleAdjusterRay: pairwise_matches is not n * n");
+        if ((int)cameras.size() != n) throw Exception(ISX_ERR_INVALID, "BundleAdjusterRay: needs n cameras");
+        std::vector<int> sizes, pij, counts, stats;
+        std::vector<double> conf;
+        std::vector<isx_mat> kp(n), mt, mk;
+        for (int i = 0; i < n; ++i) {
+            sizes.push_back(features[i].img_size.width); sizes.push_back(features[i].img_size.height);
+            kp[i] = host((void*)features[i].keypoints.data(), (int)features[i].keypoints.size(), 2, ISX_32FC1, sizeof(Point2f));
+        }
+        for (int i = 0; i < n - 1; ++i)
+            for (int j = i + 1; j < n; ++j) {
+                const MatchesInfo& mi = pairwise_matches[(size_t)i * n + j];
+                if (mi.src_img_idx < 0) continue;
+                pij.push_back(i); pij.push_back(j);
+                counts.push_back((int)mi.matches.size());
+                stats.push_back(mi.status); stats.push_back(mi.num_inliers);
+                conf.push_back(mi.confidence);
+                mt.push_back(host((void*)mi.matches.data(), (int)mi.matches.size(), 3, ISX_32SC1, sizeof(DMatch)));
+                mk.push_back(host((void*)mi.inliers_mask.data(), (int)mi.inliers_mask.size(), 1, ISX_8UC1, 1));
+            }
+        const int np = (int)pij.size() / 2;
+        if (np == 0) { counts.resize(1); stats.resize(2); conf.resize(1); }
+        std::vector<double> cin((size_t)16 * n), cams((size_t)16 * n);
+        std::vector<float> kr((size_t)18 * n);
+        for (int i = 0; i < n; ++i) {
+            const CameraParams& c = cameras[i];
+            double* s = &cin[(size_t)16 * i];
+            s[0] = c.focal; s[1] = c.aspect; s[2] = c.ppx; s[3] = c.ppy;
+            std::memcpy(s + 4, c.R, sizeof(c.R)); std::memcpy(s + 13, c.t, sizeof(c.t));
+        }
+        isx_mat cm = host(counts.data(), 1, np, ISX_32SC1, 4 * (size_t)(np > 0 ? np : 1)), sm = host(stats.data(), np, 2, ISX_32SC1, 8);
+        isx_mat fm = host(conf.data(), 1, np, ISX_64FC1, 8 * (size_t)(np > 0 ? np : 1)), em = host(est_, 1, 8, ISX_32SC1, 32);
+        isx_mat im = host(cin.data(), n, 16, ISX_64FC1, 128), om = host(cams.data(), n, 16, ISX_64FC1, 128), km = host(kr.data(), n, 18, ISX_32FC1, 72);
+        isx_mat rm = host(rig_stats_, 1, 8, ISX_32SC1, 32), re = host(rig_err_, 1, 2, ISX_64FC1, 16);
+        check(isx_bundle_adjust_ray(n, sizes.data(), kp.data(), np, pij.data(), mt.data(), mk.data(), &cm, &sm, &fm, 1, nullptr, &em, &im, conf_thresh_, max_iter_,
+                                    eps_, &om, &km, &rm, &re, info_, device_, stream_));
+        for (int i = 0; i < n; ++i) {
+            CameraParams& c = cameras[i];
+            const double* s = &cams[(size_t)16 * i];
+            c.focal = s[0]; c.aspect = s[1]; c.ppx = s[2]; c.ppy = s[3];
+            std::memcpy(c.R, s + 4, sizeof(c.R)); std::memcpy(c.t, s + 13, sizeof(c.t));
+            std::memcpy(c.K32, &kr[(size_t)18 * i], sizeof(c.K32)); std::memcpy(c.R32, &kr[(size_t)18 * i + 9], sizeof(c.R32));
+        }
+        return (rig_stats_[0] & (ISX_BUNDLE_NAN | ISX_BUNDLE_NO_EDGES | ISX_BUNDLE_EST_ASSERT)) == 0;
+    }
+    const int* rigStats() const { return rig_stats_; }      // status bits (ISX_BUNDLE_*), iterations, Jacobian and error evaluations, lambdaLg10, edges, matches, 0
+    const double* rigErr() const { return rig_err_; }       // the first and the last |err|
+    int launches() const { return info_[1]; }               // one
+    static void release() { check(isx_bundle_release()); }
+private:
+    static isx_mat host(void* data, int rows, int cols, int type, size_t step) {
+        isx_mat m; m.data = data; m.rows = rows; m.cols = cols; m.type = type; m.step = step; m.device = -1; return m;
+    }
+    int device_;
+    void* stream_;
+    double conf_thresh_ = 1.0, eps_ = 2.220446049250313e-16;
+    int max_iter_ = 1000;
+    int est_[8] = {0, 0, 0, -1, 0, 0, 1, 0};
+    int rig_stats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double rig_err_[2] = {0, 0};
+    int info_[2] = {0, 0};
+};
+
 // cv::imread(path) (W:166): the decoder follows the file's signature, as OpenCV's does - "BM" bitmaps and JFIF / Exif JPEGs;
 // cv::imwrite(path, img) for .bmp and .jpg (W:155-156,315; "pano.jpg" S:1282)
 inline Mat imread(const char* path) {

@@ -774,13 +774,81 @@ enum { ISX_ESTIMATOR_MEDIAN = 1,    /* the focal is the median of the candidates
  * range, rig_first not increasing, a misaligned mat -> ISX_ERR_INVALID; a mat of another type -> ISX_ERR_TYPE; too few rows or columns ->
  * ISX_ERR_SIZE; more than ISX_ESTIMATOR_MAX_IMAGES images in a rig -> ISX_ERR_UNSUPPORTED.  The call uploads its table (and stages host
  * mats): on a capturing stream -> ISX_ERR_STATE with nothing enqueued.  With device mats throughout nothing is read back or synchronised.
- * Host mats synchronise.  Not built: the bundle adjusters, waveCorrect (commented out at C:355-361), leaveBiggestComponent.             */
+ * Host mats synchronise.  BundleAdjusterRay is isx_bundle_adjust_ray below.  Not built: BundleAdjusterReproj, waveCorrect (commented out at
+ * C:355-361), leaveBiggestComponent.                                                                                                   */
 int isx_estimate_cameras(int num_images, const int* image_sizes_wh, int num_pairs, const int* pairs_from_to, int num_rigs, const int* rig_first,
                          const isx_mat* H, const isx_mat* stats, const isx_mat* conf, const isx_mat* focals_in, isx_mat* cameras, isx_mat* kr32,
                          isx_mat* tree, isx_mat* rig_stats, int* info, int device, void* hip_stream);
 /* Returns the scratch of the calling thread (its own: isx_homography_release does not free it).  PER THREAD and not freed at thread exit,
  * as for isx_homography_release.                                                                                                       */
 int isx_estimator_release(void);
+
+/* ---- BundleAdjusterRay (W = the reference's cylindrical-projection demo, W:183-194; the same lines stand in its other demos) ------------ */
+/* Images a rig at the most, and the matches of a tile of the accumulation (bundle.hip takes them from here; tests/helpers/bundle_np.py
+ * repeats them): an edge's inlier matches are summed in tiles of ISX_BUNDLE_TILE in match order, the tiles in order, the edges in order. */
+enum { ISX_BUNDLE_MAX_IMAGES = ISX_ESTIMATOR_MAX_IMAGES, ISX_BUNDLE_TILE = 64 };
+/* status bits of rig_stats_out column 0 */
+enum { ISX_BUNDLE_NAN = 1,          /* a parameter ended as NaN: estimate() returns false, the rig's cameras_out are cameras_in           */
+       ISX_BUNDLE_NO_EDGES = 2,     /* no pair of the rig has confidence > conf_thresh: the cameras pass through                          */
+       ISX_BUNDLE_EST_ASSERT = 4,   /* est_rig_stats carries ISX_ESTIMATOR_ASSERT (or no center inside the rig): the cameras pass through */
+       ISX_BUNDLE_SINGULAR_R = 8,   /* a camera's R has no polar factor (R^T R not finite or not positive): it started from the identity  */
+       ISX_BUNDLE_DROPPED = 16      /* a pivot of the Cholesky solve fell under the trace rule at least once: that step component was 0   */ };
+/* cameras[i].R.convertTo(R, CV_32F) (W:183-188); adjuster = new detail::BundleAdjusterRay(); adjuster->setConfThresh(1);
+ * (*adjuster)(features, pairwise_matches, cameras) (W:189-194) for every rig of a matcher call, in ONE launch, on the mats the matcher, the
+ * homography stage and the estimator left.  OpenCV 3.4.2's BundleAdjusterBase::estimate and BundleAdjusterRay restated - 4 parameters a
+ * camera (focal and a Rodrigues vector), 3 residuals an inlier match.  Per rig:
+ *   setUpInitialCameraParams   R as float32 (the kernel rounds cameras_in's float64 R: kr32's bits), its polar factor (svd(R); u * vt; the
+ *                              sign of the determinant), Rodrigues, the vector rounded to float32.
+ *   the edges                  pairs i < j in index order with conf > conf_thresh; their matches k < counts[p] with inlier_masks[p][k] != 0.
+ *   calcError                  H = Rodrigues(rvec) * K.inv(), K = [[f, 0, width / 2], [0, f, height / 2], [0, 0, 1]]; the rays of both
+ *                              keypoints divided by their length; sqrt(f1 f2) times their difference.
+ *   calcJacobian               central differences, step 1e-3, parameter by parameter.
+ *   CvLevMarq                  TermCriteria(EPS + COUNT, max_iter, eps), lambdaLg10 from -3, at most 33 retries an iteration.
+ *   after the loop             a NaN parameter: the rig's cameras pass through (ISX_BUNDLE_NAN).  Else focal = param, R = Rodrigues(rvec) as
+ *                              float32, then R_i = R_center.inv() * R_i in float64 from those float32 values, rounded once; center =
+ *                              span_tree_centers[0] = column 2 of est_rig_stats, the estimator's own findMaxSpanningTree.
+ * RESTATED AND UNPINNED: OpenCV's source is in neither tree; tests/helpers/bundle_np.py is the specification (DESIGN.md §8 "Bundle
+ * adjuster"), to which every output agrees bit for bit.  THIS PROJECT'S DECISIONS, not OpenCV's: cvSolve(CV_SVD) is a Cholesky factorisation
+ * with SVBkSb's truncation rule on the pivots (not > trace * 2 DBL_EPSILON: that parameter's step is 0); sin, cos and acos are restated in
+ * + - * / sqrt (csrc/bundle_math.hpp, absolute error below 1e-12); sums run per tile of ISX_BUNDLE_TILE matches, then tiles and edges in
+ * order; lambda = 10^lambdaLg10 is a table of correctly rounded literals; the float32 SVD and the SVD inside cvRodrigues2 are one float64
+ * polar factor; a match whose queryIdx / trainIdx lies outside its image's keypoints is no inlier; the loop also ends on a NaN parameter.
+ *   image_sizes_wh  (width, height) per image.
+ *   keypoints       num_images CV_32FC1 mats of n_i x 2 (pt.x, pt.y), the matcher's input.
+ *   pairs_from_to   num_pairs (from, to), from < to, both of one rig, no pair twice, any order: row p of counts, stats, conf, matches[p]
+ *                   and inlier_masks[p].
+ *   matches         per pair the matcher's CV_32SC1 mat, rows x >= 3: queryIdx, trainIdx, distance.
+ *   inlier_masks    per pair the homography stage's CV_8UC1 mat, rows x >= 1.
+ *   counts          the matcher's CV_32SC1 mat of at least 1 x num_pairs.  A count above the rows of its matches or mask mat is clamped to
+ *                   them, a negative one is 0.
+ *   stats, conf     the homography stage's: CV_32SC1 of at least num_pairs x 2 (checked, not read), CV_64FC1 of at least 1 x num_pairs.
+ *   rig_first       as for isx_estimate_cameras; a rig has from 2 to ISX_BUNDLE_MAX_IMAGES images.
+ *   est_rig_stats   the estimator's rig_stats: CV_32SC1, at least num_rigs x 8.
+ *   cameras_in      the estimator's cameras: CV_64FC1, at least num_images x 16.
+ *   conf_thresh     >= 0 (1 at W:189-194): an edge then has confidence > 0, and with it a mask the homography stage wrote.
+ *   max_iter, eps   1000 and DBL_EPSILON in OpenCV; max_iter in [1, 1000].
+ *   cameras_out     CV_64FC1, at least num_images x 16: cameras_in with focal and R replaced (R holds float32 values).
+ *   kr32_out        CV_32FC1, at least num_images x 18: K()[9], then R[9] - what isx_warper_* takes.
+ *   rig_stats_out   CV_32SC1, at least num_rigs x 8: status bits, iterations, Jacobian evaluations, error evaluations, the last
+ *                   lambdaLg10, edges, inlier matches, 0.  A rig that passes through before the loop has zeros in columns 1 - 4.
+ *   rig_err_out     CV_64FC1, at least num_rigs x 2: the first and the last |err|.
+ *   info            NULL, or 2 ints: the rigs processed and the kernel launches of this call - ONE, a workgroup per rig.
+ * Mats are host or device mats, 4-byte aligned in pointer and step (masks: any), 8-byte for the CV_64FC1 ones.  A device mat is read ON THE
+ * DEVICE: counts, conf and est_rig_stats are never read back, every scratch size comes from the mats' rows.  Checked before anything is
+ * written or enqueued: null pointers, fewer than 2 images in a rig, a pair with from >= to, a repeated pair, a pair across two rigs, an index
+ * out of range, rig_first not increasing, max_iter outside [1, 1000], conf_thresh negative or not a number, eps not a number, a misaligned
+ * mat -> ISX_ERR_INVALID; a mat of another type -> ISX_ERR_TYPE; too few rows or columns -> ISX_ERR_SIZE; more than ISX_BUNDLE_MAX_IMAGES
+ * images in a rig -> ISX_ERR_UNSUPPORTED.  The call uploads its tables (and stages host mats): on a capturing stream -> ISX_ERR_STATE with
+ * nothing enqueued.  With device mats throughout nothing is read back or synchronised.  Host mats synchronise.  Not built:
+ * BundleAdjusterReproj (commented out at W:190), waveCorrect (W:198), leaveBiggestComponent.                                            */
+int isx_bundle_adjust_ray(int num_images, const int* image_sizes_wh, const isx_mat* keypoints, int num_pairs, const int* pairs_from_to,
+                          const isx_mat* matches, const isx_mat* inlier_masks, const isx_mat* counts, const isx_mat* stats, const isx_mat* conf,
+                          int num_rigs, const int* rig_first, const isx_mat* est_rig_stats, const isx_mat* cameras_in, double conf_thresh, int max_iter,
+                          double eps, isx_mat* cameras_out, isx_mat* kr32_out, isx_mat* rig_stats_out /* CV_32SC1 rigs x 8 */,
+                          isx_mat* rig_err_out /* CV_64FC1 rigs x 2 */, int* info, int device, void* hip_stream);
+/* Returns the scratch of the calling thread (its own: isx_estimator_release does not free it).  PER THREAD and not freed at thread exit,
+ * as for isx_estimator_release.                                                                                                        */
+int isx_bundle_release(void);
 
 /* ---- on-disk format either side of the path: .bmp (W:166 imread, W:155-156,315 imwrite) ----------- */
 /* Reading: uncompressed Windows bitmaps only (the reference's inputs and committed artefacts are BMPs).
@@ -885,6 +953,11 @@ int isx_selftest_roi_host(int kind, float scale, const float K[9], const float R
  * (K, R) and, for ISX_WARP_PLANE, the translation T (NULL = zeros; a non-zero T is ISX_ERR_UNSUPPORTED for the other kinds).  Host code,
  * the same functions the handle's entry calls: the CPU test-suite compares it with the plane model and the oracle's mapForward.        */
 int isx_selftest_warp_point(int kind, float scale, const float K[9], const float R[9], const float T[3], float x, float y, float out_uv[2]);
+/* The host compilation of csrc/bundle_math.hpp, the arithmetic isx_bundle_adjust_ray runs per camera on the device, for n items: fn 0 sin,
+ * 1 cos, 2 acos (1 double in, 1 out); 3 Rodrigues vector -> matrix (3 in, 9 out); 4 matrix -> vector (9 in, 3 out); 5 the polar factor (9 in,
+ * 9 and a 1.0 / 0.0 "ok" out); 6 R K^-1 (f, rvec[3], width, height in, 9 out); 7 the ray (H[9], x, y in, 3 out).  Needs no device: the CPU
+ * test-suite compares it with tests/helpers/bundle_np.py bit for bit.                                                                  */
+int isx_selftest_bundle_math(int fn, int n, const double* in, double* out);
 /* Every entry of this header is a function-try-block: a C++ exception raised underneath it (std::bad_alloc of a host container, a
  * std::length_error, anything a future change throws) is stopped there and comes back as a status - ISX_ERR_NOMEM for the two allocation
  * failures, ISX_ERR_INTERNAL otherwise, the text in isx_last_error() - never as an exception in the caller's frames (the

@@ -1,0 +1,338 @@
+"""tests/helpers/bundle_np.py, the specification of isx_bundle_adjust_ray, on known answers - no GPU: the restated sin / cos / acos against
+math's and the host compilation of csrc/bundle_math.hpp against the model's bits; cvRodrigues2 both ways; the polar factor against
+np.linalg.svd; the Cholesky solve with its trace rule; CvLevMarq's state machine on a scripted problem; the skipped structural zeros
+against the dense J^T J; planted rigs of 2, 3 and 5 cameras, where the same loop solved by np.linalg.lstsq guards the Cholesky decision; the
+fuzz generator."""
+import ctypes as C
+import functools
+import math
+import os
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import bundle_cases as cases  # noqa: E402
+import fuzz_bundle as fz  # noqa: E402
+from helpers import bundle_np as bm  # noqa: E402
+from imagestitch_amd import _lib  # noqa: E402
+
+PI = math.pi
+
+
+def _boundaries(k, scale):
+    """The multiples j * scale, |j| <= k, with their two neighbours either side."""
+    b = np.arange(-k, k + 1) * scale
+    return np.concatenate([b, np.nextafter(b, np.inf), np.nextafter(b, -np.inf), np.nextafter(np.nextafter(b, np.inf), np.inf),
+                           np.nextafter(np.nextafter(b, -np.inf), -np.inf)])
+
+
+ANGLES = np.concatenate([np.linspace(-4 * PI, 4 * PI, 100001), _boundaries(16, PI / 4), _boundaries(16, PI / 2), [0.0, -0.0, 1e-300, 1e-9, -1e-9]])
+COSINES = np.concatenate([np.linspace(-1.0, 1.0, 100001), _boundaries(1, 0.5), [np.nextafter(1.0, 0), np.nextafter(-1.0, 0), 1.0, -1.0, 0.0, 1e-17]])
+COSINES = COSINES[(COSINES >= -1.0) & (COSINES <= 1.0)]
+
+
+def _host(fn, data, n_in, n_out):
+    """isx_selftest_bundle_math: the host compilation of bundle_math.hpp on rows of n_in doubles."""
+    a = np.ascontiguousarray(data, np.float64).reshape(-1, n_in)
+    out = np.zeros((a.shape[0], n_out))
+    dp = C.POINTER(C.c_double)
+    _lib.check(_lib.load().isx_selftest_bundle_math(fn, a.shape[0], a.ctypes.data_as(dp), out.ctypes.data_as(dp)))
+    return out
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float64).view(np.uint64)
+
+
+# ---- elementary functions -------------------------------------------------------------------------------------------------------------------
+def test_sin_cos_acos_are_within_1e_12_of_math():
+    assert max(abs(bm.sin(float(x)) - math.sin(x)) for x in ANGLES) <= 1e-12
+    assert max(abs(bm.cos(float(x)) - math.cos(x)) for x in ANGLES) <= 1e-12
+    assert max(abs(bm.acos(float(x)) - math.acos(x)) for x in COSINES) <= 1e-12
+    assert bm.acos(1.0) == 0.0 and bm.sin(0.0) == 0.0 and bm.cos(0.0) == 1.0
+
+
+def test_a_nan_or_an_infinity_gives_a_nan_and_never_raises():
+    for f in (bm.sin, bm.cos, bm.acos):
+        for v in (float("nan"), float("inf"), -float("inf")):
+            assert math.isnan(f(v))
+    assert isinstance(bm.sin(1e300), float) and isinstance(bm.cos(-1e300), float)      # meaningless past 2^51, but never an exception
+
+
+def test_the_host_compilation_of_the_shared_header_gives_the_models_bits():
+    special = [float("nan"), float("inf"), 1e300, -1e17, 1e6, 12345.678]
+    ang = np.concatenate([ANGLES[::7], special])
+    assert np.array_equal(_bits(_host(0, ang, 1, 1).ravel()), _bits([bm.sin(float(x)) for x in ang]))
+    assert np.array_equal(_bits(_host(1, ang, 1, 1).ravel()), _bits([bm.cos(float(x)) for x in ang]))
+    cs = np.concatenate([COSINES[::7], [float("nan")]])
+    assert np.array_equal(_bits(_host(2, cs, 1, 1).ravel()), _bits([bm.acos(float(x)) for x in cs]))
+    rng = np.random.default_rng(5)
+    rv = np.concatenate([rng.normal(size=(200, 3)) * rng.choice([1e-17, 1e-3, 1.0, 3.0, 7.0], (200, 1)), [[0, 0, 0], [PI, 0, 0], [0, PI / 2, 0]]])
+    mats = _host(3, rv, 3, 9)
+    assert np.array_equal(_bits(mats), _bits([bm.rodrigues_mat([float(v) for v in r]) for r in rv]))
+    half_turns = [np.diag([1.0, -1.0, -1.0]), np.diag([-1.0, 1.0, -1.0]), np.diag([-1.0, -1.0, 1.0]), cases.rotation(0.3, 0.2, 0.1) @ np.diag([1.0, -1.0, -1.0])
+                  @ cases.rotation(0.3, 0.2, 0.1).T, np.eye(3)]
+    ms = np.concatenate([mats, np.array(half_turns).reshape(-1, 9)])
+    assert np.array_equal(_bits(_host(4, ms, 9, 3)), _bits([bm.rodrigues_vec([float(v) for v in m]) for m in ms]))
+    sheared = np.concatenate([[(np.array(m).reshape(3, 3) * rng.uniform(0.5, 2) + rng.normal(size=(3, 3)) * 0.05).ravel() for m in mats[:60]],
+                              [np.zeros(9), np.full(9, np.nan), [1, 2, 3, 2, 4, 6, 0, 1, 1], np.full(9, np.inf)]]).astype(np.float32).astype(np.float64)
+    got = _host(5, sheared, 9, 10)
+    want = [bm.polar([float(v) for v in m]) for m in sheared]
+    assert np.array_equal(_bits(got[:, :9]), _bits([w[0] for w in want])) and [bool(v) for v in got[:, 9]] == [w[1] for w in want]
+    assert not all(w[1] for w in want) and any(w[1] for w in want)
+    cam = np.column_stack([rng.uniform(300, 3000, 50), rng.normal(size=(50, 3)) * 0.4, rng.integers(300, 4000, 50), rng.integers(200, 3000, 50)])
+    Hs = _host(6, cam, 6, 9)
+    assert np.array_equal(_bits(Hs), _bits([bm.cam_h([float(v) for v in r[:4]], int(r[4]), int(r[5])) for r in cam]))
+    pts = rng.uniform(0, 3000, (50, 2)).astype(np.float32).astype(np.float64)
+    assert np.array_equal(_bits(_host(7, np.column_stack([Hs, pts]), 11, 3)),
+                          _bits([bm.ray([float(v) for v in h], float(p[0]), float(p[1])) for h, p in zip(Hs, pts)]))
+
+
+# ---- cvRodrigues2 ----------------------------------------------------------------------------------------------------------------------------
+def test_quarter_turns_about_each_axis_give_the_exact_matrices():
+    want = {0: [1, 0, 0, 0, 0, -1, 0, 1, 0], 1: [0, 0, 1, 0, 1, 0, -1, 0, 0], 2: [0, -1, 0, 1, 0, 0, 0, 0, 1]}
+    for axis, w in want.items():
+        for sign in (1.0, -1.0):
+            rv = [0.0, 0.0, 0.0]
+            rv[axis] = sign * PI / 2
+            got = np.array(bm.rodrigues_mat(rv)).reshape(3, 3)
+            exact = np.array(w, np.float64).reshape(3, 3)
+            assert np.abs(got - (exact if sign > 0 else exact.T)).max() <= 1e-15
+
+
+def test_theta_below_dbl_epsilon_gives_the_identity():
+    eye = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0]
+    assert bm.rodrigues_mat([0.0, 0.0, 0.0]) == eye and bm.rodrigues_mat([1e-16, -1e-16, 1e-16]) == eye
+    assert bm.rodrigues_mat([3e-16, 0.0, 0.0]) != eye or bm.rodrigues_mat([3e-16, 0.0, 0.0])[7] == 3e-16
+
+
+def test_both_halves_of_the_small_sine_branch():
+    assert bm.rodrigues_vec([1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0]) == [0.0, 0.0, 0.0]                 # c > 0
+    tiny = bm.rodrigues_mat([1e-7, 0.0, 0.0])                                                                 # s = 1e-7 < 1e-5, c > 0
+    assert bm.rodrigues_vec(tiny) == [0.0, 0.0, 0.0]
+    for axis in (np.array([1.0, 0, 0]), np.array([0, 1.0, 0]), np.array([0, 0, 1.0]), np.array([1.0, 2.0, -2.0]) / 3, np.array([-2.0, 1.0, 2.0]) / 3):
+        R = 2 * np.outer(axis, axis) - np.eye(3)                                                              # a half turn: s = 0, c = -1
+        rv = np.array(bm.rodrigues_vec([float(v) for v in R.ravel()]))
+        assert abs(np.linalg.norm(rv) - PI) <= 1e-12
+        assert np.abs(np.array(bm.rodrigues_mat([float(v) for v in rv])).reshape(3, 3) - R).max() <= 1e-12
+
+
+def test_a_vector_matrix_vector_round_trip():
+    rng = np.random.default_rng(1)
+    for _ in range(200):
+        rv = rng.normal(size=3)
+        rv *= rng.uniform(0.01, 3.1) / np.linalg.norm(rv)
+        R = bm.rodrigues_mat([float(v) for v in rv])
+        assert np.abs(np.array(R).reshape(3, 3) @ np.array(R).reshape(3, 3).T - np.eye(3)).max() <= 1e-14
+        assert np.abs(np.array(bm.rodrigues_vec(R)) - rv).max() <= 1e-9 * max(1.0, 1.0 / (PI - np.linalg.norm(rv)))
+
+
+def test_the_polar_factor_against_u_vt_of_an_svd():
+    rng = np.random.default_rng(2)
+    for k in range(100):
+        R = cases.rotation(*rng.uniform(-1, 1, 3)) * rng.uniform(0.5, 2.0) + rng.normal(size=(3, 3)) * 0.1       # scaled, sheared
+        if k % 5 == 0:
+            R = -R                                                                                              # det < 0: R = -R
+        R = R.astype(np.float32).astype(np.float64)
+        Q, ok = bm.polar([float(v) for v in R.ravel()])
+        U, _, Vt = np.linalg.svd(R)
+        want = U @ Vt
+        if np.linalg.det(want) < 0:
+            want = -want
+        assert ok and np.abs(np.array(Q).reshape(3, 3) - want).max() <= 1e-12
+    assert bm.polar([1.0, 2.0, 3.0, 2.0, 4.0, 6.0, 0.0, 1.0, 1.0]) == ([1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0], False)
+    assert bm.polar([float("nan")] * 9)[1] is False and bm.polar([0.0] * 9)[1] is False
+
+
+# ---- decision 1: the solve --------------------------------------------------------------------------------------------------------------------
+def test_the_solve_against_numpy_within_the_condition_number():
+    rng = np.random.default_rng(3)
+    for n in (1, 2, 8, 12, 20, 33):
+        J = rng.normal(size=(3 * n, n)) * rng.uniform(0.1, 100.0, n)
+        A = J.T @ J
+        b = rng.normal(size=n)
+        x, dropped = bm.chol_solve([[float(v) for v in r] for r in A], [float(v) for v in b])
+        want = np.linalg.solve(A, b)
+        assert dropped == []
+        assert np.linalg.norm(np.array(x) - want) <= np.linalg.cond(A) * 2.0 ** -52 * np.linalg.norm(want)
+
+
+def test_a_zero_row_and_column_gives_step_zero_for_that_parameter():
+    rng = np.random.default_rng(4)
+    J = rng.normal(size=(30, 8))
+    J[:, 5] = 0.0                                              # a camera parameter without an edge
+    A, b = J.T @ J, J.T @ rng.normal(size=30)
+    x, dropped = bm.chol_solve([[float(v) for v in r] for r in A], [float(v) for v in b])
+    keep = [k for k in range(8) if k != 5]
+    assert dropped == [5] and x[5] == 0.0
+    want = np.linalg.solve(A[np.ix_(keep, keep)], b[keep])
+    assert np.allclose(np.array(x)[keep], want, rtol=1e-10, atol=0)
+
+
+def test_the_trace_rule_on_a_planted_null_direction():
+    rng = np.random.default_rng(5)
+    J = rng.normal(size=(40, 6))
+    J[:, 5] = J[:, 1] - 2.0 * J[:, 3]                          # column 5 depends on 1 and 3: the last pivot is rounding noise
+    A, b = J.T @ J, J.T @ rng.normal(size=40)
+    x, dropped = bm.chol_solve([[float(v) for v in r] for r in A], [float(v) for v in b])
+    assert dropped == [5] and x[5] == 0.0
+    assert np.linalg.norm(A @ np.array(x) - b) <= 1e-9 * np.linalg.norm(b)      # b lies in the range: the truncated solve still solves
+    full = A + np.eye(6) * 1e-3 * np.trace(A)                                   # well above the rule: nothing is dropped
+    assert bm.chol_solve([[float(v) for v in r] for r in full], [float(v) for v in b])[1] == []
+
+
+# ---- CvLevMarq ---------------------------------------------------------------------------------------------------------------------------------
+def test_the_state_machine_on_a_scripted_problem():
+    """A one-parameter problem whose error never improves: lambdaLg10 walks from -3 to 16, the 21st step is accepted as it is (++lambdaLg10
+    = 17 > 16), then max_iter ends the loop."""
+    trace = []
+    p, info = bm.lev_marq([1.0], lambda q: ([[1.0]], [1e17], 1.0), lambda q: 2.0, 2, bm.DBL_EPSILON, trace=trace)
+    want = [("CALC_J", -3, 0)] + [("CHECK_ERR", lg, 0) for lg in range(-3, 17)] + [("CALC_J", 16, 1), ("CHECK_ERR", 16, 1), ("DONE", 15, 2)]
+    assert trace == want
+    assert info == dict(iters=2, jac_evals=2, err_evals=2 + 21, lambda_lg10=15, first=1.0, last=2.0, dropped=False, nan=False)
+    assert p[0] == (1.0 - 1e17 / (1.0 + 1e16)) - 1e17 / (1.0 + 1e16)      # both accepted steps were taken at lambda = 1e16
+    # an error that always improves: lambdaLg10 falls by one an iteration to its floor of -16
+    trace = []
+    errs = iter([1.0 / k for k in range(2, 100)])
+    _, info = bm.lev_marq([1.0], lambda q: ([[1.0]], [0.5], 1.0), lambda q: next(errs), 20, bm.DBL_EPSILON, trace=trace)
+    assert [t[1] for t in trace if t[0] == "CALC_J"] == [max(-3 - k, -16) for k in range(20)] and info["iters"] == 20 and info["err_evals"] == 40
+    assert trace[-1] == ("DONE", -16, 20)
+    # a zero gradient: the step is 0 and the relative-step test ends the loop after one iteration
+    trace = []
+    _, info = bm.lev_marq([1.0], lambda q: ([[1.0]], [0.0], 1.0), lambda q: 1.0, 1000, bm.DBL_EPSILON, trace=trace)
+    assert trace == [("CALC_J", -3, 0), ("CHECK_ERR", -3, 0), ("DONE", -4, 1)] and info["iters"] == 1
+    # a NaN parameter ends the loop
+    _, info = bm.lev_marq([float("nan")], lambda q: ([[float("nan")]], [float("nan")], float("nan")), lambda q: float("nan"), 1000, bm.DBL_EPSILON)
+    assert info["iters"] == 1 and info["nan"] and info["dropped"]
+
+
+# ---- decision 3: the summation orders ----------------------------------------------------------------------------------------------------------
+def _problem(c):
+    o = bm.adjust_rig(c["sizes"], c["keypoints"], c["pairs"], c["matches"], c["masks"], c["counts"][0], c["conf"][0], c["est_rig_stats"][0],
+                      c["cameras_in"], max_iter=1)
+    return o
+
+
+def _rig_of(c):
+    """The model's Rig and starting parameters of a one-rig case."""
+    edges = []
+    for k in sorted(range(len(c["pairs"])), key=lambda k: c["pairs"][k]):
+        if not c["conf"][0, k] > c["conf_thresh"]:
+            continue
+        i, j = c["pairs"][k]
+        pts = [(float(c["keypoints"][i][q, 0]), float(c["keypoints"][i][q, 1]), float(c["keypoints"][j][t, 0]), float(c["keypoints"][j][t, 1]))
+               for (q, t, _), m in zip(c["matches"][k], c["masks"][k][:, 0]) if m]
+        edges.append((i, j, pts))
+    param = []
+    for i in range(len(c["sizes"])):
+        Q, _ = bm.polar([float(np.float32(v)) for v in c["cameras_in"][i, 4:13]])
+        param += [float(c["cameras_in"][i, 0])] + [float(np.float32(v)) for v in bm.rodrigues_vec(Q)]
+    return bm.Rig(c["sizes"], edges), param
+
+
+def test_skipping_the_structural_zeros_gives_the_dense_bits():
+    """J whole, mulTransposed and J^T err over every row with its zeros multiplied, against the tiles.  Where every camera has one edge of
+    one tile the two are the same running sums and agree bit for bit; where a camera has several edges the model adds per-edge sums, which
+    is another order (decision 3) and the same value to rounding."""
+    c = cases.make(4, [(0, 1), (1, 2), (2, 3)], 20, inliers=[9, 5, 12], conf=[2.0, 0.5, 2.0])
+    rig, param = _rig_of(c)
+    assert [(e[0], e[1]) for e in rig.edges] == [(0, 1), (2, 3)] and all(len(e[2]) <= bm.TILE for e in rig.edges)
+    JtJ, JtErr, _ = rig.jac_err(param)
+    dJtJ, dJtErr = rig.dense_jtj(param)
+    assert np.array_equal(_bits(JtJ), _bits(dJtJ)) and np.array_equal(_bits(JtErr), _bits(dJtErr))
+    assert not np.array(JtJ)[0:8, 8:16].any() and np.array(JtJ)[0:4, 4:8].all() and np.array(JtJ)[8:12, 12:16].all()
+    c = cases.make(4, [(0, 1), (0, 2), (1, 2), (2, 3)], 21, inliers=[9, 5, 12, 7], conf=[2.0, 2.0, 0.5, 2.0])
+    rig, param = _rig_of(c)
+    assert len(rig.edges) == 3
+    JtJ, JtErr, _ = rig.jac_err(param)
+    dJtJ, dJtErr = rig.dense_jtj(param)
+    assert np.allclose(JtJ, dJtJ, rtol=1e-12, atol=0) and np.allclose(JtErr, dJtErr, rtol=1e-9, atol=1e-9)
+    assert not np.array(JtJ)[0:4, 12:16].any() and not np.array(JtJ)[4:8, 8:12].any()      # no edge (0, 3); (1, 2) is below the threshold
+    assert np.array_equal(_bits(np.array(JtJ)[0:4, 4:8]), _bits(np.array(dJtJ)[0:4, 4:8]))  # an off-diagonal block is one edge's: the same bits
+    assert np.array_equal(np.array(JtJ), np.array(JtJ).T)
+
+
+def test_tiles_change_the_order_and_nothing_else():
+    c = cases.make(2, [(0, 1)], 22, inliers=2 * bm.TILE + 3, outliers=0.0)
+    rig, param = _rig_of(c)
+    JtJ, JtErr, en = rig.jac_err(param)
+    dJtJ, dJtErr = rig.dense_jtj(param)
+    assert not np.array_equal(_bits(JtJ), _bits(dJtJ))
+    assert np.allclose(JtJ, dJtJ, rtol=1e-12, atol=0) and np.allclose(JtErr, dJtErr, rtol=1e-9, atol=1e-9)
+    assert en == rig.err_norm(param)                           # calcError after calcJacobian: the same bits
+
+
+# ---- planted rigs -------------------------------------------------------------------------------------------------------------------------------
+PLANTED = {2: ([(0, 1)], 30), 3: (cases.all_pairs(3), 20), 5: (cases.all_pairs(5), 12)}
+
+
+@functools.lru_cache(maxsize=None)
+def _planted(n, which):
+    pairs, inl = PLANTED[n]
+    c = cases.make(n, pairs, 100 + n, inliers=inl, outliers=0.2, off_deg=1.0, off_focal=0.05, max_iter=1000, r_scale=1.0)
+    solve = bm.chol_solve if which == "cholesky" else bm.lstsq_solve
+    return c, bm.adjust_rig(c["sizes"], c["keypoints"], c["pairs"], c["matches"], c["masks"], c["counts"][0], c["conf"][0], c["est_rig_stats"][0],
+                            c["cameras_in"], 1.0, 1000, bm.DBL_EPSILON, solve)
+
+
+@pytest.mark.parametrize("n", sorted(PLANTED))
+def test_planted_rigs_converge(n):
+    """Known focal (900) and rotations, exact projections of random rays rounded to float32 keypoints, cameras started 1 degree and 5 % off.
+    (a) the last |err| is below 1 / 100 of the first (the start is of the order of f sin 1 degree a match, the minimum of the order of the
+    float32 rounding); (b) the center's R is the identity within 1e-6; (c) THE GUARD ON THE CHOLESKY DECISION: the same loop with
+    np.linalg.lstsq as its solve is the reference, and the Cholesky run's last |err| is at most 1 % above its.  Measured here (first -> last
+    |err|, iterations): n = 2: both solves 185.133224 -> 1.39442e-04 (Cholesky 8 iterations, lstsq 9); n = 3: both 271.605044 -> 2.26695e-04
+    (6, 8); n = 5: both 352.161162 -> 2.72648e-04 (11, 6) - the lstsq run alone converges on these inputs, and the two last values agree to
+    the digits printed."""
+    c, chol = _planted(n, "cholesky")
+    _, ref = _planted(n, "lstsq")
+    print(n, "cholesky", chol["rig_err"], chol["rig_stats"], "lstsq", ref["rig_err"], ref["rig_stats"])
+    for o in (chol, ref):
+        assert o["rig_stats"][bm.RIG_STATUS] == 0 and 1 < o["rig_stats"][bm.RIG_ITERS] < 1000
+        assert o["rig_err"][1] < o["rig_err"][0] / 100.0                                              # (a)
+        assert np.abs(o["cameras"][0, 4:13].reshape(3, 3) - np.eye(3)).max() <= 1e-6                   # (b): the center is camera 0
+    assert chol["rig_err"][1] <= 1.01 * ref["rig_err"][1]                                             # (c)
+    focal, Rs = c["planted"]
+    assert np.abs(chol["cameras"][:, 0] - focal).max() <= 1e-3
+    assert max(np.abs(chol["cameras"][i, 4:13].reshape(3, 3) - Rs[i]).max() for i in range(n)) <= 1e-6
+    assert chol["cameras"][:, 4:13].astype(np.float32).astype(np.float64).tolist() == chol["cameras"][:, 4:13].tolist()
+    assert np.array_equal(chol["kr32"][:, 9:18], chol["cameras"][:, 4:13].astype(np.float32))
+
+
+def test_rigs_that_pass_through():
+    named = cases.named()
+    for name, bit in (("rig_without_edge", bm.ST_NO_EDGES), ("estimator_assert_bit", bm.ST_EST_ASSERT), ("nan_focal_in", bm.ST_NAN)):
+        c = named[name]
+        cams, kr, rs, re = fz.run_model(c)
+        assert rs[0, bm.RIG_STATUS] & bit, name
+        assert np.array_equal(_bits(cams), _bits(c["cameras_in"])), name
+        assert fz.same(kr[:, 9:18], c["cameras_in"][:, 4:13].astype(np.float32)), name
+    c = named["conf_equal_thresh_is_excluded"]
+    assert fz.run_model(c)[2][0, bm.RIG_EDGES] == 2
+    c = named["camera_without_edge"]
+    cams, _, rs, _ = fz.run_model(c)
+    assert rs[0, bm.RIG_STATUS] == bm.ST_DROPPED and cams[3, 0] == c["cameras_in"][3, 0]              # its parameters never move
+    assert fz.run_model(named["singular_R_in"])[2][0, bm.RIG_STATUS] & bm.ST_SINGULAR_R
+
+
+# ---- the fuzz generator -------------------------------------------------------------------------------------------------------------------------
+def test_the_fuzz_generator():
+    seen_cls, seen_layout, faults, natural, rigs = set(), set(), 0, 0, set()
+    for s in range(48):
+        a, b = fz.make_case(s), fz.make_case(s)
+        assert all(fz.same(x, y) for x, y in zip(a["matches"] + a["keypoints"] + [a["cameras_in"], a["conf"]],
+                                                        b["matches"] + b["keypoints"] + [b["cameras_in"], b["conf"]]))
+        seen_cls.add(a["cls"])
+        seen_layout.add(a["layout"])
+        faults += 1 if a["fault"] else 0
+        natural += a["max_iter"] == 1000
+        rigs.add(1 if a["rig_first"] is None else len(a["rig_first"]) - 1)
+        n = len(a["sizes"])
+        assert all(0 <= i < j < n for i, j in a["pairs"]) and a["counts"].shape == (1, len(a["pairs"])) and a["cameras_in"].shape == (n, 16)
+    assert seen_cls == set(fz.CLASSES) and seen_layout == set(fz.LAYOUTS) and faults >= 4 and natural >= 1 and rigs == {1, 2, 3}
+    want = fz.run_model(fz.make_case(7))
+    assert want[0].shape[1] == 16 and want[1].dtype == np.float32 and want[2].dtype == np.int32 and want[3].shape[1] == 2
