@@ -8,7 +8,8 @@ from ._lib import (BORDER_CONSTANT, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_R
                    INTER_NEAREST, INTER_TIES_EVEN, PREC_F16ACC32, PREC_F32, PREC_I16, IsxError, load)
 from .blender import Blender, FeatherBlender, MultiBandBlender, NoBlender, convert_to, dilate_and, gain_apply  # noqa: F401
 from .cameras import CameraParams, HomographyBasedEstimator, estimate_cameras  # noqa: F401
-from .adjuster import BundleAdjusterRay, bundle_adjust_ray  # noqa: F401
+from .adjuster import (WAVE_CORRECT_HORIZ, WAVE_CORRECT_VERT, BundleAdjusterRay, BundleAdjusterReproj, bundle_adjust_ray,  # noqa: F401
+                       bundle_adjust_reproj, wave_correct, waveCorrect)
 from .exposure import BlocksGainCompensator, GainCompensator  # noqa: F401
 from .imgio import imread, imwrite  # noqa: F401
 from .homography import BestOf2NearestMatcher, find_homography  # noqa: F401
@@ -18,4 +19,4 @@ from .seam import DP_COLOR, DP_COLOR_GRAD, DpSeamFinder, GraphCutSeamFinder, Vor
 from ._lib import WARP_CYLINDRICAL, WARP_PLANE, WARP_SPHERICAL  # noqa: F401
 from .warper import CylindricalWarper, PlaneWarper, RotationWarper, SphericalWarper, remap  # noqa: F401
 
-__all__ = ["Blender", "MultiBandBlender", "FeatherBlender", "NoBlender", "convert_to", "dilate_and", "gain_apply", "GainCompensator", "BlocksGainCompensator", "imread", "imwrite", "resize", "dilate_resize_and", "INTER_NEAREST", "INTER_LINEAR", "seam_estimate", "seam_gradients", "DP_COLOR", "DP_COLOR_GRAD", "DpSeamFinder", "GraphCutSeamFinder", "VoronoiSeamFinder", "FeaturesMatcher", "BestOf2NearestMatcher", "MatchesInfo", "find_homography", "CameraParams", "HomographyBasedEstimator", "estimate_cameras", "BundleAdjusterRay", "bundle_adjust_ray", "remap", "CylindricalWarper", "SphericalWarper", "PlaneWarper", "WARP_CYLINDRICAL", "WARP_SPHERICAL", "WARP_PLANE", "RotationWarper", "IsxError", "load"]
+__all__ = ["Blender", "MultiBandBlender", "FeatherBlender", "NoBlender", "convert_to", "dilate_and", "gain_apply", "GainCompensator", "BlocksGainCompensator", "imread", "imwrite", "resize", "dilate_resize_and", "INTER_NEAREST", "INTER_LINEAR", "seam_estimate", "seam_gradients", "DP_COLOR", "DP_COLOR_GRAD", "DpSeamFinder", "GraphCutSeamFinder", "VoronoiSeamFinder", "FeaturesMatcher", "BestOf2NearestMatcher", "MatchesInfo", "find_homography", "CameraParams", "HomographyBasedEstimator", "estimate_cameras", "BundleAdjusterRay", "bundle_adjust_ray", "BundleAdjusterReproj", "bundle_adjust_reproj", "wave_correct", "waveCorrect", "WAVE_CORRECT_HORIZ", "WAVE_CORRECT_VERT", "remap", "CylindricalWarper", "SphericalWarper", "PlaneWarper", "WARP_CYLINDRICAL", "WARP_SPHERICAL", "WARP_PLANE", "RotationWarper", "IsxError", "load"]

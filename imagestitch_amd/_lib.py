@@ -122,6 +122,9 @@ _SIGS = {
     "isx_estimator_release": [],
     "isx_bundle_adjust_ray": [C.c_int, _IP, _MP, C.c_int, _IP, _MP, _MP, _MP, _MP, _MP, C.c_int, _IP, _MP, _MP, C.c_double, C.c_int, C.c_double, _MP, _MP,
                               _MP, _MP, _IP, C.c_int, C.c_void_p],
+    "isx_bundle_adjust_reproj": [C.c_int, _IP, _MP, C.c_int, _IP, _MP, _MP, _MP, _MP, _MP, C.c_int, _IP, _MP, _MP, C.c_double, C.c_int, C.c_double, C.c_int, _MP,
+                                 _MP, _MP, _MP, _IP, C.c_int, C.c_void_p],
+    "isx_wave_correct": [C.c_int, C.c_int, _IP, _MP, C.c_int, _MP, _MP, _MP, _IP, C.c_int, C.c_void_p],
     "isx_bundle_release": [],
     "isx_seam_estimate": [_MP, _MP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _MP, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int,
                           C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_void_p],

@@ -3,6 +3,9 @@
 //   isx_bundle_adjust_ray      focal and rotation of every camera refined over the inlier matches of every edge, for every rig of a matcher
 //                              call, reading keypoints, matches, masks, counts, conf, the estimator's rig_stats and cameras where the three
 //                              earlier stages left them
+//   isx_bundle_adjust_reproj   detail::BundleAdjusterReproj (commented out at W:190; cv::Stitcher's default) on the same inputs: focal, ppx,
+//                              ppy, aspect and rotation over the reprojection error - k_ba_rigs compiled a second time (ReprojTr)
+//   isx_wave_correct           detail::waveCorrect (commented out at W:198) for every rig: k_wave_rigs, float32 as OpenCV's is
 //   isx_bundle_release         returns the per-thread scratch
 //   isx_selftest_bundle_math   the host compilation of bundle_math.hpp (needs no device)
 //
@@ -10,12 +13,16 @@
 // BundleAdjusterRay, CvLevMarq and cvRodrigues2 restated (unpinned), with three decisions of this project - a Cholesky solve with SVBkSb's
 // truncation rule on the pivots, sin / cos / acos restated in + - * / sqrt (bundle_math.hpp), summation orders fixed by ISX_BUNDLE_TILE.
 //
-// ONE launch per call: k_ba_rigs, one block of BA_THREADS per rig, the whole Levenberg-Marquardt loop inside.  The stage is latency-bound:
+// (tests/helpers/bundle_reproj_np.py specifies the other two entries.)
+//
+// ONE launch per call: k_ba_rigs<Tr>, one block of Tr::THREADS (Ray 256, Reproj 512) per rig, the whole Levenberg-Marquardt loop inside.  The stage is latency-bound:
 // it is on the GPU so that cameras follow the estimator in stream order without a read-back, and so that many rigs cost one.  Per rig:
 //   setup   a thread per pair counts the inliers of its edge (conf > conf_thresh), one thread lays the edges out densely, a thread per pair
 //           gathers the keypoints of its inliers; a thread per camera takes the polar factor of R and its Rodrigues vector;
-//   J       a thread per (camera, parameter, sign): the perturbed R K^-1, kept in LDS; a thread per inlier match: the 1 + 16 rays and its
-//           3 x 8 Jacobian entries (27 doubles a match in scratch - J is never stored whole); a thread per (tile, entry): the 45 partial sums
+//   J       Ray: a thread per (camera, parameter, sign): the perturbed R K^-1, kept in LDS; a thread per inlier match: the 1 + 16 rays and
+//           its 3 x 8 Jacobian entries (27 doubles a match in scratch - J is never stored whole).  Reproj: two matrices x 15 variants x 64
+//           cameras do not fit LDS, so a thread per (edge, variant) forms the edge's 1 + 28 matrices H in per-rig scratch (L2-resident) and
+//           a thread per match does the 29 projections (30 doubles a match).  Both: a thread per (tile, entry): the 45 / 120 partial sums
 //           of a tile of ISX_BUNDLE_TILE matches; a thread per entry of JtJ (scratch, L2-resident) and JtErr: the tiles in edge order;
 //   solve   Cholesky, left-looking: a thread per row against the pivot row in LDS, three barriers a column; the substitutions keep a running
 //           sum per row in a register, one barrier an unknown;
@@ -37,14 +44,23 @@ using namespace isxbm;
 namespace {
 
 constexpr int BA_MAXN = ISX_BUNDLE_MAX_IMAGES;
-constexpr int BA_THREADS = 256;
-constexpr int BA_MAXP = 4 * BA_MAXN;                         // parameters a rig: a thread per row of the Cholesky
 constexpr int BA_TILE = ISX_BUNDLE_TILE;
-constexpr int BA_ENT = 45;                                   // a tile's sums: 36 upper entries of the 8 x 8 block, 8 of J^T err, err^2
-constexpr int BA_JROW = 27;                                  // a match in scratch: err[3], J[3][8]
-constexpr double BA_STEP = 1e-3;
-static_assert(BA_MAXP == BA_THREADS, "one parameter per thread; prow holds one value a thread in ba_err_norm");
 static_assert(BA_MAXN == ISX_ESTIMATOR_MAX_IMAGES, "the chain never refuses what the estimator accepted");
+
+// What k_ba_rigs takes from its traits Tr (RayTr, ReprojTr below): PC parameters a camera, RES residuals a match, STEP of the central
+// differences, THREADS a block, RV where the Rodrigues vector starts among a camera's parameters, HS / FV doubles of LDS for the camera
+// matrices, and the two phases cam_mats (the matrices calcError multiplies a keypoint by, plain and with one parameter moved either way) and
+// matches (calcError and calcJacobian of every inlier match into jrow).  The rest follows:
+template <class Tr>
+struct BaK {
+    static constexpr int W = 2 * Tr::PC;                     // columns of a match's Jacobian rows: the parameters of its two cameras
+    static constexpr int U = W * (W + 1) / 2;                // upper entries of the W x W block
+    static constexpr int ENT = U + W + 1;                    // a tile's sums: the U entries, W of J^T err, err^2 (Ray 45, Reproj 120)
+    static constexpr int JROW = Tr::RES * (1 + W);           // a match in scratch: err[RES], J[RES][W] (Ray 27, Reproj 30)
+    static constexpr int MAXP = Tr::PC * BA_MAXN;            // parameters a rig: a thread per row of the Cholesky
+    static constexpr int PROW = Tr::THREADS;                 // prow holds one value a thread in ba_err_norm, one a parameter in ba_step
+    static_assert(MAXP <= Tr::THREADS, "one parameter per thread");
+};
 
 // lambda = 10^lambdaLg10: the 33 correctly rounded literals
 __constant__ double BA_LAMBDA[33] = {1e-16, 1e-15, 1e-14, 1e-13, 1e-12, 1e-11, 1e-10, 1e-9, 1e-8, 1e-7, 1e-6, 1e-5, 1e-4, 1e-3, 1e-2, 1e-1, 1e0,
@@ -68,12 +84,13 @@ struct BaCall {
     int* rs; long long rs_step;
     double* re; long long re_step;
     float4* pts; int* match_pair;                            // per inlier match, dense per rig: the two keypoints, the pair it belongs to
-    double* jrow;                                            // BA_JROW doubles per inlier match
-    double* tiles; int* tile_pair;                           // BA_ENT doubles per tile; the pair of a tile
+    double* jrow;                                            // JROW doubles per inlier match
+    double* tiles; int* tile_pair;                           // ENT doubles per tile; the pair of a tile
     int* pair_tab;                                           // per pair: inliers, first match, first tile
-    double* jtj; double* lt;                                 // per rig 4n x 4n: JtJ (row-major, symmetric), L (column-major)
+    double* jtj; double* lt;                                 // per rig (PC n) x (PC n): JtJ (row-major, symmetric), L (column-major)
+    double* hmat;                                            // Reproj: RP_VAR x 9 doubles per pair, the edge's H plain and moved
     double conf_thresh, eps;
-    int max_iter;
+    int max_iter, refine_flags;
 };
 
 enum { C_EDGES, C_M, C_T, C_STATUS, C_CENTER, C_AGAIN, C_DONE, C_LG, C_ITERS, C_JEV, C_EEV, C_KEEP, C_NAN, C_N };
@@ -83,123 +100,219 @@ struct BaCtx {                                               // what the phases 
     double* Hs; double* fv; double* param; double* prev; double* bvec; double* bc; double* prow; double* dctl;
     short* slot; int* ctl; unsigned char* kept;
     const BaPair* prs; const int* sizes; int* ptab; const float4* pts; const int* match_pair; double* jrow; double* tiles; const int* tile_pair;
-    double* jtj; double* lt;
-    int n, N, tid;
+    double* jtj; double* lt; double* hmat;
+    int n, N, tid, pc, flags;
 };
 
-__device__ __forceinline__ int ba_upper(int a, int b) { return 8 * a - (a * (a - 1)) / 2 + (b - a); }      // (a, b), a <= b, of the 8 x 8 block
+// ---- BundleAdjusterRay: focal and rvec a camera, the difference of two rays a match -----------------------------------------------------------
+struct RayTr {
+    static constexpr int PC = 4, RES = 3, THREADS = 256, RV = 1;
+    static constexpr double STEP = 1e-3;
+    static constexpr int HS = BA_MAXN * 81;                  // [camera][variant][9]: R K^-1, plain and with one parameter moved either way
+    static constexpr int FV = BA_MAXN * 3;                   // [camera]: f, f - step, f + step
+    static constexpr int HMAT = 0;                           // no per-pair matrices in scratch
+    static const char* who() { return "bundle_adjust_ray"; }
+    static const char* kernel() { return "bundle_rigs"; }
 
-// R K^-1 of every camera at `p`: variant 0, and with jac the 8 perturbed ones (1 + 2 q + sign; sign 0: val - step, 1: val + step)
-__device__ void ba_cam_mats(const BaCtx& x, const double* p, bool jac) {
-    const int per = jac ? 9 : 1;
-    for (int w = x.tid; w < x.n * per; w += BA_THREADS) {
-        const int cam = w / per, v = w % per;
-        double p4[4] = {p[4 * cam], p[4 * cam + 1], p[4 * cam + 2], p[4 * cam + 3]};
-        if (v > 0) {
-            const int q = (v - 1) >> 1;
-            const double val = p4[q];
-            const double moved = ((v - 1) & 1) ? val + BA_STEP : val - BA_STEP;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) p4[e] = e == q ? moved : p4[e];
-        }
-        double H[9];
-        bm_cam_h(p4, x.sizes[2 * cam], x.sizes[2 * cam + 1], H);
-#pragma unroll
-        for (int e = 0; e < 9; ++e) x.Hs[(cam * 9 + v) * 9 + e] = H[e];
-        if (v <= 2) x.fv[cam * 3 + v] = p4[0];               // f, f - step, f + step
+    __device__ static void init_param(const double* ci, double* p) { p[0] = ci[0]; }
+    __device__ static void intrinsics(const double* p, const double* ci, double& focal, double& aspect, double& ppx, double& ppy) {
+        focal = p[0]; aspect = ci[1]; ppx = ci[2]; ppy = ci[3];
     }
-}
 
-// calcError (and with jac calcJacobian) of every inlier match into jrow
-__device__ void ba_matches(const BaCtx& x, bool jac) {
-    const int M = x.ctl[C_M];
-    const double h2 = 2.0 * BA_STEP;
-    for (int idx = x.tid; idx < M; idx += BA_THREADS) {
-        const BaPair& P = x.prs[x.match_pair[idx]];
-        const int i = P.from, j = P.to;
-        const float4 pt = x.pts[idx];
-        const double x1 = (double)pt.x, y1 = (double)pt.y, x2 = (double)pt.z, y2 = (double)pt.w;
-        const double fi = x.fv[3 * i], fj = x.fv[3 * j];
-        double a[3], b[3], err[3];
-        bm_ray(x.Hs + (i * 9) * 9, x1, y1, a);
-        bm_ray(x.Hs + (j * 9) * 9, x2, y2, b);
-        const double mult = sqrt(fi * fj);
-        double* const out = x.jrow + (long long)idx * BA_JROW;
+    // R K^-1 of every camera at `p`: variant 0, and with jac the 8 perturbed ones (1 + 2 q + sign; sign 0: val - step, 1: val + step)
+    __device__ static void cam_mats(const BaCtx& x, const double* p, bool jac) {
+        const int per = jac ? 9 : 1;
+        for (int w = x.tid; w < x.n * per; w += THREADS) {
+            const int cam = w / per, v = w % per;
+            double p4[4] = {p[4 * cam], p[4 * cam + 1], p[4 * cam + 2], p[4 * cam + 3]};
+            if (v > 0) {
+                const int q = (v - 1) >> 1;
+                const double val = p4[q];
+                const double moved = ((v - 1) & 1) ? val + STEP : val - STEP;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) { err[k] = mult * (a[k] - b[k]); out[k] = err[k]; }
-        if (!jac) continue;
-        for (int q = 0; q < 4; ++q) {
-            double e0[3], e1[3], r[3];
-            for (int sg = 0; sg < 2; ++sg) {                 // camera i moves
-                bm_ray(x.Hs + (i * 9 + 1 + 2 * q + sg) * 9, x1, y1, r);
-                const double mm = sqrt((q == 0 ? x.fv[3 * i + 1 + sg] : fi) * fj);
-#pragma unroll
-                for (int k = 0; k < 3; ++k) (sg ? e1 : e0)[k] = mm * (r[k] - b[k]);
+                for (int e = 0; e < 4; ++e) p4[e] = e == q ? moved : p4[e];
             }
+            double H[9];
+            bm_cam_h(p4, x.sizes[2 * cam], x.sizes[2 * cam + 1], H);
 #pragma unroll
-            for (int k = 0; k < 3; ++k) out[3 + 8 * k + q] = (e1[k] - e0[k]) / h2;
-            for (int sg = 0; sg < 2; ++sg) {                 // camera j moves
-                bm_ray(x.Hs + (j * 9 + 1 + 2 * q + sg) * 9, x2, y2, r);
-                const double mm = sqrt(fi * (q == 0 ? x.fv[3 * j + 1 + sg] : fj));
-#pragma unroll
-                for (int k = 0; k < 3; ++k) (sg ? e1 : e0)[k] = mm * (a[k] - r[k]);
-            }
-#pragma unroll
-            for (int k = 0; k < 3; ++k) out[3 + 8 * k + 4 + q] = (e1[k] - e0[k]) / h2;
+            for (int e = 0; e < 9; ++e) x.Hs[(cam * 9 + v) * 9 + e] = H[e];
+            if (v <= 2) x.fv[cam * 3 + v] = p4[0];           // f, f - step, f + step
         }
     }
-}
 
-// a tile's partial sums over its matches in order, the three residuals of each in order: all 45 with jac, the sum of err^2 alone without
+    // calcError (and with jac calcJacobian) of every inlier match into jrow
+    __device__ static void matches(const BaCtx& x, bool jac) {
+        constexpr int BA_JROW = 27;
+        const int M = x.ctl[C_M];
+        const double h2 = 2.0 * STEP;
+        for (int idx = x.tid; idx < M; idx += THREADS) {
+            const BaPair& P = x.prs[x.match_pair[idx]];
+            const int i = P.from, j = P.to;
+            const float4 pt = x.pts[idx];
+            const double x1 = (double)pt.x, y1 = (double)pt.y, x2 = (double)pt.z, y2 = (double)pt.w;
+            const double fi = x.fv[3 * i], fj = x.fv[3 * j];
+            double a[3], b[3], err[3];
+            bm_ray(x.Hs + (i * 9) * 9, x1, y1, a);
+            bm_ray(x.Hs + (j * 9) * 9, x2, y2, b);
+            const double mult = sqrt(fi * fj);
+            double* const out = x.jrow + (long long)idx * BA_JROW;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { err[k] = mult * (a[k] - b[k]); out[k] = err[k]; }
+            if (!jac) continue;
+            for (int q = 0; q < 4; ++q) {
+                double e0[3], e1[3], r[3];
+                for (int sg = 0; sg < 2; ++sg) {             // camera i moves
+                    bm_ray(x.Hs + (i * 9 + 1 + 2 * q + sg) * 9, x1, y1, r);
+                    const double mm = sqrt((q == 0 ? x.fv[3 * i + 1 + sg] : fi) * fj);
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) (sg ? e1 : e0)[k] = mm * (r[k] - b[k]);
+                }
+#pragma unroll
+                for (int k = 0; k < 3; ++k) out[3 + 8 * k + q] = (e1[k] - e0[k]) / h2;
+                for (int sg = 0; sg < 2; ++sg) {             // camera j moves
+                    bm_ray(x.Hs + (j * 9 + 1 + 2 * q + sg) * 9, x2, y2, r);
+                    const double mm = sqrt(fi * (q == 0 ? x.fv[3 * j + 1 + sg] : fj));
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) (sg ? e1 : e0)[k] = mm * (a[k] - r[k]);
+                }
+#pragma unroll
+                for (int k = 0; k < 3; ++k) out[3 + 8 * k + 4 + q] = (e1[k] - e0[k]) / h2;
+            }
+        }
+    }
+};
+
+// ---- BundleAdjusterReproj: focal, ppx, ppy, aspect and rvec a camera, the reprojection error of p1 in image 2 a match ------------------------
+constexpr int RP_VAR = 29;                                   // an edge's H: plain, then 1 + 2 q + sign for the 14 parameters of its two cameras
+struct ReprojTr {
+    static constexpr int PC = 7, RES = 2, THREADS = 512, RV = 4;
+    static constexpr double STEP = 1e-4;
+    static constexpr int HS = BA_MAXN * 9;                   // LDS holds only the rotations of the last phase: the H live in scratch
+    static constexpr int FV = 1;
+    static constexpr int HMAT = RP_VAR * 9;
+    static const char* who() { return "bundle_adjust_reproj"; }
+    static const char* kernel() { return "bundle_reproj_rigs"; }
+
+    __device__ static void init_param(const double* ci, double* p) { p[0] = ci[0]; p[1] = ci[2]; p[2] = ci[3]; p[3] = ci[1]; }
+    __device__ static void intrinsics(const double* p, const double*, double& focal, double& aspect, double& ppx, double& ppy) {
+        focal = p[0]; ppx = p[1]; ppy = p[2]; aspect = p[3];
+    }
+    // the bit of refine_flags that frees intrinsic q (focal, ppx, ppy, aspect): OpenCV's refinement mask (0,0), (0,2), (1,2), (1,1)
+    __device__ static bool refined(int flags, int q) { return q >= 4 || (flags & (q == 0 ? 1 : (q == 1 ? 4 : (q == 2 ? 16 : 8)))) != 0; }
+
+    // H of every edge with an inlier at `p`: variant 0, and with jac the 28 perturbed ones (columns 0 - 6 camera from, 7 - 13 camera to); a
+    // column that is not refined has no H and stays zero in J
+    __device__ static void cam_mats(const BaCtx& x, const double* p, bool jac) {
+        const int per = jac ? RP_VAR : 1;
+        for (int w = x.tid; w < x.pc * per; w += THREADS) {
+            const int k = w / per, v = w % per;
+            if (x.ptab[3 * k] == 0) continue;
+            const BaPair& P = x.prs[k];
+            double a[7], b[7];
+#pragma unroll
+            for (int e = 0; e < 7; ++e) { a[e] = p[7 * P.from + e]; b[e] = p[7 * P.to + e]; }
+            if (v > 0) {
+                const int col = (v - 1) >> 1, q = col >= 7 ? col - 7 : col;
+                if (!refined(x.flags, q)) continue;
+                const double val = col >= 7 ? b[q] : a[q];
+                const double moved = ((v - 1) & 1) ? val + STEP : val - STEP;
+#pragma unroll
+                for (int e = 0; e < 7; ++e) { a[e] = (col < 7 && e == q) ? moved : a[e]; b[e] = (col >= 7 && e == q) ? moved : b[e]; }
+            }
+            double H[9];
+            bm_reproj_h(a, b, H);
+#pragma unroll
+            for (int e = 0; e < 9; ++e) x.hmat[((long long)k * RP_VAR + v) * 9 + e] = H[e];
+        }
+    }
+
+    __device__ static void matches(const BaCtx& x, bool jac) {
+        constexpr int JROW = 30;
+        const int M = x.ctl[C_M];
+        const double h2 = 2.0 * STEP;
+        for (int idx = x.tid; idx < M; idx += THREADS) {
+            const double* const H = x.hmat + (long long)x.match_pair[idx] * (RP_VAR * 9);
+            const float4 pt = x.pts[idx];
+            const double x1 = (double)pt.x, y1 = (double)pt.y, x2 = (double)pt.z, y2 = (double)pt.w;
+            double* const out = x.jrow + (long long)idx * JROW;
+            double e[2];
+            bm_reproj_err(H, x1, y1, x2, y2, e);
+            out[0] = e[0]; out[1] = e[1];
+            if (!jac) continue;
+            for (int col = 0; col < 14; ++col) {
+                double d0 = 0.0, d1 = 0.0;
+                if (refined(x.flags, col >= 7 ? col - 7 : col)) {
+                    double e0[2], e1[2];
+                    bm_reproj_err(H + (1 + 2 * col) * 9, x1, y1, x2, y2, e0);
+                    bm_reproj_err(H + (2 + 2 * col) * 9, x1, y1, x2, y2, e1);
+                    d0 = (e1[0] - e0[0]) / h2; d1 = (e1[1] - e0[1]) / h2;
+                }
+                out[2 + col] = d0; out[2 + 14 + col] = d1;
+            }
+        }
+    }
+};
+static_assert(BaK<RayTr>::ENT == 45 && BaK<RayTr>::JROW == 27 && BaK<ReprojTr>::ENT == 120 && BaK<ReprojTr>::JROW == 30, "the tiles of both adjusters");
+
+// (a, b), a <= b, of the upper triangle of the W x W block, rows in order
+template <int W>
+__device__ __forceinline__ int ba_upper(int a, int b) { return W * a - (a * (a - 1)) / 2 + (b - a); }
+
+// a tile's partial sums over its matches in order, the residuals of each in order: all ENT with jac, the sum of err^2 alone without
+template <class Tr>
 __device__ void ba_tiles(const BaCtx& x, bool jac) {
+    constexpr int W = BaK<Tr>::W, U = BaK<Tr>::U, ENT = BaK<Tr>::ENT, JROW = BaK<Tr>::JROW, RES = Tr::RES;
     const int T = x.ctl[C_T];
-    const int per = jac ? BA_ENT : 1;
-    for (int w = x.tid; w < T * per; w += BA_THREADS) {
-        const int t = w / per, ent = jac ? w % per : BA_ENT - 1;
+    const int per = jac ? ENT : 1;
+    for (int w = x.tid; w < T * per; w += Tr::THREADS) {
+        const int t = w / per, ent = jac ? w % per : ENT - 1;
         const int p = x.tile_pair[t];
         const int m = x.ptab[3 * p], first = x.ptab[3 * p + 1];
         const int m0 = first + (t - x.ptab[3 * p + 2]) * BA_TILE, m1 = min(m0 + BA_TILE, first + m);
-        int ca = 0, cb = 0;                                  // the two columns of a row that are multiplied (0 - 2: err, 3 + ..: J)
-        if (ent < 36) {
+        int ca = 0, cb = 0;                                  // the two columns of a row that are multiplied (< 0: err, else a column of J)
+        if (ent < U) {
             int a = 0, rest = ent;
-            while (rest >= 8 - a) { rest -= 8 - a; ++a; }
+            while (rest >= W - a) { rest -= W - a; ++a; }
             ca = a; cb = a + rest;
-        } else if (ent < 44) {
-            ca = ent - 36; cb = -1;
+        } else if (ent < U + W) {
+            ca = ent - U; cb = -1;
         } else {
             ca = -1; cb = -1;
         }
         double s = 0.0;
         for (int idx = m0; idx < m1; ++idx) {
-            const double* row = x.jrow + (long long)idx * BA_JROW;
+            const double* row = x.jrow + (long long)idx * JROW;
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const double u = ca < 0 ? row[k] : row[3 + 8 * k + ca];
-                const double v = cb < 0 ? row[k] : row[3 + 8 * k + cb];
+            for (int k = 0; k < RES; ++k) {
+                const double u = ca < 0 ? row[k] : row[RES + W * k + ca];
+                const double v = cb < 0 ? row[k] : row[RES + W * k + cb];
                 s = s + (u * v);
             }
         }
-        x.tiles[(long long)t * BA_ENT + ent] = s;
+        x.tiles[(long long)t * ENT + ent] = s;
     }
 }
 
 // the sum over the tiles of pair p, in order, of entry `ent`, added to s
+template <class Tr>
 __device__ __forceinline__ double ba_add_tiles(const BaCtx& x, int p, int ent, double s) {
     const int m = x.ptab[3 * p], t0 = x.ptab[3 * p + 2], t1 = t0 + (m + BA_TILE - 1) / BA_TILE;
-    for (int t = t0; t < t1; ++t) s = s + x.tiles[(long long)t * BA_ENT + ent];
+    for (int t = t0; t < t1; ++t) s = s + x.tiles[(long long)t * BaK<Tr>::ENT + ent];
     return s;
 }
 
-// |err| from the tiles' sums of err^2, all tiles in order, into dctl[D_ENORM]: the block fetches BA_THREADS of them at a time into LDS (prow
-// is free outside ba_step) and thread 0 adds them in order - one memory latency a chunk, not one a tile.  Called by every thread.
+// |err| from the tiles' sums of err^2, all tiles in order, into dctl[D_ENORM]: the block fetches a thread's worth of them at a time into LDS
+// (prow is free outside ba_step) and thread 0 adds them in order - one memory latency a chunk, not one a tile.  Called by every thread.
+template <class Tr>
 __device__ void ba_err_norm(const BaCtx& x) {
+    constexpr int ENT = BaK<Tr>::ENT, THREADS = Tr::THREADS;
     const int T = x.ctl[C_T];
     double s = 0.0;
-    for (int t0 = 0; t0 < T; t0 += BA_THREADS) {
-        if (t0 + x.tid < T) x.prow[x.tid] = x.tiles[(long long)(t0 + x.tid) * BA_ENT + (BA_ENT - 1)];
+    for (int t0 = 0; t0 < T; t0 += THREADS) {
+        if (t0 + x.tid < T) x.prow[x.tid] = x.tiles[(long long)(t0 + x.tid) * ENT + (ENT - 1)];
         __syncthreads();
         if (x.tid == 0) {
-            const int m = min(BA_THREADS, T - t0);
+            const int m = min(THREADS, T - t0);
             for (int u = 0; u < m; ++u) s = s + x.prow[u];
         }
         __syncthreads();
@@ -208,42 +321,45 @@ __device__ void ba_err_norm(const BaCtx& x) {
 }
 
 // JtJ (upper triangle computed, mirrored) and JtErr from the tiles: per camera the edges that touch it in edge order
+template <class Tr>
 __device__ void ba_assemble(const BaCtx& x) {
+    constexpr int PC = Tr::PC, W = BaK<Tr>::W, U = BaK<Tr>::U;
     const int n = x.n, N = x.N;
-    for (int w = x.tid; w < N * N; w += BA_THREADS) {
+    for (int w = x.tid; w < N * N; w += Tr::THREADS) {
         const int A = w / N, B = w % N;
         if (A > B) continue;
-        const int c = A >> 2, a = A & 3, d = B >> 2, b = B & 3;
+        const int c = A / PC, a = A % PC, d = B / PC, b = B % PC;
         double s = 0.0;
         if (c == d) {
             for (int o = 0; o < n; ++o) {
                 if (o == c) continue;
                 const int p = x.slot[min(o, c) * BA_MAXN + max(o, c)];
                 if (p < 0) continue;
-                const int off = o < c ? 4 : 0;
-                s = ba_add_tiles(x, p, ba_upper(off + a, off + b), s);
+                const int off = o < c ? PC : 0;
+                s = ba_add_tiles<Tr>(x, p, ba_upper<W>(off + a, off + b), s);
             }
         } else {
             const int p = x.slot[c * BA_MAXN + d];
-            if (p >= 0) s = ba_add_tiles(x, p, ba_upper(a, 4 + b), s);
+            if (p >= 0) s = ba_add_tiles<Tr>(x, p, ba_upper<W>(a, PC + b), s);
         }
         x.jtj[(long long)A * N + B] = s;
         x.jtj[(long long)B * N + A] = s;
     }
     if (x.tid < N) {
-        const int c = x.tid >> 2, a = x.tid & 3;
+        const int c = x.tid / PC, a = x.tid % PC;
         double s = 0.0;
         for (int o = 0; o < n; ++o) {
             if (o == c) continue;
             const int p = x.slot[min(o, c) * BA_MAXN + max(o, c)];
             if (p < 0) continue;
-            s = ba_add_tiles(x, p, 36 + (o < c ? 4 : 0) + a, s);
+            s = ba_add_tiles<Tr>(x, p, U + (o < c ? PC : 0) + a, s);
         }
         x.bvec[x.tid] = s;
     }
 }
 
-// step(): JtJN = JtJ with the diagonal times 1 + lambda; Cholesky with the trace rule; the two substitutions; param = prev - d
+// step(): JtJN = JtJ with the diagonal times 1 + lambda; Cholesky with the trace rule; the two substitutions; param = prev - d.  Threads
+// past the last row only keep the barriers.
 __device__ void ba_step(const BaCtx& x, double lambda) {
     const int N = x.N, r = x.tid;
     const double scale = 1.0 + lambda;
@@ -332,10 +448,12 @@ __device__ void ba_passthrough(const BaCall& c, const BaRig& rig, int tid) {
     }
 }
 
-__global__ __launch_bounds__(BA_THREADS) void k_ba_rigs(BaCall c) {
-    __shared__ double Hs[BA_MAXN * 81];                      // [camera][variant][9]: R K^-1, plain and with one parameter moved either way
-    __shared__ double fv[BA_MAXN * 3];                       // [camera]: f, f - step, f + step
-    __shared__ double param[BA_MAXP], prev[BA_MAXP], bvec[BA_MAXP], bc[BA_MAXP], prow[BA_MAXP];
+template <class Tr>
+__global__ __launch_bounds__(Tr::THREADS) void k_ba_rigs(BaCall c) {
+    constexpr int BA_THREADS = Tr::THREADS, BA_MAXP = BaK<Tr>::MAXP, BA_ENT = BaK<Tr>::ENT, BA_JROW = BaK<Tr>::JROW, PC = Tr::PC;
+    __shared__ double Hs[Tr::HS];                            // the camera matrices of Tr::cam_mats; the rotations of the last phase
+    __shared__ double fv[Tr::FV];
+    __shared__ double param[BA_MAXP], prev[BA_MAXP], bvec[BA_MAXP], bc[BA_MAXP], prow[BaK<Tr>::PROW];
     __shared__ double dctl[D_N];
     __shared__ short slot[BA_MAXN * BA_MAXN];                // [i * 64 + j], i < j: the edge's pair in the rig's table, -1 where there is none
     __shared__ int ctl[C_N];
@@ -343,7 +461,7 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_rigs(BaCall c) {
 
     const int tid = (int)threadIdx.x;
     const BaRig rig = c.rigs[blockIdx.x];
-    const int n = rig.n, pc = rig.pair_count, N = 4 * n;
+    const int n = rig.n, pc = rig.pair_count, N = PC * n;
     const BaImg* const imgs = c.imgs + rig.img_first;
     BaCtx x;
     x.Hs = Hs; x.fv = fv; x.param = param; x.prev = prev; x.bvec = bvec; x.bc = bc; x.prow = prow; x.dctl = dctl;
@@ -355,7 +473,8 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_rigs(BaCall c) {
     x.pts = pts; x.match_pair = match_pair; x.jrow = c.jrow + rig.match_first * BA_JROW;
     x.tiles = c.tiles + rig.tile_first * BA_ENT; x.tile_pair = tile_pair;
     x.jtj = c.jtj + rig.mat_first; x.lt = c.lt + rig.mat_first;
-    x.n = n; x.N = N; x.tid = tid;
+    x.hmat = c.hmat + (long long)rig.pair_first * Tr::HMAT;
+    x.n = n; x.N = N; x.tid = tid; x.pc = pc; x.flags = c.refine_flags;
 
     for (int i = tid; i < BA_MAXN * BA_MAXN; i += BA_THREADS) slot[i] = -1;
     if (tid < C_N) ctl[tid] = 0;
@@ -426,22 +545,22 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_rigs(BaCall c) {
         for (int e = 0; e < 9; ++e) R[e] = (double)(float)ci[4 + e];      // W:183-188
         if (!bm_polar(R, Q)) atomicOr(&ctl[C_STATUS], ISX_BUNDLE_SINGULAR_R);
         bm_rodrigues_vec(Q, rv);
-        param[4 * tid] = ci[0];
+        Tr::init_param(ci, param + PC * tid);
 #pragma unroll
-        for (int e = 0; e < 3; ++e) param[4 * tid + 1 + e] = (double)(float)rv[e];
+        for (int e = 0; e < 3; ++e) param[PC * tid + Tr::RV + e] = (double)(float)rv[e];
     }
     __syncthreads();
 
     // ---- CvLevMarq ----
     for (;;) {
-        ba_cam_mats(x, param, true);
+        Tr::cam_mats(x, param, true);
         __syncthreads();
-        ba_matches(x, true);
+        Tr::matches(x, true);
         __syncthreads();
-        ba_tiles(x, true);
+        ba_tiles<Tr>(x, true);
         __syncthreads();
-        ba_assemble(x);
-        ba_err_norm(x);
+        ba_assemble<Tr>(x);
+        ba_err_norm<Tr>(x);
         if (tid < N) prev[tid] = param[tid];
         __syncthreads();
         if (tid == 0) {
@@ -450,13 +569,13 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_rigs(BaCall c) {
         }
         for (;;) {                                           // step(), calcError, CHECK_ERR: 33 times an iteration at the most
             ba_step(x, BA_LAMBDA[ctl[C_LG] + 16]);
-            ba_cam_mats(x, param, false);
+            Tr::cam_mats(x, param, false);
             __syncthreads();
-            ba_matches(x, false);
+            Tr::matches(x, false);
             __syncthreads();
-            ba_tiles(x, false);
+            ba_tiles<Tr>(x, false);
             __syncthreads();
-            ba_err_norm(x);
+            ba_err_norm<Tr>(x);
             if (tid == 0) {
                 ++ctl[C_EEV];
                 int again = 0;
@@ -495,7 +614,7 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_rigs(BaCall c) {
     } else {
         if (tid < n) {
             double R[9];
-            bm_rodrigues_mat(param + 4 * tid + 1, R);
+            bm_rodrigues_mat(param + PC * tid + Tr::RV, R);
 #pragma unroll
             for (int e = 0; e < 9; ++e) Hs[9 * tid + e] = (double)(float)R[e];
         }
@@ -510,7 +629,9 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_rigs(BaCall c) {
             for (int e = 0; e < 9; ++e) { Rc[e] = Hs[9 * ctl[C_CENTER] + e]; Ri[e] = Hs[9 * tid + e]; }
             es_inv3(Rc, Rinv);
             es_mul3(Rinv, Ri, o);
-            const double focal = param[4 * tid], aspect = ci[1], ppx = ci[2], ppy = ci[3], t0 = ci[13], t1 = ci[14], t2 = ci[15];
+            const double t0 = ci[13], t1 = ci[14], t2 = ci[15];
+            double focal, aspect, ppx, ppy;
+            Tr::intrinsics(param + PC * tid, ci, focal, aspect, ppx, ppy);
             co[0] = focal; co[1] = aspect; co[2] = ppx; co[3] = ppy;
 #pragma unroll
             for (int e = 0; e < 9; ++e) { const float f = (float)o[e]; co[4 + e] = (double)f; ko[9 + e] = f; }
@@ -531,11 +652,13 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_rigs(BaCall c) {
 
 struct BaScratch : UploadScratch {};     // pin: the tables and the staged rows of host input mats (scratch.hpp)
 
+template <class Tr>
 int ba_call(int num_images, const int* image_sizes_wh, const isx_mat* keypoints, int num_pairs, const int* pairs_from_to, const isx_mat* matches,
             const isx_mat* inlier_masks, const isx_mat* counts, const isx_mat* stats, const isx_mat* conf, int num_rigs, const int* rig_first,
-            const isx_mat* est_rig_stats, const isx_mat* cameras_in, double conf_thresh, int max_iter, double eps, isx_mat* cameras_out,
-            isx_mat* kr32_out, isx_mat* rig_stats_out, isx_mat* rig_err_out, int* info, int device, void* hip_stream) {
-    const char* who = "bundle_adjust_ray";
+            const isx_mat* est_rig_stats, const isx_mat* cameras_in, double conf_thresh, int max_iter, double eps, int refine_flags,
+            isx_mat* cameras_out, isx_mat* kr32_out, isx_mat* rig_stats_out, isx_mat* rig_err_out, int* info, int device, void* hip_stream) {
+    constexpr int BA_THREADS = Tr::THREADS, BA_ENT = BaK<Tr>::ENT, BA_JROW = BaK<Tr>::JROW, PC = Tr::PC;
+    const char* who = Tr::who();
     // ---- checks: all of them before anything is written or enqueued ----
     ISX_CHECK_ARG(image_sizes_wh && keypoints && counts && stats && conf && est_rig_stats && cameras_in && cameras_out && kr32_out && rig_stats_out && rig_err_out,
                   ISX_ERR_INVALID, "%s: null image_sizes_wh, keypoints, counts, stats, conf, est_rig_stats, cameras_in, cameras_out, kr32_out, rig_stats_out or rig_err_out", who);
@@ -546,6 +669,7 @@ int ba_call(int num_images, const int* image_sizes_wh, const isx_mat* keypoints,
     ISX_CHECK_ARG(max_iter >= 1 && max_iter <= 1000, ISX_ERR_INVALID, "%s: max_iter %d is not in [1, 1000]", who, max_iter);
     ISX_CHECK_ARG(conf_thresh >= 0, ISX_ERR_INVALID, "%s: conf_thresh %g is negative or not a number (an edge must have a mask the homography stage wrote)", who, conf_thresh);
     ISX_CHECK_ARG(eps == eps, ISX_ERR_INVALID, "%s: eps is not a number", who);
+    ISX_CHECK_ARG(refine_flags >= 0 && refine_flags <= 31, ISX_ERR_INVALID, "%s: refine_flags %d is not in [0, 31]", who, refine_flags);
     std::vector<int> first((size_t)num_rigs + 1);
     for (int r = 0; r <= num_rigs; ++r) first[r] = rig_first ? rig_first[r] : (r == 0 ? 0 : num_images);
     ISX_CHECK_ARG(first[0] == 0 && first[num_rigs] == num_images, ISX_ERR_INVALID, "%s: rig_first runs from %d to %d, not from 0 to %d", who, first[0],
@@ -611,7 +735,7 @@ int ba_call(int num_images, const int* image_sizes_wh, const isx_mat* keypoints,
                 match_total += cap[at];
                 tile_total += cap[at] > 0 ? cap[at] / BA_TILE + 1 : 0;
             }
-            mat_total += 16ll * rigs[r].n * rigs[r].n;
+            mat_total += (long long)(PC * PC) * rigs[r].n * rigs[r].n;
         }
     }
     StagedMat m_counts, m_conf, m_est, m_cin, m_cout, m_kr, m_rs, m_re;
@@ -641,6 +765,7 @@ int ba_call(int num_images, const int* image_sizes_wh, const isx_mat* keypoints,
     const size_t o_ptab = lay.take((size_t)std::max(num_pairs, 1) * 12);
     const size_t o_jtj = lay.take((size_t)mat_total * 8);
     const size_t o_lt = lay.take((size_t)mat_total * 8);
+    const size_t o_hmat = lay.take((size_t)std::max(num_pairs, 1) * Tr::HMAT * 8);
     m_cout.plan(lay, *cameras_out, num_images, 128);
     m_kr.plan(lay, *kr32_out, num_images, 72);
     m_rs.plan(lay, *rig_stats_out, num_rigs, 32);
@@ -695,9 +820,9 @@ int ba_call(int num_images, const int* image_sizes_wh, const isx_mat* keypoints,
     m_re.bind(dev, c.re, c.re_step);
     c.pts = (float4*)(dev + o_pts); c.match_pair = (int*)(dev + o_mpair); c.jrow = (double*)(dev + o_jrow);
     c.tiles = (double*)(dev + o_tiles); c.tile_pair = (int*)(dev + o_tpair); c.pair_tab = (int*)(dev + o_ptab);
-    c.jtj = (double*)(dev + o_jtj); c.lt = (double*)(dev + o_lt);
-    c.conf_thresh = conf_thresh; c.eps = eps; c.max_iter = max_iter;
-    ISX_LAUNCH("bundle_rigs", (double)match_total * 24.0 + (double)num_images * 272.0, st, k_ba_rigs, dim3((unsigned)num_rigs), dim3(BA_THREADS), 0, c);
+    c.jtj = (double*)(dev + o_jtj); c.lt = (double*)(dev + o_lt); c.hmat = (double*)(dev + o_hmat);
+    c.conf_thresh = conf_thresh; c.eps = eps; c.max_iter = max_iter; c.refine_flags = refine_flags;
+    ISX_LAUNCH(Tr::kernel(), (double)match_total * 24.0 + (double)num_images * 272.0, st, k_ba_rigs<Tr>, dim3((unsigned)num_rigs), dim3(BA_THREADS), 0, c);
     ISX_TRY(s.ran(st));
 
     // ---- host outputs ----
@@ -706,6 +831,150 @@ int ba_call(int num_images, const int* image_sizes_wh, const isx_mat* keypoints,
         ISX_TRY(m_kr.back(dev, num_images, st));
         ISX_TRY(m_rs.back(dev, num_rigs, st));
         ISX_TRY(m_re.back(dev, num_rigs, st));
+        ISX_HIP(hipStreamSynchronize(st));
+    }
+    if (info) { info[0] = num_rigs; info[1] = 1; }
+    return ISX_OK;
+}
+
+// ---- waveCorrect: one block a rig; thread 0 finds the correction (sums in image order, a 3 x 3 Jacobi), a thread per image applies it --------
+struct WvCall {
+    const int* first;
+    const double* cin; long long cin_step;
+    double* cout; long long cout_step;
+    float* kr; long long kr_step;
+    int* rs; long long rs_step;
+    int kind;
+};
+constexpr int WV_THREADS = 64;
+
+__device__ __forceinline__ float wv_r(const WvCall& c, long long img, int e) { return (float)row_ptr(c.cin, img, c.cin_step)[4 + e]; }
+
+__global__ __launch_bounds__(WV_THREADS) void k_wave_rigs(WvCall c) {
+    __shared__ float Rw[9];
+    __shared__ int status;
+    const int tid = (int)threadIdx.x;
+    const long long i0 = c.first[blockIdx.x];
+    const int n = c.first[blockIdx.x + 1] - c.first[blockIdx.x];
+    if (tid == 0) {
+        int st = n <= 1 ? ISX_WAVE_SINGLE : 0;
+        if (st == 0) {
+            float moment[9], V[9], Wv[3], k[3] = {0.f, 0.f, 0.f};
+            for (int e = 0; e < 9; ++e) moment[e] = 0.f;
+            for (int i = 0; i < n; ++i) {
+                const float col[3] = {wv_r(c, i0 + i, 0), wv_r(c, i0 + i, 3), wv_r(c, i0 + i, 6)};
+                for (int r = 0; r < 3; ++r)
+                    for (int q = 0; q < 3; ++q) moment[3 * r + q] = moment[3 * r + q] + (col[r] * col[q]);
+                k[0] = k[0] + wv_r(c, i0 + i, 2); k[1] = k[1] + wv_r(c, i0 + i, 5); k[2] = k[2] + wv_r(c, i0 + i, 8);
+            }
+            bm_jacobi3f(moment, V, Wv);
+            const int row = c.kind == ISX_WAVE_CORRECT_HORIZ ? 2 : 0;
+            float rg1[3] = {V[3 * row], V[3 * row + 1], V[3 * row + 2]};
+            float rg0[3] = {(rg1[1] * k[2]) - (rg1[2] * k[1]), (rg1[2] * k[0]) - (rg1[0] * k[2]), (rg1[0] * k[1]) - (rg1[1] * k[0])};
+            const float nrm = sqrtf(((rg0[0] * rg0[0]) + (rg0[1] * rg0[1])) + (rg0[2] * rg0[2]));
+            if ((double)nrm <= DBL_MIN) {
+                st = ISX_WAVE_DEGENERATE;
+            } else {
+                for (int e = 0; e < 3; ++e) rg0[e] = rg0[e] / nrm;
+                const float rg2[3] = {(rg0[1] * rg1[2]) - (rg0[2] * rg1[1]), (rg0[2] * rg1[0]) - (rg0[0] * rg1[2]), (rg0[0] * rg1[1]) - (rg0[1] * rg1[0])};
+                const float* const rg = c.kind == ISX_WAVE_CORRECT_HORIZ ? rg0 : rg1;
+                float conf = 0.f;
+                for (int i = 0; i < n; ++i) {
+                    const float d = ((rg[0] * wv_r(c, i0 + i, 0)) + (rg[1] * wv_r(c, i0 + i, 3))) + (rg[2] * wv_r(c, i0 + i, 6));
+                    conf = c.kind == ISX_WAVE_CORRECT_HORIZ ? conf + d : conf - d;
+                }
+                if (conf < 0.f)
+                    for (int e = 0; e < 3; ++e) { rg0[e] = -rg0[e]; rg1[e] = -rg1[e]; }
+                for (int e = 0; e < 3; ++e) { Rw[e] = rg0[e]; Rw[3 + e] = rg1[e]; Rw[6 + e] = rg2[e]; }
+            }
+        }
+        status = st;
+        int* const rs = row_ptr(c.rs, (long long)blockIdx.x, c.rs_step);
+        rs[0] = st; rs[1] = n;
+    }
+    __syncthreads();
+    const bool pass = status != 0;
+    for (int i = tid; i < n; i += WV_THREADS) {
+        const double* ci = row_ptr(c.cin, i0 + i, c.cin_step);
+        double* co = row_ptr(c.cout, i0 + i, c.cout_step);
+        float* ko = row_ptr(c.kr, i0 + i, c.kr_step);
+        double v[16];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) v[e] = ci[e];
+        float R[9], o[9];
+#pragma unroll
+        for (int e = 0; e < 9; ++e) R[e] = (float)v[4 + e];
+        if (pass) {
+#pragma unroll
+            for (int e = 0; e < 9; ++e) o[e] = R[e];
+        } else {
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+#pragma unroll
+                for (int q = 0; q < 3; ++q) o[3 * r + q] = ((Rw[3 * r] * R[q]) + (Rw[3 * r + 1] * R[3 + q])) + (Rw[3 * r + 2] * R[6 + q]);
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) co[e] = v[e];
+#pragma unroll
+        for (int e = 0; e < 9; ++e) { co[4 + e] = pass ? v[4 + e] : (double)o[e]; ko[9 + e] = o[e]; }
+#pragma unroll
+        for (int e = 13; e < 16; ++e) co[e] = v[e];
+        ko[0] = (float)v[0]; ko[1] = 0.f; ko[2] = (float)v[2];
+        ko[3] = 0.f; ko[4] = (float)(v[0] * v[1]); ko[5] = (float)v[3];
+        ko[6] = 0.f; ko[7] = 0.f; ko[8] = 1.f;
+    }
+}
+
+int wv_call(int num_images, int num_rigs, const int* rig_first, const isx_mat* cameras_in, int kind, isx_mat* cameras_out, isx_mat* kr32_out,
+            isx_mat* rig_stats_out, int* info, int device, void* hip_stream) {
+    const char* who = "wave_correct";
+    ISX_CHECK_ARG(cameras_in && cameras_out && kr32_out && rig_stats_out, ISX_ERR_INVALID, "%s: null cameras_in, cameras_out, kr32_out or rig_stats_out", who);
+    ISX_CHECK_ARG(num_rigs >= 1 && (rig_first || num_rigs == 1), ISX_ERR_INVALID, "%s: %d rigs, or more than one without rig_first", who, num_rigs);
+    ISX_CHECK_ARG(num_images >= 1, ISX_ERR_INVALID, "%s: %d images", who, num_images);
+    ISX_CHECK_ARG(kind == ISX_WAVE_CORRECT_HORIZ || kind == ISX_WAVE_CORRECT_VERT, ISX_ERR_INVALID, "%s: kind %d is neither horizontal (0) nor vertical (1)", who, kind);
+    std::vector<int> first((size_t)num_rigs + 1);
+    for (int r = 0; r <= num_rigs; ++r) first[r] = rig_first ? rig_first[r] : (r == 0 ? 0 : num_images);
+    ISX_CHECK_ARG(first[0] == 0 && first[num_rigs] == num_images, ISX_ERR_INVALID, "%s: rig_first runs from %d to %d, not from 0 to %d", who, first[0],
+                  first[num_rigs], num_images);
+    for (int r = 0; r < num_rigs; ++r) ISX_CHECK_ARG(first[r + 1] > first[r], ISX_ERR_INVALID, "%s: rig_first does not increase at rig %d", who, r);
+    ISX_TRY(check_mat_holds(*cameras_in, ISX_64FC1, num_images, 16, 8, STOP_NO_ROW_WANTED, device, who, "cameras_in", 0));
+    ISX_TRY(check_mat_holds(*cameras_out, ISX_64FC1, num_images, 16, 8, STOP_NO_ROW_WANTED, device, who, "cameras_out", 0));
+    ISX_TRY(check_mat_holds(*kr32_out, ISX_32FC1, num_images, 18, 4, STOP_NO_ROW_WANTED, device, who, "kr32_out", 0));
+    ISX_TRY(check_mat_holds(*rig_stats_out, ISX_32SC1, num_rigs, 2, 4, STOP_NO_ROW_WANTED, device, who, "rig_stats_out", 0));
+    ISX_HIP(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    ISX_TRY(refuse_capture(st, who, "the call uploads its table and may stage host mats"));
+
+    StagedMat m_cin, m_cout, m_kr, m_rs;
+    Bump lay;
+    const size_t o_first = lay.take(first.size() * 4);
+    m_cin.plan(lay, *cameras_in, num_images, 128);
+    const size_t upload_bytes = lay.at;
+    m_cout.plan(lay, *cameras_out, num_images, 128);
+    m_kr.plan(lay, *kr32_out, num_images, 72);
+    m_rs.plan(lay, *rig_stats_out, num_rigs, 8);
+    BaScratch& s = per_thread<BaScratch>();
+    ISX_TRY(s.begin(device, st, lay.at, upload_bytes));
+    char* const dev = (char*)s.work.p;
+    char* const pin = (char*)s.pin.p;
+    std::memcpy(pin + o_first, first.data(), first.size() * 4);
+    m_cin.fill(pin);
+    ISX_TRY(s.upload(st, upload_bytes));
+
+    WvCall c;
+    std::memset(&c, 0, sizeof(c));
+    c.first = (const int*)(dev + o_first);
+    m_cin.bind(dev, c.cin, c.cin_step);
+    m_cout.bind(dev, c.cout, c.cout_step);
+    m_kr.bind(dev, c.kr, c.kr_step);
+    m_rs.bind(dev, c.rs, c.rs_step);
+    c.kind = kind;
+    ISX_LAUNCH("wave_rigs", (double)num_images * 328.0, st, k_wave_rigs, dim3((unsigned)num_rigs), dim3(WV_THREADS), 0, c);
+    ISX_TRY(s.ran(st));
+    if (m_cout.staged || m_kr.staged || m_rs.staged) {
+        ISX_TRY(m_cout.back(dev, num_images, st));
+        ISX_TRY(m_kr.back(dev, num_images, st));
+        ISX_TRY(m_rs.back(dev, num_rigs, st));
         ISX_HIP(hipStreamSynchronize(st));
     }
     if (info) { info[0] = num_rigs; info[1] = 1; }
@@ -727,9 +996,26 @@ int isx_bundle_adjust_ray(int num_images, const int* image_sizes_wh, const isx_m
                           double eps, isx_mat* cameras_out, isx_mat* kr32_out, isx_mat* rig_stats_out, isx_mat* rig_err_out, int* info, int device,
                           void* hip_stream) ISX_ENTRY {
     clear_error();
-    return ba_call(num_images, image_sizes_wh, keypoints, num_pairs, pairs_from_to, matches, inlier_masks, counts, stats, conf, num_rigs, rig_first,
-                   est_rig_stats, cameras_in, conf_thresh, max_iter, eps, cameras_out, kr32_out, rig_stats_out, rig_err_out, info, device, hip_stream);
+    return ba_call<RayTr>(num_images, image_sizes_wh, keypoints, num_pairs, pairs_from_to, matches, inlier_masks, counts, stats, conf, num_rigs, rig_first,
+                          est_rig_stats, cameras_in, conf_thresh, max_iter, eps, 0, cameras_out, kr32_out, rig_stats_out, rig_err_out, info, device, hip_stream);
 } ISX_EXIT("isx_bundle_adjust_ray")
+
+int isx_bundle_adjust_reproj(int num_images, const int* image_sizes_wh, const isx_mat* keypoints, int num_pairs, const int* pairs_from_to,
+                             const isx_mat* matches, const isx_mat* inlier_masks, const isx_mat* counts, const isx_mat* stats, const isx_mat* conf,
+                             int num_rigs, const int* rig_first, const isx_mat* est_rig_stats, const isx_mat* cameras_in, double conf_thresh,
+                             int max_iter, double eps, int refine_flags, isx_mat* cameras_out, isx_mat* kr32_out, isx_mat* rig_stats_out,
+                             isx_mat* rig_err_out, int* info, int device, void* hip_stream) ISX_ENTRY {
+    clear_error();
+    return ba_call<ReprojTr>(num_images, image_sizes_wh, keypoints, num_pairs, pairs_from_to, matches, inlier_masks, counts, stats, conf, num_rigs,
+                             rig_first, est_rig_stats, cameras_in, conf_thresh, max_iter, eps, refine_flags, cameras_out, kr32_out, rig_stats_out,
+                             rig_err_out, info, device, hip_stream);
+} ISX_EXIT("isx_bundle_adjust_reproj")
+
+int isx_wave_correct(int num_images, int num_rigs, const int* rig_first, const isx_mat* cameras_in, int kind, isx_mat* cameras_out, isx_mat* kr32_out,
+                     isx_mat* rig_stats_out, int* info, int device, void* hip_stream) ISX_ENTRY {
+    clear_error();
+    return wv_call(num_images, num_rigs, rig_first, cameras_in, kind, cameras_out, kr32_out, rig_stats_out, info, device, hip_stream);
+} ISX_EXIT("isx_wave_correct")
 
 int isx_selftest_bundle_math(int fn, int n, const double* in, double* out) ISX_ENTRY {
     clear_error();

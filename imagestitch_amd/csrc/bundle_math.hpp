@@ -3,7 +3,8 @@
 // a library sin that differs by an ulp between host, device and model would change its length), cvRodrigues2 in both directions, the polar
 // factor of setUpInitialCameraParams, R * K.inv() and the ray of calcError.  tests/helpers/bundle_np.py repeats every function operation for
 // operation (DESIGN.md §8 "Bundle adjuster"); isx_selftest_bundle_math runs the host compilation.  Every expression is evaluated as written,
-// left to right, no contraction (-ffp-contract=off).  Internal.
+// left to right, no contraction (-ffp-contract=off).  Also here: the edge matrix and the two residuals of BundleAdjusterReproj's calcError
+// (tests/helpers/bundle_reproj_np.py), and the 3 x 3 Jacobi as a template, run in float32 by the wave correction.  Internal.
 #pragma once
 #include <cfloat>
 #include <cmath>
@@ -117,50 +118,56 @@ ISX_HD inline void bm_rodrigues_vec(const double* R, double* rv) {
 }
 
 // ---- JacobiImpl_ at n = 3 (homography_lm_np.jacobi_n): A's upper triangle is read and destroyed; W descending with the rows of V ----------
-ISX_HD inline double bm_hypot(double a, double b) {
-    a = fabs(a); b = fabs(b);
-    if (a > b) { b /= a; return a * sqrt(1.0 + (b * b)); }
-    if (b > 0) { a /= b; return b * sqrt(1.0 + (a * a)); }
-    return 0.0;
+ISX_HD inline double bm_fabs(double v) { return fabs(v); }
+ISX_HD inline float bm_fabs(float v) { return fabsf(v); }
+ISX_HD inline double bm_sqrt(double v) { return sqrt(v); }
+ISX_HD inline float bm_sqrt(float v) { return sqrtf(v); }
+template <class T>
+ISX_HD inline T bm_hypot_t(T a, T b) {
+    a = bm_fabs(a); b = bm_fabs(b);
+    if (a > b) { b /= a; return a * bm_sqrt(T(1) + (b * b)); }
+    if (b > 0) { a /= b; return b * bm_sqrt(T(1) + (a * a)); }
+    return T(0);
 }
-ISX_HD inline void bm_jacobi3(double* A, double* V, double* W) {
+template <class T>
+ISX_HD inline void bm_jacobi3_t(T* A, T* V, T* W, T eps) {
     constexpr int n = 3;
     int indR[n] = {0, 0, 0}, indC[n] = {0, 0, 0};
-    for (int i = 0; i < n * n; ++i) V[i] = 0.0;
-    for (int i = 0; i < n; ++i) V[i * n + i] = 1.0;
+    for (int i = 0; i < n * n; ++i) V[i] = T(0);
+    for (int i = 0; i < n; ++i) V[i * n + i] = T(1);
     for (int k = 0; k < n; ++k) {
         W[k] = A[(n + 1) * k];
         if (k < n - 1) {
             int m = k + 1;
-            double mv = fabs(A[n * k + m]);
-            for (int i = k + 2; i < n; ++i) { const double val = fabs(A[n * k + i]); if (mv < val) { mv = val; m = i; } }
+            T mv = bm_fabs(A[n * k + m]);
+            for (int i = k + 2; i < n; ++i) { const T val = bm_fabs(A[n * k + i]); if (mv < val) { mv = val; m = i; } }
             indR[k] = m;
         }
         if (k > 0) {
             int m = 0;
-            double mv = fabs(A[k]);
-            for (int i = 1; i < k; ++i) { const double val = fabs(A[n * i + k]); if (mv < val) { mv = val; m = i; } }
+            T mv = bm_fabs(A[k]);
+            for (int i = 1; i < k; ++i) { const T val = bm_fabs(A[n * i + k]); if (mv < val) { mv = val; m = i; } }
             indC[k] = m;
         }
     }
     for (int iters = 0; iters < n * n * 30; ++iters) {
         int k = 0;
-        double mv = fabs(A[indR[0]]);
-        for (int i = 1; i < n - 1; ++i) { const double val = fabs(A[n * i + indR[i]]); if (mv < val) { mv = val; k = i; } }
+        T mv = bm_fabs(A[indR[0]]);
+        for (int i = 1; i < n - 1; ++i) { const T val = bm_fabs(A[n * i + indR[i]]); if (mv < val) { mv = val; k = i; } }
         int l = indR[k];
-        for (int i = 1; i < n; ++i) { const double val = fabs(A[n * indC[i] + i]); if (mv < val) { mv = val; k = indC[i]; l = i; } }
-        const double p = A[n * k + l];
-        if (fabs(p) <= DBL_EPSILON) break;
-        const double y = (W[l] - W[k]) * 0.5;
-        double t = fabs(y) + bm_hypot(p, y);
-        double s = bm_hypot(p, t);
-        const double c = t / s;
+        for (int i = 1; i < n; ++i) { const T val = bm_fabs(A[n * indC[i] + i]); if (mv < val) { mv = val; k = indC[i]; l = i; } }
+        const T p = A[n * k + l];
+        if (bm_fabs(p) <= eps) break;
+        const T y = (W[l] - W[k]) * T(0.5);
+        T t = bm_fabs(y) + bm_hypot_t(p, y);
+        T s = bm_hypot_t(p, t);
+        const T c = t / s;
         s = p / s; t = (p / t) * p;
         if (y < 0) { s = -s; t = -t; }
-        A[n * k + l] = 0.0;
+        A[n * k + l] = T(0);
         W[k] = W[k] - t;
         W[l] = W[l] + t;
-#define BM_ROT(i0, i1, M) do { const double a0 = M[i0], b0 = M[i1]; M[i0] = (a0 * c) - (b0 * s); M[i1] = (a0 * s) + (b0 * c); } while (0)
+#define BM_ROT(i0, i1, M) do { const T a0 = M[i0], b0 = M[i1]; M[i0] = (a0 * c) - (b0 * s); M[i1] = (a0 * s) + (b0 * c); } while (0)
         for (int i = 0; i < k; ++i) BM_ROT(n * i + k, n * i + l, A);
         for (int i = k + 1; i < l; ++i) BM_ROT(n * k + i, n * i + l, A);
         for (int i = l + 1; i < n; ++i) BM_ROT(n * k + i, n * l + i, A);
@@ -170,14 +177,14 @@ ISX_HD inline void bm_jacobi3(double* A, double* V, double* W) {
             const int idx = j == 0 ? k : l;
             if (idx < n - 1) {
                 int m = idx + 1;
-                double mx = fabs(A[n * idx + m]);
-                for (int i = idx + 2; i < n; ++i) { const double val = fabs(A[n * idx + i]); if (mx < val) { mx = val; m = i; } }
+                T mx = bm_fabs(A[n * idx + m]);
+                for (int i = idx + 2; i < n; ++i) { const T val = bm_fabs(A[n * idx + i]); if (mx < val) { mx = val; m = i; } }
                 indR[idx] = m;
             }
             if (idx > 0) {
                 int m = 0;
-                double mx = fabs(A[idx]);
-                for (int i = 1; i < idx; ++i) { const double val = fabs(A[n * i + idx]); if (mx < val) { mx = val; m = i; } }
+                T mx = bm_fabs(A[idx]);
+                for (int i = 1; i < idx; ++i) { const T val = bm_fabs(A[n * i + idx]); if (mx < val) { mx = val; m = i; } }
                 indC[idx] = m;
             }
         }
@@ -187,11 +194,15 @@ ISX_HD inline void bm_jacobi3(double* A, double* V, double* W) {
         for (int i = k + 1; i < n; ++i)
             if (W[m] < W[i]) m = i;
         if (k != m) {
-            const double w = W[m]; W[m] = W[k]; W[k] = w;
-            for (int i = 0; i < n; ++i) { const double v = V[n * m + i]; V[n * m + i] = V[n * k + i]; V[n * k + i] = v; }
+            const T w = W[m]; W[m] = W[k]; W[k] = w;
+            for (int i = 0; i < n; ++i) { const T v = V[n * m + i]; V[n * m + i] = V[n * k + i]; V[n * k + i] = v; }
         }
     }
 }
+
+ISX_HD inline void bm_jacobi3(double* A, double* V, double* W) { bm_jacobi3_t<double>(A, V, W, DBL_EPSILON); }
+// cv::eigen of a CV_32F 3 x 3: the same in float32, the threshold FLT_EPSILON (waveCorrect)
+ISX_HD inline void bm_jacobi3f(float* A, float* V, float* W) { bm_jacobi3_t<float>(A, V, W, FLT_EPSILON); }
 
 // ---- svd(R); R = u * vt; if det < 0: R = -R, as the polar factor R V diag(1 / sqrt(w)) V^T of R^T R = V diag(w) V^T ------------------------
 // false where R^T R is not finite or an eigenvalue is not positive: Q is then the identity.
@@ -237,6 +248,33 @@ ISX_HD inline void bm_ray(const double* H, double x, double y, double* r) {
     const double Z = ((H[6] * x) + (H[7] * y)) + H[8];
     const double len = sqrt(((X * X) + (Y * Y)) + (Z * Z));
     r[0] = X / len; r[1] = Y / len; r[2] = Z / len;
+}
+
+// ---- BundleAdjusterReproj's calcError: p = focal, ppx, ppy, aspect, rvec[3] of a camera ------------------------------------------------------
+// H = ((K2 * R2.inv()) * R1) * K1.inv(), K = [[f, 0, ppx], [0, f * aspect, ppy], [0, 0, 1]], R = Rodrigues(rvec)
+ISX_HD inline void bm_reproj_k(const double* p, double* K) {
+    K[0] = p[0]; K[1] = 0.0; K[2] = p[1];
+    K[3] = 0.0; K[4] = p[0] * p[3]; K[5] = p[2];
+    K[6] = 0.0; K[7] = 0.0; K[8] = 1.0;
+}
+ISX_HD inline void bm_reproj_h(const double* p1, const double* p2, double* H) {
+    double K1[9], K2[9], R1[9], R2[9], K1i[9], R2i[9], A[9], B[9];
+    bm_reproj_k(p1, K1);
+    bm_reproj_k(p2, K2);
+    bm_rodrigues_mat(p1 + 4, R1);
+    bm_rodrigues_mat(p2 + 4, R2);
+    es_inv3(R2, R2i);
+    es_inv3(K1, K1i);
+    es_mul3(K2, R2i, A);
+    es_mul3(A, R1, B);
+    es_mul3(B, K1i, H);
+}
+// the two residuals of a match: p2 - H (x1, y1, 1) dehomogenised
+ISX_HD inline void bm_reproj_err(const double* H, double x1, double y1, double x2, double y2, double* e) {
+    const double X = ((H[0] * x1) + (H[1] * y1)) + H[2];
+    const double Y = ((H[3] * x1) + (H[4] * y1)) + H[5];
+    const double Z = ((H[6] * x1) + (H[7] * y1)) + H[8];
+    e[0] = x2 - (X / Z); e[1] = y2 - (Y / Z);
 }
 
 }  // namespace isxbm

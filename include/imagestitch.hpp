@@ -590,9 +590,11 @@ private:
 // factorisation with SVBkSb's truncation rule, sin / cos / acos are restated, summation orders are fixed: unpinned
 // (tests/helpers/bundle_np.py is the specification).  Returns false where estimate() would (a NaN parameter) and where the rig passes
 // through (no edge, the estimator's assert): cameras are then unchanged but for K32 / R32.
-class BundleAdjusterRay {
+// BundleAdjusterBase holds what BundleAdjusterRay and BundleAdjusterReproj share: everything but the entry point they call.
+class BundleAdjusterBase {
 public:
-    explicit BundleAdjusterRay(int device = 0, void* hip_stream = nullptr) : device_(device), stream_(hip_stream) {}
+    explicit BundleAdjusterBase(int device = 0, void* hip_stream = nullptr) : device_(device), stream_(hip_stream) {}
+    virtual ~BundleAdjusterBase() {}
     void setStream(void* hip_stream) { stream_ = hip_stream; }
     void setConfThresh(double conf_thresh) { conf_thresh_ = conf_thresh; }
     void setTermCriteria(int max_iter, double eps) { max_iter_ = max_iter; eps_ = eps; }      // TermCriteria(EPS + COUNT, 1000, DBL_EPSILON)
@@ -600,8 +602,8 @@ public:
     bool operator()(const std::vector<ImageFeatures>& features, const std::vector<MatchesInfo>& pairwise_matches, std::vector<CameraParams>& cameras) {
         static_assert(sizeof(DMatch) == 12 && sizeof(Point2f) == 8, "DMatch is a row of queryIdx, trainIdx, distance; Point2f a row of x, y");
         const int n = (int)features.size();
-        if ((int)pairwise_matches.size() != n * n) throw Exception(ISX_ERR_INVALID, "BundleAdjusterRay: pairwise_matches is not n * n");
-        if ((int)cameras.size() != n) throw Exception(ISX_ERR_INVALID, "BundleAdjusterRay: needs n cameras");
+        if ((int)pairwise_matches.size() != n * n) throw Exception(ISX_ERR_INVALID, std::string(name()) + ": pairwise_matches is not n * n");
+        if ((int)cameras.size() != n) throw Exception(ISX_ERR_INVALID, std::string(name()) + ": needs n cameras");
         std::vector<int> sizes, pij, counts, stats;
         std::vector<double> conf;
         std::vector<isx_mat> kp(n), mt, mk;
@@ -634,8 +636,7 @@ public:
         isx_mat fm = host(conf.data(), 1, np, ISX_64FC1, 8 * (size_t)(np > 0 ? np : 1)), em = host(est_, 1, 8, ISX_32SC1, 32);
         isx_mat im = host(cin.data(), n, 16, ISX_64FC1, 128), om = host(cams.data(), n, 16, ISX_64FC1, 128), km = host(kr.data(), n, 18, ISX_32FC1, 72);
         isx_mat rm = host(rig_stats_, 1, 8, ISX_32SC1, 32), re = host(rig_err_, 1, 2, ISX_64FC1, 16);
-        check(isx_bundle_adjust_ray(n, sizes.data(), kp.data(), np, pij.data(), mt.data(), mk.data(), &cm, &sm, &fm, 1, nullptr, &em, &im, conf_thresh_, max_iter_,
-                                    eps_, &om, &km, &rm, &re, info_, device_, stream_));
+        check(run(n, sizes.data(), kp.data(), np, pij.data(), mt.data(), mk.data(), &cm, &sm, &fm, &em, &im, &om, &km, &rm, &re));
         for (int i = 0; i < n; ++i) {
             CameraParams& c = cameras[i];
             const double* s = &cams[(size_t)16 * i];
@@ -649,7 +650,11 @@ public:
     const double* rigErr() const { return rig_err_; }       // the first and the last |err|
     int launches() const { return info_[1]; }               // one
     static void release() { check(isx_bundle_release()); }
-private:
+protected:
+    virtual const char* name() const = 0;
+    // the entry point on one rig of n images: isx_bundle_adjust_ray's arguments without what the members hold
+    virtual int run(int n, const int* sizes, const isx_mat* kp, int np, const int* pij, const isx_mat* mt, const isx_mat* mk, const isx_mat* counts,
+                    const isx_mat* stats, const isx_mat* conf, const isx_mat* est, const isx_mat* cin, isx_mat* cams, isx_mat* kr, isx_mat* rs, isx_mat* re) = 0;
     static isx_mat host(void* data, int rows, int cols, int type, size_t step) {
         isx_mat m; m.data = data; m.rows = rows; m.cols = cols; m.type = type; m.step = step; m.device = -1; return m;
     }
@@ -662,6 +667,69 @@ private:
     double rig_err_[2] = {0, 0};
     int info_[2] = {0, 0};
 };
+class BundleAdjusterRay : public BundleAdjusterBase {
+public:
+    explicit BundleAdjusterRay(int device = 0, void* hip_stream = nullptr) : BundleAdjusterBase(device, hip_stream) {}
+protected:
+    const char* name() const override { return "BundleAdjusterRay"; }
+    int run(int n, const int* sizes, const isx_mat* kp, int np, const int* pij, const isx_mat* mt, const isx_mat* mk, const isx_mat* counts, const isx_mat* stats,
+            const isx_mat* conf, const isx_mat* est, const isx_mat* cin, isx_mat* cams, isx_mat* kr, isx_mat* rs, isx_mat* re) override {
+        return isx_bundle_adjust_ray(n, sizes, kp, np, pij, mt, mk, counts, stats, conf, 1, nullptr, est, cin, conf_thresh_, max_iter_, eps_, cams, kr, rs, re,
+                                     info_, device_, stream_);
+    }
+};
+// detail::BundleAdjusterReproj (commented out at W:190 of the reference; cv::Stitcher's default; isx_bundle_adjust_reproj): BundleAdjusterRay's
+// call and results with focal, ppx, ppy, aspect and rotation of every camera refined over the reprojection error.  setRefinementMask takes
+// OpenCV's 3 x 3 mask row by row ((0,0) focal, (0,2) ppx, (1,1) aspect, (1,2) ppy; the other entries are not read) or the flags.  A parameter
+// that is not refined keeps its value and sets ISX_BUNDLE_DROPPED.  Unpinned: tests/helpers/bundle_reproj_np.py is the specification.
+class BundleAdjusterReproj : public BundleAdjusterBase {
+public:
+    explicit BundleAdjusterReproj(int device = 0, void* hip_stream = nullptr) : BundleAdjusterBase(device, hip_stream) {}
+    void setRefinementMask(const unsigned char mask[9]) {
+        refine_flags_ = (mask[0] ? 1 : 0) | (mask[1] ? 2 : 0) | (mask[2] ? 4 : 0) | (mask[4] ? 8 : 0) | (mask[5] ? 16 : 0);
+    }
+    void setRefinementFlags(int refine_flags) { refine_flags_ = refine_flags; }
+    int refinementFlags() const { return refine_flags_; }
+protected:
+    const char* name() const override { return "BundleAdjusterReproj"; }
+    int run(int n, const int* sizes, const isx_mat* kp, int np, const int* pij, const isx_mat* mt, const isx_mat* mk, const isx_mat* counts, const isx_mat* stats,
+            const isx_mat* conf, const isx_mat* est, const isx_mat* cin, isx_mat* cams, isx_mat* kr, isx_mat* rs, isx_mat* re) override {
+        return isx_bundle_adjust_reproj(n, sizes, kp, np, pij, mt, mk, counts, stats, conf, 1, nullptr, est, cin, conf_thresh_, max_iter_, eps_, refine_flags_,
+                                        cams, kr, rs, re, info_, device_, stream_);
+    }
+private:
+    int refine_flags_ = 31;
+};
+
+// detail::waveCorrect(rmats, kind) (commented out at W:198, C:355-361 of the reference; cv::Stitcher's default; isx_wave_correct) on the
+// cameras of one rig: R, and with it R32, of every camera replaced; focal, aspect, ppx, ppy, t and K32's values unchanged.  Returns false
+// where waveCorrect returns early (one camera, a degenerate rig): the cameras are then unchanged but for K32 / R32.
+enum WaveCorrectKind { WAVE_CORRECT_HORIZ = ISX_WAVE_CORRECT_HORIZ, WAVE_CORRECT_VERT = ISX_WAVE_CORRECT_VERT };
+inline bool waveCorrect(std::vector<CameraParams>& cameras, WaveCorrectKind kind = WAVE_CORRECT_HORIZ, int device = 0, void* hip_stream = nullptr) {
+    const int n = (int)cameras.size();
+    if (n == 0) return false;
+    std::vector<double> cin((size_t)16 * n), cams((size_t)16 * n);
+    std::vector<float> kr((size_t)18 * n);
+    int rs[2] = {0, 0};
+    for (int i = 0; i < n; ++i) {
+        const CameraParams& c = cameras[i];
+        double* s = &cin[(size_t)16 * i];
+        s[0] = c.focal; s[1] = c.aspect; s[2] = c.ppx; s[3] = c.ppy;
+        std::memcpy(s + 4, c.R, sizeof(c.R)); std::memcpy(s + 13, c.t, sizeof(c.t));
+    }
+    isx_mat im, om, km, rm;
+    im.data = cin.data(); im.rows = n; im.cols = 16; im.type = ISX_64FC1; im.step = 128; im.device = -1;
+    om = im; om.data = cams.data();
+    km.data = kr.data(); km.rows = n; km.cols = 18; km.type = ISX_32FC1; km.step = 72; km.device = -1;
+    rm.data = rs; rm.rows = 1; rm.cols = 2; rm.type = ISX_32SC1; rm.step = 8; rm.device = -1;
+    check(isx_wave_correct(n, 1, nullptr, &im, (int)kind, &om, &km, &rm, nullptr, device, hip_stream));
+    for (int i = 0; i < n; ++i) {
+        CameraParams& c = cameras[i];
+        std::memcpy(c.R, &cams[(size_t)16 * i + 4], sizeof(c.R));
+        std::memcpy(c.K32, &kr[(size_t)18 * i], sizeof(c.K32)); std::memcpy(c.R32, &kr[(size_t)18 * i + 9], sizeof(c.R32));
+    }
+    return rs[0] == 0;
+}
 
 // cv::imread(path) (W:166): the decoder follows the file's signature, as OpenCV's does - "BM" bitmaps and JFIF / Exif JPEGs;
 // cv::imwrite(path, img) for .bmp and .jpg (W:155-156,315; "pano.jpg" S:1282)

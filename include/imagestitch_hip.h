@@ -774,8 +774,8 @@ enum { ISX_ESTIMATOR_MEDIAN = 1,    /* the focal is the median of the candidates
  * range, rig_first not increasing, a misaligned mat -> ISX_ERR_INVALID; a mat of another type -> ISX_ERR_TYPE; too few rows or columns ->
  * ISX_ERR_SIZE; more than ISX_ESTIMATOR_MAX_IMAGES images in a rig -> ISX_ERR_UNSUPPORTED.  The call uploads its table (and stages host
  * mats): on a capturing stream -> ISX_ERR_STATE with nothing enqueued.  With device mats throughout nothing is read back or synchronised.
- * Host mats synchronise.  BundleAdjusterRay is isx_bundle_adjust_ray below.  Not built: BundleAdjusterReproj, waveCorrect (commented out at
- * C:355-361), leaveBiggestComponent.                                                                                                   */
+ * Host mats synchronise.  BundleAdjusterRay, BundleAdjusterReproj and waveCorrect (commented out at C:355-361) are isx_bundle_adjust_ray,
+ * isx_bundle_adjust_reproj and isx_wave_correct below.  Not built: leaveBiggestComponent.                                              */
 int isx_estimate_cameras(int num_images, const int* image_sizes_wh, int num_pairs, const int* pairs_from_to, int num_rigs, const int* rig_first,
                          const isx_mat* H, const isx_mat* stats, const isx_mat* conf, const isx_mat* focals_in, isx_mat* cameras, isx_mat* kr32,
                          isx_mat* tree, isx_mat* rig_stats, int* info, int device, void* hip_stream);
@@ -839,8 +839,8 @@ enum { ISX_BUNDLE_NAN = 1,          /* a parameter ended as NaN: estimate() retu
  * out of range, rig_first not increasing, max_iter outside [1, 1000], conf_thresh negative or not a number, eps not a number, a misaligned
  * mat -> ISX_ERR_INVALID; a mat of another type -> ISX_ERR_TYPE; too few rows or columns -> ISX_ERR_SIZE; more than ISX_BUNDLE_MAX_IMAGES
  * images in a rig -> ISX_ERR_UNSUPPORTED.  The call uploads its tables (and stages host mats): on a capturing stream -> ISX_ERR_STATE with
- * nothing enqueued.  With device mats throughout nothing is read back or synchronised.  Host mats synchronise.  Not built:
- * BundleAdjusterReproj (commented out at W:190), waveCorrect (W:198), leaveBiggestComponent.                                            */
+ * nothing enqueued.  With device mats throughout nothing is read back or synchronised.  Host mats synchronise.  BundleAdjusterReproj
+ * (commented out at W:190) and waveCorrect (W:198) follow below.  Not built: leaveBiggestComponent.                                     */
 int isx_bundle_adjust_ray(int num_images, const int* image_sizes_wh, const isx_mat* keypoints, int num_pairs, const int* pairs_from_to,
                           const isx_mat* matches, const isx_mat* inlier_masks, const isx_mat* counts, const isx_mat* stats, const isx_mat* conf,
                           int num_rigs, const int* rig_first, const isx_mat* est_rig_stats, const isx_mat* cameras_in, double conf_thresh, int max_iter,
@@ -849,6 +849,54 @@ int isx_bundle_adjust_ray(int num_images, const int* image_sizes_wh, const isx_m
 /* Returns the scratch of the calling thread (its own: isx_estimator_release does not free it).  PER THREAD and not freed at thread exit,
  * as for isx_estimator_release.                                                                                                        */
 int isx_bundle_release(void);
+
+/* ---- BundleAdjusterReproj (commented out at W:190, C:340; the default of cv::Stitcher and of stitching_detailed --ba reproj) ------------- */
+/* isx_bundle_adjust_ray with OpenCV 3.4.2's BundleAdjusterReproj restated in place of BundleAdjusterRay: 7 parameters a camera (focal, ppx,
+ * ppy, aspect and a Rodrigues vector), 2 residuals an inlier match.  The same kernel compiled a second time (512 threads a workgroup: a
+ * thread per row of the 7 n <= 448 unknowns), the same edges and inliers, CvLevMarq, lambda table, Cholesky solve with the trace rule,
+ * tiles of ISX_BUNDLE_TILE matches, status bits, validation, error codes, host-or-device mats, capture rule, ONE launch and per-thread
+ * scratch (isx_bundle_release frees it).  tests/helpers/bundle_reproj_np.py is the specification (UNPINNED, DESIGN.md §8 "Reprojection
+ * adjuster"), to which every output agrees bit for bit.  What differs:
+ *   the parameters   focal, ppx, ppy, aspect from cameras_in columns 0, 2, 3, 1; rvec as for Ray (float32 R, polar factor, Rodrigues, float32).
+ *   calcError        per edge (i, j): H = ((K_j * R_j.inv()) * R_i) * K_i.inv(), K = [[f, 0, ppx], [0, f * aspect, ppy], [0, 0, 1]]; per
+ *                    inlier match (x, y, z) = H (p_i.x, p_i.y, 1); the residuals p_j.x - x / z and p_j.y - y / z.  A z of 0 gives what
+ *                    IEEE division gives.  image_sizes_wh is checked and not read.
+ *   calcJacobian     central differences, step 1e-4.
+ *   refine_flags     OpenCV's refinement mask as bits: 1 (0,0) focal, 2 (0,1) unused, 4 (0,2) ppx, 8 (1,1) aspect, 16 (1,2) ppy; 31 in
+ *                    OpenCV; outside [0, 31] -> ISX_ERR_INVALID.  The rotation is always refined.  The Jacobian column of a parameter whose
+ *                    bit is clear stays zero: its pivot then falls under the trace rule, its step is 0 - the parameter keeps its input
+ *                    value - and ISX_BUNDLE_DROPPED is set, as for any other dropped pivot.
+ *   after the loop   focal, ppx, ppy, aspect of cameras_out and K of kr32_out are the refined parameters; R as for Ray.                  */
+int isx_bundle_adjust_reproj(int num_images, const int* image_sizes_wh, const isx_mat* keypoints, int num_pairs, const int* pairs_from_to,
+                             const isx_mat* matches, const isx_mat* inlier_masks, const isx_mat* counts, const isx_mat* stats, const isx_mat* conf,
+                             int num_rigs, const int* rig_first, const isx_mat* est_rig_stats, const isx_mat* cameras_in, double conf_thresh,
+                             int max_iter, double eps, int refine_flags, isx_mat* cameras_out, isx_mat* kr32_out,
+                             isx_mat* rig_stats_out /* CV_32SC1 rigs x 8 */, isx_mat* rig_err_out /* CV_64FC1 rigs x 2 */, int* info, int device,
+                             void* hip_stream);
+
+/* ---- waveCorrect (commented out at C:355-361, W:198; the default of cv::Stitcher and of stitching_detailed --wave_correct horiz) --------- */
+enum { ISX_WAVE_CORRECT_HORIZ = 0, ISX_WAVE_CORRECT_VERT = 1 };
+/* status bits of rig_stats_out column 0: the rig's cameras pass through */
+enum { ISX_WAVE_DEGENERATE = 1,     /* norm(rg0) <= DBL_MIN, where waveCorrect returns                                                   */
+       ISX_WAVE_SINGLE = 2          /* a rig of one image, where waveCorrect returns (rmats.size() <= 1)                                 */ };
+/* waveCorrect(rmats, kind) of OpenCV 3.4.2 restated (UNPINNED; tests/helpers/bundle_reproj_np.py wave_correct is the specification, to which
+ * every output agrees bit for bit) for every rig in ONE launch, a workgroup a rig, so that the cameras reach the warper in stream order.
+ * All arithmetic is float32 on R rounded to float32: moment = sum of col0 col0^T in image order; eigen(moment) by the restated Jacobi
+ * (eigenvalues descending, eigenvectors as rows, threshold FLT_EPSILON); rg1 = row 2 (HORIZ) or row 0 (VERT); img_k = sum of col2;
+ * rg0 = rg1 x img_k, divided by its norm; rg2 = rg0 x rg1; conf = sum of rg0 . col0 (HORIZ) or minus the sum of rg1 . col0 (VERT), and
+ * conf < 0 negates rg0 and rg1; R_i = [rg0; rg1; rg2] * R_i.
+ *   rig_first       num_rigs + 1 increasing image offsets from 0 to num_images; NULL = one rig.  A rig has at least 1 image.
+ *   cameras_in      CV_64FC1, at least num_images x 16: focal, aspect, ppx, ppy, R[9], t[3] - an adjuster's or the estimator's cameras.
+ *   kind            ISX_WAVE_CORRECT_HORIZ or ISX_WAVE_CORRECT_VERT, else ISX_ERR_INVALID.
+ *   cameras_out     CV_64FC1, at least num_images x 16: cameras_in with R replaced (float32 values); a rig that passes through is copied.
+ *                   It may be cameras_in itself.
+ *   kr32_out        CV_32FC1, at least num_images x 18: K()[9], then R[9].
+ *   rig_stats_out   CV_32SC1, at least num_rigs x 2: status bits, images.
+ *   info            NULL, or 2 ints: the rigs processed and the kernel launches of this call - ONE.
+ * Mats are host or device mats, aligned as for isx_bundle_adjust_ray; the checks (null pointers, rig_first, kind -> ISX_ERR_INVALID; type ->
+ * ISX_ERR_TYPE; rows or columns -> ISX_ERR_SIZE), the capture rule (ISX_ERR_STATE) and the scratch (isx_bundle_release) are its too.      */
+int isx_wave_correct(int num_images, int num_rigs, const int* rig_first, const isx_mat* cameras_in, int kind, isx_mat* cameras_out,
+                     isx_mat* kr32_out, isx_mat* rig_stats_out /* CV_32SC1 rigs x 2 */, int* info, int device, void* hip_stream);
 
 /* ---- on-disk format either side of the path: .bmp (W:166 imread, W:155-156,315 imwrite) ----------- */
 /* Reading: uncompressed Windows bitmaps only (the reference's inputs and committed artefacts are BMPs).
