@@ -177,6 +177,7 @@ _SIGS = {
     "isx_selftest_warp_point": [C.c_int, C.c_float, _F9, _F9, C.POINTER(C.c_float), C.c_float, C.c_float, C.POINTER(C.c_float)],
     "isx_selftest_exception_barrier": [C.c_int],
     "isx_selftest_bundle_math": [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)],
+    "isx_selftest_bundle_math_device": [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)],
     "isx_profile_enable": [C.c_int],
     "isx_profile_reset": [],
     "isx_profile_filter": [C.c_char_p],

@@ -7,7 +7,8 @@
 //                              ppy, aspect and rotation over the reprojection error - k_ba_rigs compiled a second time (ReprojTr)
 //   isx_wave_correct           detail::waveCorrect (commented out at W:198) for every rig: k_wave_rigs, float32 as OpenCV's is
 //   isx_bundle_release         returns the per-thread scratch
-//   isx_selftest_bundle_math   the host compilation of bundle_math.hpp (needs no device)
+//   isx_selftest_bundle_math   the host compilation of bundle_math.hpp (needs no device), and isx_selftest_bundle_math_device, the same items
+//                              by the device compilation: a thread each
 //
 // The specification is tests/helpers/bundle_np.py (DESIGN.md §8 "Bundle adjuster"): OpenCV 3.4.2's BundleAdjusterBase::estimate,
 // BundleAdjusterRay, CvLevMarq and cvRodrigues2 restated (unpinned), with three decisions of this project - a Cholesky solve with SVBkSb's
@@ -981,6 +982,52 @@ int wv_call(int num_images, int num_rigs, const int* rig_first, const isx_mat* c
     return ISX_OK;
 }
 
+// ---- the self-tests of bundle_math.hpp: one item of function fn, by the host's loop and by a thread of k_selftest_bundle_math --------------
+constexpr int BM_FNS = 12;
+ISX_HD inline int bm_fn_in(int fn) {                         // doubles an item reads
+    constexpr int w[BM_FNS] = {1, 1, 1, 3, 9, 9, 6, 11, 9, 9, 14, 13};
+    return w[fn];
+}
+ISX_HD inline int bm_fn_out(int fn) {                        // doubles an item writes
+    constexpr int w[BM_FNS] = {1, 1, 1, 9, 3, 10, 9, 3, 12, 12, 9, 2};
+    return w[fn];
+}
+
+ISX_HD inline void bm_selftest_item(int fn, const double* in, double* out) {
+    switch (fn) {
+    case 0: out[0] = bm_sin(in[0]); break;
+    case 1: out[0] = bm_cos(in[0]); break;
+    case 2: out[0] = bm_acos(in[0]); break;
+    case 3: bm_rodrigues_mat(in, out); break;                                        // 3 in, 9 out
+    case 4: bm_rodrigues_vec(in, out); break;                                        // 9 in, 3 out
+    case 5: out[9] = bm_polar(in, out) ? 1.0 : 0.0; break;                           // 9 in, 9 + ok out
+    case 6: bm_cam_h(in, (int)in[4], (int)in[5], out); break;                        // f, rvec, width, height in, 9 out
+    case 7: bm_ray(in, in[9], in[10], out); break;                                   // H, x, y in, 3 out
+    case 8: {                                                                        // A (float32 values) in, V and W out
+        float A[9], V[9], W[3];
+        for (int e = 0; e < 9; ++e) A[e] = (float)in[e];
+        bm_jacobi3f(A, V, W);
+        for (int e = 0; e < 9; ++e) out[e] = (double)V[e];
+        for (int e = 0; e < 3; ++e) out[9 + e] = (double)W[e];
+        break;
+    }
+    case 9: {                                                                        // A in, V and W out
+        double A[9];
+        for (int e = 0; e < 9; ++e) A[e] = in[e];
+        bm_jacobi3(A, out, out + 9);
+        break;
+    }
+    case 10: bm_reproj_h(in, in + 7, out); break;                                    // p1[7], p2[7] in, 9 out
+    default: bm_reproj_err(in, in[9], in[10], in[11], in[12], out); break;           // H, x1, y1, x2, y2 in, 2 out
+    }
+}
+
+__global__ void __launch_bounds__(256) k_selftest_bundle_math(int fn, int n, const double* __restrict__ in, double* __restrict__ out) {
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i >= n) return;
+    bm_selftest_item(fn, in + (size_t)bm_fn_in(fn) * i, out + (size_t)bm_fn_out(fn) * i);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1020,20 +1067,27 @@ int isx_wave_correct(int num_images, int num_rigs, const int* rig_first, const i
 int isx_selftest_bundle_math(int fn, int n, const double* in, double* out) ISX_ENTRY {
     clear_error();
     ISX_CHECK_ARG(n >= 0 && (n == 0 || (in && out)), ISX_ERR_INVALID, "selftest_bundle_math: n %d, or null in / out", n);
-    ISX_CHECK_ARG(fn >= 0 && fn <= 7, ISX_ERR_INVALID, "selftest_bundle_math: fn %d", fn);
-    for (int i = 0; i < n; ++i) {
-        switch (fn) {
-        case 0: out[i] = bm_sin(in[i]); break;
-        case 1: out[i] = bm_cos(in[i]); break;
-        case 2: out[i] = bm_acos(in[i]); break;
-        case 3: bm_rodrigues_mat(in + 3 * i, out + 9 * i); break;                     // 3 in, 9 out
-        case 4: bm_rodrigues_vec(in + 9 * i, out + 3 * i); break;                     // 9 in, 3 out
-        case 5: out[10 * i + 9] = bm_polar(in + 9 * i, out + 10 * i) ? 1.0 : 0.0; break;      // 9 in, 9 + ok out
-        case 6: bm_cam_h(in + 6 * i, (int)in[6 * i + 4], (int)in[6 * i + 5], out + 9 * i); break;      // f, rvec, width, height in, 9 out
-        default: bm_ray(in + 11 * i, in[11 * i + 9], in[11 * i + 10], out + 3 * i); break;             // H, x, y in, 3 out
-        }
-    }
+    ISX_CHECK_ARG(fn >= 0 && fn < BM_FNS, ISX_ERR_INVALID, "selftest_bundle_math: fn %d", fn);
+    for (int i = 0; i < n; ++i) bm_selftest_item(fn, in + (size_t)bm_fn_in(fn) * i, out + (size_t)bm_fn_out(fn) * i);
     return ISX_OK;
 } ISX_EXIT("isx_selftest_bundle_math")
+
+int isx_selftest_bundle_math_device(int fn, int n, const double* in, double* out) ISX_ENTRY {
+    clear_error();
+    ISX_CHECK_ARG(n >= 0 && (n == 0 || (in && out)), ISX_ERR_INVALID, "selftest_bundle_math_device: n %d, or null in / out", n);
+    ISX_CHECK_ARG(fn >= 0 && fn < BM_FNS, ISX_ERR_INVALID, "selftest_bundle_math_device: fn %d", fn);
+    if (n == 0) return ISX_OK;
+    hipStream_t st = nullptr;
+    const size_t in_bytes = (size_t)n * bm_fn_in(fn) * sizeof(double), out_bytes = (size_t)n * bm_fn_out(fn) * sizeof(double);
+    DevBuf din, dout;
+    ISX_TRY(din.reserve(in_bytes));
+    ISX_TRY(dout.reserve(out_bytes));
+    ISX_HIP(hipMemcpyAsync(din.p, in, in_bytes, hipMemcpyHostToDevice, st));
+    ISX_LAUNCH("selftest_bundle_math", (double)(in_bytes + out_bytes), st, k_selftest_bundle_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, fn, n,
+               (const double*)din.p, (double*)dout.p);
+    ISX_HIP(hipMemcpyAsync(out, dout.p, out_bytes, hipMemcpyDeviceToHost, st));
+    ISX_HIP(hipStreamSynchronize(st));
+    return ISX_OK;
+} ISX_EXIT("isx_selftest_bundle_math_device")
 
 }  // extern "C"

@@ -2,7 +2,8 @@
 // both take: sin, cos and acos restated in + - * / sqrt (the Levenberg-Marquardt loop of bundle.hip ends on comparisons at rounding level, so
 // a library sin that differs by an ulp between host, device and model would change its length), cvRodrigues2 in both directions, the polar
 // factor of setUpInitialCameraParams, R * K.inv() and the ray of calcError.  tests/helpers/bundle_np.py repeats every function operation for
-// operation (DESIGN.md §8 "Bundle adjuster"); isx_selftest_bundle_math runs the host compilation.  Every expression is evaluated as written,
+// operation (DESIGN.md §8 "Bundle adjuster"); isx_selftest_bundle_math runs the host compilation and isx_selftest_bundle_math_device the
+// device compilation of every function here, item by item (tests/test_gpu_bundle_math.py).  Every expression is evaluated as written,
 // left to right, no contraction (-ffp-contract=off).  Also here: the edge matrix and the two residuals of BundleAdjusterReproj's calcError
 // (tests/helpers/bundle_reproj_np.py), and the 3 x 3 Jacobi as a template, run in float32 by the wave correction.  Internal.
 #pragma once

@@ -1003,9 +1003,16 @@ int isx_selftest_roi_host(int kind, float scale, const float K[9], const float R
 int isx_selftest_warp_point(int kind, float scale, const float K[9], const float R[9], const float T[3], float x, float y, float out_uv[2]);
 /* The host compilation of csrc/bundle_math.hpp, the arithmetic isx_bundle_adjust_ray runs per camera on the device, for n items: fn 0 sin,
  * 1 cos, 2 acos (1 double in, 1 out); 3 Rodrigues vector -> matrix (3 in, 9 out); 4 matrix -> vector (9 in, 3 out); 5 the polar factor (9 in,
- * 9 and a 1.0 / 0.0 "ok" out); 6 R K^-1 (f, rvec[3], width, height in, 9 out); 7 the ray (H[9], x, y in, 3 out).  Needs no device: the CPU
- * test-suite compares it with tests/helpers/bundle_np.py bit for bit.                                                                  */
+ * 9 and a 1.0 / 0.0 "ok" out); 6 R K^-1 (f, rvec[3], width, height in, 9 out); 7 the ray (H[9], x, y in, 3 out); 8 the float32 Jacobi of the
+ * wave correction (A[9] as doubles that hold float32 values in; V[9], the eigenvectors as rows, then W[3] descending out); 9 the float64
+ * Jacobi (the same); 10 BundleAdjusterReproj's edge matrix (the seven parameters of camera 1, then of camera 2 in, 9 out); 11 its two
+ * residuals (H[9], x1, y1, x2, y2 in, 2 out).  Needs no device: the CPU test-suite compares it with tests/helpers/bundle_np.py and
+ * bundle_reproj_np.py bit for bit.  Its device twin is isx_selftest_bundle_math_device.                                               */
 int isx_selftest_bundle_math(int fn, int n, const double* in, double* out);
+/* The device compilation of the same header on the same items: `in` (host memory) is copied to the current device, one kernel runs a
+ * thread per item that calls the same function, `out` (host memory) is copied back.  Uses the null stream and synchronises it.
+ * tests/test_gpu_bundle_math.py holds the two entries and the model to the same bits.                                                 */
+int isx_selftest_bundle_math_device(int fn, int n, const double* in, double* out);
 /* Every entry of this header is a function-try-block: a C++ exception raised underneath it (std::bad_alloc of a host container, a
  * std::length_error, anything a future change throws) is stopped there and comes back as a status - ISX_ERR_NOMEM for the two allocation
  * failures, ISX_ERR_INTERNAL otherwise, the text in isx_last_error() - never as an exception in the caller's frames (the

@@ -23,11 +23,49 @@ def _axis_turn(rng, deg):
     return np.eye(3) + np.sin(t) * K + (1 - np.cos(t)) * K @ K
 
 
+MAX_AXES_DEG = 80.0                            # a pair further apart shares too little view: the inlier loop of make would not end
+
+
+def ring(n, step_deg, jitter=0.03, seed=0):
+    """Planted rotations of a panorama that goes round: camera i has yaw i * step_deg, and all three angles move by up to `jitter` rad
+    (seeded).  jitter = 0: the exact yaws, camera 0 the identity."""
+    rng = np.random.default_rng([seed, n])
+    out = []
+    for i in range(n):
+        j = rng.uniform(-jitter, jitter, 3) if jitter else np.zeros(3)
+        out.append(rotation(np.deg2rad(i * step_deg) + j[0], j[1], j[2]))
+    return out
+
+
+def axes_apart_deg(Ri, Rj):
+    """The angle between the optical axes R (0, 0, 1) of two planted cameras."""
+    return float(np.rad2deg(np.arccos(np.clip(Ri[:, 2] @ Rj[:, 2], -1.0, 1.0))))
+
+
+def ring_pairs(rotations, steps=(1,)):
+    """The pairs (i, j), i < j, that lie `steps` cameras apart round the ring (the closing pairs included where the ring closes: where their
+    axes are less than MAX_AXES_DEG apart), in index order."""
+    n = len(rotations)
+    out = set()
+    for i in range(n):
+        for s in steps:
+            a, b = sorted((i, (i + s) % n))
+            if a != b and axes_apart_deg(rotations[a], rotations[b]) < MAX_AXES_DEG:
+                out.add((a, b))
+    return sorted(out)
+
+
 def make(n, pairs, seed, inliers=40, outliers=0.25, focal=900.0, off_deg=1.0, off_focal=0.05, conf=None, center=0, r_scale=1.02, max_iter=30,
-         conf_thresh=1.0, size=(1280, 960)):
-    """One rig.  inliers: an int or one per pair; outliers: the share of mask-0 matches interleaved; conf: per pair (default 2.0)."""
+         conf_thresh=1.0, size=(1280, 960), rotations=None):
+    """One rig.  inliers: an int or one per pair; outliers: the share of mask-0 matches interleaved; conf: per pair (default 2.0); rotations:
+    the planted rotations (default: planted_rotations, yaw, pitch and roll of 0.1 to 0.3 rad) - every pair's axes less than MAX_AXES_DEG
+    apart."""
     rng = np.random.default_rng(seed)
-    Rs = planted_rotations(n, rng)
+    if rotations is None:
+        Rs = planted_rotations(n, rng)
+    else:
+        Rs = [np.array(R, np.float64) for R in rotations]
+        assert len(Rs) == n and all(axes_apart_deg(Rs[i], Rs[j]) < MAX_AXES_DEG for i, j in pairs), "a pair that shares no view"
     Rs = [Rs[center].T @ R for R in Rs]                       # the centre's R is the identity, as the adjuster leaves it
     sizes = [size] * n
     w, h = size
@@ -123,4 +161,31 @@ def named():
     out["tiles_past_a_block"] = make(24, all_pairs(24), 16, inliers=1, outliers=0.0, max_iter=2)      # 276 tiles: the norm's second chunk of 256
     out["natural_end_2"] = make(2, [(0, 1)], 13, inliers=10, max_iter=1000)
     out["natural_end_3"] = make(3, all_pairs(3), 14, inliers=8, max_iter=1000)
+    out.update(wide(make))
+    return out
+
+
+WIDE = ("ring_8x45_center_0", "ring_8x45_center_4", "ring_8x45_exact_half_turn", "ring_6x60_center_0", "arc_5x50_natural_end", "reflection_R_in",
+        "ring_16x22p5_two_steps")
+
+
+def wide(make):
+    """The rigs that go round (tests/test_bundle_model.py counts the branches of bundle_math.hpp that these take and no narrow rig does):
+    rotation vectors up to half a turn, so every branch of acos, quadrants 1 and 2 of sin / cos, the half turn of cvRodrigues2 and the
+    det < 0 of the polar factor.  make: this module's, or bundle_reproj_cases'.  12 inliers an edge."""
+    out = {}
+    r8 = ring(8, 45.0, seed=21)
+    out["ring_8x45_center_0"] = make(8, ring_pairs(r8), 31, inliers=12, max_iter=4, rotations=r8)       # the chain and the closing pair (0, 7)
+    out["ring_8x45_center_4"] = make(8, ring_pairs(r8), 32, inliers=12, max_iter=3, center=4, rotations=r8)      # camera 0: half a turn from the centre
+    e8 = ring(8, 45.0, jitter=0.0)
+    out["ring_8x45_exact_half_turn"] = make(8, ring_pairs(e8), 33, inliers=12, max_iter=3, off_deg=0.0, r_scale=1.0, rotations=e8)      # camera 4: rotation(pi, 0, 0)
+    r6 = ring(6, 60.0, seed=22)
+    out["ring_6x60_center_0"] = make(6, ring_pairs(r6), 34, inliers=12, max_iter=4, rotations=r6)
+    a5 = ring(5, 50.0, seed=23)
+    out["arc_5x50_natural_end"] = make(5, ring_pairs(a5), 35, inliers=12, max_iter=1000, rotations=a5)   # 200 degrees: the ring does not close
+    c = make(3, all_pairs(3), 36, inliers=12, max_iter=3)
+    c["cameras_in"][1, 4:13] = (c["cameras_in"][1, 4:13].reshape(3, 3) @ np.diag([1.0, 1.0, -1.0])).ravel()      # det < 0: the polar factor is negated
+    out["reflection_R_in"] = c
+    r16 = ring(16, 22.5, seed=24)
+    out["ring_16x22p5_two_steps"] = make(16, ring_pairs(r16, (1, 2)), 37, inliers=12, max_iter=2, rotations=r16)      # Ray: 64 unknowns, one wave of rows
     return out

@@ -6,7 +6,7 @@ is bundle_cases' dict with refine_flags added; planted: (focal, rotations, ppx, 
 import numpy as np
 
 import bundle_cases as bc
-from bundle_cases import EST_ASSERT, TILE, all_pairs, join  # noqa: F401
+from bundle_cases import EST_ASSERT, TILE, WIDE, all_pairs, join, ring, ring_pairs  # noqa: F401
 
 REFINE_ALL = 31
 
@@ -79,6 +79,7 @@ def named():
     c = make(3, all_pairs(3), 19, inliers=6, max_iter=3)
     c["cameras_in"][0, 0] = 0.0
     out["z_zero"] = c
+    out.update(bc.wide(make))                                                                       # the rigs that go round (Reproj: 112 unknowns for 16 cameras)
     return out
 
 

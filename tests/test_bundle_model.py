@@ -16,6 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import bundle_cases as cases  # noqa: E402
+import bundle_math_cases as mc  # noqa: E402
 import fuzz_bundle as fz  # noqa: E402
 from helpers import bundle_np as bm  # noqa: E402
 from imagestitch_amd import _lib  # noqa: E402
@@ -54,6 +55,88 @@ def test_sin_cos_acos_are_within_1e_12_of_math():
     assert max(abs(bm.cos(float(x)) - math.cos(x)) for x in ANGLES) <= 1e-12
     assert max(abs(bm.acos(float(x)) - math.acos(x)) for x in COSINES) <= 1e-12
     assert bm.acos(1.0) == 0.0 and bm.sin(0.0) == 0.0 and bm.cos(0.0) == 1.0
+
+
+def test_sin_cos_acos_are_within_1e_12_of_mpmath_over_the_device_sweeps():
+    """The header's stated bound, absolute error below 1e-12 on |x| <= 4 pi (acos: [-1, 1]), against mpmath at 50 digits over the finite
+    arguments of the sweeps that tests/test_gpu_bundle_math.py runs on the device: 20 001 points and both neighbours of every quadrant
+    switch.  Measured here: sin 1.47e-16, cos 1.51e-16, acos 3.85e-16."""
+    import mpmath as mp
+    with mp.workdps(50):
+        ang = [float(x) for x in mc.angles() if math.isfinite(x) and abs(x) <= 4 * PI]
+        cs = [float(x) for x in mc.cosines() if abs(x) <= 1.0]
+        assert len(ang) >= 20001 + 3 * 33 and len(cs) >= 20001 + 8
+        worst = (max(abs(mp.mpf(bm.sin(x)) - mp.sin(mp.mpf(x))) for x in ang), max(abs(mp.mpf(bm.cos(x)) - mp.cos(mp.mpf(x))) for x in ang),
+                 max(abs(mp.mpf(bm.acos(x)) - mp.acos(mp.mpf(x))) for x in cs))
+        print("sin, cos, acos against mpmath:", [float(w) for w in worst])
+        assert all(w <= mp.mpf("1e-12") for w in worst), [float(w) for w in worst]
+
+
+def _mp_rodrigues(mp, rv):
+    x, y, z = (mp.mpf(v) for v in rv)
+    th = mp.sqrt(x * x + y * y + z * z)
+    if th == 0:
+        return [mp.mpf(v) for v in (1, 0, 0, 0, 1, 0, 0, 0, 1)]
+    c, s = mp.cos(th), mp.sin(th)
+    c1, x, y, z = 1 - c, x / th, y / th, z / th
+    return [c + c1 * x * x, c1 * x * y - s * z, c1 * x * z + s * y, c1 * x * y + s * z, c + c1 * y * y, c1 * y * z - s * x, c1 * x * z - s * y,
+            c1 * y * z + s * x, c + c1 * z * z]
+
+
+def test_the_rodrigues_round_trip_against_mpmath():
+    """rodrigues_mat(rodrigues_vec(rodrigues_mat(v))) against Rodrigues' formula of v in mpmath at 50 digits, over the vectors of the device
+    sweep (lengths 0, either side of DBL_EPSILON, pi / 4, pi / 2, pi, 3 pi / 2 with their neighbours, 2 pi; random and coordinate axes).  No
+    bound is stated for the pair, so the bounds are four times what the model measured here, as room for another platform's sqrt-free
+    rounding to differ: the worst entry error is 1.786e-08, at the neighbours of a half turn, where cvRodrigues2 takes the axis from
+    sqrt((R_kk + 1) / 2) of a sum that cancelled to 1e-16; away from the s < 1e-5 branch (whose c > 0 half snaps to the identity: 1e-09 for
+    a vector of that length) it is 1.352e-15; rodrigues_mat alone is within 5.70e-16."""
+    import mpmath as mp
+    with mp.workdps(50):
+        alone = branch = elsewhere = mp.mpf(0)
+        for rv in mc.rotation_vectors():
+            rv = [float(v) for v in rv]
+            want = _mp_rodrigues(mp, rv)
+            R = bm.rodrigues_mat(rv)
+            back = bm.rodrigues_mat(bm.rodrigues_vec(R))
+            alone = max(alone, max(abs(mp.mpf(a) - b) for a, b in zip(R, want)))
+            err = max(abs(mp.mpf(a) - b) for a, b in zip(back, want))
+            if mc._small_s_of(R) < 1e-5:
+                branch = max(branch, err)
+            else:
+                elsewhere = max(elsewhere, err)
+        print("rodrigues against mpmath: alone %.3e, round trip %.3e in the s < 1e-5 branch, %.3e elsewhere" % (alone, branch, elsewhere))
+        assert alone <= 4 * 5.70e-16 and branch <= 4 * 1.786e-08 and elsewhere <= 4 * 1.352e-15
+
+
+def test_the_device_sweeps_reach_what_they_are_there_for():
+    """Every branch and threshold that tests/bundle_math_cases.py aims a sweep at is taken (counted on the model's arithmetic), and the host
+    compilation gives the model's bits on all twelve functions over them - the three Reproj and Jacobi functions included."""
+    taken = mc.branches()
+    assert all(n >= 1 for n in taken.values()), taken
+    assert taken["half turn, rz negated"] >= 3 and taken["quadrant -1"] >= 100 and taken["polar det < 0"] >= 20
+    for name, rows in mc.sweeps().items():
+        got, want = _host(mc.FN[name], rows, rows.shape[1], mc.N_OUT[name]), mc.model(name)
+        same = (_bits(got) == _bits(want)) | (np.isnan(got) & np.isnan(want))
+        assert same.all(), (name, rows[np.flatnonzero(~same.all(axis=1))[:3]].tolist())
+
+
+def test_which_branches_the_named_cases_take():
+    """A condition, not a measurement: each rig that goes round (bundle_cases.WIDE) takes, in the model, the branches of bundle_math.hpp it
+    was written for - so that tests/test_gpu_bundle.py, which compares the device with this model on the same case, runs them on the
+    device; a wide case that stops reaching its branch fails here.  And why they exist: no narrow named case takes |x| < 0.5 or x <= -0.5 of
+    acos, the half turn of cvRodrigues2 or det < 0 of the polar factor; under this adjuster none at all takes quadrant -1 (the Rodrigues
+    vector of a rotation matrix is no longer than pi, and no step here overshoots it), which the device sweep reaches on purpose."""
+    named = cases.named()
+    assert set(cases.WIDE) == set(mc.WIDE_TAKES) <= set(named)
+    for name, c in named.items():
+        with mc.BranchCounter() as b:
+            fz.run_model(c)
+        if name in mc.WIDE_TAKES:
+            assert all(b.taken[k] >= 1 for k in mc.WIDE_TAKES[name]), (name, b.taken)
+        else:
+            assert all(b.taken[k] == 0 for k in mc.NARROW_NEVER), (name, b.taken)
+        assert b.taken["quadrant -1"] == 0, (name, b.taken)
+    assert bm._reduce.__module__ == bm.__name__ and bm.polar.__module__ == bm.__name__      # the counters are gone
 
 
 def test_a_nan_or_an_infinity_gives_a_nan_and_never_raises():

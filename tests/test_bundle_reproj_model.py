@@ -14,6 +14,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+import bundle_math_cases as mc  # noqa: E402
 import bundle_reproj_cases as cases  # noqa: E402
 import fuzz_bundle_reproj as fz  # noqa: E402
 from helpers import bundle_reproj_np as rp  # noqa: E402
@@ -253,6 +254,22 @@ def test_the_float32_jacobi_gives_eigenpairs():
         assert np.abs(V @ A.astype(np.float64) - W[:, None] * V).max() <= 2e-5 * max(1.0, W[0])
 
 
+# ---- the rigs that go round ---------------------------------------------------------------------------------------------------------------------
+def test_which_branches_the_named_cases_take():
+    """tests/test_bundle_model.py's condition under this adjuster: every rig of bundle_cases.WIDE takes, in the model, the branches of
+    bundle_math.hpp it was written for (so tests/test_gpu_bundle_reproj.py runs them on the device), and no narrow named case takes
+    |x| < 0.5 or x <= -0.5 of acos, the half turn of cvRodrigues2 or det < 0 of the polar factor."""
+    assert set(cases.WIDE) == set(mc.WIDE_TAKES) <= set(NAMED)
+    for name, c in NAMED.items():
+        with mc.BranchCounter() as b:
+            fz.run_model(c)
+        if name in mc.WIDE_TAKES:
+            assert all(b.taken[k] >= 1 for k in mc.WIDE_TAKES[name]), (name, b.taken)
+        else:
+            assert all(b.taken[k] == 0 for k in mc.NARROW_NEVER), (name, b.taken)
+    assert rp.polar is rp.bm.polar and rp.rodrigues_vec is rp.bm.rodrigues_vec and rp.polar.__module__ == rp.bm.__name__      # the counters are gone
+
+
 # ---- the entries ----------------------------------------------------------------------------------------------------------------------------
 def _declared(name):
     text = open(os.path.join(ROOT, "include", "imagestitch_hip.h")).read()
@@ -270,6 +287,10 @@ def test_both_entries_are_declared_and_in_sigs_with_matching_arity():
     assert _lib._SIGS["isx_bundle_adjust_reproj"][at] is _lib.C.c_int
     assert len(wave) == len(_lib._SIGS["isx_wave_correct"]) == 11
     assert {"isx_bundle_adjust_reproj", "isx_wave_correct"} <= set(_lib.declared_symbols())
+    host, dev = _declared("isx_selftest_bundle_math"), _declared("isx_selftest_bundle_math_device")      # the self-test and its device twin
+    assert host == dev and len(dev) == len(_lib._SIGS["isx_selftest_bundle_math_device"]) == 4
+    assert _lib._SIGS["isx_selftest_bundle_math_device"] == _lib._SIGS["isx_selftest_bundle_math"]
+    assert "isx_selftest_bundle_math_device" in _lib.declared_symbols()
     import imagestitch_amd as I
     for name in ("BundleAdjusterReproj", "bundle_adjust_reproj", "wave_correct", "waveCorrect", "WAVE_CORRECT_HORIZ", "WAVE_CORRECT_VERT"):
         assert hasattr(I, name) and name in I.__all__, name

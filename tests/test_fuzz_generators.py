@@ -1,6 +1,6 @@
 """The generator and model halves of the fuzz families tools/fuzz_parity.py has for the entry points merged after round 6 (the plane
 projector, GainCompensator::feed, the Voronoi and graph-cut seam finders, COLOR_GRAD and seam_gradients, BlocksGainCompensator, cv::resize with
-the scaled mask stage), without a GPU: every shape
+the scaled mask stage) and of the rigs that go round of tools/fuzz_bundle.py and tools/fuzz_bundle_reproj.py, without a GPU: every shape
 class of a family is drawn, every drawn case has the shape its class names - recomputed from the case itself, against the tiling
 constants read from the kernels' sources -, and the models stay busy on them: few skips, seams that cut, overlaps that count."""
 import os
@@ -11,12 +11,14 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+import fuzz_bundle as FB  # noqa: E402
+import fuzz_bundle_reproj as FBR  # noqa: E402
 import fuzz_parity as F  # noqa: E402
 from helpers import voronoi_np as V  # noqa: E402
 
 FAMILIES = {"plane_warp": F.PLANE_CLASSES, "gain_feed": F.GAIN_CLASSES, "voronoi": F.VORONOI_CLASSES, "graphcut": F.GRAPHCUT_CLASSES,
             "seam_grad": F.SEAM_GRAD_CLASSES, "blocks_gain": F.BLOCKS_GAIN_CLASSES, "resize": F.RESIZE_CLASSES,
-            "graphcut_grad": F.GRAPHCUT_GRAD_CLASSES}
+            "graphcut_grad": F.GRAPHCUT_GRAD_CLASSES, "bundle_wide": FB.WIDE_CLASSES, "bundle_reproj_wide": FB.WIDE_CLASSES}
 GEN_SEEDS, MODEL_SEEDS = range(200), range(5000, 5030)
 GCG_MODEL_SEEDS = range(5000, 5010)                                     # graphcut_grad's model is a max-flow on Python ints: a third of the seeds
 
@@ -229,9 +231,61 @@ def check_resize(c):
                 assert (((bits & 0x7f800000) == 0) & ((bits & 0x007fffff) != 0)).any() and (bits == 0x80000000).any() and (src == np.float32(3.4028235e38)).any()
 
 
+# ---- the rigs that go round of tools/fuzz_bundle.py and tools/fuzz_bundle_reproj.py: generators keyed by a seed, models that never skip -------
+def _gen_wide(tool):
+    def gen(rng):
+        c = tool.make_wide_case(int(rng.integers(1 << 30)))
+        c["where"] = "host" if c["layout"] == "host" else "device"      # strided mats are device mats
+        return c
+    return gen
+
+
+def _model_wide(tool):
+    """The model's outputs with the branches of bundle_math.hpp it took on the way (tests/bundle_math_cases.BranchCounter)."""
+    def model(c):
+        import bundle_math_cases as mc
+        with mc.BranchCounter() as b:
+            outs = tool.run_model(c)
+        return dict(outs=outs, taken=b.taken)
+    return model
+
+
+EXTRA = {"bundle_wide": (_gen_wide(FB), _model_wide(FB)), "bundle_reproj_wide": (_gen_wide(FBR), _model_wide(FBR))}
+
+
+def _family(family):
+    """(gen(rng), model(case)) of a family: tools/fuzz_parity.py's, or EXTRA's"""
+    return EXTRA[family] if family in EXTRA else (getattr(F, "gen_" + family), getattr(F, "model_" + family))
+
+
+def check_bundle_wide(c):
+    import bundle_cases as bc
+    n0 = c["rig_first"][1] if c["rig_first"] is not None else len(c["sizes"])
+    Rs, step = c["rotations"], c["step_deg"]
+    assert c["wide"] and c["fault"] == 0 and c["layout"] in FB.LAYOUTS and len(Rs) == n0 and 3 <= n0 <= 9 and 20.0 <= step <= 60.0
+    assert 1 <= c["max_iter"] <= 6 or (c["max_iter"] in (40, 1000) and n0 <= 3)
+    first = [(i, j) for i, j in c["pairs"] if j < n0]
+    assert first == sorted(first) and all(i < j for i, j in first) and len(first) >= n0 - 1
+    assert all(min(j - i, n0 - (j - i)) in c["steps"] and bc.axes_apart_deg(Rs[i], Rs[j]) < bc.MAX_AXES_DEG for i, j in first)
+    assert all((i, i + 1) in first for i in range(n0 - 1))                                   # the chain is always there
+    span = (n0 - 1) * step
+    if c["cls"] == "ring":
+        assert n0 >= 6 and abs(n0 * step - 360.0) < 1e-9 and (0, n0 - 1) in first            # it closes
+    if c["cls"] == "arc":
+        assert span <= 300.0
+    assert span >= 40.0                                                                      # past what planted_rotations ever draws between two cameras
+    rest = len(c["sizes"]) - n0
+    assert rest in (0, 2, 3, 4) and c["cameras_in"].shape == (n0 + rest, 16) and c["counts"].shape == (1, len(c["pairs"]))
+
+
+def check_bundle_reproj_wide(c):
+    check_bundle_wide(c)
+    assert 0 <= c["refine_flags"] <= 31 and c["max_iter"] != 1000
+
+
 @pytest.mark.parametrize("family", sorted(FAMILIES))
 def test_every_class_is_drawn_and_has_its_shape(family):
-    gen, check = getattr(F, "gen_" + family), globals()["check_" + family]
+    gen, check = _family(family)[0], globals()["check_" + family]
     seen = set()
     for seed in GEN_SEEDS:
         c = gen(np.random.default_rng(seed))
@@ -248,11 +302,12 @@ def test_every_class_is_drawn_and_has_its_shape(family):
 def test_the_models_stay_busy(family):
     """30 cases through gen + model: at most 10 % skips; the seam finders' models change a mask in at least half of the cases that have
     masks (all of them, but for seam_grad's gradient half); at least half of the gain cases count an overlap (an off-diagonal N above 1,
-    the value an empty intersection gets), and at least half of the blocks-gain cases have an off-diagonal record with N above 1; the resize
+    the value an empty intersection gets), and at least half of the blocks-gain cases have an off-diagonal record with N above 1; at least
+    half of the rigs that go round are adjusted (an iteration or more) through a branch of bundle_math.hpp that no narrow rig takes; the resize
     family never skips, and at least half of its up-scaled byte cases (larger in both directions) come out with more than 2 distinct values."""
     if family == "graphcut":
         pytest.importorskip("scipy")
-    gen, model = getattr(F, "gen_" + family), getattr(F, "model_" + family)
+    gen, model = _family(family)
     skips = busy = with_masks = upscaled = 0
     seeds = GCG_MODEL_SEEDS if family == "graphcut_grad" else MODEL_SEEDS
     for seed in seeds:
@@ -273,6 +328,9 @@ def test_the_models_stay_busy(family):
             busy += any(p[2] > 1 for p in want["pairs"])
             if c["cls"] == "no_pairs":                                   # diag and b are the same sums: the quotient is exact
                 assert want["pairs"] == [] and np.all(want["gains"] == 1.0)
+        elif family in EXTRA:                                            # busy: a branch that no narrow rig takes was taken, and the rig was adjusted
+            import bundle_math_cases as mc
+            busy += any(want["taken"][k] for k in mc.NARROW_NEVER) and int(want["outs"][2][0, 1]) >= 1
         elif "masks" in c:
             with_masks += 1
             masks = want[0] if family in ("graphcut", "graphcut_grad") else want
@@ -283,7 +341,7 @@ def test_the_models_stay_busy(family):
     if family == "resize":
         assert skips == 0 and upscaled >= 3 and busy * 2 >= upscaled, (skips, busy, upscaled)
         return
-    if family in ("gain_feed", "blocks_gain"):
+    if family in ("gain_feed", "blocks_gain") or family in EXTRA:
         assert busy * 2 >= n, (busy, n)
     elif family != "plane_warp":
         assert with_masks >= (n // 3 if family == "seam_grad" else n - skips) and busy * 2 >= with_masks, (busy, with_masks, n)

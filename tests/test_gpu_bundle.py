@@ -3,7 +3,8 @@ through their uint64 views, kr32 through uint32, rig_stats with np.array_equal. 
 inliers; max_iter 1, 2, 3; a pair at conf == conf_thresh; edges one fewer, exactly and one more inlier than the tile of the accumulation with
 zeros interleaved in the masks; a camera and a rig without an edge; the estimator's assert bit; a NaN focal; a count above its mat's rows;
 indices outside the keypoints; a singular R; pairs in another order; a chain of 64 images - 256 parameters, the block's size; 276 edges - more tiles than the block has threads; two runs to
-their natural end), three rigs in one launch, host / device / strided mats, and the chain matcher -> homography -> estimator -> adjuster on CUDA
+their natural end; the rigs that go round of bundle_cases.WIDE - rings of 8, 6 and 16 cameras, an arc, an exact half turn, a mirrored R - which
+take the branches of csrc/bundle_math.hpp that no narrow rig does), three rigs in one launch - narrow ones, and a ring, a narrow rig and the half turn -, host / device / strided mats, and the chain matcher -> homography -> estimator -> adjuster on CUDA
 tensors."""
 import functools
 import os
@@ -36,6 +37,30 @@ def check(got, want, what):
         assert fz.same(g, w), (what, name, np.argwhere(g != w)[:5].tolist(), g, w)
 
 
+def check_wide(name, c, got):
+    """What a rig that goes round shows beyond its bits: it does not pass through, every edge has its 12 inliers, the focals moved."""
+    st, centre = int(got[2][0, bm.RIG_STATUS]), int(c["est_rig_stats"][0, 2])
+    assert st & (bm.ST_NAN | bm.ST_NO_EDGES | bm.ST_EST_ASSERT | bm.ST_SINGULAR_R) == 0
+    assert got[2][0, bm.RIG_EDGES] == len(c["pairs"]) and got[2][0, bm.RIG_MATCHES] == 12 * len(c["pairs"])
+    assert not (got[0][:, 0] == c["cameras_in"][:, 0]).any()
+    if name.startswith("ring_8x45"):
+        assert (0, 7) in c["pairs"] and len(c["pairs"]) == 8 and got[2][0, bm.RIG_ITERS] == c["max_iter"] and got[3][0, 1] < got[3][0, 0] / 1000.0
+        far = got[0][(centre + 4) % 8, 4:13].reshape(3, 3)     # half a turn from the centre: 1 + 2 cos(theta) is near -1
+        assert np.trace(far) < -0.9 and np.abs(got[0][centre, 4:13] - np.eye(3).ravel()).max() <= 1e-6
+    if name == "ring_8x45_center_4":
+        assert centre == 4
+    if name == "ring_8x45_exact_half_turn":
+        assert np.array_equal(np.diag(c["cameras_in"][4, 4:13].reshape(3, 3)), [-1.0, 1.0, -1.0]) and np.array_equal(c["cameras_in"][0, 4:13], np.eye(3).ravel())
+    if name == "ring_6x60_center_0":
+        assert (0, 5) in c["pairs"] and got[2][0, bm.RIG_ITERS] == 4 and got[3][0, 1] < got[3][0, 0] / 1000.0
+    if name == "arc_5x50_natural_end":
+        assert (0, 4) not in c["pairs"] and 1 < got[2][0, bm.RIG_ITERS] < 1000 and got[3][0, 1] < got[3][0, 0] / 100.0
+    if name == "reflection_R_in":
+        assert np.linalg.det(c["cameras_in"][1, 4:13].reshape(3, 3)) < -0.9
+    if name == "ring_16x22p5_two_steps":
+        assert 4 * len(c["sizes"]) == 64 and len(c["pairs"]) == 32 and got[2][0, bm.RIG_ITERS] == 2
+
+
 @pytest.mark.parametrize("name", sorted(NAMED))
 def test_named_cases(gpu, name):
     """Every named case on device mats, by bits (NaNs, which only the NaN focal carries, by position)."""
@@ -61,6 +86,27 @@ def test_named_cases(gpu, name):
         assert got[2][0, bm.RIG_STATUS] == bm.ST_DROPPED and got[0][3, 0] == c["cameras_in"][3, 0]
     if name == "count_above_rows":
         assert got[2][0, bm.RIG_EDGES] == 3 and got[2][0, bm.RIG_MATCHES] == int(c["masks"][0].sum() + c["masks"][1].sum())
+    if name in cases.WIDE:
+        check_wide(name, c, got)
+
+
+def test_a_ring_a_narrow_rig_and_the_exact_half_turn_in_one_launch(gpu):
+    """Three blocks of one launch, of which two take branches of bundle_math.hpp that the narrow one between them never does: each rig
+    equals its run alone and the model."""
+    rigs = [NAMED["ring_8x45_center_4"], NAMED["max_iter_3"], NAMED["ring_8x45_exact_half_turn"]]
+    assert all(r["max_iter"] == 3 and r["conf_thresh"] == 1.0 for r in rigs)
+    joined = cases.join(rigs)
+    got, info = fz.run_library(joined, "device")
+    assert info == (3, 1)
+    at = 0
+    for k, r in enumerate(rigs):
+        alone, info1 = fz.run_library(r, "device")
+        assert info1 == (1, 1)
+        m = len(r["sizes"])
+        assert fz.same(got[0][at:at + m], alone[0]) and fz.same(got[1][at:at + m], alone[1]), k
+        assert np.array_equal(got[2][k:k + 1], alone[2]) and fz.same(got[3][k:k + 1], alone[3]), k
+        at += m
+    check(got, fz.run_model(joined), "ring, narrow, half turn")
 
 
 def test_three_rigs_in_one_launch_equal_the_three_alone(gpu):

@@ -1,6 +1,6 @@
 """A 5-second slice of tools/fuzz_bundle.py: isx_bundle_adjust_ray against tests/helpers/bundle_np.py over the seeded classes (2, 3, 5 and
 9 images in the first rig; one to three rigs; chains to complete graphs; inliers around the tile of the accumulation; confidences either side
-of the threshold; host, device and strided mats; planted faults).  Every case is compared, none skipped; 0 mismatches."""
+of the threshold; host, device and strided mats; planted faults), every fourth case a rig that goes round (make_wide_case).  Every case is compared, none skipped; 0 mismatches."""
 import os
 import sys
 
@@ -17,4 +17,5 @@ def test_fuzz_slice(gpu):
     out = fz.run(5.0, 20261020)
     print(out)
     assert out["mismatches"] == 0, out["failing_seeds"]
-    assert out["cases"] >= len(fz.CLASSES) and min(out["per_class"].values()) >= 1 and sum(out["per_class"].values()) == out["cases"]
+    assert out["cases"] >= len(fz.CLASSES) and min(out["per_class"].values()) >= 1 and sum(out["per_class"].values()) + out["wide"] == out["cases"]
+    assert out["wide"] >= 1 and out["wide"] == sum(out["per_wide_class"].values())          # every fourth case is a rig that goes round

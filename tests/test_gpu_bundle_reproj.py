@@ -5,8 +5,9 @@ an edge; the estimator's assert bit; a NaN focal; a count above its mat's rows; 
 order; two runs to their natural end) and the shapes where the new constants can go wrong: 2 images with 8 inliers (14 unknowns, 16 rows),
 edges around the tile of the accumulation, a chain of 37 images (259 unknowns: past 256 rows and four waves), 528 tiles (more than the block
 has threads), a chain of 64 images (448 unknowns, against outputs of the model recorded in tests/golden), refine_flags 0, 1 and 31, a z of
-0 - then three rigs in one launch, host / device / strided mats, and the chain matcher -> homography -> estimator -> BundleAdjusterReproj ->
-waveCorrect on CUDA tensors."""
+0, the rigs that go round of bundle_cases.WIDE (112 unknowns for 16 cameras) - then three rigs in one launch (narrow ones; a ring, a narrow
+rig and an exact half turn), host / device / strided mats, the chain matcher -> homography -> estimator -> BundleAdjusterReproj ->
+waveCorrect on CUDA tensors, and the ring of 8 from the estimator through the adjuster to both kinds of wave correction."""
 import functools
 import os
 import sys
@@ -78,6 +79,51 @@ def test_named_cases(gpu, name):
         assert not (got[0][:, 0:4] == c["cameras_in"][:, 0:4]).any()
     if name == "z_zero":                                       # NaN residuals: every pivot drops, the step is 0, the error norms are NaN
         assert np.isnan(got[3]).all() and st & rp.ST_DROPPED and got[0][0, 0] == 0.0
+    if name in cases.WIDE:
+        check_wide(name, c, got)
+
+
+def check_wide(name, c, got):
+    """What a rig that goes round shows beyond its bits: it does not pass through, every edge has its 12 inliers, all four intrinsics moved."""
+    st, centre = int(got[2][0, rp.RIG_STATUS]), int(c["est_rig_stats"][0, 2])
+    assert st & (rp.ST_NAN | rp.ST_NO_EDGES | rp.ST_EST_ASSERT | rp.ST_SINGULAR_R) == 0
+    assert got[2][0, rp.RIG_EDGES] == len(c["pairs"]) and got[2][0, rp.RIG_MATCHES] == 12 * len(c["pairs"])
+    assert not (got[0][:, 0:4] == c["cameras_in"][:, 0:4]).any() and got[3][0, 1] < got[3][0, 0]
+    if name.startswith("ring_8x45"):
+        assert (0, 7) in c["pairs"] and len(c["pairs"]) == 8 and got[2][0, rp.RIG_ITERS] == c["max_iter"] and got[3][0, 1] < got[3][0, 0] / 1000.0
+        far = got[0][(centre + 4) % 8, 4:13].reshape(3, 3)     # half a turn from the centre: 1 + 2 cos(theta) is near -1
+        assert np.trace(far) < -0.9 and np.abs(got[0][centre, 4:13] - np.eye(3).ravel()).max() <= 1e-6
+    if name == "ring_8x45_center_4":
+        assert centre == 4
+    if name == "ring_8x45_exact_half_turn":
+        assert np.array_equal(np.diag(c["cameras_in"][4, 4:13].reshape(3, 3)), [-1.0, 1.0, -1.0]) and np.array_equal(c["cameras_in"][0, 4:13], np.eye(3).ravel())
+    if name == "ring_6x60_center_0":
+        assert (0, 5) in c["pairs"] and got[2][0, rp.RIG_ITERS] == 4
+    if name == "arc_5x50_natural_end":
+        assert (0, 4) not in c["pairs"] and 6 < got[2][0, rp.RIG_ITERS] < 1000 and got[3][0, 1] < got[3][0, 0] / 100.0
+    if name == "reflection_R_in":
+        assert np.linalg.det(c["cameras_in"][1, 4:13].reshape(3, 3)) < -0.9
+    if name == "ring_16x22p5_two_steps":
+        assert rp.PC * len(c["sizes"]) == 112 and len(c["pairs"]) == 32 and got[2][0, rp.RIG_ITERS] == 2
+
+
+def test_a_ring_a_narrow_rig_and_the_exact_half_turn_in_one_launch(gpu):
+    """Three blocks of one launch, of which two take branches of bundle_math.hpp that the narrow one between them never does: each rig
+    equals its run alone and the model."""
+    rigs = [NAMED["ring_8x45_center_4"], NAMED["max_iter_3"], NAMED["ring_8x45_exact_half_turn"]]
+    assert all(r["max_iter"] == 3 and r["conf_thresh"] == 1.0 and r["refine_flags"] == 31 for r in rigs)
+    joined = dict(cases.join(rigs), refine_flags=31)
+    got, info = fz.run_library(joined, "device")
+    assert info == (3, 1)
+    at = 0
+    for k, r in enumerate(rigs):
+        alone, info1 = fz.run_library(r, "device")
+        assert info1 == (1, 1)
+        m = len(r["sizes"])
+        assert fz.same(got[0][at:at + m], alone[0]) and fz.same(got[1][at:at + m], alone[1]), k
+        assert np.array_equal(got[2][k:k + 1], alone[2]) and fz.same(got[3][k:k + 1], alone[3]), k
+        at += m
+    check(got, fz.run_model(joined), "ring, narrow, half turn")
 
 
 def test_chain_64_against_the_recorded_model(gpu):
@@ -116,6 +162,57 @@ def test_host_device_and_strided_mats_give_the_same_bits(gpu, name):
         got, info = fz.run_library(NAMED[name], layout)
         check(got, want, (name, layout))
         assert info == (1, 1)
+
+
+def ring_chain_inputs():
+    """The ring of 8 cameras 45 degrees apart as the homography stage would leave it: (case, H of its pairs stacked 3 k x 3) with H the
+    planted K R_j^T R_i K^-1 / h22 of estimator_cases.homography."""
+    import estimator_cases as EC
+    c = NAMED["ring_8x45_center_0"]
+    focal, Rs = c["planted"][:2]
+    return c, np.concatenate([EC.homography(Rs[i], Rs[j], focal) for i, j in c["pairs"]])
+
+
+def test_the_ring_from_the_estimator_to_both_wave_corrections_on_cuda_tensors(gpu):
+    """HomographyBasedEstimator on the planted homographies of the ring, BundleAdjusterReproj on its cameras - which reach half a turn from
+    the centre - and waveCorrect of both kinds on the adjuster's, every mat on the device, four launches in stream order with no
+    synchronisation: each equal to its model fed the read-back mats."""
+    import torch
+    from helpers import estimator_np as EM
+    from imagestitch_amd import adjuster as adj
+    from imagestitch_amd import cameras as cam
+    from test_gpu_estimator import check as check_estimator
+    c, H = ring_chain_inputs()
+    n, pairs, dev = len(c["sizes"]), c["pairs"], dict(device="cuda")
+    put = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()      # noqa: E731
+    kps, ms, mk = [put(k) for k in c["keypoints"]], [put(m) for m in c["matches"]], [put(m) for m in c["masks"]]
+    counts, stats, conf, Hd = put(c["counts"]), put(c["stats"]), put(c["conf"]), put(H)
+    est = (torch.empty((n, 16), dtype=torch.float64, **dev), torch.empty((n, 18), dtype=torch.float32, **dev),
+           torch.empty((n, 2), dtype=torch.int32, **dev), torch.empty((1, 8), dtype=torch.int32, **dev))
+    outs = (torch.empty((n, 16), dtype=torch.float64, **dev), torch.empty((n, 18), dtype=torch.float32, **dev),
+            torch.empty((1, 8), dtype=torch.int32, **dev), torch.empty((1, 2), dtype=torch.float64, **dev))
+    waves = [(torch.empty((n, 16), dtype=torch.float64, **dev), torch.empty((n, 18), dtype=torch.float32, **dev), torch.empty((1, 2), dtype=torch.int32, **dev))
+             for _ in range(2)]
+    torch.cuda.synchronize()
+    cam.estimate_cameras(c["sizes"], pairs, Hd, stats, conf, *est)                          # four launches in stream order, nothing in between
+    info = adj.bundle_adjust_reproj(c["sizes"], kps, pairs, ms, mk, counts, stats, conf, est[3], est[0], *outs, conf_thresh=1.0, max_iter=3)
+    winfo = [adj.wave_correct(outs[0], *w, kind=kind) for w, kind in zip(waves, (adj.WAVE_CORRECT_HORIZ, adj.WAVE_CORRECT_VERT))]
+    torch.cuda.synchronize()
+    assert info == (1, 1) and winfo == [(1, 1), (1, 1)]
+    got_est = tuple(a.cpu().numpy() for a in est)
+    check_estimator(got_est, EM.estimate(c["sizes"], pairs, H, c["stats"]), "ring: estimator")
+    turns = [np.trace(R.reshape(3, 3)) / np.cbrt(np.linalg.det(R.reshape(3, 3))) for R in got_est[0][:, 4:13]]      # 1 + 2 cos(theta): R comes scaled
+    assert min(turns) < -0.9 and got_est[3][0, 0] & (EM.EST_ASSERT | EM.EST_UNREACHED) == 0             # a camera half a turn from the centre
+    want = rp.adjust(c["sizes"], c["keypoints"], pairs, c["matches"], c["masks"], c["counts"], c["conf"], got_est[3], got_est[0], None, 1.0, 3)
+    got = tuple(a.cpu().numpy() for a in outs)
+    check(got, want, "ring: adjuster")
+    assert got[2][0, rp.RIG_STATUS] & ~rp.ST_DROPPED == 0 and got[2][0, rp.RIG_ITERS] == 3 and got[3][0, 1] < got[3][0, 0]
+    for w, kind in zip(waves, (rp.WAVE_HORIZ, rp.WAVE_VERT)):
+        wwant = rp.wave_correct(got[0], None, kind)
+        for g, m in zip((a.cpu().numpy() for a in w), wwant):
+            assert g.dtype == m.dtype and fz.same(g, m), kind
+        assert wwant[2][0].tolist() == [0, n]
+    assert not fz.same(waves[0][0].cpu().numpy(), waves[1][0].cpu().numpy())
 
 
 def test_the_chain_to_the_wave_correction_on_cuda_tensors(gpu):

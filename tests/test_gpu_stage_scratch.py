@@ -17,8 +17,10 @@
 
 2. The cross-stream fence and the pinned upload buffer in use: two different problems at once on two streams with no host synchronisation
    in between, a call with device mats followed at once by one with host mats (which refills the pinned buffer the first call's upload
-   reads), and big / small / release() sequences - for the matcher, the homography, the matcher-then-homography chain and the estimator.
-   These pin RESULTS only: a missing fence or a pinned buffer rewritten too early is a race, and a race need not fail on any given run.
+   reads), and big / small / release() sequences - for the matcher, the homography, the matcher-then-homography chain, the estimator,
+   and the three entries that carve one BaScratch: BundleAdjusterRay, BundleAdjusterReproj, the wave correction and the three in
+   cv::Stitcher's order, each on the cameras of the one before; those three also back to back on three streams, and from two threads,
+   which have a scratch each.  These pin RESULTS only: a missing fence or a pinned buffer rewritten too early is a race, and a race need not fail on any given run.
 
 3. The full message of every refused call that test_errors_leave_the_outputs_untouched of the matcher's and the homography's suites
    lists, and of every one that _refusals() of tests/test_gpu_estimator_guard.py lists plus its capturing stream, against the fixture.
@@ -39,10 +41,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for _p in (ROOT, os.path.dirname(os.path.abspath(__file__)), os.path.join(ROOT, "tools")):      # (run as a script too: --record)
     if _p not in sys.path:
         sys.path.insert(0, _p)
+import bundle_cases as BC  # noqa: E402
+import bundle_reproj_cases as BRC  # noqa: E402
 import estimator_cases as EC  # noqa: E402
 import homography_cases as HC  # noqa: E402
 import match_cases as MC  # noqa: E402
 from helpers import blocks_gain_np as BGM  # noqa: E402
+from helpers import bundle_np as BM  # noqa: E402
+from helpers import bundle_reproj_np as BRP  # noqa: E402
 from helpers import dpseam_grad_np as DPG  # noqa: E402
 from helpers import estimator_np as EM  # noqa: E402
 from helpers import graphcut_grad_np as GG  # noqa: E402
@@ -586,8 +592,131 @@ def _chain_check(bs, prob, what):
     hg_check(bs[1], [prob[4]], what)
 
 
+# ---- the adjusters and the wave correction: three entries on one per-thread BaScratch ------------------------------------------------------
+_BA_OUTS = (((16,), np.float64, S_F), ((18,), np.float32, S_F), ((8,), np.int32, S_I), ((2,), np.float64, S_F))      # cameras, kr32, rig_stats, rig_err
+
+
+@functools.lru_cache(maxsize=None)
+def ba_problem(kind, name):
+    """(case, model) of a named case of tests/bundle_cases.py (kind "ray") or tests/bundle_reproj_cases.py ("reproj")"""
+    import fuzz_bundle
+    import fuzz_bundle_reproj
+    if kind == "ray":
+        c = BC.named()[name]
+        return c, fuzz_bundle.run_model(c)
+    c = BRC.named()[name]
+    return c, fuzz_bundle_reproj.run_model(c)
+
+
+def _ba_outs(put, n, nrigs, k0=0):
+    rows = (n, n, nrigs, nrigs)
+    return [put(np.full((r,) + shape, fill, dt), k0 + k) for k, (r, (shape, dt, fill)) in enumerate(zip(rows, _BA_OUTS))]
+
+
+def ba_prepare(prob, where, cameras_in=None):
+    """cameras_in: a mat to read as it is (the cameras_out of the call before); otherwise the case's"""
+    c = prob[0]
+    put = _placer(where)
+    n = len(c["sizes"])
+    nrigs = 1 if c["rig_first"] is None else len(c["rig_first"]) - 1
+    b = dict(case=c)
+    b["kp"] = [put(k, i) for i, k in enumerate(c["keypoints"])]
+    b["m"] = [put(m, i + 1) for i, m in enumerate(c["matches"])]
+    b["mk"] = [put(m, i) for i, m in enumerate(c["masks"])]
+    b["c"], b["st"], b["cf"], b["est"] = put(c["counts"], 1), put(c["stats"], 2), put(c["conf"], 3), put(c["est_rig_stats"], 4)
+    b["cin"] = put(c["cameras_in"], 5) if cameras_in is None else cameras_in
+    b["outs"] = _ba_outs(put, n, nrigs, 6)
+    return b
+
+
+def ba_run(b, stream, kind):
+    from imagestitch_amd import adjuster as adj
+    c = b["case"]
+    fn, kw = (adj.bundle_adjust_ray, {}) if kind == "ray" else (adj.bundle_adjust_reproj, dict(refine_flags=c["refine_flags"]))
+    b["info"] = fn(c["sizes"], b["kp"], c["pairs"], b["m"], b["mk"], b["c"], b["st"], b["cf"], b["est"], b["cin"], *b["outs"], rig_first=c["rig_first"],
+                   conf_thresh=c["conf_thresh"], max_iter=c["max_iter"], stream=stream, **kw)
+    return b
+
+
+def _same_outs(got, want, what):
+    from fuzz_estimator import same
+    for k, (g, w) in enumerate(zip(got, want)):
+        g = _np(g)
+        assert g.shape == w.shape and g.dtype == w.dtype and same(g, w), (what, k, g, w)
+
+
+def ba_check(b, prob, what):
+    nrigs = 1 if prob[0]["rig_first"] is None else len(prob[0]["rig_first"]) - 1
+    assert b["info"] == (nrigs, 1), (what, b["info"])
+    _same_outs(b["outs"], prob[1], what)
+
+
+@functools.lru_cache(maxsize=None)
+def wv_problem(name):
+    """(cameras, model) of a rig of bundle_reproj_cases.wave_rigs(), horizontal"""
+    cams = BRC.wave_rigs()[name]
+    return cams, BRP.wave_correct(cams, None, BRP.WAVE_HORIZ)
+
+
+def _wv_outs(put, n, k0=0):
+    return [put(np.full((n, 16), S_F, np.float64), k0), put(np.full((n, 18), S_F, np.float32), k0 + 1), put(np.full((1, 2), S_I, np.int32), k0 + 2)]
+
+
+def wv_prepare(prob, where, cameras_in=None):
+    put = _placer(where)
+    return dict(cin=put(prob[0], 0) if cameras_in is None else cameras_in, outs=_wv_outs(put, prob[0].shape[0], 1))
+
+
+def wv_run(b, stream):
+    from imagestitch_amd import adjuster as adj
+    b["info"] = adj.wave_correct(b["cin"], *b["outs"], kind=adj.WAVE_CORRECT_HORIZ, stream=stream)
+    return b
+
+
+def wv_check(b, prob, what):
+    assert b["info"] == (1, 1), (what, b["info"])
+    _same_outs(b["outs"], prob[1], what)
+
+
+@functools.lru_cache(maxsize=None)
+def adjust_chain_problem(name):
+    """BundleAdjusterRay, BundleAdjusterReproj on its cameras, waveCorrect on those, as cv::Stitcher runs them one after the other: (the Ray
+    case, the three models, each fed the model's cameras of the one before)"""
+    c = BC.named()[name]
+    ray = BM.adjust(c["sizes"], c["keypoints"], c["pairs"], c["matches"], c["masks"], c["counts"], c["conf"], c["est_rig_stats"], c["cameras_in"],
+                    c["rig_first"], c["conf_thresh"], c["max_iter"])
+    reproj = BRP.adjust(c["sizes"], c["keypoints"], c["pairs"], c["matches"], c["masks"], c["counts"], c["conf"], c["est_rig_stats"], ray[0],
+                        c["rig_first"], c["conf_thresh"], c["max_iter"])
+    return dict(c, refine_flags=BRP.REFINE_ALL), ray, reproj, BRP.wave_correct(reproj[0], c["rig_first"], BRP.WAVE_HORIZ)
+
+
+def _adjust_chain_prepare(prob, where):
+    """each call reads the cameras_out of the one before where that call leaves it: nothing in between"""
+    ray = ba_prepare(prob, where)
+    reproj = dict(ray, cin=ray["outs"][0], outs=_ba_outs(_placer(where), len(prob[0]["sizes"]), 1))
+    return ray, reproj, wv_prepare((prob[0]["cameras_in"],), where, cameras_in=reproj["outs"][0])
+
+
+def _adjust_chain_run(bs, stream):
+    return ba_run(bs[0], stream, "ray"), ba_run(bs[1], stream, "reproj"), wv_run(bs[2], stream)
+
+
+def _adjust_chain_check(bs, prob, what):
+    for b, want, stage in zip(bs, prob[1:], ("ray", "reproj", "wave")):
+        assert b["info"] == (1, 1), (what, stage, b["info"])
+        _same_outs(b["outs"], want, (what, stage))
+
+
 def _stage(name):
     """(the big and the small problem, prepare(problem, where) -> buffers, run(buffers, stream), check(buffers, problem, what)) of a stage"""
+    if name == "bundle_ray":      # 24 images and 276 edges, then 3 and 3
+        return ([ba_problem("ray", "tiles_past_a_block"), ba_problem("ray", "max_iter_3")], ba_prepare, lambda b, s: ba_run(b, s, "ray"), ba_check)
+    if name == "bundle_reproj":   # 37 images (259 unknowns), then 2
+        return ([ba_problem("reproj", "chain_37"), ba_problem("reproj", "two_images_8_inliers")], ba_prepare, lambda b, s: ba_run(b, s, "reproj"), ba_check)
+    if name == "wave":
+        return [wv_problem("pan_64"), wv_problem("pan_3")], wv_prepare, wv_run, wv_check
+    if name == "adjust_chain":    # three calls a run on one scratch: 5 images with edges of up to 129 inliers, then 2 images with 8
+        return [adjust_chain_problem("tiles_5"), adjust_chain_problem("two_images_8_inliers")], _adjust_chain_prepare, _adjust_chain_run, _adjust_chain_check
     if name == "match":
         return (_mt_two(), lambda p, where: mt_prepare(p[0], [(0, 1)], 0.3, p[1], p[2], where, True), mt_run,
                 lambda b, p, what: mt_check(b, p[3], what))
@@ -599,14 +728,16 @@ def _stage(name):
 
 
 def _release(gpu):
+    from imagestitch_amd import adjuster as adj
     from imagestitch_amd import cameras as cam
     from imagestitch_amd import homography as hg
     gpu.FeaturesMatcher.release()
     hg.release()
     cam.release()
+    adj.release()
 
 
-STAGES = ["match", "homography", "chain", "estimator"]
+STAGES = ["match", "homography", "chain", "estimator", "bundle_ray", "bundle_reproj", "wave", "adjust_chain"]
 
 
 @pytest.mark.parametrize("stage", STAGES)
@@ -660,6 +791,68 @@ def test_big_small_release_small_big_release_twice(gpu, stage, where):
         _sync()
         check(b, prob, (stage, where, what))
     _release(gpu)
+    _release(gpu)
+
+
+def test_ray_reproj_and_wave_on_three_streams(gpu):
+    """The three entries that carve one per-thread BaScratch, back to back on three streams with no host synchronisation: Ray(A) on s1,
+    Reproj(B) on s2, the wave correction (C) on s3.  k_ba_rigs keeps JtJ, L, the tiles and the per-edge matrices in `work` for its whole
+    Levenberg-Marquardt loop, so each call must wait for the one before on another stream.  Three rounds: the first allocates (Ray, then the
+    larger Reproj, which grows `work` with a hipFree that waits for the device); the later ones find everything in place, and only the
+    fence orders them.  All three results equal their models (results only: see the module's docstring)."""
+    import torch
+    A, B, Cw = ba_problem("ray", "tiles_past_a_block"), ba_problem("reproj", "chain_37"), wv_problem("pan_64")
+    s1, s2, s3 = torch.cuda.Stream(), torch.cuda.Stream(), torch.cuda.Stream()
+    _release(gpu)
+    for round_ in range(3):
+        a, b, c = ba_prepare(A, "dev"), ba_prepare(B, "dev"), wv_prepare(Cw, "dev")
+        _sync()                                                   # the inputs are in place
+        ba_run(a, s1, "ray")
+        ba_run(b, s2, "reproj")
+        wv_run(c, s3)
+        _sync()
+        ba_check(a, A, ("ray", round_)); ba_check(b, B, ("reproj", round_)); wv_check(c, Cw, ("wave", round_))
+    _release(gpu)
+
+
+def test_two_threads_have_their_own_scratch(gpu):
+    """The scratch is per calling thread (per_thread<BaScratch>()): two Python threads, each on its own stream, one running Ray on 276
+    edges five times, the other Reproj and the wave correction twenty times, share nothing and need no fence between them.  Every result
+    equals its model; each thread returns its own scratch at its end, since nothing frees it when the thread exits."""
+    import threading
+    import torch
+    from imagestitch_amd import adjuster as adj
+    A, B, Cw = ba_problem("ray", "tiles_past_a_block"), ba_problem("reproj", "max_iter_3"), wv_problem("pan_5_planted")
+    _release(gpu)
+    _sync()
+    errors = []
+
+    def worker(jobs, rounds):
+        try:
+            torch.cuda.set_device(0)
+            s = torch.cuda.Stream()
+            for round_ in range(rounds):
+                with torch.cuda.stream(s):                        # the inputs are placed on the thread's own stream, which orders them before the call
+                    bufs = [prepare(prob, "dev") for prob, prepare, _, _ in jobs]
+                for (prob, _, run, _), b in zip(jobs, bufs):
+                    run(b, s)
+                s.synchronize()
+                for (prob, _, _, check), b in zip(jobs, bufs):
+                    check(b, prob, (threading.current_thread().name, round_))
+            adj.release()
+        except BaseException as e:      # noqa: BLE001 - handed to the main thread, which fails the test
+            errors.append(e)
+
+    threads = [threading.Thread(target=worker, name="ray", args=([(A, ba_prepare, lambda b, s: ba_run(b, s, "ray"), ba_check)], 5)),
+               threading.Thread(target=worker, name="reproj-wave",
+                                args=([(B, ba_prepare, lambda b, s: ba_run(b, s, "reproj"), ba_check), (Cw, wv_prepare, wv_run, wv_check)], 20))]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    _sync()
+    if errors:
+        raise errors[0]
     _release(gpu)
 
 

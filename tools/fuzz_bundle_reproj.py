@@ -7,7 +7,8 @@ The cases are tools/fuzz_bundle.py's (its classes of 2, 3, 5 and 9 images in the
 inliers around the tile of the accumulation, confidences either side of conf_thresh, max_iter, layouts and planted faults: a NaN focal, a
 singular R, a count above its mat's rows, an index outside the keypoints, the estimator's assert bit) with what BundleAdjusterReproj adds drawn
 on top: every camera comes in with ppx and ppy moved by up to 12 pixels and its aspect scaled by up to 2 %, and refine_flags is random -
-everything, nothing, the focal alone or any of the 32 values.  Every case is compared with the model (cameras, kr32, rig_stats, rig_err:
+everything, nothing, the focal alone or any of the 32 values.  Every fourth case is fuzz_bundle.make_wide_case's, a rig that goes round, with
+the same drawn on top (counted as `wide`).  Every case is compared with the model (cameras, kr32, rig_stats, rig_err:
 bits, NaNs by position); none is skipped.  The model in Python sets the pace.  Prints one JSON line; exit status 1 on a mismatch."""
 import argparse
 import json
@@ -28,9 +29,8 @@ from helpers import bundle_reproj_np as rp  # noqa: E402
 CLASSES, LAYOUTS, NAMES = fz.CLASSES, fz.LAYOUTS, fz.NAMES
 
 
-def make_case(seed, cls=None):
-    """fuzz_bundle.make_case(seed) with planted ppx / ppy / aspect offsets on cameras_in and a refine_flags."""
-    c = fz.make_case(seed, cls)
+def _plant(c, seed):
+    """The ppx / ppy / aspect offsets and the refine_flags of `seed` on a case of fuzz_bundle (in place)."""
     rng = np.random.default_rng([seed, 7])
     cams = c["cameras_in"]
     n = cams.shape[0]
@@ -42,6 +42,16 @@ def make_case(seed, cls=None):
     if c["max_iter"] == 1000:
         c["max_iter"] = 40                                   # the natural end of seven parameters a camera is slower in the model
     return c
+
+
+def make_case(seed, cls=None):
+    """fuzz_bundle.make_case(seed) with planted ppx / ppy / aspect offsets on cameras_in and a refine_flags."""
+    return _plant(fz.make_case(seed, cls), seed)
+
+
+def make_wide_case(seed):
+    """fuzz_bundle.make_wide_case(seed), a rig that goes round, with the same offsets and refine_flags drawn on top."""
+    return _plant(fz.make_wide_case(seed), seed)
 
 
 def run_model(c):
@@ -82,17 +92,20 @@ def run_case(c):
 
 
 def run(seconds, seed, verbose=False):
-    """Draws cases (the classes in turn) for `seconds` and compares the library with the model.  Returns a summary dict."""
+    """Draws cases (the classes in turn; every fourth a rig that goes round, counted as `wide`) for `seconds` and compares the library with
+    the model.  Returns a summary dict."""
     import torch
     import imagestitch_amd
     imagestitch_amd.load()
     t0 = time.time()
     per, failing, n, rigs, faults, flags = {c: 0 for c in CLASSES}, [], 0, 0, 0, {}
+    wide = {c: 0 for c in fz.WIDE_CLASSES}
     while time.time() - t0 < seconds:
-        s = int(seed) * 1000 + n
-        c = make_case(s)
+        is_wide = n % fz.WIDE_EVERY == fz.WIDE_EVERY - 1
+        s = int(seed) * 1000 + (sum(wide.values()) if is_wide else sum(per.values()))      # make_case's seeds run on as without the wide share
+        c = make_wide_case(s) if is_wide else make_case(s)
         bad = run_case(c)
-        per[c["cls"]] += 1
+        (wide if is_wide else per)[c["cls"]] += 1
         rigs += 1 if c["rig_first"] is None else len(c["rig_first"]) - 1
         faults += 1 if c["fault"] else 0
         flags[c["refine_flags"]] = flags.get(c["refine_flags"], 0) + 1
@@ -102,7 +115,8 @@ def run(seconds, seed, verbose=False):
             if verbose:
                 print("MISMATCH", s, c["cls"], c["layout"], c["refine_flags"], bad, flush=True)
     return dict(tool="fuzz_bundle_reproj", seconds=round(time.time() - t0, 1), seed=int(seed), cases=n, rigs=rigs, planted_faults=faults,
-                mismatches=len(failing), per_class=per, refine_flags_seen=len(flags), failing_seeds=failing[:20], device=torch.cuda.get_device_name(0))
+                mismatches=len(failing), wide=sum(wide.values()), per_class=per,
+                per_wide_class=wide, refine_flags_seen=len(flags), failing_seeds=failing[:20], device=torch.cuda.get_device_name(0))
 
 
 def main():
