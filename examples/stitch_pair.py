@@ -29,8 +29,9 @@ def main():
     ap.add_argument("images", nargs="*")
     ap.add_argument("--focal", type=float, default=None)
     ap.add_argument("--yaw", type=float, default=0.18)
-    ap.add_argument("--warper", default="cylindrical", choices=["cylindrical", "spherical", "plane"],
-                    help="the warper list of the reference's demos (B:91-95): cv::PlaneWarper, cv::CylindricalWarper (the one they run), cv::SphericalWarper")
+    ap.add_argument("--warper", default="cylindrical", choices=["cylindrical", "spherical", "plane", "fisheye", "stereographic"],
+                    help="the warper list of the reference's demos (B:91-95): cv::PlaneWarper, cv::CylindricalWarper (the one they run), cv::SphericalWarper, "
+                         "cv::FisheyeWarper, cv::StereographicWarper")
     ap.add_argument("--blend", default="feather", choices=["feather", "multiband"])
     ap.add_argument("--gains", type=float, nargs=2, default=[1.0, 1.0])
     ap.add_argument("--estimate-gains", action="store_true",
@@ -63,7 +64,8 @@ def main():
     H, W = imgs[0].shape[:2]
     F = a.focal or 1.1 * W
     K, Rs = synth.camera_pair(W, H, F, yaw=a.yaw)
-    creator = {"cylindrical": isx.CylindricalWarper, "spherical": isx.SphericalWarper, "plane": isx.PlaneWarper}[a.warper]   # B:91-95
+    creator = {"cylindrical": isx.CylindricalWarper, "spherical": isx.SphericalWarper, "plane": isx.PlaneWarper, "fisheye": isx.FisheyeWarper,
+               "stereographic": isx.StereographicWarper}[a.warper]          # B:91-95
     warper = creator().create(F)                                            # W:217-222
     corners, warped, wmasks = [], [], []
     for i in range(2):

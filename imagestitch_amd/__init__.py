@@ -16,7 +16,8 @@ from .homography import BestOf2NearestMatcher, find_homography  # noqa: F401
 from .matcher import FeaturesMatcher, MatchesInfo  # noqa: F401
 from .resize import dilate_resize_and, resize  # noqa: F401
 from .seam import DP_COLOR, DP_COLOR_GRAD, DpSeamFinder, GraphCutSeamFinder, VoronoiSeamFinder, seam_estimate, seam_gradients  # noqa: F401
-from ._lib import WARP_CYLINDRICAL, WARP_PLANE, WARP_SPHERICAL  # noqa: F401
-from .warper import CylindricalWarper, PlaneWarper, RotationWarper, SphericalWarper, remap  # noqa: F401
+from ._lib import WARP_CYLINDRICAL, WARP_FISHEYE, WARP_PLANE, WARP_SPHERICAL, WARP_STEREOGRAPHIC  # noqa: F401
+from .warper import (CylindricalWarper, FisheyeWarper, PlaneWarper, RotationWarper, SphericalWarper, StereographicWarper,  # noqa: F401
+                     remap)
 
-__all__ = ["Blender", "MultiBandBlender", "FeatherBlender", "NoBlender", "convert_to", "dilate_and", "gain_apply", "GainCompensator", "BlocksGainCompensator", "imread", "imwrite", "resize", "dilate_resize_and", "INTER_NEAREST", "INTER_LINEAR", "seam_estimate", "seam_gradients", "DP_COLOR", "DP_COLOR_GRAD", "DpSeamFinder", "GraphCutSeamFinder", "VoronoiSeamFinder", "FeaturesMatcher", "BestOf2NearestMatcher", "MatchesInfo", "find_homography", "CameraParams", "HomographyBasedEstimator", "estimate_cameras", "BundleAdjusterRay", "bundle_adjust_ray", "BundleAdjusterReproj", "bundle_adjust_reproj", "wave_correct", "waveCorrect", "WAVE_CORRECT_HORIZ", "WAVE_CORRECT_VERT", "remap", "CylindricalWarper", "SphericalWarper", "PlaneWarper", "WARP_CYLINDRICAL", "WARP_SPHERICAL", "WARP_PLANE", "RotationWarper", "IsxError", "load"]
+__all__ = ["Blender", "MultiBandBlender", "FeatherBlender", "NoBlender", "convert_to", "dilate_and", "gain_apply", "GainCompensator", "BlocksGainCompensator", "imread", "imwrite", "resize", "dilate_resize_and", "INTER_NEAREST", "INTER_LINEAR", "seam_estimate", "seam_gradients", "DP_COLOR", "DP_COLOR_GRAD", "DpSeamFinder", "GraphCutSeamFinder", "VoronoiSeamFinder", "FeaturesMatcher", "BestOf2NearestMatcher", "MatchesInfo", "find_homography", "CameraParams", "HomographyBasedEstimator", "estimate_cameras", "BundleAdjusterRay", "bundle_adjust_ray", "BundleAdjusterReproj", "bundle_adjust_reproj", "wave_correct", "waveCorrect", "WAVE_CORRECT_HORIZ", "WAVE_CORRECT_VERT", "remap", "CylindricalWarper", "SphericalWarper", "PlaneWarper", "FisheyeWarper", "StereographicWarper", "WARP_CYLINDRICAL", "WARP_SPHERICAL", "WARP_PLANE", "WARP_FISHEYE", "WARP_STEREOGRAPHIC", "RotationWarper", "IsxError", "load"]

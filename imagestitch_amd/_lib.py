@@ -16,7 +16,7 @@ ISX_64FC1 = 6              # MatchesInfo::H and confidence: isx_find_homography 
 INTER_NEAREST, INTER_LINEAR = 0, 1
 INTER_TIES_EVEN = 0x100   # OR to INTER_LINEAR: OpenCV's OpenCL (UMat) remap rounding, half to even
 BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT_101 = 0, 1, 2, 3, 4
-WARP_CYLINDRICAL, WARP_SPHERICAL, WARP_PLANE = 0, 1, 2
+WARP_CYLINDRICAL, WARP_SPHERICAL, WARP_PLANE, WARP_FISHEYE, WARP_STEREOGRAPHIC = 0, 1, 2, 3, 4
 BLEND_NO, BLEND_FEATHER, BLEND_MULTI_BAND = 0, 1, 2
 PREC_I16, PREC_F32, PREC_F16ACC32 = 0, 1, 2
 WINDOW_GRANULE = 128       # ISX_WINDOW_GRANULE: a column window of blend() starts on a multiple of it
@@ -178,6 +178,8 @@ _SIGS = {
     "isx_selftest_exception_barrier": [C.c_int],
     "isx_selftest_bundle_math": [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)],
     "isx_selftest_bundle_math_device": [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)],
+    "isx_selftest_proj_math": [C.c_int, C.c_int, _F9, _F9, _F9],
+    "isx_selftest_proj_math_device": [C.c_int, C.c_int, _F9, _F9, _F9],
     "isx_profile_enable": [C.c_int],
     "isx_profile_reset": [],
     "isx_profile_filter": [C.c_char_p],

@@ -1,4 +1,5 @@
-// warp.hip — cylindrical / spherical / plane rotation warper for MI355X (gfx950).
+// warp.hip — cylindrical / spherical / plane rotation warper for MI355X (gfx950), and the host side of the fisheye and
+// stereographic kinds, whose kernels are warp_polar.hip's.
 // Replaces the reference's in-tree warper (W:30-161: mapForward, mapBackward, detectResultRoi,
 // setCameraParams, buildMaps, warp) and the cv::remap call it ends in (W:157; arithmetic spec:
 // SURVEY.md §8(a) A8).  buildMaps + remap are fused: the back-projection is evaluated per
@@ -14,6 +15,8 @@
 // v / scale - t[1] per row, and the constant 1 - t[2] of the call fills the second row table.
 #include "isx_device.hpp"
 #include "isx_internal.hpp"
+#include "warp_polar.hpp"
+#include "warp_sample.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -81,73 +84,6 @@ template <bool PLANE>
 __device__ __forceinline__ void map_backward_k(const Proj& p, const MapTabs& t, int dx, int dy, float& x, float& y) {
     if constexpr (PLANE) map_backward_plane(p, t, dx, dy, x, y);
     else map_backward(p, t, dx, dy, x, y);
-}
-
-struct SrcView {
-    const unsigned char* data;
-    size_t step;
-    int rows, cols;
-};
-
-__device__ __forceinline__ int clamp_short(int v) { return min(max(v, -32768), 32767); }
-
-// cv::remap, INTER_NEAREST on a u8 / f32 image of CN channels
-template <class T, int CN>
-__device__ __forceinline__ void sample_nearest(const SrcView& s, float mx, float my, int border, T* out) {
-    int sx = clamp_short(cvround_x86(mx)), sy = clamp_short(cvround_x86(my));
-    if (!((unsigned)sx < (unsigned)s.cols && (unsigned)sy < (unsigned)s.rows)) {
-        if (border == ISX_BORDER_CONSTANT) {
-#pragma unroll
-            for (int c = 0; c < CN; ++c) out[c] = 0;
-            return;
-        }
-        sx = border_index(sx, s.cols, border); sy = border_index(sy, s.rows, border);
-    }
-    const T* q = (const T*)(s.data + (size_t)sy * s.step) + (size_t)sx * CN;
-#pragma unroll
-    for (int c = 0; c < CN; ++c) out[c] = q[c];
-}
-
-// cv::remap, INTER_LINEAR: coordinates quantised to 1/32 px (cvRound(x*32)), taps through
-// borderInterpolate; u8 uses the 15-bit fixed-point table, f32 the float table.
-template <class T, int CN>
-__device__ __forceinline__ void sample_linear(const SrcView& s, float mx, float my, int border, T* out, bool ties_even = false) {
-    int isx = cvround_x86(mx * 32.f), isy = cvround_x86(my * 32.f);
-    int fx = isx & 31, fy = isy & 31;
-    int sx = clamp_short(isx >> 5), sy = clamp_short(isy >> 5);
-    if (border == ISX_BORDER_CONSTANT && (sx >= s.cols || sx + 1 < 0 || sy >= s.rows || sy + 1 < 0)) {
-#pragma unroll
-        for (int c = 0; c < CN; ++c) out[c] = 0;
-        return;
-    }
-    int sx0 = border_index(sx, s.cols, border), sx1 = border_index(sx + 1, s.cols, border);
-    int sy0 = border_index(sy, s.rows, border), sy1 = border_index(sy + 1, s.rows, border);
-    const bool ok00 = sx0 >= 0 && sy0 >= 0, ok01 = sx1 >= 0 && sy0 >= 0, ok10 = sx0 >= 0 && sy1 >= 0, ok11 = sx1 >= 0 && sy1 >= 0;
-    const T* r0 = (const T*)(s.data + (size_t)max(sy0, 0) * s.step);
-    const T* r1 = (const T*)(s.data + (size_t)max(sy1, 0) * s.step);
-    const int o0 = max(sx0, 0) * CN, o1 = max(sx1, 0) * CN;
-    if constexpr (sizeof(T) == 1) {
-        // BilinearTab_i: (32-fx)(32-fy)*32 ... ; entry (0,0) saturates to {32767,0,0,1}
-        int w0 = (32 - fx) * (32 - fy) * 32, w1 = fx * (32 - fy) * 32, w2 = (32 - fx) * fy * 32, w3 = fx * fy * 32;
-        if ((fx | fy) == 0) { w0 = 32767; w3 = 1; }
-#pragma unroll
-        for (int c = 0; c < CN; ++c) {
-            int v0 = ok00 ? r0[o0 + c] : 0, v1 = ok01 ? r0[o1 + c] : 0, v2 = ok10 ? r1[o0 + c] : 0, v3 = ok11 ? r1[o1 + c] : 0;
-            const int sum = v0 * w0 + v1 * w1 + v2 * w2 + v3 * w3;
-            int r = (sum + (1 << 14)) >> 15;                               // FixedPtCast: round half up (OpenCV's CPU remap)
-            // ISX_INTER_TIES_EVEN: the same sum as OpenCV's OpenCL (UMat) remap rounds it — half to even
-            if (ties_even) r = (fx | fy) == 0 ? v0 : r - (((sum & 32767) == (1 << 14)) & (r & 1));
-            out[c] = (T)sat_u8(r);
-        }
-    } else {
-        float ax1 = fx * (1.f / 32.f), ax0 = 1.f - ax1, ay1 = fy * (1.f / 32.f), ay0 = 1.f - ay1;
-        float w0 = ay0 * ax0, w1 = ay0 * ax1, w2 = ay1 * ax0, w3 = ay1 * ax1;
-#pragma unroll
-        for (int c = 0; c < CN; ++c) {
-            float v0 = ok00 ? r0[o0 + c] : 0.f, v1 = ok01 ? r0[o1 + c] : 0.f, v2 = ok10 ? r1[o0 + c] : 0.f, v3 = ok11 ? r1[o1 + c] : 0.f;
-            out[c] = v0 * w0 + v1 * w1 + v2 * w2 + v3 * w3;
-        }
-    }
 }
 
 // generic warp: one destination pixel per thread, 64 x 4 pixels per block
@@ -1199,7 +1135,12 @@ void trunc_interval(int bound, double& lo, double& hi) {
     else { lo = -1.0; hi = 1.0; }
 }
 
-bool valid_kind(int kind) { return kind == ISX_WARP_CYLINDRICAL || kind == ISX_WARP_SPHERICAL || kind == ISX_WARP_PLANE; }
+bool valid_kind(int kind) { return kind == ISX_WARP_CYLINDRICAL || kind == ISX_WARP_SPHERICAL || kind == ISX_WARP_PLANE || polar_kind(kind); }
+
+// The fisheye and stereographic kinds (warp_polar.hip) take the same Proj, under the name that translation unit knows
+static_assert(sizeof(PolarProj) == sizeof(Proj), "PolarProj is Proj");
+PolarProj as_polar(const Proj& p) { PolarProj q; memcpy(&q, &p, sizeof(q)); return q; }
+PolarSrc as_polar(const SrcView& v) { return PolarSrc{v.data, v.step, v.rows, v.cols}; }
 
 // is what is enqueued on the stream captured instead of run?  (a query that fails counts as no; its error is swallowed)
 bool stream_is_capturing(hipStream_t st) {
@@ -1459,6 +1400,13 @@ int set_camera(isx_warper* w, const float K[9], const float R[9]) {
     for (int i = 0; i < 9; ++i)
         ISX_CHECK_ARG(std::isfinite(K[i]) && std::isfinite(R[i]), ISX_ERR_INVALID, "setCameraParams: K / R contain non-finite values");
     make_proj(w->kind, w->scale, K, R, &w->proj, w->k, w->rinv);
+    return ISX_OK;
+}
+
+// The planned and batched forms are not built for the fisheye and stereographic kinds: their entries refuse such a handle, unchanged
+int refuse_polar(const isx_warper* w, const char* entry) {
+    if (w != nullptr && polar_kind(w->kind))
+        return fail(ISX_ERR_UNSUPPORTED, "%s: not built for the %s warper (no planned ROI, batch or column range for that kind)", entry, polar_kind_name(w->kind));
     return ISX_OK;
 }
 
@@ -1854,12 +1802,34 @@ int roi_cylindrical(isx_warper* w, int sw, int sh, hipStream_t st, int roi[4], f
     return ISX_OK;
 }
 
+// FisheyeWarper / StereographicWarper: RotationWarperBase::detectResultRoi, mapForward of every source pixel.  The device evaluates the
+// exact u, v (proj_math.hpp, the text the host compiles too), so the scan's four keys ARE the answer: one launch, the copy of 16 bytes into
+// pinned memory and the re-arming of the keys back to back, one synchronisation.  Remembered like the cylindrical answer (the last one, or
+// 1024 with isx_warper_set_roi_cache).
+int roi_polar(isx_warper* w, int sw, int sh, hipStream_t st, int roi[4], float mm[4]) {
+    SyncRoi& s = w->roi;
+    if (const RoiMemo::Entry* e = s.cyl.find(w->proj, w->k, w->rinv, sw, sh)) { roi_answer(e->roi, e->mm, roi, mm); return ISX_OK; }
+    unsigned* keys = (unsigned*)s.scan.p;
+    ISX_TRY(polar_launch_roi_scan(st, as_polar(w->proj), sw, sh, keys));
+    if (!s.pin) ISX_HIP(hipHostMalloc(&s.pin, 64 + (size_t)CAND_FIRST * 8, hipHostMallocDefault));
+    ISX_HIP(hipMemcpyAsync(s.pin, keys, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    ISX_LAUNCH("roi_rearm", 0.0, st, k_roi_rearm, dim3(1), dim3(1), 0, keys);
+    ISX_HIP(hipStreamSynchronize(st));
+    int r[4];
+    float emm[4];
+    for (int k = 0; k < 4; ++k) { emm[k] = fkey_inv(((const unsigned*)s.pin)[k]); r[k] = f2i_host(emm[k]); }      // W:83-86
+    roi_answer(r, emm, roi, mm);
+    s.cyl.remember(s.cache_on ? 1024 : 1, w->proj, w->k, w->rinv, sw, sh, r, emm);
+    return ISX_OK;
+}
+
 // detectResultRoi of the handle's current camera, synchronously: roi, and the float extrema where mm is not null
 int detect_roi(isx_warper* w, int sw, int sh, int roi[4], float mm[4]) {
     if (w->kind == ISX_WARP_PLANE) return roi_plane(w, sw, sh, roi, mm);
     hipStream_t st = nullptr;
     ISX_TRY(roi_stream_of(w, &st));
     ISX_TRY(arm_scan_once(w->roi.scan, 64 + (size_t)CAND_CAP * 8, st));
+    if (polar_kind(w->kind)) return roi_polar(w, sw, sh, st, roi, mm);
     return w->kind == ISX_WARP_SPHERICAL ? roi_spherical(w, sw, sh, roi, mm) : roi_cylindrical(w, sw, sh, st, roi, mm);
 }
 
@@ -1915,7 +1885,8 @@ int warp_setup(isx_warper* w, const isx_mat* src, isx_mat* dst, const float K[9]
     s->dw = s->roi[2] - s->roi[0] + 1; s->dh = s->roi[3] - s->roi[1] + 1;   // dst.create(roi.height + 1, roi.width + 1)  W:150
     ISX_CHECK_ARG(dst->rows == s->dh && dst->cols == s->dw, ISX_ERR_SIZE, "warp: dst is %dx%d, the warped tile is %dx%d (query isx_warper_roi first)",
                   dst->cols, dst->rows, s->dw, s->dh);
-    ISX_TRY(make_tabs(w, s->roi, &s->t));
+    if (polar_kind(w->kind)) s->t = MapTabs{nullptr, nullptr, nullptr, nullptr};      // not separable: no tables
+    else ISX_TRY(make_tabs(w, s->roi, &s->t));
     ISX_TRY(w->st_src.use_in(src, w->stream, "warp: src"));
     ISX_TRY(w->st_dst.use_out(dst, w->stream, "warp: dst"));
     s->sv = SrcView{(const unsigned char*)w->st_src.d.data, w->st_src.d.step, src->rows, src->cols};
@@ -1973,7 +1944,9 @@ int warp_fused(isx_warper* w, const isx_mat* src, const isx_mat* src_mask, const
     ISX_CHECK_ARG(!(gained && src_mask), ISX_ERR_UNSUPPORTED, "warp_with_mask: isx_warper_set_gain applies to tiles warped with the all-255 mask (src_mask == NULL)");
     const bool collect = !src_mask && w->batch.open && !gained && dst->device >= 0 && dst_mask->device >= 0 && src->device >= 0;
     if (!collect) ISX_TRY(flush_warp_batch(w));      // whatever is launched here goes out BEHIND what was collected so far
-    if (src_mask) {
+    if (polar_kind(w->kind)) {      // (never planned, batched or ranged: those entries refuse the kind)
+        ISX_TRY(polar_launch_warp_img_mask(st, as_polar(w->proj), out16, bytes, as_polar(s.sv), as_polar(mv), gained ? w->gain_lut : nullptr, dd, dm, s.roi[0], s.roi[1], dw, dh));
+    } else if (src_mask) {
         ISX_TRY(launch_warp_img_mask(st, w->kind, out16, vec, bytes, w->proj, s.t, s.sv, mv, dd, dm, dw, dh));
     } else {
         // (xg = 0: the plain block order; k_warp_tile's XCD-run order was measured and left off)
@@ -2015,7 +1988,9 @@ int warp_plain(isx_warper* w, const isx_mat* src, const float K[9], const float 
     // The two calls the reference makes per tile take the tile kernels, within the limits of the fused entry (32-bit offsets from 24-bit multiplies)
     const bool small = (unsigned long long)w->st_src.d.step * src->rows < (1ull << 31) && w->st_src.d.step < (1u << 24) && src->cols <= 32767 && src->rows <= 32767 &&
                        ds < (1u << 24) && (unsigned long long)ds * dh < (1ull << 32);
-    if (small && src->type == ISX_8UC3 && interp == ISX_INTER_LINEAR && border == ISX_BORDER_REFLECT) {
+    if (polar_kind(w->kind)) {
+        ISX_TRY(polar_launch_warp(st, as_polar(w->proj), src->type, bytes, as_polar(s.sv), dp, ds, s.roi[0], s.roi[1], dw, dh, interp, border));
+    } else if (small && src->type == ISX_8UC3 && interp == ISX_INTER_LINEAR && border == ISX_BORDER_REFLECT) {
         const dim3 gridt(cdiv(dw, 64), cdiv(dh, 4 * WARP_WAVES));
         const WarpTileArgs wta{w->proj, s.t, s.sv, TileDst{dp, (unsigned)ds, nullptr, 0u, dw, dh, 0, 0, 0xFFFFFFFFu / gridt.x + 1u}, {}};      // (xg = 0: as in warp_fused)
         ISX_TRY(launch_warp_tile_img(st, w->kind, gridt, bytes, wta));
@@ -2076,6 +2051,7 @@ int isx_warper_destroy(isx_warper* w) ISX_ENTRY {
 int isx_warper_begin_batch(isx_warper* w) ISX_ENTRY {
     clear_error();
     ISX_CHECK_ARG(w != nullptr, ISX_ERR_INVALID, "isx_warper_begin_batch: null warper");
+    ISX_TRY(refuse_polar(w, "isx_warper_begin_batch"));
     ISX_HIP(hipSetDevice(w->device));
     ISX_TRY(flush_warp_batch(w));
     w->batch.open = true;
@@ -2125,7 +2101,8 @@ int isx_warper_set_translation(isx_warper* w, const float T[3]) ISX_ENTRY {
     ISX_CHECK_ARG(w != nullptr && T != nullptr, ISX_ERR_INVALID, "isx_warper_set_translation: null argument");
     ISX_CHECK_ARG(std::isfinite(T[0]) && std::isfinite(T[1]) && std::isfinite(T[2]), ISX_ERR_INVALID, "isx_warper_set_translation: T contains non-finite values");
     ISX_CHECK_ARG(w->kind == ISX_WARP_PLANE || (T[0] == 0.f && T[1] == 0.f && T[2] == 0.f), ISX_ERR_UNSUPPORTED,
-                  "isx_warper_set_translation: only the plane warper takes a translation (cv::detail::PlaneWarper)");
+                  "isx_warper_set_translation: only the plane warper takes a translation (cv::detail::PlaneWarper), this is the %s warper",
+                  w->kind == ISX_WARP_CYLINDRICAL ? "cylindrical" : w->kind == ISX_WARP_SPHERICAL ? "spherical" : polar_kind_name(w->kind));
     for (int i = 0; i < 3; ++i) w->t[i] = T[i];
     return ISX_OK;
 } ISX_EXIT("isx_warper_set_translation")
@@ -2135,6 +2112,7 @@ int isx_warper_warp_point(isx_warper* w, const float K[9], const float R[9], flo
     ISX_CHECK_ARG(w != nullptr && out_uv != nullptr, ISX_ERR_INVALID, "isx_warper_warp_point: null argument");
     ISX_TRY(set_camera(w, K, R));
     if (w->kind == ISX_WARP_PLANE) map_forward_plane_host(w->proj, w->t, x, y, out_uv[0], out_uv[1]);
+    else if (polar_kind(w->kind)) polar_map_forward_host(as_polar(w->proj), x, y, out_uv[0], out_uv[1]);
     else map_forward_host(w->proj, x, y, out_uv[0], out_uv[1]);
     return ISX_OK;
 } ISX_EXIT("isx_warper_warp_point")
@@ -2155,6 +2133,7 @@ int isx_warper_set_roi_cache(isx_warper* w, int on) ISX_ENTRY {
 int isx_warper_set_dst_columns(isx_warper* w, int col0, int col1) ISX_ENTRY {
     clear_error();
     ISX_CHECK_ARG(w != nullptr, ISX_ERR_INVALID, "isx_warper_set_dst_columns: null warper");
+    ISX_TRY(refuse_polar(w, "isx_warper_set_dst_columns"));
     ISX_CHECK_ARG((col0 == 0 && col1 == 0) || (col0 >= 0 && col1 > col0), ISX_ERR_INVALID, "isx_warper_set_dst_columns: columns [%d, %d)", col0, col1);
     w->col0 = col0; w->col1 = col1;
     return ISX_OK;
@@ -2191,12 +2170,13 @@ int build_maps_common(isx_warper* w, int src_w, int src_h, const float K[9], con
     const int dw = roi[2] - roi[0] + 1, dh = roi[3] - roi[1] + 1;   // W:128-129
     ISX_CHECK_ARG(xmap->rows == dh && xmap->cols == dw && ymap->rows == dh && ymap->cols == dw, ISX_ERR_SIZE,
                   "buildMaps: maps must be %dx%d", dw, dh);
-    MapTabs t;
-    ISX_TRY(make_tabs(w, roi, &t));
+    MapTabs t{nullptr, nullptr, nullptr, nullptr};
+    if (!polar_kind(w->kind)) ISX_TRY(make_tabs(w, roi, &t));
     hipStream_t st = w->stream;
     ISX_TRY(w->st_x.use_out(xmap, st, "buildMaps: xmap"));
     ISX_TRY(w->st_y.use_out(ymap, st, "buildMaps: ymap"));
-    ISX_TRY(launch_build_maps(st, w->kind, w->proj, t, w->st_x.d, w->st_y.d, dw, dh));
+    if (polar_kind(w->kind)) ISX_TRY(polar_launch_build_maps(st, as_polar(w->proj), w->st_x.d, w->st_y.d, roi[0], roi[1], dw, dh));
+    else ISX_TRY(launch_build_maps(st, w->kind, w->proj, t, w->st_x.d, w->st_y.d, dw, dh));
     ISX_TRY(w->st_x.finish_out(st));
     ISX_TRY(w->st_y.finish_out(st));
     return ISX_OK;
@@ -2260,6 +2240,7 @@ int isx_warper_warp_with_mask_planned(isx_warper* w, const isx_mat* src_img, con
                                       const int planned_roi[4], isx_mat* dst_img, isx_mat* dst_mask) ISX_ENTRY {
     clear_error();
     ISX_CHECK_ARG(planned_roi != nullptr, ISX_ERR_INVALID, "planned warp: null planned_roi");
+    ISX_TRY(refuse_polar(w, "isx_warper_warp_with_mask_planned"));
     return end_batch_on_failure(w, warp_fused(w, src_img, src_mask, K, R, dst_img, dst_mask, nullptr, WarpRequest{planned_roi, true}));
 } ISX_EXIT("isx_warper_warp_with_mask_planned")
 
@@ -2292,6 +2273,10 @@ int isx_selftest_roi_host(int kind, float scale, const float K[9], const float R
         roi_plane_host(p, t0, src_w, src_h, roi, minmax);
         return ISX_OK;
     }
+    if (polar_kind(kind)) {            // the base class's scan of every source pixel as a plain loop, with the text the device runs
+        polar_roi_host(as_polar(p), src_w, src_h, roi, minmax);
+        return ISX_OK;
+    }
     ISX_CHECK_ARG(kind == ISX_WARP_SPHERICAL || cyl_extrema_on_border(p, k, rinv, src_w, src_h), ISX_ERR_UNSUPPORTED,
                   "selftest_roi_host: the extrema of this cylindrical camera are not provably on the border");
     std::vector<int> cand;
@@ -2316,6 +2301,7 @@ int isx_selftest_warp_point(int kind, float scale, const float K[9], const float
     float k[9], rinv[9];
     make_proj(kind, scale, K, R, &p, k, rinv);
     if (kind == ISX_WARP_PLANE) map_forward_plane_host(p, t, x, y, out_uv[0], out_uv[1]);
+    else if (polar_kind(kind)) polar_map_forward_host(as_polar(p), x, y, out_uv[0], out_uv[1]);
     else map_forward_host(p, x, y, out_uv[0], out_uv[1]);
     return ISX_OK;
 } ISX_EXIT("isx_selftest_warp_point")
@@ -2338,6 +2324,7 @@ int isx_selftest_division(int device, int n, unsigned long long seed, int* misma
 
 int isx_warper_set_deferred_verify(isx_warper* w, int on) ISX_ENTRY {
     ISX_CHECK_ARG(w != nullptr, ISX_ERR_INVALID, "isx_warper_set_deferred_verify: null warper");
+    if (on) ISX_TRY(refuse_polar(w, "isx_warper_set_deferred_verify"));
     w->verify.deferred = on != 0;
     return ISX_OK;
 } ISX_EXIT("isx_warper_set_deferred_verify")
@@ -2345,6 +2332,7 @@ int isx_warper_set_deferred_verify(isx_warper* w, int on) ISX_ENTRY {
 int isx_warper_verify_is_light(isx_warper* w, int src_cols, int src_rows, const float K[9], const float R[9], int* light) ISX_ENTRY {
     clear_error();
     ISX_CHECK_ARG(w != nullptr && light != nullptr && src_cols > 0 && src_rows > 0, ISX_ERR_INVALID, "isx_warper_verify_is_light: bad argument");
+    ISX_TRY(refuse_polar(w, "isx_warper_verify_is_light"));
     ISX_TRY(set_camera(w, K, R));
     *light = verify_is_light(w->proj, w->k, w->rinv, src_cols, src_rows) ? 1 : 0;
     return ISX_OK;
@@ -2380,6 +2368,7 @@ int isx_warper_queue_verify(isx_warper* w, int src_w, int src_h, const float K[9
     clear_error();
     ISX_CHECK_ARG(w != nullptr && K != nullptr && R != nullptr && planned_roi != nullptr, ISX_ERR_INVALID, "isx_warper_queue_verify: null argument");
     ISX_CHECK_ARG(src_w > 0 && src_h > 0, ISX_ERR_INVALID, "isx_warper_queue_verify: empty source %d x %d", src_w, src_h);
+    ISX_TRY(refuse_polar(w, "isx_warper_queue_verify"));
     ISX_HIP(hipSetDevice(w->device));
     ISX_TRY(set_camera(w, K, R));
     return queue_plan_check(w, src_w, src_h, planned_roi);

@@ -67,6 +67,14 @@ def model_bytes(src_px, warped_px, tile_base_px, mosaic_px, precision, num_bands
     return {"warp": warp, "feed": feed, "blend": blend, "total": warp + feed + blend}
 
 
+def _planning_warper(kind, device, stream, scale):
+    """The warper of a stitcher.  The stitchers plan their ROIs (warp_with_mask_planned, deferred verification): for the kinds those
+    entries are not built for (fisheye, stereographic) the library's ISX_ERR_UNSUPPORTED is raised here, before anything is allocated."""
+    warper = CREATORS[kind](device, stream).create(scale)
+    warper.set_deferred_verify(True)   # both ROI scans start after the last warp of a step (see PairStitcher.step())
+    return warper
+
+
 class PairStitcher:
     """The n >= 2 tiles of one mosaic (normally a pair) -> one blended mosaic, buffers resident in HBM (torch CUDA
     tensors), on the deferred blender cycle (isx_blender_set_deferred_level0; more than 20 tiles: their descriptors in a device table)."""
@@ -84,9 +92,7 @@ class PairStitcher:
         # tile_type "s16": the warped tiles are CV_16SC3 - the warp writes them so (the convertTo(CV_16S) of W:294 folded into its store) and
         # feed() receives what the reference's feed() receives (W:302); "u8": CV_8UC3 tiles through feed_u8 (the conversion fused into feed)
         self.tile_type = tile_type
-        creator = CREATORS[kind]
-        self.warper = creator(device, stream).create(scale)
-        self.warper.set_deferred_verify(True)   # both ROI scans start after the last warp of a step (see step())
+        self.warper = _planning_warper(kind, device, stream, scale)
         self.blender = MultiBandBlender(False, num_bands, precision, device, stream)
         # the warped tiles and seam masks below live as long as this object: the deferred level-0 contract holds
         self.blender.set_deferred_level0(deferred)   # True: this object's buffers outlive blend(); "copy": feed() copies them
@@ -428,8 +434,7 @@ class SplitStitcher:
         from . import mosaic
         self.torch = torch
         dev = torch.device("cuda", device)
-        creator = CREATORS[kind]
-        wp = creator(device, None).create(scale)
+        wp = _planning_warper(kind, device, None, scale)
         src_size = (imgs[0].shape[1], imgs[0].shape[0])
         rois = [wp.warpRoi(src_size, K, R) for R in Rs]
         del wp

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (BORDER_CONSTANT, BORDER_REFLECT, INTER_LINEAR, INTER_NEAREST, WARP_CYLINDRICAL,  # noqa: F401
-                   WARP_PLANE, WARP_SPHERICAL, IsxError, as_mat, check, f9)
+                   WARP_FISHEYE, WARP_PLANE, WARP_SPHERICAL, WARP_STEREOGRAPHIC, IsxError, as_mat, check, f9)
 
 
 def _is_tensor(a):
@@ -36,6 +36,11 @@ class RotationWarper:
     """cv::detail::RotationWarper: warp / buildMaps / warpRoi on one projector kind."""
 
     def __init__(self, kind, scale, device=0, stream=None):
+        """kind: a WARP_* value or its name ("cylindrical", "spherical", "plane", "fisheye", "stereographic")."""
+        if isinstance(kind, str):
+            if kind not in CREATORS:
+                raise IsxError(1, "RotationWarper: unknown warper kind %r (one of %s)" % (kind, ", ".join(sorted(CREATORS))))
+            kind = CREATORS[kind].kind
         self._lib = _lib.load()
         self._h = C.c_void_p()
         check(self._lib.isx_warper_create(kind, float(scale), int(device), C.byref(self._h)))
@@ -257,7 +262,19 @@ class PlaneWarper(_Creator):
     kind = WARP_PLANE
 
 
-CREATORS = {"cylindrical": CylindricalWarper, "spherical": SphericalWarper, "plane": PlaneWarper}
+class FisheyeWarper(_Creator):
+    """cv::FisheyeWarper (B:94): not separable - every pixel evaluates the restated transcendentals (csrc/proj_math.hpp).  The planned and
+    batched entries are not built for it (ISX_ERR_UNSUPPORTED)."""
+    kind = WARP_FISHEYE
+
+
+class StereographicWarper(_Creator):
+    """cv::StereographicWarper (B:95): as FisheyeWarper, with v_ = 2 atanf(1 / r)."""
+    kind = WARP_STEREOGRAPHIC
+
+
+CREATORS = {"cylindrical": CylindricalWarper, "spherical": SphericalWarper, "plane": PlaneWarper, "fisheye": FisheyeWarper,
+            "stereographic": StereographicWarper}
 
 
 def remap(src, xmap, ymap, interp_mode=INTER_LINEAR, border_mode=BORDER_REFLECT, device=0, stream=None):

@@ -157,6 +157,14 @@ struct SphericalWarper : WarperCreator {     // cv::SphericalWarper  B:93 (comme
 struct PlaneWarper : WarperCreator {         // cv::PlaneWarper  B:91 (commented out in the reference)
     std::shared_ptr<RotationWarper> create(float scale) const override { return std::make_shared<RotationWarper>(ISX_WARP_PLANE, scale); }
 };
+// The two projectors that are not separable: every pixel evaluates the restated transcendentals.  warp / warpRoi / buildMaps / warpPoint /
+// setGain serve them; the planned and batched entries throw ISX_ERR_UNSUPPORTED, as does a non-zero setTranslation.
+struct FisheyeWarper : WarperCreator {       // cv::FisheyeWarper  B:94 (commented out in the reference)
+    std::shared_ptr<RotationWarper> create(float scale) const override { return std::make_shared<RotationWarper>(ISX_WARP_FISHEYE, scale); }
+};
+struct StereographicWarper : WarperCreator { // cv::StereographicWarper  B:95 (commented out in the reference)
+    std::shared_ptr<RotationWarper> create(float scale) const override { return std::make_shared<RotationWarper>(ISX_WARP_STEREOGRAPHIC, scale); }
+};
 
 // cv::detail::Blender / MultiBandBlender (W:271-281,302,313)
 class Blender {

@@ -65,8 +65,14 @@ enum { ISX_INTER_NEAREST = 0, ISX_INTER_LINEAR = 1,
 enum { ISX_BORDER_CONSTANT = 0, ISX_BORDER_REPLICATE = 1, ISX_BORDER_REFLECT = 2,
        ISX_BORDER_WRAP = 3, ISX_BORDER_REFLECT_101 = 4 };
 
-/* warper kinds: cv::CylindricalWarper (W:219) / cv::SphericalWarper (B:93, commented) / cv::PlaneWarper (B:91, commented) */
-enum { ISX_WARP_CYLINDRICAL = 0, ISX_WARP_SPHERICAL = 1, ISX_WARP_PLANE = 2 };
+/* warper kinds: cv::CylindricalWarper (W:219) / cv::SphericalWarper (B:93, commented) / cv::PlaneWarper (B:91, commented) /
+ * cv::FisheyeWarper (B:94, commented) / cv::StereographicWarper (B:95, commented).
+ * The last two are not separable (no column / row tables): every pixel evaluates the restated float32 sinf / cosf / atan2f / atanf / acosf
+ * of csrc/proj_math.hpp, and detectResultRoi is the base class's scan of every source pixel, exact on the device (one launch, four floats
+ * back).  They serve isx_warper_create, _camera, _roi, _warp_point, _build_maps(_roi), _warp(_roi), _warp_with_mask(_roi), _set_gain,
+ * _set_stream and _set_roi_cache.  isx_warper_warp_with_mask_planned, _queue_verify, _verify_is_light, _begin_batch, _set_dst_columns,
+ * _set_deferred_verify(on) and a non-zero _set_translation return ISX_ERR_UNSUPPORTED for them and change no state.                  */
+enum { ISX_WARP_CYLINDRICAL = 0, ISX_WARP_SPHERICAL = 1, ISX_WARP_PLANE = 2, ISX_WARP_FISHEYE = 3, ISX_WARP_STEREOGRAPHIC = 4 };
 
 /* cv::detail::Blender::{NO, FEATHER, MULTI_BAND} (W:271,276,278) */
 enum { ISX_BLEND_NO = 0, ISX_BLEND_FEATHER = 1, ISX_BLEND_MULTI_BAND = 2 };
@@ -1013,6 +1019,12 @@ int isx_selftest_bundle_math(int fn, int n, const double* in, double* out);
  * thread per item that calls the same function, `out` (host memory) is copied back.  Uses the null stream and synchronises it.
  * tests/test_gpu_bundle_math.py holds the two entries and the model to the same bits.                                                 */
 int isx_selftest_bundle_math_device(int fn, int n, const double* in, double* out);
+/* The host compilation of csrc/proj_math.hpp, the float32 transcendentals of the fisheye and stereographic projectors, on n items: fn 0 sinf,
+ * 1 cosf, 2 atan2f(in, in2), 3 atanf, 4 acosf; in2 is read by atan2f only (NULL otherwise).  Needs no device: the CPU test-suite compares it
+ * with tests/helpers/polar_np.py bit for bit.                                                                                          */
+int isx_selftest_proj_math(int fn, int n, const float* in, const float* in2, float* out);
+/* The device compilation of the same header on the same items (host pointers; one thread per item).  Uses the null stream and synchronises it. */
+int isx_selftest_proj_math_device(int fn, int n, const float* in, const float* in2, float* out);
 /* Every entry of this header is a function-try-block: a C++ exception raised underneath it (std::bad_alloc of a host container, a
  * std::length_error, anything a future change throws) is stopped there and comes back as a status - ISX_ERR_NOMEM for the two allocation
  * failures, ISX_ERR_INTERNAL otherwise, the text in isx_last_error() - never as an exception in the caller's frames (the
