@@ -15,6 +15,7 @@
 // v / scale - t[1] per row, and the constant 1 - t[2] of the call fills the second row table.
 #include "isx_device.hpp"
 #include "isx_internal.hpp"
+#include "scratch.hpp"
 #include "warp_polar.hpp"
 #include "warp_sample.hpp"
 
@@ -1833,6 +1834,33 @@ int detect_roi(isx_warper* w, int sw, int sh, int roi[4], float mm[4]) {
     return w->kind == ISX_WARP_SPHERICAL ? roi_spherical(w, sw, sh, roi, mm) : roi_cylindrical(w, sw, sh, st, roi, mm);
 }
 
+// The capture rule of the fisheye and stereographic kinds (DESIGN.md "Capture"), checked before set_camera changes the handle and before
+// anything is enqueued.  On device mats a served entry is one kernel launch whose PolarProj and gain table travel in its arguments, which
+// a capture holds.  Two things it cannot hold, and they are refused with ISX_ERR_STATE while w->stream is capturing:
+//  - a host mat: MatStage allocates its staged copy, copies on the stream and synchronises it (use_in, finish_out);
+//  - detectResultRoi of a camera and source size the memo does not hold (sw > 0: the entries that find the ROI themselves): roi_polar
+//    allocates the scan's keys and its pinned landing zone, copies on the shared ROI stream and synchronises it.  A remembered answer is
+//    served from the host alone, as a warmed table is for the tabulated kinds.
+// The other kinds keep their own rule (make_tabs).  Not capturing, this is one hipStreamIsCapturing per call of a polar handle.
+int polar_capture_rule(isx_warper* w, const char* who, const float K[9], const float R[9], int sw, int sh, const isx_mat* const mats[], int n_mats) {
+    if (w == nullptr || !polar_kind(w->kind)) return ISX_OK;
+    ISX_HIP(hipSetDevice(w->device));
+    bool capturing = false;
+    ISX_TRY(is_capturing(w->stream, capturing));
+    if (!capturing) return ISX_OK;
+    for (int i = 0; i < n_mats; ++i)
+        ISX_CHECK_ARG(mats[i] == nullptr || mats[i]->device >= 0, ISX_ERR_STATE, "%s: the stream is capturing (a host mat is staged through an allocation, a copy "
+                      "and a synchronisation: pass device mats)", who);
+    if (sw <= 0 || sh <= 0 || K == nullptr || R == nullptr) return ISX_OK;      // no ROI to find here (or an argument the entry refuses itself)
+    for (int i = 0; i < 9; ++i) if (!std::isfinite(K[i]) || !std::isfinite(R[i])) return ISX_OK;      // set_camera's refusal
+    Proj p;
+    float k[9], rinv[9];
+    make_proj(w->kind, w->scale, K, R, &p, k, rinv);
+    ISX_CHECK_ARG(w->roi.cyl.find(p, k, rinv, sw, sh) != nullptr, ISX_ERR_STATE, "%s: the stream is capturing (the ROI of this camera and %d x %d source is not "
+                  "remembered, and its scan allocates, copies and synchronises: query the ROI once before capture)", who, sw, sh);
+    return ISX_OK;
+}
+
 // ---- the tables of a warped tile (TableArena) ----------------------------------------------------------------------------------------------
 int make_tabs(isx_warper* w, const int roi[4], MapTabs* t) {
     const int mw = roi[2] - roi[0] + 1, mh = roi[3] - roi[1] + 1;
@@ -1861,8 +1889,10 @@ int make_tabs(isx_warper* w, const int roi[4], MapTabs* t) {
     return ISX_OK;
 }
 
+// (INT_MIN is what static_cast<int> makes of a NaN, of +-FLT_MAX and of every extremum out of int's range: where mapForward is NaN on every
+// source pixel all four corners are INT_MIN, which would otherwise pass as a 1 x 1 tile)
 int check_roi_sane(const int roi[4]) {
-    ISX_CHECK_ARG(roi[2] >= roi[0] && roi[3] >= roi[1] && (long long)roi[2] - roi[0] < 65536 && (long long)roi[3] - roi[1] < 65536,
+    ISX_CHECK_ARG(roi[2] >= roi[0] && roi[3] >= roi[1] && (long long)roi[2] - roi[0] < 65536 && (long long)roi[3] - roi[1] < 65536 && roi[2] != INT_MIN && roi[3] != INT_MIN,
                   ISX_ERR_INVALID, "detectResultRoi produced a degenerate ROI [%d,%d]-[%d,%d] (bad K / R / scale?)", roi[0], roi[1], roi[2], roi[3]);
     return ISX_OK;
 }
@@ -1878,6 +1908,8 @@ int warp_setup(isx_warper* w, const isx_mat* src, isx_mat* dst, const float K[9]
     ISX_TRY(check_mat(src, "warp: src"));
     ISX_TRY(check_mat(dst, "warp: dst"));
     ISX_HIP(hipSetDevice(w->device));
+    const isx_mat* const mats[2] = {src, dst};
+    ISX_TRY(polar_capture_rule(w, "warp", K, R, req.planned ? 0 : src->cols, req.planned ? 0 : src->rows, mats, 2));
     ISX_TRY(set_camera(w, K, R));
     if (req.planned) std::copy(req.planned, req.planned + 4, s->roi);
     else ISX_TRY(detect_roi(w, src->cols, src->rows, s->roi, nullptr));
@@ -1898,6 +1930,8 @@ int warp_setup(isx_warper* w, const isx_mat* src, isx_mat* dst, const float K[9]
 int warp_fused(isx_warper* w, const isx_mat* src, const isx_mat* src_mask, const float K[9], const float R[9], isx_mat* dst, isx_mat* dst_mask, int corner[2],
                const WarpRequest& req) {
     WarpSetup s;
+    const isx_mat* const masks[2] = {src_mask, dst_mask};
+    ISX_TRY(polar_capture_rule(w, "warp_with_mask", nullptr, nullptr, 0, 0, masks, 2));      // (the image mats and the ROI: in warp_setup)
     ISX_TRY(warp_setup(w, src, dst, K, R, req, &s));
     const hipStream_t st = w->stream;
     const int dw = s.dw, dh = s.dh;
@@ -2153,6 +2187,7 @@ int isx_warper_roi(isx_warper* w, int src_w, int src_h, const float K[9], const 
     ISX_CHECK_ARG(w != nullptr && roi != nullptr, ISX_ERR_INVALID, "isx_warper_roi: null argument");
     ISX_CHECK_ARG(src_w > 0 && src_h > 0, ISX_ERR_INVALID, "isx_warper_roi: empty source size %d x %d", src_w, src_h);
     ISX_HIP(hipSetDevice(w->device));
+    ISX_TRY(polar_capture_rule(w, "isx_warper_roi", K, R, src_w, src_h, nullptr, 0));
     ISX_TRY(set_camera(w, K, R));
     return detect_roi(w, src_w, src_h, roi, minmax);
 } ISX_EXIT("isx_warper_roi")
@@ -2164,6 +2199,8 @@ int build_maps_common(isx_warper* w, int src_w, int src_h, const float K[9], con
     ISX_TRY(check_mat(ymap, "buildMaps: ymap"));
     ISX_CHECK_ARG(xmap->type == ISX_32FC1 && ymap->type == ISX_32FC1, ISX_ERR_TYPE, "buildMaps: maps must be CV_32FC1");
     ISX_HIP(hipSetDevice(w->device));
+    const isx_mat* const mats[2] = {xmap, ymap};
+    ISX_TRY(polar_capture_rule(w, "buildMaps", K, R, given_roi ? 0 : src_w, given_roi ? 0 : src_h, mats, 2));
     ISX_TRY(set_camera(w, K, R));
     if (!given_roi) ISX_TRY(detect_roi(w, src_w, src_h, roi, nullptr));
     ISX_TRY(check_roi_sane(roi));

@@ -129,7 +129,11 @@ int isx_warper_set_roi_cache(isx_warper* w, int on);
  * stream this handle left (isx_warper_set_stream) since the last start-over.  A chunk that a warp enqueued on a CAPTURING stream read from is
  * never rewritten: a start-over sets it aside until isx_warper_destroy and continues in fresh chunks - at most the 4 chunks (16 MiB) the
  * arena held per start-over that follows a capture.  A warp on a capturing stream whose table is not cached fails with ISX_ERR_STATE
- * before it enqueues anything: run the same warp once eagerly before the capture.                                                   */
+ * before it enqueues anything: run the same warp once eagerly before the capture.
+ * The fisheye and stereographic kinds have no tables; their rule on a capturing stream ("Capture"): _warp_roi, _warp_with_mask_roi
+ * and _build_maps_roi on device mats are one kernel launch and can be captured; any entry given a host mat, and _roi / _warp /
+ * _warp_with_mask / _build_maps for a camera and source size whose ROI the handle does not remember (isx_warper_set_roi_cache), fail with
+ * ISX_ERR_STATE before the handle changes or anything is enqueued: pass device mats, and query the ROI once before the capture.      */
 int isx_warper_table_resets(isx_warper* w, long long* resets);
 /* compensator->apply(i, corners[i], images_warped[i], masks_warped[i]) (W:241-244) folded into the fused tile warps that
  * follow (isx_warper_warp_with_mask / _roi / _planned with src_mask == NULL): every byte of the warped IMAGE becomes

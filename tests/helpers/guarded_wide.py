@@ -7,6 +7,7 @@ them, a generic size_t kernel and ISX_ERR_UNSUPPORTED by  step < 2^24,  step * r
     "wide"        pitch 2^24 (the default) or 2^24 + 64: the first pitch a 24-bit multiply truncates
     "wide_below"  pitch 2^24 - 64 (2^24 - 4 for a one-byte, one-channel mat): the fast side of that edge
     "tall31"      pitch 2^23: 255 rows give step * rows < 2^31, 256 rows exactly 2^31
+                  (or pitch 2^24: 129 rows end past 2^31 - a source the size_t kernels serve whole)
     "tall32"      pitch 2^23 (the default; 511 / 512 rows) or 2^24 - 64 (256 / 257 rows): either side of step * rows = 2^32
 
     g = wide_guarded((h, w, 3), np.uint8, "tall31", seed)        # the interface of guarded.Guarded: .view .set() .get() .check()
@@ -36,7 +37,7 @@ from .guarded import NOTHING, GuardError
 LAYOUTS = ("wide", "wide_below", "tall31", "tall32")
 CHUNK = 256 << 20
 KIB64 = 64 << 10
-_PITCHES = {"wide": (1 << 24, (1 << 24) + 64), "wide_below": ((1 << 24) - 64,), "tall31": (1 << 23,), "tall32": (1 << 23, (1 << 24) - 64)}
+_PITCHES = {"wide": (1 << 24, (1 << 24) + 64), "wide_below": ((1 << 24) - 64,), "tall31": (1 << 23, 1 << 24), "tall32": (1 << 23, (1 << 24) - 64)}
 
 Plan = collections.namedtuple("Plan", "pitch rows row_bytes offset span nbytes")
 

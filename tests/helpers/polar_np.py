@@ -189,7 +189,8 @@ class Polar:
             rr = sv / (F(1) - cv)
             return self.scale * rr * cu, self.scale * rr * su
 
-    def map_backward(self, u, v):
+    def backward_xyz(self, u, v):
+        """mapBackward up to its division: (x, y, z) of k_rinv times the ray, float32 (tests/test_polar_accuracy.py measures z)"""
         k = self.k_rinv
         u, v = np.broadcast_arrays(np.asarray(u, F), np.asarray(v, F))
         with np.errstate(all="ignore"):
@@ -206,6 +207,11 @@ class Polar:
             x = k[0] * x_ + k[1] * y_ + k[2] * z_
             y = k[3] * x_ + k[4] * y_ + k[5] * z_
             z = k[6] * x_ + k[7] * y_ + k[8] * z_
+            return x, y, z
+
+    def map_backward(self, u, v):
+        x, y, z = self.backward_xyz(u, v)
+        with np.errstate(all="ignore"):
             front = z > 0
             return np.where(front, x / z, F(-1)).astype(F), np.where(front, y / z, F(-1)).astype(F)
 

@@ -12,7 +12,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import fuzz_polar_warp as Z  # noqa: E402
 from helpers import polar_np as P  # noqa: E402
 
-CASES = [Z.case(7000 + i, Z.CLASSES[i % len(Z.CLASSES)]) for i in range(400)]
+FIRST = Z.CLASSES[:5]                       # (the classes of the first sweep keep their seeds)
+CASES = [Z.case(7000 + i, FIRST[i % len(FIRST)]) for i in range(400)] + [Z.case(9000 + i, "captured") for i in range(80)]
 
 
 def test_cases_are_a_function_of_the_seed():
@@ -56,3 +57,13 @@ def test_the_model_evaluates_every_window():
         assert xm.shape == (c["window"][3] - c["window"][1] + 1, c["window"][2] - c["window"][0] + 1) and not np.isnan(xm).any() and not np.isnan(ym).any()
         if max(abs(v) for v in c["window"]) / c["scale"] > 2.0 ** 28 + 200:
             assert ((xm == -1) & (ym == -1)).all()                    # sinf / cosf give NaN out there: z > 0 fails, the sentinel
+
+
+def test_the_captured_class():
+    """device mats, an entry that takes the caller's window (the ROI scan synchronises: never captured), every such entry and both window forms drawn"""
+    cap = [c for c in CASES if c["cls"] == "captured"]
+    assert len(cap) == 80 and Z.CLASSES[5] == "captured"
+    assert all(c["layout"] == "device" and c["entry"] != "roi" for c in cap)
+    assert {c["entry"] for c in cap} == {"maps", "warp", "fused"} and {c["window"] is None for c in cap} == {False, True}
+    assert {c["kind"] for c in cap} == {P.FISHEYE, P.STEREOGRAPHIC} and {c["with_mask"] for c in cap if c["entry"] == "fused"} == {False, True}
+    assert any(c["gain"] != 1.0 for c in cap if c["entry"] == "fused")

@@ -11,6 +11,9 @@ The generator (no GPU needed: tests/test_polar_fuzz_generator.py checks it).  ca
     pole_window   a window around the destination origin (r = 0: atan2f(0, 0), 1.f / 0, atanf(inf))
     far_window    a window far outside the image's ROI: r up to 2^31 / scale, beyond the 2^28 at which sinf / cosf give NaN
     fused         warp_with_mask: with or without a source mask, CV_8UC3 or CV_16SC3, with or without a gain
+    captured      buildMaps, warp or the fused warp over a given window on device mats, captured ONCE into a hipGraph on a side stream; the
+                  source (and the source mask) is then overwritten in place, the destinations are cleared, and the REPLAY is compared with
+                  the model on the new bytes
 Every case draws the entry (roi, maps, warp, fused), the pixel type, interpolation (NEAREST, LINEAR, LINEAR | TIES_EVEN), border mode and
 layout (host mats, device tensors, rows that are views into wider mats).  A rig whose ROI exceeds FULL_WARP_PIXELS is warped through a
 window only (tests/polar_cases.py: window_of)."""
@@ -29,7 +32,7 @@ import numpy as np  # noqa: E402
 import polar_cases as PC  # noqa: E402
 from helpers import polar_np as P  # noqa: E402
 
-CLASSES = ("rigs", "tile_edges", "pole_window", "far_window", "fused")
+CLASSES = ("rigs", "tile_edges", "pole_window", "far_window", "fused", "captured")
 ENTRIES = ("roi", "maps", "warp", "fused")
 TYPES = ((3, "uint8"), (1, "uint8"), (3, "float32"), (1, "float32"))
 INTERPS = (PC.NEAREST, PC.LINEAR, PC.LINEAR | PC.TIES_EVEN)
@@ -84,12 +87,18 @@ def case(seed, cls=None):
         ww, wh = _edge(rng, COL_BLOCK), _edge(rng, ROW_BLOCK, 12)
         x0, y0 = int(rng.integers(-80, 40)), int(rng.integers(-60, 30))
         window = (x0, y0, x0 + ww - 1, y0 + wh - 1)
+    elif cls == "captured":
+        entry = ("maps", "warp", "fused")[int(rng.integers(0, 3))]
+        if rng.random() < 0.5:          # (else the rig's ROI, found eagerly before the capture, or its window_of)
+            ww, wh = _edge(rng, COL_BLOCK), _edge(rng, ROW_BLOCK, 12)
+            x0, y0 = int(rng.integers(-80, 40)), int(rng.integers(-60, 30))
+            window = (x0, y0, x0 + ww - 1, y0 + wh - 1)
     cn, dtype = TYPES[int(rng.integers(0, len(TYPES)))]
     with_mask = bool(rng.random() < 0.5)
     gain = 1.0 if with_mask or rng.random() < 0.5 else float(rng.uniform(0.4, 2.2))
     return dict(seed=int(seed), cls=cls, kind=kind, rname=rname, w=w, h=h, scale=scale, K=K, R=R, entry=entry, cn=cn, dtype=dtype,
                 interp=INTERPS[int(rng.integers(0, len(INTERPS)))], border=BORDERS[int(rng.integers(0, len(BORDERS)))],
-                layout=LAYOUTS[int(rng.integers(0, len(LAYOUTS)))], window=window, with_mask=with_mask, out16=bool(rng.random() < 0.5), gain=gain,
+                layout="device" if cls == "captured" else LAYOUTS[int(rng.integers(0, len(LAYOUTS)))], window=window, with_mask=with_mask, out16=bool(rng.random() < 0.5), gain=gain,
                 img_seed=int(rng.integers(0, 2 ** 31)))
 
 
@@ -107,6 +116,26 @@ def _place(a, layout, pad=3):
 
 def _np(a):
     return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+
+
+def _capture_and_replay(warper, call, overwrite, outs):
+    """call() captured once on a side stream (nothing runs), the inputs overwritten and the outputs cleared, then one replay."""
+    import gc
+    import torch
+    st = torch.cuda.Stream()
+    st.wait_stream(torch.cuda.current_stream())
+    warper.set_stream(st)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    gc.collect()          # a graph a dead cycle still holds must not be destroyed (a device synchronisation) inside the capture
+    with torch.cuda.graph(g, stream=st, capture_error_mode="relaxed"):
+        call()
+    overwrite()
+    for o in outs:
+        o.zero_()
+    torch.cuda.synchronize()
+    g.replay()
+    torch.cuda.synchronize()
 
 
 def run_case(c):
@@ -129,12 +158,21 @@ def run_case(c):
     sane = mroi[2] >= mroi[0] and mroi[3] >= mroi[1] and mroi[2] - mroi[0] < 65536 and mroi[3] - mroi[1] < 65536
     win = c["window"] or (PC.window_of(mroi) if sane else (-61, -50, 66, 45))
     xm, ym = m.build_maps(win)
+    captured = c["cls"] == "captured"
+    if captured:
+        import torch
     if c["entry"] == "maps":
         like = None
         if c["layout"] == "device":
             import torch
             like = torch.empty(1, device="cuda")
-        gx, gy = warper.buildMapsRoi(K, R, win, like=like)
+        if captured:
+            gx, gy = torch.full(xm.shape, 7.0, device="cuda"), torch.full(xm.shape, 7.0, device="cuda")
+            mx, my = as_mat(gx), as_mat(gy)
+            _capture_and_replay(warper, lambda: check(warper._lib.isx_warper_build_maps_roi(warper._h, f9(K)[1], f9(R)[1], (C.c_int * 4)(*win), C.byref(mx), C.byref(my))),
+                                lambda: None, [gx, gy])
+        else:
+            gx, gy = warper.buildMapsRoi(K, R, win, like=like)
         if not (PC.same_bits(_np(gx), xm) and PC.same_bits(_np(gy), ym)):
             bad.append("maps of %s differ" % (win,))
         return bad
@@ -142,14 +180,23 @@ def run_case(c):
     if c["entry"] == "warp":
         src = PC.image(rng, h, w, c["cn"], np.dtype(c["dtype"]).type)
         interp, border = c["interp"], c["border"]
-        want = I.remap(src, xm, ym, interp, border) if (interp & PC.TIES_EVEN or border == PC.WRAP) else O.remap(src, xm, ym, interp, border)
         dst = _place(np.zeros(xm.shape + src.shape[2:], src.dtype), c["layout"])
-        got = _np(warper.warp_roi(_place(src, c["layout"]), K, R, interp, border, win, dst))
+        if captured:
+            s, src = _place(src, "device"), PC.image(rng, h, w, c["cn"], np.dtype(c["dtype"]).type)      # the replay reads the second image
+            _capture_and_replay(warper, lambda: warper.warp_roi(s, K, R, interp, border, win, dst), lambda: s.copy_(torch.from_numpy(src)), [dst])
+            got = _np(dst)
+        else:
+            got = _np(warper.warp_roi(_place(src, c["layout"]), K, R, interp, border, win, dst))
+        want = I.remap(src, xm, ym, interp, border) if (interp & PC.TIES_EVEN or border == PC.WRAP) else O.remap(src, xm, ym, interp, border)
         if not np.array_equal(got, want):
             bad.append("warp of %s differs at %s" % (win, np.argwhere(got != want)[:3].tolist()))
         return bad
     img = PC.image(rng, h, w)
     holes = (rng.integers(0, 4, (h, w)) > 0).astype(np.uint8) * 255
+    first = (img, holes)
+    if captured:                          # captured on `first`, replayed on these
+        img = PC.image(rng, h, w)
+        holes = (rng.integers(0, 4, (h, w)) > 0).astype(np.uint8) * 255
     wi = O.remap(img, xm, ym, PC.LINEAR, PC.REFLECT)
     wm = O.remap(holes if c["with_mask"] else np.full((h, w), 255, np.uint8), xm, ym, PC.NEAREST, PC.CONST)
     if c["gain"] != 1.0:
@@ -157,11 +204,22 @@ def run_case(c):
     warper.set_gain(c["gain"])
     di = _place(np.zeros(xm.shape + (3,), np.int16 if c["out16"] else np.uint8), c["layout"])
     dm = _place(np.zeros(xm.shape, np.uint8), c["layout"])
-    s, hm = _place(img, c["layout"]), (_place(holes, c["layout"]) if c["with_mask"] else None)
+    s, hm = _place(first[0], c["layout"]), (_place(first[1], c["layout"]) if c["with_mask"] else None)
     mi, mdi, mdm = as_mat(s), as_mat(di), as_mat(dm)
     mh = as_mat(hm) if hm is not None else None
-    check(warper._lib.isx_warper_warp_with_mask_roi(warper._h, C.byref(mi), C.byref(mh) if mh is not None else None, f9(K)[1], f9(R)[1],
-                                                    (C.c_int * 4)(*win), C.byref(mdi), C.byref(mdm)))
+
+    def fused():
+        check(warper._lib.isx_warper_warp_with_mask_roi(warper._h, C.byref(mi), C.byref(mh) if mh is not None else None, f9(K)[1], f9(R)[1],
+                                                        (C.c_int * 4)(*win), C.byref(mdi), C.byref(mdm)))
+
+    def overwrite():
+        s.copy_(torch.from_numpy(img))
+        if hm is not None:
+            hm.copy_(torch.from_numpy(holes))
+    if captured:
+        _capture_and_replay(warper, fused, overwrite, [di, dm])
+    else:
+        fused()
     if not np.array_equal(_np(di), wi.astype(_np(di).dtype)):
         bad.append("fused image of %s differs" % (win,))
     if not np.array_equal(_np(dm), wm):
