@@ -2,10 +2,12 @@
 """The reference demo's post-registration stage on one pair of images, every step on the GPU through imagestitch_amd
 (needs an MI355X):
 
-    python examples/stitch_pair.py [left.bmp right.bmp] [--focal F] [--yaw RAD] [--warper cylindrical|spherical|plane] [--blend feather|multiband] [--seam-megapix M] [--out pano.bmp | pano.jpg]
+    python examples/stitch_pair.py [left.bmp right.bmp] [--register] [--focal F] [--yaw RAD] [--warper cylindrical|spherical|plane] [--blend feather|multiband] [--seam-megapix M] [--out pano.bmp | pano.jpg]
 
-Registration (features, matching, bundle adjustment — out of scope of this library) is replaced by a known rig: two cameras
+By default registration is replaced by a known rig: two cameras
 with focal length F rotated by -/+ yaw about the vertical axis.  Without input files a synthetic pair is generated.
+With --register nothing is supplied from outside: OrbFeaturesFinder (F:948-1017), BestOf2NearestMatcher (M:307-308, R:830-911) and
+HomographyBasedEstimator (C:246-284) take the two images to the cameras the warp uses, from image files to pano.bmp.
 
 Steps = the reference's main(): warp image + mask (W:223-233), gain apply with given gains (W:241-244) - or, with
 --estimate-gains, the compensator's feed on the warped tiles (W:238-240) and its apply (W:241-244): --compensator gain is the
@@ -27,6 +29,8 @@ from imagestitch_amd import synth  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("images", nargs="*")
+    ap.add_argument("--register", action="store_true",
+                    help="find ORB features, match them and estimate the cameras on the GPU instead of assuming the rig of --focal and --yaw")
     ap.add_argument("--focal", type=float, default=None)
     ap.add_argument("--yaw", type=float, default=0.18)
     ap.add_argument("--warper", default="cylindrical", choices=["cylindrical", "spherical", "plane", "fisheye", "stereographic"],
@@ -59,24 +63,40 @@ def main():
     a = ap.parse_args()
     if a.images:
         imgs = [isx.imread(p) for p in a.images[:2]]                       # W:166
+    elif a.register:                                                        # two views of one scene: overlapping crops
+        wide = synth.make_tile(720, 1600, 0)
+        imgs = [np.ascontiguousarray(wide[:, :1280]), np.ascontiguousarray(wide[:, 320:])]
     else:
         imgs = [synth.make_tile(720, 1280, i) for i in range(2)]
     H, W = imgs[0].shape[:2]
-    F = a.focal or 1.1 * W
-    K, Rs = synth.camera_pair(W, H, F, yaw=a.yaw)
+    if a.register:
+        features = isx.OrbFeaturesFinder().find(imgs)                       # F:1034-1040: finder(img, features)
+        matcher = isx.BestOf2NearestMatcher(match_conf=0.3)                 # M:307
+        info = matcher.match([f.descriptors for f in features], [f.keypoints for f in features], [f.img_size for f in features])   # M:308
+        if not info or info[0].H is None:
+            sys.exit("registration failed: %s keypoints, %d matches" % ([int(f.keypoints.shape[0]) for f in features], info[0].matches.shape[0] if info else 0))
+        cameras = isx.HomographyBasedEstimator()([f.img_size for f in features], matcher)      # C:246-284
+        F = float(np.median([c.focal for c in cameras]))                    # W:207-216: the warper's scale is the median focal
+        Kl, Rs = [c.K32 for c in cameras], [c.R32 for c in cameras]
+        print("registered: keypoints %s, %d matches, %d inliers, focals %s" % ([int(f.keypoints.shape[0]) for f in features], info[0].matches.shape[0],
+                                                                             info[0].num_inliers, ["%.1f" % c.focal for c in cameras]))
+    else:
+        F = a.focal or 1.1 * W
+        K, Rs = synth.camera_pair(W, H, F, yaw=a.yaw)
+        Kl = [K, K]
     creator = {"cylindrical": isx.CylindricalWarper, "spherical": isx.SphericalWarper, "plane": isx.PlaneWarper, "fisheye": isx.FisheyeWarper,
                "stereographic": isx.StereographicWarper}[a.warper]          # B:91-95
     warper = creator().create(F)                                            # W:217-222
     corners, warped, wmasks = [], [], []
     for i in range(2):
         if a.estimate_gains:                                                # the gains are not known before the warp: apply comes after feed
-            c, wi, wm = warper.warp_with_mask(imgs[i], K, Rs[i])           # W:229, W:232
+            c, wi, wm = warper.warp_with_mask(imgs[i], Kl[i], Rs[i])           # W:229, W:232
         elif a.separate:
-            c, wi, wm = warper.warp_with_mask(imgs[i], K, Rs[i])           # W:229, W:232
+            c, wi, wm = warper.warp_with_mask(imgs[i], Kl[i], Rs[i])           # W:229, W:232
             isx.gain_apply(wi, a.gains[i])                                  # W:241-244
         else:                                                               # W:241-244 folded into the warp's store (gains known: a fixed rig)
             warper.set_gain(a.gains[i])
-            c, wi, wm = warper.warp_with_mask(imgs[i], K, Rs[i])           # W:229, W:232
+            c, wi, wm = warper.warp_with_mask(imgs[i], Kl[i], Rs[i])           # W:229, W:232
         corners.append(tuple(c)); warped.append(wi); wmasks.append(wm)
     if a.estimate_gains:
         compensator = isx.BlocksGainCompensator() if a.compensator == "gain_blocks" else isx.GainCompensator()   # W:238
@@ -103,13 +123,14 @@ def main():
         # K and the warper's scale multiplied by the same factor; the small seam masks come back to full size in the compose loop below
         seam_scale = min(1.0, float(np.sqrt(a.seam_megapix * 1e6 / (W * H))))
         small = [isx.resize(im, fx=seam_scale, fy=seam_scale) for im in imgs]
-        Ks = K.copy()
-        for r, c in ((0, 0), (0, 2), (1, 1), (1, 2)):
-            Ks[r, c] = np.float32(Ks[r, c] * np.float32(seam_scale))
+        Ks = [np.array(k, np.float32) for k in Kl]
+        for k in Ks:
+            for r, c in ((0, 0), (0, 2), (1, 1), (1, 2)):
+                k[r, c] = np.float32(k[r, c] * np.float32(seam_scale))
         small_warper = creator().create(float(np.float32(F) * np.float32(seam_scale)))
         small_corners, small_warped, seam = [], [], []
         for i in range(2):
-            c, wi, wm = small_warper.warp_with_mask(small[i], Ks, Rs[i])
+            c, wi, wm = small_warper.warp_with_mask(small[i], Ks[i], Rs[i])
             small_corners.append(tuple(c)); small_warped.append(wi); seam.append(wm)
         find(small_warped, small_corners, seam)
         print("seam scale %.4f: sources %d x %d, warped tiles %s" % (seam_scale, small[0].shape[1], small[0].shape[0], [(w.shape[1], w.shape[0]) for w in small_warped]))

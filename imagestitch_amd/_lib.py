@@ -11,6 +11,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libimagestitch_hip.so")
 
 # ---- enums (numeric values of include/imagestitch_hip.h == OpenCV's) -------------------------
 ISX_8UC1, ISX_8UC3, ISX_16SC3, ISX_32FC1, ISX_32FC3 = 0, 16, 19, 5, 21
+ISX_8UC4 = 24              # a BGRA source image: isx_orb_find only
 ISX_32SC1 = 4
 ISX_64FC1 = 6              # MatchesInfo::H and confidence: isx_find_homography only
 INTER_NEAREST, INTER_LINEAR = 0, 1
@@ -112,6 +113,12 @@ _SIGS = {
     "isx_voronoi_seam_find": [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _MP, C.c_int, C.c_void_p],
     "isx_voronoi_seam_reserve": [C.c_int, C.c_int, C.c_int],
     "isx_voronoi_seam_release": [],
+    "isx_orb_default_params": [C.c_void_p],
+    "isx_orb_capacity": [C.c_void_p, _IP],
+    "isx_orb_default_pattern": [_MP],
+    "isx_orb_find": [_MP, C.c_void_p, _MP, _MP, _MP, _MP, _MP, C.c_int, C.c_void_p],
+    "isx_orb_reserve": [C.c_void_p, C.c_int, C.c_int, C.c_int],
+    "isx_orb_release": [],
     "isx_match_features": [C.c_int, _MP, _MP, _IP, C.c_int, _IP, C.c_float, _MP, _MP, _MP, _MP, _IP, C.c_int, C.c_void_p],
     "isx_match_release": [],
     "isx_find_homography": [C.c_int, _MP, _MP, C.c_double, C.c_int, C.c_double, C.c_int, C.c_int, _MP, _MP, _MP, _MP, _IP, C.c_int, C.c_void_p],
@@ -228,7 +235,7 @@ def f9(a):
     return arr, arr.ctypes.data_as(_F9)
 
 
-_NP_TYPES = {("uint8", 1): ISX_8UC1, ("uint8", 3): ISX_8UC3, ("int16", 3): ISX_16SC3, ("float32", 1): ISX_32FC1, ("float32", 3): ISX_32FC3, ("int32", 1): ISX_32SC1,
+_NP_TYPES = {("uint8", 1): ISX_8UC1, ("uint8", 3): ISX_8UC3, ("uint8", 4): ISX_8UC4, ("int16", 3): ISX_16SC3, ("float32", 1): ISX_32FC1, ("float32", 3): ISX_32FC3, ("int32", 1): ISX_32SC1,
              ("float64", 1): ISX_64FC1}
 
 

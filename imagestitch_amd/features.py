@@ -1,0 +1,109 @@
+"""The reference's features finder (F = its 特征点检测 demo): OrbFeaturesFinder(grid_size, n_features, scaleFactor, nlevels) and
+find(image, features) (F:40-44, F:948-1017) on the GPU (isx_orb_find, DESIGN.md §8 "Features finder").  The sampling pattern is an input: the
+default is makeRandomPattern(31) (F:709-718); a caller who has OpenCV's learned table passes it through set_pattern."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import IsxMat, as_mat, check
+from .matcher import _allocator, _is_device, _synchronize
+
+# ISX_ORB_* of include/imagestitch_hip.h
+MAX_LEVELS, CAND_TIE_ROOM, KEEP_TIE_ROOM, MAX_CANDIDATES = 8, 256, 32, 4096
+TRUNCATED, BAD_PATTERN = 1, 2
+HARRIS_SCORE, FAST_SCORE = 0, 1
+
+
+class OrbParams(C.Structure):
+    """isx_orb_params"""
+    _fields_ = [("grid_width", C.c_int), ("grid_height", C.c_int), ("n_features", C.c_int), ("scale_factor", C.c_float), ("nlevels", C.c_int),
+                ("edge_threshold", C.c_int), ("first_level", C.c_int), ("wta_k", C.c_int), ("score_type", C.c_int), ("patch_size", C.c_int),
+                ("fast_threshold", C.c_int)]
+
+
+def default_params():
+    p = OrbParams()
+    check(_lib.load().isx_orb_default_params(C.byref(p)))
+    return p
+
+
+def capacity(params):
+    """isx_orb_capacity: the rows the outputs of a find need"""
+    n = C.c_int()
+    check(_lib.load().isx_orb_capacity(C.byref(params), C.byref(n)))
+    return n.value
+
+
+def default_pattern():
+    """isx_orb_default_pattern: the 512 x 2 int32 points a None pattern means"""
+    out = np.empty((512, 2), np.int32)
+    check(_lib.load().isx_orb_default_pattern(C.byref(as_mat(out))))
+    return out
+
+
+def orb_find(image, params, keypoints, meta, descriptors, count_status, pattern=None, device=0, stream=None):
+    """isx_orb_find on caller-allocated outputs: keypoints cap x 2 and meta cap x 4 float32, descriptors cap x 32 uint8, count_status 1 x 2
+    int32, NumPy arrays or CUDA tensors; image: uint8 HxW, HxWx3 or HxWx4."""
+    ptr = getattr(stream, "cuda_stream", stream)
+    check(_lib.load().isx_orb_find(C.byref(as_mat(image)), C.byref(params), None if pattern is None else C.byref(as_mat(pattern)),
+                                   C.byref(as_mat(keypoints)), C.byref(as_mat(meta)), C.byref(as_mat(descriptors)), C.byref(as_mat(count_status)),
+                                   int(device), C.c_void_p(ptr or 0)))
+
+
+def orb_reserve(params, width, height, device=0):
+    """isx_orb_reserve: size the calling thread's scratch (and upload the default pattern) ahead of a stream capture"""
+    check(_lib.load().isx_orb_reserve(C.byref(params), int(width), int(height), int(device)))
+
+
+class ImageFeatures:
+    """detail::ImageFeatures as find fills it: img_idx, img_size (width, height), keypoints n x 2 float32 (pt.x, pt.y), meta n x 4 float32
+    (size, angle, response, octave), descriptors n x 32 uint8 - row-sliced views of the finder's mats, in canonical order (cell, level, y, x) -
+    and status (ISX_ORB_TRUNCATED | ISX_ORB_BAD_PATTERN)."""
+
+    def __init__(self, img_idx, img_size, keypoints, meta, descriptors, status):
+        self.img_idx, self.img_size, self.keypoints, self.meta, self.descriptors, self.status = img_idx, img_size, keypoints, meta, descriptors, status
+
+
+class OrbFeaturesFinder:
+    """OrbFeaturesFinder(Size grid_size = Size(3, 1), int nfeatures = 1500, float scaleFactor = 1.3f, int nlevels = 5) (F:40-54)."""
+
+    def __init__(self, grid=(3, 1), n_features=1500, scale_factor=1.3, nlevels=5, device=0, stream=None):
+        p = default_params()
+        p.grid_width, p.grid_height, p.n_features, p.scale_factor, p.nlevels = int(grid[0]), int(grid[1]), int(n_features), float(scale_factor), int(nlevels)
+        self.params, self.device, self.stream = p, device, stream
+        self.pattern = None
+        self.capacity = capacity(p)
+
+    def set_pattern(self, pattern):
+        """A 512 x 2 int32 array or CUDA tensor of (x, y) points inside the 31 x 31 patch (OpenCV's bit_pattern_31_, say); None: the default."""
+        self.pattern = pattern
+
+    def find(self, images):
+        """find(image, features) for every image (uint8 HxW, HxWx3 or HxWx4; NumPy arrays or CUDA tensors): one ImageFeatures each.  With a
+        CUDA image the outputs are CUDA tensors.  All counts are read back in one synchronisation."""
+        out = []
+        for i, img in enumerate(images):
+            alloc = _allocator("cuda:%d" % int(self.device) if _is_device(img) else None)
+            cap = max(self.capacity, 1)
+            kp, meta, desc, cs = alloc(cap, 2, np.float32), alloc(cap, 4, np.float32), alloc(cap, 32, np.uint8), alloc(1, 2, np.int32)
+            orb_find(img, self.params, kp, meta, desc, cs, self.pattern, self.device, self.stream)
+            out.append((i, (int(img.shape[1]), int(img.shape[0])), kp, meta, desc, cs))
+        if any(_is_device(o[5]) for o in out):
+            _synchronize(self.stream, self.device)
+        feats = []
+        for i, size, kp, meta, desc, cs in out:
+            c = cs.cpu().numpy()[0] if _is_device(cs) else cs[0]
+            n = int(c[0])
+            feats.append(ImageFeatures(i, size, kp[:n], meta[:n], desc[:n], int(c[1])))
+        return feats
+
+    __call__ = find
+
+    def reserve(self, width, height):
+        orb_reserve(self.params, width, height, self.device)
+
+    @staticmethod
+    def release():
+        """Return the scratch the finder keeps per calling thread between calls (isx_orb_release)."""
+        check(_lib.load().isx_orb_release())

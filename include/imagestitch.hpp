@@ -382,6 +382,56 @@ struct MatchesInfo {
     int status = 0;                               // the ISX_HOMOGRAPHY_* bits of the pair
 };
 
+// The features finder of the F demo (F = the reference's 特征点检测 demo): OrbFeaturesFinder(grid_size, nfeatures, scaleFactor, nlevels) and
+// find(image, features) (F:40-54, F:948-1017) on the GPU (isx_orb_find; tests/helpers/orb_np.py is the specification, DESIGN.md §8 "Features
+// finder").  Keypoints come in canonical order (cell, level, y, x).  The sampling pattern is an input: the default is makeRandomPattern(31)
+// (F:709-718); setPattern takes a CV_32SC1 512 x 2 mat of (x, y) inside the 31 x 31 patch - OpenCV's learned table, for a caller who has it.
+struct KeyPoint { Point2f pt; float size = 0.f, angle = -1.f, response = 0.f; int octave = 0; };      // cv::KeyPoint as find fills it
+class OrbFeaturesFinder {
+public:
+    explicit OrbFeaturesFinder(Size grid_size = Size(3, 1), int nfeatures = 1500, float scaleFactor = 1.3f, int nlevels = 5, int device = 0, void* hip_stream = nullptr)
+        : device_(device), stream_(hip_stream) {
+        check(isx_orb_default_params(&params_));
+        params_.grid_width = grid_size.width; params_.grid_height = grid_size.height; params_.n_features = nfeatures; params_.scale_factor = scaleFactor;
+        params_.nlevels = nlevels;
+        check(isx_orb_capacity(&params_, &capacity_));
+    }
+    void setStream(void* hip_stream) { stream_ = hip_stream; }
+    void setPattern(const Mat& pattern) { pattern_ = pattern; }
+    int capacity() const { return capacity_; }
+    int status() const { return status_; }        // of the last find: ISX_ORB_TRUNCATED | ISX_ORB_BAD_PATTERN
+    const isx_orb_params& params() const { return params_; }
+    // find(image, features) (F:948): image CV_8UC1, CV_8UC3 or CV_8UC4, host or device.  features.keypoints holds pt, features.descriptors
+    // n x 32 CV_8UC1 on the host; `full`, when given, the whole cv::KeyPoint of each.
+    void find(const Mat& image, ImageFeatures& features, std::vector<KeyPoint>* full = nullptr) {
+        const int cap = capacity_ > 0 ? capacity_ : 1;
+        Mat kp(cap, 2, ISX_32FC1), meta(cap, 4, ISX_32FC1), desc(cap, 32, ISX_8UC1), cs(1, 2, ISX_32SC1);
+        check(isx_orb_find(image.c(), &params_, pattern_.empty() ? nullptr : pattern_.c(), kp.c(), meta.c(), desc.c(), cs.c(), device_, stream_));
+        const int n = cs.ptr<int>(0)[0];
+        status_ = cs.ptr<int>(0)[1];
+        features.img_size = image.size();
+        features.keypoints.clear();
+        if (full) full->clear();
+        features.descriptors = Mat();
+        if (n > 0) features.descriptors.create(n, 32, ISX_8UC1);
+        for (int r = 0; r < n; ++r) {
+            const float* p = kp.ptr<float>(r);
+            const float* m = meta.ptr<float>(r);
+            features.keypoints.push_back(Point2f(p[0], p[1]));
+            std::memcpy(features.descriptors.ptr<unsigned char>(r), desc.ptr<unsigned char>(r), 32);
+            if (full) { KeyPoint k; k.pt = Point2f(p[0], p[1]); k.size = m[0]; k.angle = m[1]; k.response = m[2]; k.octave = (int)m[3]; full->push_back(k); }
+        }
+    }
+    void operator()(const Mat& image, ImageFeatures& features) { find(image, features); }
+    void reserve(Size image_size) { check(isx_orb_reserve(&params_, image_size.width, image_size.height, device_)); }
+    static void release() { check(isx_orb_release()); }
+private:
+    isx_orb_params params_;
+    Mat pattern_;
+    int capacity_ = 0, status_ = 0, device_;
+    void* stream_;
+};
+
 class FeaturesMatcher {
 public:
     explicit FeaturesMatcher(float match_conf = 0.3f, int device = 0, void* hip_stream = nullptr) : conf_(match_conf), device_(device), stream_(hip_stream) {}

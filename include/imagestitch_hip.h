@@ -49,6 +49,7 @@ typedef enum {
 enum {
     ISX_8UC1 = 0,   /* CV_8UC1  : masks (W:213-214,232)                                       */
     ISX_8UC3 = 16,  /* CV_8UC3  : source and warped images (W:166-169,229)                    */
+    ISX_8UC4 = 24,  /* CV_8UC4  : a BGRA source image (F:959-960): isx_orb_find only          */
     ISX_16SC3 = 19, /* CV_16SC3 : Blender::feed input / blend output (W:294,302,313)          */
     ISX_32SC1 = 4,  /* CV_32SC1 : the seam finder's label image labels_ (S:83)                    */
     ISX_32FC1 = 5,  /* CV_32FC1 : xmap / ymap (W:128-129)                                     */
@@ -629,6 +630,79 @@ int isx_voronoi_seam_reserve(int max_roi_width, int max_roi_height, int device);
 /* Returns the scratch and the staged host masks of the calling thread (the finder going out of scope, S:1192).  PER THREAD and not
  * freed at thread exit, as for isx_dp_seam_release.                                                                                    */
 int isx_voronoi_seam_release(void);
+
+/* ---- the features finder of the F demo (F = the reference's 特征点检测/特征点检测/特征点检测.cpp) --------------------------------- */
+/* Limits and room (orb.hip takes them from here; tests/helpers/orb_np.py repeats them): pyramid levels; the ties a (cell, level) keeps past
+ * 2 n_l candidates after the first cut and past n_l keypoints after the final one; the candidates one workgroup ranks; (cell, level)
+ * layers; pixels a side.                                                                                                                */
+enum { ISX_ORB_MAX_LEVELS = 8, ISX_ORB_CAND_TIE_ROOM = 256, ISX_ORB_KEEP_TIE_ROOM = 32, ISX_ORB_MAX_CANDIDATES = 4096,
+       ISX_ORB_MAX_LAYERS = 1024, ISX_ORB_MAX_SIDE = 16384 };
+/* status bits of count_status[1] */
+enum { ISX_ORB_TRUNCATED = 1,     /* a set had more ties at its cut than room: the first in canonical order were kept            */
+       ISX_ORB_BAD_PATTERN = 2 }; /* a DEVICE pattern holds a point with |x| or |y| > 15: count is 0 and no row is written      */
+enum { ISX_ORB_HARRIS_SCORE = 0, ISX_ORB_FAST_SCORE = 1 };      /* cv::ORB::HARRIS_SCORE, FAST_SCORE */
+/* OrbFeaturesFinder(grid_size, n_features, scaleFactor, nlevels) (F:40-44) and the ORB::create arguments F:45-54 fixes. */
+typedef struct isx_orb_params {
+    int   grid_width, grid_height; /* F:54: Size(3, 1)                                                                      */
+    int   n_features;              /* 1500; a cell finds n_features * (99 + area) / 100 / area (F:43): 510                  */
+    float scale_factor;            /* 1.3f, widened to double as `double scaleFactor = 1.3f` does (F:45); > 1                */
+    int   nlevels;                 /* 5 (F:46); 1 .. ISX_ORB_MAX_LEVELS                                                     */
+    int   edge_threshold;          /* 31 (F:47)   other values: ISX_ERR_UNSUPPORTED                                         */
+    int   first_level;             /* 0 (F:48)    other values: ISX_ERR_UNSUPPORTED                                         */
+    int   wta_k;                   /* 2 (F:49)    other values: ISX_ERR_UNSUPPORTED                                         */
+    int   score_type;              /* ISX_ORB_HARRIS_SCORE (F:50); FAST_SCORE: ISX_ERR_UNSUPPORTED                          */
+    int   patch_size;              /* 31 (F:51)   other values: ISX_ERR_UNSUPPORTED                                         */
+    int   fast_threshold;          /* 20 (F:52); 1 .. 254                                                                   */
+} isx_orb_params;
+/* The defaults above. */
+int isx_orb_default_params(isx_orb_params* params);
+/* The rows a call's outputs need: cells * sum over levels of (n_l + ISX_ORB_KEEP_TIE_ROOM), n_l as F:72-82 gives it.  The parameter checks
+ * of isx_orb_find. */
+int isx_orb_capacity(const isx_orb_params* params, int* capacity);
+/* makeRandomPattern(31) (F:709-718) on the restated cv::RNG of isx_find_homography, seed 0x34985739: 512 (x, y) points into a HOST CV_32SC1
+ * mat of at least 512 x 2.  It is what a NULL pattern means.  The reference's learned table bit_pattern_31_ (F:355-706) exists as program
+ * text only and is not part of this library: a caller who has OpenCV passes it as `pattern`.                                              */
+int isx_orb_default_pattern(isx_mat* pattern);
+/* OrbFeaturesFinder::find (F:948-1017) = per grid cell detectAndCompute (F:727-946): computeKeyPoints (F:56-191), HarrisResponses
+ * (F:204-246), ICAngles (F:250-283), computeOrbDescriptors (F:287-353).  The specification is tests/helpers/orb_np.py, which the kernels
+ * match bit for bit (DESIGN.md §8 "Features finder" lists what is restated, decided and unpinned):
+ *   gray        (B*1868 + G*9617 + R*4899 + 8192) >> 14 (F:956-964); CV_8UC1 passes through, CV_8UC4 ignores alpha.
+ *   cells       F:984-987's integer bounds; every cell is found on its own and xl, yl are added to pt afterwards (F:1006-1007).
+ *   pyramid     layer l is cvRound(cols / scale) x cvRound(rows / scale), scale = (float)pow(scaleFactor, l) (F:792-794), resized from layer
+ *               l - 1 by isx_resize's INTER_LINEAR on CV_8U (F:834 asks for INTER_LINEAR_EXACT: a departure).  No border is built (F:842-851):
+ *               every keypoint lies 31 px inside its layer and no reader goes further than 25.
+ *   FAST        FastFeatureDetector::create(fast_threshold, true) (F:118-119) restated: score = max(a, -b) - 1 over the 16 arcs of 9, a corner
+ *               where score >= threshold, kept where its score is strictly greater than its 8 neighbours'.
+ *   cuts        runByImageBorder(31) (F:123), retainBest(2 n_l) by FAST score (F:126), Harris block 7, k = 0.04f (F:155), retainBest(n_l)
+ *               (F:172); retainBest keeps every point >= the n-th largest.  Points strictly above a cut always fit; its ties fill
+ *               ISX_ORB_CAND_TIE_ROOM / ISX_ORB_KEEP_TIE_ROOM rows in canonical order; dropped ties set ISX_ORB_TRUNCATED.
+ *   angle       the moments of F:261-280 through the restated atan2f (csrc/proj_math.hpp) in degrees, [0, 360) (F:281 calls fastAtan2).
+ *   descriptor  F:299-352 on the layer blurred 7 x 7, sigma 2 in exact integers (F:936; Q8 taps 18 34 49 54 49 34 18), the restated
+ *               cosf / sinf, WTA_K = 2, 32 bytes.
+ *   order       cell (row-major), level, y, x.  (OpenCV's own order is what nth_element leaves.)
+ *   image        CV_8UC1, CV_8UC3 or CV_8UC4, host or device, any pointer alignment and step, 1 .. ISX_ORB_MAX_SIDE pixels a side.
+ *   pattern      NULL, or a CV_32SC1 mat of 512 x 2, host or device, 4-byte aligned.  A host pattern with |x| or |y| > 15 is refused
+ *                (ISX_ERR_INVALID); a device pattern is checked by the kernel that reads it (ISX_ORB_BAD_PATTERN).
+ *   keypoints    CV_32FC1, at least cap x 2: pt.x, pt.y - the layout isx_match_features takes.      cap = isx_orb_capacity(params)
+ *   meta         CV_32FC1, at least cap x 4: size (31 scale), angle, response (Harris), octave.
+ *   descriptors  CV_8UC1, at least cap x 32, any pointer alignment and step.
+ *   count_status CV_32SC1, at least 1 x 2: the number of keypoints, the status bits.  Rows from count on are not written.
+ * keypoints, meta and count_status are 4-byte aligned in pointer and step.  Checked before anything is written or enqueued: null pointers,
+ * a parameter out of range, a grid finer than the image, a misaligned mat, a bad host pattern -> ISX_ERR_INVALID; the parameters F fixes at
+ * another value, more than ISX_ORB_MAX_CANDIDATES candidates a layer (2 n_0 + ISX_ORB_CAND_TIE_ROOM), more than ISX_ORB_MAX_LAYERS layers,
+ * a side past ISX_ORB_MAX_SIDE -> ISX_ERR_UNSUPPORTED; a mat of another type -> ISX_ERR_TYPE; an empty image, a pattern that is not
+ * 512 x 2, too few rows or columns -> ISX_ERR_SIZE.
+ * With device mats throughout nothing is read back or synchronised: count_status stays on the device.  Host mats synchronise.  On a
+ * capturing stream the call works with device mats once isx_orb_reserve has sized the scratch (the default pattern then lies there); a host
+ * mat, or a call that would have to grow the scratch, -> ISX_ERR_STATE with nothing enqueued.  The launch count depends on nlevels only.  */
+int isx_orb_find(const isx_mat* image, const isx_orb_params* params, const isx_mat* pattern, isx_mat* keypoints, isx_mat* meta,
+                 isx_mat* descriptors, isx_mat* count_status, int device, void* hip_stream);
+/* Sizes the calling thread's scratch for device images of up to width x height under `params` and uploads the default pattern, ahead of a
+ * stream capture.  A captured graph keeps pointing at this scratch: growing or releasing it while such a graph exists is the caller's
+ * error.                                                                                                                                  */
+int isx_orb_reserve(const isx_orb_params* params, int width, int height, int device);
+/* Returns the scratch of the calling thread.  PER THREAD and not freed at thread exit, as for isx_match_release.                          */
+int isx_orb_release(void);
 
 /* ---- the features matcher of the M demo (M = the reference's 特征点匹配/特征点匹配/特征点匹配.cpp) --------------------------------- */
 /* The tiling of the search kernel (match.hip takes them from here; imagestitch_amd/matcher.py repeats them): queries per block, train rows
