@@ -24,6 +24,7 @@ f32 = np.float32
 EDGE, PATCH, HALF_PATCH, HARRIS_BLOCK = 31, 31, 15, 7
 CAND_TIE_ROOM, KEEP_TIE_ROOM = 256, 32          # ISX_ORB_CAND_TIE_ROOM, ISX_ORB_KEEP_TIE_ROOM
 MAX_LEVELS, MAX_CANDIDATES = 8, 4096            # ISX_ORB_MAX_LEVELS, ISX_ORB_MAX_CANDIDATES
+MAX_LAYERS, MAX_SIDE = 1024, 16384              # ISX_ORB_MAX_LAYERS, ISX_ORB_MAX_SIDE
 STATUS_TRUNCATED, STATUS_BAD_PATTERN = 1, 2     # ISX_ORB_TRUNCATED, ISX_ORB_BAD_PATTERN
 BLUR_TAPS = (18, 34, 49, 54, 49, 34, 18)
 CIRCLE = ((0, 3), (1, 3), (2, 2), (3, 1), (3, 0), (3, -1), (2, -2), (1, -3), (0, -3), (-1, -3), (-2, -2), (-3, -1), (-3, 0), (-3, 1), (-2, 2),

@@ -8,7 +8,13 @@ grid of identical dots (ties at both cuts, with and without room), periodic squa
 (nothing).  The seed draws the rest: 40 to 330 pixels a side, 1, 3 or 4 channels, a grid of 1 to 3 cells a side, 0 to 600 features, 1 to 8
 levels, the scale factor (2.0 takes the 2 x 2 area rule), the FAST threshold, host / device / strided mats and - one case in three - a
 pattern of the caller's.  Every case is compared with the model (count, status, keypoints, meta, descriptors: bits; the rows from count on
-untouched); none is skipped.  Prints one JSON line; exit status 1 on a mismatch."""
+untouched); none is skipped.  Prints one JSON line; exit status 1 on a mismatch.
+
+    python tools/fuzz_orb.py --family limits ...
+
+draws from the builders of the limit cases (tests/orb_cases.py) instead: 700 to 1920 features on one or two levels over noise or identical dots
+(more than one pass of the final cut's 1024 candidates), strips 64 to 72 pixels high under grids of up to 1024 layers (keypoints in layers
+past 256), and images of 1 to 70 pixels a side, down to cells of one pixel.  The default family is what it was, seed for seed."""
 import argparse
 import json
 import os
@@ -27,6 +33,7 @@ CLASSES = ("blobs", "noise", "dots", "squares", "flat")
 LAYOUTS = ("host", "device", "strided")
 SCALES = (1.3, 1.2, 2.0, 1.5, 1.05)
 SENTINEL = 91
+LIMIT_KINDS = ("passes", "layers", "sides")
 
 
 def make_case(seed, cls=None):
@@ -59,6 +66,43 @@ def make_case(seed, cls=None):
         pattern = rng.integers(-om.HALF_PATCH, om.HALF_PATCH + 1, (512, 2)).astype(np.int32)
     layout = LAYOUTS[(seed // len(CLASSES) + seed) % 3]
     return dict(seed=seed, cls=cls, image=img, params=params, pattern=pattern, layout=layout)
+
+
+def make_limit_case(seed, kind=None):
+    """The case of `seed` in the limits family; kind: one of LIMIT_KINDS (default: in turn)."""
+    rng = np.random.default_rng(seed)
+    kind = LIMIT_KINDS[seed % len(LIMIT_KINDS)] if kind is None else kind
+    channels = int(rng.choice([1, 1, 3, 4]))
+    if kind == "passes":
+        if rng.random() < 0.5:
+            side = int(rng.integers(200, 281))
+            img, threshold = cases.noise(side, side, seed), int(rng.choice([1, 20]))
+        else:
+            img, threshold = cases.dots(400, 400, period=6, count=[None, 1100, 1300, 2100][int(rng.integers(0, 4))]), 20
+        params = om.Params(grid=(1, 1), n_features=int(rng.integers(700, 1921)), scale_factor=float(rng.choice([1.2, 1.3])), nlevels=int(rng.integers(1, 3)),
+                           fast_threshold=threshold)
+    elif kind == "layers":
+        nlevels = int(rng.choice([8, 8, 4]))
+        cells = int(rng.integers(33, om.MAX_LAYERS // nlevels + 1)) if rng.random() < 0.4 else int(rng.integers(33, 48))
+        h, w = int(rng.integers(64, 73)), min(cells * int(rng.integers(64, 73)) + int(rng.integers(0, cells)), om.MAX_SIDE)      # cells of two widths
+        img = cases.noise(h, w, seed)
+        params = om.Params(grid=(cells, 1), n_features=cells * int(rng.choice([10, 40])), scale_factor=float(rng.choice([1.05, 1.05, 1.3])), nlevels=nlevels,
+                           fast_threshold=int(rng.choice([5, 20])))
+    else:
+        h, w = int(rng.integers(1, 71)), int(rng.integers(1, 71))
+        if rng.random() < 0.25:
+            h, w = [(h, 200), (200, w)][int(rng.integers(0, 2))]
+        img = [cases.dots_from(h, w, period=int(rng.choice([4, 8]))), cases.noise(h, w, seed), cases.flat(h, w, int(rng.integers(0, 256)))][int(rng.integers(0, 3))]
+        grid = (int(rng.integers(1, min(w, 5) + 1)), int(rng.integers(1, min(h, 3) + 1))) if rng.random() < 0.5 else (1, 1)
+        params = om.Params(grid=grid, n_features=int(rng.choice([0, 10, 100, 1500])), scale_factor=float(rng.choice(SCALES)), nlevels=int(rng.integers(1, om.MAX_LEVELS + 1)),
+                           fast_threshold=int(rng.choice([20, 5, 1])))
+    if channels > 1:
+        img = np.ascontiguousarray(np.stack([img] + [np.clip(img.astype(np.int64) + rng.integers(-9, 10, img.shape), 0, 255).astype(np.uint8) for _ in range(channels - 1)], 2))
+    pattern = rng.integers(-om.HALF_PATCH, om.HALF_PATCH + 1, (512, 2)).astype(np.int32) if seed % 4 == 1 else None
+    return dict(seed=seed, cls=kind, image=img, params=params, pattern=pattern, layout=LAYOUTS[(seed // len(LIMIT_KINDS) + seed) % 3])
+
+
+FAMILIES = {"default": (make_case, CLASSES), "limits": (make_limit_case, LIMIT_KINDS)}
 
 
 def place(a, layout, sentinel=None):
@@ -112,16 +156,17 @@ def run_case(c):
     return bad
 
 
-def run(seconds, seed, verbose=False):
-    """Draws cases (the classes in turn) for `seconds` and compares the library with the model.  Returns a summary dict."""
+def run(seconds, seed, verbose=False, family="default"):
+    """Draws cases of `family` (its classes in turn) for `seconds` and compares the library with the model.  Returns a summary dict."""
     import torch
     import imagestitch_amd
     imagestitch_amd.load()
     t0 = time.time()
-    per, failing, n = {c: 0 for c in CLASSES}, [], 0
+    make, classes = FAMILIES[family]
+    per, failing, n = {c: 0 for c in classes}, [], 0
     while time.time() - t0 < seconds:
         s = int(seed) * 1000 + n
-        c = make_case(s)
+        c = make(s)
         bad = run_case(c)
         per[c["cls"]] += 1
         n += 1
@@ -129,7 +174,7 @@ def run(seconds, seed, verbose=False):
             failing.append(dict(seed=s, cls=c["cls"], layout=c["layout"], differences=bad))
             if verbose:
                 print("MISMATCH", s, c["cls"], c["layout"], bad, flush=True)
-    return dict(tool="fuzz_orb", seconds=round(time.time() - t0, 1), seed=int(seed), cases=n, mismatches=len(failing), per_class=per, failing_seeds=failing[:20],
+    return dict(tool="fuzz_orb", family=family, seconds=round(time.time() - t0, 1), seed=int(seed), cases=n, mismatches=len(failing), per_class=per, failing_seeds=failing[:20],
                 device=torch.cuda.get_device_name(0))
 
 
@@ -138,8 +183,9 @@ def main():
     ap.add_argument("--seconds", type=float, default=60.0)
     ap.add_argument("--seed", type=int, default=20261021)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--family", choices=sorted(FAMILIES), default="default")
     a = ap.parse_args()
-    out = run(a.seconds, a.seed, verbose=True)
+    out = run(a.seconds, a.seed, verbose=True, family=a.family)
     print(json.dumps(out), flush=True)
     if a.out:
         with open(a.out, "w") as f:
