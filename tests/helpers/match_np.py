@@ -16,28 +16,61 @@ F32 = np.float32
 _POP = np.array([bin(v).count("1") for v in range(256)], np.uint8)
 
 
+BLOCK_BYTES = 32 << 20      # the largest temporary of hamming / knn2: a block of XORed rows (and its popcounts, a second one of this size)
+_Q_BLOCK = 256
+
+
+def _train_block(nq):
+    return max(1, BLOCK_BYTES // (32 * max(1, min(nq, _Q_BLOCK))))
+
+
+def _block(q, t):
+    """(len(q), len(t)) int32 distances of one block: the XOR is the temporary BLOCK_BYTES bounds."""
+    if hasattr(np, "bitwise_count"):                       # popcounts of 4 x 64 bits a row: the same integers, an eighth of the lookups
+        x = q.view(np.uint64)[:, None, :] ^ t.view(np.uint64)[None, :, :]
+        return np.bitwise_count(x).sum(axis=2, dtype=np.int32)
+    return _POP[q[:, None, :] ^ t[None, :, :]].sum(axis=2, dtype=np.int32)
+
+
+def _rows(a):
+    return np.ascontiguousarray(np.asarray(a, np.uint8).reshape(-1, 32))
+
+
 def hamming(q, t):
-    """(nq, nt) int32 Hamming distances between the rows of two n x 32 uint8 arrays."""
-    q, t = np.asarray(q, np.uint8), np.asarray(t, np.uint8)
+    """(nq, nt) int32 Hamming distances between the rows of two n x 32 uint8 arrays, in blocks over both."""
+    q, t = _rows(q), _rows(t)
     out = np.zeros((q.shape[0], t.shape[0]), np.int32)
-    for r0 in range(0, q.shape[0], 256):                   # (bounds the temporary)
-        x = q[r0:r0 + 256, None, :] ^ t[None, :, :]
-        out[r0:r0 + 256] = _POP[x].sum(axis=2, dtype=np.int32)
+    step = _train_block(q.shape[0])
+    for r0 in range(0, q.shape[0], _Q_BLOCK):
+        for c0 in range(0, t.shape[0], step):
+            out[r0:r0 + _Q_BLOCK, c0:c0 + step] = _block(q[r0:r0 + _Q_BLOCK], t[c0:c0 + step])
     return out
 
 
 def knn2(q, t):
-    """n_query x 4 int32: (row0, d0, row1, d1), the two nearest rows of t by (distance, row); -1, -1 where there is none."""
+    """n_query x 4 int32: (row0, d0, row1, d1), the two nearest rows of t by (distance, row); -1, -1 where there is none.  Blocked over
+    queries and train rows: a block's distances become keys distance << 32 | row, unique per query, and the two smallest of a block are
+    merged with the two kept so far - the order of (distance, row) whatever the blocking, as a stable sort of the whole row gives it."""
+    q, t = _rows(q), _rows(t)
     nq, nt = q.shape[0], t.shape[0]
     out = np.full((nq, 4), -1, np.int32)
     if nq == 0 or nt == 0:
         return out
-    d = hamming(q, t)
-    order = np.argsort(d, axis=1, kind="stable")[:, :2]    # stable: ties by row
-    rows = np.arange(nq)
-    out[:, 0], out[:, 1] = order[:, 0], d[rows, order[:, 0]]
-    if nt >= 2:
-        out[:, 2], out[:, 3] = order[:, 1], d[rows, order[:, 1]]
+    none = np.int64(1) << 62
+    step = _train_block(nq)
+    for r0 in range(0, nq, _Q_BLOCK):
+        qb = q[r0:r0 + _Q_BLOCK]
+        best = np.full((qb.shape[0], 2), none, np.int64)
+        for c0 in range(0, nt, step):
+            d = _block(qb, t[c0:c0 + step])
+            keys = (d.astype(np.int64) << 32) | np.arange(c0, c0 + d.shape[1], dtype=np.int64)[None, :]
+            if keys.shape[1] > 2:
+                keys = np.partition(keys, 1, axis=1)[:, :2]
+            best = np.sort(np.concatenate([best, keys], axis=1), axis=1)[:, :2]
+        for k in range(2):
+            has = best[:, k] != none
+            out[r0:r0 + _Q_BLOCK, 2 * k] = np.where(has, best[:, k] & 0xFFFFFFFF, -1)
+            out[r0:r0 + _Q_BLOCK, 2 * k + 1] = np.where(has, best[:, k] >> 32, -1)
     return out
 
 

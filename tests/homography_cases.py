@@ -132,6 +132,44 @@ def named():
     return c
 
 
+def limits():
+    """name -> points of tests/test_gpu_homography_limits.py: counts either side of two ballots of 64, 2 000 and 8 193 correspondences
+    (the scoring loop, the compaction, pass 2 and the refit over thousands of rows), a half-outlier set of 4 096 (the iteration count
+    shortens more than once) and the two exact sets either side of confidence > 3 -> 0: 240 / (8 + 0.3 * 240) = 3, 241 / 80.3 > 3.  The
+    seeds are those at which tests/test_homography_model.py finds every margin >= 1e-6."""
+    return {
+        "n127_noisy": planted(2127, 127, 114, 0.2),
+        "n128_noisy": planted(2128, 128, 115, 0.2),
+        "n129_noisy": planted(2129, 129, 116, 0.2),
+        "n2000_noisy": planted(4000, 2000, 1800, 0.3),
+        "n8193_noisy": planted(10193, 8193, 7000, 0.3),
+        "n4096_half_noisy": planted(6096, 4096, 2048, 0.5),
+        "n240_exact": exact(2240, 240),
+        "n241_exact": exact(2241, 241),
+    }
+
+
+def mixed_2016():
+    """(point sets, the names of the distinct ones per set, keyword arguments) of one call of 2 016 pairs: 34 substantive sets - named ones
+    and generated(0 .. 25) - at pairs 0, 255, 256, 257, 1 023, 2 015 and every 69th from 30, and between them, in turn, counts of 0, 1, 2
+    and 3 (below num_matches_thresh1 = 4), the two n4 sets (runKernel over the four rows: one finds H, one does not), n5 (one pass) and
+    n6_exact.  Sets that repeat are the same array, so a model run serves every place it stands at."""
+    c = named()
+    heavy = ["win_at_64", "n300_half_noisy", "collinear_40", "repeated_9x8", "outliers_to_the_end", "n65_half_noisy", "stop_at_64", "n64_exact"]
+    sets = {k: c[k][0] for k in heavy}
+    sets.update({"generated_%d" % i: generated(i) for i in range(26)})
+    substantive = list(sets)
+    light = ["n0", "n1", "n2", "n3", "n4_thresh1_4", "n4_degenerate", "n5_below_thresh1", "n6_exact"]
+    sets.update({k: c[k][0] for k in light if k in c})
+    sets.update({"n%d" % k: exact(3, 3)[:k] for k in (1, 2, 3)})
+    at = [0, 255, 256, 257, 1023, 2015] + [30 + 69 * k for k in range(28)]
+    assert len(set(at)) == len(at) == len(substantive) == 34 and max(at) == 2015
+    names = [light[k % len(light)] for k in range(2016)]
+    for k, name in zip(at, substantive):
+        names[k] = name
+    return sets, names, dict(num_matches_thresh1=4)
+
+
 def generated(index):
     """Case `index` of the seeded generator: 6 - 300 correspondences, 30 - 90 % inliers, 0 - 1 px of noise."""
     r = np.random.default_rng(20261019 + index)

@@ -411,3 +411,33 @@ def test_plan_verify_generator_and_model():
     assert PV.MUST_FLAG not in true and true.count(PV.MUST_PASS) * 4 >= len(true) * 3       # (a tile on the back seam has a border pixel within the allowance of it now and then)
     assert PV.MUST_PASS not in moved and moved.count(PV.MUST_FLAG) * 10 >= len(moved) * 9
     assert (true + moved).count(PV.NO_CLAIM) * 10 <= len(true + moved)
+
+
+def test_homography_large_class_is_drawn_and_the_older_classes_draw_what_they_drew():
+    """tools/fuzz_homography.py: a soak's first 200 cases (scheduled(): the classes in turn) hold the `large` class with counts past 300 - the
+    most any older class or test reached - up to thousands; it has a generator of its own, so case(seed, cls) of the six older classes
+    gives the bytes it gave before (digests taken from the generator as it was)."""
+    import hashlib
+    import fuzz_homography as FH
+
+    def digest(c):
+        h = hashlib.sha256()
+        for p, n in c["pairs"]:
+            h.update(np.ascontiguousarray(p).tobytes())
+            h.update(repr(int(n)).encode())
+        h.update(repr((sorted(c["kw"].items()), c["device"], c["wide"], c["spare"])).encode())
+        return h.hexdigest()[:16]
+    counts = []
+    for n in range(200):
+        s, cls = FH.scheduled(20261201, n)
+        if cls == "large":
+            c = FH.case(s, cls)
+            (pts, count), = c["pairs"]
+            assert count == len(pts) and 400 <= count <= 9000 and c["kw"] == {}
+            counts.append(count)
+    assert len(counts) >= 28 and min(counts) > 300 and max(counts) > 8192 - 1500 and sum(1 for v in counts if v > 2000) >= 10, counts
+    assert FH.CLASSES[:6] == ("tiny", "chunk_edges", "count_limits", "noisy", "degenerate", "multi")
+    want = {(1, "tiny"): "a39b4b39d9efe37e", (2, "chunk_edges"): "f57296396d7e14d2", (3, "noisy"): "baca7781bd07449b", (4, "multi"): "d5a8ec2f22e57291",
+            (5, "degenerate"): "cc51dd68cdb99d7b"}
+    assert {k: digest(FH.case(*k)) for k in want} == want
+    assert FH.lm_iters_of(7) == int(np.random.default_rng([7, 0x4C4D]).choice([1, 2, 10]))

@@ -165,6 +165,41 @@ def test_the_generators_first_200_cases_are_not_fragile():
     assert min(margins) >= 1e-7                                       # far inside: a fuzz that skips fragile cases skips next to none
 
 
+def test_the_limit_cases_are_what_their_names_say():
+    """tests/test_gpu_homography_limits.py's cases: both passes everywhere, margins far from fragile, the confidence boundary between 240
+    and 241 exact correspondences, a half-outlier set whose winner changes in turn, and - with the LM polish at 10 and 1 iterations - both
+    passes of the two largest sets iterate."""
+    from helpers import homography_lm_np as lm
+    L = cases.limits()
+    r = {k: hm.find_homography_np(p) for k, p in L.items()}
+    assert [len(L[k]) for k in ("n127_noisy", "n128_noisy", "n129_noisy", "n2000_noisy", "n8193_noisy", "n4096_half_noisy")] == [127, 128, 129, 2000, 8193, 4096]
+    for k, w in r.items():
+        assert w["stats"][0] == hm.ST_H | hm.ST_PASS2 and w["margin"] >= 1e-6, (k, w["stats"], w["margin"])
+    assert r["n240_exact"]["conf"] == 3.0 and r["n241_exact"]["conf"] == 0.0
+    assert r["n240_exact"]["stats"][1] == 240 and r["n241_exact"]["stats"][1] == 241
+    assert r["n2000_noisy"]["stats"][1] > 1700 and r["n8193_noisy"]["stats"][1] > 6900      # thousands of rows through pass 2 and the refit
+    half = r["n4096_half_noisy"]["stats"]
+    assert half[2] > 64 and half[3] > 0 and 1900 < half[1] < 2200    # more than one chunk of hypotheses; a later one took over
+    for k in ("n2000_noisy", "n8193_noisy"):
+        for iters in (10, 1):
+            w = lm.find_homography_lm_np(L[k], lm_max_iters=iters)
+            assert w["margin"] >= 1e-6 and np.array_equal(w["stats"][:7], r[k]["stats"][:7])
+            assert w["stats"][8] != 0 and w["stats"][9] > 0 and w["stats"][10] != 0 and w["stats"][11] > 0, (k, iters, w["stats"])
+            assert (w["stats"][8] == -1 and w["stats"][10] == -1) == (iters == 1)
+
+
+def test_the_2016_pair_mix_holds_what_it_says():
+    sets, names, kw = cases.mixed_2016()
+    assert len(names) == 2016 and set(names) == set(sets) and len(sets) == 42
+    heavy = [k for k, n in enumerate(names) if len(sets[n]) > 6 or n.startswith("generated")]
+    assert len(heavy) == 34 and {0, 255, 256, 257, 1023, 2015} <= set(heavy)
+    assert {"win_at_64", "n300_half_noisy", "collinear_40", "repeated_9x8", "outliers_to_the_end"} <= {names[k] for k in heavy}
+    assert sorted({len(sets[n]) for n in names if n not in {names[k] for k in heavy}}) == [0, 1, 2, 3, 4, 5, 6]
+    st = {n: hm.find_homography_np(sets[n], **kw)["stats"] for n in ("n3", "n4_thresh1_4", "n4_degenerate", "n5_below_thresh1", "n6_exact")}
+    assert st["n3"].tolist() == [0] * 8 and st["n4_thresh1_4"][0] == hm.ST_H and st["n4_degenerate"][0] == 0 and st["n4_degenerate"][3] == -1
+    assert st["n5_below_thresh1"][0] == hm.ST_H and st["n6_exact"][0] == hm.ST_H | hm.ST_PASS2
+
+
 def test_header_arity_equals_the_ctypes_signature():
     from imagestitch_amd import _lib
     text = open(os.path.join(ROOT, "include", "imagestitch_hip.h"), encoding="utf-8").read()

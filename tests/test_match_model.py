@@ -93,6 +93,69 @@ def test_knn_orders_ties_by_row_and_matches_do_not_depend_on_it():
     assert sorted(map(tuple, back[n12:])) == sorted(map(tuple, m[n12:]))      # 2->1: in order of the permuted rows
 
 
+def _hamming_whole(q, t):
+    """hamming as it was before it blocked over train rows: one lookup table, one temporary per 256 queries."""
+    q, t = np.asarray(q, np.uint8), np.asarray(t, np.uint8)
+    out = np.zeros((q.shape[0], t.shape[0]), np.int32)
+    for r0 in range(0, q.shape[0], 256):
+        out[r0:r0 + 256] = M._POP[q[r0:r0 + 256, None, :] ^ t[None, :, :]].sum(axis=2, dtype=np.int32)
+    return out
+
+
+def _knn2_whole(q, t):
+    """knn2 as it was: a stable argsort of every whole row of distances."""
+    nq, nt = q.shape[0], t.shape[0]
+    out = np.full((nq, 4), -1, np.int32)
+    if nq == 0 or nt == 0:
+        return out
+    d = _hamming_whole(q, t)
+    order = np.argsort(d, axis=1, kind="stable")[:, :2]
+    rows = np.arange(nq)
+    out[:, 0], out[:, 1] = order[:, 0], d[rows, order[:, 0]]
+    if nt >= 2:
+        out[:, 2], out[:, 3] = order[:, 1], d[rows, order[:, 1]]
+    return out
+
+
+def test_blocked_hamming_and_knn2_equal_the_whole_row_forms(monkeypatch):
+    """On the hand case, the degenerate cases (0, 1 and 2 rows, all rows identical) and a 300 x 700 random case with duplicated rows - at
+    the module's block size (one block) and at blocks of 7 queries x 9 and 1 train rows, so that ties and both neighbours cross blocks."""
+    a, b, _ = cases.hand_case()
+    pairs = [(a, b)] + [(c[0][0], c[0][1]) for c in cases.degenerate_cases().values()]
+    rng = np.random.default_rng(300700)
+    big_q, big_t = cases.random_rows(rng, 300), cases.random_rows(rng, 700)
+    big_t[rng.integers(0, 700, 120)] = big_t[rng.integers(0, 700, 120)]      # duplicates: ties of the first and of the second neighbour
+    big_q[:40] = big_t[rng.integers(0, 700, 40)]
+    pairs.append((big_q, big_t))
+    for q_block, block_bytes in ((M._Q_BLOCK, M.BLOCK_BYTES), (7, 32 * 7 * 9), (7, 32 * 7)):
+        monkeypatch.setattr(M, "_Q_BLOCK", q_block)
+        monkeypatch.setattr(M, "BLOCK_BYTES", block_bytes)
+        for x, y in pairs:
+            for q, t in ((x, y), (y, x)):
+                q, t = q.reshape(-1, 32), t.reshape(-1, 32)
+                assert np.array_equal(M.hamming(q, t), _hamming_whole(q, t))
+                got, want = M.knn2(q, t), _knn2_whole(q, t)
+                assert got.dtype == want.dtype and np.array_equal(got, want), (q.shape, t.shape, block_bytes)
+    assert M.BLOCK_BYTES <= 64 << 20
+
+
+def test_chunk_plan_of_the_split_shapes():
+    """The host's plan (csrc/match.hip: chunk_rows = TRAIN_CHUNK * ceil(nt / (TRAIN_CHUNK * 32))) for every train-row count
+    tests/test_gpu_match_split.py names: if the rule is retuned, those shapes stop meaning what their names say."""
+    want = {8191: (256, 32), 8192: (256, 32), 8193: (512, 17), 16384: (512, 32), 16385: (768, 22), 1 << 20: (32768, 32)}
+    assert {nt: cases.chunk_plan(nt) for nt in want} == want
+    src = open(os.path.join(ROOT, "imagestitch_amd", "csrc", "match.hip")).read()
+    assert "MT_MAX_SPLIT = %d;" % cases.MAX_SPLIT in src and "MT_CHUNK * cdiv(nt, MT_CHUNK * MT_MAX_SPLIT)" in src
+
+
+@pytest.mark.parametrize("n_from,n_to", [(200, 8193), (8193, 140), (130, 16385)])
+def test_split_pair_plants_what_it_says(n_from, n_to):
+    a, b, planted = cases.split_pair(7, n_from, n_to)
+    want = M.match_model([a, b], [(0, 1)], 0.3)[0]
+    cases.check_split_planted(want, planted)
+    assert planted["rows"]["roomy"] == (max(n_from, n_to) != 8193)
+
+
 def test_every_generator_class_appears_and_every_case_exercises_the_three_kinds():
     import fuzz_match
     seen = {}
@@ -106,9 +169,46 @@ def test_every_generator_class_appears_and_every_case_exercises_the_three_kinds(
             fa, fb1, fb2 = planted["fork"]
             rb, ra1, ra2 = planted["reverse_fork"]
             assert {(fa, fb1, 3), (fa, fb2, 3), (ra1, rb, 4), (ra2, rb, 4), planted["mutual"][0]} <= got, (seed, c["cls"])
-    assert sorted(seen) == sorted(fuzz_match.CLASSES), seen
+    assert sorted(seen) == sorted(fuzz_match.BASE_CLASSES), seen      # case(seed) alone draws the six it drew before `split`
     for cls in fuzz_match.CLASSES:
         assert fuzz_match.case(1, cls)["cls"] == cls
+
+
+def _case_digest(c):
+    import hashlib
+    h = hashlib.sha256()
+    for a in c["descriptors"] + c["keypoints"]:
+        h.update(np.ascontiguousarray(a).tobytes())
+    h.update(repr((c["cls"], c["pairs"], c["img_sizes"], c["match_conf"], c["layout_seed"], None if c["mask"] is None else c["mask"].tolist())).encode())
+    return h.hexdigest()[:16]
+
+
+def test_the_split_class_is_drawn_and_the_older_classes_draw_what_they_drew():
+    """A soak's first 200 cases (scheduled(): the classes in turn) hold the `split` class at every k and on either side, so chunks of 512
+    and 768 rows and the cap of 32 chunks; its planted structure is found by the model; and case(seed, cls) of the six older classes gives
+    the bytes it gave before `split` was added (digests taken from the generator as it was)."""
+    import fuzz_match
+    plans, orders, fillers = set(), set(), 0
+    for n in range(200):
+        s, cls = fuzz_match.scheduled(20261119, n)
+        if cls != "split":
+            continue
+        c = fuzz_match.case(s, cls)
+        rows = [d.shape[0] for d in c["descriptors"]]
+        big, small = max(rows), min(rows)
+        assert c["cls"] == "split" and c["pairs"] == [(0, 1)] and 4 <= small <= 300 and big % 8192 in (0, 1, 8191) and 8191 <= big <= 3 * 8192 + 1
+        plans.add(cases.chunk_plan(big))
+        orders.add(rows[0] > rows[1])
+        if n < 60:                                                    # the model on a few: every kind of match is there
+            rec = M.match_model(c["descriptors"], c["pairs"], c["match_conf"])[0]
+            assert min(rec["kinds"]) >= 1 and tuple(c["planted"][0]["mutual"][0]) in {tuple(r) for r in rec["matches"]}, (s, rec["kinds"])
+    assert {p[0] for p in plans} == {256, 512, 768, 1024} and {(256, 32), (512, 17), (768, 22)} <= plans and orders == {True, False}, plans
+    assert sum(1 for n in range(200) if fuzz_match.scheduled(1, n)[1] == "split") >= 28
+    want = {(1, "tiny"): "26878bdf4cb09a3b", (2, "chunk_edges"): "f43082ce0b01939e", (3, "clustered"): "ebcaa54c07e4a270", (4, "many"): "b5b260d59fef53e3",
+            (6, "duplicates"): "5366dfb48a2e34f0"}
+    assert {k: _case_digest(fuzz_match.case(*k)) for k in want} == want
+    assert (fuzz_match.case(0)["cls"], _case_digest(fuzz_match.case(0))) == ("many", "28fb6ae79a4501f0")
+    assert (fuzz_match.case(5)["cls"], _case_digest(fuzz_match.case(5))) == ("clustered", "2b27b71ac35dcdb6")
 
 
 def test_header_declares_the_entries_and_the_constants_match_python():

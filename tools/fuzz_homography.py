@@ -13,7 +13,9 @@ case(seed, cls) draws one of CLASSES (no GPU needed):
     count_limits  counts below, at and past the rows of the points and mask mats (clamped, status bit 3), negative counts
     noisy         13 .. 96 correspondences, 45 - 95 % inliers, 0 - 1 px of noise, thresholds and confidences drawn
     degenerate    collinear, repeated or identical points; pure outliers with a small max_iters
-    multi         2 .. 5 pairs of the other classes in one call
+    multi         2 .. 5 pairs of the five classes above in one call
+    large         400 .. 9 000 correspondences, 40 - 95 % inliers, 0 - 1 px of noise: scoring, compaction, pass 2 and the refit over thousands
+                  of rows; drawn by a generator of its own, so that case(seed, cls) of the classes above is what it was before `large`
 Layouts: host or device mats, points of 4 or 6 columns, masks of 1 or 3, spare rows past the count.
 A case whose model margin is below 1e-9 is fragile (its outcome hangs on an ulp of pow / log): it is skipped and counted, and the run fails
 when more than 1 % are."""
@@ -32,7 +34,7 @@ import homography_cases as cases  # noqa: E402
 from helpers import homography_lm_np as lm  # noqa: E402
 from helpers import homography_np as hm  # noqa: E402
 
-CLASSES = ("tiny", "chunk_edges", "count_limits", "noisy", "degenerate", "multi")
+CLASSES = ("tiny", "chunk_edges", "count_limits", "noisy", "degenerate", "multi", "large")
 SENT_I, SENT_F, SENT_B = -7777, -7777.25, 0xA5
 
 
@@ -68,12 +70,15 @@ def one(rng, cls):
         else:
             pts, kw = cases.outliers(s, int(rng.integers(8, 50))), dict(max_iters=int(rng.integers(1, 80)))
         return pts, len(pts), kw
+    if cls == "large":
+        n = int(rng.integers(400, 9001))
+        return cases.planted(s, n, int(n * rng.uniform(0.40, 0.95)), float(rng.uniform(0.0, 1.0))), n, kw
     raise ValueError(cls)
 
 
 def case(seed, cls):
     """A call: per pair (points, count), shared keyword arguments, the layout."""
-    rng = np.random.default_rng(seed)
+    rng = np.random.default_rng([int(seed), 0x4C47]) if cls == "large" else np.random.default_rng(seed)
     if cls == "multi":
         pairs = [one(rng, CLASSES[int(rng.integers(5))])[:2] for _ in range(int(rng.integers(2, 6)))]
         kw = {}
@@ -133,6 +138,11 @@ def run_case(c, want, lm_max_iters=None):
     return bad
 
 
+def scheduled(seed, n):
+    """(case seed, class) of a soak's n-th case: the classes in turn."""
+    return int(seed) * 1000003 + n, CLASSES[n % len(CLASSES)]
+
+
 def run(seconds, seed, verbose=False, progress_path=None, refine=False):
     """Draws cases (the classes in turn) for `seconds` and compares the library with the model.  Returns a summary dict."""
     import torch
@@ -145,8 +155,7 @@ def run(seconds, seed, verbose=False, progress_path=None, refine=False):
             told = time.time()
             with open(progress_path, "w") as f:
                 json.dump(dict(seconds=round(told - t0, 1), cases=n, mismatches=len(failing), skipped_fragile=skipped), f)
-        cls = CLASSES[n % len(CLASSES)]
-        s = int(seed) * 1000003 + n
+        s, cls = scheduled(seed, n)
         c = case(s, cls)
         iters = lm_iters_of(s) if refine else None
         want = expected(c, iters)

@@ -10,6 +10,10 @@ The generator (no GPU needed: tests/test_match_model.py checks it).  case(seed) 
     duplicates    filler rows repeated (ties of the first and of the second neighbour)
     clustered     filler rows a few bits from one base row (small distances, many ties, ratio tests either side of the bound)
     many          3 .. 5 images, a mask, an image without rows now and then
+    split         one image of 8192 k - 1, 8192 k or 8192 k + 1 rows, k = 1 .. 3, against one of 4 .. 300, in either order (past 32 chunks of
+                  TRAIN_CHUNK the chunk of a work item grows: 512 and 768 rows, last chunks that are not whole tiles, up to 32 partials
+                  a query), with `duplicates` or `clustered` filler now and then
+case(seed) without a class draws one of the first six, as it did before `split`; a soak takes all seven in turn (scheduled()).
 Every pair of every case carries planted structure among fresh random rows (which lie about 128 +- 8 bits from every other row, so what
 is planted stays isolated): mutual matches at distances 0, 1, .. (at most 16) - accepted both ways -, a fork (two rows of `to` 3 disjoint
 flips from one row of `from`: 1->2 ties and is rejected, both 2->1 matches are appended) and a reverse fork (two rows of `from` 4 flips
@@ -30,7 +34,9 @@ import numpy as np  # noqa: E402
 from helpers import match_np as M  # noqa: E402
 from imagestitch_amd.matcher import QUERY_BLOCK, TRAIN_CHUNK, TRAIN_TILE  # noqa: E402
 
-CLASSES = ("tiny", "tile_edges", "chunk_edges", "duplicates", "clustered", "many")
+BASE_CLASSES = ("tiny", "tile_edges", "chunk_edges", "duplicates", "clustered", "many")
+CLASSES = BASE_CLASSES + ("split",)
+SPLIT_ROWS = TRAIN_CHUNK * 32      # 8192: the rows of a train image from which on the chunk of a work item grows
 CONFS = (0.0, 0.3, 0.5, 0.65)
 ROWS_PER_PAIR = 4          # rows of an image the planted structure of one pair needs at least
 MAX_MUTUAL = 17            # distances 0 .. 16
@@ -93,8 +99,9 @@ def build(rng, rows, pairs, filler="random"):
         else:
             d[f] = random_rows(rng, len(f))
             if filler == "duplicates" and len(f) >= 2:
+                fa = np.asarray(f)                         # (the same draws as from the list, without converting it every time)
                 for _ in range(max(1, len(f) // 3)):
-                    src, dst = rng.choice(f, 2, replace=False)
+                    src, dst = rng.choice(fa, 2, replace=False)
                     d[dst] = d[src]
     return descs, planted
 
@@ -106,8 +113,9 @@ def _edge(rng, unit, most=3):
 def case(seed, cls=None):
     """One case: dict(cls, descriptors, keypoints, img_sizes, pairs, mask, match_conf, planted)."""
     rng = np.random.default_rng(seed)
-    cls = cls or CLASSES[int(rng.integers(len(CLASSES)))]
+    cls = cls or BASE_CLASSES[int(rng.integers(len(BASE_CLASSES)))]
     mask = None
+    filler = cls if cls in ("duplicates", "clustered") else "random"
     if cls == "tiny":
         rows = [int(rng.integers(4, 13)) for _ in range(2)]
     elif cls == "tile_edges":
@@ -116,6 +124,11 @@ def case(seed, cls=None):
         rows = [_edge(rng, TRAIN_CHUNK, 2), _edge(rng, TRAIN_CHUNK, 2)]
     elif cls in ("duplicates", "clustered"):
         rows = [int(rng.integers(8, 300)) for _ in range(2)]
+    elif cls == "split":
+        rows = [SPLIT_ROWS * int(rng.integers(1, 4)) + int(rng.integers(-1, 2)), int(rng.integers(4, 301))]
+        if rng.random() < 0.5:
+            rows.reverse()
+        filler = ("random", "random", "duplicates", "clustered")[int(rng.integers(4))]
     else:
         n = int(rng.integers(3, 6))
         rows = [int(rng.integers(ROWS_PER_PAIR * (n - 1), 200)) for _ in range(n)]
@@ -125,7 +138,6 @@ def case(seed, cls=None):
         if not any(mask[i, j] for i, j in M.near_pairs(rows)):
             mask = None
     pairs = M.near_pairs(rows, mask)
-    filler = cls if cls in ("duplicates", "clustered") else "random"
     descs, planted = build(rng, rows, pairs, filler)
     sizes = [(int(rng.integers(1, 5000)), int(rng.integers(1, 5000))) for _ in rows]
     kps = [(rng.random((n, 2)) * np.array(s)).astype(np.float32) for n, s in zip(rows, sizes)]
@@ -208,6 +220,11 @@ def run_case(c, rng=None):
     return bad
 
 
+def scheduled(seed, n):
+    """(case seed, class) of a soak's n-th case: the classes in turn."""
+    return int(seed) * 1000003 + n, CLASSES[n % len(CLASSES)]
+
+
 def run(seconds, seed, verbose=False, progress_path=None):
     """Draws cases (the classes in turn) for `seconds` and compares the library with the model.  Returns a summary dict; progress_path: a file
     that gets the running counts every 30 seconds."""
@@ -221,8 +238,7 @@ def run(seconds, seed, verbose=False, progress_path=None):
             told = time.time()
             with open(progress_path, "w") as f:
                 json.dump(dict(seconds=round(told - t0, 1), cases=n, mismatches=len(failing)), f)
-        cls = CLASSES[n % len(CLASSES)]
-        s = int(seed) * 1000003 + n
+        s, cls = scheduled(seed, n)
         c = case(s, cls)
         bad = run_case(c)
         per[cls] += 1
