@@ -120,6 +120,7 @@ _SIGS = {
     "isx_orb_reserve": [C.c_void_p, C.c_int, C.c_int, C.c_int],
     "isx_orb_release": [],
     "isx_match_features": [C.c_int, _MP, _MP, _IP, C.c_int, _IP, C.c_float, _MP, _MP, _MP, _MP, _IP, C.c_int, C.c_void_p],
+    "isx_match_features_f32": [C.c_int, _MP, _MP, _IP, C.c_int, _IP, C.c_float, _MP, _MP, _MP, _MP, _IP, C.c_int, C.c_void_p],
     "isx_match_release": [],
     "isx_find_homography": [C.c_int, _MP, _MP, C.c_double, C.c_int, C.c_double, C.c_int, C.c_int, _MP, _MP, _MP, _MP, _IP, C.c_int, C.c_void_p],
     "isx_find_homography_lm": [C.c_int, _MP, _MP, C.c_double, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _MP, _MP, _MP, _MP, _IP, C.c_int,

@@ -1,6 +1,9 @@
 // match.hip — the features matcher of the M demo (the reference's 特征点匹配/特征点匹配/特征点匹配.cpp) on gfx950:
 //   isx_match_features   BestOf2NearestMatcher1 matcher(false, 0.3f, 6, 6); matcher(features, pairwise_matches)      M:307-308
 //                        = near_pairs M:131-135, CpuMatcher1::match M:232-289 per pair, the point gather M:164-179
+//   isx_match_features_f32   the same over CV_32F descriptors of 1 .. 128 columns (M:237): exact L2 2-NN (DESIGN.md §8 "Features matcher,
+//                        float descriptors"; tests/helpers/match_f32_np.py) - the kernels k_mf_pack / k_mf_search and the second
+//                        instantiation of k_mt_finalise, the host code one template for both
 //   isx_match_release    returns the per-thread scratch
 //
 // The specification (DESIGN.md §8 "Features matcher"; tests/helpers/match_np.py): exact 2-nearest neighbours by (Hamming distance, row)
@@ -17,6 +20,8 @@
 //                  chunk go to the partials.  Keys are unique per query, so the later merge is exact whatever the chunking.
 //   k_mt_finalise  one block per pair: merges the partials, writes knn, runs the ratio test and - for 2->1 - the lookup "1->2 accepted
 //                  this row with that neighbour", compacts in order with a ballot prefix scan and writes matches, points and the count.
+#include <type_traits>
+
 #include "isx_device.hpp"
 #include "pairwise.hpp"
 #include "scratch.hpp"
@@ -49,7 +54,7 @@ struct MtImage {
 struct MtPair {
     int from, to;                        // images
     int nchunks[2], chunk_rows[2];       // per direction (0: 1->2, the train set is image `to`)
-    long long part_off[2];               // first uint2 of the direction's partials: [query][chunk]
+    long long part_off[2];               // first entry (uint2; ulonglong2 for float descriptors) of the direction's partials: [query][chunk]
     long long acc_off;                   // n_from ints: the row 1->2 accepted for each query, or -1
     int* matches; long long matches_step;
     float* points; long long points_step;
@@ -69,10 +74,30 @@ __global__ __launch_bounds__(MT_PACK_ROWS * 8) void k_mt_pack(const MtImage* __r
     packed[((size_t)I.off + row) * 8 + w] = v;
 }
 
-__device__ __forceinline__ void mt_update(unsigned key, unsigned& k0, unsigned& k1) {
+template <class K>
+__device__ __forceinline__ void mt_update(K key, K& k0, K& k1) {
     k1 = min(k1, max(k0, key));
     k0 = min(k0, key);
 }
+
+// What k_mt_finalise needs of a key: the partials' type, "no neighbour", the train row, the int32 that knn and matches carry as the
+// distance, and that distance as the float of the ratio test.
+struct HamKey {                                      // distance << 22 | row
+    typedef unsigned key_t;
+    typedef uint2 part_t;
+    static constexpr key_t NONE = MT_NONE;
+    static __device__ __forceinline__ int row(key_t k) { return (int)(k & MT_IDX_MASK); }
+    static __device__ __forceinline__ int carried(key_t k) { return (int)(k >> MT_KEY_SHIFT); }
+    static __device__ __forceinline__ float dist(int carried) { return (float)carried; }
+};
+struct L2Key {                                       // bits(s) << 32 | row, s the squared distance (>= +0, so its bits order as an integer)
+    typedef unsigned long long key_t;
+    typedef ulonglong2 part_t;
+    static constexpr key_t NONE = ~0ull;
+    static __device__ __forceinline__ int row(key_t k) { return (int)(unsigned)k; }
+    static __device__ __forceinline__ int carried(key_t k) { return __float_as_int(sqrtf(__uint_as_float((unsigned)(k >> 32)))); }      // bits(d), d = sqrtf(s) correctly rounded
+    static __device__ __forceinline__ float dist(int carried) { return __int_as_float(carried); }
+};
 
 // work: (pair, direction, query block, train chunk) per block
 __global__ __launch_bounds__(MT_Q) void k_mt_search(const MtPair* __restrict__ pairs, const MtImage* __restrict__ imgs, const int4* __restrict__ work,
@@ -107,7 +132,104 @@ __global__ __launch_bounds__(MT_Q) void k_mt_search(const MtPair* __restrict__ p
     if (q < nq) partial[P.part_off[dir] + (long long)q * nch + wi.w] = make_uint2(k0, k1);
 }
 
-__global__ __launch_bounds__(MT_FIN_NT) void k_mt_finalise(const MtPair* __restrict__ pairs, const MtImage* __restrict__ imgs, const uint2* __restrict__ partial,
+// ---- float descriptors: rows of W floats (64 where cols <= 64, else 128), zero-padded - s + 0 * 0 is s, so the padding changes no bit ----
+constexpr int MF_T = ISX_MATCH_F32_TRAIN_TILE;   // train rows per LDS tile: 8 / 16 KiB, so that several blocks share a CU's LDS
+constexpr int MF_U = 4;                          // candidates in flight: independent chains of sub, mul, add hide the add's latency
+constexpr int MF_G = 2;                          // float4s of a candidate read from the LDS ahead of their arithmetic
+static_assert(MT_CHUNK % MF_T == 0 && MF_T % MF_U == 0, "a chunk is whole tiles, a tile whole groups of candidates");
+
+// blocks: (image, first row) per block, as for k_mt_pack; a wave copies a row, dword loads at any 4-aligned step
+__global__ __launch_bounds__(MT_PACK_ROWS * 8) void k_mf_pack(const MtImage* __restrict__ imgs, const int2* __restrict__ blocks, float* __restrict__ packed, int cols, int W) {
+    imgs = as_global(imgs); blocks = as_global(blocks); packed = as_global(packed);
+    const int2 b = blocks[blockIdx.x];
+    const MtImage& I = imgs[b.x];
+    for (int r = (int)(threadIdx.x >> 6); r < MT_PACK_ROWS; r += (MT_PACK_ROWS * 8) >> 6) {
+        const int row = b.y + r;
+        if (row >= I.rows) break;
+        const float* p = (const float*)(as_global(I.desc) + (long long)row * I.desc_step);
+        for (int c = (int)(threadIdx.x & 63); c < W; c += 64) packed[((size_t)I.off + row) * W + c] = c < cols ? p[c] : 0.f;
+    }
+}
+
+// work: (pair, direction, query block, train chunk) per block, as for k_mt_search.  A thread owns one query row in W registers; the tile's
+// rows are read by all lanes at one address (ds_read_b128 broadcasts).  s = 0, then s = s + e * e for c = 0 .. W - 1 in that order, e =
+// a[c] - b[c], every operation rounded on its own (-ffp-contract=off); an s that is not finite becomes +inf.
+template <int W>
+__global__ __launch_bounds__(MT_Q) void k_mf_search(const MtPair* __restrict__ pairs, const MtImage* __restrict__ imgs, const int4* __restrict__ work,
+                                                    const float4* __restrict__ packed, ulonglong2* __restrict__ partial) {
+    constexpr int V = W / 4;                                      // float4s a row
+    __shared__ float4 s_tile[MF_T * V];
+    pairs = as_global(pairs); imgs = as_global(imgs); work = as_global(work); packed = as_global(packed); partial = as_global(partial);
+    const int4 wi = work[blockIdx.x];
+    const MtPair& P = pairs[wi.x];
+    const int dir = wi.y, t = (int)threadIdx.x;
+    const MtImage& Q = imgs[dir ? P.to : P.from];
+    const MtImage& R = imgs[dir ? P.from : P.to];
+    const int nq = Q.rows, nt = R.rows, nch = P.nchunks[dir], crows = P.chunk_rows[dir];
+    const int q = wi.z * MT_Q + t;
+    float4 qv[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) qv[v] = q < nq ? packed[((size_t)Q.off + q) * V + v] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const int t0 = wi.w * crows, t1 = min(nt, t0 + crows);       // t0 < nt: the host makes no empty chunk
+    unsigned long long k0 = L2Key::NONE, k1 = L2Key::NONE;
+    for (int tb = t0; tb < t1; tb += MF_T) {
+        __syncthreads();                                          // the previous tile's readers are done
+        for (int i = t; i < MF_T * V; i += MT_Q)                  // rows past the chunk's end are zeros: computed, never kept
+            s_tile[i] = tb + i / V < t1 ? packed[((size_t)R.off + tb) * V + i] : make_float4(0.f, 0.f, 0.f, 0.f);
+        __syncthreads();
+        const int n = min(MF_T, t1 - tb);
+#pragma unroll 1
+        for (int j = 0; j < n; j += MF_U) {
+            float s[MF_U];
+#pragma unroll
+            for (int u = 0; u < MF_U; ++u) s[u] = 0.f;
+            // groups of MF_G float4s a candidate: the next group's LDS reads are issued before this group's arithmetic and no further
+            // ahead (the fence), so the tile's values in flight stay at 2 * MF_U * MF_G float4s beside the query row - no spill
+            float4 cur[MF_U][MF_G], nxt[MF_U][MF_G];
+#pragma unroll
+            for (int u = 0; u < MF_U; ++u)
+#pragma unroll
+                for (int g = 0; g < MF_G; ++g) cur[u][g] = s_tile[(j + u) * V + g];
+#pragma unroll
+            for (int v0 = 0; v0 < V; v0 += MF_G) {
+                if (v0 + MF_G < V) {
+#pragma unroll
+                    for (int u = 0; u < MF_U; ++u)
+#pragma unroll
+                        for (int g = 0; g < MF_G; ++g) nxt[u][g] = s_tile[(j + u) * V + v0 + MF_G + g];
+                }
+#pragma unroll
+                for (int g = 0; g < MF_G; ++g) {
+#pragma unroll
+                    for (int u = 0; u < MF_U; ++u) {
+                        const float4 a = cur[u][g], b = qv[v0 + g];
+                        float e;
+                        e = b.x - a.x; s[u] = s[u] + e * e;
+                        e = b.y - a.y; s[u] = s[u] + e * e;
+                        e = b.z - a.z; s[u] = s[u] + e * e;
+                        e = b.w - a.w; s[u] = s[u] + e * e;
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int u = 0; u < MF_U; ++u)
+#pragma unroll
+                    for (int g = 0; g < MF_G; ++g) cur[u][g] = nxt[u][g];
+            }
+#pragma unroll
+            for (int u = 0; u < MF_U; ++u) {
+                const float sv = s[u] <= 3.402823466e38f ? s[u] : __uint_as_float(0x7F800000u);      // NaN and overflow: +inf
+                const unsigned long long key = ((unsigned long long)__float_as_uint(sv) << 32) | (unsigned)(tb + j + u);
+                mt_update(j + u < n ? key : L2Key::NONE, k0, k1);      // a select, not a branch: the MF_U chains stay interleaved
+            }
+        }
+    }
+    if (q < nq) partial[P.part_off[dir] + (long long)q * nch + wi.w] = make_ulonglong2(k0, k1);
+}
+
+template <class K>
+__global__ __launch_bounds__(MT_FIN_NT) void k_mt_finalise(const MtPair* __restrict__ pairs, const MtImage* __restrict__ imgs,
+                                                           const typename K::part_t* __restrict__ partial,
                                                            int* acc, float k) {
     __shared__ int s_cnt[MT_FIN_NT / WAVE];
     pairs = as_global(pairs); imgs = as_global(imgs); partial = as_global(partial); acc = as_global(acc);
@@ -127,25 +249,25 @@ __global__ __launch_bounds__(MT_FIN_NT) void k_mt_finalise(const MtPair* __restr
     int base = 0;
     for (int dir = 0; dir < 2; ++dir) {
         const int nq = dir ? T.rows : F.rows, nt = dir ? F.rows : T.rows, nch = P.nchunks[dir];
-        const uint2* part = partial + P.part_off[dir];
+        const typename K::part_t* part = partial + P.part_off[dir];
         int* knn = as_global(P.knn[dir]);
         for (int q0 = 0; q0 < nq; q0 += MT_FIN_NT) {
             const int q = q0 + t;
             bool ok = false;
             int i0 = -1, d0 = -1;
             if (q < nq) {
-                unsigned k0 = MT_NONE, k1 = MT_NONE;
+                typename K::key_t k0 = K::NONE, k1 = K::NONE;
                 for (int c = 0; c < nch; ++c) {
-                    const uint2 p = part[(long long)q * nch + c];
-                    mt_update(p.x, k0, k1); mt_update(p.y, k0, k1);
+                    const typename K::part_t p = part[(long long)q * nch + c];
+                    mt_update<typename K::key_t>(p.x, k0, k1); mt_update<typename K::key_t>(p.y, k0, k1);
                 }
-                const int i1 = k1 == MT_NONE ? -1 : (int)(k1 & MT_IDX_MASK), d1 = k1 == MT_NONE ? -1 : (int)(k1 >> MT_KEY_SHIFT);
-                i0 = k0 == MT_NONE ? -1 : (int)(k0 & MT_IDX_MASK); d0 = k0 == MT_NONE ? -1 : (int)(k0 >> MT_KEY_SHIFT);
+                const int i1 = k1 == K::NONE ? -1 : K::row(k1), d1 = k1 == K::NONE ? -1 : K::carried(k1);
+                i0 = k0 == K::NONE ? -1 : K::row(k0); d0 = k0 == K::NONE ? -1 : K::carried(k0);
                 if (knn) {
                     int* o = (int*)((char*)knn + (long long)q * P.knn_step[dir]);
                     o[0] = i0; o[1] = d0; o[2] = i1; o[3] = d1;
                 }
-                if (nt >= 2) ok = (float)d0 < k * (float)d1;     // M:260, M:267 (-ffp-contract=off: one rounded multiply)
+                if (nt >= 2) ok = K::dist(d0) < k * K::dist(d1); // M:260, M:267 (-ffp-contract=off: one rounded multiply)
                 if (dir == 0) accp[q] = ok ? i0 : -1;
                 else if (ok) ok = accp[i0] != q;                 // M:285
             }
@@ -176,20 +298,12 @@ __global__ __launch_bounds__(MT_FIN_NT) void k_mt_finalise(const MtPair* __restr
 
 struct MtScratch : UploadScratch {};      // pin: the tables, staged keypoints and packed descriptors of host mats (scratch.hpp)
 
-}  // namespace
-
-extern "C" {
-
-int isx_match_release(void) ISX_ENTRY {
-    clear_error();
-    return per_thread<MtScratch>().release();
-} ISX_EXIT("isx_match_release")
-
-int isx_match_features(int num_images, const isx_mat* descriptors, const isx_mat* keypoints, const int* image_sizes_wh,
-                       int num_pairs, const int* pairs_ij, float match_conf, isx_mat* matches, isx_mat* points, isx_mat* counts,
-                       isx_mat* knn, int* info, int device, void* hip_stream) ISX_ENTRY {
-    clear_error();
-    const char* who = "match_features";
+// Both entries: K = HamKey over n x 32 CV_8UC1 rows (32 bytes a packed row), K = L2Key over n x cols CV_32FC1 rows (W floats a packed row).
+template <class K>
+int match_entry(const char* who, int num_images, const isx_mat* descriptors, const isx_mat* keypoints, const int* image_sizes_wh,
+                int num_pairs, const int* pairs_ij, float match_conf, isx_mat* matches, isx_mat* points, isx_mat* counts,
+                isx_mat* knn, int* info, int device, void* hip_stream) {
+    constexpr bool F32 = std::is_same<K, L2Key>::value;
     // ---- checks: all of them before anything is written or enqueued ----
     ISX_CHECK_ARG(num_images >= 0 && num_pairs >= 0, ISX_ERR_INVALID, "%s: %d images, %d pairs", who, num_images, num_pairs);
     ISX_CHECK_ARG(num_images == 0 || descriptors, ISX_ERR_INVALID, "%s: null descriptors", who);
@@ -202,16 +316,27 @@ int isx_match_features(int num_images, const isx_mat* descriptors, const isx_mat
         ISX_CHECK_ARG(i >= 0 && i < j && j < num_images, ISX_ERR_INVALID, "%s: pair %d is (%d, %d) of %d images (from < to)", who, p, i, j, num_images);
     }
     long long total_rows = 0;
+    int cols = 0;                                                 // of the images with rows (float descriptors: one width a call)
     for (int i = 0; i < num_images; ++i) {
         const isx_mat& m = descriptors[i];
-        ISX_CHECK_ARG(m.type == ISX_8UC1, ISX_ERR_TYPE, "%s: descriptors %d are %s (CV_8UC1)", who, i, type_name(m.type));
+        ISX_CHECK_ARG(m.type == (F32 ? ISX_32FC1 : ISX_8UC1), ISX_ERR_TYPE, "%s: descriptors %d are %s (%s)", who, i, type_name(m.type), F32 ? "CV_32FC1" : "CV_8UC1");
         ISX_CHECK_ARG(m.rows >= 0, ISX_ERR_INVALID, "%s: descriptors %d have %d rows", who, i, m.rows);
         if (m.rows > 0) {
-            // CV_32F (SURF) descriptors and binary descriptors of another length are not built
-            ISX_CHECK_ARG(m.cols == 32, ISX_ERR_UNSUPPORTED, "%s: descriptors %d have %d columns (32-byte ORB descriptors only)", who, i, m.cols);
+            if (F32) {
+                ISX_CHECK_ARG(m.cols >= 1, ISX_ERR_INVALID, "%s: descriptors %d have %d columns", who, i, m.cols);
+                ISX_CHECK_ARG(m.cols <= ISX_MATCH_F32_MAX_COLS, ISX_ERR_UNSUPPORTED, "%s: descriptors %d have %d columns (at most %d)", who, i, m.cols, ISX_MATCH_F32_MAX_COLS);
+                ISX_CHECK_ARG(cols == 0 || m.cols == cols, ISX_ERR_SIZE, "%s: descriptors %d have %d columns, those before %d", who, i, m.cols, cols);
+                cols = m.cols;
+            } else {
+                // binary descriptors of another length are not built
+                ISX_CHECK_ARG(m.cols == 32, ISX_ERR_UNSUPPORTED, "%s: descriptors %d have %d columns (32-byte ORB descriptors only)", who, i, m.cols);
+                cols = 32;
+            }
             ISX_CHECK_ARG(m.rows <= ISX_MATCH_MAX_ROWS, ISX_ERR_UNSUPPORTED, "%s: descriptors %d have %d rows (at most %d)", who, i, m.rows, ISX_MATCH_MAX_ROWS);
             ISX_CHECK_ARG(m.data != nullptr, ISX_ERR_INVALID, "%s: descriptors %d have a null data pointer", who, i);
-            ISX_CHECK_ARG(m.step >= 32 || m.rows == 1, ISX_ERR_INVALID, "%s: descriptors %d: step %zu smaller than a row", who, i, m.step);
+            ISX_CHECK_ARG(m.step >= (size_t)cols * (F32 ? 4 : 1) || m.rows == 1, ISX_ERR_INVALID, "%s: descriptors %d: step %zu smaller than a row", who, i, m.step);
+            if (F32)
+                ISX_CHECK_ARG(((uintptr_t)m.data & 3) == 0 && (m.step & 3) == 0, ISX_ERR_INVALID, "%s: descriptors %d are not 4-byte aligned in pointer and step", who, i);
             ISX_CHECK_ARG(m.device < 0 || m.device == device, ISX_ERR_INVALID, "%s: descriptors %d live on device %d, the call runs on %d", who, i, m.device, device);
         }
         total_rows += m.rows;
@@ -250,6 +375,8 @@ int isx_match_features(int num_images, const isx_mat* descriptors, const isx_mat
     }
 
     // ---- the plan: packed rows (host mats first: they travel in the upload), chunking, work items ----
+    const int W = cols <= 64 ? 64 : 128;                          // floats a packed row (float descriptors)
+    const size_t row_bytes = F32 ? (size_t)W * 4 : 32;
     std::vector<MtImage> imgs((size_t)num_images);
     int host_rows = 0, dev_rows = 0;
     for (int i = 0; i < num_images; ++i)
@@ -298,9 +425,9 @@ int isx_match_features(int num_images, const isx_mat* descriptors, const isx_mat
     if (keypoints)
         for (int i = 0; i < num_images; ++i) m_kp[i].plan(lay, keypoints[i], imgs[i].rows, 8);
     const size_t o_packed = lay.take(0);
-    const size_t upload_bytes = o_packed + (size_t)host_rows * 32;
-    lay.take((size_t)(host_rows + dev_rows) * 32);
-    const size_t o_part = lay.take((size_t)part_count * sizeof(uint2)), o_acc = lay.take((size_t)acc_count * sizeof(int));
+    const size_t upload_bytes = o_packed + (size_t)host_rows * row_bytes;
+    lay.take((size_t)(host_rows + dev_rows) * row_bytes);
+    const size_t o_part = lay.take((size_t)part_count * sizeof(typename K::part_t)), o_acc = lay.take((size_t)acc_count * sizeof(int));
     StagedMat m_counts;
     m_counts.plan(lay, *counts, 1, (size_t)num_pairs * 4);
     std::vector<StagedMat> m_m((size_t)num_pairs), m_p((size_t)num_pairs), m_k((size_t)2 * num_pairs);
@@ -326,7 +453,12 @@ int isx_match_features(int num_images, const isx_mat* descriptors, const isx_mat
         if (I.rows == 0) continue;
         const isx_mat& m = descriptors[i];
         if (m.device < 0)
-            for (int r = 0; r < m.rows; ++r) std::memcpy(pin + o_packed + ((size_t)I.off + r) * 32, (const char*)m.data + (size_t)r * m.step, 32);
+            for (int r = 0; r < m.rows; ++r) {
+                char* const row = pin + o_packed + ((size_t)I.off + r) * row_bytes;
+                const size_t have = F32 ? (size_t)cols * 4 : 32;
+                std::memcpy(row, (const char*)m.data + (size_t)r * m.step, have);
+                std::memset(row + have, 0, row_bytes - have);
+            }
         if (!keypoints) continue;
         m_kp[i].fill(pin);
         m_kp[i].bind(dev, I.kp, I.kp_step);
@@ -353,18 +485,29 @@ int isx_match_features(int num_images, const isx_mat* descriptors, const isx_mat
     const MtPair* d_prs = (const MtPair*)(dev + o_prs);
     int launches = 0;
     if (!pack_blocks.empty()) {
-        ISX_LAUNCH("match_pack", (double)dev_rows * 64.0, st, k_mt_pack, dim3((unsigned)pack_blocks.size()), dim3(MT_PACK_ROWS * 8), 0, d_imgs,
-                   (const int2*)(dev + o_pblk), (unsigned*)(dev + o_packed));
+        if (F32)
+            ISX_LAUNCH("match_f32_pack", (double)dev_rows * (cols * 4.0 + (double)row_bytes), st, k_mf_pack, dim3((unsigned)pack_blocks.size()), dim3(MT_PACK_ROWS * 8), 0,
+                       d_imgs, (const int2*)(dev + o_pblk), (float*)(dev + o_packed), cols, W);
+        else
+            ISX_LAUNCH("match_pack", (double)dev_rows * 64.0, st, k_mt_pack, dim3((unsigned)pack_blocks.size()), dim3(MT_PACK_ROWS * 8), 0, d_imgs,
+                       (const int2*)(dev + o_pblk), (unsigned*)(dev + o_packed));
         ++launches;
     }
     if (!work.empty()) {
-        ISX_LAUNCH("match_search", (double)work.size() * (MT_Q + MT_CHUNK) * 32.0, st, k_mt_search, dim3((unsigned)work.size()), dim3(MT_Q), 0, d_prs, d_imgs,
-                   (const int4*)(dev + o_work), (const uint4*)(dev + o_packed), (uint2*)(dev + o_part));
+        if (!F32)
+            ISX_LAUNCH("match_search", (double)work.size() * (MT_Q + MT_CHUNK) * 32.0, st, k_mt_search, dim3((unsigned)work.size()), dim3(MT_Q), 0, d_prs, d_imgs,
+                       (const int4*)(dev + o_work), (const uint4*)(dev + o_packed), (uint2*)(dev + o_part));
+        else if (W == 64)
+            ISX_LAUNCH("match_f32_search", (double)work.size() * (MT_Q + MT_CHUNK) * 256.0, st, k_mf_search<64>, dim3((unsigned)work.size()), dim3(MT_Q), 0, d_prs,
+                       d_imgs, (const int4*)(dev + o_work), (const float4*)(dev + o_packed), (ulonglong2*)(dev + o_part));
+        else
+            ISX_LAUNCH("match_f32_search", (double)work.size() * (MT_Q + MT_CHUNK) * 512.0, st, k_mf_search<128>, dim3((unsigned)work.size()), dim3(MT_Q), 0, d_prs,
+                       d_imgs, (const int4*)(dev + o_work), (const float4*)(dev + o_packed), (ulonglong2*)(dev + o_part));
         ++launches;
     }
     const float k = 1.f - match_conf;
-    ISX_LAUNCH("match_finalise", (double)part_count * 8.0, st, k_mt_finalise, dim3((unsigned)num_pairs), dim3(MT_FIN_NT), 0, d_prs, d_imgs,
-               (const uint2*)(dev + o_part), (int*)(dev + o_acc), k);
+    ISX_LAUNCH(F32 ? "match_f32_finalise" : "match_finalise", (double)part_count * sizeof(typename K::part_t), st, k_mt_finalise<K>, dim3((unsigned)num_pairs),
+               dim3(MT_FIN_NT), 0, d_prs, d_imgs, (const typename K::part_t*)(dev + o_part), (int*)(dev + o_acc), k);
     ++launches;
     ISX_TRY(s.ran(st));
 
@@ -382,6 +525,31 @@ int isx_match_features(int num_images, const isx_mat* descriptors, const isx_mat
     }
     if (info) { info[0] = searched; info[1] = launches; }
     return ISX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int isx_match_release(void) ISX_ENTRY {
+    clear_error();
+    return per_thread<MtScratch>().release();
+} ISX_EXIT("isx_match_release")
+
+int isx_match_features(int num_images, const isx_mat* descriptors, const isx_mat* keypoints, const int* image_sizes_wh,
+                       int num_pairs, const int* pairs_ij, float match_conf, isx_mat* matches, isx_mat* points, isx_mat* counts,
+                       isx_mat* knn, int* info, int device, void* hip_stream) ISX_ENTRY {
+    clear_error();
+    return match_entry<HamKey>("match_features", num_images, descriptors, keypoints, image_sizes_wh, num_pairs, pairs_ij, match_conf, matches, points, counts, knn,
+                               info, device, hip_stream);
 } ISX_EXIT("isx_match_features")
+
+int isx_match_features_f32(int num_images, const isx_mat* descriptors, const isx_mat* keypoints, const int* image_sizes_wh,
+                           int num_pairs, const int* pairs_ij, float match_conf, isx_mat* matches, isx_mat* points, isx_mat* counts,
+                           isx_mat* knn, int* info, int device, void* hip_stream) ISX_ENTRY {
+    clear_error();
+    return match_entry<L2Key>("match_features_f32", num_images, descriptors, keypoints, image_sizes_wh, num_pairs, pairs_ij, match_conf, matches, points, counts,
+                              knn, info, device, hip_stream);
+} ISX_EXIT("isx_match_features_f32")
 
 }  // extern "C"

@@ -369,8 +369,10 @@ private:
 // matcher(features, pairwise_matches) (M:307-308) as far as M:158 and the point gather of M:164-179 (isx_match_features): an exact 2-nearest-
 // neighbour search over 32-byte descriptors on the GPU, the ratio test and the de-duplication of M:232-289.  Homography, inliers and
 // confidence (M:181-229) are BestOf2NearestMatcher's, below: FeaturesMatcher leaves H and inliers_mask empty, num_inliers and confidence 0.
+// CV_32FC1 descriptors of 1 .. 128 columns (the other depth CpuMatcher1::match admits, M:237) take isx_match_features_f32: an exact L2 search,
+// DMatch::distance the float32 distance.  Both classes pick the entry by the mats' type; mixed types throw ISX_ERR_TYPE.
 struct DMatch { int queryIdx = -1, trainIdx = -1; float distance = 0.f; };
-struct ImageFeatures { int img_idx = 0; Size img_size; std::vector<Point2f> keypoints; Mat descriptors; };      // descriptors: n x 32 CV_8UC1
+struct ImageFeatures { int img_idx = 0; Size img_size; std::vector<Point2f> keypoints; Mat descriptors; };      // descriptors: n x 32 CV_8UC1, or n x cols CV_32FC1
 struct MatchesInfo {
     int src_img_idx = -1, dst_img_idx = -1;
     std::vector<DMatch> matches;
@@ -447,8 +449,10 @@ public:
             throw Exception(ISX_ERR_INVALID, "match: the mask is not a CV_8U host mat of n x n");
         std::vector<isx_mat> d(n), kp(n);
         std::vector<int> sizes, pij;
+        bool f32 = false, other = false;
         for (int i = 0; i < n; ++i) {
             d[i] = *descriptors[i].c();
+            if (d[i].rows > 0 || d[i].cols > 0) (d[i].type == ISX_32FC1 ? f32 : other) = true;      // (a default Mat is an image without features)
             if (!pts) continue;
             if ((int)keypoints[i].size() != d[i].rows) throw Exception(ISX_ERR_SIZE, "match: keypoints and descriptor rows differ");
             kp[i].data = (void*)keypoints[i].data(); kp[i].rows = d[i].rows; kp[i].cols = 2; kp[i].type = ISX_32FC1; kp[i].step = sizeof(Point2f); kp[i].device = -1;
@@ -457,6 +461,7 @@ public:
         for (int i = 0; i < n - 1; ++i)
             for (int j = i + 1; j < n; ++j)
                 if (d[i].rows > 0 && d[j].rows > 0 && (mask.empty() || mask.ptr<unsigned char>(i)[j])) { pij.push_back(i); pij.push_back(j); }
+        if (f32 && other) throw Exception(ISX_ERR_TYPE, "match: descriptors of mixed types");
         const int np = (int)pij.size() / 2;
         std::vector<MatchesInfo> out(np);
         if (np == 0) return out;
@@ -468,8 +473,10 @@ public:
             m[k].create(cap, 3, ISX_32SC1); mm[k] = *m[k].c();
             if (pts) { p[k].create(cap, 4, ISX_32FC1); pm[k] = *p[k].c(); }
         }
-        check(isx_match_features(n, d.data(), pts ? kp.data() : nullptr, pts ? sizes.data() : nullptr, np, pij.data(), conf_, mm.data(), pts ? pm.data() : nullptr,
-                                 counts.c(), nullptr, info_, device_, stream_));
+        if (f32)
+            for (int i = 0; i < n; ++i) d[i].type = ISX_32FC1;                                    // (so that an empty default Mat passes the type check)
+        check((f32 ? isx_match_features_f32 : isx_match_features)(n, d.data(), pts ? kp.data() : nullptr, pts ? sizes.data() : nullptr, np, pij.data(), conf_,
+                                                                  mm.data(), pts ? pm.data() : nullptr, counts.c(), nullptr, info_, device_, stream_));
         afterMatch(pts ? &pm : nullptr, counts.c(), out);
         for (int k = 0; k < np; ++k) {
             MatchesInfo& mi = out[k];
@@ -478,6 +485,7 @@ public:
             for (int r = 0; r < cnt; ++r) {
                 const int* row = m[k].ptr<int>(r);
                 DMatch dm; dm.queryIdx = row[0]; dm.trainIdx = row[1]; dm.distance = (float)row[2];
+                if (f32) std::memcpy(&dm.distance, &row[2], sizeof(float));                       // the float entry carries the distance's bits
                 mi.matches.push_back(dm);
                 if (pts) { const float* q = p[k].ptr<float>(r); mi.src_points.push_back(Point2f(q[0], q[1])); mi.dst_points.push_back(Point2f(q[2], q[3])); }
             }

@@ -709,6 +709,9 @@ int isx_orb_release(void);
  * per LDS tile, train rows per work item, and the row limits - the width of the packed key distance << 22 | row.                          */
 enum { ISX_MATCH_QUERY_BLOCK = 128, ISX_MATCH_TRAIN_TILE = 128, ISX_MATCH_TRAIN_CHUNK = 256,
        ISX_MATCH_MAX_ROWS = 1 << 20, ISX_MATCH_MAX_TOTAL_ROWS = 1 << 22 };
+/* isx_match_features_f32 shares the query block, the chunk plan and the row limits; its LDS tile holds fewer (wider) rows, and a row has
+ * at most ISX_MATCH_F32_MAX_COLS floats.                                                                                                 */
+enum { ISX_MATCH_F32_TRAIN_TILE = 32, ISX_MATCH_F32_MAX_COLS = 128 };
 /* BestOf2NearestMatcher1 matcher(false, match_conf, ...); matcher(features, pairwise_matches) (M:307-308) up to where M:158 returns, plus
  * the point gather of M:164-179: for every pair of near_pairs (M:131-135) CpuMatcher1::match (M:232-289) with an EXACT 2-nearest-neighbour
  * search over 256-bit Hamming distances in place of the FLANN LSH index of M:241-250 (approximate and randomised: not reproduced).
@@ -719,7 +722,7 @@ enum { ISX_MATCH_QUERY_BLOCK = 128, ISX_MATCH_TRAIN_TILE = 128, ISX_MATCH_TRAIN_
  * An accepted match has a unique nearest neighbour (d0 < k d1 <= d1), so the list does not depend on how ties are ordered.  A pair with an
  * empty image is skipped: its count is 0 and nothing else of it is written (M:134).  homography, inliers and confidence (M:181-229) are
  * isx_find_homography's, which reads `points` and `counts` where this call leaves them.
- *   descriptors  num_images CV_8UC1 mats of n_i x 32 (ORB; CV_32F / SURF descriptors are not built: cols != 32 -> ISX_ERR_UNSUPPORTED), host or
+ *   descriptors  num_images CV_8UC1 mats of n_i x 32 (ORB; cols != 32 -> ISX_ERR_UNSUPPORTED; CV_32F descriptors go to isx_match_features_f32), host or
  *                device, any pointer alignment and step; rows may be 0 (then data and cols are not looked at).  At most 2^20 rows an
  *                image and 2^22 in all (ISX_ERR_UNSUPPORTED).
  *   keypoints    NULL, or num_images CV_32FC1 mats of n_i x 2 (pt.x, pt.y); then image_sizes_wh holds (width, height) per image (img_size).
@@ -741,6 +744,24 @@ enum { ISX_MATCH_QUERY_BLOCK = 128, ISX_MATCH_TRAIN_TILE = 128, ISX_MATCH_TRAIN_
 int isx_match_features(int num_images, const isx_mat* descriptors, const isx_mat* keypoints, const int* image_sizes_wh,
                        int num_pairs, const int* pairs_ij, float match_conf, isx_mat* matches, isx_mat* points, isx_mat* counts,
                        isx_mat* knn, int* info, int device, void* hip_stream);
+/* The same call over CV_32F descriptors (SURF 64 / 128, SIFT 128, learned ones; CpuMatcher1::match admits both depths, M:237): an EXACT
+ * brute-force L2 2-nearest-neighbour search in place of the FLANN KD-tree index of M:241-250 (approximate and randomised: not reproduced).
+ * Every parameter means what it means for isx_match_features, except:
+ *   descriptors  num_images CV_32FC1 mats of n_i x cols, 1 <= cols <= 128 (cols > 128 -> ISX_ERR_UNSUPPORTED), the same cols for every image
+ *                with rows (else ISX_ERR_SIZE), host or device, 4-byte aligned in pointer and step (else ISX_ERR_INVALID); another type ->
+ *                ISX_ERR_TYPE.  Rows may be 0; the row limits are isx_match_features'.
+ *   the search   s(q, t) in float32: s = 0, then for c = 0 .. cols - 1 in that order e = a[c] - b[c], s = s + e * e, every operation
+ *                rounded on its own (no FMA).  An s that is not finite - overflow, or NaN from non-finite input - becomes +inf: nothing is
+ *                refused.  The two nearest rows are the two smallest by (s, row); the distance is d = sqrtf(s), correctly rounded; the
+ *                ratio test is d0 < k * d1.  Two distinct s can round to one d: knn is ordered by s.
+ *   matches      column 2 carries the IEEE-754 bits of the float32 distance d0 (DMatch::distance is a float).
+ *   knn          row0, bits(d0), row1, bits(d1); -1, -1 where there is no such neighbour.
+ * Same statuses, same capture rule, at most three launches a call, no read-back with device mats throughout, the same per-thread scratch
+ * (isx_match_release).  An accepted match has s0 < s1, so the list is that of any exact L2 matcher computing the same distances; parity
+ * with OpenCV is unpinned twice over (the KD-tree is approximate, and its SIMD normL2Sqr sums in another order).                        */
+int isx_match_features_f32(int num_images, const isx_mat* descriptors, const isx_mat* keypoints, const int* image_sizes_wh,
+                           int num_pairs, const int* pairs_ij, float match_conf, isx_mat* matches, isx_mat* points, isx_mat* counts,
+                           isx_mat* knn, int* info, int device, void* hip_stream);
 /* Returns the scratch of the calling thread (the matcher going out of scope).  PER THREAD and not freed at thread exit, as for
  * isx_voronoi_seam_release.                                                                                                            */
 int isx_match_release(void);
