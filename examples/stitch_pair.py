@@ -2,7 +2,7 @@
 """The reference demo's post-registration stage on one pair of images, every step on the GPU through imagestitch_amd
 (needs an MI355X):
 
-    python examples/stitch_pair.py [left.bmp right.bmp] [--register] [--focal F] [--yaw RAD] [--warper cylindrical|spherical|plane] [--blend feather|multiband] [--seam-megapix M] [--out pano.bmp | pano.jpg]
+    python examples/stitch_pair.py [left.bmp right.bmp] [--register [--small]] [--focal F] [--yaw RAD] [--warper cylindrical|spherical|plane] [--blend feather|multiband] [--seam-megapix M] [--out pano.bmp | pano.jpg]
 
 By default registration is replaced by a known rig: two cameras
 with focal length F rotated by -/+ yaw about the vertical axis.  Without input files a synthetic pair is generated.
@@ -26,11 +26,21 @@ import imagestitch_amd as isx  # noqa: E402
 from imagestitch_amd import synth  # noqa: E402
 
 
+def register_views(small=False):
+    """The two views --register takes without input files: overlapping crops of one synthetic scene, 1280 x 720 out of 1600 x 720 - or,
+    small, 480 x 270 out of 600 x 270; three quarters of each crop lie in the other."""
+    h, w, shift = (270, 480, 120) if small else (720, 1280, 320)
+    wide = synth.make_tile(h, w + shift, 0)
+    return [np.ascontiguousarray(wide[:, :w]), np.ascontiguousarray(wide[:, shift:])]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("images", nargs="*")
     ap.add_argument("--register", action="store_true",
                     help="find ORB features, match them and estimate the cameras on the GPU instead of assuming the rig of --focal and --yaw")
+    ap.add_argument("--small", action="store_true",
+                    help="with --register and no input files: crops of 480 x 270 instead of 1280 x 720 (a quick run)")
     ap.add_argument("--focal", type=float, default=None)
     ap.add_argument("--yaw", type=float, default=0.18)
     ap.add_argument("--warper", default="cylindrical", choices=["cylindrical", "spherical", "plane", "fisheye", "stereographic"],
@@ -64,8 +74,7 @@ def main():
     if a.images:
         imgs = [isx.imread(p) for p in a.images[:2]]                       # W:166
     elif a.register:                                                        # two views of one scene: overlapping crops
-        wide = synth.make_tile(720, 1600, 0)
-        imgs = [np.ascontiguousarray(wide[:, :1280]), np.ascontiguousarray(wide[:, 320:])]
+        imgs = register_views(a.small)
     else:
         imgs = [synth.make_tile(720, 1280, i) for i in range(2)]
     H, W = imgs[0].shape[:2]
