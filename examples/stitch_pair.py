@@ -2,7 +2,7 @@
 """The reference demo's post-registration stage on one pair of images, every step on the GPU through imagestitch_amd
 (needs an MI355X):
 
-    python examples/stitch_pair.py [left.bmp right.bmp] [--register [--small]] [--focal F] [--yaw RAD] [--warper cylindrical|spherical|plane] [--blend feather|multiband] [--seam-megapix M] [--out pano.bmp | pano.jpg]
+    python examples/stitch_pair.py [left.bmp right.bmp] [--register [--small] [--features orb|surf]] [--focal F] [--yaw RAD] [--warper cylindrical|spherical|plane] [--blend feather|multiband] [--seam-megapix M] [--out pano.bmp | pano.jpg]
 
 By default registration is replaced by a known rig: two cameras
 with focal length F rotated by -/+ yaw about the vertical axis.  Without input files a synthetic pair is generated.
@@ -26,6 +26,9 @@ import imagestitch_amd as isx  # noqa: E402
 from imagestitch_amd import synth  # noqa: E402
 
 
+BUILT_IN_HESS_THRESH = 100.0
+
+
 def register_views(small=False):
     """The two views --register takes without input files: overlapping crops of one synthetic scene, 1280 x 720 out of 1600 x 720 - or,
     small, 480 x 270 out of 600 x 270; three quarters of each crop lie in the other."""
@@ -41,6 +44,11 @@ def main():
                     help="find ORB features, match them and estimate the cameras on the GPU instead of assuming the rig of --focal and --yaw")
     ap.add_argument("--small", action="store_true",
                     help="with --register and no input files: crops of 480 x 270 instead of 1280 x 720 (a quick run)")
+    ap.add_argument("--features", default="orb", choices=["orb", "surf"],
+                    help="with --register: OrbFeaturesFinder (32-byte descriptors, Hamming) or SurfFeaturesFinder (64 floats, L2)")
+    ap.add_argument("--hess-thresh", type=float, default=None,
+                    help="with --features surf: SurfFeaturesFinder's hess_thresh; default 300, or 100 on the built-in views, whose smooth synthetic "
+                         "scene has no Hessian response above 200")
     ap.add_argument("--focal", type=float, default=None)
     ap.add_argument("--yaw", type=float, default=0.18)
     ap.add_argument("--warper", default="cylindrical", choices=["cylindrical", "spherical", "plane", "fisheye", "stereographic"],
@@ -79,7 +87,9 @@ def main():
         imgs = [synth.make_tile(720, 1280, i) for i in range(2)]
     H, W = imgs[0].shape[:2]
     if a.register:
-        features = isx.OrbFeaturesFinder().find(imgs)                       # F:1034-1040: finder(img, features)
+        hess = a.hess_thresh if a.hess_thresh is not None else (300.0 if a.images else BUILT_IN_HESS_THRESH)
+        finder = isx.SurfFeaturesFinder(hess_thresh=hess) if a.features == "surf" else isx.OrbFeaturesFinder()       # B:36-37: the line the demos comment out
+        features = finder.find(imgs)                                        # F:1034-1040: finder(img, features)
         matcher = isx.BestOf2NearestMatcher(match_conf=0.3)                 # M:307
         info = matcher.match([f.descriptors for f in features], [f.keypoints for f in features], [f.img_size for f in features])   # M:308
         if not info or info[0].H is None:

@@ -119,6 +119,10 @@ _SIGS = {
     "isx_orb_find": [_MP, C.c_void_p, _MP, _MP, _MP, _MP, _MP, C.c_int, C.c_void_p],
     "isx_orb_reserve": [C.c_void_p, C.c_int, C.c_int, C.c_int],
     "isx_orb_release": [],
+    "isx_surf_default_params": [C.c_void_p],
+    "isx_surf_find": [_MP, C.c_void_p, _MP, _MP, _MP, _MP, C.c_int, C.c_void_p],
+    "isx_surf_reserve": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int],
+    "isx_surf_release": [],
     "isx_match_features": [C.c_int, _MP, _MP, _IP, C.c_int, _IP, C.c_float, _MP, _MP, _MP, _MP, _IP, C.c_int, C.c_void_p],
     "isx_match_features_f32": [C.c_int, _MP, _MP, _IP, C.c_int, _IP, C.c_float, _MP, _MP, _MP, _MP, _IP, C.c_int, C.c_void_p],
     "isx_match_release": [],

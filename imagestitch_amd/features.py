@@ -1,6 +1,8 @@
 """The reference's features finder (F = its 特征点检测 demo): OrbFeaturesFinder(grid_size, n_features, scaleFactor, nlevels) and
 find(image, features) (F:40-44, F:948-1017) on the GPU (isx_orb_find, DESIGN.md §8 "Features finder").  The sampling pattern is an input: the
-default is makeRandomPattern(31) (F:709-718); a caller who has OpenCV's learned table passes it through set_pattern."""
+default is makeRandomPattern(31) (F:709-718); a caller who has OpenCV's learned table passes it through set_pattern.
+SurfFeaturesFinder is the finder every main of the reference comments out (isx_surf_find, DESIGN.md §8 "Features finder, SURF"): 64 float32
+a keypoint, which FeaturesMatcher sends to the L2 entry."""
 import ctypes as C
 
 import numpy as np
@@ -59,7 +61,8 @@ def orb_reserve(params, width, height, device=0):
 class ImageFeatures:
     """detail::ImageFeatures as find fills it: img_idx, img_size (width, height), keypoints n x 2 float32 (pt.x, pt.y), meta n x 4 float32
     (size, angle, response, octave), descriptors n x 32 uint8 - row-sliced views of the finder's mats, in canonical order (cell, level, y, x) -
-    and status (ISX_ORB_TRUNCATED | ISX_ORB_BAD_PATTERN)."""
+    and status (ISX_ORB_TRUNCATED | ISX_ORB_BAD_PATTERN).  From SurfFeaturesFinder: meta n x 5 (laplacian last), descriptors n x 64 float32,
+    strongest first, status (ISX_SURF_TRUNCATED | ISX_SURF_CANDIDATES_DROPPED)."""
 
     def __init__(self, img_idx, img_size, keypoints, meta, descriptors, status):
         self.img_idx, self.img_size, self.keypoints, self.meta, self.descriptors, self.status = img_idx, img_size, keypoints, meta, descriptors, status
@@ -107,3 +110,75 @@ class OrbFeaturesFinder:
     def release():
         """Return the scratch the finder keeps per calling thread between calls (isx_orb_release)."""
         check(_lib.load().isx_orb_release())
+
+
+# ISX_SURF_* of include/imagestitch_hip.h
+SURF_MAX_CANDIDATES, SURF_MAX_SIDE, SURF_MAX_PIXELS = 32768, 16384, 1 << 24
+SURF_TRUNCATED, SURF_CANDIDATES_DROPPED = 1, 2
+
+
+class SurfParams(C.Structure):
+    """isx_surf_params"""
+    _fields_ = [("hess_thresh", C.c_double), ("num_octaves", C.c_int), ("num_layers", C.c_int), ("num_octaves_descr", C.c_int),
+                ("num_layers_descr", C.c_int), ("extended", C.c_int), ("upright", C.c_int)]
+
+
+def surf_default_params():
+    p = SurfParams()
+    check(_lib.load().isx_surf_default_params(C.byref(p)))
+    return p
+
+
+def surf_find(image, params, keypoints, meta, descriptors, count_status, device=0, stream=None):
+    """isx_surf_find on caller-allocated outputs: keypoints cap x 2, meta cap x 5 and descriptors cap x 64 float32, count_status 1 x 2 int32,
+    NumPy arrays or CUDA tensors; cap is the smallest of the three row counts; image: uint8 HxW, HxWx3 or HxWx4."""
+    ptr = getattr(stream, "cuda_stream", stream)
+    check(_lib.load().isx_surf_find(C.byref(as_mat(image)), C.byref(params), C.byref(as_mat(keypoints)), C.byref(as_mat(meta)),
+                                    C.byref(as_mat(descriptors)), C.byref(as_mat(count_status)), int(device), C.c_void_p(ptr or 0)))
+
+
+def surf_reserve(params, width, height, cap, device=0):
+    """isx_surf_reserve: size the calling thread's scratch ahead of a stream capture"""
+    check(_lib.load().isx_surf_reserve(C.byref(params), int(width), int(height), int(cap), int(device)))
+
+
+class SurfFeaturesFinder:
+    """SurfFeaturesFinder(double hess_thresh = 300., int num_octaves = 3, int num_layers = 4, int num_octaves_descr = 3,
+    int num_layers_descr = 4) of OpenCV 3.4.2's stitching module.  max_keypoints is the row count of the outputs (cap): the strongest
+    max_keypoints keypoints are returned and ISX_SURF_TRUNCATED says that there were more."""
+
+    def __init__(self, hess_thresh=300., num_octaves=3, num_layers=4, num_octaves_descr=3, num_layers_descr=4, max_keypoints=4096, device=0,
+                 stream=None):
+        p = surf_default_params()
+        p.hess_thresh, p.num_octaves, p.num_layers = float(hess_thresh), int(num_octaves), int(num_layers)
+        p.num_octaves_descr, p.num_layers_descr = int(num_octaves_descr), int(num_layers_descr)
+        self.params, self.device, self.stream, self.capacity = p, device, stream, int(max_keypoints)
+
+    def find(self, images):
+        """find(image, features) for every image (uint8 HxW, HxWx3 or HxWx4; NumPy arrays or CUDA tensors): one ImageFeatures each.  With a
+        CUDA image the outputs are CUDA tensors.  All counts are read back in one synchronisation."""
+        out = []
+        for i, img in enumerate(images):
+            alloc = _allocator("cuda:%d" % int(self.device) if _is_device(img) else None)
+            cap = self.capacity
+            kp, meta, desc, cs = alloc(cap, 2, np.float32), alloc(cap, 5, np.float32), alloc(cap, 64, np.float32), alloc(1, 2, np.int32)
+            surf_find(img, self.params, kp, meta, desc, cs, self.device, self.stream)
+            out.append((i, (int(img.shape[1]), int(img.shape[0])), kp, meta, desc, cs))
+        if any(_is_device(o[5]) for o in out):
+            _synchronize(self.stream, self.device)
+        feats = []
+        for i, size, kp, meta, desc, cs in out:
+            c = cs.cpu().numpy()[0] if _is_device(cs) else cs[0]
+            n = int(c[0])
+            feats.append(ImageFeatures(i, size, kp[:n], meta[:n], desc[:n], int(c[1])))
+        return feats
+
+    __call__ = find
+
+    def reserve(self, width, height):
+        surf_reserve(self.params, width, height, self.capacity, self.device)
+
+    @staticmethod
+    def release():
+        """Return the scratch the finder keeps per calling thread between calls (isx_surf_release)."""
+        check(_lib.load().isx_surf_release())

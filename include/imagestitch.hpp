@@ -434,6 +434,53 @@ private:
     void* stream_;
 };
 
+// The finder every main of the reference comments out: SurfFeaturesFinder(hess_thresh, num_octaves, num_layers, num_octaves_descr,
+// num_layers_descr) of OpenCV 3.4.2's stitching module on the GPU (isx_surf_find; tests/helpers/surf_np.py is the specification, DESIGN.md §8
+// "Features finder, SURF").  Keypoints come strongest first; the descriptors are n x 64 CV_32FC1, which FeaturesMatcher sends to the L2 entry.
+// max_keypoints is the row count of the outputs: the strongest max_keypoints are returned and status() says ISX_SURF_TRUNCATED.
+class SurfFeaturesFinder {
+public:
+    explicit SurfFeaturesFinder(double hess_thresh = 300., int num_octaves = 3, int num_layers = 4, int num_octaves_descr = 3, int num_layers_descr = 4,
+                                int max_keypoints = 4096, int device = 0, void* hip_stream = nullptr)
+        : capacity_(max_keypoints), device_(device), stream_(hip_stream) {
+        check(isx_surf_default_params(&params_));
+        params_.hess_thresh = hess_thresh; params_.num_octaves = num_octaves; params_.num_layers = num_layers;
+        params_.num_octaves_descr = num_octaves_descr; params_.num_layers_descr = num_layers_descr;
+    }
+    void setStream(void* hip_stream) { stream_ = hip_stream; }
+    int capacity() const { return capacity_; }
+    int status() const { return status_; }        // of the last find: ISX_SURF_TRUNCATED | ISX_SURF_CANDIDATES_DROPPED
+    const isx_surf_params& params() const { return params_; }
+    // find(image, features): image CV_8UC1, CV_8UC3 or CV_8UC4, host or device.  features.keypoints holds pt, features.descriptors n x 64
+    // CV_32FC1 on the host; `full`, when given, the whole cv::KeyPoint of each (class_id, the laplacian's sign, is not carried).
+    void find(const Mat& image, ImageFeatures& features, std::vector<KeyPoint>* full = nullptr) {
+        const int cap = capacity_ > 0 ? capacity_ : 1;
+        Mat kp(cap, 2, ISX_32FC1), meta(cap, 5, ISX_32FC1), desc(cap, 64, ISX_32FC1), cs(1, 2, ISX_32SC1);
+        check(isx_surf_find(image.c(), &params_, kp.c(), meta.c(), desc.c(), cs.c(), device_, stream_));
+        const int n = cs.ptr<int>(0)[0];
+        status_ = cs.ptr<int>(0)[1];
+        features.img_size = image.size();
+        features.keypoints.clear();
+        if (full) full->clear();
+        features.descriptors = Mat();
+        if (n > 0) features.descriptors.create(n, 64, ISX_32FC1);
+        for (int r = 0; r < n; ++r) {
+            const float* p = kp.ptr<float>(r);
+            const float* m = meta.ptr<float>(r);
+            features.keypoints.push_back(Point2f(p[0], p[1]));
+            std::memcpy(features.descriptors.ptr<float>(r), desc.ptr<float>(r), 64 * sizeof(float));
+            if (full) { KeyPoint k; k.pt = Point2f(p[0], p[1]); k.size = m[0]; k.angle = m[1]; k.response = m[2]; k.octave = (int)m[3]; full->push_back(k); }
+        }
+    }
+    void operator()(const Mat& image, ImageFeatures& features) { find(image, features); }
+    void reserve(Size image_size) { check(isx_surf_reserve(&params_, image_size.width, image_size.height, capacity_ > 0 ? capacity_ : 1, device_)); }
+    static void release() { check(isx_surf_release()); }
+private:
+    isx_surf_params params_;
+    int capacity_ = 0, status_ = 0, device_;
+    void* stream_;
+};
+
 class FeaturesMatcher {
 public:
     explicit FeaturesMatcher(float match_conf = 0.3f, int device = 0, void* hip_stream = nullptr) : conf_(match_conf), device_(device), stream_(hip_stream) {}

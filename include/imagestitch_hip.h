@@ -704,6 +704,58 @@ int isx_orb_reserve(const isx_orb_params* params, int width, int height, int dev
 /* Returns the scratch of the calling thread.  PER THREAD and not freed at thread exit, as for isx_match_release.                          */
 int isx_orb_release(void);
 
+/* ---- the features finder every main of the reference comments out: `//finder = new SurfFeaturesFinder();` (B:37, C:296, S:1104) ------- */
+/* Limits (surf.hip takes them from here; tests/helpers/surf_np.py repeats them): the maxima that are ranked; pixels a side; pixels.     */
+enum { ISX_SURF_MAX_CANDIDATES = 32768, ISX_SURF_MAX_SIDE = 16384, ISX_SURF_MAX_PIXELS = 1 << 24,
+       ISX_SURF_MAX_OCTAVES = 4, ISX_SURF_MAX_LAYERS = 4 };
+/* status bits of count_status[1] */
+enum { ISX_SURF_TRUNCATED = 1,            /* more keypoints than cap: the first cap in canonical order (strongest first) were written      */
+       ISX_SURF_CANDIDATES_DROPPED = 2 }; /* more than ISX_SURF_MAX_CANDIDATES maxima: the first in scan order (octave, layer, y, x) ranked */
+/* SurfFeaturesFinder(hess_thresh, num_octaves, num_layers, num_octaves_descr, num_layers_descr) of OpenCV 3.4.2's stitching module.      */
+typedef struct isx_surf_params {
+    double hess_thresh;            /* 300; >= 0, compared as (float)                                                         */
+    int    num_octaves;            /* 3; 1 .. ISX_SURF_MAX_OCTAVES                                                           */
+    int    num_layers;             /* 4; 1 .. ISX_SURF_MAX_LAYERS                                                            */
+    int    num_octaves_descr;      /* 3; any value but num_octaves: ISX_ERR_UNSUPPORTED (one detectAndCompute)               */
+    int    num_layers_descr;       /* 4; any value but num_layers: ISX_ERR_UNSUPPORTED                                       */
+    int    extended;               /* 0; non-zero (128 floats): ISX_ERR_UNSUPPORTED                                          */
+    int    upright;                /* 0; non-zero: ISX_ERR_UNSUPPORTED                                                       */
+} isx_surf_params;
+/* The defaults above. */
+int isx_surf_default_params(isx_surf_params* params);
+/* SurfFeaturesFinder::find = SURF::detectAndCompute(image, no mask) with extended = false, upright = false.  OpenCV's source is in neither
+ * tree: the specification is tests/helpers/surf_np.py, which the kernels match bit for bit, and OpenCV parity is UNPINNED (DESIGN.md §8
+ * "Features finder, SURF" lists what is decided).
+ *   gray        as isx_orb_find.
+ *   integral    (rows + 1) x (cols + 1), unsigned 32-bit with wrapping adds; box differences are exact.
+ *   Hessian     octave o < num_octaves, layer l < num_layers + 2: filter (9 + 6 l) << o at step 1 << o; det = dx dy - 0.81f dxy dxy.
+ *   maxima      det > (float)hess_thresh and strictly above its 26 neighbours, then interpolateKeypoint (Cramer's rule in float32).
+ *   order       response, size, octave, pt.y, pt.x descending (KeypointGreater), then the scan index (octave, layer, y, x) ascending.
+ *   angle       113 Haar samples, a 60 degree window every 5 degrees, through the restated atan2f in degrees, [0, 360).
+ *   descriptor  the rotated window walked as OpenCV accumulates it, INTER_AREA to 21 x 21 by the general table, 4 x 4 cells of
+ *               (sum dx, sum dy, sum |dx|, sum |dy|), normalised: 64 floats.
+ *   image        CV_8UC1, CV_8UC3 or CV_8UC4, host or device, any pointer alignment and step, at most ISX_SURF_MAX_SIDE pixels a side and
+ *                ISX_SURF_MAX_PIXELS pixels.
+ *   keypoints    CV_32FC1, cap x 2: pt.x, pt.y - the layout the matchers take.
+ *   meta         CV_32FC1, cap x 5: size, angle, response, octave, laplacian (the sign of the trace).
+ *   descriptors  CV_32FC1, cap x 64 - the layout isx_match_features_f32 takes.
+ *   count_status CV_32SC1, at least 1 x 2: the number of keypoints, the status bits.  Rows from count on are not written.
+ * cap is the caller's: the smallest row count of keypoints, meta and descriptors, at least 1 (ISX_ERR_SIZE).  Every output is 4-byte
+ * aligned in pointer and step.  Checked before anything is written or enqueued: null pointers, a parameter out of range, a misaligned mat
+ * -> ISX_ERR_INVALID; another descriptor octave / layer pair, extended, upright, a side or a pixel count past its limit ->
+ * ISX_ERR_UNSUPPORTED; a mat of another type -> ISX_ERR_TYPE; an empty image, too few rows or columns -> ISX_ERR_SIZE.
+ * With device mats throughout nothing is read back or synchronised.  Host mats synchronise.  On a capturing stream the call works with
+ * device mats once isx_surf_reserve has sized the scratch; a host mat, or a call that would have to grow the scratch, -> ISX_ERR_STATE
+ * with nothing enqueued.  The launch count depends on num_octaves only.                                                                  */
+int isx_surf_find(const isx_mat* image, const isx_surf_params* params, isx_mat* keypoints, isx_mat* meta, isx_mat* descriptors,
+                  isx_mat* count_status, int device, void* hip_stream);
+/* Sizes the calling thread's scratch for device images of up to width x height under `params` and device outputs of `cap` rows, ahead of
+ * a stream capture.  A captured graph keeps pointing at this scratch: growing or releasing it while such a graph exists is the caller's
+ * error.                                                                                                                                  */
+int isx_surf_reserve(const isx_surf_params* params, int width, int height, int cap, int device);
+/* Returns the scratch of the calling thread.  PER THREAD and not freed at thread exit, as for isx_orb_release.                           */
+int isx_surf_release(void);
+
 /* ---- the features matcher of the M demo (M = the reference's 特征点匹配/特征点匹配/特征点匹配.cpp) --------------------------------- */
 /* The tiling of the search kernel (match.hip takes them from here; imagestitch_amd/matcher.py repeats them): queries per block, train rows
  * per LDS tile, train rows per work item, and the row limits - the width of the packed key distance << 22 | row.                          */
