@@ -2,7 +2,7 @@
 """The reference demo's post-registration stage on one pair of images, every step on the GPU through imagestitch_amd
 (needs an MI355X):
 
-    python examples/stitch_pair.py [left.bmp right.bmp] [--register [--small] [--features orb|surf]] [--focal F] [--yaw RAD] [--warper cylindrical|spherical|plane] [--blend feather|multiband] [--seam-megapix M] [--out pano.bmp | pano.jpg]
+    python examples/stitch_pair.py [left.bmp right.bmp] [--register [--small] [--features orb|surf|sift]] [--focal F] [--yaw RAD] [--warper cylindrical|spherical|plane] [--blend feather|multiband] [--seam-megapix M] [--out pano.bmp | pano.jpg]
 
 By default registration is replaced by a known rig: two cameras
 with focal length F rotated by -/+ yaw about the vertical axis.  Without input files a synthetic pair is generated.
@@ -27,6 +27,7 @@ from imagestitch_amd import synth  # noqa: E402
 
 
 BUILT_IN_HESS_THRESH = 100.0
+BUILT_IN_CONTRAST_THRESHOLD = 0.02
 
 
 def register_views(small=False):
@@ -44,8 +45,12 @@ def main():
                     help="find ORB features, match them and estimate the cameras on the GPU instead of assuming the rig of --focal and --yaw")
     ap.add_argument("--small", action="store_true",
                     help="with --register and no input files: crops of 480 x 270 instead of 1280 x 720 (a quick run)")
-    ap.add_argument("--features", default="orb", choices=["orb", "surf"],
-                    help="with --register: OrbFeaturesFinder (32-byte descriptors, Hamming) or SurfFeaturesFinder (64 floats, L2)")
+    ap.add_argument("--features", default="orb", choices=["orb", "surf", "sift"],
+                    help="with --register: OrbFeaturesFinder (32-byte descriptors, Hamming), SurfFeaturesFinder (64 floats, L2) or "
+                         "SiftFeaturesFinder (128 floats, L2)")
+    ap.add_argument("--contrast-threshold", type=float, default=None,
+                    help="with --features sift: SiftFeaturesFinder's contrast_threshold; default 0.04, or 0.02 on the built-in views, whose smooth "
+                         "synthetic scene leaves 15 keypoints a view at 0.04")
     ap.add_argument("--hess-thresh", type=float, default=None,
                     help="with --features surf: SurfFeaturesFinder's hess_thresh; default 300, or 100 on the built-in views, whose smooth synthetic "
                          "scene has no Hessian response above 200")
@@ -89,6 +94,9 @@ def main():
     if a.register:
         hess = a.hess_thresh if a.hess_thresh is not None else (300.0 if a.images else BUILT_IN_HESS_THRESH)
         finder = isx.SurfFeaturesFinder(hess_thresh=hess) if a.features == "surf" else isx.OrbFeaturesFinder()       # B:36-37: the line the demos comment out
+        if a.features == "sift":                                            # cv::Stitcher's other finder; stitching_detailed --features sift
+            contrast = a.contrast_threshold if a.contrast_threshold is not None else (0.04 if a.images else BUILT_IN_CONTRAST_THRESHOLD)
+            finder = isx.SiftFeaturesFinder(contrast_threshold=contrast)
         features = finder.find(imgs)                                        # F:1034-1040: finder(img, features)
         matcher = isx.BestOf2NearestMatcher(match_conf=0.3)                 # M:307
         info = matcher.match([f.descriptors for f in features], [f.keypoints for f in features], [f.img_size for f in features])   # M:308

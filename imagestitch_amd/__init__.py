@@ -13,6 +13,7 @@ from .adjuster import (WAVE_CORRECT_HORIZ, WAVE_CORRECT_VERT, BundleAdjusterRay,
 from .exposure import BlocksGainCompensator, GainCompensator  # noqa: F401
 from .imgio import imread, imwrite  # noqa: F401
 from .features import ImageFeatures, OrbFeaturesFinder, orb_find, SurfFeaturesFinder, SurfParams, surf_find, surf_reserve  # noqa: F401
+from .features import SiftFeaturesFinder, SiftParams, sift_find, sift_reserve  # noqa: F401
 from .homography import BestOf2NearestMatcher, find_homography  # noqa: F401
 from .matcher import FeaturesMatcher, MatchesInfo  # noqa: F401
 from .resize import dilate_resize_and, resize  # noqa: F401
@@ -21,4 +22,4 @@ from ._lib import WARP_CYLINDRICAL, WARP_FISHEYE, WARP_PLANE, WARP_SPHERICAL, WA
 from .warper import (CylindricalWarper, FisheyeWarper, PlaneWarper, RotationWarper, SphericalWarper, StereographicWarper,  # noqa: F401
                      remap)
 
-__all__ = ["Blender", "MultiBandBlender", "FeatherBlender", "NoBlender", "convert_to", "dilate_and", "gain_apply", "GainCompensator", "BlocksGainCompensator", "imread", "imwrite", "resize", "dilate_resize_and", "INTER_NEAREST", "INTER_LINEAR", "seam_estimate", "seam_gradients", "DP_COLOR", "DP_COLOR_GRAD", "DpSeamFinder", "GraphCutSeamFinder", "VoronoiSeamFinder", "OrbFeaturesFinder", "ImageFeatures", "orb_find", "SurfFeaturesFinder", "SurfParams", "surf_find", "surf_reserve", "FeaturesMatcher", "BestOf2NearestMatcher", "MatchesInfo", "find_homography", "CameraParams", "HomographyBasedEstimator", "estimate_cameras", "BundleAdjusterRay", "bundle_adjust_ray", "BundleAdjusterReproj", "bundle_adjust_reproj", "wave_correct", "waveCorrect", "WAVE_CORRECT_HORIZ", "WAVE_CORRECT_VERT", "remap", "CylindricalWarper", "SphericalWarper", "PlaneWarper", "FisheyeWarper", "StereographicWarper", "WARP_CYLINDRICAL", "WARP_SPHERICAL", "WARP_PLANE", "WARP_FISHEYE", "WARP_STEREOGRAPHIC", "RotationWarper", "IsxError", "load"]
+__all__ = ["Blender", "MultiBandBlender", "FeatherBlender", "NoBlender", "convert_to", "dilate_and", "gain_apply", "GainCompensator", "BlocksGainCompensator", "imread", "imwrite", "resize", "dilate_resize_and", "INTER_NEAREST", "INTER_LINEAR", "seam_estimate", "seam_gradients", "DP_COLOR", "DP_COLOR_GRAD", "DpSeamFinder", "GraphCutSeamFinder", "VoronoiSeamFinder", "OrbFeaturesFinder", "ImageFeatures", "orb_find", "SurfFeaturesFinder", "SurfParams", "surf_find", "surf_reserve", "SiftFeaturesFinder", "SiftParams", "sift_find", "sift_reserve", "FeaturesMatcher", "BestOf2NearestMatcher", "MatchesInfo", "find_homography", "CameraParams", "HomographyBasedEstimator", "estimate_cameras", "BundleAdjusterRay", "bundle_adjust_ray", "BundleAdjusterReproj", "bundle_adjust_reproj", "wave_correct", "waveCorrect", "WAVE_CORRECT_HORIZ", "WAVE_CORRECT_VERT", "remap", "CylindricalWarper", "SphericalWarper", "PlaneWarper", "FisheyeWarper", "StereographicWarper", "WARP_CYLINDRICAL", "WARP_SPHERICAL", "WARP_PLANE", "WARP_FISHEYE", "WARP_STEREOGRAPHIC", "RotationWarper", "IsxError", "load"]

@@ -123,6 +123,10 @@ _SIGS = {
     "isx_surf_find": [_MP, C.c_void_p, _MP, _MP, _MP, _MP, C.c_int, C.c_void_p],
     "isx_surf_reserve": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int],
     "isx_surf_release": [],
+    "isx_sift_default_params": [C.c_void_p],
+    "isx_sift_find": [_MP, C.c_void_p, _MP, _MP, _MP, _MP, C.c_int, C.c_void_p],
+    "isx_sift_reserve": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int],
+    "isx_sift_release": [],
     "isx_match_features": [C.c_int, _MP, _MP, _IP, C.c_int, _IP, C.c_float, _MP, _MP, _MP, _MP, _IP, C.c_int, C.c_void_p],
     "isx_match_features_f32": [C.c_int, _MP, _MP, _IP, C.c_int, _IP, C.c_float, _MP, _MP, _MP, _MP, _IP, C.c_int, C.c_void_p],
     "isx_match_release": [],
@@ -192,6 +196,8 @@ _SIGS = {
     "isx_selftest_bundle_math_device": [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)],
     "isx_selftest_proj_math": [C.c_int, C.c_int, _F9, _F9, _F9],
     "isx_selftest_proj_math_device": [C.c_int, C.c_int, _F9, _F9, _F9],
+    "isx_selftest_sift_math": [C.c_int, C.c_int, _F9, _F9],
+    "isx_selftest_sift_math_device": [C.c_int, C.c_int, _F9, _F9],
     "isx_profile_enable": [C.c_int],
     "isx_profile_reset": [],
     "isx_profile_filter": [C.c_char_p],

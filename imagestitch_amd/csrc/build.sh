@@ -13,7 +13,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="-O3 -std=c++17 --offload-arch=gfx950 -fPIC -ffp-contract=off -fno-fast-math -fno-slp-vectorize -Wall -Wno-unused-function ${ISX_EXTRA_FLAGS:-}"
 mkdir -p build
 pids=()
-for f in isx_core.cpp imgio.cpp jpegdec.cpp seamfind.cpp gather.cpp warp.hip warp_polar.hip blend.hip prep.hip linear_blend.hip seam.hip gain.hip blocks_gain.hip graphcut.hip voronoi.hip resize.hip orb.hip surf.hip match.hip homography.hip estimator.hip bundle.hip; do
+for f in isx_core.cpp imgio.cpp jpegdec.cpp seamfind.cpp gather.cpp warp.hip warp_polar.hip blend.hip prep.hip linear_blend.hip seam.hip gain.hip blocks_gain.hip graphcut.hip voronoi.hip resize.hip orb.hip surf.hip sift.hip match.hip homography.hip estimator.hip bundle.hip; do
     [ -f "$f" ] || continue
     o=build/${f%.*}.o
     stale=0

@@ -24,6 +24,7 @@
 //                    model's order; gradients and cell sums through LDS; one work item the double-precision norm
 // No float atomics, no atomics at all; nothing read back on device mats.
 #include "isx_device.hpp"
+#include "block_scan.hpp"
 #include "pairwise.hpp"
 #include "scratch.hpp"
 #include "proj_math.hpp"
@@ -104,35 +105,6 @@ __host__ __device__ inline SfBox sf_resize_box(int x1, int y1, int x2, int y2, i
     return b;
 }
 
-// The exclusive count of `flag` over the block's threads in thread order, and the block's total.  `cnt` is this call's own LDS row.
-template <int NT>
-__device__ __forceinline__ int sf_count_before(bool flag, int* cnt, int& total) {
-    const int lane = (int)(threadIdx.x & (WAVE - 1)), wv = (int)(threadIdx.x / WAVE);
-    const unsigned long long bal = __ballot(flag);
-    if (lane == 0) cnt[wv] = __popcll(bal);
-    __syncthreads();
-    int before = __popcll(bal & ((1ull << lane) - 1ull));
-    total = 0;
-#pragma unroll
-    for (int i = 0; i < NT / WAVE; ++i) { const int c = cnt[i]; before += i < wv ? c : 0; total += c; }
-    return before;
-}
-// The exclusive sum of v over the block's threads in thread order, and the block's total (one barrier; `tot` is NT / WAVE ints of LDS).
-template <int NT>
-__device__ __forceinline__ int sf_sum_before(int v, int* tot, int& total) {
-    const int lane = (int)(threadIdx.x & (WAVE - 1)), wv = (int)(threadIdx.x / WAVE);
-    int upto = v;
-#pragma unroll
-    for (int o = 1; o < WAVE; o <<= 1) { const int n = __shfl_up(upto, o, WAVE); upto += lane >= o ? n : 0; }
-    if (lane == WAVE - 1) tot[wv] = upto;
-    __syncthreads();
-    int before = upto - v;
-    total = 0;
-#pragma unroll
-    for (int i = 0; i < NT / WAVE; ++i) { const int c = tot[i]; before += i < wv ? c : 0; total += c; }
-    return before;
-}
-
 template <int CN>
 __global__ __launch_bounds__(256) void k_surf_rows(const unsigned char* __restrict__ src, long long sstep, int W, int H, unsigned char* __restrict__ gray,
                                                    unsigned* __restrict__ S) {
@@ -190,18 +162,6 @@ __global__ __launch_bounds__(256) void k_surf_hessian(SfOctave Q, const unsigned
     trace[at] = dx + dy;
 }
 
-// Matx_FastSolveOp<float, 3, 1>
-__device__ __forceinline__ bool sf_solve3(float a00, float a01, float a02, float a10, float a11, float a12, float a20, float a21, float a22, float b0, float b1,
-                                          float b2, float& x0, float& x1, float& x2) {
-    float d = a00 * (a11 * a22 - a12 * a21) - a01 * (a10 * a22 - a12 * a20) + a02 * (a10 * a21 - a11 * a20);
-    if (d == 0.f) return false;
-    d = 1.f / d;
-    x0 = d * (b0 * (a11 * a22 - a12 * a21) - a01 * (b1 * a22 - a12 * b2) + a02 * (b1 * a21 - a11 * b2));
-    x1 = d * (a00 * (b1 * a22 - a12 * b2) - b0 * (a10 * a22 - a12 * a20) + a02 * (a10 * b2 - b1 * a20));
-    x2 = d * (a00 * (a11 * b2 - b1 * a21) - a01 * (a10 * b2 - b1 * a20) + b0 * (a10 * a21 - a11 * a20));
-    return true;
-}
-
 // candidates: six rows of SF_MAX floats: pt.x, pt.y, size, response, octave, laplacian
 template <bool WRITE>
 __global__ __launch_bounds__(256) void k_surf_maxima(SfPlan P, const float* __restrict__ det, const float* __restrict__ trace, int* __restrict__ blk_count,
@@ -240,7 +200,7 @@ __global__ __launch_bounds__(256) void k_surf_maxima(SfPlan P, const float* __re
                 const float a01 = (N1[8] - N1[6] - N1[2] + N1[0]) / 4.f, a02 = (N2[5] - N2[3] - N0[5] + N0[3]) / 4.f, a12 = (N2[7] - N2[1] - N0[7] + N0[1]) / 4.f;
                 const float a00 = N1[3] - 2.f * N1[4] + N1[5], a11 = N1[1] - 2.f * N1[4] + N1[7], a22 = N0[4] - 2.f * N1[4] + N2[4];
                 float x0, x1, x2;
-                if (sf_solve3(a00, a01, a02, a01, a11, a12, a02, a12, a22, b0, b1, b2, x0, x1, x2) && (x0 != 0.f || x1 != 0.f || x2 != 0.f) && fabsf(x0) <= 1.f &&
+                if (fast_solve3(a00, a01, a02, a01, a11, a12, a02, a12, a22, b0, b1, b2, x0, x1, x2) && (x0 != 0.f || x1 != 0.f || x2 != 0.f) && fabsf(x0) <= 1.f &&
                     fabsf(x1) <= 1.f && fabsf(x2) <= 1.f) {
                     keep = true;
                     px = cx + x0 * (float)G.step; py = cy + x1 * (float)G.step;
@@ -253,7 +213,7 @@ __global__ __launch_bounds__(256) void k_surf_maxima(SfPlan P, const float* __re
         }
     }
     int total;
-    const int before = sf_count_before<256>(keep, s_cnt, total);
+    const int before = block_count_before<256>(keep, s_cnt, total);
     if constexpr (!WRITE) {
         if (t == 0) blk_count[blk] = total;
     } else {
@@ -273,7 +233,7 @@ __global__ __launch_bounds__(SF_SCAN_NT) void k_surf_prefix(int n, const int* __
     for (long long i = lo; i < hi; ++i) mine += cnt[i];
     // (a count that passes 2^31 cannot occur: there are fewer search positions than ISX_SURF_MAX_PIXELS * 4 / 3 * 4 < 2^27)
     int total;
-    int run = sf_sum_before<SF_SCAN_NT>((int)mine, s_tot, total);
+    int run = block_sum_before<SF_SCAN_NT>((int)mine, s_tot, total);
     for (long long i = lo; i < hi; ++i) { base[i] = run; run += cnt[i]; }
     if (t == 0) {
         ncand_status[0] = total < SF_MAX ? total : SF_MAX;
@@ -333,7 +293,7 @@ __global__ __launch_bounds__(SF_ORI_NT) void k_surf_orient(int rows, int cols, c
     const int di = t / 13 - 6, dj = t % 13 - 6;
     const bool in_disc = t < 169 && di * di + dj * dj <= 36;
     int total;
-    const int at = sf_count_before<SF_ORI_NT>(in_disc, s_cnt, total);
+    const int at = block_count_before<SF_ORI_NT>(in_disc, s_cnt, total);
     if (in_disc && at < SF_ORI_POINTS) { s_pi[at] = di; s_pj[at] = dj; }      // (the disc has exactly SF_ORI_POINTS points)
     __syncthreads();
     bool use = false;
@@ -391,7 +351,7 @@ __global__ __launch_bounds__(SF_SCAN_NT) void k_surf_compact(const int* __restri
     int mine = 0;
     for (int i = lo; i < hi; ++i) mine += valid[i];
     int total;
-    int run = sf_sum_before<SF_SCAN_NT>(mine, s_tot, total);
+    int run = block_sum_before<SF_SCAN_NT>(mine, s_tot, total);
     for (int i = lo; i < hi; ++i) {
         const int v = valid[i];
         slot[i] = v ? run : -1;

@@ -2,7 +2,8 @@
 find(image, features) (F:40-44, F:948-1017) on the GPU (isx_orb_find, DESIGN.md §8 "Features finder").  The sampling pattern is an input: the
 default is makeRandomPattern(31) (F:709-718); a caller who has OpenCV's learned table passes it through set_pattern.
 SurfFeaturesFinder is the finder every main of the reference comments out (isx_surf_find, DESIGN.md §8 "Features finder, SURF"): 64 float32
-a keypoint, which FeaturesMatcher sends to the L2 entry."""
+a keypoint, which FeaturesMatcher sends to the L2 entry.  SiftFeaturesFinder is the finder cv::Stitcher and stitching_detailed --features sift
+offer beside them (isx_sift_find, DESIGN.md §8 "Features finder, SIFT"): 128 float32 a keypoint, the same entry."""
 import ctypes as C
 
 import numpy as np
@@ -62,7 +63,8 @@ class ImageFeatures:
     """detail::ImageFeatures as find fills it: img_idx, img_size (width, height), keypoints n x 2 float32 (pt.x, pt.y), meta n x 4 float32
     (size, angle, response, octave), descriptors n x 32 uint8 - row-sliced views of the finder's mats, in canonical order (cell, level, y, x) -
     and status (ISX_ORB_TRUNCATED | ISX_ORB_BAD_PATTERN).  From SurfFeaturesFinder: meta n x 5 (laplacian last), descriptors n x 64 float32,
-    strongest first, status (ISX_SURF_TRUNCATED | ISX_SURF_CANDIDATES_DROPPED)."""
+    strongest first, status (ISX_SURF_TRUNCATED | ISX_SURF_CANDIDATES_DROPPED).  From SiftFeaturesFinder: meta n x 5 (octave from -1, then the
+    layer), descriptors n x 128 float32, strongest first, status (ISX_SIFT_TRUNCATED | ISX_SIFT_CANDIDATES_DROPPED)."""
 
     def __init__(self, img_idx, img_size, keypoints, meta, descriptors, status):
         self.img_idx, self.img_size, self.keypoints, self.meta, self.descriptors, self.status = img_idx, img_size, keypoints, meta, descriptors, status
@@ -182,3 +184,75 @@ class SurfFeaturesFinder:
     def release():
         """Return the scratch the finder keeps per calling thread between calls (isx_surf_release)."""
         check(_lib.load().isx_surf_release())
+
+
+# ISX_SIFT_* of include/imagestitch_hip.h
+SIFT_MAX_CANDIDATES, SIFT_MAX_SIDE, SIFT_MAX_PIXELS = 32768, 8192, 1 << 23
+SIFT_TRUNCATED, SIFT_CANDIDATES_DROPPED = 1, 2
+
+
+class SiftParams(C.Structure):
+    """isx_sift_params"""
+    _fields_ = [("nfeatures", C.c_int), ("n_octave_layers", C.c_int), ("contrast_threshold", C.c_double), ("edge_threshold", C.c_double),
+                ("sigma", C.c_double)]
+
+
+def sift_default_params():
+    p = SiftParams()
+    check(_lib.load().isx_sift_default_params(C.byref(p)))
+    return p
+
+
+def sift_find(image, params, keypoints, meta, descriptors, count_status, device=0, stream=None):
+    """isx_sift_find on caller-allocated outputs: keypoints cap x 2, meta cap x 5 and descriptors cap x 128 float32, count_status 1 x 2 int32,
+    NumPy arrays or CUDA tensors; cap is the smallest of the three row counts; image: uint8 HxW, HxWx3 or HxWx4."""
+    ptr = getattr(stream, "cuda_stream", stream)
+    check(_lib.load().isx_sift_find(C.byref(as_mat(image)), C.byref(params), C.byref(as_mat(keypoints)), C.byref(as_mat(meta)),
+                                    C.byref(as_mat(descriptors)), C.byref(as_mat(count_status)), int(device), C.c_void_p(ptr or 0)))
+
+
+def sift_reserve(params, width, height, cap, device=0):
+    """isx_sift_reserve: size the calling thread's scratch ahead of a stream capture"""
+    check(_lib.load().isx_sift_reserve(C.byref(params), int(width), int(height), int(cap), int(device)))
+
+
+class SiftFeaturesFinder:
+    """SIFT::create(int nfeatures = 0, int nOctaveLayers = 3, double contrastThreshold = 0.04, double edgeThreshold = 10, double sigma = 1.6)
+    of OpenCV 4.x, the finder cv::Stitcher and stitching_detailed --features sift offer.  max_keypoints is the row count of the outputs (cap):
+    the strongest max_keypoints keypoints are returned and ISX_SIFT_TRUNCATED says that there were more.  ImageFeatures: meta n x 5 (size,
+    angle, response, octave from -1, layer), descriptors n x 128 float32, strongest first."""
+
+    def __init__(self, nfeatures=0, n_octave_layers=3, contrast_threshold=0.04, edge_threshold=10, sigma=1.6, max_keypoints=4096, device=0, stream=None):
+        p = sift_default_params()
+        p.nfeatures, p.n_octave_layers = int(nfeatures), int(n_octave_layers)
+        p.contrast_threshold, p.edge_threshold, p.sigma = float(contrast_threshold), float(edge_threshold), float(sigma)
+        self.params, self.device, self.stream, self.capacity = p, device, stream, int(max_keypoints)
+
+    def find(self, images):
+        """find(image, features) for every image (uint8 HxW, HxWx3 or HxWx4; NumPy arrays or CUDA tensors): one ImageFeatures each.  With a
+        CUDA image the outputs are CUDA tensors.  All counts are read back in one synchronisation."""
+        out = []
+        for i, img in enumerate(images):
+            alloc = _allocator("cuda:%d" % int(self.device) if _is_device(img) else None)
+            cap = self.capacity
+            kp, meta, desc, cs = alloc(cap, 2, np.float32), alloc(cap, 5, np.float32), alloc(cap, 128, np.float32), alloc(1, 2, np.int32)
+            sift_find(img, self.params, kp, meta, desc, cs, self.device, self.stream)
+            out.append((i, (int(img.shape[1]), int(img.shape[0])), kp, meta, desc, cs))
+        if any(_is_device(o[5]) for o in out):
+            _synchronize(self.stream, self.device)
+        feats = []
+        for i, size, kp, meta, desc, cs in out:
+            c = cs.cpu().numpy()[0] if _is_device(cs) else cs[0]
+            n = int(c[0])
+            feats.append(ImageFeatures(i, size, kp[:n], meta[:n], desc[:n], int(c[1])))
+        return feats
+
+    __call__ = find
+
+    def reserve(self, width, height):
+        sift_reserve(self.params, width, height, self.capacity, self.device)
+
+    @staticmethod
+    def release():
+        """Return the scratch the finder keeps per calling thread between calls (isx_sift_release)."""
+        check(_lib.load().isx_sift_release())

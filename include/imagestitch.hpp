@@ -481,6 +481,58 @@ private:
     void* stream_;
 };
 
+// The finder cv::Stitcher and stitching_detailed --features sift offer beside the two above: SIFT::create(nfeatures, nOctaveLayers,
+// contrastThreshold, edgeThreshold, sigma) of OpenCV 4.x on the GPU (isx_sift_find; tests/helpers/sift_np.py is the specification, DESIGN.md §8
+// "Features finder, SIFT").  Keypoints come strongest first; the descriptors are n x 128 CV_32FC1, which FeaturesMatcher sends to the L2 entry.
+// max_keypoints is the row count of the outputs: the strongest max_keypoints are returned and status() says ISX_SIFT_TRUNCATED.
+class SiftFeaturesFinder {
+public:
+    explicit SiftFeaturesFinder(int nfeatures = 0, int n_octave_layers = 3, double contrast_threshold = 0.04, double edge_threshold = 10, double sigma = 1.6,
+                                int max_keypoints = 4096, int device = 0, void* hip_stream = nullptr)
+        : capacity_(max_keypoints), device_(device), stream_(hip_stream) {
+        check(isx_sift_default_params(&params_));
+        params_.nfeatures = nfeatures; params_.n_octave_layers = n_octave_layers; params_.contrast_threshold = contrast_threshold;
+        params_.edge_threshold = edge_threshold; params_.sigma = sigma;
+    }
+    void setStream(void* hip_stream) { stream_ = hip_stream; }
+    int capacity() const { return capacity_; }
+    int status() const { return status_; }        // of the last find: ISX_SIFT_TRUNCATED | ISX_SIFT_CANDIDATES_DROPPED
+    const isx_sift_params& params() const { return params_; }
+    // find(image, features): image CV_8UC1, CV_8UC3 or CV_8UC4, host or device.  features.keypoints holds pt, features.descriptors n x 128
+    // CV_32FC1 on the host; `full`, when given, the whole cv::KeyPoint of each: octave is packed as SIFT packs it, (octave & 255) | (layer << 8), without
+    // the byte of the sub-layer offset.
+    void find(const Mat& image, ImageFeatures& features, std::vector<KeyPoint>* full = nullptr) {
+        const int cap = capacity_ > 0 ? capacity_ : 1;
+        Mat kp(cap, 2, ISX_32FC1), meta(cap, 5, ISX_32FC1), desc(cap, 128, ISX_32FC1), cs(1, 2, ISX_32SC1);
+        check(isx_sift_find(image.c(), &params_, kp.c(), meta.c(), desc.c(), cs.c(), device_, stream_));
+        const int n = cs.ptr<int>(0)[0];
+        status_ = cs.ptr<int>(0)[1];
+        features.img_size = image.size();
+        features.keypoints.clear();
+        if (full) full->clear();
+        features.descriptors = Mat();
+        if (n > 0) features.descriptors.create(n, 128, ISX_32FC1);
+        for (int r = 0; r < n; ++r) {
+            const float* p = kp.ptr<float>(r);
+            const float* m = meta.ptr<float>(r);
+            features.keypoints.push_back(Point2f(p[0], p[1]));
+            std::memcpy(features.descriptors.ptr<float>(r), desc.ptr<float>(r), 128 * sizeof(float));
+            if (full) {
+                KeyPoint k;
+                k.pt = Point2f(p[0], p[1]); k.size = m[0]; k.angle = m[1]; k.response = m[2]; k.octave = ((int)m[3] & 255) | ((int)m[4] << 8);
+                full->push_back(k);
+            }
+        }
+    }
+    void operator()(const Mat& image, ImageFeatures& features) { find(image, features); }
+    void reserve(Size image_size) { check(isx_sift_reserve(&params_, image_size.width, image_size.height, capacity_ > 0 ? capacity_ : 1, device_)); }
+    static void release() { check(isx_sift_release()); }
+private:
+    isx_sift_params params_;
+    int capacity_ = 0, status_ = 0, device_;
+    void* stream_;
+};
+
 class FeaturesMatcher {
 public:
     explicit FeaturesMatcher(float match_conf = 0.3f, int device = 0, void* hip_stream = nullptr) : conf_(match_conf), device_(device), stream_(hip_stream) {}

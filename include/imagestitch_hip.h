@@ -756,6 +756,63 @@ int isx_surf_reserve(const isx_surf_params* params, int width, int height, int c
 /* Returns the scratch of the calling thread.  PER THREAD and not freed at thread exit, as for isx_orb_release.                           */
 int isx_surf_release(void);
 
+/* ---- the third finder cv::Stitcher and stitching_detailed --features sift offer: SIFT, 128 floats a keypoint ------------------------- */
+/* Limits (sift.hip takes them from here; tests/helpers/sift_np.py repeats them): the candidates that are ranked; source pixels a side;
+ * source pixels (a 3840 x 2160 frame fits).  The doubled pyramid of ISX_SIFT_MAX_PIXELS source pixels is about 2 GiB of scratch: six
+ * Gaussian and five DoG layers an octave and one row-pass buffer, float32, at four times the source's pixels in the first octave.      */
+enum { ISX_SIFT_MAX_CANDIDATES = 32768, ISX_SIFT_MAX_SIDE = 8192, ISX_SIFT_MAX_PIXELS = 1 << 23 };
+/* status bits of count_status[1] */
+enum { ISX_SIFT_TRUNCATED = 1,            /* more keypoints than cap: the first cap in canonical order (strongest first) were written       */
+       ISX_SIFT_CANDIDATES_DROPPED = 2 }; /* more than ISX_SIFT_MAX_CANDIDATES candidates: the first in scan order (octave, layer, r, c) kept */
+/* SIFT::create(nfeatures, nOctaveLayers, contrastThreshold, edgeThreshold, sigma) of OpenCV 4.x.                                         */
+typedef struct isx_sift_params {
+    int    nfeatures;              /* 0: all; > 0: the strongest nfeatures (no keep-the-ties rule); < 0: ISX_ERR_INVALID       */
+    int    n_octave_layers;        /* 3; any other value: ISX_ERR_UNSUPPORTED (the blur taps are committed tables)             */
+    double contrast_threshold;     /* 0.04; in [0, 3e38], compared as (float)                                                  */
+    double edge_threshold;         /* 10; in (0, 3e38], compared as (float)                                                    */
+    double sigma;                  /* 1.6; any other value: ISX_ERR_UNSUPPORTED                                                */
+} isx_sift_params;
+/* The defaults above. */
+int isx_sift_default_params(isx_sift_params* params);
+/* SIFT::detectAndCompute(image, noArray()) (float DoG, SIFT_FIXPT_SCALE 1, firstOctave -1).  OpenCV's source is in neither tree: the
+ * specification is tests/helpers/sift_np.py, which the kernels match bit for bit, and OpenCV parity is UNPINNED (DESIGN.md §8 "Features
+ * finder, SIFT" lists what is decided).
+ *   gray        as isx_orb_find, converted to float32.
+ *   base        resize to (2 cols, 2 rows) with the CV_32F INTER_LINEAR taps of isx_resize, blurred by sqrt(1.6^2 - 1).
+ *   octaves     the largest c with 2^(2 c + 1) <= m^2, m the smaller side of the doubled image (cvRound(log2 m - 2) + 1 in integers); an
+ *               octave narrower than 11 pixels either way and every octave after it are not built.
+ *   pyramid     6 Gaussian layers an octave, each a separable blur of the one before (committed taps, BORDER_REFLECT_101 repeated, rows
+ *               first, the symmetric sum order); the next octave starts from layer 3 at (2 x, 2 y); 5 DoG layers.
+ *   extrema     |v| > floor(0.5 contrast_threshold / 3 * 255) and v >= (v > 0) or <= (v < 0) its 26 neighbours, 5 pixels inside, then
+ *               adjustLocalExtrema (Cramer's rule in float32, at most 5 steps, the contrast and the edge tests).
+ *   duplicates  a candidate is removed when an earlier one in scan order ends on the same (octave, layer, r, c).
+ *   order       response, size, octave, pt.y, pt.x descending, then the scan index (octave, layer, r, c of the starting pixel) ascending;
+ *               keypoints follow their candidate's rank, then the ascending bin of the orientation histogram.
+ *   angle       36 bins, each summed in sample order, through the restated atan2f in degrees and sift_math.hpp's expf; one keypoint a peak.
+ *   descriptor  4 x 4 x 8 trilinear, each cell summed in sample order, clipped at 0.2, scaled by 512, rounded to 0 .. 255: 128 floats.
+ *   image        CV_8UC1, CV_8UC3 or CV_8UC4, host or device, any pointer alignment and step, at most ISX_SIFT_MAX_SIDE pixels a side and
+ *                ISX_SIFT_MAX_PIXELS pixels.
+ *   keypoints    CV_32FC1, cap x 2: pt.x, pt.y in source pixels - the layout the matchers take.
+ *   meta         CV_32FC1, cap x 5: size, angle, response, octave (-1 upward), layer (1 .. 3).
+ *   descriptors  CV_32FC1, cap x 128 - the layout isx_match_features_f32 takes.
+ *   count_status CV_32SC1, at least 1 x 2: the number of keypoints, the status bits.  Rows from count on are not written.
+ * cap is the caller's: the smallest row count of keypoints, meta and descriptors, at least 1 (ISX_ERR_SIZE).  count =
+ * min(total, nfeatures if nfeatures > 0, cap); ISX_SIFT_TRUNCATED when cap cut it.  Every output is 4-byte aligned in pointer and step.
+ * Checked before anything is written or enqueued: null pointers, a parameter out of range or NaN, a misaligned mat -> ISX_ERR_INVALID;
+ * another n_octave_layers or sigma, a side or a pixel count past its limit -> ISX_ERR_UNSUPPORTED; a mat of another type -> ISX_ERR_TYPE;
+ * an empty image, too few rows or columns -> ISX_ERR_SIZE.
+ * With device mats throughout nothing is read back or synchronised.  Host mats synchronise.  On a capturing stream the call works with
+ * device mats once isx_sift_reserve has sized the scratch; a host mat, or a call that would have to grow the scratch, -> ISX_ERR_STATE
+ * with nothing enqueued.  The launch count depends on the image size only: 10 + 11 n - (n > 0) for n built octaves.                     */
+int isx_sift_find(const isx_mat* image, const isx_sift_params* params, isx_mat* keypoints, isx_mat* meta, isx_mat* descriptors,
+                  isx_mat* count_status, int device, void* hip_stream);
+/* Sizes the calling thread's scratch for device images of up to width x height under `params` and device outputs of `cap` rows, ahead of
+ * a stream capture.  A captured graph keeps pointing at this scratch: growing or releasing it while such a graph exists is the caller's
+ * error.                                                                                                                                  */
+int isx_sift_reserve(const isx_sift_params* params, int width, int height, int cap, int device);
+/* Returns the scratch of the calling thread.  PER THREAD and not freed at thread exit, as for isx_orb_release.                           */
+int isx_sift_release(void);
+
 /* ---- the features matcher of the M demo (M = the reference's 特征点匹配/特征点匹配/特征点匹配.cpp) --------------------------------- */
 /* The tiling of the search kernel (match.hip takes them from here; imagestitch_amd/matcher.py repeats them): queries per block, train rows
  * per LDS tile, train rows per work item, and the row limits - the width of the packed key distance << 22 | row.                          */
@@ -1176,6 +1233,11 @@ int isx_selftest_bundle_math_device(int fn, int n, const double* in, double* out
 int isx_selftest_proj_math(int fn, int n, const float* in, const float* in2, float* out);
 /* The device compilation of the same header on the same items (host pointers; one thread per item).  Uses the null stream and synchronises it. */
 int isx_selftest_proj_math_device(int fn, int n, const float* in, const float* in2, float* out);
+/* The host compilation of csrc/sift_math.hpp, the two float32 exponentials of the SIFT finder, on n items: fn 0 expf, 1 exp2f.  Needs no
+ * device: the CPU test-suite compares it with tests/helpers/sift_np.py bit for bit.                                                    */
+int isx_selftest_sift_math(int fn, int n, const float* in, float* out);
+/* The device compilation of the same header on the same items (host pointers; one thread per item).  Uses the null stream and synchronises it. */
+int isx_selftest_sift_math_device(int fn, int n, const float* in, float* out);
 /* Every entry of this header is a function-try-block: a C++ exception raised underneath it (std::bad_alloc of a host container, a
  * std::length_error, anything a future change throws) is stopped there and comes back as a status - ISX_ERR_NOMEM for the two allocation
  * failures, ISX_ERR_INTERNAL otherwise, the text in isx_last_error() - never as an exception in the caller's frames (the
